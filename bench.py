@@ -2,6 +2,7 @@
 """bench.py -- BASELINE.json's metric on MI355X: NLP solves/s (N=12, 6-state bicycle).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg2_filtered|cfg3|cfg4|cfg5|lmpc|races|game|overtake] [--scaling weak|strong]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already resident in HBM.
 
@@ -10,7 +11,9 @@ reference), 1 obstacle, batch 256 per GPU, N = 12, drawn exactly as SURVEY.md se
 since round 2: crash states are part of the batch and end in the restoration verdict).  The batch shards by problem, no
 data-path collective: weak scaling, `value` = problems of all ranks / max-over-ranks time.
 
-Without --workload the same run also measures the other single-GPU BASELINE configs and reports them in `configs`
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the status read-back and unscaled-KKT check that
+`value` counts by, --dump-outputs, and the line.  --full adds everything else: latency, kernel-train timing, the collective alone, the
+CPU baseline, the full-record file, and -- without --workload -- the other single-GPU BASELINE configs, reported in `configs`
 (each with its own roofline object): cfg3 (1024 planner scenarios x 4 region QPs + selection), cfg4 (16384 tracking NLPs,
 N = 20, 3 obstacles), lmpc (learning-MPC QPs) and cfg5 -- configs[4], the Monte-Carlo sweep
 of overtake-planner scenarios sharded by scenario over the ranks, raw scenario -> Bezier/bounds prep -> region QPs ->
@@ -126,6 +129,49 @@ class Workload:
 
     def solve(self):
         raise NotImplementedError
+
+    def outputs(self):
+        """what a caller of step() receives: the solver workspace's output tensors (--dump-outputs)"""
+        return ws_tensors(self.ws)
+
+
+def ws_tensors(ws, prefix=""):
+    """The output tensors of a solver workspace: every tensor attribute, and status / iters / kkt where they are properties
+    (concurrent sub-batches)."""
+    out = {prefix + k: v for k, v in sorted(vars(ws).items()) if torch.is_tensor(v)}
+    for k in ("status", "iters", "kkt"):
+        v = getattr(ws, k, None)
+        if prefix + k not in out and torch.is_tensor(v):
+            out[prefix + k] = v
+    return out
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def host_outputs(w):
+    """w.outputs() copied to the host as float64 (float32 stays float32): called right after the timed steps, so the arrays are those
+    of the last timed step."""
+    out = {}
+    for k, v in w.outputs().items():
+        a = v.detach().cpu().numpy()
+        out[k] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    return out
+
+
+def write_outputs(outs, d):
+    """DIR/<name>.npy per output.  Above DUMP_LIMIT_BYTES in all, every array keeps a fixed, seeded sample of its rows (first axis), and
+    the row indices kept go to DIR/<name>.rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.nbytes for a in outs.values())
+    with_rows = total + sum(8 * a.shape[0] for a in outs.values() if a.ndim)      # a sampled array also stores its row indices
+    keep = 0.9 * DUMP_LIMIT_BYTES / with_rows if total > DUMP_LIMIT_BYTES else 1.0
+    for k, a in sorted(outs.items()):
+        if keep < 1.0 and a.ndim and a.shape[0] > 1:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * keep)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(d, k + ".rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 class CatWs:
@@ -262,6 +308,7 @@ def make_planner(cx, args, n_scen=None):
         torch_api.select_dev(sdesc, t_sel[0], w.ws.X.view(n_scen, V + 1, N + 1, 6), t_sel[1], t_sel[2], t_sel[3], ws=sws)
 
     w.step = step
+    w.outputs = lambda: {**ws_tensors(w.ws), **ws_tensors(sws, "select_")}
     w.name = "overtake planner: %d scenarios x %d region QPs (overtake_traj_planner.py:248-379) + selection (:205-246), N=12, per GPU" % (n_scen, V + 1)
     keys = ("x0", "bez_s", "bez_ey", "ey_lb", "ey_ub")
     w.cpu = ("planner", w.desc, {k: p[k] for k in keys})
@@ -293,6 +340,7 @@ def make_sweep(cx, args, scaling):
     w.batch = w.units = sw.n_local * (sw.V + 1)
     w.kernel = "crx_solve_kernel<0>"
     w.step, w.gather = sw.step, sw.gather
+    w.outputs = lambda: {"flag": sw.flag_all, "best_X": sw.best_all, "status": sw.status_all}     # what step() returns: the gathered winners
     w.solve = lambda: sw.be.planner_solve_dev(sw.desc, sw.pws.x0, sw.pws.bez_s, sw.pws.bez_ey, sw.pws.ey_lb, sw.pws.ey_ub, ws=sw.ws)
     w.name = ("Monte-Carlo overtake-planner sweep, %s scaling: %d scenarios in total, %d on this rank x %d region QPs; raw scenario -> "
               "Bezier/bounds prep -> QPs -> selection on the device, then ONE all-gather of the winners over %d rank(s)" % (
@@ -518,8 +566,10 @@ def occupancy(w):
     return int(L.crx_debug_lds_bytes(lk, int(w.N), int(w.n_obs))), int(L.crx_debug_resident_per_cu(lk, int(w.N), int(w.n_obs)))
 
 
-def measure(cx, w, steps, warmup, with_latency=True):
-    """W untimed steps, then exactly `steps` timed steps bracketed by barrier + synchronize, MAX over ranks."""
+def measure(cx, w, steps, warmup, with_latency=True, full=True, dump=False):
+    """W untimed steps, then exactly `steps` timed steps bracketed by barrier + synchronize, MAX over ranks.  full=False (a plain bench run):
+    only what `value` needs -- no latency, collective or kernel-train runs of their own; the roofline takes the kernel time from the HIP events
+    around the timed steps where a step is one launch, else it has none.  dump: w.outputs() of the last timed step -> rec["outputs"]."""
     for _ in range(warmup):
         w.step()
     if w.rewind is not None:     # closed loops: the timed steps start at the stated lap phase whatever --warmup was
@@ -557,6 +607,7 @@ def measure(cx, w, steps, warmup, with_latency=True):
             region_tm.end()
         cx.sync_all()
         elapsed = time.perf_counter() - t0
+    outputs = host_outputs(w) if dump else None
     region_ms = region_tm.ms() / steps if region_tm is not None else None
     if cx.world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=cx.dev)
@@ -569,7 +620,7 @@ def measure(cx, w, steps, warmup, with_latency=True):
         units_all = int(t.item())
     launched_rate = units_all * steps / elapsed
     allgather_ms = None
-    if w.gather is not None:                           # the collective alone, same barrier / synchronize bracket
+    if full and w.gather is not None:                  # the collective alone, same barrier / synchronize bracket
         reps = min(50, max(5, steps))
         w.gather()
         cx.sync_all()
@@ -579,6 +630,7 @@ def measure(cx, w, steps, warmup, with_latency=True):
         cx.sync_all()
         allgather_ms = (time.perf_counter() - t1) / reps * 1e3
     lat, hlat = [], []
+    with_latency = with_latency and full
     if with_latency:
         # latency of one synchronous step (what a 10 Hz controller sees): p50 over blocking calls
         for _ in range(min(100, max(10, steps))):
@@ -607,7 +659,9 @@ def measure(cx, w, steps, warmup, with_latency=True):
         w.step()
         cx.dsync()
     st, it, kkt = w.ws.status.cpu().numpy(), w.ws.iters.cpu().numpy(), w.ws.kkt.cpu().numpy()
-    k_ms, k_ms_single = kernel_ms_samples(cx, w, min(50, max(5, steps)))
+    k_ms = k_ms_single = None
+    if full:
+        k_ms, k_ms_single = kernel_ms_samples(cx, w, min(50, max(5, steps)))
     k_ms_train = k_ms
     if region_ms is not None:
         k_ms = region_ms
@@ -649,7 +703,7 @@ def measure(cx, w, steps, warmup, with_latency=True):
     abytes = algorithmic_bytes(w.kind, N, n_obs)
     launched = int(ran.sum())                          # masked launches: the problems whose wavefront did not return at once
     conv_of_launched = float(conv[ran].mean()) if ran.any() else 0.0
-    achieved = abytes * launched / (k_ms * 1e-3) / 1e9
+    achieved = abytes * launched / (k_ms * 1e-3) / 1e9 if k_ms is not None else None
     # analytic FP64 work: Riccati factor + solves per interior-point iteration
     nx, nu = 6 + n_obs, 2 + n_obs
     nz = nx + nu
@@ -659,7 +713,7 @@ def measure(cx, w, steps, warmup, with_latency=True):
         nu2, M = 2 * N, n_obs
         flop_iter = nu2 ** 3 / 3 + 2 * 7 * nu2 * nu2 / 2 + (45 * 6 + 6 * 12 + 24 * 4) * M + 4 * (N - 1) * nu2 * nu2 / 2 \
             + 2 * nu2 * nu2 + 12 * (N - 1) * nu2
-    gflops = float(it.sum()) * flop_iter / (k_ms * 1e-3) / 1e9
+    gflops = float(it.sum()) * flop_iter / (k_ms * 1e-3) / 1e9 if k_ms is not None else None
     lds, resident = occupancy(w)
     traffic, tsrc = None, "none"     # none: no rocprofv3 --pmc summary under profiles/ for this workload and batch
     try:  # PMC-measured HBM bytes per launch of this workload at this batch (profiles/, rocprofv3 --pmc, calibrated)
@@ -701,16 +755,19 @@ def measure(cx, w, steps, warmup, with_latency=True):
     rec = {"key": w.key, "value": launched_rate * conv_of_launched, "value_launched": launched_rate, "unit": "solves/s", "steps": steps,
            "warmup": warmup, "ms_per_step": elapsed / steps * 1e3, "scaling": w.scaling, "config": cfg,
            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tsrc,
+                        "frac": achieved / HBM_PEAK_GBS if achieved is not None else None, "traffic": traffic, "traffic_source": tsrc,
                         "kernel": w.kernel, "kernel_ms": k_ms, "kernel_ms_single_launch": k_ms_single, "kernel_ms_train_after_the_run": k_ms_train,
                         "kernel_ms_is": ("HIP events around the timed steps themselves (one launch per step)" if region_ms is not None else
-                                         "HIP events around a train of re-issued launches after the timed steps"), "algorithmic_bytes_per_solve": abytes,
+                                         "HIP events around a train of re-issued launches after the timed steps" if k_ms is not None else
+                                         "not measured: the kernel-train runs are part of --full"), "algorithmic_bytes_per_solve": abytes,
                         "note": "serial-dependency/FP64-issue bound, not HBM bound (DESIGN.md section 5)",
-                        "fp64_gflops": gflops, "fp64_frac_of_valu_peak": gflops / FP64_VALU_PEAK_GFLOPS,
+                        "fp64_gflops": gflops, "fp64_frac_of_valu_peak": gflops / FP64_VALU_PEAK_GFLOPS if gflops is not None else None,
                         "lds_bytes_per_problem": lds, "resident_problems_per_cu": resident, "lds_limit_per_cu": int((160 * 1024) // max(lds, 1))}}
     if allgather_ms is not None:
         rec["allgather_ms"] = allgather_ms
         rec["world_size"] = dist.get_world_size() if dist.is_initialized() else 1
+    if outputs is not None:
+        rec["outputs"] = outputs
     return rec
 
 
@@ -935,6 +992,11 @@ def main():
                          "3 = the eager crash path (every violated zero start takes that point: faster, further from the reference's local minimum)")
     ap.add_argument("--collective", default="torch", choices=["torch", "crx"],
                     help="cfg5's all-gather: torch.distributed (nccl = RCCL) or libcrx's own crx_allgather_winners_dev (RCCL through the C ABI)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-step and host-call latency, kernel-train timing, the collective alone, the CPU baseline, "
+                         "the other configs (without --workload) and the full-record file.  Default: the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy (float64 / float32; rank 0's shard)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -954,7 +1016,8 @@ def main():
             "cfg5": lambda: make_sweep(cx, args, args.scaling), "lmpc": lambda: make_lmpc(cx, args, b), "races": lambda: make_races(cx, args, b),
             "game": lambda: make_game(cx, args, b), "overtake": lambda: make_overtake(cx, args, b)}
     head = headline_workload(cx, args, make)
-    rec = measure(cx, head, args.steps, args.warmup, with_latency=head.host_call is not None)
+    rec = measure(cx, head, args.steps, args.warmup, with_latency=head.host_call is not None, full=args.full, dump=args.dump_outputs is not None)
+    outputs = rec.pop("outputs", None)
     full = {"metric": METRIC, "value": rec["value"], "value_launched": rec["value_launched"], "unit": "solves/s", "n_gpus": cx.world,
             "steps": rec["steps"], "warmup": args.warmup, "ms_per_step": rec["ms_per_step"], "higher_is_better": True, "scaling": rec["scaling"],   # (rec["steps"] == --steps but for the closed loops: whole passes of their lap window)
             "vs_baseline": None, "dtype": "f64", "data": "synthetic", "config": rec["config"], "roofline": rec["roofline"], "headline": rec,
@@ -962,10 +1025,10 @@ def main():
     for k in ("allgather_ms", "world_size"):
         if k in rec:
             full[k] = rec[k]
-    if cx.rank == 0 and cx.world == 1 and not args.no_cpu_baseline and head.cpu is not None:   # N = 1 only: the other ranks would wait for it
+    if args.full and cx.rank == 0 and cx.world == 1 and not args.no_cpu_baseline and head.cpu is not None:   # N = 1 only: the other ranks would wait for it
         full["cpu_baseline"] = cpu_baseline(head)
     full["configs"] = []
-    for key, mk, st, wu, wl in sub_configs(cx, args):
+    for key, mk, st, wu, wl in (sub_configs(cx, args) if args.full else []):
         w = mk()
         full["configs"].append(measure(cx, w, st, wu, with_latency=wl))
         del w
@@ -985,7 +1048,9 @@ def main():
     if dist.is_initialized():
         dist.destroy_process_group()
     if cx.rank == 0:
-        full["full_record"] = write_full_record(full, args.full_out)
+        full["full_record"] = write_full_record(full, args.full_out) if args.full else None
+        if outputs is not None:
+            write_outputs(outputs, args.dump_outputs)
         # the JSON line must be the LAST line on stdout: RCCL prints its version banner through C stdio, which (on a pipe)
         # is flushed only at exit, i.e. after anything Python printed -- flush C stdio first, then print
         try:

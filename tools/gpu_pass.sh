@@ -9,7 +9,7 @@
 #   issue     SQ issue / wait / instruction counters of the solver kernels -> pmc_issue.txt (profiles/summarize_issue.py)
 #   trace     per-phase shader cycles of one solve, on tools/ab/libcrx_trace.so (built beforehand with -DCRX_PHASE_CLOCKS) -> phase_cycles.txt
 #   budget    tools/budget_experiment.sh (solver budgets vs closed-loop quality) -> budget_experiment.txt
-#   lines     one line per workload (bench.py --workload ...), for A/B-ing; CRX_LIB selects another build
+#   lines     one line per workload (bench.py --full --workload ...), for A/B-ing; CRX_LIB selects another build
 #   ab:NAME   the `lines` step with CRX_LIB=tools/ab/libcrx_NAME.so (tools/build_variant.sh NAME "FLAGS" beforehand, in the build container)
 #   suite:NAME the GPU parity suite on tools/ab/libcrx_NAME.so
 #   gen:NAME   the tests that run the GENERAL instantiations (descriptor fuzz, non-tuned horizons, 4..6 obstacles) on tools/ab/libcrx_NAME.so
@@ -23,29 +23,29 @@ cd $R
 make -C oracle -s
 line() { python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); c=d['config']; print('$1: %.4g /s converged (%.4g launched)  %.4f ms/step  kernel %.4f ms  status %s  iters p50 %s p90 %s max %s' % (d['value'], d['value_launched'], d['ms_per_step'], d['roofline']['kernel_ms'], c['status_frac'], c['iters_p50'], c['iters_p90'], c['iters_max']))"; }
 lines() {  # one line per workload
-  timeout 300 python bench.py --workload cfg2 --no-cpu-baseline --steps 200 --warmup 10 2> /dev/null | line "cfg2"
-  timeout 300 python bench.py --workload cfg2 --batch 4096 --no-cpu-baseline --steps 30 --warmup 5 2> /dev/null | line "cfg2x4096"
-  timeout 300 python bench.py --workload cfg3 --no-cpu-baseline --steps 100 --warmup 5 2> /dev/null | line "cfg3"
-  timeout 300 python bench.py --workload cfg4 --no-cpu-baseline --steps 10 --warmup 2 2> /dev/null | line "cfg4"
-  timeout 300 python bench.py --workload cfg5 --no-cpu-baseline --steps 10 --warmup 2 2> /dev/null | line "cfg5"
-  timeout 300 python bench.py --workload lmpc --no-cpu-baseline --steps 30 --warmup 3 2> /dev/null | line "lmpc"
-  timeout 300 python bench.py --workload races --no-cpu-baseline --steps 30 --warmup 5 2> /dev/null | line "races"
-  timeout 300 python bench.py --workload game --no-cpu-baseline --steps 60 --warmup 5 2> /dev/null | line "game"
-  timeout 300 python bench.py --workload overtake --no-cpu-baseline --steps 60 --warmup 5 2> /dev/null | line "overtake"
+  timeout 300 python bench.py --full --workload cfg2 --no-cpu-baseline --steps 200 --warmup 10 2> /dev/null | line "cfg2"
+  timeout 300 python bench.py --full --workload cfg2 --batch 4096 --no-cpu-baseline --steps 30 --warmup 5 2> /dev/null | line "cfg2x4096"
+  timeout 300 python bench.py --full --workload cfg3 --no-cpu-baseline --steps 100 --warmup 5 2> /dev/null | line "cfg3"
+  timeout 300 python bench.py --full --workload cfg4 --no-cpu-baseline --steps 10 --warmup 2 2> /dev/null | line "cfg4"
+  timeout 300 python bench.py --full --workload cfg5 --no-cpu-baseline --steps 10 --warmup 2 2> /dev/null | line "cfg5"
+  timeout 300 python bench.py --full --workload lmpc --no-cpu-baseline --steps 30 --warmup 3 2> /dev/null | line "lmpc"
+  timeout 300 python bench.py --full --workload races --no-cpu-baseline --steps 30 --warmup 5 2> /dev/null | line "races"
+  timeout 300 python bench.py --full --workload game --no-cpu-baseline --steps 60 --warmup 5 2> /dev/null | line "game"
+  timeout 300 python bench.py --full --workload overtake --no-cpu-baseline --steps 60 --warmup 5 2> /dev/null | line "overtake"
 }
 quick() {  # the four solver workloads only (A/B-ing kernel builds)
-  timeout 300 python bench.py --workload cfg2 --no-cpu-baseline --steps 200 --warmup 10 2> /dev/null | line "cfg2"
-  timeout 300 python bench.py --workload cfg2 --batch 4096 --no-cpu-baseline --steps 30 --warmup 5 2> /dev/null | line "cfg2x4096"
-  timeout 300 python bench.py --workload cfg3 --no-cpu-baseline --steps 100 --warmup 5 2> /dev/null | line "cfg3"
-  timeout 300 python bench.py --workload cfg4 --no-cpu-baseline --steps 10 --warmup 2 2> /dev/null | line "cfg4"
+  timeout 300 python bench.py --full --workload cfg2 --no-cpu-baseline --steps 200 --warmup 10 2> /dev/null | line "cfg2"
+  timeout 300 python bench.py --full --workload cfg2 --batch 4096 --no-cpu-baseline --steps 30 --warmup 5 2> /dev/null | line "cfg2x4096"
+  timeout 300 python bench.py --full --workload cfg3 --no-cpu-baseline --steps 100 --warmup 5 2> /dev/null | line "cfg3"
+  timeout 300 python bench.py --full --workload cfg4 --no-cpu-baseline --steps 10 --warmup 2 2> /dev/null | line "cfg4"
 }
 for step in "$@"; do
 case $step in
 game:*)   # the learning-MPC workloads on tools/ab/libcrx_NAME.so ("game:" alone = the in-tree library)
   n=${step#game:}; [ -n "$n" ] && export CRX_LIB=$R/tools/ab/libcrx_$n.so; echo "== lmpc workloads ${n:-in-tree}"
-  ( timeout 300 python bench.py --workload lmpc --no-cpu-baseline --steps 30 --warmup 3 2> /dev/null | line "lmpc"
-    timeout 300 python bench.py --workload game --no-cpu-baseline --steps 60 --warmup 5 2> /dev/null | line "game"
-    timeout 300 python bench.py --workload overtake --no-cpu-baseline --steps 60 --warmup 5 2> /dev/null | line "overtake" ) | tee $O/game_${n:-intree}.txt; unset CRX_LIB ;;
+  ( timeout 300 python bench.py --full --workload lmpc --no-cpu-baseline --steps 30 --warmup 3 2> /dev/null | line "lmpc"
+    timeout 300 python bench.py --full --workload game --no-cpu-baseline --steps 60 --warmup 5 2> /dev/null | line "game"
+    timeout 300 python bench.py --full --workload overtake --no-cpu-baseline --steps 60 --warmup 5 2> /dev/null | line "overtake" ) | tee $O/game_${n:-intree}.txt; unset CRX_LIB ;;
 bits:*)  # bit-for-bit A/B of the in-tree library against tools/ab/libcrx_NAME.so (tools/cbf_ab.py: solver draws + closed loops)
   n=${step#bits:}
   python tools/cbf_ab.py intree > /dev/null 2>&1; CRX_LIB=$R/tools/ab/libcrx_$n.so python tools/cbf_ab.py $n > /dev/null 2>&1
@@ -66,7 +66,7 @@ gen:*)   # the general-instantiation tests (descriptor fuzz, non-tuned horizons 
   ( CRX_LIB=$R/tools/ab/libcrx_$n.so timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -q -x -k "fuzz_descriptors or general_horizons or many_obstacles or no_stale_lds" 2>&1 | grep -v "^  File\|^Extension\|^$" | tail -30 ) > $O/pytest_gen_$n.log
   echo "$n: $(grep -h 'passed\|failed' $O/pytest_gen_$n.log | tail -1)" ;;
 bench)
-  python bench.py --full-out $O/bench_full.json > $O/bench.json 2> $O/bench.err
+  python bench.py --full --full-out $O/bench_full.json > $O/bench.json 2> $O/bench.err
   wc -c $O/bench.json; cat $O/bench.json ;;
 lines) lines | tee $O/lines.txt ;;
 ab:*)
@@ -77,7 +77,7 @@ stats)
   for wl in cfg2 cfg2_filtered cfg3 cfg4 lmpc cfg5 races game overtake; do
     st=50; [ $wl = cfg4 ] && st=5; [ $wl = lmpc ] && st=10; [ $wl = races ] && st=30; [ $wl = cfg5 ] && st=8; [ $wl = game ] && st=40; [ $wl = overtake ] && st=40
     rm -rf $P/$wl
-    rocprofv3 --kernel-trace --stats -d $P/$wl -o $wl -- python $R/bench.py --steps $st --warmup 3 --workload $wl --no-cpu-baseline --full-out $P/full_$wl.json > $P/bench_$wl.json 2> $P/err_$wl.log
+    rocprofv3 --kernel-trace --stats -d $P/$wl -o $wl -- python $R/bench.py --full --steps $st --warmup 3 --workload $wl --no-cpu-baseline --full-out $P/full_$wl.json > $P/bench_$wl.json 2> $P/err_$wl.log
     db=$(find $P/$wl -name "*.db" | head -1)
     python3 $R/profiles/summarize.py $db $P/bench_$wl.json > $O/${wl}_kernel_stats.txt 2>> $P/err_$wl.log
     find $P/$wl -type f ! -name "*.txt" -delete
@@ -91,7 +91,7 @@ pmc)
     st=10; [ $wl = cfg4 ] && st=3; [ $wl = cfg5 ] && st=3
     for ctr in FETCH_SIZE WRITE_SIZE; do
       rm -rf $M/${wl}_$ctr
-      rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $M/${wl}_$ctr -o p -- python $R/bench.py --steps $st --warmup 2 --workload $wl --no-cpu-baseline > /dev/null 2> $M/err_${wl}_$ctr.log
+      rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $M/${wl}_$ctr -o p -- python $R/bench.py --full --steps $st --warmup 2 --workload $wl --no-cpu-baseline > /dev/null 2> $M/err_${wl}_$ctr.log
     done
   done )
   find $M -type f ! -name "*counter_collection.csv" ! -name "*.txt" ! -name "*.log" -delete
@@ -101,7 +101,7 @@ issue)
   pmc() {  # tag workload batch steps extra-bench-args counters...
     tag=$1; wl=$2; b=$3; st=$4; ex=$5; shift 5
     rm -rf $O/pmc_$tag
-    rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/pmc_$tag -o p -- python $R/bench.py --steps $st --warmup 1 --workload $wl --batch $b $ex --no-cpu-baseline > /dev/null 2> $O/err_$tag.log
+    rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/pmc_$tag -o p -- python $R/bench.py --full --steps $st --warmup 1 --workload $wl --batch $b $ex --no-cpu-baseline > /dev/null 2> $O/err_$tag.log
     find $O/pmc_$tag -type f ! -name "*counter_collection.csv" -delete
   }
   A="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA"

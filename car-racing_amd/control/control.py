@@ -6,12 +6,15 @@ bodies marshal arrays into the crx C ABI instead of building a CasADi Opti probl
   mpc_lti           <- reference control/control.py:198-248   (same NLP family with no obstacle)
   lmpc              <- reference control/control.py:610-730   (QP on the GPU, crx_lmpc_solve)
   pid               <- reference control/control.py:15-25
+  lqr               <- reference control/control.py:28-61    (host numpy: a 6x6 Riccati fixed point, no hot path)
+  ilqr              <- reference control/control.py:64-195   (crx_ilqr_solve; derivatives of control/ilqr_helper.py:4-55)
 
 There is no CPU path: without libcrx / a GPU these raise crx.CrxUnavailable.
 """
 import datetime
 
 import numpy as np
+import scipy.linalg as la
 
 import crx
 from crx import abi, hostprep
@@ -134,14 +137,6 @@ def mpc_multi_agents(xcurv, mpc_lti_param, track, matrix_Atv, matrix_Btv, matrix
     return r["U"][0, 0, :], r["X"][0]
 
 
-def _out_of_scope(name):
-    def f(*a, **k):
-        raise NotImplementedError(
-            "%s is outside the accelerated hot path (SURVEY.md section 8f, 'next' rows); use the reference" % name)
-    f.__name__ = name
-    return f
-
-
 def lmpc(xcurv, lmpc_param, matrix_Atv, matrix_Btv, matrix_Ctv, ss_curv, Qfun, iter, lap_length, lap_width, u_old,
          system_param):
     """Learning MPC step (reference control/control.py:610-730): safe-set selection on the host
@@ -179,5 +174,53 @@ def lmpc(xcurv, lmpc_param, matrix_Atv, matrix_Btv, matrix_Ctv, ss_curv, Qfun, i
     return u_pred, x_pred, ss_sel, q_sel, lin_points, lin_input
 
 
-lqr = _out_of_scope("lqr")
-ilqr = _out_of_scope("ilqr")
+def _lqr_gain(A, B, Q, R, max_iter, tol=0.01):
+    """Fixed-point iteration of the discrete algebraic Riccati equation, P <- A'PA - A'PB (R + B'PB)^-1 B'PA + Q from P = Q,
+    stopped when no entry moves by tol or more (reference :45-52).  Quirk L1: the stopping iterate is discarded -- the gain comes
+    from the P in hand when the test passes, not from the one just computed (:53-54)."""
+    P = Q
+    for _ in range(max_iter):
+        PB = P @ B
+        nxt = A.T @ P @ A - A.T @ PB @ la.inv(R + B.T @ PB) @ B.T @ P @ A + Q
+        if np.abs(nxt - P).max() < tol:
+            break
+        P = nxt
+    return la.inv(B.T @ P @ B + R) @ B.T @ P @ A
+
+
+def lqr(xcurv, xtarget, lqr_param):
+    """Infinite-horizon LQR about the target (reference :28-61).  The gain does not depend on the state; the input is
+    -K (x - xtarget) with the reference's shapes: x is a column, so a (6, 1) target (LQRTracking's) gives the textbook law."""
+    start = datetime.datetime.now()
+    K = _lqr_gain(lqr_param.matrix_A, lqr_param.matrix_B, lqr_param.matrix_Q, lqr_param.matrix_R, lqr_param.max_iter)
+    u = -K @ (np.asarray(xcurv, dtype=float).reshape(X_DIM, 1) - xtarget)
+    print("solver time: {}".format((datetime.datetime.now() - start).total_seconds()))
+    return np.array([u[0, 0], u[1, 0]])
+
+
+def ilqr(xcurv, xtarget, ilqr_param, vehicles, agent_name, lap_length, time, timestep, track, system_param):
+    """iLQR step of the ego racer (reference :64-195) as one crx_ilqr_solve of batch 1; returns u_0 of the accepted plan.
+    Quirk I1: the obstacle is the LAST vehicle other than the agent in `vehicles` order, its size that of "car1".  With no other
+    vehicle the reference raises NameError; here the solve runs without a barrier term."""
+    start = datetime.datetime.now()
+    N = ilqr_param.num_horizon
+    x = np.asarray(xcurv, dtype=float).reshape(X_DIM)
+    others = [n for n in list(vehicles) if n != agent_name]
+    obs_s, obs_ey, lap_off = np.zeros((1, 1, N + 1)), np.zeros((1, 1, N + 1)), np.zeros((1, 1))
+    ego = vehicles[agent_name].param
+    l_sum, w_sum = 0.4, 0.2
+    if others:
+        traj, _ = vehicles[others[-1]].get_trajectory_nsteps(time, timestep, N + 1)
+        traj = np.asarray(traj, dtype=float)
+        obs_s[0, 0], obs_ey[0, 0] = traj[4, :], traj[5, :]
+        lap_off[0, 0] = (int(x[4] / lap_length) - int(traj[4, 0] / lap_length)) * lap_length
+        car1 = vehicles["car1"].param
+        l_sum, w_sum = ego.length / 2 + car1.length / 2, ego.width / 2 + car1.width / 2
+    desc = abi.ilqr_desc(N, ilqr_param.matrix_A, ilqr_param.matrix_B, Q=ilqr_param.matrix_Q, R=ilqr_param.matrix_R,
+                         max_iter=ilqr_param.max_iter, n_obs_max=1, l_sum=l_sum, w_sum=w_sum)
+    r = crx.ilqr_solve(desc, x[None], np.asarray(xtarget, dtype=float).reshape(1, X_DIM), obs_s, obs_ey, lap_off,
+                       np.array([1 if others else 0], dtype=np.int32))
+    if r["status"][0] == abi.CRX_CONVERGED:
+        print("Convergence achieved")
+    print("solver time: {}".format((datetime.datetime.now() - start).total_seconds()))
+    return r["U"][0, 0, :]

@@ -81,6 +81,10 @@ def lmpc_solve(desc, x0, u_old, A, B, Cm, ss, qfun, n_ss=None):
     return binding().lmpc_solve(desc, x0, u_old, A, B, Cm, ss, qfun, n_ss)
 
 
+def ilqr_solve(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs):
+    return binding().ilqr_solve(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs)
+
+
 def path_solve(desc, opt, bez, lb, ub, e0, eN):
     return binding().path_solve(desc, opt, bez, lb, ub, e0, eN)
 

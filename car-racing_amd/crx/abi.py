@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 
 CRX_MAX_N = 24
+CRX_ILQR_MAX_N = 64   # horizon limit of crx_ilqr_solve
 CRX_MAX_OBS = 6     # obstacles per MPC-CBF NLP
 CRX_MAX_VEH = 6     # vehicles of interest per planner scenario (= CRX_MAX_OBS)
 
@@ -113,6 +114,28 @@ class LmpcDesc(C.Structure):
         ("a_max", C.c_double),
         ("w_x0", C.c_double),
         ("opts", IpmOpts),
+    ]
+
+
+class IlqrDesc(C.Structure):
+    _fields_ = [
+        ("N", C.c_int32),
+        ("max_iter", C.c_int32),
+        ("n_obs_max", C.c_int32),
+        ("pad_", C.c_int32),
+        ("A", C.c_double * 36),
+        ("B", C.c_double * 12),
+        ("Q", C.c_double * 36),
+        ("R", C.c_double * 4),
+        ("eps", C.c_double),
+        ("lamb_init", C.c_double),
+        ("lamb_factor", C.c_double),
+        ("lamb_max", C.c_double),
+        ("margin", C.c_double),
+        ("q1", C.c_double),
+        ("q2", C.c_double),
+        ("l_sum", C.c_double),
+        ("w_sum", C.c_double),
     ]
 
 
@@ -222,6 +245,18 @@ def lmpc_desc(N=12, n_ss_max=44, Q=(0.0,) * 6, R=(1.0, 0.25), dR=(4.0, 0.0), x_t
                     _arr(C.c_double, 6, x_track), v_max, ey_max, delta_max, a_max, w_x0, opts or default_opts())
 
 
+def ilqr_desc(N, A, B, Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]), R=np.diag([0.1, 0.1]), max_iter=150, n_obs_max=1,
+              eps=0.01, lamb_init=1.0, lamb_factor=10.0, lamb_max=1000.0, margin=0.15, q1=2.5, q2=2.5, l_sum=0.4, w_sum=0.2):
+    """Defaults = iLQRRacingParam / CarParam (utils/base.py) and the literals of control.ilqr (control.py:80-83) and
+    ilqr_helper.get_cost_derivation (ilqr_helper.py:25-27).  Q, R are full matrices (a 1-D argument is a diagonal)."""
+    Q, R = np.asarray(Q, dtype=float), np.asarray(R, dtype=float)
+    Q = np.diag(Q) if Q.ndim == 1 else Q
+    R = np.diag(R) if R.ndim == 1 else R
+    return IlqrDesc(int(N), int(max_iter), int(n_obs_max), 0, _arr(C.c_double, 36, A), _arr(C.c_double, 12, B),
+                    _arr(C.c_double, 36, Q), _arr(C.c_double, 4, R), eps, lamb_init, lamb_factor, lamb_max, margin, q1, q2,
+                    l_sum, w_sum)
+
+
 def prep_desc(N, n_veh_max, n_opt, track_width, lap_length, prediction_factor=0.5, veh_length=0.4, veh_width=0.2):
     """planner_helper.py:51-53 and overtake_traj_planner.py:288,296 literals."""
     return PrepDesc(int(N), int(n_veh_max), int(n_opt), 0, prediction_factor, 4.0, track_width, lap_length,
@@ -267,7 +302,7 @@ class Binding:
 
     def __init__(self, lib, prefix):
         self.lib, self.prefix = lib, prefix
-        for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve"):
+        for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve", "ilqr_solve"):
             if hasattr(lib, prefix + name):
                 getattr(lib, prefix + name).restype = C.c_int
         self._check = None
@@ -300,6 +335,24 @@ class Binding:
             _p(ey_ub), _p(out["X"]), _p(out["U"]), _p(out["cost"]), _p(out["status"]),
             _p(out["kkt"]), _p(out["iters"]),
         )
+        return out
+
+    def ilqr_solve(self, desc, x0, xt, obs_s, obs_ey, lap_off, n_obs):
+        """crx_ilqr_solve.  x0, xt (Bn,6); obs_s, obs_ey (Bn,V,N+1); lap_off (Bn,V); n_obs (Bn,) with V = desc.n_obs_max.
+        Returns X (Bn,N+1,6), U (Bn,N,2), cost, status, iters."""
+        N, V = desc.N, desc.n_obs_max
+        x0 = np.ascontiguousarray(x0, dtype=_D)
+        Bn = x0.shape[0]
+        x0 = _in(x0, _D, (Bn, 6))
+        xt = _in(xt, _D, (Bn, 6))
+        obs_s = _in(obs_s, _D, (Bn, V, N + 1))
+        obs_ey = _in(obs_ey, _D, (Bn, V, N + 1))
+        lap_off = _in(lap_off, _D, (Bn, V))
+        n_obs = _in(n_obs, _I, (Bn,))
+        out = dict(X=np.zeros((Bn, N + 1, 6)), U=np.zeros((Bn, N, 2)), cost=np.zeros(Bn), status=np.zeros(Bn, dtype=_I),
+                   iters=np.zeros(Bn, dtype=_I))
+        self._call("ilqr_solve", C.byref(desc), C.c_int(Bn), _p(x0), _p(xt), _p(obs_s), _p(obs_ey), _p(lap_off), _p(n_obs),
+                   _p(out["X"]), _p(out["U"]), _p(out["cost"]), _p(out["status"]), _p(out["iters"]))
         return out
 
     def cbf_solve(self, desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, obs_dims=None):

@@ -250,6 +250,74 @@ def mpccbf_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, car
                 status=torch.stack(log_st).cpu().numpy(), laps=r.laps.cpu().numpy())
 
 
+class IlqrRaces:
+    """B copies of the reference's iLQR racing scenario (car_racing/tests/ilqr_test.py: ego under iLQRRacing, one scripted car
+    s(t) = v t + s0, ey(t) = ey), device-resident.  Per control step, without touching the host: the scripted car's N+1
+    predictions from its own clock (utils/base.py:879-886; control.ilqr applies no distance window, quirk I1), the lap offset
+    (int(s_ego / L) - int(s_obs,0 / L)) L (quirk I5), ONE crx_ilqr_solve_dev over all races, ONE crx_plant_step_wrap_dev."""
+
+    def __init__(self, track_table, lap_length, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, vt=0.8, eyt=0.0, N=50,
+                 max_iter=150, timestep=0.1, ego_dims=(0.4, 0.2), car_dims=(0.4, 0.2), device=None, noise_seed=None):
+        dev = torch.device(device if device is not None else "cuda")
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.noise = _Noise(noise_seed, dev)
+        self.xc = torch.as_tensor(np.ascontiguousarray(xcurv0), **f64).clone()
+        self.xg = torch.as_tensor(np.ascontiguousarray(xglob0), **f64).clone()
+        self.s0, self.v, self.ey = (torch.as_tensor(np.ascontiguousarray(a, dtype=float).reshape(-1, 1), **f64)
+                                    for a in (car_s0, car_v, car_ey))
+        Bn = self.xc.shape[0]
+        self.N, self.batch, self.lap_length, self.timestep = N, Bn, lap_length, timestep
+        self.tab = torch.as_tensor(np.ascontiguousarray(track_table), **f64)
+        self.desc = abi.ilqr_desc(N, A, B, max_iter=max_iter, n_obs_max=1, l_sum=ego_dims[0] / 2 + car_dims[0] / 2,
+                                  w_sum=ego_dims[1] / 2 + car_dims[1] / 2)
+        self.pdesc = abi.plant_desc(self.tab.shape[0], lap_length, timestep=timestep)
+        self.xt = torch.tensor([vt, 0, 0, 0, 0, eyt], **f64).repeat(Bn, 1).contiguous()
+        self.ws = torch_api.IlqrWorkspace(self.desc, Bn, dev)
+        self.jdt = torch.arange(N + 1, **f64) * timestep
+        self.laps = torch.zeros(Bn, dtype=torch.int32, device=dev)
+        self.n_obs = torch.ones(Bn, dtype=torch.int32, device=dev)
+        self.xg_next, self.xc_next = torch.empty_like(self.xg), torch.empty_like(self.xc)
+        self.t = 0.0   # the scripted car's clock, advanced by `+= timestep` like the reference's (base.py:889)
+        self.u = None
+
+    def predictions(self):
+        """(obs_s, obs_ey [B,1,N+1], lap_off [B,1]) of the current step."""
+        L = self.lap_length
+        tt = self.t + self.jdt                                                  # time + index * delta_t
+        obs_s = (self.v * tt[None, :] + self.s0)[:, None, :].contiguous()
+        obs_e = (self.ey + 0.0 * tt[None, :])[:, None, :].contiguous()
+        lap_off = ((_LAP_TRUNC(self.xc[:, 4:5] / L) - _LAP_TRUNC(obs_s[:, :, 0] / L)) * L).contiguous()
+        return obs_s, obs_e, lap_off
+
+    def step(self):
+        obs_s, obs_e, lap_off = self.predictions()
+        torch_api.ilqr_solve_dev(self.desc, self.xc, self.xt, obs_s, obs_e, lap_off, self.n_obs, ws=self.ws)
+        torch_api.plant_step_wrap_dev(self.pdesc, self.tab, self.xg, self.xc, self.ws.U, 2 * self.N, self.xg_next, self.xc_next,
+                                      self.laps, noise_z=self.noise.draw(self.batch))
+        self.xg, self.xg_next = self.xg_next, self.xg
+        self.xc, self.xc_next = self.xc_next, self.xc
+        self.u = self.ws.U[:, 0, :]
+        self.t += self.timestep
+
+
+def ilqr_races(track_table, lap_length, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, steps, vt=0.8, eyt=0.0, N=50, max_iter=150,
+               timestep=0.1, device=None, log_every=1):
+    """xcurv0, xglob0 [B,6]; car_s0, car_v, car_ey [B]: one scripted car per race.  Returns host arrays: xcurv [T+1,B,6]
+    (T = steps / log_every), u [T,B,2], status [T,B], iters [T,B], laps [B]."""
+    r = IlqrRaces(track_table, lap_length, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, vt=vt, eyt=eyt, N=N, max_iter=max_iter,
+                  timestep=timestep, device=device)
+    log_x, log_u, log_st, log_it = [r.xc.clone()], [], [], []
+    for k in range(steps):
+        r.step()
+        if (k + 1) % log_every == 0:
+            log_x.append(r.xc.clone())
+            log_u.append(r.u.clone())
+            log_st.append(r.ws.status.clone())
+            log_it.append(r.ws.iters.clone())
+    return dict(xcurv=torch.stack(log_x).cpu().numpy(), u=torch.stack(log_u).cpu().numpy(),
+                status=torch.stack(log_st).cpu().numpy(), iters=torch.stack(log_it).cpu().numpy(), laps=r.laps.cpu().numpy())
+
+
 class LmpcLaps:
     """B learning-MPC laps at once, device-resident (SURVEY.md section 8f rows 1 + 4): the lap of the reference's racing
     game in which LMPCRacingGame drives alone (tests/auto_racing_game_test.py:60-66 -> utils/base.py:468-517), with the

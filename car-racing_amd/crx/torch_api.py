@@ -154,6 +154,39 @@ def cbf_solve_dev(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, ws=None, active=N
     return ws
 
 
+class IlqrWorkspace:
+    """Pre-allocated outputs for repeated ilqr_solve_dev calls of one shape."""
+
+    def __init__(self, desc, batch, device):
+        N = desc.N
+        f64 = dict(dtype=torch.float64, device=device)
+        i32 = dict(dtype=torch.int32, device=device)
+        self.X = torch.zeros((batch, N + 1, 6), **f64)
+        self.U = torch.zeros((batch, N, 2), **f64)
+        self.cost = torch.zeros(batch, **f64)
+        self.status = torch.zeros(batch, **i32)
+        self.iters = torch.zeros(batch, **i32)
+
+
+def ilqr_solve_dev(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, ws=None, active=None):
+    """crx_ilqr_solve_dev: x0, xt [B,6]; obs_s, obs_ey [B,n_obs_max,N+1]; lap_off [B,n_obs_max]; n_obs int32 [B]; `active`
+    (int32 [B], 0 = leave the problem alone: status CRX_SKIPPED, outputs untouched) optional."""
+    N, V, B = desc.N, desc.n_obs_max, x0.shape[0]
+    _chk(x0, torch.float64, (B, 6), "x0")
+    _chk(xt, torch.float64, (B, 6), "xt")
+    _chk(obs_s, torch.float64, (B, V, N + 1), "obs_s")
+    _chk(obs_ey, torch.float64, (B, V, N + 1), "obs_ey")
+    _chk(lap_off, torch.float64, (B, V), "lap_off")
+    _chk(n_obs, torch.int32, (B,), "n_obs")
+    if active is not None:
+        _chk(active, torch.int32, (B,), "active")
+    ws = ws or IlqrWorkspace(desc, B, x0.device)
+    _call("crx_ilqr_solve_dev", C.byref(desc), C.c_int(B), _ptr(active) if active is not None else None, _ptr(x0), _ptr(xt),
+          _ptr(obs_s), _ptr(obs_ey), _ptr(lap_off), _ptr(n_obs), _ptr(ws.X), _ptr(ws.U), _ptr(ws.cost), _ptr(ws.status),
+          _ptr(ws.iters), _stream())
+    return ws
+
+
 class PlannerWorkspace:
     def __init__(self, desc, batch, device):
         N = desc.N

@@ -948,6 +948,84 @@ int crx_lmpc_solve(const crx_lmpc_desc* d, int batch, const double* x0, const do
     return sg.down(g_stream);
 }
 
+// ---- iLQR (control/control.py:64-195) -----------------------------------------------------------------
+void crx_ilqr_desc_default(crx_ilqr_desc* d, int N, const double* A, const double* B) {
+    memset(d, 0, sizeof(*d));
+    d->N = N; d->max_iter = 150; d->n_obs_max = 1;
+    if (A) memcpy(d->A, A, sizeof(d->A));
+    if (B) memcpy(d->B, B, sizeof(d->B));
+    d->Q[0] = 10.0; d->Q[3 * 7] = 4.0; d->Q[5 * 7] = 40.0;
+    d->R[0] = 0.1; d->R[3] = 0.1;
+    d->eps = 0.01; d->lamb_init = 1.0; d->lamb_factor = 10.0; d->lamb_max = 1000.0;
+    d->margin = 0.15; d->q1 = 2.5; d->q2 = 2.5; d->l_sum = 0.4; d->w_sum = 0.2;
+}
+
+// argument checks come before the device check: a malformed call is reported as such with or without a GPU
+static int fill_ilqr(crx_ilqr_kparams& kp, const crx_ilqr_desc* d, int batch) {
+    if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
+    if (d->N < 1 || d->N > CRX_ILQR_MAX_N) return fail(CRX_ERR_ARG, "N=%d outside [1,%d]", d->N, CRX_ILQR_MAX_N);
+    if (d->n_obs_max < 0 || d->n_obs_max > CRX_MAX_OBS) return fail(CRX_ERR_ARG, "n_obs_max=%d outside [0,%d]", d->n_obs_max, CRX_MAX_OBS);
+    if (d->max_iter < 0) return fail(CRX_ERR_ARG, "max_iter < 0");
+    if (batch < 0) return fail(CRX_ERR_ARG, "batch < 0");
+    if (!(d->lamb_init > 0.0) || !(d->lamb_factor > 0.0) || !(d->eps >= 0.0)) return fail(CRX_ERR_ARG, "lamb_init, lamb_factor must be positive, eps non-negative");
+    if (d->n_obs_max > 0 && !(d->l_sum > 0.0 && d->w_sum > 0.0)) return fail(CRX_ERR_ARG, "l_sum, w_sum must be positive");
+    memset(&kp, 0, sizeof(kp));
+    kp.N = d->N; kp.batch = batch; kp.n_obs_max = d->n_obs_max; kp.max_iter = d->max_iter;
+    memcpy(kp.A, d->A, sizeof(kp.A)); memcpy(kp.B, d->B, sizeof(kp.B)); memcpy(kp.Q, d->Q, sizeof(kp.Q)); memcpy(kp.R, d->R, sizeof(kp.R));
+    kp.eps = d->eps; kp.lamb_init = d->lamb_init; kp.lamb_factor = d->lamb_factor; kp.lamb_max = d->lamb_max;
+    kp.margin = d->margin; kp.q1 = d->q1; kp.q2 = d->q2; kp.l_sum = d->l_sum; kp.w_sum = d->w_sum;
+    return 0;
+}
+
+static bool ilqr_null(const crx_ilqr_desc* d, const double* x0, const double* xt, const double* obs_s, const double* obs_ey,
+                      const double* lap_off, const int32_t* n_obs, const double* X, const double* U, const double* cost,
+                      const int32_t* status, const int32_t* iters) {
+    const bool obs = d->n_obs_max > 0;
+    return !x0 || !xt || !n_obs || !X || !U || !cost || !status || !iters || (obs && (!obs_s || !obs_ey || !lap_off));
+}
+
+int crx_ilqr_solve_dev(const crx_ilqr_desc* d, int batch, const int32_t* active, const double* x0, const double* xt,
+                       const double* obs_s, const double* obs_ey, const double* lap_off, const int32_t* n_obs, double* X, double* U,
+                       double* cost, int32_t* status, int32_t* iters, void* stream) {
+    crx_ilqr_kparams kp;
+    if (int rc = fill_ilqr(kp, d, batch)) return rc;
+    if (batch > 0 && ilqr_null(d, x0, xt, obs_s, obs_ey, lap_off, n_obs, X, U, cost, status, iters))
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    if (int rc = ensure_init()) return rc;
+    if (batch == 0) return CRX_OK;
+    kp.x0 = x0; kp.xt = xt; kp.obs_s = obs_s; kp.obs_ey = obs_ey; kp.lap_off = lap_off; kp.n_obs = n_obs; kp.active = active;
+    kp.X = X; kp.U = U; kp.cost = cost; kp.status = status; kp.iters = iters;
+    hipError_t e = crx_launch_ilqr(kp, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(CRX_ERR_HIP, "ilqr launch: %s", hipGetErrorString(e));
+    return CRX_OK;
+}
+
+int crx_ilqr_solve(const crx_ilqr_desc* d, int batch, const double* x0, const double* xt, const double* obs_s, const double* obs_ey,
+                   const double* lap_off, const int32_t* n_obs, double* X, double* U, double* cost, int32_t* status, int32_t* iters) {
+    crx_ilqr_kparams chk;
+    if (int rc = fill_ilqr(chk, d, batch)) return rc;
+    if (batch > 0 && ilqr_null(d, x0, xt, obs_s, obs_ey, lap_off, n_obs, X, U, cost, status, iters))
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    for (int b = 0; b < batch; b++)
+        if (n_obs[b] < 0 || n_obs[b] > d->n_obs_max) return fail(CRX_ERR_ARG, "n_obs[%d]=%d outside [0,%d]", b, n_obs[b], d->n_obs_max);
+    if (int rc = ensure_init()) return rc;
+    if (batch == 0) return CRX_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    const size_t Bn = (size_t)batch, N = (size_t)d->N, V = (size_t)d->n_obs_max;
+    const size_t n_obs_pts = Bn * V * (N + 1), n_X = Bn * (N + 1) * 6, n_U = Bn * N * 2;
+    Stage sg;
+    if (int rc = sg.reserve((Bn * 12 + 2 * n_obs_pts + Bn * V) * 8 + Bn * 4, (n_X + n_U + Bn) * 8 + 2 * Bn * 4)) return rc;
+    double* dx0 = sg.in(x0, Bn * 6); double* dxt = sg.in(xt, Bn * 6);
+    double* dos = sg.in(obs_s, n_obs_pts); double* doe = sg.in(obs_ey, n_obs_pts); double* dlo = sg.in(lap_off, Bn * V);
+    int32_t* dn = sg.in(n_obs, Bn);
+    double* dX = sg.out(X, n_X); double* dU = sg.out(U, n_U); double* dc = sg.out(cost, Bn);
+    int32_t* ds = sg.out(status, Bn); int32_t* di = sg.out(iters, Bn);
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_ilqr_solve_dev(d, batch, nullptr, dx0, dxt, dos, doe, dlo, dn, dX, dU, dc, ds, di, g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
 // ---- planner front (interest test, partial sort, vehicle infos) on the device ------------------------
 void crx_scene_desc_default(crx_scene_desc* d, int N, int n_all_max, int n_veh_max, double lap_length) {
     memset(d, 0, sizeof(*d));

@@ -195,5 +195,18 @@ hipError_t crx_launch_lmpc_addpoint(const crx_lmpcprep_desc& d, int batch, doubl
                                     hipStream_t st);
 size_t crx_lmpc_lds_bytes(int N, int n_ss_max);
 int crx_lmpc_resident_per_cu(int N, int n_ss_max);
+// iLQR (crx_ilqr.hip)
+struct crx_ilqr_kparams {
+    int N, batch, n_obs_max, max_iter;
+    double A[36], B[12], Q[36], R[4];
+    double eps, lamb_init, lamb_factor, lamb_max, margin, q1, q2, l_sum, w_sum;
+    const double *x0, *xt, *obs_s, *obs_ey, *lap_off;
+    const int32_t *n_obs, *active;
+    double *X, *U, *cost;
+    int32_t *status, *iters;
+};
+hipError_t crx_launch_ilqr(const crx_ilqr_kparams& kp, hipStream_t st);
+size_t crx_ilqr_lds_bytes(int N);
+int crx_ilqr_resident_per_cu(int N);
 #endif
 #endif

@@ -16,6 +16,14 @@ class MPCTracking(base.MPCTracking):
     pass
 
 
+class LQRTracking(base.LQRTracking):
+    pass
+
+
+class iLQRRacing(base.iLQRRacing):
+    pass
+
+
 class MPCCBFRacing(base.MPCCBFRacing):
     def __init__(self, mpc_cbf_param, system_param):
         base.MPCCBFRacing.__init__(self, mpc_cbf_param, system_param)

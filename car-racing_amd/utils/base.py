@@ -1,6 +1,8 @@
 """Controller / vehicle / simulator classes with the reference's surface (utils/base.py), so that
-the reference's drivers (tests/auto_mpccbf_test.py, car_racing/tests/mpccbf_test.py) run against
-this package unchanged.  LQR and iLQR are out of scope and raise.
+the reference's drivers (tests/auto_mpccbf_test.py, car_racing/tests/mpccbf_test.py, ilqr_test.py,
+control_test.py) run against this package unchanged.  Every controller of the reference has its class here:
+PIDTracking and LQRTracking compute on the host (a P law and a fixed Riccati gain), MPCTracking,
+MPCCBFRacing, iLQRRacing and LMPCRacingGame solve on the GPU through libcrx.
 
 Objects stay picklable: the GPU library handle lives in the `crx` module, never in instance state
 (the reference pickles its simulator, tests/auto_mpccbf_test.py:42-43).
@@ -146,6 +148,49 @@ class MPCCBFRacing(ControlBase):
         if vehicles is not None:
             self.u = control.mpccbf(self.x, xtarget, self.mpc_cbf_param, vehicles, self.agent_name, lap_length,
                                     self.time, self.timestep, self.realtime_flag, self.track, self.system_param)
+        self._ego_log_none()
+        self.time += self.timestep
+
+
+class LQRTrackingParam:
+    def __init__(self, matrix_A=_A_DEFAULT, matrix_B=_B_DEFAULT, matrix_Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]),
+                 matrix_R=np.diag([0.1, 0.1]), vt=0.6, eyt=0.0, max_iter=50):
+        self.matrix_A, self.matrix_B, self.matrix_Q, self.matrix_R = matrix_A, matrix_B, matrix_Q, matrix_R
+        self.vt, self.eyt, self.max_iter = vt, eyt, max_iter
+
+
+class LQRTracking(ControlBase):
+    def __init__(self, lqr_param, system_param):
+        ControlBase.__init__(self)
+        self.set_target_speed(lqr_param.vt)
+        self.set_target_deviation(lqr_param.eyt)
+        self.lqr_param, self.system_param = lqr_param, system_param
+
+    def calc_input(self):
+        xtarget = np.array([self.vt, 0, 0, 0, 0, self.eyt]).reshape(X_DIM, 1)
+        self.u = control.lqr(self.x, xtarget, self.lqr_param)
+        self._ego_log_none()
+        self.time += self.timestep
+
+
+class iLQRRacingParam:
+    def __init__(self, matrix_A=_A_DEFAULT, matrix_B=_B_DEFAULT, matrix_Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]),
+                 matrix_R=np.diag([0.1, 0.1]), vt=0.6, eyt=0.0, max_iter=150, num_horizon=50):
+        self.matrix_A, self.matrix_B, self.matrix_Q, self.matrix_R = matrix_A, matrix_B, matrix_Q, matrix_R
+        self.vt, self.eyt, self.max_iter, self.num_horizon = vt, eyt, max_iter, num_horizon
+
+
+class iLQRRacing(ControlBase):
+    def __init__(self, ilqr_param, system_param):
+        ControlBase.__init__(self)
+        self.set_target_speed(ilqr_param.vt)
+        self.set_target_deviation(ilqr_param.eyt)
+        self.ilqr_param, self.system_param = ilqr_param, system_param
+
+    def calc_input(self):
+        xtarget = np.array([self.vt, 0, 0, 0, 0, self.eyt])   # a flat target here, unlike the other controllers
+        self.u = control.ilqr(self.x, xtarget, self.ilqr_param, self.racing_sim.vehicles, self.agent_name,
+                              self.racing_sim.track.lap_length, self.time, self.timestep, self.track, self.system_param)
         self._ego_log_none()
         self.time += self.timestep
 

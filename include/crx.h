@@ -44,7 +44,9 @@
 extern "C" {
 #endif
 
-#define CRX_VERSION 400 /* 0.4.0: NOT layout-compatible with 0.3.x -- crx_ipm_opts grew by IPOPT's three UNSCALED termination tolerances
+#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_ilqr_desc, crx_ilqr_desc_default, crx_ilqr_solve, crx_ilqr_solve_dev and
+                          CRX_ILQR_MAX_N -- new entry points only, every earlier signature and struct layout unchanged.
+                          0.4.0: NOT layout-compatible with 0.3.x -- crx_ipm_opts grew by IPOPT's three UNSCALED termination tolerances
                           (`dual_inf_tol`, `constr_viol_tol`, `compl_inf_tol`: "converged" now means IPOPT's complete test, not the scaled error
                           alone) and by `stall_iters` (the stall rule's budget, a kernel constant until 0.3.x; crx_cbf_desc_default picks it and
                           `restore_iters` by problem class).
@@ -75,6 +77,7 @@ extern "C" {
 #define CRX_MAX_REGIONS (CRX_MAX_VEH + 1)
 #define CRX_LMPC_MAX_N 16 /* horizon limit of crx_lmpc_solve (its dense factors share one LDS slice) */
 #define CRX_MAX_SS 60      /* safe-set points per learning-MPC QP (reference: 44) */
+#define CRX_ILQR_MAX_N 64  /* horizon limit of crx_ilqr_solve (one stage per lane in the derivative phase; reference: 50) */
 
 typedef enum crx_err {
     CRX_OK = 0,
@@ -231,6 +234,55 @@ typedef struct crx_lmpc_desc {
                               (see crx_lmpc_solve) */
     crx_ipm_opts opts;
 } crx_lmpc_desc;
+
+/* ---- iLQR of the ego racer (control/control.py:64-195 ilqr, control/ilqr_helper.py:4-55) ----------------------------------
+ * Quirks of the reference kept on purpose (crx_ilqr.hip names them at the lines that implement them):
+ *   I1  the obstacle is the LAST non-ego vehicle in `vehicles` order (control.py:99-104 overwrites obs_traj in its loop); its
+ *       dimensions always come from the vehicle named "car1" (:106-109).  The reference raises NameError with no other vehicle;
+ *       here n_obs = 0 means no barrier term (a deviation).  The kernel sums the barrier terms of n_obs obstacles (what the
+ *       helper's comment intends, ilqr_helper.py:33); the control.ilqr mirror passes exactly one, as the reference does.
+ *   I2  stage derivatives cover stages 0..N-1 only (ilqr_helper.py:29): the terminal Vx, Vxx are stage N-1's running derivatives
+ *       (control.py:136-137), so stage N-1 enters twice and stage N never enters the backward pass.  Stage N enters the cost.
+ *   I3  the cost of the accept and stop tests has no barrier term: sum_{k<N} (x_k-xt)'Q(x_k-xt) + u_k'Ru_k + (x_N-xt)'Q(x_N-xt).
+ *   I4  Qux = B' Vxx A with no l_ux (:145); Vx = Qx - K' Quu k, Vxx = Qxx - K' Quu K use the UNREGULARISED Quu (:158-159); k, K use
+ *       V diag(1 / (max(l_i, 0) + lamb)) V' (:147-151).
+ *   I5  barrier of degree 2, h = 1 + margin - d' P d, P = diag(1/l_sum^2, 1/w_sum^2) on (ds, dey); gradient q1 q2 e^{q2 h} h',
+ *       Hessian q1 q2^2 e^{q2 h} h' h'^T (Gauss-Newton, no -2P term; ilqr_helper.py:36-52); ds = s_k - s_obs,k - lap_off with
+ *       lap_off = (int(s_ego / L) - int(s_obs,0 / L)) L (int() truncates toward zero; the obstacle's cycle from its stage 0 only).
+ *   I6  no warm start: every call starts from u = 0 (:86); no input or state bounds.
+ * Stops: CRX_CONVERGED = relative decrease below eps after an accepted step (the reference prints "Convergence achieved",
+ * :181-183); CRX_STALLED = lamb > lamb_max (:187-188); CRX_MAX_ITER = max_iter backward passes.  iters counts backward passes
+ * (= the reference's get_cost_derivation calls). */
+typedef struct crx_ilqr_desc {
+    int32_t N;             /* ilqr_param.num_horizon (utils/base.py:175), 1..CRX_ILQR_MAX_N; 50 */
+    int32_t max_iter;      /* ilqr_param.max_iter (:174), 150 */
+    int32_t n_obs_max;     /* leading dimension of obs_s / obs_ey / lap_off, 0..CRX_MAX_OBS */
+    int32_t pad_;
+    double A[36];          /* matrix_A, row-major (:168; data/sys/LTI/matrix_A.csv) */
+    double B[12];          /* matrix_B, row-major 6x2 (:169) */
+    double Q[36];          /* matrix_Q, full (:170) diag(10, 0, 0, 4, 0, 40) */
+    double R[4];           /* matrix_R, full (:171) diag(0.1, 0.1) */
+    double eps;            /* 0.01  relative-decrease stop (control.py:80) */
+    double lamb_init;      /* 1     (:81) */
+    double lamb_factor;    /* 10    (:82) */
+    double lamb_max;       /* 1000  (:83) */
+    double margin;         /* 0.15  safety_margin (ilqr_helper.py:25) */
+    double q1, q2;         /* 2.5, 2.5 (ilqr_helper.py:26-27) */
+    double l_sum;          /* l_agent + l_obs, half lengths (control.py:106-108): 0.4 */
+    double w_sum;          /* w_agent + w_obs, half widths (:107-109): 0.2 */
+} crx_ilqr_desc;
+
+/* Defaults above; A, B copied when non-NULL (zero otherwise). */
+void crx_ilqr_desc_default(crx_ilqr_desc* d, int N, const double* A, const double* B);
+/* x0 [batch][6], xt [batch][6]; obs_s, obs_ey [batch][n_obs_max][N+1]; lap_off [batch][n_obs_max]; n_obs [batch] in
+ * [0, n_obs_max].  X [batch][N+1][6], U [batch][N][2]: the accepted trajectory (the reference returns U[0], control.py:195);
+ * cost [batch]: its barrier-free cost (I3); status [batch]; iters [batch]. */
+int crx_ilqr_solve(const crx_ilqr_desc* d, int batch, const double* x0, const double* xt, const double* obs_s, const double* obs_ey,
+                   const double* lap_off, const int32_t* n_obs, double* X, double* U, double* cost, int32_t* status, int32_t* iters);
+/* device pointers; active [batch] as in the masked launches (NULL = all; 0 = CRX_SKIPPED, outputs untouched) */
+int crx_ilqr_solve_dev(const crx_ilqr_desc* d, int batch, const int32_t* active, const double* x0, const double* xt,
+                       const double* obs_s, const double* obs_ey, const double* lap_off, const int32_t* n_obs, double* X, double* U,
+                       double* cost, int32_t* status, int32_t* iters, void* stream);
 
 /* ---- region selection (overtake_traj_planner.py:205-246) ------------------------------------- */
 typedef struct crx_select_desc {

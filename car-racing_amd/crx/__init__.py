@@ -85,6 +85,11 @@ def ilqr_solve(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs):
     return binding().ilqr_solve(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs)
 
 
+def sysid_fit(x, u, offsets=None, group_offsets=None, lamb=1e-9):
+    """Batched system identification (include/crx.h S1..S5) on host arrays: see abi.Binding.sysid_fit."""
+    return binding().sysid_fit(abi.sysid_desc(lamb), x, u, offsets, group_offsets)
+
+
 def path_solve(desc, opt, bez, lb, ub, e0, eN):
     return binding().path_solve(desc, opt, bez, lb, ub, e0, eN)
 

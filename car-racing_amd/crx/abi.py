@@ -139,6 +139,15 @@ class IlqrDesc(C.Structure):
     ]
 
 
+class SysidDesc(C.Structure):
+    _fields_ = [
+        ("lamb", C.c_double),
+        ("first_row", C.c_int32),
+        ("chunk_rows", C.c_int32),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 class PrepDesc(C.Structure):
     _fields_ = [
         ("N", C.c_int32),
@@ -257,6 +266,24 @@ def ilqr_desc(N, A, B, Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]), R=np.diag([0
                     l_sum, w_sum)
 
 
+def sysid_desc(lamb=1e-9, first_row=1, chunk_rows=8192):
+    """crx_sysid_desc_default: lamb of system_identification_test.py:42; first_row = 1 drops row 0 (S1)."""
+    return SysidDesc(float(lamb), int(first_row), int(chunk_rows))
+
+
+def sysid_offsets(x, offsets):
+    """(x [rows,6], int64 log offsets [n_logs+1]) from a [T,6] log with offsets None, a [B,T,6] batch of equal logs, or packed rows
+    with explicit offsets."""
+    x = np.asarray(x, dtype=_D)
+    if offsets is None:
+        if x.ndim == 3:
+            offsets = np.arange(x.shape[0] + 1, dtype=np.int64) * x.shape[1]
+            x = x.reshape(-1, 6)
+        else:
+            offsets = np.array([0, x.shape[0]], dtype=np.int64)
+    return x, np.ascontiguousarray(offsets, dtype=np.int64)
+
+
 def prep_desc(N, n_veh_max, n_opt, track_width, lap_length, prediction_factor=0.5, veh_length=0.4, veh_width=0.2):
     """planner_helper.py:51-53 and overtake_traj_planner.py:288,296 literals."""
     return PrepDesc(int(N), int(n_veh_max), int(n_opt), 0, prediction_factor, 4.0, track_width, lap_length,
@@ -302,7 +329,8 @@ class Binding:
 
     def __init__(self, lib, prefix):
         self.lib, self.prefix = lib, prefix
-        for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve", "ilqr_solve"):
+        for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve", "ilqr_solve",
+                     "sysid_fit"):
             if hasattr(lib, prefix + name):
                 getattr(lib, prefix + name).restype = C.c_int
         self._check = None
@@ -353,6 +381,25 @@ class Binding:
                    iters=np.zeros(Bn, dtype=_I))
         self._call("ilqr_solve", C.byref(desc), C.c_int(Bn), _p(x0), _p(xt), _p(obs_s), _p(obs_ey), _p(lap_off), _p(n_obs),
                    _p(out["X"]), _p(out["U"]), _p(out["cost"]), _p(out["status"]), _p(out["iters"]))
+        return out
+
+    def sysid_fit(self, desc, x, u, offsets=None, group_offsets=None):
+        """crx_sysid_fit.  x [rows,6], u [rows,2] packed logs with int64 offsets [n_logs+1] (or a [T,6] log / [B,T,6] batch and
+        offsets None); group_offsets int32 [n_groups+1] or None (one fit per log).  Returns A (G,6,6), B (G,6,2), err (G,2,6),
+        n_pairs (G,) int64, status (G,)."""
+        x, offsets = sysid_offsets(x, offsets)
+        u = np.asarray(u, dtype=_D).reshape(-1, 2)
+        n_logs = offsets.shape[0] - 1
+        x = _in(x, _D, (x.shape[0], 6))
+        u = _in(u, _D, (x.shape[0], 2))
+        go = None
+        if group_offsets is not None:
+            go = np.ascontiguousarray(group_offsets, dtype=_I)
+        G = n_logs if go is None else go.shape[0] - 1
+        out = dict(A=np.zeros((G, 6, 6)), B=np.zeros((G, 6, 2)), err=np.zeros((G, 2, 6)), n_pairs=np.zeros(G, dtype=np.int64),
+                   status=np.zeros(G, dtype=_I))
+        self._call("sysid_fit", C.byref(desc), C.c_int(n_logs), _p(offsets), _p(go) if go is not None else None, C.c_int(G), _p(x),
+                   _p(u), _p(out["A"]), _p(out["B"]), _p(out["err"]), _p(out["n_pairs"]), _p(out["status"]))
         return out
 
     def cbf_solve(self, desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, obs_dims=None):

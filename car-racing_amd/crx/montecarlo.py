@@ -629,3 +629,70 @@ def game_laps(track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u
     return dict(xcurv=torch.stack(lx).cpu().numpy(), u=torch.stack(lu).cpu().numpy(), overtake=torch.stack(lo).cpu().numpy(),
                 flag=torch.stack(lf).cpu().numpy(), cars_s=torch.stack(lc).cpu().numpy(), laps=r.lm.laps.cpu().numpy(),
                 traj_status=r.lm.traj_status.cpu().numpy(), scene_overflow=r.overflow_seen.cpu().numpy())
+
+
+class PidLaps:
+    """B copies of the reference's identification experiment (car_racing/tests/system_identification_test.py: one car under
+    PIDTracking on its own, logged for `steps` control steps), device-resident, then identified without leaving the device.
+    Per control step: ONE crx_plant_step_noise_dev (with the lap wrap of update_memory, base.py:795-819) and ONE crx_pid_log_dev
+    that logs the step's row and computes the next input.  x_log [B,T,6] holds xcurv_log (s wrapped, S2) and u_log [B,T,2]
+    what get_udata assembles from it (S5: u[k] = the input applied in the step that produced x[k]).
+    Noise: noise_z [T,B,3] standard-normal draws (the reference's three randn per step, in call order), else a device generator
+    seeded with noise_seed; both None = zero noise."""
+
+    def __init__(self, track_table, lap_length, xcurv0, xglob0, steps, vt=0.5, eyt=0.0, timestep=0.1, noise_z=None,
+                 noise_seed=None, device=None):
+        dev = torch.device(device if device is not None else "cuda")
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.xc = torch.as_tensor(np.ascontiguousarray(xcurv0), **f64).clone()
+        self.xg = torch.as_tensor(np.ascontiguousarray(xglob0), **f64).clone()
+        Bn, T = self.xc.shape[0], int(steps)
+        self.batch, self.steps, self.device = Bn, T, dev
+        self.vt = torch.as_tensor(np.broadcast_to(np.asarray(vt, dtype=float), (Bn,)).copy(), **f64)
+        self.eyt = torch.as_tensor(np.broadcast_to(np.asarray(eyt, dtype=float), (Bn,)).copy(), **f64)
+        self.tab = torch.as_tensor(np.ascontiguousarray(track_table), **f64)
+        self.pdesc = abi.plant_desc(self.tab.shape[0], lap_length, timestep=timestep)
+        self.noise_z = None
+        if noise_z is not None:
+            self.noise_z = torch.as_tensor(np.ascontiguousarray(noise_z), **f64) if not torch.is_tensor(noise_z) else noise_z.to(**f64)
+            if tuple(self.noise_z.shape) != (T, Bn, 3):
+                raise ValueError("noise_z: expected shape %s, got %s" % ((T, Bn, 3), tuple(self.noise_z.shape)))
+        self.noise = _Noise(noise_seed, dev)
+        self.x_log = torch.zeros((Bn, T, 6), **f64)
+        self.u_log = torch.zeros((Bn, T, 2), **f64)
+        self.laps = torch.zeros(Bn, dtype=torch.int32, device=dev)
+        self.u, self.u_next = torch.zeros((Bn, 2), **f64), torch.zeros((Bn, 2), **f64)
+        self.xg_next, self.xc_next = torch.empty_like(self.xg), torch.empty_like(self.xc)
+        self.k = 0
+        torch_api.pid_log_dev(T, -1, self.vt, self.eyt, self.xc, None, self.u, self.x_log, self.u_log)
+
+    def step(self):
+        k = self.k
+        z = self.noise_z[k] if self.noise_z is not None else self.noise.draw(self.batch)
+        torch_api.plant_step_wrap_dev(self.pdesc, self.tab, self.xg, self.xc, self.u, 2, self.xg_next, self.xc_next, self.laps,
+                                      noise_z=z)
+        self.xg, self.xg_next = self.xg_next, self.xg
+        self.xc, self.xc_next = self.xc_next, self.xc
+        torch_api.pid_log_dev(self.steps, k, self.vt, self.eyt, self.xc, self.u, self.u_next if k + 1 < self.steps else None,
+                              self.x_log, self.u_log)
+        self.u, self.u_next = self.u_next, self.u
+        self.k += 1
+
+    def run(self):
+        while self.k < self.steps:
+            self.step()
+        return self
+
+    def identify(self, lamb=1e-9, group_offsets=None, chunk_rows=8192):
+        """crx_sysid_fit_dev over the resident logs: one fit per car (group_offsets None) or per group of cars."""
+        T, Bn = self.steps, self.batch
+        offsets = torch.arange(Bn + 1, dtype=torch.int64, device=self.device) * T
+        return torch_api.sysid_fit_dev(abi.sysid_desc(lamb, chunk_rows=chunk_rows), self.x_log.view(-1, 6), self.u_log.view(-1, 2),
+                                       offsets, group_offsets, max_log_rows=T)
+
+
+def pid_laps(track_table, lap_length, xcurv0, xglob0, steps, vt=0.5, eyt=0.0, timestep=0.1, noise_z=None, noise_seed=None,
+             device=None):
+    """PidLaps run to the end: the logs stay on the device (r.x_log, r.u_log); r.identify(lamb) fits them."""
+    return PidLaps(track_table, lap_length, xcurv0, xglob0, steps, vt=vt, eyt=eyt, timestep=timestep, noise_z=noise_z,
+                   noise_seed=noise_seed, device=device).run()

@@ -187,6 +187,61 @@ def ilqr_solve_dev(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, ws=None, active=
     return ws
 
 
+class SysidWorkspace:
+    """Outputs and device scratch of sysid_fit_dev calls for n_logs logs of at most max_log_rows rows in n_groups groups."""
+
+    def __init__(self, desc, n_logs, n_groups, max_log_rows, device):
+        f64 = dict(dtype=torch.float64, device=device)
+        self.n_logs, self.n_groups, self.max_log_rows = int(n_logs), int(n_groups), int(max_log_rows)
+        self.A = torch.zeros((n_groups, 6, 6), **f64)
+        self.B = torch.zeros((n_groups, 6, 2), **f64)
+        self.err = torch.zeros((n_groups, 2, 6), **f64)
+        self.n_pairs = torch.zeros(n_groups, dtype=torch.int64, device=device)
+        self.status = torch.zeros(n_groups, dtype=torch.int32, device=device)
+        fn = lib().crx_sysid_workspace_bytes
+        fn.restype = C.c_size_t
+        self.ws_bytes = int(fn(C.byref(desc), C.c_int(n_logs), C.c_int(n_groups), C.c_int64(max_log_rows)))
+        self.scratch = torch.empty(self.ws_bytes, dtype=torch.uint8, device=device)
+
+
+def sysid_fit_dev(desc, x, u, offsets, group_offsets=None, max_log_rows=None, ws=None):
+    """crx_sysid_fit_dev: x [rows,6], u [rows,2] float64; offsets int64 [n_logs+1]; group_offsets int32 [n_groups+1] or None (one
+    fit per log).  max_log_rows bounds every log (None: read from offsets, one device-to-host copy)."""
+    rows, n_logs = x.shape[0], offsets.shape[0] - 1
+    _chk(x, torch.float64, (rows, 6), "x")
+    _chk(u, torch.float64, (rows, 2), "u")
+    _chk(offsets, torch.int64, (n_logs + 1,), "offsets")
+    G = n_logs
+    if group_offsets is not None:
+        G = group_offsets.shape[0] - 1
+        _chk(group_offsets, torch.int32, (G + 1,), "group_offsets")
+    if max_log_rows is None:
+        max_log_rows = int((offsets[1:] - offsets[:-1]).max().item()) if n_logs > 0 else 0
+    if ws is None or ws.n_logs != n_logs or ws.n_groups != G or ws.max_log_rows < max_log_rows:
+        ws = SysidWorkspace(desc, n_logs, G, max_log_rows, x.device)
+    _call("crx_sysid_fit_dev", C.byref(desc), C.c_int(n_logs), _ptr(offsets), _ptr(group_offsets), C.c_int(G), C.c_int64(ws.max_log_rows),
+          _ptr(x), _ptr(u), _ptr(ws.scratch), C.c_size_t(ws.ws_bytes), _ptr(ws.A), _ptr(ws.B), _ptr(ws.err), _ptr(ws.n_pairs),
+          _ptr(ws.status), _stream())
+    return ws
+
+
+def pid_log_dev(T, row, vt, eyt, xcurv, u_prev, u_next, x_log, u_log):
+    """crx_pid_log_dev: log row `row` (< 0: none) of x_log [B,T,6] / u_log [B,T,2] from (xcurv [B,6], u_prev [B,2]), then
+    u_next [B,2] = control.pid(xcurv) with targets vt, eyt [B] (u_next may be None)."""
+    B = xcurv.shape[0]
+    _chk(xcurv, torch.float64, (B, 6), "xcurv")
+    _chk(vt, torch.float64, (B,), "vt")
+    _chk(eyt, torch.float64, (B,), "eyt")
+    _chk(x_log, torch.float64, (B, T, 6), "x_log")
+    _chk(u_log, torch.float64, (B, T, 2), "u_log")
+    if u_next is not None:
+        _chk(u_next, torch.float64, (B, 2), "u_next")
+    if row >= 0:
+        _chk(u_prev, torch.float64, (B, 2), "u_prev")
+    _call("crx_pid_log_dev", C.c_int(B), C.c_int(T), C.c_int(row), _ptr(vt), _ptr(eyt), _ptr(xcurv), _ptr(u_prev if row >= 0 else None),
+          _ptr(u_next), _ptr(x_log), _ptr(u_log), _stream())
+
+
 class PlannerWorkspace:
     def __init__(self, desc, batch, device):
         N = desc.N

@@ -1026,6 +1026,117 @@ int crx_ilqr_solve(const crx_ilqr_desc* d, int batch, const double* x0, const do
     return sg.down(g_stream);
 }
 
+// ---- LTI system identification (system/system_identification.py:4-43) --------------------------------------------------
+void crx_sysid_desc_default(crx_sysid_desc* d) {
+    memset(d, 0, sizeof(*d));
+    d->lamb = 1e-9; d->first_row = 1; d->chunk_rows = 8192;
+}
+
+static int check_sysid(const crx_sysid_desc* d, int n_logs, int n_groups, bool grouped) {
+    if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
+    if (!(d->lamb >= 0.0) || !isfinite(d->lamb)) return fail(CRX_ERR_ARG, "lamb must be finite and non-negative");
+    if (d->first_row < 0) return fail(CRX_ERR_ARG, "first_row < 0");
+    if (d->chunk_rows < 256 || d->chunk_rows > 65536 || d->chunk_rows % 256) return fail(CRX_ERR_ARG, "chunk_rows=%d: a multiple of 256 in [256, 65536]", d->chunk_rows);
+    if (n_logs < 0 || n_groups < 0) return fail(CRX_ERR_ARG, "n_logs, n_groups must be >= 0");
+    if (!grouped && n_groups != n_logs) return fail(CRX_ERR_ARG, "group_offset NULL needs n_groups == n_logs");
+    return 0;
+}
+
+static int sysid_tpl(const crx_sysid_desc* d, int64_t max_log_rows) {
+    const int64_t pairs = max_log_rows - 1 - d->first_row;
+    const int64_t t = pairs > 0 ? (pairs + d->chunk_rows - 1) / d->chunk_rows : 0;
+    return t > 1 ? (int)t : 1;
+}
+
+size_t crx_sysid_workspace_bytes(const crx_sysid_desc* d, int n_logs, int n_groups, int64_t max_log_rows) {
+    if (!d || d->chunk_rows <= 0 || n_logs < 0 || n_groups < 0) return 0;
+    const size_t tiles = (size_t)n_logs * (size_t)sysid_tpl(d, max_log_rows);
+    return (tiles * (84 + 12) + (size_t)n_groups * 48) * sizeof(double) + 2 * 256;
+}
+
+int crx_sysid_fit_dev(const crx_sysid_desc* d, int n_logs, const int64_t* log_offset, const int32_t* group_offset, int n_groups,
+                      int64_t max_log_rows, const double* x, const double* u, void* workspace, size_t ws_bytes, double* A, double* B,
+                      double* err, int64_t* n_pairs, int32_t* status, void* stream) {
+    if (int rc = check_sysid(d, n_logs, n_groups, group_offset != nullptr)) return rc;
+    if (max_log_rows < 0) return fail(CRX_ERR_ARG, "max_log_rows < 0");
+    const int tpl = sysid_tpl(d, max_log_rows);
+    if ((int64_t)n_logs * tpl > INT32_MAX) return fail(CRX_ERR_ARG, "n_logs * tiles per log exceeds the grid");
+    if (n_groups > 0 && (!log_offset || !A || !B || !err || !n_pairs || !status || !workspace)) return fail(CRX_ERR_ARG, "NULL array argument");
+    if (n_groups > 0 && max_log_rows > 0 && (!x || !u)) return fail(CRX_ERR_ARG, "NULL array argument");
+    if (n_groups > 0 && ws_bytes < crx_sysid_workspace_bytes(d, n_logs, n_groups, max_log_rows))
+        return fail(CRX_ERR_ARG, "workspace of %zu bytes, %zu needed", ws_bytes, crx_sysid_workspace_bytes(d, n_logs, n_groups, max_log_rows));
+    if (((uintptr_t)x | (uintptr_t)u) & 15) return fail(CRX_ERR_ARG, "x and u must be 16-byte aligned");
+    if (int rc = ensure_init()) return rc;
+    if (n_groups == 0) return CRX_OK;
+    crx_sysid_kparams kp;
+    kp.n_logs = n_logs; kp.n_groups = n_groups; kp.first_row = d->first_row; kp.chunk = d->chunk_rows; kp.tpl = tpl; kp.lamb = d->lamb;
+    kp.log_off = log_offset; kp.grp_off = group_offset; kp.x = x; kp.u = u;
+    char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    const size_t tiles = (size_t)n_logs * tpl;
+    kp.ws_gram = (double*)ws;
+    kp.ws_res = kp.ws_gram + tiles * 84;
+    kp.ws_W = kp.ws_res + tiles * 12;
+    kp.A = A; kp.B = B; kp.err = err; kp.n_pairs = n_pairs; kp.status = status;
+    hipError_t e = crx_launch_sysid(kp, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(CRX_ERR_HIP, "sysid launch: %s", hipGetErrorString(e));
+    return CRX_OK;
+}
+
+int crx_sysid_fit(const crx_sysid_desc* d, int n_logs, const int64_t* log_offset, const int32_t* group_offset, int n_groups,
+                  const double* x, const double* u, double* A, double* B, double* err, int64_t* n_pairs, int32_t* status) {
+    if (int rc = check_sysid(d, n_logs, n_groups, group_offset != nullptr)) return rc;
+    if (n_groups > 0 && (!log_offset || !A || !B || !err || !n_pairs || !status)) return fail(CRX_ERR_ARG, "NULL array argument");
+    int64_t max_rows = 0, rows = 0;
+    if (n_groups > 0) {
+        if (log_offset[0] < 0) return fail(CRX_ERR_ARG, "log_offset[0] < 0");
+        for (int l = 0; l < n_logs; l++) {
+            const int64_t n = log_offset[l + 1] - log_offset[l];
+            if (n < 0) return fail(CRX_ERR_ARG, "log_offset decreases at %d", l);
+            if (n > max_rows) max_rows = n;
+        }
+        rows = log_offset[n_logs];
+        if (group_offset) {
+            if (group_offset[0] != 0 || group_offset[n_groups] != n_logs) return fail(CRX_ERR_ARG, "group_offset must run from 0 to n_logs");
+            for (int g = 0; g < n_groups; g++)
+                if (group_offset[g + 1] < group_offset[g]) return fail(CRX_ERR_ARG, "group_offset decreases at %d", g);
+        }
+        if (rows > 0 && (!x || !u)) return fail(CRX_ERR_ARG, "NULL array argument");
+    }
+    if (int rc = ensure_init()) return rc;
+    if (n_groups == 0) return CRX_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    const size_t L = (size_t)n_logs, G = (size_t)n_groups, R = (size_t)rows;
+    const size_t ws_bytes = crx_sysid_workspace_bytes(d, n_logs, n_groups, max_rows);
+    Stage sg;
+    if (int rc = sg.reserve(R * 8 * 8 + (L + 1) * 8 + (G + 1) * 4, G * (36 + 12 + 12 + 1) * 8 + G * 4 + ws_bytes)) return rc;
+    const double* dx = sg.in(x, R * 6); const double* du = sg.in(u, R * 2);
+    const int64_t* dlo = sg.in(log_offset, L + 1);
+    const int32_t* dgo = group_offset ? sg.in(group_offset, G + 1) : nullptr;
+    double* dA = sg.out(A, G * 36); double* dB = sg.out(B, G * 12); double* de = sg.out(err, G * 12);
+    int64_t* dn = sg.out(n_pairs, G); int32_t* ds = sg.out(status, G);
+    char* dws = sg.out((char*)nullptr, ws_bytes);
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_sysid_fit_dev(d, n_logs, dlo, dgo, n_groups, max_rows, dx, du, dws, ws_bytes, dA, dB, de, dn, ds, g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
+// ---- PID step + log row of the identification experiment (control/control.py:15-25, utils/base.py PIDTracking) ------------
+int crx_pid_log_dev(int batch, int T, int row, const double* vt, const double* eyt, const double* xcurv, const double* u_prev,
+                    double* u_next, double* x_log, double* u_log, void* stream) {
+    if (batch < 0 || row >= T) return fail(CRX_ERR_ARG, "batch < 0 or row >= T");
+    if (batch > 0 && (!xcurv || (u_next && (!vt || !eyt)) || (row >= 0 && (!u_prev || !x_log || !u_log))))
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    if (int rc = ensure_init()) return rc;
+    if (batch == 0) return CRX_OK;
+    crx_pid_kparams kp;
+    kp.batch = batch; kp.T = T; kp.row = row; kp.vt = vt; kp.eyt = eyt; kp.xcurv = xcurv; kp.u_prev = u_prev;
+    kp.u_next = u_next; kp.x_log = x_log; kp.u_log = u_log;
+    hipError_t e = crx_launch_pid_log(kp, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(CRX_ERR_HIP, "pid launch: %s", hipGetErrorString(e));
+    return CRX_OK;
+}
+
 // ---- planner front (interest test, partial sort, vehicle infos) on the device ------------------------
 void crx_scene_desc_default(crx_scene_desc* d, int N, int n_all_max, int n_veh_max, double lap_length) {
     memset(d, 0, sizeof(*d));

@@ -208,5 +208,24 @@ struct crx_ilqr_kparams {
 hipError_t crx_launch_ilqr(const crx_ilqr_kparams& kp, hipStream_t st);
 size_t crx_ilqr_lds_bytes(int N);
 int crx_ilqr_resident_per_cu(int N);
+// system identification (crx_sysid.hip)
+struct crx_sysid_kparams {
+    int n_logs, n_groups, first_row, chunk, tpl;   // tpl = tile slots per log in the workspace
+    double lamb;
+    const int64_t* log_off;
+    const int32_t* grp_off;   // NULL = one group per log
+    const double *x, *u;
+    double *ws_gram, *ws_res, *ws_W;
+    double *A, *B, *err;
+    int64_t* n_pairs;
+    int32_t* status;
+};
+hipError_t crx_launch_sysid(const crx_sysid_kparams& kp, hipStream_t st);
+struct crx_pid_kparams {
+    int batch, T, row;
+    const double *vt, *eyt, *xcurv, *u_prev;
+    double *u_next, *x_log, *u_log;
+};
+hipError_t crx_launch_pid_log(const crx_pid_kparams& kp, hipStream_t st);
 #endif
 #endif

@@ -44,7 +44,9 @@
 extern "C" {
 #endif
 
-#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_ilqr_desc, crx_ilqr_desc_default, crx_ilqr_solve, crx_ilqr_solve_dev and
+#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_sysid_desc, crx_sysid_desc_default, crx_sysid_fit, crx_sysid_fit_dev,
+                          crx_sysid_workspace_bytes, crx_pid_log_dev and status CRX_SINGULAR -- new entry points only.
+                          0.4.0 (additive, same number): crx_ilqr_desc, crx_ilqr_desc_default, crx_ilqr_solve, crx_ilqr_solve_dev and
                           CRX_ILQR_MAX_N -- new entry points only, every earlier signature and struct layout unchanged.
                           0.4.0: NOT layout-compatible with 0.3.x -- crx_ipm_opts grew by IPOPT's three UNSCALED termination tolerances
                           (`dual_inf_tol`, `constr_viol_tol`, `compl_inf_tol`: "converged" now means IPOPT's complete test, not the scaled error
@@ -97,11 +99,13 @@ typedef enum crx_status {
                               the closed-form slack restoration) and used up opts.restore_iters further iterations without
                               converging.  The returned iterate satisfies every CBF row through its slacks sigma but is not optimal. */
     CRX_SKIPPED = 4,       /* *_masked_dev launches only: active[b] == 0, the problem was left alone (outputs untouched) */
-    CRX_STALLED = 5        /* gave up WITHOUT a proof at a point that still violates its constraints: no acceptable step (IPOPT:
+    CRX_STALLED = 5,       /* gave up WITHOUT a proof at a point that still violates its constraints: no acceptable step (IPOPT:
                               "restoration failed" / "converged to a point of local infeasibility"), or multipliers past 1e12 (IPOPT's
                               divergence heuristic).  libcrx <= 0.1.3 reported these as CRX_INFEASIBLE.  Like every status != 0 it
                               selects the reference's "solver failed" branch (control.py:600-603: keep the last iterate;
                               overtake_traj_planner.py:365-374: the fall-back trajectory). */
+    CRX_SINGULAR = 6       /* crx_sysid_fit only: a zero or non-finite pivot in the LU of X'X + lamb I, where numpy.linalg.inv raises
+                              LinAlgError; W, A, B and err are NaN */
 } crx_status;
 
 /* Interior-point options.  Defaults (crx_ipm_opts_default) restate IPOPT 3.x defaults that the
@@ -283,6 +287,53 @@ int crx_ilqr_solve(const crx_ilqr_desc* d, int batch, const double* x0, const do
 int crx_ilqr_solve_dev(const crx_ilqr_desc* d, int batch, const int32_t* active, const double* x0, const double* xt,
                        const double* obs_s, const double* obs_ey, const double* lap_off, const int32_t* n_obs, double* X, double* U,
                        double* cost, int32_t* status, int32_t* iters, void* stream);
+
+/* ---- LTI system identification (system/system_identification.py:4-43 linear_regression, get_udata) ------------------------
+ * Batched ridge regression of x_{k+1} on (x_k, u_k) over packed logs, FP64 on the device.  Semantics of the reference kept:
+ *   S1  rows used: Y = x[2:T], X = [x[1:T-1] | u[1:T-1]] of each log (first_row = 1: row 0 is dropped), T - 2 pairs for a log of
+ *       T rows; pairs never cross two logs.  A group (a contiguous run of logs) pools the pairs of its logs into one fit.
+ *   S2  no unwrapping: the lap wrap of s stays in the data, as logged.
+ *   S3  W = inv(X'X + lamb I) (X'Y): the inverse is formed as numpy does (LU with partial pivoting, solved against I), then
+ *       multiplied; no direct solve.  A zero or non-finite pivot is CRX_SINGULAR (numpy raises LinAlgError).
+ *   S4  A = W'[:, 0:6], B = W'[:, 6:8]; err = [max_rows(XW - Y); min_rows(XW - Y)], [2][6] (NaN propagates, as numpy's max).
+ *   S5  get_udata (the lap-by-lap assembly of ego.inputs and lap_inputs) stays on the host (crx.montecarlo.PidLaps logs u in
+ *       the layout it produces: u[k] = the input applied in the step that produced x[k]).
+ * Summation: (log, chunk) tiles of chunk_rows pairs, one workgroup each; lanes accumulate their pairs in ascending order, the
+ * wave reduces with crx_wave.h's fixed butterfly, the waves in ascending order.  The tiles of a group are summed by the group's
+ * solve workgroup: the group's logs are dealt to its 256 lanes in turn (log j to lane j mod 256), a lane adds its logs' tiles
+ * log ascending, tile ascending, then the lanes are reduced as above.  The order depends on the group's own logs and
+ * chunk_rows only: a fit is bit-identical whatever the batch, the position of its logs in it and the other groups launched
+ * with it.  No atomics. */
+typedef struct crx_sysid_desc {
+    double lamb;           /* 1e-9: ridge coefficient (system_identification_test.py:42) */
+    int32_t first_row;     /* 1: first log row that enters X (S1) */
+    int32_t chunk_rows;    /* 8192: pairs per tile (part of the summation order; 64..65536, a multiple of 256) */
+    int32_t reserved[4];   /* 0 */
+} crx_sysid_desc;
+
+/* Defaults above. */
+void crx_sysid_desc_default(crx_sysid_desc* d);
+/* Host pointers.  x [rows][6], u [rows][2] packed logs; log l is rows log_offset[l] .. log_offset[l+1]-1 (int64, non-decreasing,
+ * log_offset[0] >= 0, rows = log_offset[n_logs]).  group_offset [n_groups+1] (int32, non-decreasing from 0 to n_logs): group g
+ * pools logs group_offset[g] .. group_offset[g+1]-1; NULL = one group per log (n_groups must then equal n_logs).
+ * Outputs per group: A [g][6][6], B [g][6][2], err [g][2][6], n_pairs [g] (int64), status [g]: CRX_CONVERGED (0), CRX_SKIPPED
+ * (no pair in the group), CRX_SINGULAR; A, B, err are NaN unless the status is 0. */
+int crx_sysid_fit(const crx_sysid_desc* d, int n_logs, const int64_t* log_offset, const int32_t* group_offset, int n_groups,
+                  const double* x, const double* u, double* A, double* B, double* err, int64_t* n_pairs, int32_t* status);
+/* Bytes of device workspace crx_sysid_fit_dev needs for n_logs logs of at most max_log_rows rows in n_groups groups. */
+size_t crx_sysid_workspace_bytes(const crx_sysid_desc* d, int n_logs, int n_groups, int64_t max_log_rows);
+/* Device pointers.  Same arrays; max_log_rows bounds every log's length (the tiles of a log are laid out in the workspace at a
+ * stride of ceil(max_log_rows / chunk_rows)); workspace of ws_bytes >= crx_sysid_workspace_bytes(...) bytes.  The offsets are
+ * not validated on the device: they must satisfy the host entry point's rules and max_log_rows. */
+int crx_sysid_fit_dev(const crx_sysid_desc* d, int n_logs, const int64_t* log_offset, const int32_t* group_offset, int n_groups,
+                      int64_t max_log_rows, const double* x, const double* u, void* workspace, size_t ws_bytes, double* A, double* B,
+                      double* err, int64_t* n_pairs, int32_t* status, void* stream);
+/* One control step of PIDTracking (control/control.py:15-25 pid; utils/base.py PIDTracking) for a batch of vehicles, with the
+ * log row of the step before it.  xcurv [batch][6]: the state the plant just produced.  row >= 0: x_log[b][row] = xcurv[b] and
+ * u_log[b][row] = u_prev[b] (logs [batch][T][6] / [batch][T][2], row < T); row < 0: nothing is logged.  u_next [batch][2] (may be
+ * NULL) = pid(xcurv[b]) with the target (vt[b], eyt[b]): delta = -0.6 (ey - eyt) - 0.9 epsi, a = 1.5 (vt - vx). */
+int crx_pid_log_dev(int batch, int T, int row, const double* vt, const double* eyt, const double* xcurv, const double* u_prev,
+                    double* u_next, double* x_log, double* u_log, void* stream);
 
 /* ---- region selection (overtake_traj_planner.py:205-246) ------------------------------------- */
 typedef struct crx_select_desc {

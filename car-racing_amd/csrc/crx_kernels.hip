@@ -19,9 +19,12 @@
 //   MPC-CBF NLP         control/control.py:492-591 (mpccbf), :270-382 (mpc_multi_agents)
 //   region selection    planning/overtake_traj_planner.py:205-246
 //
-// Structure of this file: (1) wave primitives, (2) compile-time LDS layout, (3) set-up of the
-// canonical stage problem, (4) per-iteration phases, (5) the solver kernel, (6) selection kernel,
-// (7) launchers.  Stage coordinates everywhere:  z_k = [x_k (6), sigma_k (NOBS), u_k (2),
+// Structure of this file: build parameters and the switches that are still open, (2) compile-time LDS layout (the wave primitives
+// live in crx_wave.h), (3) set-up of the canonical stage problem, (4) per-iteration phases, (5) the solver kernel, (6) selection
+// kernel, (7) launchers: ONE selector per translation unit from (obstacle slots, horizon, exponent) to the instantiation that
+// serves it, and the entry points as callables over it.  The file is compiled four times -- as it stands, and through
+// crx_kernels_obs.hip, crx_kernels_gen.hip and crx_kernels_spec.hip (CRX_TU_OBSTACLES, CRX_TU_GENERAL, CRX_TU_SPEC) -- section (7)
+// says which unit holds which instantiations.  Stage coordinates everywhere:  z_k = [x_k (6), sigma_k (NOBS), u_k (2),
 // sigma_{k+1} (NOBS)];  the iterate is stored as Z[k][NZ], the Newton step as dZ[k][NZ]
 // (sigma_{k+1} therefore appears twice, as an input of stage k and as a state of stage k+1; the
 // two copies are kept identical).
@@ -33,68 +36,28 @@
 #include "crx_kparams.h"
 #include "crx_wave.h"
 
-#ifndef CRX_KKT_DIAG
-#define CRX_KKT_DIAG 1   /* 0: without the unscaled-KKT diagnostics block of the write-back (A/B builds) */
-#endif
+// Preprocessor switches of this file.  Translation unit: CRX_TU_GENERAL, CRX_TU_OBSTACLES, CRX_TU_SPEC (set by the including unit).  Code generation
+// forms that the general unit and the canary builds of tools/variants.sh still exercise, because the compiler defect of DESIGN.md section 8 is open:
+// CRX_OPAQUE_LANE, CRX_STATIC_LDS, CRX_SWEEP_MASK, CRX_SWEEP_LOCAL_LANE, CRX_ROWDPP (section (4)).  Residency / build parameters: CRX_PLANNER_WAVES,
+// CRX_OBS1_WAVES, CRX_GEN_WAVES, CRX_KERNEL_EXTRA_ATTR (section (5)), CRX_NFIX_LIST (section (7)).  Diagnostic builds: CRX_PHASE_CLOCKS,
+// CRX_PROBE_ONE.  The A/B switches whose verdict is in were folded into the code; HISTORY.md lists them with the record of each verdict.
 #ifndef CRX_TU_GENERAL
 #define CRX_TU_GENERAL 0   /* 1: crx_kernels_gen.hip -- the general instantiations, built conservatively (section (7)) */
 #endif
 #ifndef CRX_OPAQUE_LANE
 #define CRX_OPAQUE_LANE 1 /* make EXTRA=-DCRX_OPAQUE_LANE=0: round-2 behaviour (lane maps hoisted out of the interior-point loop) */
 #endif
-#ifndef CRX_OPAQUE_OUTER
-#define CRX_OPAQUE_OUTER 0 /* 0: A/B builds without the per-pass lane barrier of the (re)start loop */
-#endif
-#ifndef CRX_W2_FLOOR
-#define CRX_W2_FLOOR 0 /* 1: pin <2,12> at two waves per SIMD (256 registers, 76 B of scratch) = 6 instead of 4 problems per CU */
-#endif
 #ifndef CRX_STATIC_LDS
 #define CRX_STATIC_LDS 1   // 0: the solver's LDS as a dynamic (extern) array, as up to libcrx 0.2.0 (A/B builds)
 #endif
-#ifndef CRX_SWEEP_UNROLL
-#define CRX_SWEEP_UNROLL 1   // 1: the forward and adjoint sweeps of the fixed-horizon instantiations are unrolled completely; 0: two stages per trip
-#endif
 #ifndef CRX_SWEEP_MASK
 #define CRX_SWEEP_MASK 1   // 1: the adjoint / forward sweeps run as one predicated region over lanes < NZ; 0: every lane runs them, sink stores (A/B builds)
-#endif
-#ifndef CRX_FWD_ONE_DOT
-#define CRX_FWD_ONE_DOT 1   // forward sweep: one lane-specific dot product per lane and stage (0: state and input chains in every lane; A/B builds)
 #endif
 #ifndef CRX_SWEEP_LOCAL_LANE
 // bit 0: forward sweep, bit 1: adjoint sweep.  The forward sweep alone removes the scratch frame.  (A build of a later source state with BOTH
 // failed tests/test_gpu_parity.py::test_fuzz_descriptors on <2,24,6,0> -- e_d of the second iteration off by 3 % -- while either one alone, the
 // unmasked sweeps, the v_readlane sweeps and a build with s_barrier at every SYNC passed: not understood)
 #define CRX_SWEEP_LOCAL_LANE 1
-#endif
-#ifndef CRX_STAGE_FENCE
-#define CRX_STAGE_FENCE 1
-#endif
-#ifndef CRX_RIC_UNROLL
-#define CRX_RIC_UNROLL 0   // stages of the Riccati backward sweep per trip of its loop in the fixed-horizon instantiations; 0 = all of them
-#endif
-#ifndef CRX_NFIX
-#define CRX_NFIX 1   // 0: every launch reads the horizon from its arguments (A/B builds)
-#endif
-#ifndef CRX_DEG6
-#define CRX_DEG6 1   // 0: every CBF launch takes the general-exponent instantiation (A/B builds)
-#endif
-#ifndef CRX_T_PAD
-#define CRX_T_PAD 0
-#endif
-#ifndef CRX_MASK_FMA
-#define CRX_MASK_FMA 1   // [r6] Riccati sweep: "add x on the lanes of a set" as fma(mask, x, t) with a 0 / 1 lane mask kept in registers instead of v_cndmask pairs + add (0: selects; A/B builds)
-#endif
-#ifndef CRX_H_MIRROR
-#define CRX_H_MIRROR 0   // 1: the H phase of the Riccati sweep stores the upper triangle of H as well, as up to round 6 (A/B builds)
-#endif
-#ifndef CRX_HUU_FIRST
-#define CRX_HUU_FIRST 1   // [r6] update phase of the Riccati sweep: the loads of Huu are issued before the other operands (0: the scheduler's order; A/B builds)
-#endif
-#ifndef CRX_PT_REG
-#define CRX_PT_REG 1   // [r6] Riccati sweep of the 0- / 1-obstacle instantiations: (P | p) in registers, T by half-row broadcast-FMAs (0: P through LDS; A/B builds)
-#endif
-#ifndef CRX_SLIM
-#define CRX_SLIM 1 /* make EXTRA=-DCRX_SLIM=0: the full LDS layout for every instantiation (A/B builds, tools/ab_slim.sh) */
 #endif
 #define MAXF 12 /* filter entries (reset at every barrier update; when full, further entries are dropped) */
 
@@ -159,11 +122,7 @@ __device__ __forceinline__ double interp_lin(const double* xs, const double* ys,
 #define LOADS_DONE() __builtin_amdgcn_sched_barrier(0)
 // end of a stage of an UNROLLED sweep [r4]: without it the scheduler lifts the loads of all later stages to the top of the sweep and the
 // registers they occupy are paid for in scratch (a wave writes its spills once: 100 B per lane were x8 the algorithmic bytes written of a cfg2 launch)
-#if CRX_STAGE_FENCE
 #define STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define STAGE_FENCE() ((void)0)
-#endif
 
 // row table entries (unsigned 16-bit): index into Z / dZ in bits 0..12 (<= 25 * 14 coordinates), flags above
 #define RIV_SIMPLE (1 << 13) /* table-driven row that is present: c = +-(z[iv] - bound) */
@@ -201,7 +160,7 @@ struct Lay {
     // table entry, the rows of a coordinate and the triangle map from arithmetic -- and the curvature table G shares the
     // storage of the feedback gains Kk (G lives from first_order to assemble_newton, Kk from the backward to the forward
     // sweep).  Same operations on the same operands in the same order: results identical to the full layout bit for bit.
-    static constexpr bool SLIM = CRX_SLIM && NOBS == 3 && NMAX == 20;   // the other 3-obstacle instantiations are register-bound at 4 per CU either way
+    static constexpr bool SLIM = NOBS == 3 && NMAX == 20;   // the other 3-obstacle instantiations are register-bound at 4 per CU either way
     static constexpr int MRS = SLIM ? 0 : MR;        // length of the per-row arrays a slim layout does without
     static constexpr int rsig = rtt + MR;            // Sigma = nu/t                               (full layout only)
     static constexpr int rw = rsig + MRS;            // w = nu - mu/t + Sigma*(c - t)              (full layout only)
@@ -226,9 +185,9 @@ struct Lay {
     // 28 412 -> 27 164 B; its residency stays at four per CU, the register file's limit: 296 registers, and a floor of two
     // waves per SIMD would park 92 of them).
     static constexpr int HS = NZ + 1;                // row stride of H: column NZ is the gradient hv (odd strides for NZ = 8, 10, 12, 14)
-    // row stride of T (A/B builds, VERDICT r5 item 6: -DCRX_T_PAD=1 pads the even strides of the obstacle layouts to odd ones against LDS bank conflicts of
-    // the T stores; measured round 6: profiles/r06_pmc_issue.txt)
-    static constexpr int TS = NZ + ((CRX_T_PAD && NOBS > 0 && (NZ % 2 == 0)) ? 1 : 0);
+    // row stride of T (padding the even strides of the obstacle layouts to odd ones against LDS bank conflicts of the T stores was measured in
+    // round 6 -- no effect, identical bits: profiles/r06_pmc_issue.txt)
+    static constexpr int TS = NZ;
     static constexpr bool PT_ALIAS = NX * NX + NX + NX * TS <= MR, H_ALIAS = NZ * HS <= NV;
     static constexpr int WORK = kS + (NOBS ? 2 * NMAX : 0);
     static constexpr int P = PT_ALIAS ? rdt : WORK;
@@ -781,7 +740,7 @@ __device__ __forceinline__ void assemble_newton(double* sm, const int* si, const
 // of the free initial components (sigma_0).
 // [r6] REG = 1: the same sweep on the SECOND set of work arrays (Lay::P2 ..: the speculating wave of crx_solve_kernel<.., SPEC = 1>); CVX: the caller may
 // ask for the convexified matrix (`convex`: the reverse-convex part kS / kE of the CBF curvature read as zero -- the one-wave kernel zeroes it in LDS
-// instead, which two concurrent sweeps cannot).  <.., 0, false> is the code of rounds 1-5, operation for operation.
+// instead, which two concurrent sweeps cannot).
 // KEEPF [r6]: the factor of every stage's Huu (unit-lower L, reciprocal pivots) is left behind in the stage's slice of Hd -- consumed by this stage's H
 // phase, rewritten by the next assemble_newton -- for riccati_backward_vec, the second solve of the predictor-corrector iteration.
 template <int NOBS, int NMAX, int UNR = 1, int REG = 0, bool CVX = false, bool KEEPF = false>
@@ -802,7 +761,7 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
     // between the update and the T phase, one of the three of a stage, is gone; the sigma column of P goes from the update phase straight into T.
     // Same operations on the same operands in the same order as the LDS form: identical bits (tools/cbf_ab.py).  hv = M'p + hg is formed in the
     // DPP row that holds p (lanes 48 ..).  The NX + 1 feedback columns take the lanes the map leaves free (NX = 7: lanes 8 g + 7; NX = 6: 56 .. 62).
-    constexpr bool PTR = CRX_PT_REG && ROWDPP<L> && L::UCNT == 1 && NX <= 7;
+    constexpr bool PTR = ROWDPP<L> && L::UCNT == 1 && NX <= 7;
     constexpr bool PREG = !PTR && ROWDPP<L> && L::UCNT == 1;
     constexpr int PVF = (NX * 8) & 15;   // position of p[0] inside its DPP row (row 3 for NX = 6 and 7)
     static_assert(!PTR || (NX * 8) / 16 == 3, "p sits in DPP row 3, where hv is formed");
@@ -849,7 +808,7 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
     constexpr bool FULL = NZ * NZ <= WAVE;
     constexpr int NTRI = FULL ? NZ * NZ : NZ * (NZ + 1) / 2;
     constexpr int HCNT = (NTRI + WAVE - 1) / WAVE;
-    int hr[HCNT], ha[HCNT], hst[HCNT], hst2[HCNT];
+    int hr[HCNT], ha[HCNT], hst[HCNT];
 #pragma unroll
     for (int q = 0; q < HCNT; q++) {
         const int e0 = lane + q * WAVE;
@@ -858,7 +817,6 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
         else if constexpr (L::SLIM) tri_decode(e, hr[q], ha[q]);
         else { const int pk = si[L::triH + e]; hr[q] = pk >> 8; ha[q] = pk & 255; }
         hst[q] = SINK(e0 < NTRI, oH + hr[q] * HS + ha[q]);
-        hst2[q] = SINK(CRX_H_MIRROR && !FULL && e0 < NTRI, oH + ha[q] * HS + hr[q]);
     }
     const bool hvl = PTR ? (lane >= 48 && lane < 48 + NZ) : lane < NZ;   // the lanes that form hv (PTR: in the DPP row of p)
     const int lz = hvl ? (PTR ? lane - 48 : lane) : 0;
@@ -910,9 +868,9 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
     // [NP, NP+NX+1) one feedback column each (<= 64 lanes for NX <= 9: one pass; the six-obstacle instantiation takes two [r4])
     constexpr int NP = NX * (NX + 1) / 2 + NX, UCNT = L::UCNT;
     int yiA[UCNT], yjA[UCNT], s0A[UCNT], pst1[UCNT], pst2[UCNT], kstr[UCNT], kstep[UCNT], kst[UCNT];
-    bool exSl[UCNT], exEl[UCNT];
     // [r6] 0 / 1 lane masks: t + x on the lanes of a set, t on the others, is fma(mask, x, t) -- one rounding of the same sum (x finite: 0 * x = 0) --
     // instead of two v_cndmask_b32 and an add per use and stage
+    bool exSl[UCNT], exEl[UCNT];   // (the lane sets of the two masks below)
     double mSl[UCNT], mEl[UCNT], mdg[HCNT];
 #pragma unroll
     for (int q = 0; q < HCNT; q++) mdg[q] = hr[q] == ha[q] ? 1.0 : 0.0;
@@ -935,7 +893,7 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
         // [r6] H(ui, uj) is read from the LOWER triangle (uj >= ui), like every other operand of the phase: the H phase need not mirror its entries
         // (one LDS store per pass and stage).  The planner's H is a full matrix, every entry its own sum: its (ui, uj) stays where it was.
         yiA[q] = oH + NX * HS + ui; yjA[q] = oH + NX * HS + ujj;
-        s0A[q] = (FULL || CRX_H_MIRROR) ? oH + ui * HS + ujj : seli(gcol, oH + ui * HS + ujj, oH + uj * HS + ui);
+        s0A[q] = FULL ? oH + ui * HS + ujj : seli(gcol, oH + ui * HS + ujj, oH + uj * HS + ui);
         pst1[q] = SINK(isP, seli(gcol, opv + ui, oP + ui * NX + uj));
         pst2[q] = SINK(isP, seli(gcol, opv + ui, oP + uj * NX + ui));
         kstr[q] = seli(isK, seli(gcol, 1, NX), 0); kstep[q] = seli(isK, seli(gcol, NU, NU * NX), 0);
@@ -1034,8 +992,7 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
 #pragma unroll
                 for (int i = 0; i < NX; i++) t += mH[q][i] * tc[q][i];
                 const double dg = hd[q] + sel(r >= NX || (k == 0 && r >= 6), dw, 0.0);
-                if constexpr (CRX_MASK_FMA) t = fma(mdg[q], dg, t);
-                else t += sel(r == a, dg, 0.0);
+                t = fma(mdg[q], dg, t);
                 if (NOBS) {
 #pragma unroll
                     for (int o = 0; o < NOBS; o++) t += rs[o] * jr[q][o] * ja[q][o];
@@ -1053,10 +1010,7 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
                 for (int i = 0; i < NX; i++) hvs += mz[i] * pvv[i];
             }
 #pragma unroll
-            for (int q = 0; q < HCNT; q++) {
-                LD(hst[q]) = hs[q];
-                if (!FULL && CRX_H_MIRROR) LD(hst2[q]) = hs[q];
-            }
+            for (int q = 0; q < HCNT; q++) LD(hst[q]) = hs[q];
             LD(hvst) = hvs;
         }
         SYNC();
@@ -1074,7 +1028,7 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
                 for (int b2 = 0; b2 <= a; b2++) Lf[a][b2] = LD(oH + (NX + a) * HS + NX + b2);
             // (Huu FIRST: the pivot chain -- the longest of the phase -- starts when these are back, while the other loads are in flight; left alone the
             // scheduler issues them fourth)
-            if constexpr (CRX_HUU_FIRST) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int q = 0; q < UCNT; q++) {
 #pragma unroll
@@ -1129,8 +1083,7 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
                 // (yj carries MINUS D^{-1} y from here on: the feedback -L^{-T} D^{-1} y is then stored as it comes out of the back substitution --
                 // negation commutes with every rounding below, the bits are those of the negate-at-the-store form [r4])
                 for (int a = 0; a < NU; a++) { yj[q][a] *= -rD[a]; t[q] = fma(yi[q][a], yj[q][a], t[q]); }
-                if constexpr (CRX_MASK_FMA) t[q] = fma(mSl[q], exS, fma(mEl[q], exE, t[q]));   // (at most one of the two masks is set)
-                else t[q] += sel(exSl[q], exS, sel(exEl[q], exE, 0.0));
+                t[q] = fma(mSl[q], exS, fma(mEl[q], exE, t[q]));   // (at most one of the two masks is set)
                 if constexpr (PTR) {
                     pn = t[0];                     // (P_new | p_new) stays in registers; its sigma column is the next stage's sigma_{k+1} column of T
                     if (NOBS) LD(SINK(isPm && c8 == 6, oT + g8 * L::TS + NX + 2)) = pn;
@@ -1279,7 +1232,7 @@ __device__ __forceinline__ void riccati_forward(double* sm, const Ctx& c) {
     // the interior-point loop and, at the register limit of two waves per SIMD, parked in scratch (one reload each per iteration) [r4]
     if (NOBS > 0) asm volatile("" : "+v"(lane));
 #endif
-    if constexpr (ROWDPP<L> && CRX_SWEEP_MASK && CRX_FWD_ONE_DOT && NOBS > 0) {   // (planner instantiations: measured 1.5 % slower with it, cfg3)
+    if constexpr (ROWDPP<L> && CRX_SWEEP_MASK && NOBS > 0) {   // (planner instantiations: measured 1.5 % slower with it, cfg3)
         // [r4] ONE dot product per lane and stage.  A state lane i < NX needs x_{k+1}[i] = M[i][0..NX) x_k + M[i][NX..) du_k, an input lane
         // NX + a needs du_k[a] = kff_k[a] + K_k[a] x_k: both are `c0 + coef . x_k` with lane-specific (c0, coef) -- the coefficients come
         // from a lane-specific ADDRESS (row i of M, every stage; row a of K_k), not from a select, so the sweep no longer runs both
@@ -1612,7 +1565,7 @@ __device__ __forceinline__ void planner_fallback(double* sm, const crx_kparams& 
 // measured in round 1 and rejected: spills inside the loop).
 #ifndef CRX_PLANNER_WAVES
 // Planner instantiation <0,12>: 3 = a third resident wave per SIMD (193 -> 168 registers, 21 dwords parked in scratch), which
-// lifts the residency from 8 (register-bound) to 11 problems per CU (LDS-bound).  Measured round 2 (tools/ab_planner_waves.sh):
+// lifts the residency from 8 (register-bound) to 11 problems per CU (LDS-bound).  Measured round 2 (HISTORY.md, round 2):
 // 4096 QPs +0.4 %, 65536 QPs (the cfg5 shard) +10.6 %.  (Round 1 had measured -4 % at 4096 with the allocator's choice of
 // spills then; make EXTRA=-DCRX_PLANNER_WAVES=1 restores the uncapped build.)
 #define CRX_PLANNER_WAVES 3
@@ -1627,7 +1580,7 @@ __device__ __forceinline__ void planner_fallback(double* sm, const crx_kparams& 
 #define CRX_GEN_WAVES 0   // > 0: every instantiation of this translation unit is held to that many waves per SIMD (crx_kernels_gen.hip: 2 = 256 registers, no AGPRs)
 #endif
 template <int NOBS, int NMAX> struct MinWaves {
-    static constexpr int v = CRX_GEN_WAVES ? CRX_GEN_WAVES : (((NOBS == 1 || (CRX_W2_FLOOR && NOBS == 2)) && NMAX == 12) ? CRX_OBS1_WAVES : ((NOBS == 0 && NMAX == 12) ? CRX_PLANNER_WAVES : 1));
+    static constexpr int v = CRX_GEN_WAVES ? CRX_GEN_WAVES : ((NOBS == 1 && NMAX == 12) ? CRX_OBS1_WAVES : ((NOBS == 0 && NMAX == 12) ? CRX_PLANNER_WAVES : 1));
 };
 
 // DEG [r3]: the exponent of the super-ellipse as a compile-time constant (6 = the reference's literal, control.py:528 / :312; 0 = read
@@ -1636,10 +1589,10 @@ template <int NOBS, int NMAX> struct MinWaves {
 // stand for -- same association, same bits, no branch in the row passes (a run-time `if (p == 6)` there was measured 3 % SLOWER).
 // NFIX [r3]: the horizon as a compile-time constant (10, 12 or 20: the reference's defaults and the BASELINE configs; 0 = read kp.N).
 // The trip counts of the stage loops, the number of row passes (m = N NR + NOBS rows over 64 lanes) and the stage addresses become
-// immediates: cfg2 0.942 -> 0.868 ms per 256 NLPs (+8.6 %), cfg3 +8 %, the cfg5 shard +6 %, cfg4 +3.7 % (tools/gpu_round3_aa.sh), same
+// immediates: cfg2 0.942 -> 0.868 ms per 256 NLPs (+8.6 %), cfg3 +8 %, the cfg5 shard +6 %, cfg4 +3.7 % (HISTORY.md, round 3), same
 // operations in the same order.
-template <int NFIX> struct SweepUnroll { static constexpr int v = NFIX == 0 ? 1 : (CRX_SWEEP_UNROLL ? NFIX : 2); };   // forward / adjoint sweeps
-template <int NOBS, int NFIX> struct RicUnroll { static constexpr int v = NFIX == 0 ? 1 : (CRX_RIC_UNROLL == 0 ? NFIX : CRX_RIC_UNROLL); };
+// The stage loops of a fixed-horizon instantiation -- the Riccati backward sweep, the forward and adjoint sweeps -- are unrolled completely.
+template <int NFIX> constexpr int StageUnroll = NFIX == 0 ? 1 : NFIX;
 // SPEC [r6]: 1 = TWO waves per problem (a 128-thread workgroup).  Wave 0 runs the solve as the one-wave kernel does; wave 1 sleeps at a workgroup
 // barrier and, at every Newton system, factorises the reduced Hessian with the NEXT entry of the inertia-correction schedule (the convexified matrix
 // on the crash path, then IPOPT's delta_w sequence) in its own work arrays while wave 0 tries the current one; the first success in schedule order
@@ -1708,7 +1661,7 @@ crx_solve_kernel(const crx_kparams kp) {
                 const int cmd = __builtin_amdgcn_readfirstlane((int)LD(L::ctl));
                 if (cmd == 0) break;
                 bool ok1 = false;
-                if (cmd == 1) ok1 = riccati_backward<NOBS, NMAX, RicUnroll<NOBS, NFIX>::v, 1, true>(sm, si, c1, LD(L::ctl + 1), nullptr, LD(L::ctl + 2) != 0.0);
+                if (cmd == 1) ok1 = riccati_backward<NOBS, NMAX, StageUnroll<NFIX>, 1, true>(sm, si, c1, LD(L::ctl + 1), nullptr, LD(L::ctl + 2) != 0.0);
                 if (lane == 0) LD(L::ctl + 3) = ok1 ? 1.0 : 0.0;
                 __syncthreads();
             }
@@ -2082,15 +2035,15 @@ crx_solve_kernel(const crx_kparams kp) {
         const int lane = c.lane;   // shadows the kernel's `lane` inside the loop body (see the loop below)
 #endif
         const double sd = fmax(smax, nus / fmax(mact, 1.0)) / smax;
-        const double e_du = dual_infeasibility<NOBS, NMAX, (SweepUnroll<NFIX>::v > 2 ? SweepUnroll<NFIX>::v : 1)>(sm, c);
+        const double e_du = dual_infeasibility<NOBS, NMAX, (StageUnroll<NFIX> > 2 ? StageUnroll<NFIX> : 1)>(sm, c);
         E0 = fmax(e_du / sd, fmax(e_p, cmax / sd));
         if (E0 <= o.tol && e_du <= o.dual_inf_tol && e_p <= o.constr_viol_tol && cmax <= o.compl_inf_tol) { status = 0; break; }   // IPOPT's complete test
         if (it >= o.max_iter) break;
         const double mu_k = gap / fmax(mact, 1.0);
         // ---- predictor: the affine-scaling direction ---------------------------------------------------
         assemble_newton<NOBS, NMAX>(sm, si, c, 0.0);
-        if (!riccati_backward<NOBS, NMAX, RicUnroll<NOBS, NFIX>::v, 0, false, true>(sm, si, c, 0.0)) break;   // (a convex QP: cannot happen short of overflow)
-        riccati_forward<NOBS, NMAX, SweepUnroll<NFIX>::v>(sm, c);
+        if (!riccati_backward<NOBS, NMAX, StageUnroll<NFIX>, 0, false, true>(sm, si, c, 0.0)) break;   // (a convex QP: cannot happen short of overflow)
+        riccati_forward<NOBS, NMAX, StageUnroll<NFIX>>(sm, c);
         double dta[RP], dna[RP], rpm = 0.0, rdm = 0.0;
 #pragma unroll
         for (int q_ = 0; q_ < RP; q_++) {
@@ -2151,8 +2104,8 @@ crx_solve_kernel(const crx_kparams kp) {
                 LD(SINK(ev && !(k == N && a >= NX), L::hg + e)) = g0 + sel(rl >= 0, dl, 0.0) - sel(rh >= 0, dh, 0.0);
             }
             SYNC();
-            riccati_backward_vec<NOBS, NMAX, SweepUnroll<NFIX>::v>(sm, c);
-            riccati_forward<NOBS, NMAX, SweepUnroll<NFIX>::v>(sm, c);
+            riccati_backward_vec<NOBS, NMAX, StageUnroll<NFIX>>(sm, c);
+            riccati_forward<NOBS, NMAX, StageUnroll<NFIX>>(sm, c);
             rpm = 0.0; rdm = 0.0;
 #pragma unroll
             for (int q_ = 0; q_ < RP; q_++) {
@@ -2238,14 +2191,6 @@ crx_solve_kernel(const crx_kparams kp) {
     // of the sweeps (model-matrix rows, lane maps: ~200 registers) are hoisted out of BOTH loops and stay live across
     // the restart / restoration code, whose own temporaries then push the kernel past 256 registers.
     asm volatile("" ::: "memory");
-#if CRX_OPAQUE_OUTER
-    // [r4] ... and the lane index is made opaque once per PASS of this outer loop (obstacle instantiations): what the sweeps derive
-    // from it is still hoisted out of the interior-point loop (they are issue-bound: the hoisted maps are worth 4..5 %), but only to
-    // the top of the pass, not out of the outer loop -- so it is dead while the crash restart at the bottom of the pass runs.
-    // Without: +21 registers and 64 B of scratch per lane for <1,12>, 164 B for <3,20>.
-    if (NOBS > 0) asm volatile("" : "+v"(c.lane));
-    const int lane = c.lane;   // shadows the kernel's `lane` inside the pass
-#endif
 
     for (;; it++) {
         long long tc0 = CLK();
@@ -2254,11 +2199,11 @@ crx_solve_kernel(const crx_kparams kp) {
         // from it (which entry a lane owns, LDS addresses, the selects of the row / coordinate passes) is recomputed inside
         // the iteration instead of being hoisted out of the interior-point loop and kept alive across it.  <0,12>: 168 VGPRs +
         // 116 B of scratch per lane -> 160 and NO scratch (the parked dwords were x6..10 the algorithmic HBM traffic of the
-        // planner launches); cfg3 +4.7 %, cfg5 +1.7 % (tools/gpu_round3_a.sh).  The obstacle instantiations run one wave per
+        // planner launches); cfg3 +4.7 %, cfg5 +1.7 % (HISTORY.md, round 3).  The obstacle instantiations run one wave per
         // SIMD and are bound by instruction ISSUE (one instruction per four clocks and wave: profiles/r03_pmc_issue.txt); the
         // recomputation is ~19 % more VALU instructions there and costs 4..5 % (cfg2, cfg4, races) although it frees 40..140
         // registers -- they keep the hoisted maps.  (With the barrier, the full-layout 3-obstacle instantiations also produced
-        // a kernel that faults on MI355X / ROCm 7.0.2 -- not understood; found by the GPU suite, tools/gpu_round3_b.sh.)
+        // a kernel that faults on MI355X / ROCm 7.0.2 -- not understood; found by the GPU suite, HISTORY.md round 3.)
         if (NOBS == 0 || CRX_OPAQUE_LANE >= 2) asm volatile("" : "+v"(c.lane));   // (2: every instantiation -- the A/B build of the fault hunt, tools/variants.sh)
         const int lane = c.lane;   // shadows the kernel's `lane` inside the loop body
 #endif
@@ -2266,7 +2211,7 @@ crx_solve_kernel(const crx_kparams kp) {
         double e_c = cmax;
         const double sd = fmax(smax, nus / fmax(mact, 1.0)) / smax;
         long long tc1 = CLK();
-        const double e_du = dual_infeasibility<NOBS, NMAX, (SweepUnroll<NFIX>::v > 2 ? SweepUnroll<NFIX>::v : 1)>(sm, c);
+        const double e_du = dual_infeasibility<NOBS, NMAX, (StageUnroll<NFIX> > 2 ? StageUnroll<NFIX> : 1)>(sm, c);
         const double e_d = e_du / sd;
         long long tc2 = CLK();
         e_c /= sd;
@@ -2339,7 +2284,7 @@ crx_solve_kernel(const crx_kparams kp) {
                 const bool post = nvalid && kp.spec_idle == 0;      // (spec_idle: diagnostics -- the second wave is never asked: the schedule runs one attempt at a time)
                 if (lane == 0) { LD(L::ctl) = post ? 1.0 : 2.0; LD(L::ctl + 1) = ndw; LD(L::ctl + 2) = ncz ? 1.0 : 0.0; }
                 __syncthreads();
-                ok = riccati_backward<NOBS, NMAX, RicUnroll<NOBS, NFIX>::v, 0, true>(sm, si, c, sdw, tsub, cz != 0);
+                ok = riccati_backward<NOBS, NMAX, StageUnroll<NFIX>, 0, true>(sm, si, c, sdw, tsub, cz != 0);
                 __syncthreads();
                 if (ok) { dw = sdw; used_convex = cz; break; }
                 dw = ndw;
@@ -2361,7 +2306,7 @@ crx_solve_kernel(const crx_kparams kp) {
             }
         } else
         for (int tries = 0, convex = (NOBS > 0 && crash && !used_convex) ? 0 : 1;; ) {
-            ok = riccati_backward<NOBS, NMAX, RicUnroll<NOBS, NFIX>::v>(sm, si, c, dw, tsub);
+            ok = riccati_backward<NOBS, NMAX, StageUnroll<NFIX>>(sm, si, c, dw, tsub);
             if (ok) break;
             if (NOBS && !convex) {
                 used_convex = 1;
@@ -2381,7 +2326,7 @@ crx_solve_kernel(const crx_kparams kp) {
         if (dw != 0.0) dw_last = dw;
         cvx_run = used_convex ? cvx_run + 1 : 0;
         long long tc5 = CLK();
-        riccati_forward<NOBS, NMAX, SweepUnroll<NFIX>::v>(sm, c);
+        riccati_forward<NOBS, NMAX, StageUnroll<NFIX>>(sm, c);
         long long tc6 = CLK();
         // ---- row steps, step lengths, merit pieces ---------------------------------------------------
         // fraction-to-the-boundary without per-row divisions: a = min(1, tau / max_j(-d_j / v_j))
@@ -2658,7 +2603,7 @@ crx_solve_kernel(const crx_kparams kp) {
         }
     }
     double Eout = E0;
-    if (CRX_KKT_DIAG && kp.kkt_unscaled && status == 0) {
+    if (kp.kkt_unscaled && status == 0) {
         // diagnostics (crx_debug_kkt_unscaled): the converged exit is taken right after dual_infeasibility(), so ga holds the reduced Lagrangian gradient
         // of the returned iterate; the row arrays hold its slacks, multipliers and (scaled) row values.  Outside every loop: no register is carried for it.
         // kkt_unscaled = 1: the max of the three, 2: dual infeasibility, 3: constraint violation, 4: complementarity
@@ -2675,10 +2620,10 @@ crx_solve_kernel(const crx_kparams kp) {
     }
 }
 
-// This file is compiled TWICE (Makefile): as it stands for the planner instantiations <0, *> and everything else in it, and
-// through crx_kernels_obs.hip (CRX_TU_OBSTACLES) for the obstacle instantiations <1..3, *> alone -- with the machine scheduler's
+// The tuned instantiations are compiled in TWO units (Makefile): this file as it stands for the planner instantiations <0, *> and everything else
+// in it, and crx_kernels_obs.hip (CRX_TU_OBSTACLES) for the obstacle instantiations <1..3, *> alone -- with the machine scheduler's
 // iterative-ilp strategy, which is worth +3.7 % on BASELINE configs[1] (0.991 -> 0.956 ms per 256 NLPs) and +7 % on configs[3] to
-// the obstacle kernels and costs the planner kernels 1 % (tools/gpu_round3_l.sh: max-ilp, max-memory-clause, iterative-minreg
+// the obstacle kernels and costs the planner kernels 1 % (HISTORY.md, round 3: max-ilp, max-memory-clause, iterative-minreg
 // and the occupancy / latency bias were measured beside it).  Same arithmetic either way: the schedule does not re-associate.
 #ifndef CRX_TU_OBSTACLES
 // ------------------------------------------------------------------------------------------------
@@ -2752,7 +2697,83 @@ static hipError_t launch_t(const crx_kparams& kp, hipStream_t st) {
 #endif
     return hipGetLastError();
 }
-#ifdef CRX_TU_SPEC
+// resident single-wave workgroups per CU of an instantiation: the runtime's answer, i.e. min over the LDS and the register file (the fixed-horizon
+// instantiations are other kernels than the general ones, with their own register counts)
+template <int NOBS, int NMAX, int DEG, int NFIX>
+static int occ_t() {
+    int n = 0;
+#if CRX_STATIC_LDS
+    const size_t bytes = 0;   // the layout is static LDS of the kernel: the runtime counts it by itself
+#else
+    const size_t bytes = Lay<NOBS, NMAX>::BYTES;
+    if (hipFuncSetAttribute((const void*)crx_solve_kernel<NOBS, NMAX, DEG, NFIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return -1;
+#endif
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, crx_solve_kernel<NOBS, NMAX, DEG, NFIX>, WAVE, bytes) != hipSuccess) return -1;
+    return n;
+}
+
+// WHICH instantiation serves a problem is decided once per translation unit, by select_inst(nobs_template, N, degree, f): it calls f with the
+// instantiation as a type, Inst<NOBS, NMAX, DEG, NFIX>, and returns false where the unit holds none for the problem.  Launching, the occupancy
+// query and the LDS figure are callables over that one selection, so what bench.py reports as resident is the kernel that runs.  The units:
+//   this file as it stands     the planner instantiations <0, *> at the horizons of CRX_NFIX_LIST, the selection kernel, the entry points
+//   crx_kernels_obs.hip        <1..3, *>, exponent 6, at the horizons of CRX_NFIX_LIST
+//   crx_kernels_gen.hip [r5]   everything else -- run-time horizon (NFIX = 0), run-time exponent (DEG = 0), the generic 4..6-obstacle ones -- built
+//                              conservatively: no inline-assembly DPP, nothing lane-derived hoisted out of the interior-point loop
+//   crx_kernels_spec.hip [r6]  the two two-wave kernels; crx_api.hip routes a launch there by itself
+// A launch walks main -> obstacle -> general unit until one holds its instantiation.
+template <int NOBS, int NMAX, int DEG, int NFIX> struct Inst { static constexpr int nobs = NOBS, nmax = NMAX, deg = DEG, nfix = NFIX; };
+// layout class of a horizon: <= 12 -> 12; <= 20 with three obstacle slots -> 20 (the slim layout, four problems per CU); otherwise CRX_MAX_N
+constexpr int horizon_class(int nobs, int N) { return N <= 12 ? 12 : ((nobs == 3 && N <= 20) ? 20 : CRX_MAX_N); }
+// fixed-horizon (tuned) instantiations [r6: a BUILD PARAMETER].  CRX_NFIX_LIST -- `make NFIX_LIST=10,12,16,20` -- names the horizons that get an
+// instantiation with the horizon as a compile-time constant (straight-line sweeps, immediates for every stage address: 1.5 .. 2x the general unit's
+// speed, profiles/r06_variants.txt) for every obstacle count 0 .. 3; any other horizon runs on the general unit.  Default: 10 (the reference's
+// defaults: utils/base.py:281, :390), 12 (BASELINE configs[1], [2], [4]), 20 (configs[3]).  Layout class of a horizon: <= 12 -> 12; <= 20 with three
+// obstacle slots -> 20 (the slim layout, four problems per CU); otherwise CRX_MAX_N.  Budget per entry: one kernel per obstacle count (two for the
+// planner: crx_ipm_opts.qp_method), ~100 KB of code and 15 .. 40 s of build time each; registers / LDS as its layout class (DESIGN.md 5.1 table).
+#ifndef CRX_NFIX_LIST
+#define CRX_NFIX_LIST 10, 12, 20
+#endif
+#ifndef CRX_NFIX_LIST
+#define CRX_NFIX_LIST 10, 12, 20
+#endif
+template <int NOBS, int DEG, int... NFS, class F>
+static bool select_fixed(int N, F&& f) {
+    return ((N == NFS ? (f(Inst<NOBS, horizon_class(NOBS, NFS), DEG, NFS>{}), true) : false) || ...);
+}
+// run-time horizon: the smallest layout that holds N
+template <int NOBS, int DEG, class F>
+static void select_class(int N, F&& f) {
+    constexpr int MID = horizon_class(NOBS, 20);   // (CRX_MAX_N for every obstacle count but three)
+    const int cls = horizon_class(NOBS, N);
+    if (cls == 12) f(Inst<NOBS, 12, DEG, 0>{});
+    else if (cls == MID) f(Inst<NOBS, MID, DEG, 0>{});
+    else f(Inst<NOBS, CRX_MAX_N, DEG, 0>{});
+}
+// the general instantiations: the exponent 6 of the reference as a constant for one to three slots, any other read at run time.
+// [r4] Four to six slots (CRX_MAX_OBS = 6: the reference admits any number, control.py:524-562): ONE generic instantiation per horizon class --
+// exponent and horizon read at run time, the Riccati update in two passes, the sigma columns of T in three; the slow path: correct first
+template <class F>
+static bool select_general(int nobs_template, int N, int degree, F&& f) {
+    const bool d6 = degree == 6;
+    switch (nobs_template) {
+        case 0: select_class<0, 0>(N, f); return true;
+        case 1: d6 ? select_class<1, 6>(N, f) : select_class<1, 0>(N, f); return true;
+        case 2: d6 ? select_class<2, 6>(N, f) : select_class<2, 0>(N, f); return true;
+        case 3: d6 ? select_class<3, 6>(N, f) : select_class<3, 0>(N, f); return true;
+        case 4: case 5: case 6: select_class<6, 0>(N, f); return true;
+        default: return false;
+    }
+}
+// the queries (crx_solve_lds_bytes, crx_solve_resident_per_cu*) answer for the reference's exponent whatever the descriptor says, and for the
+// six-slot instantiations when asked about a slot count that has none
+static int query_slots(int nobs_template) { return nobs_template >= 0 && nobs_template <= 3 ? nobs_template : CRX_MAX_OBS; }
+
+hipError_t crx_launch_solve_obs(const crx_kparams& kp, int nobs_template, hipStream_t st);
+int crx_solve_resident_per_cu_obs(int N, int nobs_template);
+hipError_t crx_launch_solve_general(const crx_kparams& kp, int nobs_template, hipStream_t st);
+int crx_solve_resident_per_cu_general(int N, int nobs_template);
+
+#if defined(CRX_TU_SPEC)
 // [r6] crx_kernels_spec.hip: the two-wave (speculating) instantiations of the one-obstacle, degree-6 kernel at the tuned horizons 12 and 10 --
 // BASELINE configs[1] and the reference's default horizon -- and nothing else.  crx_api.hip routes a launch here when it leaves SIMDs idle.
 hipError_t crx_launch_solve_spec(const crx_kparams& kp, hipStream_t st) {
@@ -2763,171 +2784,52 @@ hipError_t crx_launch_solve_spec(const crx_kparams& kp, hipStream_t st) {
     return hipErrorInvalidValue;
 }
 #else
-// [r5] The GENERAL instantiations (run-time horizon NFIX = 0, run-time exponent DEG = 0, the generic 4..6-obstacle ones) live in a third
-// translation unit, crx_kernels_gen.hip, built conservatively: 256 registers and no AGPRs, no inline-assembly DPP,
-// nothing lane-derived hoisted out of the interior-point loop.  This unit and the obstacle unit only hold the tuned fixed-horizon ones.
-hipError_t crx_launch_solve_general(const crx_kparams& kp, int nobs_template, hipStream_t st);
-int crx_solve_resident_per_cu_general(int N, int nobs_template);
-#if !CRX_TU_GENERAL
-// fixed-horizon (tuned) instantiations [r6: a BUILD PARAMETER].  CRX_NFIX_LIST -- `make NFIX_LIST=10,12,16,20` -- names the horizons that get an
-// instantiation with the horizon as a compile-time constant (straight-line sweeps, immediates for every stage address: 1.5 .. 2x the general unit's
-// speed, profiles/r06_variants.txt) for every obstacle count 0 .. 3; any other horizon runs on the general unit.  Default: 10 (the reference's
-// defaults: utils/base.py:281, :390), 12 (BASELINE configs[1], [2], [4]), 20 (configs[3]).  Layout class of a horizon: <= 12 -> 12; <= 20 with three
-// obstacle slots -> 20 (the slim layout, four problems per CU); otherwise CRX_MAX_N.  Budget per entry: one kernel per obstacle count (two for the
-// planner: crx_ipm_opts.qp_method), ~100 KB of code and 15 .. 40 s of build time each; registers / LDS as its layout class (DESIGN.md 5.1 table).
-#ifndef CRX_NFIX_LIST
-#define CRX_NFIX_LIST 10, 12, 20
-#endif
-template <int NOBS, int NF> struct NfixLayout { static constexpr int v = NF <= 12 ? 12 : ((NOBS == 3 && NF <= 20) ? 20 : CRX_MAX_N); };
-template <int NOBS, int DEG, int... NFS>
-static bool launch_fixed(const crx_kparams& kp, hipStream_t st, hipError_t& e) {
-    bool hit = false;
-    (void)((kp.N == NFS ? (e = launch_t<NOBS, NfixLayout<NOBS, NFS>::v, DEG, NFS>(kp, st), hit = true) : false) || ...);
-    return hit;
-}
-// obstacle instantiations: the degree-6 one for the reference's exponent; other exponents (2 / 4 / 8) take the general unit
-template <int NOBS>
-static hipError_t launch_n(const crx_kparams& kp, hipStream_t st) {
-    hipError_t e = hipSuccess;
-    (void)e;
-#if CRX_NFIX
-    if constexpr (NOBS > 0 && CRX_DEG6) {
-        if (kp.degree == 6 && launch_fixed<NOBS, 6, CRX_NFIX_LIST>(kp, st, e)) return e;
-    } else {
-        if (launch_fixed<NOBS, 0, CRX_NFIX_LIST>(kp, st, e)) return e;
-    }
-#endif
-    return crx_launch_solve_general(kp, NOBS, st);
-}
-#endif  // !CRX_TU_GENERAL
-
-// the obstacle instantiations live in the other translation unit
-hipError_t crx_launch_solve_obs(const crx_kparams& kp, int nobs_template, hipStream_t st);
-int crx_solve_resident_per_cu_obs(int N, int nobs_template);
-
 #if CRX_TU_GENERAL
-// horizon class of a general launch: the smallest layout that holds kp.N
-template <int NOBS, int DEG>
-static hipError_t launch_g(const crx_kparams& kp, hipStream_t st) {
-    if (kp.N <= 12) return launch_t<NOBS, 12, DEG, 0>(kp, st);
-    if constexpr (NOBS == 3) {
-        if (kp.N <= 20) return launch_t<3, 20, DEG, 0>(kp, st);
-    }
-    return launch_t<NOBS, CRX_MAX_N, DEG, 0>(kp, st);
-}
-template <int NOBS>
-static hipError_t launch_gd(const crx_kparams& kp, hipStream_t st) {
-    if constexpr (NOBS > 0 && CRX_DEG6) {
-        if (kp.degree == 6) return launch_g<NOBS, 6>(kp, st);
-    }
-    return launch_g<NOBS, 0>(kp, st);
-}
-hipError_t crx_launch_solve_general(const crx_kparams& kp, int nobs_template, hipStream_t st) {
-    switch (nobs_template) {
-        case 0: return launch_gd<0>(kp, st);
-        case 1: return launch_gd<1>(kp, st);
-        case 2: return launch_gd<2>(kp, st);
-        case 3: return launch_gd<3>(kp, st);
-        // [r4] four to six obstacles (CRX_MAX_OBS = 6: the reference admits any number, control.py:524-562): ONE generic instantiation
-        // per horizon class -- exponent and horizon read at run time, the Riccati update in two passes, the sigma columns of T in
-        // three; the slow path: correct first
-        case 4: case 5: case 6: return kp.N <= 12 ? launch_t<6, 12, 0, 0>(kp, st) : launch_t<6, CRX_MAX_N, 0, 0>(kp, st);
-        default: return hipErrorInvalidValue;
-    }
-}
+#define CRX_UNIT(name) name##_general
+template <class F>
+static bool select_inst(int nobs_template, int N, int degree, F&& f) { return select_general(nobs_template, N, degree, f); }
+static hipError_t next_unit_launch(const crx_kparams&, int, hipStream_t) { return hipErrorInvalidValue; }
+static int next_unit_resident(int, int) { return -1; }
 #elif defined(CRX_TU_OBSTACLES)
-hipError_t crx_launch_solve_obs(const crx_kparams& kp, int nobs_template, hipStream_t st) {
+#define CRX_UNIT(name) name##_obs
+template <class F>
+static bool select_inst(int nobs_template, int N, int degree, F&& f) {
+    if (degree != 6) return false;   // (other exponents, 2 / 4 / 8, take the general unit)
     switch (nobs_template) {
-        case 1: return launch_n<1>(kp, st);
-        case 2: return launch_n<2>(kp, st);
-        case 3: return launch_n<3>(kp, st);
-        case 4: case 5: case 6: return crx_launch_solve_general(kp, nobs_template, st);
-        default: return hipErrorInvalidValue;
+        case 1: return select_fixed<1, 6, CRX_NFIX_LIST>(N, f);
+        case 2: return select_fixed<2, 6, CRX_NFIX_LIST>(N, f);
+        case 3: return select_fixed<3, 6, CRX_NFIX_LIST>(N, f);
+        default: return false;
     }
 }
+static hipError_t next_unit_launch(const crx_kparams& kp, int nobs_template, hipStream_t st) { return crx_launch_solve_general(kp, nobs_template, st); }
+static int next_unit_resident(int N, int nobs_template) { return crx_solve_resident_per_cu_general(N, nobs_template); }
 #else
-hipError_t crx_launch_solve(const crx_kparams& kp, int nobs_template, hipStream_t st) {
+#define CRX_UNIT(name) name
+template <class F>
+static bool select_inst(int nobs_template, int N, int, F&& f) { return nobs_template == 0 && select_fixed<0, 0, CRX_NFIX_LIST>(N, f); }
+static hipError_t next_unit_launch(const crx_kparams& kp, int nobs_template, hipStream_t st) { return crx_launch_solve_obs(kp, nobs_template, st); }
+static int next_unit_resident(int N, int nobs_template) { return crx_solve_resident_per_cu_obs(N, nobs_template); }
+#endif
+
+hipError_t CRX_UNIT(crx_launch_solve)(const crx_kparams& kp, int nobs_template, hipStream_t st) {
     if (kp.batch == 0) return hipSuccess;
-    if (nobs_template == 0) return launch_n<0>(kp, st);
-    return crx_launch_solve_obs(kp, nobs_template, st);
+    hipError_t e = hipSuccess;
+    if (select_inst(nobs_template, kp.N, kp.degree, [&](auto i) { e = launch_t<i.nobs, i.nmax, i.deg, i.nfix>(kp, st); })) return e;
+    return next_unit_launch(kp, nobs_template, st);
+}
+int CRX_UNIT(crx_solve_resident_per_cu)(int N, int nobs_template) {
+    int n = 0;
+    if (select_inst(query_slots(nobs_template), N, 6, [&](auto i) { n = occ_t<i.nobs, i.nmax, i.deg, i.nfix>(); })) return n;
+    return next_unit_resident(N, nobs_template);
 }
 
+#ifndef CRX_TU_OBSTACLES
+// LDS bytes of the layout a problem runs in (every instantiation of a horizon class has the same)
 size_t crx_solve_lds_bytes(int N, int nobs_template) {
-    const bool small = N <= 12;
-    switch (nobs_template) {
-        case 0: return small ? Lay<0, 12>::BYTES : Lay<0, CRX_MAX_N>::BYTES;
-        case 1: return small ? Lay<1, 12>::BYTES : Lay<1, CRX_MAX_N>::BYTES;
-        case 2: return small ? Lay<2, 12>::BYTES : Lay<2, CRX_MAX_N>::BYTES;
-        case 3: return small ? Lay<3, 12>::BYTES : (N <= 20 ? Lay<3, 20>::BYTES : Lay<3, CRX_MAX_N>::BYTES);
-        default: return small ? Lay<6, 12>::BYTES : Lay<6, CRX_MAX_N>::BYTES;
-    }
-}
-
-#endif  // translation unit
-
-// resident single-wave workgroups per CU of the instantiation that WOULD RUN (N, nobs_template) with the reference's exponent: the
-// runtime's answer, i.e. min over the LDS and the register file, for the same (DEG, NFIX) selection as launch_d / launch_h -- the
-// fixed-horizon instantiations are other kernels than the general ones, with their own register counts
-template <int NOBS, int NMAX, int NFIX>
-static int occ_t() {
-    int n = 0;
-    constexpr int DEG = (NOBS > 0 && NOBS <= 3 && CRX_DEG6) ? 6 : 0;   // (the generic six-obstacle instantiation reads the exponent at run time)
-#if CRX_STATIC_LDS
-    const size_t bytes = 0;   // the layout is static LDS of the kernel: the runtime counts it by itself
-#else
-    const size_t bytes = Lay<NOBS, NMAX>::BYTES;
-    if (hipFuncSetAttribute((const void*)crx_solve_kernel<NOBS, NMAX, DEG, NFIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return -1;
-#endif
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, crx_solve_kernel<NOBS, NMAX, DEG, NFIX>, WAVE, bytes) != hipSuccess) return -1;
-    return n;
-}
-#if CRX_TU_GENERAL
-template <int NOBS>
-static int occ_g(int N) {
-    if (N <= 12) return occ_t<NOBS, 12, 0>();
-    if constexpr (NOBS == 3) {
-        if (N <= 20) return occ_t<3, 20, 0>();
-    }
-    return occ_t<NOBS, CRX_MAX_N, 0>();
-}
-int crx_solve_resident_per_cu_general(int N, int nobs_template) {
-    switch (nobs_template) {
-        case 0: return occ_g<0>(N);
-        case 1: return occ_g<1>(N);
-        case 2: return occ_g<2>(N);
-        case 3: return occ_g<3>(N);
-        default: return N <= 12 ? occ_t<6, 12, 0>() : occ_t<6, CRX_MAX_N, 0>();
-    }
-}
-#else
-template <int NOBS, int... NFS>
-static bool occ_fixed(int N, int& n) {
-    bool hit = false;
-    (void)((N == NFS ? (n = occ_t<NOBS, NfixLayout<NOBS, NFS>::v, NFS>(), hit = true) : false) || ...);
-    return hit;
-}
-template <int NOBS>
-static int occ_n(int N) {
-#if CRX_NFIX
-    int n = 0;
-    if (occ_fixed<NOBS, CRX_NFIX_LIST>(N, n)) return n;
-#endif
-    return crx_solve_resident_per_cu_general(N, NOBS);
-}
-#endif
-#if CRX_TU_GENERAL
-#elif defined(CRX_TU_OBSTACLES)
-int crx_solve_resident_per_cu_obs(int N, int nobs_template) {
-    switch (nobs_template) {
-        case 1: return occ_n<1>(N);
-        case 2: return occ_n<2>(N);
-        case 3: return occ_n<3>(N);
-        default: return crx_solve_resident_per_cu_general(N, nobs_template);
-    }
-}
-#else
-int crx_solve_resident_per_cu(int N, int nobs_template) {
-    return nobs_template == 0 ? occ_n<0>(N) : crx_solve_resident_per_cu_obs(N, nobs_template);
+    size_t bytes = 0;
+    select_general(query_slots(nobs_template), N, 6, [&](auto i) { bytes = Lay<i.nobs, i.nmax>::BYTES; });
+    return bytes;
 }
 
 hipError_t crx_launch_select(const crx_select_kparams& sp, hipStream_t st) {

@@ -36,12 +36,7 @@
 #include "crx_wave.h"
 
 #define LMAXF 16
-#ifndef CRX_LMPC_LATE
-#define CRX_LMPC_LATE 25   // stagnation rule: iterations with mu < 1e-6 before the QP is left on its noise floor (oracle: LATE_ITERS)
-#endif
-#ifndef CRX_STATIC_LDS
-#define CRX_STATIC_LDS 1   // 0: dynamic (extern) LDS as up to libcrx 0.2.0 (A/B builds)
-#endif
+#define LMPC_LATE_ITERS 25   // stagnation rule: iterations with mu < 1e-6 before the QP is left on its noise floor (oracle: LATE_ITERS)
 #define CRX_LMPC_SS44 44   // the reference's num_ss_points (utils/base.py:357): capacity of the six-per-CU instantiation
 
 template <int NMAX, bool DENSE = true, int MSS = CRX_MAX_SS>
@@ -209,7 +204,7 @@ __device__ __forceinline__ void l_lagr(double* sm, const LCtx& x, const crx_lmpc
 }
 
 // NFIX [r3]: the horizon as a compile-time constant (12, the reference's lmpc_param.num_horizon; 0 = read kp.N), as in crx_solve_kernel:
-// +3 % on the stand-alone launch and on the closed-loop step (tools/gpu_round3_ac.sh), identical bits (tools/lmpc_ab.py).  The safe-set
+// +3 % on the stand-alone launch and on the closed-loop step (HISTORY.md, round 3), identical bits (tools/lmpc_ab.py).  The safe-set
 // count as a constant too was measured beside it and does not pay.
 // [r4] The fixed-horizon instantiation keeps its (compile-time) layout in a STATIC array: the compiler then knows the address (0) and folds
 // it into the offset fields of the DS instructions instead of adding a symbol that resolves to 0 at every run-time address (crx_solve_kernel
@@ -217,7 +212,7 @@ __device__ __forceinline__ void l_lagr(double* sm, const LCtx& x, const crx_lmpc
 // compiler also sees how many waves the LDS admits per CU, rounds five or six per CU down to ONE per SIMD and takes > 256 registers (four per
 // CU); and an amdgpu_waves_per_eu(2) floor against that costs the tuned instantiation 8 % (1.654 ms) -- both measured, tools/gpu_pass.sh game:NAME.
 // [r5] The unit is built with MachineLICM off + max-ilp scheduling (Makefile has the numbers): 216 / 222 VGPRs, two waves per SIMD everywhere.
-template <int NFIX> struct LmpcStaticLds { static constexpr bool v = CRX_STATIC_LDS && NFIX != 0; };
+template <int NFIX> struct LmpcStaticLds { static constexpr bool v = NFIX != 0; };
 template <int NMAX, bool DENSE, int MSS, int NFIX = 0>
 __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams kp) {
     static_assert(NFIX <= NMAX, "fixed horizon inside the layout");
@@ -502,7 +497,7 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
             // dual_inf_tol / compl_inf_tol (rows are unscaled here: the violation test is implied by e_p <= tol)
             if (E0 <= o.tol && e_d * sd <= o.dual_inf_tol && e_p <= o.constr_viol_tol && e_c * sc <= o.compl_inf_tol) { status = CRX_CONVERGED; break; }
             if (it >= o.max_iter) break;
-            if (mu < 1e-6 && ++late >= CRX_LMPC_LATE) break;
+            if (mu < 1e-6 && ++late >= LMPC_LATE_ITERS) break;
             // Still violated: look for the proof that it must be (first attempt only; oracle/crx_oracle_lmpc.c
             // lmpc_certificate()) [r2].  Domain D: inputs in their box, lambd in the unit simplex.  With nu >= 0 on the state
             // rows and ANY y on x_N - SS lambd = 0,  F(v) = sum nu_j c_j(u) - y'e(v)  is linear and >= 0 at every feasible v:

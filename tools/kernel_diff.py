@@ -1,0 +1,104 @@
+"""Are the GPU kernels of two builds the same bits?  Needs no GPU.
+
+    python tools/kernel_diff.py OLD NEW          (two libcrx.so, or two .o of the same translation unit)
+
+Every gfx950 code object embedded in the two files is extracted (exec_prologue_check.code_objects) and read as an ELF file.  One line per kernel
+(a function symbol NAME with a kernel descriptor NAME.kd):
+    same      identical .text bytes, identical 64-byte kernel descriptor, identical metadata entry (VGPR / AGPR / SGPR counts, LDS and
+              scratch sizes, arguments) -- whatever its position inside the code object or the order of the code objects
+    differs   names which of text / kd / meta differ
+    missing   in one of the two files only
+A kernel that moved inside its code object has the same text and metadata but shows `differs (kd)`: the descriptor holds the distance to the entry point.
+Exit status 0 when every kernel is `same`, 1 otherwise, 2 when the ROCm binutils are absent.
+"""
+import os
+import shutil
+import struct
+import subprocess
+import sys
+import tempfile
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from exec_prologue_check import OBJDUMP, code_objects, demangle  # noqa: E402
+
+READELF = os.path.join(os.path.dirname(OBJDUMP), "llvm-readelf")
+
+
+def elf_kernels(path):
+    """-> {kernel symbol: (text bytes, descriptor bytes)} of one ELF64 little-endian code object"""
+    d = open(path, "rb").read()
+    shoff, = struct.unpack_from("<Q", d, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", d, 0x3A)
+    sec = [struct.unpack_from("<IIQQQQIIQQ", d, shoff + i * shentsize) for i in range(shnum)]   # name, type, flags, addr, offset, size, link, info, ..
+
+    def body(shndx, value, size):
+        _, typ, _, addr, off, _, _, _, _, _ = sec[shndx]
+        return b"" if typ == 8 else d[off + value - addr: off + value - addr + size]   # (8 = SHT_NOBITS)
+
+    syms = {}
+    for (_, typ, _, _, off, size, link, _, _, entsize) in sec:
+        if typ != 2:   # SHT_SYMTAB
+            continue
+        stroff = sec[link][4]
+        for o in range(off, off + size, entsize):
+            name, info, _, shndx, value, ssize = struct.unpack_from("<IBBHQQ", d, o)
+            if 0 < shndx < shnum:
+                syms[d[stroff + name: d.index(b"\0", stroff + name)].decode()] = (info & 15, shndx, value, ssize)
+    return {n: (body(*syms[n][1:]), body(*syms[n + ".kd"][1:])) for n in syms if syms[n][0] == 2 and n + ".kd" in syms}   # (2 = STT_FUNC)
+
+
+def metadata(path):
+    """-> {kernel symbol: the lines of its entry in the amdhsa.kernels note, sorted}"""
+    txt = subprocess.run([READELF, "--notes", path], capture_output=True, text=True, check=True).stdout
+    out, cur, inside = {}, None, False
+    for l in txt.split("\n"):
+        if l.startswith("amdhsa.kernels:"):
+            inside = True
+        elif inside and l[:1] not in (" ", ""):
+            inside = False
+        elif inside and l.startswith("  - "):
+            cur = []
+            l = "    " + l[4:]
+        if inside and cur is not None and l.startswith("    "):
+            cur.append(l.strip())
+            if l.strip().startswith(".symbol:"):
+                out[l.split(":", 1)[1].strip().strip("'\"")[:-3]] = cur   # ('NAME.kd')
+    return {k: sorted(v) for k, v in out.items()}
+
+
+def kernels(path):
+    tmp = tempfile.mkdtemp(prefix="crx_kd_")
+    try:
+        res = {}
+        for co in code_objects(path, tmp):
+            meta = metadata(co)
+            for n, (text, kd) in elf_kernels(co).items():
+                res[n] = (text, kd, meta.get(n))
+        return res
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def main(argv):
+    if len(argv) != 2:
+        print(__doc__)
+        return 2
+    if not (os.path.exists(OBJDUMP) and os.path.exists(READELF)):
+        print("kernel_diff: %s / llvm-readelf not found -- nothing compared" % OBJDUMP)
+        return 2
+    old, new = kernels(argv[0]), kernels(argv[1])
+    bad = 0
+    for n in sorted(set(old) | set(new)):
+        if n not in old or n not in new:
+            verdict = "missing in " + (argv[0] if n not in old else argv[1])
+        else:
+            what = [w for w, a, b in zip(("text", "kd", "meta"), old[n], new[n]) if a != b or a is None]
+            verdict = "differs (%s)" % ", ".join(what) if what else "same"
+        bad += verdict != "same"
+        print("%-8s %s  [%d B]" % (verdict, demangle(n), len((new.get(n) or old[n])[0])))
+    print("kernel_diff: %d kernel(s), %d not the same" % (len(set(old) | set(new)), bad))
+    return 1 if bad or not old else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv[1:]))

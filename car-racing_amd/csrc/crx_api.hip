@@ -53,51 +53,42 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(CRX_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_));   \
     } while (0)
 
-struct DevBuf {
+// grow-only buffer over one allocate / free pair: device memory, or pinned host memory
+struct DevMem {
+    static constexpr const char* name = "hipMalloc";
+    static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+    static hipError_t release(void* p) { return hipFree(p); }
+};
+struct PinMem {
+    static constexpr const char* name = "hipHostMalloc";
+    static hipError_t alloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static hipError_t release(void* p) { return hipHostFree(p); }
+};
+template <typename Mem>
+struct Buf {
     void* p = nullptr;
     size_t cap = 0;
     int ensure(size_t bytes) {
         if (bytes <= cap) return 0;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
+        release();
         size_t want = bytes + bytes / 2 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) return fail(CRX_ERR_HIP, "hipMalloc(%zu): %s", want, hipGetErrorString(e));
+        hipError_t e = Mem::alloc(&p, want);
+        if (e != hipSuccess) return fail(CRX_ERR_HIP, "%s(%zu): %s", Mem::name, want, hipGetErrorString(e));
         cap = want;
         return 0;
     }
     void release() {
-        if (p) (void)hipFree(p);
+        if (p) (void)Mem::release(p);
         p = nullptr;
         cap = 0;
     }
 };
+using DevBuf = Buf<DevMem>;
+using PinBuf = Buf<PinMem>;
 DevBuf g_in, g_out;  // staging for the host-pointer entry points
-
 // pinned host mirrors of g_in / g_out: a host-pointer call gathers ALL its inputs into one pinned block
 // (one H2D copy), and scatters its outputs from one pinned block (one D2H copy) -- a batch-1 control step
 // is launch-latency bound, and a dozen separate small copies cost more than the solve itself
-struct PinBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return 0;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = bytes + bytes / 2 + 256;
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(CRX_ERR_HIP, "hipHostMalloc(%zu): %s", want, hipGetErrorString(e));
-        cap = want;
-        return 0;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 PinBuf g_hin, g_hout;
 DevBuf g_trace;
 int g_poison = 0;
@@ -110,62 +101,76 @@ int ensure_init() {
     return fail(CRX_ERR_NOT_INIT, "crx_init() has not been called (or failed)");
 }
 
-// staging plan of one host-pointer call: in()/out() carve the device buffers and their pinned mirrors
-// at identical offsets; up() / down() move each block once
+using arr = const void*;   // an array argument of which a check only asks whether it is there
+template <typename... P>
+bool any_null(const P*... p) { return (... || !p); }
+
+// staging plan of one host-pointer call.  The call site names each array ONCE -- in / out / inout / scratch with the host
+// pointer and the element count -- and keeps the handle.  up() lays the arrays out, each 256-byte aligned: the inputs in g_in;
+// in g_out first the in/outs, then the outputs, last the scratch, so that one H2D copy covers the in/outs and the one D2H copy
+// stops in front of the scratch.  It sizes the four buffers from that layout, gathers into the pinned mirrors and uploads.
+// The buffers may move when they grow, so sg[handle] is the device address only AFTER up().  down() copies back and scatters.
 struct Stage {
-    size_t oi = 0, oo = 0;
-    struct Back { void* host; size_t off, bytes; };
-    Back backs[16];
-    int nb = 0;
-    int reserve(size_t bytes_in, size_t bytes_out) {
-        bytes_in += 20 * 256; bytes_out += 20 * 256;   // alignment slack for up to 20 arrays each
-        if (int rc = g_in.ensure(bytes_in)) return rc;
-        if (int rc = g_hin.ensure(bytes_in)) return rc;
-        if (int rc = g_out.ensure(bytes_out)) return rc;
-        return g_hout.ensure(bytes_out);
+    enum Kind { IN, INOUT, OUT, SCRATCH };
+    template <typename T>
+    struct Ref { int i = -1; };   // -1: an array this call does not use; sg[ref] is NULL
+    struct Slot { Kind kind; const void* src; void* dst; size_t bytes, off; };
+    static constexpr int MAX_SLOTS = 24;
+    Slot slots[MAX_SLOTS];
+    int n = 0;
+    bool overrun = false;
+    size_t end[4] = {0, 0, 0, 0};   // bytes of g_in up to its last input; of g_out up to its last in/out, output, scratch
+
+    template <typename T>
+    Ref<T> add(Kind kind, const T* src, T* dst, size_t count) {
+        if (n == MAX_SLOTS) { overrun = true; return {}; }   // reported by up(), before anything is copied or launched
+        slots[n] = Slot{kind, src, dst, count * sizeof(T), 0};
+        return Ref<T>{n++};
     }
     template <typename T>
-    T* in(const T* src, size_t n) {   // src may be NULL (array not used by this call): zero-filled
-        oi = (oi + 255) & ~size_t(255);
-        T* dev = (T*)((char*)g_in.p + oi);
-        if (n) {
-            if (src) memcpy((char*)g_hin.p + oi, src, n * sizeof(T)); else memset((char*)g_hin.p + oi, 0, n * sizeof(T));
-        }
-        oi += n * sizeof(T);
-        return dev;
-    }
+    Ref<T> in(const T* src, size_t count) { return add(IN, src, (T*)nullptr, count); }   // src may be NULL (array not used by this call): zero-filled
     template <typename T>
-    T* out(T* host, size_t n) {       // host may be NULL (result not wanted)
-        oo = (oo + 255) & ~size_t(255);
-        T* dev = (T*)((char*)g_out.p + oo);
-        backs[nb++] = Back{(void*)host, oo, n * sizeof(T)};
-        oo += n * sizeof(T);
-        return dev;
+    Ref<T> out(T* host, size_t count) { return add(OUT, (const T*)nullptr, host, count); }   // host may be NULL (result not wanted)
+    template <typename T>
+    Ref<T> inout(T* host, size_t count) { return add(INOUT, (const T*)host, host, count); }   // the kernel updates the caller's data in place
+    Ref<char> scratch(size_t bytes) { return add(SCRATCH, (const char*)nullptr, (char*)nullptr, bytes); }   // device bytes without a host side
+    template <typename T>
+    T* operator[](Ref<T> r) const {
+        return r.i < 0 ? nullptr : (T*)((char*)(slots[r.i].kind == IN ? g_in.p : g_out.p) + slots[r.i].off);
     }
+
     int up(hipStream_t st) {
-        if (oi) HIP_TRY(hipMemcpyAsync(g_in.p, g_hin.p, oi, hipMemcpyHostToDevice, st));
+        if (overrun) return fail(CRX_ERR_ARG, "internal: more than %d staged arrays in one call", MAX_SLOTS);
+        size_t cur = 0;
+        for (int k = IN; k <= SCRATCH; k++) {
+            if (k == INOUT) cur = 0;   // g_out starts here
+            for (int i = 0; i < n; i++)
+                if (slots[i].kind == k) {
+                    slots[i].off = cur = (cur + 255) & ~size_t(255);
+                    cur += slots[i].bytes;
+                }
+            end[k] = cur;
+        }
+        if (int rc = g_in.ensure(end[IN])) return rc;
+        if (int rc = g_hin.ensure(end[IN])) return rc;
+        if (int rc = g_out.ensure(end[SCRATCH])) return rc;
+        if (int rc = g_hout.ensure(end[OUT])) return rc;
+        for (int i = 0; i < n; i++) {
+            const Slot& s = slots[i];
+            if (s.kind > INOUT || !s.bytes) continue;
+            char* pin = (char*)(s.kind == IN ? g_hin.p : g_hout.p) + s.off;
+            if (s.src) memcpy(pin, s.src, s.bytes); else memset(pin, 0, s.bytes);
+        }
+        if (end[IN]) HIP_TRY(hipMemcpyAsync(g_in.p, g_hin.p, end[IN], hipMemcpyHostToDevice, st));
+        if (end[INOUT]) HIP_TRY(hipMemcpyAsync(g_out.p, g_hout.p, end[INOUT], hipMemcpyHostToDevice, st));
         return 0;
     }
     int down(hipStream_t st) {
-        if (oo) HIP_TRY(hipMemcpyAsync(g_hout.p, g_out.p, oo, hipMemcpyDeviceToHost, st));
+        if (end[OUT]) HIP_TRY(hipMemcpyAsync(g_hout.p, g_out.p, end[OUT], hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
-        for (int i = 0; i < nb; i++)
-            if (backs[i].host && backs[i].bytes) memcpy(backs[i].host, (char*)g_hout.p + backs[i].off, backs[i].bytes);
+        for (int i = 0; i < n; i++)
+            if (slots[i].dst && slots[i].bytes) memcpy(slots[i].dst, (char*)g_hout.p + slots[i].off, slots[i].bytes);
         return 0;
-    }
-};
-
-// bump allocator over a DevBuf
-struct Carver {
-    char* base;
-    size_t off = 0;
-    explicit Carver(void* b) : base((char*)b) {}
-    template <typename T>
-    T* take(size_t n) {
-        off = (off + 255) & ~size_t(255);
-        T* r = (T*)(base + off);
-        off += n * sizeof(T);
-        return r;
     }
 };
 
@@ -175,6 +180,25 @@ int check_opts(const crx_ipm_opts& o) {
         o.slack_start < 0 || o.slack_start > 3 || !(o.dual_inf_tol > 0) || !(o.constr_viol_tol > 0) || !(o.compl_inf_tol > 0) || o.stall_iters < 1 || o.qp_method < 0 || o.qp_method > 1)
         return fail(CRX_ERR_ARG, "invalid crx_ipm_opts (a descriptor built for libcrx <= 0.3.x? crx_ipm_opts grew in 0.2 and in 0.4: include/crx.h)");
     return 0;
+}
+
+// reach of one state coordinate under the boxed inputs: gain[j] = sum_{m<j} |e_row' A^m B| (delta_max, a_max)' for j = 0..n;
+// rows (may be NULL): rows[j] = e_row' A^j
+void reach_bound(const double* A, const double* B, double delta_max, double a_max, int row, int n, double* gain, double (*rows)[6]) {
+    double w[6] = {0, 0, 0, 0, 0, 0}, acc = 0.0;
+    w[row] = 1.0;
+    gain[0] = 0.0;
+    if (rows) memcpy(rows[0], w, sizeof(w));
+    for (int j = 1; j <= n; j++) {
+        double v0 = 0.0, v1 = 0.0, wn[6] = {0, 0, 0, 0, 0, 0};
+        for (int i = 0; i < 6; i++) { v0 += w[i] * B[i * 2]; v1 += w[i] * B[i * 2 + 1]; }
+        acc += fabs(v0) * delta_max + fabs(v1) * a_max;
+        gain[j] = acc;
+        for (int a = 0; a < 6; a++)
+            for (int i = 0; i < 6; i++) wn[a] += w[i] * A[i * 6 + a];
+        memcpy(w, wn, sizeof(w));
+        if (rows) memcpy(rows[j], w, sizeof(w));
+    }
 }
 
 int fill_planner(crx_kparams& kp, const crx_planner_desc* d, int batch) {
@@ -190,21 +214,9 @@ int fill_planner(crx_kparams& kp, const crx_planner_desc* d, int batch) {
     kp.delta_max = d->delta_max; kp.a_max = d->a_max; kp.v_min = -INFINITY; kp.v_max = d->vx_max; kp.ey_max = INFINITY;
     kp.alpha = 0.0; kp.margin = 0.0; kp.l_sum = 1.0; kp.w_sum = 1.0;
     kp.dt_ref = d->dt_ref; kp.fallback_gain = d->fallback_gain; kp.opts = d->opts;
-    // reachability screen (crx_kernels.hip, set-up): reach_gain[j] = sum_{m < j} |e_ey' A^m B| (delta_max, a_max)'
+    // reachability screen (crx_kernels.hip, set-up): the reach of ey at stages 0..N-1 and the rows of its free response
     kp.reach_screen = d->opts.reach_screen ? 1 : 0;
-    double w[6] = {0, 0, 0, 0, 0, 1}, acc = 0.0;
-    kp.reach_gain[0] = 0.0;
-    memcpy(kp.reach_row[0], w, sizeof(w));
-    for (int j = 1; j < d->N; j++) {
-        double v0 = 0.0, v1 = 0.0, wn[6] = {0, 0, 0, 0, 0, 0};
-        for (int i = 0; i < 6; i++) { v0 += w[i] * d->B[i * 2]; v1 += w[i] * d->B[i * 2 + 1]; }
-        acc += fabs(v0) * d->delta_max + fabs(v1) * d->a_max;
-        kp.reach_gain[j] = acc;
-        for (int a = 0; a < 6; a++)
-            for (int i = 0; i < 6; i++) wn[a] += w[i] * d->A[i * 6 + a];
-        memcpy(w, wn, sizeof(w));
-        memcpy(kp.reach_row[j], w, sizeof(w));
-    }
+    reach_bound(d->A, d->B, d->delta_max, d->a_max, 5, d->N - 1, kp.reach_gain, kp.reach_row);
     return 0;
 }
 
@@ -225,31 +237,32 @@ int fill_cbf(crx_kparams& kp, const crx_cbf_desc* d, int batch) {
     kp.delta_max = d->delta_max; kp.a_max = d->a_max; kp.v_min = d->v_min; kp.v_max = d->v_max; kp.ey_max = d->ey_max;
     kp.alpha = d->alpha; kp.margin = d->margin; kp.l_sum = d->l_sum; kp.w_sum = d->w_sum;
     kp.dt_ref = 0.1; kp.fallback_gain = 1.1; kp.opts = d->opts;
-    // reach of s and ey under the boxed inputs (crx_kernels.hip: slack start): sum_{m<j} |e' A^m B| (delta_max, a_max)'
+    // reach of s and ey at stages 0..N under the boxed inputs (crx_kernels.hip: slack start)
     kp.slack_start = d->opts.slack_start;
-    double ws[6] = {0, 0, 0, 0, 1, 0}, we[6] = {0, 0, 0, 0, 0, 1}, as = 0.0, ae = 0.0;
-    kp.reach_s[0] = 0.0; kp.reach_gain[0] = 0.0;
-    for (int j = 1; j <= d->N; j++) {
-        double s0 = 0.0, s1 = 0.0, e0 = 0.0, e1 = 0.0, wn[6] = {0, 0, 0, 0, 0, 0}, en[6] = {0, 0, 0, 0, 0, 0};
-        for (int i = 0; i < 6; i++) {
-            s0 += ws[i] * d->B[i * 2]; s1 += ws[i] * d->B[i * 2 + 1];
-            e0 += we[i] * d->B[i * 2]; e1 += we[i] * d->B[i * 2 + 1];
-        }
-        as += fabs(s0) * d->delta_max + fabs(s1) * d->a_max;
-        ae += fabs(e0) * d->delta_max + fabs(e1) * d->a_max;
-        kp.reach_s[j] = as; kp.reach_gain[j] = ae;
-        for (int a = 0; a < 6; a++)
-            for (int i = 0; i < 6; i++) { wn[a] += ws[i] * d->A[i * 6 + a]; en[a] += we[i] * d->A[i * 6 + a]; }
-        memcpy(ws, wn, sizeof(ws)); memcpy(we, en, sizeof(we));
-    }
+    reach_bound(d->A, d->B, d->delta_max, d->a_max, 4, d->N, kp.reach_s, nullptr);
+    reach_bound(d->A, d->B, d->delta_max, d->a_max, 5, d->N, kp.reach_gain, nullptr);
     return 0;
+}
+
+int launched(hipError_t e, const char* what) {
+    return e == hipSuccess ? CRX_OK : fail(CRX_ERR_HIP, "%s launch: %s", what, hipGetErrorString(e));
+}
+
+// the diagnostics switches (crx_trace_enable, crx_debug_poison_lds, crx_debug_kkt_unscaled) of the following launch.  A negative
+// trace_rows asks for the Riccati sub-phase cycles, which only the planner / CBF kernel records; so does kkt_unscaled
+void apply_diagnostics(crx_kparams& kp) {
+    if (g_trace_rows != 0) { kp.trace = (double*)g_trace.p; kp.trace_problem = g_trace_problem; kp.trace_rows = g_trace_rows; }
+    kp.poison = g_poison;
+    kp.kkt_unscaled = g_kkt_unscaled;
+}
+void apply_diagnostics(crx_lmpc_kparams& kp) {
+    if (g_trace_rows > 0) { kp.trace = (double*)g_trace.p; kp.trace_problem = g_trace_problem; kp.trace_rows = g_trace_rows; }
+    kp.poison = g_poison;
 }
 
 int launch_solve(const crx_kparams& kp, int tmpl, hipStream_t st) {
     crx_kparams kq = kp;
-    if (g_trace_rows != 0) { kq.trace = (double*)g_trace.p; kq.trace_problem = g_trace_problem; kq.trace_rows = g_trace_rows; }
-    kq.poison = g_poison;
-    kq.kkt_unscaled = g_kkt_unscaled;
+    apply_diagnostics(kq);
     size_t lds = crx_solve_lds_bytes(kp.N, tmpl);
     if (lds > 160 * 1024) return fail(CRX_ERR_ARG, "N=%d with %d obstacles needs %zu B of LDS (> 160 KiB)", kp.N, tmpl, lds);
     // [r6] The TWO-WAVE instantiation (one obstacle slot, the reference's exponent, N = 12 / 10; crx_kernels.hip SPEC): a second wave per problem factorises
@@ -259,9 +272,7 @@ int launch_solve(const crx_kparams& kp, int tmpl, hipStream_t st) {
     // pays two workgroup barriers per iteration in every problem, loses 1 % (0.4759 -> 0.4805 ms).
     const bool spec = tmpl == 1 && kq.mode == 1 && kq.degree == 6 && (kq.N == 12 || kq.N == 10) && g_spec > 0;
     kq.spec_idle = g_spec == 2;
-    hipError_t e = spec ? crx_launch_solve_spec(kq, st) : crx_launch_solve(kq, tmpl, st);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "solver launch: %s", hipGetErrorString(e));
-    return 0;
+    return launched(spec ? crx_launch_solve_spec(kq, st) : crx_launch_solve(kq, tmpl, st), "solver");
 }
 
 }  // namespace
@@ -357,11 +368,10 @@ int crx_debug_wave_reduce(const double* in, double* out) {
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
     Stage sg;
-    if (int rc = sg.reserve(256 * 8, 208 * 8)) return rc;
-    double* din = sg.in(in, 256);
-    double* dout = sg.out(out, 208);
+    auto din = sg.in(in, 256);
+    auto dout = sg.out(out, 208);
     if (int rc = sg.up(g_stream)) return rc;
-    hipError_t e = crx_launch_debug_reduce(din, dout, g_stream);
+    hipError_t e = crx_launch_debug_reduce(sg[din], sg[dout], g_stream);
     if (e != hipSuccess) return fail(CRX_ERR_HIP, "debug reduce launch: %s", hipGetErrorString(e));
     return sg.down(g_stream);
 }
@@ -461,6 +471,22 @@ void crx_select_desc_default(crx_select_desc* d, int N, int n_veh_max, double la
 }
 
 // ---- planner --------------------------------------------------------------------------------------
+// Every family below has ONE statement of what its host-pointer and its _dev entry points refuse alike: the descriptor, the
+// dimensions and the NULL-pointer list (not looked at by an empty call, which succeeds).  The host-pointer entry point adds the
+// per-element checks on host arrays and calls the _dev entry point on the staged copies.
+static bool planner_null(arr x0, arr bez_s, arr bez_ey, arr ey_lb, arr ey_ub, arr X, arr U, arr cost, arr status, arr kkt, arr iters) {
+    return any_null(x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters);
+}
+
+static int check_planner(crx_kparams& kp, const crx_planner_desc* d, int batch, arr x0, arr bez_s, arr bez_ey, arr ey_lb, arr ey_ub, arr X, arr U,
+                         arr cost, arr status, arr kkt, arr iters) {
+    if (int rc = ensure_init()) return rc;
+    if (int rc = fill_planner(kp, d, batch)) return rc;
+    if (batch > 0 && planner_null(x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters))
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    return 0;
+}
+
 static int planner_solve_masked(const crx_planner_desc* d, int batch, const int32_t* active, int active_div, const double* x0,
                                 const double* bez_s, const double* bez_ey, const double* ey_lb, const double* ey_ub, double* X,
                                 double* U, double* cost, int32_t* status, double* kkt, int32_t* iters, void* stream);
@@ -474,12 +500,9 @@ int crx_planner_solve_dev(const crx_planner_desc* d, int batch, const double* x0
 static int planner_solve_masked(const crx_planner_desc* d, int batch, const int32_t* active, int active_div, const double* x0,
                                 const double* bez_s, const double* bez_ey, const double* ey_lb, const double* ey_ub, double* X,
                                 double* U, double* cost, int32_t* status, double* kkt, int32_t* iters, void* stream) {
-    if (int rc = ensure_init()) return rc;
     crx_kparams kp;
-    if (int rc = fill_planner(kp, d, batch)) return rc;
+    if (int rc = check_planner(kp, d, batch, x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters)) return rc;
     if (batch == 0) return CRX_OK;
-    if (!x0 || !bez_s || !bez_ey || !ey_lb || !ey_ub || !X || !U || !cost || !status || !kkt || !iters)
-        return fail(CRX_ERR_ARG, "NULL array argument");
     kp.x0 = x0; kp.bez_s = bez_s; kp.bez_ey = bez_ey; kp.ey_lb = ey_lb; kp.ey_ub = ey_ub;
     kp.X = X; kp.U = U; kp.sigma = nullptr; kp.cost = cost; kp.status = status; kp.kkt = kkt; kp.iters = iters;
     kp.active = active; kp.active_div = active_div;
@@ -489,25 +512,20 @@ static int planner_solve_masked(const crx_planner_desc* d, int batch, const int3
 int crx_planner_solve(const crx_planner_desc* d, int batch, const double* x0, const double* bez_s,
                       const double* bez_ey, const double* ey_lb, const double* ey_ub, double* X, double* U,
                       double* cost, int32_t* status, double* kkt, int32_t* iters) {
-    if (int rc = ensure_init()) return rc;
     crx_kparams chk;
-    if (int rc = fill_planner(chk, d, batch)) return rc;
+    if (int rc = check_planner(chk, d, batch, x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters)) return rc;
     if (batch == 0) return CRX_OK;
-    if (!x0 || !bez_s || !bez_ey || !ey_lb || !ey_ub || !X || !U || !cost || !status || !kkt || !iters)
-        return fail(CRX_ERR_ARG, "NULL array argument");
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
     const size_t B = (size_t)batch, N = (size_t)d->N;
-    const size_t n_x0 = B * 6, n_bz = B * (N + 1), n_lb = B * N, n_ub = B;
-    const size_t n_X = B * (N + 1) * 6, n_U = B * N * 2;
     Stage sg;
-    if (int rc = sg.reserve((n_x0 + 2 * n_bz + n_lb + n_ub) * 8, (n_X + n_U + 2 * B) * 8 + 2 * B * 4)) return rc;
-    double* dx0 = sg.in(x0, n_x0); double* dbs = sg.in(bez_s, n_bz); double* dbe = sg.in(bez_ey, n_bz);
-    double* dlb = sg.in(ey_lb, n_lb); double* dub = sg.in(ey_ub, n_ub);
-    double* dX = sg.out(X, n_X); double* dU = sg.out(U, n_U); double* dc = sg.out(cost, B);
-    double* dk = sg.out(kkt, B); int32_t* ds = sg.out(status, B); int32_t* di = sg.out(iters, B);
+    auto dx0 = sg.in(x0, B * 6); auto dbs = sg.in(bez_s, B * (N + 1)); auto dbe = sg.in(bez_ey, B * (N + 1));
+    auto dlb = sg.in(ey_lb, B * N); auto dub = sg.in(ey_ub, B);
+    auto dX = sg.out(X, B * (N + 1) * 6); auto dU = sg.out(U, B * N * 2); auto dc = sg.out(cost, B);
+    auto dk = sg.out(kkt, B); auto ds = sg.out(status, B); auto di = sg.out(iters, B);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_planner_solve_dev(d, batch, dx0, dbs, dbe, dlb, dub, dX, dU, dc, ds, dk, di, g_stream)) return rc;
+    if (int rc = crx_planner_solve_dev(d, batch, sg[dx0], sg[dbs], sg[dbe], sg[dlb], sg[dub], sg[dX], sg[dU], sg[dc], sg[ds], sg[dk],
+                                       sg[di], g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -531,17 +549,24 @@ int crx_cbf_solve_dims_dev(const crx_cbf_desc* d, int batch, const int32_t* acti
     return crx_cbf_solve_ordered_dev(d, batch, active, nullptr, x0, xt, obs_s, obs_ey, lap_off, n_obs, obs_dims, X, U, sigma, cost, status, kkt, iters, stream);
 }
 
+static int check_cbf(crx_kparams& kp, const crx_cbf_desc* d, int batch, arr x0, arr xt, arr obs_s, arr obs_ey, arr lap_off, arr n_obs, arr X, arr U,
+                     arr sigma, arr cost, arr status, arr kkt, arr iters) {
+    if (int rc = ensure_init()) return rc;
+    if (int rc = fill_cbf(kp, d, batch)) return rc;
+    if (batch == 0) return 0;
+    if (any_null(x0, xt, X, U, cost, status, kkt, iters)) return fail(CRX_ERR_ARG, "NULL array argument");
+    if (d->n_obs_max > 0 && any_null(obs_s, obs_ey, lap_off, n_obs, sigma))
+        return fail(CRX_ERR_ARG, "NULL obstacle array with n_obs_max > 0");
+    return 0;
+}
+
 int crx_cbf_solve_ordered_dev(const crx_cbf_desc* d, int batch, const int32_t* active, const int32_t* order, const double* x0,
                               const double* xt, const double* obs_s, const double* obs_ey, const double* lap_off,
                               const int32_t* n_obs, const double* obs_dims, double* X, double* U, double* sigma, double* cost,
                               int32_t* status, double* kkt, int32_t* iters, void* stream) {
-    if (int rc = ensure_init()) return rc;
     crx_kparams kp;
-    if (int rc = fill_cbf(kp, d, batch)) return rc;
+    if (int rc = check_cbf(kp, d, batch, x0, xt, obs_s, obs_ey, lap_off, n_obs, X, U, sigma, cost, status, kkt, iters)) return rc;
     if (batch == 0) return CRX_OK;
-    if (!x0 || !xt || !X || !U || !cost || !status || !kkt || !iters) return fail(CRX_ERR_ARG, "NULL array argument");
-    if (d->n_obs_max > 0 && (!obs_s || !obs_ey || !lap_off || !n_obs || !sigma))
-        return fail(CRX_ERR_ARG, "NULL obstacle array with n_obs_max > 0");
     kp.x0 = x0; kp.xt = xt; kp.obs_s = obs_s; kp.obs_ey = obs_ey; kp.lap_off = lap_off; kp.n_obs = n_obs;
     kp.X = X; kp.U = U; kp.sigma = sigma; kp.cost = cost; kp.status = status; kp.kkt = kkt; kp.iters = iters;
     kp.active = active; kp.order = order; kp.obs_dims = d->n_obs_max > 0 ? obs_dims : nullptr;
@@ -557,14 +582,11 @@ int crx_cbf_solve(const crx_cbf_desc* d, int batch, const double* x0, const doub
 int crx_cbf_solve_dims(const crx_cbf_desc* d, int batch, const double* x0, const double* xt, const double* obs_s,
                   const double* obs_ey, const double* lap_off, const int32_t* n_obs, const double* obs_dims, double* X, double* U,
                   double* sigma, double* cost, int32_t* status, double* kkt, int32_t* iters) {
-    if (int rc = ensure_init()) return rc;
     crx_kparams chk;
-    if (int rc = fill_cbf(chk, d, batch)) return rc;
+    if (int rc = check_cbf(chk, d, batch, x0, xt, obs_s, obs_ey, lap_off, n_obs, X, U, sigma, cost, status, kkt, iters)) return rc;
     if (batch == 0) return CRX_OK;
-    if (!x0 || !xt || !X || !U || !cost || !status || !kkt || !iters) return fail(CRX_ERR_ARG, "NULL array argument");
     const size_t B = (size_t)batch, N = (size_t)d->N, V = (size_t)d->n_obs_max;
     if (V > 0) {
-        if (!obs_s || !obs_ey || !lap_off || !n_obs || !sigma) return fail(CRX_ERR_ARG, "NULL obstacle array with n_obs_max > 0");
         for (size_t b = 0; b < B; b++)
             if (n_obs[b] < 0 || n_obs[b] > (int)V) return fail(CRX_ERR_ARG, "n_obs[%zu]=%d outside [0,%zu]", b, n_obs[b], V);
         if (obs_dims)
@@ -575,18 +597,17 @@ int crx_cbf_solve_dims(const crx_cbf_desc* d, int batch, const double* x0, const
     }
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
-    const size_t n_x0 = B * 6, n_xt = d->per_stage_target ? B * (N + 1) * 6 : B * 6, n_ob = B * V * (N + 1), n_lo = B * V;
-    const size_t n_X = B * (N + 1) * 6, n_U = B * N * 2;
+    const size_t n_ob = B * V * (N + 1);
     Stage sg;
-    if (int rc = sg.reserve((n_x0 + n_xt + 2 * n_ob + 3 * n_lo) * 8 + B * 4, (n_X + n_U + n_ob + 2 * B) * 8 + 2 * B * 4)) return rc;
-    double* dx0 = sg.in(x0, n_x0); double* dxt = sg.in(xt, n_xt);
-    double* dos = sg.in(obs_s, n_ob); double* doe = sg.in(obs_ey, n_ob); double* dlo = sg.in(lap_off, n_lo);
-    double* ddm = (obs_dims && V > 0) ? sg.in(obs_dims, 2 * n_lo) : nullptr;
-    int32_t* dno = sg.in(V > 0 ? n_obs : (const int32_t*)nullptr, B);
-    double* dX = sg.out(X, n_X); double* dU = sg.out(U, n_U); double* dsg = sg.out(sigma, n_ob);
-    double* dc = sg.out(cost, B); double* dk = sg.out(kkt, B); int32_t* ds = sg.out(status, B); int32_t* di = sg.out(iters, B);
+    auto dx0 = sg.in(x0, B * 6); auto dxt = sg.in(xt, d->per_stage_target ? B * (N + 1) * 6 : B * 6);
+    auto dos = sg.in(obs_s, n_ob); auto doe = sg.in(obs_ey, n_ob); auto dlo = sg.in(lap_off, B * V);
+    auto ddm = (obs_dims && V > 0) ? sg.in(obs_dims, B * V * 2) : Stage::Ref<double>{};
+    auto dno = sg.in(V > 0 ? n_obs : (const int32_t*)nullptr, B);
+    auto dX = sg.out(X, B * (N + 1) * 6); auto dU = sg.out(U, B * N * 2); auto dsg = sg.out(sigma, n_ob);
+    auto dc = sg.out(cost, B); auto dk = sg.out(kkt, B); auto ds = sg.out(status, B); auto di = sg.out(iters, B);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_cbf_solve_dims_dev(d, batch, nullptr, dx0, dxt, dos, doe, dlo, dno, ddm, dX, dU, dsg, dc, ds, dk, di, g_stream)) return rc;
+    if (int rc = crx_cbf_solve_dims_dev(d, batch, nullptr, sg[dx0], sg[dxt], sg[dos], sg[doe], sg[dlo], sg[dno], sg[ddm], sg[dX], sg[dU],
+                                        sg[dsg], sg[dc], sg[ds], sg[dk], sg[di], g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -602,45 +623,47 @@ static int check_select(const crx_select_desc* d, int n_scen) {
     return 0;
 }
 
+static bool select_null(const crx_select_desc* d, arr n_veh, arr X, arr obs_s, arr obs_ey, arr old_flag, arr flag, arr sel_cost, arr best_X) {
+    return any_null(n_veh, X, old_flag, flag, sel_cost, best_X) || (d->n_veh_max > 0 && any_null(obs_s, obs_ey));
+}
+
+static int check_select_call(const crx_select_desc* d, int n_scen, arr n_veh, arr X, arr obs_s, arr obs_ey, arr old_flag, arr flag, arr sel_cost,
+                             arr best_X) {
+    if (int rc = ensure_init()) return rc;
+    if (int rc = check_select(d, n_scen)) return rc;
+    if (n_scen > 0 && select_null(d, n_veh, X, obs_s, obs_ey, old_flag, flag, sel_cost, best_X)) return fail(CRX_ERR_ARG, "NULL array argument");
+    return 0;
+}
+
 int crx_select_dev(const crx_select_desc* d, int n_scen, const int32_t* n_veh, const double* X, const double* obs_s,
                    const double* obs_ey, const int32_t* old_flag, int32_t* flag, double* sel_cost, double* best_X,
                    void* stream) {
-    if (int rc = ensure_init()) return rc;
-    if (int rc = check_select(d, n_scen)) return rc;
+    if (int rc = check_select_call(d, n_scen, n_veh, X, obs_s, obs_ey, old_flag, flag, sel_cost, best_X)) return rc;
     if (n_scen == 0) return CRX_OK;
-    if (!n_veh || !X || !old_flag || !flag || !sel_cost || !best_X || (d->n_veh_max > 0 && (!obs_s || !obs_ey)))
-        return fail(CRX_ERR_ARG, "NULL array argument");
     crx_select_kparams sp;
     sp.N = d->N; sp.V = d->n_veh_max; sp.n_scen = n_scen;
     sp.veh_length = d->veh_length; sp.veh_width = d->veh_width; sp.lap_length = d->lap_length;
     sp.w_prog = d->w_prog; sp.w_coll = d->w_coll; sp.w_switch = d->w_switch;
     sp.n_veh = n_veh; sp.X = X; sp.obs_s = obs_s; sp.obs_ey = obs_ey; sp.old_flag = old_flag;
     sp.flag = flag; sp.sel_cost = sel_cost; sp.best_X = best_X;
-    hipError_t e = crx_launch_select(sp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "selection launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_select(sp, (hipStream_t)stream), "selection");
 }
 
 int crx_select(const crx_select_desc* d, int n_scen, const int32_t* n_veh, const double* X, const double* obs_s,
                const double* obs_ey, const int32_t* old_flag, int32_t* flag, double* sel_cost, double* best_X) {
-    if (int rc = ensure_init()) return rc;
-    if (int rc = check_select(d, n_scen)) return rc;
+    if (int rc = check_select_call(d, n_scen, n_veh, X, obs_s, obs_ey, old_flag, flag, sel_cost, best_X)) return rc;
     if (n_scen == 0) return CRX_OK;
-    if (!n_veh || !X || !old_flag || !flag || !sel_cost || !best_X || (d->n_veh_max > 0 && (!obs_s || !obs_ey)))
-        return fail(CRX_ERR_ARG, "NULL array argument");
     const size_t S = (size_t)n_scen, N = (size_t)d->N, V = (size_t)d->n_veh_max, R = V + 1;
     for (size_t s = 0; s < S; s++)
         if (n_veh[s] < 0 || n_veh[s] > (int)V) return fail(CRX_ERR_ARG, "n_veh[%zu]=%d outside [0,%zu]", s, n_veh[s], V);
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
-    const size_t n_X = S * R * (N + 1) * 6, n_ob = S * V * (N + 1), n_bX = S * (N + 1) * 6;
     Stage sg;
-    if (int rc = sg.reserve((n_X + 2 * n_ob) * 8 + 2 * S * 4, (S * R + n_bX) * 8 + S * 4)) return rc;
-    double* dX = sg.in(X, n_X); double* dos = sg.in(obs_s, n_ob); double* doe = sg.in(obs_ey, n_ob);
-    int32_t* dnv = sg.in(n_veh, S); int32_t* dof = sg.in(old_flag, S);
-    int32_t* dfl = sg.out(flag, S); double* dsc = sg.out(sel_cost, S * R); double* dbX = sg.out(best_X, n_bX);
+    auto dX = sg.in(X, S * R * (N + 1) * 6); auto dos = sg.in(obs_s, S * V * (N + 1)); auto doe = sg.in(obs_ey, S * V * (N + 1));
+    auto dnv = sg.in(n_veh, S); auto dof = sg.in(old_flag, S);
+    auto dfl = sg.out(flag, S); auto dsc = sg.out(sel_cost, S * R); auto dbX = sg.out(best_X, S * (N + 1) * 6);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_select_dev(d, n_scen, dnv, dX, dos, doe, dof, dfl, dsc, dbX, g_stream)) return rc;
+    if (int rc = crx_select_dev(d, n_scen, sg[dnv], sg[dX], sg[dos], sg[doe], sg[dof], sg[dfl], sg[dsc], sg[dbX], g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -662,40 +685,41 @@ static int fill_path(crx_path_kparams& pp, const crx_path_desc* d, int batch) {
     return 0;
 }
 
+static int check_path(crx_path_kparams& pp, const crx_path_desc* d, int batch, arr opt, arr bez, arr lb, arr ub, arr e0, arr eN, arr E, arr cost,
+                      arr status, arr kkt, arr iters) {
+    if (int rc = ensure_init()) return rc;
+    if (int rc = fill_path(pp, d, batch)) return rc;
+    if (batch > 0 && any_null(opt, bez, lb, ub, e0, eN, E, cost, status, kkt, iters)) return fail(CRX_ERR_ARG, "NULL array argument");
+    return 0;
+}
+
 int crx_path_solve_dev(const crx_path_desc* d, int batch, const double* opt, const double* bez, const double* lb,
                        const double* ub, const double* e0, const double* eN, double* E, double* cost, int32_t* status,
                        double* kkt, int32_t* iters, void* stream) {
-    if (int rc = ensure_init()) return rc;
     crx_path_kparams pp;
-    if (int rc = fill_path(pp, d, batch)) return rc;
+    if (int rc = check_path(pp, d, batch, opt, bez, lb, ub, e0, eN, E, cost, status, kkt, iters)) return rc;
     if (batch == 0) return CRX_OK;
-    if (!opt || !bez || !lb || !ub || !e0 || !eN || !E || !cost || !status || !kkt || !iters) return fail(CRX_ERR_ARG, "NULL array argument");
     pp.opt = opt; pp.bez = bez; pp.lb = lb; pp.ub = ub; pp.e0 = e0; pp.eN = eN;
     pp.E = E; pp.cost = cost; pp.status = status; pp.kkt = kkt; pp.iters = iters;
-    hipError_t e = crx_launch_path(pp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "path launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_path(pp, (hipStream_t)stream), "path");
 }
 
 int crx_path_solve(const crx_path_desc* d, int batch, const double* opt, const double* bez, const double* lb,
                    const double* ub, const double* e0, const double* eN, double* E, double* cost, int32_t* status,
                    double* kkt, int32_t* iters) {
-    if (int rc = ensure_init()) return rc;
     crx_path_kparams chk;
-    if (int rc = fill_path(chk, d, batch)) return rc;
+    if (int rc = check_path(chk, d, batch, opt, bez, lb, ub, e0, eN, E, cost, status, kkt, iters)) return rc;
     if (batch == 0) return CRX_OK;
-    if (!opt || !bez || !lb || !ub || !e0 || !eN || !E || !cost || !status || !kkt || !iters) return fail(CRX_ERR_ARG, "NULL array argument");
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
     const size_t B = (size_t)batch, n1 = B * (size_t)(d->N + 1);
     Stage sg;
-    if (int rc = sg.reserve((4 * n1 + 2 * B) * 8, (n1 + 2 * B) * 8 + 2 * B * 4)) return rc;
-    double* dop = sg.in(opt, n1); double* dbz = sg.in(bez, n1); double* dlb = sg.in(lb, n1); double* dub = sg.in(ub, n1);
-    double* d0 = sg.in(e0, B); double* dN = sg.in(eN, B);
-    double* dE = sg.out(E, n1); double* dc = sg.out(cost, B); double* dk = sg.out(kkt, B);
-    int32_t* ds = sg.out(status, B); int32_t* di = sg.out(iters, B);
+    auto dop = sg.in(opt, n1); auto dbz = sg.in(bez, n1); auto dlb = sg.in(lb, n1); auto dub = sg.in(ub, n1);
+    auto d0 = sg.in(e0, B); auto dN = sg.in(eN, B);
+    auto dE = sg.out(E, n1); auto dc = sg.out(cost, B); auto dk = sg.out(kkt, B); auto ds = sg.out(status, B); auto di = sg.out(iters, B);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_path_solve_dev(d, batch, dop, dbz, dlb, dub, d0, dN, dE, dc, ds, dk, di, g_stream)) return rc;
+    if (int rc = crx_path_solve_dev(d, batch, sg[dop], sg[dbz], sg[dlb], sg[dub], sg[d0], sg[dN], sg[dE], sg[dc], sg[ds], sg[dk], sg[di],
+                                    g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -708,26 +732,25 @@ void crx_plant_desc_default(crx_plant_desc* d, int n_seg, double lap_length) {
     d->Dr = 0.8 * 1.98 * 9.81 / 2.0; d->Cr = 1.25; d->Br = 1.0;
 }
 
-static int check_plant(const crx_plant_desc* d, int batch) {
+static int check_plant(const crx_plant_desc* d, int batch, int u_stride, arr track, arr xglob, arr xcurv, arr u, arr xglob_next, arr xcurv_next) {
+    if (int rc = ensure_init()) return rc;
     if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
     if (d->n_sub < 0 || d->n_seg < 1 || d->n_seg > 64) return fail(CRX_ERR_ARG, "n_sub < 0 or n_seg outside [1,64]");
     if (!(d->lap_length > 0.0) || !(d->m > 0.0) || !(d->Iz > 0.0)) return fail(CRX_ERR_ARG, "lap_length, m, Iz must be positive");
     if (batch < 0) return fail(CRX_ERR_ARG, "batch < 0");
+    if (u_stride < 2) return fail(CRX_ERR_ARG, "u_stride < 2");
+    if (batch > 0 && any_null(track, xglob, xcurv, u, xglob_next, xcurv_next)) return fail(CRX_ERR_ARG, "NULL array argument");
     return 0;
 }
 
 int crx_plant_step_dev(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
                        const double* u, double* xglob_next, double* xcurv_next, void* stream) {
-    if (int rc = ensure_init()) return rc;
-    if (int rc = check_plant(d, batch)) return rc;
+    if (int rc = check_plant(d, batch, 2, track, xglob, xcurv, u, xglob_next, xcurv_next)) return rc;
     if (batch == 0) return CRX_OK;
-    if (!track || !xglob || !xcurv || !u || !xglob_next || !xcurv_next) return fail(CRX_ERR_ARG, "NULL array argument");
     crx_plant_kparams pk;
     pk.d = *d; pk.batch = batch; pk.u_stride = 2; pk.wrap = 0; pk.track = track; pk.xglob = xglob; pk.xcurv = xcurv; pk.u = u;
     pk.xglob_next = xglob_next; pk.xcurv_next = xcurv_next; pk.laps = nullptr; pk.noise_z = nullptr;
-    hipError_t e = crx_launch_plant(pk, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "plant launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_plant(pk, (hipStream_t)stream), "plant");
 }
 
 int crx_plant_step_wrap_dev(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
@@ -738,17 +761,12 @@ int crx_plant_step_wrap_dev(const crx_plant_desc* d, int batch, const double* tr
 int crx_plant_step_noise_dev(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
                              const double* u, int u_stride, const double* noise_z, double* xglob_next, double* xcurv_next,
                              int32_t* laps, void* stream) {
-    if (int rc = ensure_init()) return rc;
-    if (int rc = check_plant(d, batch)) return rc;
-    if (u_stride < 2) return fail(CRX_ERR_ARG, "u_stride < 2");
+    if (int rc = check_plant(d, batch, u_stride, track, xglob, xcurv, u, xglob_next, xcurv_next)) return rc;
     if (batch == 0) return CRX_OK;
-    if (!track || !xglob || !xcurv || !u || !xglob_next || !xcurv_next) return fail(CRX_ERR_ARG, "NULL array argument");
     crx_plant_kparams pk;
     pk.d = *d; pk.batch = batch; pk.u_stride = u_stride; pk.wrap = 1; pk.track = track; pk.xglob = xglob; pk.xcurv = xcurv; pk.u = u;
     pk.xglob_next = xglob_next; pk.xcurv_next = xcurv_next; pk.laps = laps; pk.noise_z = noise_z;
-    hipError_t e = crx_launch_plant(pk, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "plant launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_plant(pk, (hipStream_t)stream), "plant");
 }
 
 int crx_cbf_prep_dev(int N, int V, double lap_length, double t, double dt, double safety_time, int batch,
@@ -762,26 +780,21 @@ int crx_cbf_prep_dev(int N, int V, double lap_length, double t, double dt, doubl
     cp.N = N; cp.V = V; cp.batch = batch; cp.lap_length = lap_length; cp.t = t; cp.dt = dt; cp.safety_time = safety_time;
     cp.xcurv = xcurv; cp.car_s0 = car_s0; cp.car_v = car_v; cp.car_ey = car_ey;
     cp.obs_s = obs_s; cp.obs_ey = obs_ey; cp.lap_off = lap_off; cp.n_obs = n_obs;
-    hipError_t e = crx_launch_cbfprep(cp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "cbf prep launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_cbfprep(cp, (hipStream_t)stream), "cbf prep");
 }
 
 int crx_plant_step(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
                    const double* u, double* xglob_next, double* xcurv_next) {
-    if (int rc = ensure_init()) return rc;
-    if (int rc = check_plant(d, batch)) return rc;
+    if (int rc = check_plant(d, batch, 2, track, xglob, xcurv, u, xglob_next, xcurv_next)) return rc;
     if (batch == 0) return CRX_OK;
-    if (!track || !xglob || !xcurv || !u || !xglob_next || !xcurv_next) return fail(CRX_ERR_ARG, "NULL array argument");
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
-    const size_t B = (size_t)batch, T = (size_t)d->n_seg * 6;
+    const size_t B = (size_t)batch;
     Stage sg;
-    if (int rc = sg.reserve((T + B * 14) * 8, B * 12 * 8)) return rc;
-    double* dtr = sg.in(track, T); double* dg = sg.in(xglob, B * 6); double* dc = sg.in(xcurv, B * 6); double* du = sg.in(u, B * 2);
-    double* dgn = sg.out(xglob_next, B * 6); double* dcn = sg.out(xcurv_next, B * 6);
+    auto dtr = sg.in(track, (size_t)d->n_seg * 6); auto dg = sg.in(xglob, B * 6); auto dc = sg.in(xcurv, B * 6); auto du = sg.in(u, B * 2);
+    auto dgn = sg.out(xglob_next, B * 6); auto dcn = sg.out(xcurv_next, B * 6);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_plant_step_dev(d, batch, dtr, dg, dc, du, dgn, dcn, g_stream)) return rc;
+    if (int rc = crx_plant_step_dev(d, batch, sg[dtr], sg[dg], sg[dc], sg[du], sg[dgn], sg[dcn], g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -808,51 +821,53 @@ static int fill_prep(crx_prep_kparams& pp, const crx_prep_desc* d, int n_scen) {
     return 0;
 }
 
+static int check_prep(crx_prep_kparams& pp, const crx_prep_desc* d, int n_scen, arr x_wrapped, arr x_raw, arr n_veh, arr veh_info, arr max_dv,
+                      arr obs_s, arr obs_ey, arr opt_s, arr opt_ey, arr x0, arr bez_s, arr bez_ey, arr ey_lb, arr ey_ub) {
+    if (int rc = ensure_init()) return rc;
+    if (int rc = fill_prep(pp, d, n_scen)) return rc;
+    if (n_scen > 0 && (any_null(x_wrapped, x_raw, n_veh, max_dv, opt_s, opt_ey, x0, bez_s, bez_ey, ey_lb, ey_ub) ||
+                       (d->n_veh_max > 0 && any_null(veh_info, obs_s, obs_ey))))
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    return 0;
+}
+
 int crx_planner_prep_dev(const crx_prep_desc* d, int n_scen, const double* x_wrapped, const double* x_raw,
                          const int32_t* n_veh, const double* veh_info, const double* max_dv, const double* obs_s,
                          const double* obs_ey, const double* opt_s, const double* opt_ey, double* x0, double* bez_s,
                          double* bez_ey, double* ey_lb, double* ey_ub, void* stream) {
-    if (int rc = ensure_init()) return rc;
     crx_prep_kparams pp;
-    if (int rc = fill_prep(pp, d, n_scen)) return rc;
+    if (int rc = check_prep(pp, d, n_scen, x_wrapped, x_raw, n_veh, veh_info, max_dv, obs_s, obs_ey, opt_s, opt_ey, x0, bez_s, bez_ey, ey_lb,
+                            ey_ub)) return rc;
     if (n_scen == 0) return CRX_OK;
-    if (!x_wrapped || !x_raw || !n_veh || !max_dv || !opt_s || !opt_ey || !x0 || !bez_s || !bez_ey || !ey_lb || !ey_ub ||
-        (d->n_veh_max > 0 && (!veh_info || !obs_s || !obs_ey)))
-        return fail(CRX_ERR_ARG, "NULL array argument");
     pp.x_wrapped = x_wrapped; pp.x_raw = x_raw; pp.n_veh = n_veh; pp.veh_info = veh_info; pp.max_dv = max_dv;
     pp.obs_s = obs_s; pp.obs_ey = obs_ey; pp.opt_s = opt_s; pp.opt_ey = opt_ey;
     pp.x0 = x0; pp.bez_s = bez_s; pp.bez_ey = bez_ey; pp.ey_lb = ey_lb; pp.ey_ub = ey_ub;
-    hipError_t e = crx_launch_prep(pp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "prep launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_prep(pp, (hipStream_t)stream), "prep");
 }
 
 int crx_planner_prep(const crx_prep_desc* d, int n_scen, const double* x_wrapped, const double* x_raw,
                      const int32_t* n_veh, const double* veh_info, const double* max_dv, const double* obs_s,
                      const double* obs_ey, const double* opt_s, const double* opt_ey, double* x0, double* bez_s,
                      double* bez_ey, double* ey_lb, double* ey_ub) {
-    if (int rc = ensure_init()) return rc;
     crx_prep_kparams chk;
-    if (int rc = fill_prep(chk, d, n_scen)) return rc;
+    if (int rc = check_prep(chk, d, n_scen, x_wrapped, x_raw, n_veh, veh_info, max_dv, obs_s, obs_ey, opt_s, opt_ey, x0, bez_s, bez_ey, ey_lb,
+                            ey_ub)) return rc;
     if (n_scen == 0) return CRX_OK;
-    if (!x_wrapped || !x_raw || !n_veh || !max_dv || !opt_s || !opt_ey || !x0 || !bez_s || !bez_ey || !ey_lb || !ey_ub ||
-        (d->n_veh_max > 0 && (!veh_info || !obs_s || !obs_ey)))
-        return fail(CRX_ERR_ARG, "NULL array argument");
     for (int i = 0; i < n_scen; i++)
         if (n_veh[i] < 0 || n_veh[i] > d->n_veh_max) return fail(CRX_ERR_ARG, "n_veh[%d]=%d outside [0,%d]", i, n_veh[i], d->n_veh_max);
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
     const size_t S = (size_t)n_scen, N = (size_t)d->N, V = (size_t)d->n_veh_max, R = V + 1, T = (size_t)d->n_opt;
-    const size_t n_vi = S * V * 3, n_ob = S * V * (N + 1), n_bz = S * R * (N + 1), n_lb = S * R * N;
+    const size_t n_ob = S * V * (N + 1), n_bz = S * R * (N + 1);
     Stage sg;
-    if (int rc = sg.reserve((S * 13 + n_vi + 2 * n_ob + 2 * T) * 8 + S * 4, (S * R * 7 + 2 * n_bz + n_lb) * 8)) return rc;
-    double* dxw = sg.in(x_wrapped, S * 6); double* dxr = sg.in(x_raw, S * 6); double* dmd = sg.in(max_dv, S);
-    double* dvi = sg.in(veh_info, n_vi); double* dos = sg.in(obs_s, n_ob); double* doe = sg.in(obs_ey, n_ob);
-    double* dts = sg.in(opt_s, T); double* dte = sg.in(opt_ey, T); int32_t* dnv = sg.in(n_veh, S);
-    double* dx0 = sg.out(x0, S * R * 6); double* dbs = sg.out(bez_s, n_bz); double* dbe = sg.out(bez_ey, n_bz);
-    double* dlb = sg.out(ey_lb, n_lb); double* dub = sg.out(ey_ub, S * R);
+    auto dxw = sg.in(x_wrapped, S * 6); auto dxr = sg.in(x_raw, S * 6); auto dmd = sg.in(max_dv, S);
+    auto dvi = sg.in(veh_info, S * V * 3); auto dos = sg.in(obs_s, n_ob); auto doe = sg.in(obs_ey, n_ob);
+    auto dts = sg.in(opt_s, T); auto dte = sg.in(opt_ey, T); auto dnv = sg.in(n_veh, S);
+    auto dx0 = sg.out(x0, S * R * 6); auto dbs = sg.out(bez_s, n_bz); auto dbe = sg.out(bez_ey, n_bz);
+    auto dlb = sg.out(ey_lb, S * R * N); auto dub = sg.out(ey_ub, S * R);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_planner_prep_dev(d, n_scen, dxw, dxr, dnv, dvi, dmd, dos, doe, dts, dte, dx0, dbs, dbe, dlb, dub, g_stream)) return rc;
+    if (int rc = crx_planner_prep_dev(d, n_scen, sg[dxw], sg[dxr], sg[dnv], sg[dvi], sg[dmd], sg[dos], sg[doe], sg[dts], sg[dte], sg[dx0],
+                                      sg[dbs], sg[dbe], sg[dlb], sg[dub], g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -884,6 +899,15 @@ static int fill_lmpc(crx_lmpc_kparams& kp, const crx_lmpc_desc* d, int batch) {
     return 0;
 }
 
+static int check_lmpc(crx_lmpc_kparams& kp, const crx_lmpc_desc* d, int batch, arr x0, arr u_old, arr A, arr B, arr C, arr ss, arr qfun, arr n_ss,
+                      arr X, arr U, arr lambda, arr cost, arr status, arr kkt, arr iters) {
+    if (int rc = ensure_init()) return rc;
+    if (int rc = fill_lmpc(kp, d, batch)) return rc;
+    if (batch > 0 && any_null(x0, u_old, A, B, C, ss, qfun, n_ss, X, U, lambda, cost, status, kkt, iters))
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    return 0;
+}
+
 // n_ss[] is validated on the device side of the boundary only by clamping is NOT acceptable (it indexes
 // LDS), so the host entry point checks it; the _dev variant documents the precondition 1 <= n_ss <= n_ss_max.
 int crx_lmpc_solve_dev(const crx_lmpc_desc* d, int batch, const double* x0, const double* u_old, const double* A,
@@ -904,47 +928,36 @@ int crx_lmpc_solve_ordered_dev(const crx_lmpc_desc* d, int batch, const int32_t*
                                const double* u_old, const double* A, const double* B, const double* C, const double* ss,
                                const double* qfun, const int32_t* n_ss, double* X, double* U, double* lambda, double* cost,
                                int32_t* status, double* kkt, int32_t* iters, void* stream) {
-    if (int rc = ensure_init()) return rc;
     crx_lmpc_kparams kp;
-    if (int rc = fill_lmpc(kp, d, batch)) return rc;
+    if (int rc = check_lmpc(kp, d, batch, x0, u_old, A, B, C, ss, qfun, n_ss, X, U, lambda, cost, status, kkt, iters)) return rc;
     if (batch == 0) return CRX_OK;
-    if (!x0 || !u_old || !A || !B || !C || !ss || !qfun || !n_ss || !X || !U || !lambda || !cost || !status || !kkt || !iters)
-        return fail(CRX_ERR_ARG, "NULL array argument");
     kp.x0 = x0; kp.u_old = u_old; kp.A = A; kp.B = B; kp.C = C; kp.ss = ss; kp.qfun = qfun; kp.n_ss = n_ss;
     kp.X = X; kp.U = U; kp.lambda = lambda; kp.cost = cost; kp.status = status; kp.kkt = kkt; kp.iters = iters;
     kp.active = active; kp.order = order; kp.reach_screen = d->opts.reach_screen ? 1 : 0;
-    if (g_trace_rows > 0) { kp.trace = (double*)g_trace.p; kp.trace_problem = g_trace_problem; kp.trace_rows = g_trace_rows; }
-    kp.poison = g_poison;
-    hipError_t e = crx_launch_lmpc(kp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "lmpc launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    apply_diagnostics(kp);
+    return launched(crx_launch_lmpc(kp, (hipStream_t)stream), "lmpc");
 }
 
 int crx_lmpc_solve(const crx_lmpc_desc* d, int batch, const double* x0, const double* u_old, const double* A,
                    const double* B, const double* C, const double* ss, const double* qfun, const int32_t* n_ss,
                    double* X, double* U, double* lambda, double* cost, int32_t* status, double* kkt, int32_t* iters) {
-    if (int rc = ensure_init()) return rc;
     crx_lmpc_kparams chk;
-    if (int rc = fill_lmpc(chk, d, batch)) return rc;
+    if (int rc = check_lmpc(chk, d, batch, x0, u_old, A, B, C, ss, qfun, n_ss, X, U, lambda, cost, status, kkt, iters)) return rc;
     if (batch == 0) return CRX_OK;
-    if (!x0 || !u_old || !A || !B || !C || !ss || !qfun || !n_ss || !X || !U || !lambda || !cost || !status || !kkt || !iters)
-        return fail(CRX_ERR_ARG, "NULL array argument");
     for (int b = 0; b < batch; b++)
         if (n_ss[b] < 1 || n_ss[b] > d->n_ss_max) return fail(CRX_ERR_ARG, "n_ss[%d]=%d outside [1,%d]", b, n_ss[b], d->n_ss_max);
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
     const size_t Bn = (size_t)batch, N = (size_t)d->N, M = (size_t)d->n_ss_max;
-    const size_t n_A = Bn * N * 36, n_B = Bn * N * 12, n_C = Bn * N * 6, n_ss_ = Bn * 6 * M, n_q = Bn * M;
-    const size_t n_X = Bn * (N + 1) * 6, n_U = Bn * N * 2;
     Stage sg;
-    if (int rc = sg.reserve((Bn * 8 + n_A + n_B + n_C + n_ss_ + n_q) * 8 + Bn * 4, (n_X + n_U + n_q + 2 * Bn) * 8 + 2 * Bn * 4)) return rc;
-    double* dx0 = sg.in(x0, Bn * 6); double* duo = sg.in(u_old, Bn * 2);
-    double* dA = sg.in(A, n_A); double* dB = sg.in(B, n_B); double* dC = sg.in(C, n_C);
-    double* dss = sg.in(ss, n_ss_); double* dq = sg.in(qfun, n_q); int32_t* dn = sg.in(n_ss, Bn);
-    double* dX = sg.out(X, n_X); double* dU = sg.out(U, n_U); double* dl = sg.out(lambda, n_q);
-    double* dc = sg.out(cost, Bn); double* dk = sg.out(kkt, Bn); int32_t* ds = sg.out(status, Bn); int32_t* di = sg.out(iters, Bn);
+    auto dx0 = sg.in(x0, Bn * 6); auto duo = sg.in(u_old, Bn * 2);
+    auto dA = sg.in(A, Bn * N * 36); auto dB = sg.in(B, Bn * N * 12); auto dC = sg.in(C, Bn * N * 6);
+    auto dss = sg.in(ss, Bn * 6 * M); auto dq = sg.in(qfun, Bn * M); auto dn = sg.in(n_ss, Bn);
+    auto dX = sg.out(X, Bn * (N + 1) * 6); auto dU = sg.out(U, Bn * N * 2); auto dl = sg.out(lambda, Bn * M);
+    auto dc = sg.out(cost, Bn); auto dk = sg.out(kkt, Bn); auto ds = sg.out(status, Bn); auto di = sg.out(iters, Bn);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_lmpc_solve_dev(d, batch, dx0, duo, dA, dB, dC, dss, dq, dn, dX, dU, dl, dc, ds, dk, di, g_stream)) return rc;
+    if (int rc = crx_lmpc_solve_dev(d, batch, sg[dx0], sg[duo], sg[dA], sg[dB], sg[dC], sg[dss], sg[dq], sg[dn], sg[dX], sg[dU], sg[dl],
+                                    sg[dc], sg[ds], sg[dk], sg[di], g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -977,35 +990,30 @@ static int fill_ilqr(crx_ilqr_kparams& kp, const crx_ilqr_desc* d, int batch) {
     return 0;
 }
 
-static bool ilqr_null(const crx_ilqr_desc* d, const double* x0, const double* xt, const double* obs_s, const double* obs_ey,
-                      const double* lap_off, const int32_t* n_obs, const double* X, const double* U, const double* cost,
-                      const int32_t* status, const int32_t* iters) {
-    const bool obs = d->n_obs_max > 0;
-    return !x0 || !xt || !n_obs || !X || !U || !cost || !status || !iters || (obs && (!obs_s || !obs_ey || !lap_off));
+static int check_ilqr(crx_ilqr_kparams& kp, const crx_ilqr_desc* d, int batch, arr x0, arr xt, arr obs_s, arr obs_ey, arr lap_off, arr n_obs, arr X,
+                      arr U, arr cost, arr status, arr iters) {
+    if (int rc = fill_ilqr(kp, d, batch)) return rc;
+    if (batch > 0 && (any_null(x0, xt, n_obs, X, U, cost, status, iters) || (d->n_obs_max > 0 && any_null(obs_s, obs_ey, lap_off))))
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    return 0;
 }
 
 int crx_ilqr_solve_dev(const crx_ilqr_desc* d, int batch, const int32_t* active, const double* x0, const double* xt,
                        const double* obs_s, const double* obs_ey, const double* lap_off, const int32_t* n_obs, double* X, double* U,
                        double* cost, int32_t* status, int32_t* iters, void* stream) {
     crx_ilqr_kparams kp;
-    if (int rc = fill_ilqr(kp, d, batch)) return rc;
-    if (batch > 0 && ilqr_null(d, x0, xt, obs_s, obs_ey, lap_off, n_obs, X, U, cost, status, iters))
-        return fail(CRX_ERR_ARG, "NULL array argument");
+    if (int rc = check_ilqr(kp, d, batch, x0, xt, obs_s, obs_ey, lap_off, n_obs, X, U, cost, status, iters)) return rc;
     if (int rc = ensure_init()) return rc;
     if (batch == 0) return CRX_OK;
     kp.x0 = x0; kp.xt = xt; kp.obs_s = obs_s; kp.obs_ey = obs_ey; kp.lap_off = lap_off; kp.n_obs = n_obs; kp.active = active;
     kp.X = X; kp.U = U; kp.cost = cost; kp.status = status; kp.iters = iters;
-    hipError_t e = crx_launch_ilqr(kp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "ilqr launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_ilqr(kp, (hipStream_t)stream), "ilqr");
 }
 
 int crx_ilqr_solve(const crx_ilqr_desc* d, int batch, const double* x0, const double* xt, const double* obs_s, const double* obs_ey,
                    const double* lap_off, const int32_t* n_obs, double* X, double* U, double* cost, int32_t* status, int32_t* iters) {
     crx_ilqr_kparams chk;
-    if (int rc = fill_ilqr(chk, d, batch)) return rc;
-    if (batch > 0 && ilqr_null(d, x0, xt, obs_s, obs_ey, lap_off, n_obs, X, U, cost, status, iters))
-        return fail(CRX_ERR_ARG, "NULL array argument");
+    if (int rc = check_ilqr(chk, d, batch, x0, xt, obs_s, obs_ey, lap_off, n_obs, X, U, cost, status, iters)) return rc;
     for (int b = 0; b < batch; b++)
         if (n_obs[b] < 0 || n_obs[b] > d->n_obs_max) return fail(CRX_ERR_ARG, "n_obs[%d]=%d outside [0,%d]", b, n_obs[b], d->n_obs_max);
     if (int rc = ensure_init()) return rc;
@@ -1013,16 +1021,15 @@ int crx_ilqr_solve(const crx_ilqr_desc* d, int batch, const double* x0, const do
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
     const size_t Bn = (size_t)batch, N = (size_t)d->N, V = (size_t)d->n_obs_max;
-    const size_t n_obs_pts = Bn * V * (N + 1), n_X = Bn * (N + 1) * 6, n_U = Bn * N * 2;
     Stage sg;
-    if (int rc = sg.reserve((Bn * 12 + 2 * n_obs_pts + Bn * V) * 8 + Bn * 4, (n_X + n_U + Bn) * 8 + 2 * Bn * 4)) return rc;
-    double* dx0 = sg.in(x0, Bn * 6); double* dxt = sg.in(xt, Bn * 6);
-    double* dos = sg.in(obs_s, n_obs_pts); double* doe = sg.in(obs_ey, n_obs_pts); double* dlo = sg.in(lap_off, Bn * V);
-    int32_t* dn = sg.in(n_obs, Bn);
-    double* dX = sg.out(X, n_X); double* dU = sg.out(U, n_U); double* dc = sg.out(cost, Bn);
-    int32_t* ds = sg.out(status, Bn); int32_t* di = sg.out(iters, Bn);
+    auto dx0 = sg.in(x0, Bn * 6); auto dxt = sg.in(xt, Bn * 6);
+    auto dos = sg.in(obs_s, Bn * V * (N + 1)); auto doe = sg.in(obs_ey, Bn * V * (N + 1)); auto dlo = sg.in(lap_off, Bn * V);
+    auto dn = sg.in(n_obs, Bn);
+    auto dX = sg.out(X, Bn * (N + 1) * 6); auto dU = sg.out(U, Bn * N * 2); auto dc = sg.out(cost, Bn);
+    auto ds = sg.out(status, Bn); auto di = sg.out(iters, Bn);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_ilqr_solve_dev(d, batch, nullptr, dx0, dxt, dos, doe, dlo, dn, dX, dU, dc, ds, di, g_stream)) return rc;
+    if (int rc = crx_ilqr_solve_dev(d, batch, nullptr, sg[dx0], sg[dxt], sg[dos], sg[doe], sg[dlo], sg[dn], sg[dX], sg[dU], sg[dc], sg[ds],
+                                    sg[di], g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -1032,20 +1039,25 @@ void crx_sysid_desc_default(crx_sysid_desc* d) {
     d->lamb = 1e-9; d->first_row = 1; d->chunk_rows = 8192;
 }
 
-static int check_sysid(const crx_sysid_desc* d, int n_logs, int n_groups, bool grouped) {
+static int sysid_tpl(const crx_sysid_desc* d, int64_t max_log_rows) {
+    const int64_t pairs = max_log_rows - 1 - d->first_row;
+    const int64_t t = pairs > 0 ? (pairs + d->chunk_rows - 1) / d->chunk_rows : 0;
+    return t > 1 ? (int)t : 1;
+}
+
+// max_log_rows: the _dev caller's; the host-pointer entry point derives its own from log_offset AFTER this check and passes 0 here
+static int check_sysid(const crx_sysid_desc* d, int n_logs, arr log_offset, arr group_offset, int n_groups, int64_t max_log_rows, arr A, arr B,
+                       arr err, arr n_pairs, arr status) {
     if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
     if (!(d->lamb >= 0.0) || !isfinite(d->lamb)) return fail(CRX_ERR_ARG, "lamb must be finite and non-negative");
     if (d->first_row < 0) return fail(CRX_ERR_ARG, "first_row < 0");
     if (d->chunk_rows < 256 || d->chunk_rows > 65536 || d->chunk_rows % 256) return fail(CRX_ERR_ARG, "chunk_rows=%d: a multiple of 256 in [256, 65536]", d->chunk_rows);
     if (n_logs < 0 || n_groups < 0) return fail(CRX_ERR_ARG, "n_logs, n_groups must be >= 0");
-    if (!grouped && n_groups != n_logs) return fail(CRX_ERR_ARG, "group_offset NULL needs n_groups == n_logs");
+    if (!group_offset && n_groups != n_logs) return fail(CRX_ERR_ARG, "group_offset NULL needs n_groups == n_logs");
+    if (max_log_rows < 0) return fail(CRX_ERR_ARG, "max_log_rows < 0");
+    if ((int64_t)n_logs * sysid_tpl(d, max_log_rows) > INT32_MAX) return fail(CRX_ERR_ARG, "n_logs * tiles per log exceeds the grid");
+    if (n_groups > 0 && any_null(log_offset, A, B, err, n_pairs, status)) return fail(CRX_ERR_ARG, "NULL array argument");
     return 0;
-}
-
-static int sysid_tpl(const crx_sysid_desc* d, int64_t max_log_rows) {
-    const int64_t pairs = max_log_rows - 1 - d->first_row;
-    const int64_t t = pairs > 0 ? (pairs + d->chunk_rows - 1) / d->chunk_rows : 0;
-    return t > 1 ? (int)t : 1;
 }
 
 size_t crx_sysid_workspace_bytes(const crx_sysid_desc* d, int n_logs, int n_groups, int64_t max_log_rows) {
@@ -1057,11 +1069,9 @@ size_t crx_sysid_workspace_bytes(const crx_sysid_desc* d, int n_logs, int n_grou
 int crx_sysid_fit_dev(const crx_sysid_desc* d, int n_logs, const int64_t* log_offset, const int32_t* group_offset, int n_groups,
                       int64_t max_log_rows, const double* x, const double* u, void* workspace, size_t ws_bytes, double* A, double* B,
                       double* err, int64_t* n_pairs, int32_t* status, void* stream) {
-    if (int rc = check_sysid(d, n_logs, n_groups, group_offset != nullptr)) return rc;
-    if (max_log_rows < 0) return fail(CRX_ERR_ARG, "max_log_rows < 0");
+    if (int rc = check_sysid(d, n_logs, log_offset, group_offset, n_groups, max_log_rows, A, B, err, n_pairs, status)) return rc;
     const int tpl = sysid_tpl(d, max_log_rows);
-    if ((int64_t)n_logs * tpl > INT32_MAX) return fail(CRX_ERR_ARG, "n_logs * tiles per log exceeds the grid");
-    if (n_groups > 0 && (!log_offset || !A || !B || !err || !n_pairs || !status || !workspace)) return fail(CRX_ERR_ARG, "NULL array argument");
+    if (n_groups > 0 && !workspace) return fail(CRX_ERR_ARG, "NULL array argument");
     if (n_groups > 0 && max_log_rows > 0 && (!x || !u)) return fail(CRX_ERR_ARG, "NULL array argument");
     if (n_groups > 0 && ws_bytes < crx_sysid_workspace_bytes(d, n_logs, n_groups, max_log_rows))
         return fail(CRX_ERR_ARG, "workspace of %zu bytes, %zu needed", ws_bytes, crx_sysid_workspace_bytes(d, n_logs, n_groups, max_log_rows));
@@ -1077,15 +1087,12 @@ int crx_sysid_fit_dev(const crx_sysid_desc* d, int n_logs, const int64_t* log_of
     kp.ws_res = kp.ws_gram + tiles * 84;
     kp.ws_W = kp.ws_res + tiles * 12;
     kp.A = A; kp.B = B; kp.err = err; kp.n_pairs = n_pairs; kp.status = status;
-    hipError_t e = crx_launch_sysid(kp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "sysid launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_sysid(kp, (hipStream_t)stream), "sysid");
 }
 
 int crx_sysid_fit(const crx_sysid_desc* d, int n_logs, const int64_t* log_offset, const int32_t* group_offset, int n_groups,
                   const double* x, const double* u, double* A, double* B, double* err, int64_t* n_pairs, int32_t* status) {
-    if (int rc = check_sysid(d, n_logs, n_groups, group_offset != nullptr)) return rc;
-    if (n_groups > 0 && (!log_offset || !A || !B || !err || !n_pairs || !status)) return fail(CRX_ERR_ARG, "NULL array argument");
+    if (int rc = check_sysid(d, n_logs, log_offset, group_offset, n_groups, 0, A, B, err, n_pairs, status)) return rc;
     int64_t max_rows = 0, rows = 0;
     if (n_groups > 0) {
         if (log_offset[0] < 0) return fail(CRX_ERR_ARG, "log_offset[0] < 0");
@@ -1109,15 +1116,14 @@ int crx_sysid_fit(const crx_sysid_desc* d, int n_logs, const int64_t* log_offset
     const size_t L = (size_t)n_logs, G = (size_t)n_groups, R = (size_t)rows;
     const size_t ws_bytes = crx_sysid_workspace_bytes(d, n_logs, n_groups, max_rows);
     Stage sg;
-    if (int rc = sg.reserve(R * 8 * 8 + (L + 1) * 8 + (G + 1) * 4, G * (36 + 12 + 12 + 1) * 8 + G * 4 + ws_bytes)) return rc;
-    const double* dx = sg.in(x, R * 6); const double* du = sg.in(u, R * 2);
-    const int64_t* dlo = sg.in(log_offset, L + 1);
-    const int32_t* dgo = group_offset ? sg.in(group_offset, G + 1) : nullptr;
-    double* dA = sg.out(A, G * 36); double* dB = sg.out(B, G * 12); double* de = sg.out(err, G * 12);
-    int64_t* dn = sg.out(n_pairs, G); int32_t* ds = sg.out(status, G);
-    char* dws = sg.out((char*)nullptr, ws_bytes);
+    auto dx = sg.in(x, R * 6); auto du = sg.in(u, R * 2); auto dlo = sg.in(log_offset, L + 1);
+    auto dgo = group_offset ? sg.in(group_offset, G + 1) : Stage::Ref<int32_t>{};
+    auto dA = sg.out(A, G * 36); auto dB = sg.out(B, G * 12); auto de = sg.out(err, G * 12);
+    auto dn = sg.out(n_pairs, G); auto ds = sg.out(status, G);
+    auto dws = sg.scratch(ws_bytes);   // the tile partials stay on the device: the copy back stops in front of them
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_sysid_fit_dev(d, n_logs, dlo, dgo, n_groups, max_rows, dx, du, dws, ws_bytes, dA, dB, de, dn, ds, g_stream)) return rc;
+    if (int rc = crx_sysid_fit_dev(d, n_logs, sg[dlo], sg[dgo], n_groups, max_rows, sg[dx], sg[du], sg[dws], ws_bytes, sg[dA], sg[dB], sg[de],
+                                   sg[dn], sg[ds], g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -1132,9 +1138,7 @@ int crx_pid_log_dev(int batch, int T, int row, const double* vt, const double* e
     crx_pid_kparams kp;
     kp.batch = batch; kp.T = T; kp.row = row; kp.vt = vt; kp.eyt = eyt; kp.xcurv = xcurv; kp.u_prev = u_prev;
     kp.u_next = u_next; kp.x_log = x_log; kp.u_log = u_log;
-    hipError_t e = crx_launch_pid_log(kp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "pid launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_pid_log(kp, (hipStream_t)stream), "pid");
 }
 
 // ---- planner front (interest test, partial sort, vehicle infos) on the device ------------------------
@@ -1144,13 +1148,17 @@ void crx_scene_desc_default(crx_scene_desc* d, int N, int n_all_max, int n_veh_m
     d->safety_factor = 4.5; d->prediction_factor = 0.5; d->veh_length = 0.4; d->lap_length = lap_length;
 }
 
-static int check_scene(const crx_scene_desc* d, int n_scen) {
+static int check_scene(const crx_scene_desc* d, int n_scen, arr ego_xcurv, arr n_all, arr veh_xcurv, arr pred_s, arr pred_ey, arr n_veh, arr overflow,
+                       arr order, arr veh_info, arr max_dv, arr obs_s, arr obs_ey) {
+    if (int rc = ensure_init()) return rc;
     if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
     if (d->N < 1 || d->N > CRX_MAX_N) return fail(CRX_ERR_ARG, "N=%d outside [1,%d]", d->N, CRX_MAX_N);
     if (d->n_all_max < 1 || d->n_all_max > 64) return fail(CRX_ERR_ARG, "n_all_max=%d outside [1,64]", d->n_all_max);
     if (d->n_veh_max < 1 || d->n_veh_max > CRX_MAX_VEH) return fail(CRX_ERR_ARG, "n_veh_max=%d outside [1,%d]", d->n_veh_max, CRX_MAX_VEH);
     if (!(d->lap_length > 0.0) || !isfinite(d->lap_length)) return fail(CRX_ERR_ARG, "lap_length must be positive and finite");
     if (n_scen < 0) return fail(CRX_ERR_ARG, "n_scen < 0");
+    if (n_scen > 0 && any_null(ego_xcurv, n_all, veh_xcurv, pred_s, pred_ey, n_veh, overflow, order, veh_info, max_dv, obs_s, obs_ey))
+        return fail(CRX_ERR_ARG, "NULL array argument");
     return 0;
 }
 
@@ -1158,42 +1166,36 @@ int crx_planner_scene_dev(const crx_scene_desc* d, int n_scen, const double* ego
                           const double* veh_xcurv, const double* pred_s, const double* pred_ey, int32_t* n_veh,
                           int32_t* overflow, int32_t* order, double* veh_info, double* max_dv, double* obs_s, double* obs_ey,
                           void* stream) {
-    if (int rc = ensure_init()) return rc;
-    if (int rc = check_scene(d, n_scen)) return rc;
+    if (int rc = check_scene(d, n_scen, ego_xcurv, n_all, veh_xcurv, pred_s, pred_ey, n_veh, overflow, order, veh_info, max_dv, obs_s, obs_ey))
+        return rc;
     if (n_scen == 0) return CRX_OK;
-    if (!ego_xcurv || !n_all || !veh_xcurv || !pred_s || !pred_ey || !n_veh || !overflow || !order || !veh_info || !max_dv || !obs_s || !obs_ey)
-        return fail(CRX_ERR_ARG, "NULL array argument");
     crx_scene_kparams sp;
     sp.d = *d; sp.n_scen = n_scen; sp.ego_xcurv = ego_xcurv; sp.n_all = n_all; sp.veh_xcurv = veh_xcurv; sp.pred_s = pred_s;
     sp.pred_ey = pred_ey; sp.n_veh = n_veh; sp.overflow = overflow; sp.order = order; sp.veh_info = veh_info; sp.max_dv = max_dv;
     sp.obs_s = obs_s; sp.obs_ey = obs_ey;
-    hipError_t e = crx_launch_scene(sp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "scene launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_scene(sp, (hipStream_t)stream), "scene");
 }
 
 int crx_planner_scene(const crx_scene_desc* d, int n_scen, const double* ego_xcurv, const int32_t* n_all, const double* veh_xcurv,
                       const double* pred_s, const double* pred_ey, int32_t* n_veh, int32_t* overflow, int32_t* order,
                       double* veh_info, double* max_dv, double* obs_s, double* obs_ey) {
-    if (int rc = ensure_init()) return rc;
-    if (int rc = check_scene(d, n_scen)) return rc;
+    if (int rc = check_scene(d, n_scen, ego_xcurv, n_all, veh_xcurv, pred_s, pred_ey, n_veh, overflow, order, veh_info, max_dv, obs_s, obs_ey))
+        return rc;
     if (n_scen == 0) return CRX_OK;
-    if (!ego_xcurv || !n_all || !veh_xcurv || !pred_s || !pred_ey || !n_veh || !overflow || !order || !veh_info || !max_dv || !obs_s || !obs_ey)
-        return fail(CRX_ERR_ARG, "NULL array argument");
     for (int i = 0; i < n_scen; i++)
         if (n_all[i] < 0 || n_all[i] > d->n_all_max) return fail(CRX_ERR_ARG, "n_all[%d]=%d outside [0,%d]", i, n_all[i], d->n_all_max);
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
     const size_t S = (size_t)n_scen, VA = (size_t)d->n_all_max, V = (size_t)d->n_veh_max, N1 = (size_t)d->N + 1;
     Stage sg;
-    if (int rc = sg.reserve((S * 6 + S * VA * 6 + 2 * S * VA * N1) * 8 + S * 4, (S * V * 3 + S + 2 * S * V * N1) * 8 + (2 * S + S * V) * 4)) return rc;
-    double* dego = sg.in(ego_xcurv, S * 6); double* dvx = sg.in(veh_xcurv, S * VA * 6);
-    double* dps = sg.in(pred_s, S * VA * N1); double* dpe = sg.in(pred_ey, S * VA * N1); int32_t* dna = sg.in(n_all, S);
-    int32_t* dnv = sg.out(n_veh, S); int32_t* dov = sg.out(overflow, S); int32_t* dor = sg.out(order, S * V);
-    double* dvi = sg.out(veh_info, S * V * 3); double* dmd = sg.out(max_dv, S);
-    double* dos = sg.out(obs_s, S * V * N1); double* doe = sg.out(obs_ey, S * V * N1);
+    auto dego = sg.in(ego_xcurv, S * 6); auto dvx = sg.in(veh_xcurv, S * VA * 6);
+    auto dps = sg.in(pred_s, S * VA * N1); auto dpe = sg.in(pred_ey, S * VA * N1); auto dna = sg.in(n_all, S);
+    auto dnv = sg.out(n_veh, S); auto dov = sg.out(overflow, S); auto dor = sg.out(order, S * V);
+    auto dvi = sg.out(veh_info, S * V * 3); auto dmd = sg.out(max_dv, S);
+    auto dos = sg.out(obs_s, S * V * N1); auto doe = sg.out(obs_ey, S * V * N1);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_planner_scene_dev(d, n_scen, dego, dna, dvx, dps, dpe, dnv, dov, dor, dvi, dmd, dos, doe, g_stream)) return rc;
+    if (int rc = crx_planner_scene_dev(d, n_scen, sg[dego], sg[dna], sg[dvx], sg[dps], sg[dpe], sg[dnv], sg[dov], sg[dor], sg[dvi], sg[dmd],
+                                       sg[dos], sg[doe], g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -1210,9 +1212,7 @@ int crx_track_prep_dev(int N, int V, double lap_length, double safety_time, doub
     tp.N = N; tp.V = V; tp.batch = batch; tp.lap_length = lap_length; tp.safety_time = safety_time; tp.dt_ref = dt_ref;
     tp.x = x; tp.n_veh = n_veh; tp.obs_s_in = obs_s_in; tp.obs_ey_in = obs_ey_in; tp.traj = traj;
     tp.xt = xt; tp.obs_s = obs_s; tp.obs_ey = obs_ey; tp.lap_off = lap_off; tp.n_obs = n_obs;
-    hipError_t e = crx_launch_trackprep(tp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "track prep launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_trackprep(tp, (hipStream_t)stream), "track prep");
 }
 
 // ---- learning-MPC host prep on the device ------------------------------------------------------------
@@ -1238,6 +1238,15 @@ static int check_lmpcprep(const crx_lmpcprep_desc* d, int batch) {
     return 0;
 }
 
+static int check_lmpcprep_call(const crx_lmpcprep_desc* d, int batch, arr ss_xcurv, arr u_ss, arr qfun, arr time_ss, arr iter, arr x, arr lin_points,
+                               arr lin_input, arr track, arr A, arr B, arr C, arr ss_sel, arr q_sel, arr status) {
+    if (int rc = ensure_init()) return rc;
+    if (int rc = check_lmpcprep(d, batch)) return rc;
+    if (batch > 0 && any_null(ss_xcurv, u_ss, qfun, time_ss, iter, x, lin_points, lin_input, track, A, B, C, ss_sel, q_sel, status))
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    return 0;
+}
+
 int crx_lmpc_prep_dev(const crx_lmpcprep_desc* d, int batch, const double* ss_xcurv, const double* u_ss, const double* qfun,
                       const int32_t* time_ss, const int32_t* iter, const double* x, const double* lin_points,
                       const double* lin_input, int from_plan, const double* track, double* A, double* B, double* C,
@@ -1250,32 +1259,24 @@ int crx_lmpc_prep_masked_dev(const crx_lmpcprep_desc* d, int batch, const int32_
                              const double* qfun, const int32_t* time_ss, const int32_t* iter, const double* x, const double* lin_points,
                              const double* lin_input, int from_plan, const double* track, double* A, double* B, double* C,
                              double* ss_sel, double* q_sel, int32_t* status, void* stream) {
-    if (int rc = ensure_init()) return rc;
-    if (int rc = check_lmpcprep(d, batch)) return rc;
+    if (int rc = check_lmpcprep_call(d, batch, ss_xcurv, u_ss, qfun, time_ss, iter, x, lin_points, lin_input, track, A, B, C, ss_sel, q_sel,
+                                     status)) return rc;
     if (batch == 0) return CRX_OK;
-    if (!ss_xcurv || !u_ss || !qfun || !time_ss || !iter || !x || !lin_points || !lin_input || !track || !A || !B || !C || !ss_sel ||
-        !q_sel || !status)
-        return fail(CRX_ERR_ARG, "NULL array argument");
     crx_lmpcprep_kparams kp;
     kp.d = *d; kp.batch = batch; kp.from_plan = from_plan ? 1 : 0;
     kp.ss_xcurv = ss_xcurv; kp.u_ss = u_ss; kp.qfun = qfun; kp.time_ss = time_ss; kp.iter = iter; kp.x = x;
     kp.lin_points = lin_points; kp.lin_input = lin_input; kp.track = track;
     kp.A = A; kp.B = B; kp.C = C; kp.ss_sel = ss_sel; kp.q_sel = q_sel; kp.status = status; kp.active = active;
-    hipError_t e = crx_launch_lmpcprep(kp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "lmpc prep launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_lmpcprep(kp, (hipStream_t)stream), "lmpc prep");
 }
 
 int crx_lmpc_prep(const crx_lmpcprep_desc* d, int batch, const double* ss_xcurv, const double* u_ss, const double* qfun,
                   const int32_t* time_ss, const int32_t* iter, const double* x, const double* lin_points,
                   const double* lin_input, int from_plan, const double* track, double* A, double* B, double* C,
                   double* ss_sel, double* q_sel, int32_t* status) {
-    if (int rc = ensure_init()) return rc;
-    if (int rc = check_lmpcprep(d, batch)) return rc;
+    if (int rc = check_lmpcprep_call(d, batch, ss_xcurv, u_ss, qfun, time_ss, iter, x, lin_points, lin_input, track, A, B, C, ss_sel, q_sel,
+                                     status)) return rc;
     if (batch == 0) return CRX_OK;
-    if (!ss_xcurv || !u_ss || !qfun || !time_ss || !iter || !x || !lin_points || !lin_input || !track || !A || !B || !C || !ss_sel ||
-        !q_sel || !status)
-        return fail(CRX_ERR_ARG, "NULL array argument");
     const size_t Bn = (size_t)batch, N = (size_t)d->N, P = (size_t)d->n_points, L = (size_t)d->n_laps;
     const size_t M = (size_t)d->n_ss_per_lap * d->n_ss_laps;
     for (size_t b = 0; b < Bn; b++) {
@@ -1288,21 +1289,17 @@ int crx_lmpc_prep(const crx_lmpcprep_desc* d, int batch, const double* ss_xcurv,
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
     Stage sg;
-    if (int rc = sg.reserve((Bn * L * P * 9 + Bn * (6 + (N + 1) * 6 + N * 2) + (size_t)d->n_seg * 6) * 8 + Bn * (L + 1) * 4,
-                            (Bn * N * 54 + Bn * 7 * M) * 8 + Bn * 4)) return rc;
-    double* dss = sg.in(ss_xcurv, Bn * L * P * 6); double* dus = sg.in(u_ss, Bn * L * P * 2); double* dqf = sg.in(qfun, Bn * L * P);
-    double* dx = sg.in(x, Bn * 6); double* dlp = sg.in(lin_points, Bn * (N + 1) * 6); double* dli = sg.in(lin_input, Bn * N * 2);
-    double* dtr = sg.in(track, (size_t)d->n_seg * 6);
-    int32_t* dts = sg.in(time_ss, Bn * L); int32_t* dit = sg.in(iter, Bn);
-    double* dA = sg.out(A, Bn * N * 36); double* dB = sg.out(B, Bn * N * 12); double* dC = sg.out(C, Bn * N * 6);
-    double* dsel = sg.out(ss_sel, Bn * 6 * M); double* dq = sg.out(q_sel, Bn * M); int32_t* dst = sg.out(status, Bn);
-    if (int rc = sg.up(g_stream)) return rc;
+    auto dss = sg.in(ss_xcurv, Bn * L * P * 6); auto dus = sg.in(u_ss, Bn * L * P * 2); auto dqf = sg.in(qfun, Bn * L * P);
+    auto dx = sg.in(x, Bn * 6); auto dlp = sg.in(lin_points, Bn * (N + 1) * 6); auto dli = sg.in(lin_input, Bn * N * 2);
+    auto dtr = sg.in(track, (size_t)d->n_seg * 6);
+    auto dts = sg.in(time_ss, Bn * L); auto dit = sg.in(iter, Bn);
     // A, B, C are in/out: a singular stage leaves its three regression rows untouched (include/crx.h), so the staging copies
     // start from the caller's arrays, not from whatever an earlier call left in the staging buffer
-    HIP_TRY(hipMemcpyAsync(dA, A, Bn * N * 36 * sizeof(double), hipMemcpyHostToDevice, g_stream));
-    HIP_TRY(hipMemcpyAsync(dB, B, Bn * N * 12 * sizeof(double), hipMemcpyHostToDevice, g_stream));
-    HIP_TRY(hipMemcpyAsync(dC, C, Bn * N * 6 * sizeof(double), hipMemcpyHostToDevice, g_stream));
-    if (int rc = crx_lmpc_prep_dev(d, batch, dss, dus, dqf, dts, dit, dx, dlp, dli, from_plan, dtr, dA, dB, dC, dsel, dq, dst, g_stream)) return rc;
+    auto dA = sg.inout(A, Bn * N * 36); auto dB = sg.inout(B, Bn * N * 12); auto dC = sg.inout(C, Bn * N * 6);
+    auto dsel = sg.out(ss_sel, Bn * 6 * M); auto dq = sg.out(q_sel, Bn * M); auto dst = sg.out(status, Bn);
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_lmpc_prep_dev(d, batch, sg[dss], sg[dus], sg[dqf], sg[dts], sg[dit], sg[dx], sg[dlp], sg[dli], from_plan, sg[dtr], sg[dA],
+                                   sg[dB], sg[dC], sg[dsel], sg[dq], sg[dst], g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -1313,9 +1310,7 @@ int crx_lmpc_addpoint_dev(const crx_lmpcprep_desc* d, int batch, double* ss_xcur
     if (u_stride < 2) return fail(CRX_ERR_ARG, "u_stride < 2");
     if (batch == 0) return CRX_OK;
     if (!ss_xcurv || !u_ss || !time_ss || !iter || !step || !x || !u) return fail(CRX_ERR_ARG, "NULL array argument");
-    hipError_t e = crx_launch_lmpc_addpoint(*d, batch, ss_xcurv, u_ss, time_ss, iter, step, x, u, u_stride, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "lmpc addpoint launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_lmpc_addpoint(*d, batch, ss_xcurv, u_ss, time_ss, iter, step, x, u, u_stride, (hipStream_t)stream), "lmpc addpoint");
 }
 
 int crx_lmpc_addtraj_dev(const crx_lmpcprep_desc* d, int batch, const int32_t* crossed, double* log_x, const double* log_u,
@@ -1326,13 +1321,18 @@ int crx_lmpc_addtraj_dev(const crx_lmpcprep_desc* d, int batch, const int32_t* c
     if (batch == 0) return CRX_OK;
     if (!crossed || !log_x || !log_u || !n_log || !ss_xcurv || !u_ss || !qfun || !time_ss || !iter || !step || !x || !status)
         return fail(CRX_ERR_ARG, "NULL array argument");
-    hipError_t e = crx_launch_lmpc_addtraj(*d, batch, crossed, log_x, log_u, n_log, ss_xcurv, u_ss, qfun, time_ss, iter, step, x, status,
-                                           (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "lmpc addtraj launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_lmpc_addtraj(*d, batch, crossed, log_x, log_u, n_log, ss_xcurv, u_ss, qfun, time_ss, iter, step, x, status,
+                                           (hipStream_t)stream), "lmpc addtraj");
 }
 
 // ---- fused planner step ------------------------------------------------------------------------------
+// the two descriptors of the fused step are looked at before the device is (unlike every family above)
+static int check_plan_descs(const crx_planner_desc* d, const crx_select_desc* sd) {
+    if (!d || !sd) return fail(CRX_ERR_ARG, "desc is NULL");
+    if (sd->N != d->N) return fail(CRX_ERR_ARG, "planner and selection horizons differ");
+    return 0;
+}
+
 int crx_planner_plan_dev(const crx_planner_desc* d, const crx_select_desc* sd, int n_scen, const double* x0,
                          const double* bez_s, const double* bez_ey, const double* ey_lb, const double* ey_ub,
                          const int32_t* n_veh, const double* obs_s, const double* obs_ey, const int32_t* old_flag,
@@ -1347,8 +1347,7 @@ int crx_planner_plan_masked_dev(const crx_planner_desc* d, const crx_select_desc
                                 const double* ey_ub, const int32_t* n_veh, const double* obs_s, const double* obs_ey,
                                 const int32_t* old_flag, double* X, double* U, double* cost, int32_t* status, double* kkt,
                                 int32_t* iters, int32_t* flag, double* sel_cost, double* best_X, void* stream) {
-    if (!d || !sd) return fail(CRX_ERR_ARG, "desc is NULL");
-    if (sd->N != d->N) return fail(CRX_ERR_ARG, "planner and selection horizons differ");
+    if (int rc = check_plan_descs(d, sd)) return rc;
     if (int rc = check_select(sd, n_scen)) return rc;   // before R = n_veh_max + 1 sizes the QP launch
     const int R = sd->n_veh_max + 1;
     if ((long long)n_scen * R > 0x7fffffffLL) return fail(CRX_ERR_ARG, "n_scen * (n_veh_max + 1) overflows int");
@@ -1361,16 +1360,15 @@ int crx_planner_plan(const crx_planner_desc* d, const crx_select_desc* sd, int n
                      const int32_t* n_veh, const double* obs_s, const double* obs_ey, const int32_t* old_flag,
                      double* X, double* U, double* cost, int32_t* status, double* kkt, int32_t* iters,
                      int32_t* flag, double* sel_cost, double* best_X) {
-    if (!d || !sd) return fail(CRX_ERR_ARG, "desc is NULL");
-    if (sd->N != d->N) return fail(CRX_ERR_ARG, "planner and selection horizons differ");
+    if (int rc = check_plan_descs(d, sd)) return rc;
     if (n_scen < 0) return fail(CRX_ERR_ARG, "n_scen < 0");
     if (int rc = ensure_init()) return rc;
     crx_kparams chk;
     if (int rc = fill_planner(chk, d, 0)) return rc;
     if (int rc = check_select(sd, n_scen)) return rc;
     if (n_scen == 0) return CRX_OK;
-    if (!x0 || !bez_s || !bez_ey || !ey_lb || !ey_ub || !n_veh || !old_flag || !X || !U || !cost || !status || !kkt || !iters ||
-        !flag || !sel_cost || !best_X || (sd->n_veh_max > 0 && (!obs_s || !obs_ey)))
+    if (planner_null(x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters) ||
+        select_null(sd, n_veh, X, obs_s, obs_ey, old_flag, flag, sel_cost, best_X))
         return fail(CRX_ERR_ARG, "NULL array argument");
     const size_t S = (size_t)n_scen, N = (size_t)d->N, V = (size_t)sd->n_veh_max, R = V + 1, B = S * R;
     for (size_t i = 0; i < S; i++)
@@ -1378,21 +1376,17 @@ int crx_planner_plan(const crx_planner_desc* d, const crx_select_desc* sd, int n
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
     // one staging round trip for the whole step; X stays on the device between the two kernels
-    const size_t n_x0 = B * 6, n_bz = B * (N + 1), n_lb = B * N, n_ob = S * V * (N + 1);
-    const size_t n_X = B * (N + 1) * 6, n_U = B * N * 2, n_bX = S * (N + 1) * 6;
     Stage sg;
-    if (int rc = sg.reserve((n_x0 + 2 * n_bz + n_lb + B + 2 * n_ob) * 8 + 2 * S * 4,
-                            (n_X + n_U + 2 * B + S * R + n_bX) * 8 + 2 * B * 4 + S * 4)) return rc;
-    double* dx0 = sg.in(x0, n_x0); double* dbs = sg.in(bez_s, n_bz); double* dbe = sg.in(bez_ey, n_bz);
-    double* dlb = sg.in(ey_lb, n_lb); double* dub = sg.in(ey_ub, B);
-    double* dos = sg.in(obs_s, n_ob); double* doe = sg.in(obs_ey, n_ob);
-    int32_t* dnv = sg.in(n_veh, S); int32_t* dof = sg.in(old_flag, S);
-    double* dX = sg.out(X, n_X); double* dU = sg.out(U, n_U); double* dc = sg.out(cost, B); double* dk = sg.out(kkt, B);
-    int32_t* ds = sg.out(status, B); int32_t* di = sg.out(iters, B);
-    int32_t* dfl = sg.out(flag, S); double* dsc = sg.out(sel_cost, S * R); double* dbX = sg.out(best_X, n_bX);
+    auto dx0 = sg.in(x0, B * 6); auto dbs = sg.in(bez_s, B * (N + 1)); auto dbe = sg.in(bez_ey, B * (N + 1));
+    auto dlb = sg.in(ey_lb, B * N); auto dub = sg.in(ey_ub, B);
+    auto dos = sg.in(obs_s, S * V * (N + 1)); auto doe = sg.in(obs_ey, S * V * (N + 1));
+    auto dnv = sg.in(n_veh, S); auto dof = sg.in(old_flag, S);
+    auto dX = sg.out(X, B * (N + 1) * 6); auto dU = sg.out(U, B * N * 2); auto dc = sg.out(cost, B); auto dk = sg.out(kkt, B);
+    auto ds = sg.out(status, B); auto di = sg.out(iters, B);
+    auto dfl = sg.out(flag, S); auto dsc = sg.out(sel_cost, S * R); auto dbX = sg.out(best_X, S * (N + 1) * 6);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_planner_plan_dev(d, sd, n_scen, dx0, dbs, dbe, dlb, dub, dnv, dos, doe, dof, dX, dU, dc, ds, dk, di,
-                                      dfl, dsc, dbX, g_stream)) return rc;
+    if (int rc = crx_planner_plan_dev(d, sd, n_scen, sg[dx0], sg[dbs], sg[dbe], sg[dlb], sg[dub], sg[dnv], sg[dos], sg[doe], sg[dof], sg[dX],
+                                      sg[dU], sg[dc], sg[ds], sg[dk], sg[di], sg[dfl], sg[dsc], sg[dbX], g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -1409,9 +1403,7 @@ int crx_order_longest_first_dev(int batch, const int32_t* iters, const int32_t* 
     crx_order_kparams op;
     memset(&op, 0, sizeof(op));
     op.batch = batch; op.mode = 0; op.iters = iters; op.active = active; op.order = order;
-    hipError_t e = crx_launch_order(op, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "order launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_order(op, (hipStream_t)stream), "order");
 }
 
 int crx_cbf_order_dev(const crx_cbf_desc* d, int batch, const int32_t* active, const double* x0, const double* xt,
@@ -1429,9 +1421,7 @@ int crx_cbf_order_dev(const crx_cbf_desc* d, int batch, const int32_t* active, c
     op.V = d->n_obs_max; op.stride = d->N + 1; op.degree = d->degree; op.margin = d->margin; op.l_sum = d->l_sum; op.w_sum = d->w_sum;
     op.per_stage_target = d->per_stage_target; op.ds_per_vx = d->A[4 * 6 + 0]; op.xt = xt;
     op.x0 = x0; op.obs_s = obs_s; op.obs_ey = obs_ey; op.lap_off = lap_off; op.obs_dims = d->n_obs_max > 0 ? obs_dims : nullptr; op.n_obs = n_obs;
-    hipError_t e = crx_launch_order(op, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "order launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_order(op, (hipStream_t)stream), "order");
 }
 
 }  // extern "C"
@@ -1449,9 +1439,7 @@ int crx_game_traffic_dev(int N, int batch, int n_cars, double lap_length, double
     memset(&gp, 0, sizeof(gp));
     gp.Np = N; gp.batch = batch; gp.n_cars = n_cars; gp.lap_length = lap_length; gp.t = t; gp.dt = dt;
     gp.car_s0 = car_s0; gp.car_v = car_v; gp.car_ey = car_ey; gp.veh_xcurv = veh_xcurv; gp.pred_s = pred_s; gp.pred_ey = pred_ey;
-    hipError_t e = crx_launch_game(0, gp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "game traffic launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_game(0, gp, (hipStream_t)stream), "game traffic");
 }
 
 int crx_game_masks_dev(int batch, const int32_t* n_veh, const int32_t* overflow, int32_t* m_overtake, int32_t* m_lmpc,
@@ -1464,9 +1452,7 @@ int crx_game_masks_dev(int batch, const int32_t* n_veh, const int32_t* overflow,
     memset(&gp, 0, sizeof(gp));
     gp.batch = batch; gp.n_veh = n_veh; gp.m_overtake = m_overtake; gp.m_lmpc = m_lmpc;
     if (overflow && overflow_seen) { gp.overflow = overflow; gp.overflow_seen = overflow_seen; }
-    hipError_t e = crx_launch_game(1, gp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "game masks launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_game(1, gp, (hipStream_t)stream), "game masks");
 }
 
 int crx_game_commit_dev(int N, int Np, int batch, const int32_t* overtake, const double* U_track, const double* X_lmpc,
@@ -1483,9 +1469,7 @@ int crx_game_commit_dev(int N, int Np, int batch, const int32_t* overtake, const
     gp.N = N; gp.Np = Np; gp.batch = batch; gp.overtake = overtake; gp.U_track = U_track; gp.X_lmpc = X_lmpc; gp.U_lmpc = U_lmpc;
     gp.flag = flag; gp.u = u; gp.u_old = u_old; gp.u_prev = u_prev; gp.lin_points = lin_points; gp.lin_input = lin_input;
     gp.step_no = step_no; gp.addpoint_step = addpoint_step; gp.old_flag = old_flag;
-    hipError_t e = crx_launch_game(2, gp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "game commit launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_game(2, gp, (hipStream_t)stream), "game commit");
 }
 
 int crx_game_log_dev(int batch, int n_points, double lap_length, const double* xcurv, const double* u, const int32_t* laps,
@@ -1498,9 +1482,7 @@ int crx_game_log_dev(int batch, int n_points, double lap_length, const double* x
     memset(&gp, 0, sizeof(gp));
     gp.batch = batch; gp.n_points = n_points; gp.lap_length = lap_length; gp.xcurv = xcurv; gp.u = (double*)u; gp.laps = laps;
     gp.laps_prev = laps_prev; gp.log_x = log_x; gp.log_u = log_u; gp.n_log = n_log; gp.crossed = crossed;
-    hipError_t e = crx_launch_game(3, gp, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(CRX_ERR_HIP, "game log launch: %s", hipGetErrorString(e));
-    return CRX_OK;
+    return launched(crx_launch_game(3, gp, (hipStream_t)stream), "game log");
 }
 
 }  // extern "C"

@@ -35,6 +35,8 @@
 
 #include "crx_kparams.h"
 #include "crx_wave.h"
+#include "crx_num.h"
+#include "crx_ipm.h"
 
 // Preprocessor switches of this file.  Translation unit: CRX_TU_GENERAL, CRX_TU_OBSTACLES, CRX_TU_SPEC (set by the including unit).  Code generation
 // forms that the general unit and the canary builds of tools/variants.sh still exercise, because the compiler defect of DESIGN.md section 8 is open:
@@ -77,16 +79,6 @@ __device__ __forceinline__ double ipow_d(double a, int p) {
     // chain gives, enough to move a chaotic closed loop (test_mpccbf_racing_m_shape).  The empty asm keeps the product a product.
     asm volatile("" : "+v"(r));
     return r;
-}
-
-// scipy interp1d(kind="linear") (searchsorted-left, index clipped to [1,n-1], slope form)
-__device__ __forceinline__ double interp_lin(const double* xs, const double* ys, int n, double x) {
-    int hi = 0;
-    while (hi < n && xs[hi] < x) hi++;
-    hi = hi < 1 ? 1 : (hi > n - 1 ? n - 1 : hi);
-    int lo = hi - 1;
-    double slope = (ys[hi] - ys[lo]) / (xs[hi] - xs[lo]);
-    return slope * (x - xs[lo]) + ys[lo];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1544,7 +1536,7 @@ __device__ __forceinline__ void planner_fallback(double* sm, const crx_kparams& 
         double v = 0.0;
         if (i == 0) v = kp.fallback_gain * vx0;
         else if (i == 4) v = st;
-        else if (i == 5) v = interp_lin(bs, be, N + 1, fmin(fmax(st, bs[0]), bs[N]));
+        else if (i == 5) v = interp1d<INTERP_SCAN>(bs, be, N + 1, fmin(fmax(st, bs[0]), bs[N]));
         Xb[e] = v;
     }
     for (int e = lane; e < N * 2; e += WAVE) Ub[e] = 0.0;
@@ -1755,7 +1747,7 @@ crx_solve_kernel(const crx_kparams kp) {
 #pragma unroll
             for (int i = 0; i < 6; i++) LD(L::xr + j * 6 + i) = 0.0;
             LD(L::xr + j * 6 + 4) = st;
-            LD(L::xr + j * 6 + 5) = interp_lin(bs, be, N + 1, st);                         // :332
+            LD(L::xr + j * 6 + 5) = interp1d<INTERP_SCAN>(bs, be, N + 1, st);                         // :332
             if (j < N) LD(L::wc + j) = (j >= 1 && j <= N - 2) ? kp.w_dey : 0.0;            // :325-327
         }
         c.lin_sN = -kp.w_prog;                                                             // :328
@@ -1780,10 +1772,7 @@ crx_solve_kernel(const crx_kparams kp) {
                 const bool own = kp.obs_dims != nullptr && lane < c.nobs;
                 double ls = own ? kp.obs_dims[((size_t)b * kp.n_obs_max + lane) * 2] : kp.l_sum;
                 double ws = own ? kp.obs_dims[((size_t)b * kp.n_obs_max + lane) * 2 + 1] : kp.w_sum;
-                // device-resident dimensions cannot be validated on the host (the host-pointer entry point rejects them): a
-                // non-positive or non-finite entry falls back to the descriptor's pair instead of turning the rows into inf / NaN
-                if (!(ls > 0.0) || !isfinite(ls)) ls = kp.l_sum;
-                if (!(ws > 0.0) || !isfinite(ws)) ws = kp.w_sum;
+                ls = dim_or_default(ls, kp.l_sum); ws = dim_or_default(ws, kp.w_sum);
                 LD(L::cst + 16 + lane) = 1.0 / ls;
                 LD(L::cst + 16 + NOBS + lane) = 1.0 / ws;
             }
@@ -1900,7 +1889,7 @@ crx_solve_kernel(const crx_kparams kp) {
     double mact = 0.0;
     for (int j = lane; j < m; j += WAVE) mact += (LD(L::rnu + j) != 0.0) ? 1.0 : 0.0;   // rnu = presence flag of the row (table loop above)
     mact = wave_sum(mact);
-    const double kappa_sigma = 1e10, smax = 100.0, eta = 1e-8;
+    const double smax = 100.0;
     long long tph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
     // row statistics of the current iterate: sum nu, max |c - t|, max and min of t*nu over the present rows.  Computed
@@ -2037,7 +2026,8 @@ crx_solve_kernel(const crx_kparams kp) {
         const double sd = fmax(smax, nus / fmax(mact, 1.0)) / smax;
         const double e_du = dual_infeasibility<NOBS, NMAX, (StageUnroll<NFIX> > 2 ? StageUnroll<NFIX> : 1)>(sm, c);
         E0 = fmax(e_du / sd, fmax(e_p, cmax / sd));
-        if (E0 <= o.tol && e_du <= o.dual_inf_tol && e_p <= o.constr_viol_tol && cmax <= o.compl_inf_tol) { status = 0; break; }   // IPOPT's complete test
+        // IPOPT's complete test, written out: crx_ipm.h, table
+        if (E0 <= o.tol && e_du <= o.dual_inf_tol && e_p <= o.constr_viol_tol && cmax <= o.compl_inf_tol) { status = 0; break; }
         if (it >= o.max_iter) break;
         const double mu_k = gap / fmax(mact, 1.0);
         // ---- predictor: the affine-scaling direction ---------------------------------------------------
@@ -2081,7 +2071,7 @@ crx_solve_kernel(const crx_kparams kp) {
         double cr[RP], s_new = smu, s_old = 0.0, c_old = 0.0, a_p = 1.0, a_d = 1.0;
 #pragma unroll
         for (int q_ = 0; q_ < RP; q_++) cr[q_] = dta[q_] * dna[q_];
-        const double tau = fmax(o.tau_min, 1.0 - mu_k);
+        const double tau = ipm_tau(mu_k, o.tau_min);
         for (int pass = 0;; pass++) {
             const double c_new = pass == 0 ? 1.0 : 0.0;       // weight of the second-order term
             SYNC();                                           // every lane has read its dZ entries: dZ is scratch from here to the forward sweep
@@ -2219,9 +2209,10 @@ crx_solve_kernel(const crx_kparams kp) {
         if (E0 <= o.tol) {
             // [r6] IPOPT's COMPLETE termination test (OptimalityErrorConvergenceCheck; the reference runs IPOPT on its defaults): the scaled
             // error <= tol AND the unscaled dual infeasibility <= dual_inf_tol (1), constraint violation <= constr_viol_tol (1e-4),
-            // complementarity <= compl_inf_tol (1e-4).  Unscaled = no s_d, CBF rows in the reference's units (the simple rows are unscaled; t nu is
-            // invariant under the row scaling).  The second half binds on crash states: multipliers of 1e7..1e9 make s_d 1e4..1e7 and the scaled
-            // complementarity passes at mu = 1e-4 already.  Same test in oracle/crx_oracle.c.  The row pass runs on this (once-per-solve) path only.
+            // complementarity <= compl_inf_tol (1e-4); written out: crx_ipm.h, table.  Unscaled = no s_d, CBF rows in the reference's units (the
+            // simple rows are unscaled; t nu is invariant under the row scaling).  The second half binds on crash states: multipliers of
+            // 1e7..1e9 make s_d 1e4..1e7 and the scaled complementarity passes at mu = 1e-4 already.  Same test in oracle/crx_oracle.c.  The row
+            // pass runs on this (once-per-solve) path only.
             double vu = e_p;
             if (NOBS) {
                 for (int e = lane; e < N * NOBS; e += WAVE) {
@@ -2240,13 +2231,13 @@ crx_solve_kernel(const crx_kparams kp) {
             // max_j |t_j nu_j - mu| from the extremes of t*nu: no pass over the rows
             const double e_cm = fmax(cmax - mu, mu - cmin) / sd;
             const double Emu = fmax(e_d, fmax(e_p, e_cm));
-            if (Emu <= o.kappa_eps * mu && mu > o.tol / 10.0) {
-                mu = fmax(o.tol / 10.0, fmin(o.kappa_mu * mu, o.theta_mu == 1.5 ? mu * sqrt(mu) : pow(mu, o.theta_mu)));
+            if (ipm_mu_reached(Emu, mu, o.kappa_eps, o.tol)) {
+                mu = ipm_next_mu<true>(mu, o.kappa_mu, o.theta_mu, o.tol);
                 nf = 0;
             } else
                 break;
         }
-        const double tau = fmax(o.tau_min, 1.0 - mu);
+        const double tau = ipm_tau(mu, o.tau_min);
         // ---- Newton step ---------------------------------------------------------------------------
         long long tc3 = CLK();
         assemble_newton<NOBS, NMAX>(sm, si, c, mu);
@@ -2374,10 +2365,7 @@ crx_solve_kernel(const crx_kparams kp) {
         wave_sum4(theta, Dphi, cost_d, cost_qq);                    // four sums, one row reduction (crx_wave.h)
         Dphi += cost_d;
         const double phi0 = f - mu * logsum_t;
-        if (theta_min < 0.0) {
-            theta_min = 1e-4 * fmax(1.0, theta);
-            theta_max = 1e4 * fmax(1.0, theta);
-        }
+        if (theta_min < 0.0) ipm_theta_bounds(theta, theta_min, theta_max);
         long long tc7 = CLK();
         // ---- filter line search ----------------------------------------------------------------------
         double al = a_p, fn = f, lt_acc = logsum_t;
@@ -2387,12 +2375,8 @@ crx_solve_kernel(const crx_kparams kp) {
         // ... compared in the log2 domain: log2(al) + 2.3 log2(-Dphi) > 1.1 log2(theta), with log2_fast (double exponent +
         // v_log_f32 of the mantissa, ~1e-7 absolute).  Two pow() calls were ~2.6 k cycles of this iteration and kept ~50
         // VGPRs of polynomial constants alive; the test is a heuristic threshold, a tie within 1e-7 may fall either way.
-        const double sw_gap = sw_try ? 2.3 * log2_fast(-Dphi) - 1.1 * log2_fast(theta) : 0.0;
-        // The backtracking stops at alpha_min = 1e-10 ("no acceptable step"; IPOPT's alpha_min plays the same role): below it
-        // a step changes nothing in double precision relative to the iterate, the trial values differ from the current
-        // ones by rounding only, and whether the filter happens to accept one of them is noise -- on infeasible problems
-        // (slacks collapsed to ~1e-20) that noise used to decide at which iteration the solve gave up.
-        for (int ls = 0; ls < 40 && al >= 1e-10; ls++) {
+        const double sw_gap = sw_try ? IPM_S_PHI * log2_fast(-Dphi) - IPM_S_THETA * log2_fast(theta) : 0.0;
+        for (int ls = 0; ls < IPM_MAX_BACKTRACK && al >= IPM_ALPHA_MIN; ls++) {   // alpha_min: see crx_ipm.h
             fn = f + al * (cost_d + al * cost_qq);   // exact: the cost is quadratic along the step
             double thn = 0.0;
             LogAcc lg;
@@ -2429,8 +2413,8 @@ crx_solve_kernel(const crx_kparams kp) {
             }
             if (okf) {
                 if (sw_try && log2_fast(al) + sw_gap > 0.0) {
-                    if (phin <= phi0 + eta * al * Dphi + 10.0 * 2.2e-16 * fabs(phi0)) { acc = 1; ftype = 1; }
-                } else if (thn <= (1.0 - 1e-5) * theta || phin <= phi0 - 1e-8 * theta) {
+                    if (phin <= phi0 + IPM_ETA_PHI * al * Dphi + 10.0 * IPM_EPS * fabs(phi0)) { acc = 1; ftype = 1; }   // Armijo: crx_ipm.h, table
+                } else if (ipm_sufficient_decrease(theta, thn, phi0, phin)) {
                     acc = 1;
                 }
             }
@@ -2447,7 +2431,7 @@ crx_solve_kernel(const crx_kparams kp) {
             tr[0] = e_d; tr[1] = e_p; tr[2] = e_c; tr[3] = mu; tr[4] = al; tr[5] = a_d; tr[6] = dw; tr[7] = acc ? (ftype ? 2.0 : 1.0) : 0.0;
         }
         if (acc && !ftype && nf < MAXF) {
-            if (lane == 0) { LD(L::Fth + nf) = (1.0 - 1e-5) * theta; LD(L::Fph + nf) = phi0 - 1e-8 * theta; }
+            if (lane == 0) { LD(L::Fth + nf) = ipm_filter_theta(theta); LD(L::Fph + nf) = ipm_filter_phi(theta, phi0); }
             nf++;
         }
         if (!acc) { ls_failed = 1; break; }
@@ -2484,7 +2468,7 @@ crx_solve_kernel(const crx_kparams kp) {
             const double rp = rcj - rtj;                       // dnu as in the row-step pass (rc, rt, rw, rsig still hold that state)
             const double dnu = -rwj + rsj * (rp - rdj);
             double nn = rnj + a_d * dnu;
-            nn = fmin(fmax(nn, mut * (1.0 / kappa_sigma)), kappa_sigma * mut);
+            nn = ipm_dual_safeguard(nn, mut);
             LD(SINK(cnt, L::rt + j)) = tn;
             LD(SINK(cnt, L::rnu + j)) = nn;             // read-modify-write
             numax = fmax(numax, sel(cnt, nn, 0.0));     // cnt, not on: a lane past the last row re-reads row 0 AFTER its update

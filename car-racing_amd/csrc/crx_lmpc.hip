@@ -34,6 +34,7 @@
 
 #include "crx_kparams.h"
 #include "crx_wave.h"
+#include "crx_ipm.h"
 
 #define LMAXF 16
 #define LMPC_LATE_ITERS 25   // stagnation rule: iterations with mu < 1e-6 before the QP is left on its noise floor (oracle: LATE_ITERS)
@@ -493,8 +494,8 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
             e_d /= sd;
             e_c /= sc;
             E0 = fmax(e_d, fmax(e_p, e_c));
-            // [r6] IPOPT's complete test (crx_kernels.hip has the note): scaled error <= tol AND unscaled dual infeasibility / complementarity within
-            // dual_inf_tol / compl_inf_tol (rows are unscaled here: the violation test is implied by e_p <= tol)
+            // [r6] IPOPT's complete test, written out (crx_ipm.h, table): scaled error <= tol AND unscaled dual infeasibility / complementarity
+            // within dual_inf_tol / compl_inf_tol (rows are unscaled here: the violation test is implied by e_p <= tol)
             if (E0 <= o.tol && e_d * sd <= o.dual_inf_tol && e_p <= o.constr_viol_tol && e_c * sc <= o.compl_inf_tol) { status = CRX_CONVERGED; break; }
             if (it >= o.max_iter) break;
             if (mu < 1e-6 && ++late >= LMPC_LATE_ITERS) break;
@@ -526,14 +527,14 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
                 double e_cm = 0.0;
                 LROWS(r, rv, lane, m) { (void)rv; e_cm = fmax(e_cm, fabs(LDS(L::t + r) * LDS(L::nu + r) - mu)); }
                 e_cm = wave_max(e_cm) / sc;
-                if (fmax(e_d, fmax(e_p, e_cm)) <= o.kappa_eps * mu && mu > o.tol / 10.0) {
+                if (fmax(e_d, fmax(e_p, e_cm)) <= o.kappa_eps * mu && mu > o.tol / 10.0) {   // barrier update, written out: crx_ipm.h, table
                     mu = fmax(o.tol / 10.0, fmin(o.kappa_mu * mu, o.theta_mu == 1.5 ? mu * sqrt(mu) : pow(mu, o.theta_mu)));
                     nf = 0;
                 } else
                     break;
             }
             TICK();   // 3
-            const double tau = fmax(o.tau_min, 1.0 - mu);
+            const double tau = ipm_tau(mu, o.tau_min);
             // ---- Sigma (in dnu), omega = mu/t - Sigma rp (in wv); rhs = -(g + E'y - J'omega) ----
             LROWS(r, rv, lane, m) {
                 (void)rv;
@@ -787,7 +788,7 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
             Dphi += gdv;
             const double a_p = rp_max > tau ? tau / rp_max : 1.0, a_d = rd_max > tau ? tau / rd_max : 1.0;
             const double phi0 = f - mu * logsum_t;
-            if (it == 0) {
+            if (it == 0) {   // theta_min / theta_max, written out: crx_ipm.h, table
                 theta_min = 1e-4 * fmax(1.0, theta);
                 theta_max = 1e4 * fmax(1.0, theta);
             }
@@ -795,7 +796,7 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
             // ---- filter line search (all rows linear: c(v + al dv) = c + al J dv) ----
             double al = a_p, fn = f, lt = logsum_t;
             int acc = 0, ftype = 0;
-            for (int ls = 0; ls < 40 && al >= 1e-10; ls++) {   // alpha_min: see crx_kernels.hip
+            for (int ls = 0; ls < IPM_MAX_BACKTRACK && al >= IPM_ALPHA_MIN; ls++) {   // alpha_min: see crx_ipm.h
                 fn = f + al * (gdv + 0.5 * al * qd);
                 double thn = 0.0;
                 LogAcc la;
@@ -814,11 +815,11 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
                 for (int i = 0; i < nf && okf; i++)
                     if (!(thn < LDS(L::Fth + i) || phin < LDS(L::Fph + i))) okf = 0;
                 if (okf) {
-                    // switching test al (-Dphi)^2.3 > theta^1.1 in the log2 domain (crx_kernels.hip: two pow() are ~2.6 k cycles)
-                    const int sw = (Dphi < 0.0) && (log2_fast(al) + 2.3 * log2_fast(-Dphi) > 1.1 * log2_fast(theta));
+                    // switching test al (-Dphi)^s_phi > theta^s_theta (crx_ipm.h) in the log2 domain (crx_kernels.hip: two pow() are ~2.6 k cycles)
+                    const int sw = (Dphi < 0.0) && (log2_fast(al) + IPM_S_PHI * log2_fast(-Dphi) > IPM_S_THETA * log2_fast(theta));
                     if (theta <= theta_min && sw) {
-                        if (phin <= phi0 + 1e-8 * al * Dphi + 10.0 * 2.2e-16 * fabs(phi0)) { acc = 1; ftype = 1; }
-                    } else if (thn <= (1.0 - 1e-5) * theta || phin <= phi0 - 1e-8 * theta) {
+                        if (phin <= phi0 + IPM_ETA_PHI * al * Dphi + 10.0 * IPM_EPS * fabs(phi0)) { acc = 1; ftype = 1; }   // Armijo: crx_ipm.h, table
+                    } else if (ipm_sufficient_decrease(theta, thn, phi0, phin)) {
                         acc = 1;
                     }
                 }
@@ -827,8 +828,8 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
             }
             if (acc && !ftype && nf < LMAXF) {
                 if (lane == 0) {
-                    LDS(L::Fth + nf) = (1.0 - 1e-5) * theta;
-                    LDS(L::Fph + nf) = phi0 - 1e-8 * theta;
+                    LDS(L::Fth + nf) = ipm_filter_theta(theta);
+                    LDS(L::Fph + nf) = ipm_filter_phi(theta, phi0);
                 }
                 nf++;
             }
@@ -843,7 +844,7 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
                 const double tn = fmax(fma(al, rpr + jd, tt), cj);
                 double nn = fma(a_d, LDS(L::dnu + r), LDS(L::nu + r));
                 const double mut = mu * frcp(tn);
-                nn = fmin(fmax(nn, mut * 1e-10), mut * 1e10);
+                nn = ipm_dual_safeguard(nn, mut);
                 LDS(LSINK(rv, L::t + r)) = tn;          // read-modify-write
                 LDS(LSINK(rv, L::nu + r)) = nn;
                 numax = fmax(numax, sel(rv, nn, 0.0));

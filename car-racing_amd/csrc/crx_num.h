@@ -1,0 +1,71 @@
+// crx_num.h -- small numerics that the prep kernels (crx_prep.hip) and the solver's set-up (crx_kernels.hip) share, each stated once.
+// Plain per-thread functions over pointers and scalars; not wave primitives (those are crx_wave.h, pinned by tests/wave_model.py).
+//
+// A site goes through a function here only where the kernel's machine code stayed bit for bit what it was (tools/kernel_diff.py);
+// the table at the end lists the others.
+//
+// Floating-point contraction: both units include this header at their head, in the compiler's default state (hipcc: contraction
+// on).  interp1d() (slope * dx + y) and lap_fold() (s - laps * L) contain a multiply-add and may fuse, as the written-out
+// copies did; none of them is called from under `#pragma clang fp contract(off)` (crx_game_traffic_kernel, crx_lmpcprep.hip).
+#ifndef CRX_NUM_H
+#define CRX_NUM_H
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stddef.h>
+
+// ---- scipy interp1d(kind="linear") ---------------------------------------------------------------------------------------------
+// searchsorted-left (first index with xs[i] >= x), index clipped to [1, n-1], slope form -- so a point outside the table is
+// extrapolated from the first / last interval, and x = xs[0] takes the first.  As used at planner_helper.py:121-134,
+// overtake_traj_planner.py:332 and control.py:373-382.  Two searches, one clip and slope tail: INTERP_SCAN, a linear scan (tables of
+// a horizon's length); INTERP_BISECT, a bisection (the optimal line's few hundred points).  (One function with a compile-time
+// search: with the tail as a function of its own under two named searches, crx_prep_kernel's code changes.)
+enum InterpSearch { INTERP_SCAN, INTERP_BISECT };
+template <InterpSearch HOW>
+__device__ __forceinline__ double interp1d(const double* xs, const double* ys, int n, double x) {
+    int hi = 0;   // first index with xs[hi] >= x
+    if constexpr (HOW == INTERP_BISECT) {
+        int end = n;
+        while (hi < end) {
+            const int mid = (hi + end) >> 1;
+            if (xs[mid] < x) hi = mid + 1; else end = mid;
+        }
+    } else {
+        while (hi < n && xs[hi] < x) hi++;
+    }
+    hi = hi < 1 ? 1 : (hi > n - 1 ? n - 1 : hi);
+    const int lo = hi - 1;
+    const double slope = (ys[hi] - ys[lo]) / (xs[hi] - xs[lo]);
+    return slope * (x - xs[lo]) + ys[lo];
+}
+
+// ---- obstacle window of control.mpccbf / mpc_multi_agents (control.py:293-309, :500-519) ----------------------------------------
+// lap_fold: a position folded into one lap, and the laps taken off (int() of the reference truncates toward zero).
+// safety_window: is an obstacle at s_obs inside +- margin (= safety_time * vx) of the ego, both folded?  lap_off: what brings the
+// obstacle's unfolded positions onto the ego's lap.
+__device__ __forceinline__ double lap_fold(double s, double L, double& laps) {
+    laps = trunc(s / L);
+    return s - laps * L;
+}
+__device__ __forceinline__ bool safety_window(double dist_ego, double laps_ego, double s_obs, double margin, double L, double& lap_off) {
+    double laps_obs;
+    const double dist_obs = lap_fold(s_obs, L, laps_obs);
+    lap_off = (laps_ego - laps_obs) * L;
+    return dist_ego > dist_obs - margin && dist_ego < dist_obs + margin;
+}
+
+// ---- obstacle dimensions ------------------------------------------------------------------------------------------------------
+// device-resident dimensions cannot be validated on the host (the host-pointer entry point rejects them): a non-positive or
+// non-finite entry falls back to the descriptor's value instead of turning the rows into inf / NaN
+__device__ __forceinline__ double dim_or_default(double v, double dflt) { return (!(v > 0.0) || !isfinite(v)) ? dflt : v; }
+
+// ---- Sites that are NOT shared, and why each stays ---------------------------------------------------------------------------------
+// "code changes": as in crx_ipm.h -- same arithmetic, but through a function the kernel's machine code is no longer what it was.
+// Lines as of this header's last edit; the kernel and its comment "crx_num.h" find the site.
+//   strided interp1d        crx_trackprep_kernel (crx_prep.hip:171-185)      the scan over the trajectory's rows (stride 6): code changes through a
+//                                                                            strided interp1d, also with the column offsets as template parameters
+//   zeroed obstacle slots   crx_trackprep_kernel (crx_prep.hip:205-210)      code changes in crx_trackprep_kernel with any shared form, down to the inner
+//                           crx_cbfprep_kernel (crx_prep.hip:336-341)        loop alone; a function with one caller is no sharing, so both copies stay
+//   super-ellipse value     crx_order_key (crx_prep.hip:632-634, :648-650)   code changes as a lambda and as a function (the loop over the degree)
+//   curvature lookup        the plant of crx_prep.hip (LDS tables), crx_lmpcprep.hip (global table, contraction off): two storage forms; left alone
+
+#endif

@@ -19,20 +19,8 @@
 
 #include "crx_kparams.h"
 #include "crx_wave.h"
-
-// scipy interp1d(kind="linear") (searchsorted-left, index clipped to [1,n-1], slope form), as used at
-// planner_helper.py:121-134
-__device__ __forceinline__ double prep_interp(const double* xs, const double* ys, int n, double x) {
-    int lo = 0, hi = n;   // first index with xs[i] >= x
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (xs[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    int i1 = lo < 1 ? 1 : (lo > n - 1 ? n - 1 : lo);
-    const int i0 = i1 - 1;
-    const double slope = (ys[i1] - ys[i0]) / (xs[i1] - xs[i0]);
-    return slope * (x - xs[i0]) + ys[i0];
-}
+#include "crx_num.h"
+#include "crx_ipm.h"
 
 __global__ void __launch_bounds__(WAVE) crx_prep_kernel(const crx_prep_kparams pp) {
     const int s = blockIdx.x, lane = threadIdx.x;
@@ -49,7 +37,7 @@ __global__ void __launch_bounds__(WAVE) crx_prep_kernel(const crx_prep_kparams p
     const double s1 = span / 3.0 + s0, s2 = 2.0 * span / 3.0 + s0;
     // end point rides the optimal trajectory (:121-134)
     const double s_end = s3 >= L ? s3 - L : s3;
-    const double e3 = s_end <= pp.opt_s[0] ? pp.opt_ey[0] : prep_interp(pp.opt_s, pp.opt_ey, pp.n_opt, s_end);
+    const double e3 = s_end <= pp.opt_s[0] ? pp.opt_ey[0] : interp1d<INTERP_BISECT>(pp.opt_s, pp.opt_ey, pp.n_opt, s_end);
     const double e0 = xw[5];   // :95 overrides :87-94
     for (int e = lane; e < R * (N + 1); e += WAVE) {
         const int r = e / (N + 1), j = e - r * (N + 1);
@@ -180,7 +168,8 @@ __global__ void __launch_bounds__(256) crx_trackprep_kernel(const crx_trackprep_
     const double* x = tp.x + (size_t)6 * b;
     const double* tr = tp.traj + (size_t)b * N1 * 6;
     const double L = tp.lap_length, vx = x[0], se = x[4];
-    // targets: s clipped to the trajectory's range, scipy interp1d(kind="linear") (searchsorted-left, index in [1, n-1], slope form)
+    // targets: s clipped to the trajectory's range, scipy interp1d(kind="linear") over the trajectory's (s, ey) columns: the scan of
+    // interp1d<INTERP_SCAN> (crx_num.h) at stride 6, written out (the table at the end of crx_num.h says why)
     const double s_lo = tr[4], s_hi = tr[(size_t)N * 6 + 4];
     for (int i = 0; i <= N; i++) {
         double s = se + vx * tp.dt_ref * i;
@@ -195,20 +184,21 @@ __global__ void __launch_bounds__(256) crx_trackprep_kernel(const crx_trackprep_
         xt[0] = vx; xt[1] = 0.0; xt[2] = 0.0; xt[3] = 0.0; xt[4] = 0.0;
         xt[5] = slope * (s - tr[(size_t)lo * 6 + 4]) + tr[(size_t)lo * 6 + 5];
     }
-    // obstacles: +-safety_time*vx window on the lap-folded positions (int() truncation as in the reference), lap offsets, packing
+    // obstacles: the safety-time window, lap offsets, packing
     const double margin = tp.safety_time * vx;
-    const double nce = trunc(se / L), dist_ego = se - nce * L;
+    double nce;
+    const double dist_ego = lap_fold(se, L, nce);
     const int nv = min(max(tp.n_veh[b], 0), V);
     int n = 0;
     for (int v = 0; v < nv; v++) {
         const double* is = tp.obs_s_in + ((size_t)b * V + v) * N1;
         const double* ie = tp.obs_ey_in + ((size_t)b * V + v) * N1;
-        const double nco = trunc(is[0] / L), dist_obs = is[0] - nco * L;
-        if (dist_ego > dist_obs - margin && dist_ego < dist_obs + margin) {
+        double off;
+        if (safety_window(dist_ego, nce, is[0], margin, L, off)) {
             double* os = tp.obs_s + ((size_t)b * V + n) * N1;
             double* oe = tp.obs_ey + ((size_t)b * V + n) * N1;
             for (int j = 0; j < N1; j++) { os[j] = is[j]; oe[j] = ie[j]; }
-            tp.lap_off[(size_t)b * V + n] = (nce - nco) * L;
+            tp.lap_off[(size_t)b * V + n] = off;
             n++;
         }
     }
@@ -324,13 +314,14 @@ __global__ void __launch_bounds__(256) crx_cbfprep_kernel(const crx_cbfprep_kpar
     const int N = cp.N, V = cp.V;
     const double L = cp.lap_length, vx = cp.xcurv[6 * (size_t)b], se = cp.xcurv[6 * (size_t)b + 4];
     const double margin = cp.safety_time * vx;
-    const double nce = trunc(se / L), dist_ego = se - nce * L;
+    double nce;
+    const double dist_ego = lap_fold(se, L, nce);
     int n = 0;
     for (int v = 0; v < V; v++) {
         const double s0 = cp.car_s0[(size_t)b * V + v], sv = cp.car_v[(size_t)b * V + v], ey = cp.car_ey[(size_t)b * V + v];
         const double s_now = sv * (cp.t + 0 * cp.dt) + s0;
-        const double nco = trunc(s_now / L), dist_obs = s_now - nco * L;
-        if (dist_ego > dist_obs - margin && dist_ego < dist_obs + margin) {
+        double off;
+        if (safety_window(dist_ego, nce, s_now, margin, L, off)) {
             double* os = cp.obs_s + ((size_t)b * V + n) * (N + 1);
             double* oe = cp.obs_ey + ((size_t)b * V + n) * (N + 1);
             for (int j = 0; j <= N; j++) {
@@ -338,7 +329,7 @@ __global__ void __launch_bounds__(256) crx_cbfprep_kernel(const crx_cbfprep_kpar
                 os[j] = sv * tj + s0;
                 oe[j] = ey + 0.0 * tj;
             }
-            cp.lap_off[(size_t)b * V + n] = (nce - nco) * L;
+            cp.lap_off[(size_t)b * V + n] = off;
             n++;
         }
     }
@@ -418,17 +409,18 @@ __global__ void __launch_bounds__(WAVE) crx_path_kernel(const crx_path_kparams p
         const double e_c = wave_max(fmax(hasL ? tL * nL : 0.0, hasU ? tU * nU : 0.0)) / sd;
         const double theta = wave_sum(fabs(rpL) + fabs(rpU));
         E0 = fmax(e_d, fmax(e_p, e_c));
-        if (E0 <= o.tol && e_d * sd <= o.dual_inf_tol && e_p <= o.constr_viol_tol && e_c * sd <= o.compl_inf_tol) { st = CRX_CONVERGED; break; }   // [r6] IPOPT's complete test
+        // IPOPT's complete test, written out: crx_ipm.h, table
+        if (E0 <= o.tol && e_d * sd <= o.dual_inf_tol && e_p <= o.constr_viol_tol && e_c * sd <= o.compl_inf_tol) { st = CRX_CONVERGED; break; }
         if (it >= o.max_iter) break;
         for (;;) {
             const double e_cm = wave_max(fmax(hasL ? fabs(tL * nL - mu) : 0.0, hasU ? fabs(tU * nU - mu) : 0.0)) / sd;
-            if (fmax(e_d, fmax(e_p, e_cm)) <= o.kappa_eps * mu && mu > o.tol / 10.0) {
-                mu = fmax(o.tol / 10.0, fmin(o.kappa_mu * mu, pow(mu, o.theta_mu)));
+            if (ipm_mu_reached(fmax(e_d, fmax(e_p, e_cm)), mu, o.kappa_eps, o.tol)) {
+                mu = ipm_next_mu<false>(mu, o.kappa_mu, o.theta_mu, o.tol);   // (pow() for every theta_mu)
                 nf = 0;
             } else
                 break;
         }
-        const double tau = fmax(o.tau_min, 1.0 - mu);
+        const double tau = ipm_tau(mu, o.tau_min);
         // Newton matrix (lower triangle, row per lane) with the right-hand side as the extra row
         const double sgL = hasL ? nL / tL : 0.0, sgU = hasU ? nU / tU : 0.0;
         const double rhs = mine ? -g + (hasL ? mu / tL - sgL * rpL : 0.0) - (hasU ? mu / tU - sgU * rpU : 0.0) : 0.0;
@@ -461,10 +453,10 @@ __global__ void __launch_bounds__(WAVE) crx_path_kernel(const crx_path_kparams p
         if (hasL) l0.mul(tL);
         if (hasU) l0.mul(tU);
         const double phi0 = f - mu * l0.wave_total();
-        if (it == 0) { theta_min = 1e-4 * fmax(1.0, theta); theta_max = 1e4 * fmax(1.0, theta); }
+        if (it == 0) ipm_theta_bounds(theta, theta_min, theta_max);
         double al = a_p, fn = f, tLn = tL, tUn = tU;
         int acc = 0, ftype = 0;
-        for (int ls = 0; ls < 40 && al >= 1e-10; ls++) {   // alpha_min: see crx_kernels.hip
+        for (int ls = 0; ls < IPM_MAX_BACKTRACK && al >= IPM_ALPHA_MIN; ls++) {
             fn = f + al * (gdv + 0.5 * al * qd);
             const double vt = vi + al * d;
             tLn = hasL ? fmax(tL + al * dtL, vt - lj) : 1.0;
@@ -478,10 +470,10 @@ __global__ void __launch_bounds__(WAVE) crx_path_kernel(const crx_path_kparams p
             for (int i = 0; i < nf && okf; i++)
                 if (!(thn < Fth[i] || phin < Fph[i])) okf = 0;
             if (okf) {
-                const int sw = (Dphi < 0.0) && (al * pow(-Dphi, 2.3) > pow(theta, 1.1));
-                if (theta <= theta_min && sw) {
-                    if (phin <= phi0 + 1e-8 * al * Dphi + 10.0 * 2.2e-16 * fabs(phi0)) { acc = 1; ftype = 1; }
-                } else if (thn <= (1.0 - 1e-5) * theta || phin <= phi0 - 1e-8 * theta) {
+                const int sw = (Dphi < 0.0) && (al * pow(-Dphi, IPM_S_PHI) > pow(theta, IPM_S_THETA));   // (the other kernels: log2 domain)
+                if (theta <= theta_min && sw) {   // Armijo, written out: crx_ipm.h, table
+                    if (phin <= phi0 + IPM_ETA_PHI * al * Dphi + 10.0 * IPM_EPS * fabs(phi0)) { acc = 1; ftype = 1; }
+                } else if (ipm_sufficient_decrease(theta, thn, phi0, phin)) {
                     acc = 1;
                 }
             }
@@ -489,15 +481,16 @@ __global__ void __launch_bounds__(WAVE) crx_path_kernel(const crx_path_kparams p
             al *= 0.5;
         }
         if (acc && !ftype && nf < 16) {
-            if (lane == 0) { Fth[nf] = (1.0 - 1e-5) * theta; Fph[nf] = phi0 - 1e-8 * theta; }
+            if (lane == 0) { Fth[nf] = ipm_filter_theta(theta); Fph[nf] = ipm_filter_phi(theta, phi0); }
             nf++;
         }
         if (!acc) break;
         vi += al * d;
         f = fn;
         tL = tLn; tU = tUn;
-        if (hasL) nL = fmin(fmax(nL + a_d * dnL, mu / (1e10 * tL)), 1e10 * mu / tL);
-        if (hasU) nU = fmin(fmax(nU + a_d * dnU, mu / (1e10 * tU)), 1e10 * mu / tU);
+        // (dual safeguard in this kernel's own arithmetic order, not ipm_dual_safeguard's: crx_ipm.h, table at the end)
+        if (hasL) nL = fmin(fmax(nL + a_d * dnL, mu / (IPM_KAPPA_SIGMA * tL)), IPM_KAPPA_SIGMA * mu / tL);
+        if (hasU) nU = fmin(fmax(nU + a_d * dnU, mu / (IPM_KAPPA_SIGMA * tU)), IPM_KAPPA_SIGMA * mu / tU);
         if (mine) v[lane] = vi;
         SYNC();
     }
@@ -634,13 +627,11 @@ __device__ __forceinline__ int crx_order_key(const crx_order_kparams& op, int b)
     for (int o = 0; o < n; o++) {
         const size_t r = (size_t)b * V + o;
         double ls = op.obs_dims ? op.obs_dims[r * 2] : op.l_sum, ws = op.obs_dims ? op.obs_dims[r * 2 + 1] : op.w_sum;
-        // same fall-back as the solver kernel (crx_kernels.hip set-up): a non-positive or non-finite device-resident entry -> the descriptor's pair
-        if (!(ls > 0.0) || !isfinite(ls)) ls = op.l_sum;
-        if (!(ws > 0.0) || !isfinite(ws)) ws = op.w_sum;
+        ls = dim_or_default(ls, op.l_sum); ws = dim_or_default(ws, op.w_sum);   // the solver kernel's fall-back
         const double ds = (op.obs_s[r * op.stride] + op.lap_off[r] - s) / ls, de = (op.obs_ey[r * op.stride] - ey) / ws;
         double ps = ds * ds, pe = de * de;
         for (int k = 2; k < op.degree; k += 2) { ps *= ds * ds; pe *= de * de; }
-        hmin = fmin(hmin, ps + pe - 1.0 - op.margin);
+        hmin = fmin(hmin, ps + pe - 1.0 - op.margin);   // (the barrier value is written out here and below: crx_num.h, table at the end)
     }
     if (!(hmin == hmin) || !(vx0_finite(op, b))) return 0;   // NaN inputs (device-resident data cannot be validated on the host): first, like the deepest crash state
     if (hmin < 0.0) return min(max((int)((hmin + 1.0 + op.margin) * (128.0 / (1.0 + op.margin))), 0), 127);
@@ -652,8 +643,7 @@ __device__ __forceinline__ int crx_order_key(const crx_order_kparams& op, int b)
         for (int o = 0; o < n; o++) {
             const size_t r = (size_t)b * V + o;
             double ls = op.obs_dims ? op.obs_dims[r * 2] : op.l_sum, ws = op.obs_dims ? op.obs_dims[r * 2 + 1] : op.w_sum;
-            if (!(ls > 0.0) || !isfinite(ls)) ls = op.l_sum;
-            if (!(ws > 0.0) || !isfinite(ws)) ws = op.w_sum;
+            ls = dim_or_default(ls, op.l_sum); ws = dim_or_default(ws, op.w_sum);
             const double ds = (op.obs_s[r * op.stride + j] + op.lap_off[r] - sj) / ls, de = (op.obs_ey[r * op.stride + j] - eyj) / ws;
             double ps = ds * ds, pe = de * de;
             for (int k = 2; k < op.degree; k += 2) { ps *= ds * ds; pe *= de * de; }

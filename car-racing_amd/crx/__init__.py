@@ -81,8 +81,13 @@ def lmpc_solve(desc, x0, u_old, A, B, Cm, ss, qfun, n_ss=None):
     return binding().lmpc_solve(desc, x0, u_old, A, B, Cm, ss, qfun, n_ss)
 
 
-def ilqr_solve(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs):
-    return binding().ilqr_solve(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs)
+def ilqr_solve(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, models=None):
+    return binding().ilqr_solve(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, models)
+
+
+def lqr_design(desc, A, B, want_P=True):
+    """Batched LQR design (include/crx.h L1..L4) on host arrays: see abi.Binding.lqr_design."""
+    return binding().lqr_design(desc, A, B, want_P)
 
 
 def sysid_fit(x, u, offsets=None, group_offsets=None, lamb=1e-9):

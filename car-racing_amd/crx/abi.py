@@ -14,6 +14,7 @@ CRX_MAX_OBS = 6     # obstacles per MPC-CBF NLP
 CRX_MAX_VEH = 6     # vehicles of interest per planner scenario (= CRX_MAX_OBS)
 
 CRX_CONVERGED, CRX_MAX_ITER, CRX_INFEASIBLE, CRX_RESTORED, CRX_SKIPPED, CRX_STALLED = 0, 1, 2, 3, 4, 5
+CRX_SINGULAR = 6    # crx_sysid_fit, crx_lqr_design
 
 
 class IpmOpts(C.Structure):
@@ -136,6 +137,16 @@ class IlqrDesc(C.Structure):
         ("q2", C.c_double),
         ("l_sum", C.c_double),
         ("w_sum", C.c_double),
+    ]
+
+
+class LqrDesc(C.Structure):
+    _fields_ = [
+        ("max_iter", C.c_int32),
+        ("pad_", C.c_int32),
+        ("Q", C.c_double * 36),
+        ("R", C.c_double * 4),
+        ("eps", C.c_double),
     ]
 
 
@@ -266,6 +277,26 @@ def ilqr_desc(N, A, B, Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]), R=np.diag([0
                     l_sum, w_sum)
 
 
+def lqr_desc(Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]), R=np.diag([0.1, 0.1]), max_iter=50, eps=0.01):
+    """Defaults = LQRTrackingParam (utils/base.py) and the literal eps of control.lqr (control.py:44).  Q, R are full matrices (a 1-D
+    argument is a diagonal)."""
+    Q, R = np.asarray(Q, dtype=float), np.asarray(R, dtype=float)
+    Q = np.diag(Q) if Q.ndim == 1 else Q
+    R = np.diag(R) if R.ndim == 1 else R
+    return LqrDesc(int(max_iter), 0, _arr(C.c_double, 36, Q), _arr(C.c_double, 4, R), float(eps))
+
+
+def lqr_models(A, B, batch=None):
+    """(A [Bn,6,6], B [Bn,6,2]) float64 from one model (6,6), (6,2) -- repeated `batch` times when given -- or per-problem models."""
+    A, B = np.asarray(A, dtype=_D), np.asarray(B, dtype=_D)
+    if A.ndim == 2 and B.ndim == 2:
+        A, B = A[None], B[None]
+        if batch is not None:
+            A, B = np.repeat(A, batch, axis=0), np.repeat(B, batch, axis=0)
+    Bn = A.shape[0] if batch is None else batch
+    return _in(A, _D, (Bn, 6, 6)), _in(B, _D, (Bn, 6, 2))
+
+
 def sysid_desc(lamb=1e-9, first_row=1, chunk_rows=8192):
     """crx_sysid_desc_default: lamb of system_identification_test.py:42; first_row = 1 drops row 0 (S1)."""
     return SysidDesc(float(lamb), int(first_row), int(chunk_rows))
@@ -330,7 +361,7 @@ class Binding:
     def __init__(self, lib, prefix):
         self.lib, self.prefix = lib, prefix
         for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve", "ilqr_solve",
-                     "sysid_fit"):
+                     "ilqr_solve_models", "lqr_design", "sysid_fit"):
             if hasattr(lib, prefix + name):
                 getattr(lib, prefix + name).restype = C.c_int
         self._check = None
@@ -365,8 +396,9 @@ class Binding:
         )
         return out
 
-    def ilqr_solve(self, desc, x0, xt, obs_s, obs_ey, lap_off, n_obs):
+    def ilqr_solve(self, desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, models=None):
         """crx_ilqr_solve.  x0, xt (Bn,6); obs_s, obs_ey (Bn,V,N+1); lap_off (Bn,V); n_obs (Bn,) with V = desc.n_obs_max.
+        models = (A (Bn,6,6), B (Bn,6,2)): crx_ilqr_solve_models, problem b on its own model (desc.A, desc.B are ignored).
         Returns X (Bn,N+1,6), U (Bn,N,2), cost, status, iters."""
         N, V = desc.N, desc.n_obs_max
         x0 = np.ascontiguousarray(x0, dtype=_D)
@@ -379,8 +411,25 @@ class Binding:
         n_obs = _in(n_obs, _I, (Bn,))
         out = dict(X=np.zeros((Bn, N + 1, 6)), U=np.zeros((Bn, N, 2)), cost=np.zeros(Bn), status=np.zeros(Bn, dtype=_I),
                    iters=np.zeros(Bn, dtype=_I))
+        if models is not None:
+            mA, mB = _in(models[0], _D, (Bn, 6, 6)), _in(models[1], _D, (Bn, 6, 2))
+            self._call("ilqr_solve_models", C.byref(desc), C.c_int(Bn), _p(x0), _p(mA), _p(mB), _p(xt), _p(obs_s), _p(obs_ey),
+                       _p(lap_off), _p(n_obs), _p(out["X"]), _p(out["U"]), _p(out["cost"]), _p(out["status"]), _p(out["iters"]))
+            return out
         self._call("ilqr_solve", C.byref(desc), C.c_int(Bn), _p(x0), _p(xt), _p(obs_s), _p(obs_ey), _p(lap_off), _p(n_obs),
                    _p(out["X"]), _p(out["U"]), _p(out["cost"]), _p(out["status"]), _p(out["iters"]))
+        return out
+
+    def lqr_design(self, desc, A, B, want_P=True):
+        """crx_lqr_design.  A (Bn,6,6), B (Bn,6,2), or one model (6,6), (6,2).  Returns K (Bn,2,6), P (Bn,6,6) (the P behind K;
+        absent with want_P False), iters, status."""
+        A, B = lqr_models(A, B)
+        Bn = A.shape[0]
+        out = dict(K=np.zeros((Bn, 2, 6)), iters=np.zeros(Bn, dtype=_I), status=np.zeros(Bn, dtype=_I))
+        if want_P:
+            out["P"] = np.zeros((Bn, 6, 6))
+        self._call("lqr_design", C.byref(desc), C.c_int(Bn), _p(A), _p(B), _p(out["K"]), _p(out["P"]) if want_P else None,
+                   _p(out["iters"]), _p(out["status"]))
         return out
 
     def sysid_fit(self, desc, x, u, offsets=None, group_offsets=None):

@@ -36,6 +36,19 @@ class _Noise:
         return torch.randn((batch, 3), generator=self.gen, dtype=torch.float64, device=self.device)
 
 
+def _models(A, B, batch, dev):
+    """(A [batch,6,6], B [batch,6,2]) contiguous float64 on `dev` from one model (6,6), (6,2) or per-problem models, host arrays
+    or device tensors (as PidLaps.identify() returns them)."""
+    f64 = dict(dtype=torch.float64, device=dev)
+    A = A.to(**f64) if torch.is_tensor(A) else torch.as_tensor(np.ascontiguousarray(A, dtype=float), **f64)
+    B = B.to(**f64) if torch.is_tensor(B) else torch.as_tensor(np.ascontiguousarray(B, dtype=float), **f64)
+    if A.dim() == 2 and B.dim() == 2:
+        A, B = A.expand(batch, 6, 6), B.expand(batch, 6, 2)
+    if tuple(A.shape) != (batch, 6, 6) or tuple(B.shape) != (batch, 6, 2):
+        raise ValueError("models: expected shapes %s and %s, got %s and %s" % ((batch, 6, 6), (batch, 6, 2), tuple(A.shape), tuple(B.shape)))
+    return A.contiguous(), B.contiguous()
+
+
 def _order(obj, iters, active=None):
     """Dispatch order of the next solver launch (include/crx.h, "Dispatch order"): obj.dispatch = "longest_first" lists the races
     whose previous solve took most iterations first (and the masked-out ones last); "index" (default) = launch order."""
@@ -257,7 +270,7 @@ class IlqrRaces:
     (int(s_ego / L) - int(s_obs,0 / L)) L (quirk I5), ONE crx_ilqr_solve_dev over all races, ONE crx_plant_step_wrap_dev."""
 
     def __init__(self, track_table, lap_length, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, vt=0.8, eyt=0.0, N=50,
-                 max_iter=150, timestep=0.1, ego_dims=(0.4, 0.2), car_dims=(0.4, 0.2), device=None, noise_seed=None):
+                 max_iter=150, timestep=0.1, ego_dims=(0.4, 0.2), car_dims=(0.4, 0.2), device=None, noise_seed=None, models=None):
         dev = torch.device(device if device is not None else "cuda")
         f64 = dict(dtype=torch.float64, device=dev)
         self.noise = _Noise(noise_seed, dev)
@@ -279,6 +292,8 @@ class IlqrRaces:
         self.xg_next, self.xc_next = torch.empty_like(self.xg), torch.empty_like(self.xc)
         self.t = 0.0   # the scripted car's clock, advanced by `+= timestep` like the reference's (base.py:889)
         self.u = None
+        # models = (A [B,6,6], B [B,6,2]): every race on its own model (crx_ilqr_solve_models_dev); A, B above are then unused
+        self.models = None if models is None else _models(models[0], models[1], Bn, dev)
 
     def predictions(self):
         """(obs_s, obs_ey [B,1,N+1], lap_off [B,1]) of the current step."""
@@ -291,7 +306,7 @@ class IlqrRaces:
 
     def step(self):
         obs_s, obs_e, lap_off = self.predictions()
-        torch_api.ilqr_solve_dev(self.desc, self.xc, self.xt, obs_s, obs_e, lap_off, self.n_obs, ws=self.ws)
+        torch_api.ilqr_solve_dev(self.desc, self.xc, self.xt, obs_s, obs_e, lap_off, self.n_obs, ws=self.ws, models=self.models)
         torch_api.plant_step_wrap_dev(self.pdesc, self.tab, self.xg, self.xc, self.ws.U, 2 * self.N, self.xg_next, self.xc_next,
                                       self.laps, noise_z=self.noise.draw(self.batch))
         self.xg, self.xg_next = self.xg_next, self.xg
@@ -301,11 +316,12 @@ class IlqrRaces:
 
 
 def ilqr_races(track_table, lap_length, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, steps, vt=0.8, eyt=0.0, N=50, max_iter=150,
-               timestep=0.1, device=None, log_every=1):
-    """xcurv0, xglob0 [B,6]; car_s0, car_v, car_ey [B]: one scripted car per race.  Returns host arrays: xcurv [T+1,B,6]
-    (T = steps / log_every), u [T,B,2], status [T,B], iters [T,B], laps [B]."""
+               timestep=0.1, device=None, log_every=1, models=None):
+    """xcurv0, xglob0 [B,6]; car_s0, car_v, car_ey [B]: one scripted car per race; models = (A [B,6,6], B [B,6,2]): one model per
+    race (host arrays or device tensors).  Returns host arrays: xcurv [T+1,B,6] (T = steps / log_every), u [T,B,2], status [T,B],
+    iters [T,B], laps [B]."""
     r = IlqrRaces(track_table, lap_length, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, vt=vt, eyt=eyt, N=N, max_iter=max_iter,
-                  timestep=timestep, device=device)
+                  timestep=timestep, device=device, models=models)
     log_x, log_u, log_st, log_it = [r.xc.clone()], [], [], []
     for k in range(steps):
         r.step()
@@ -696,3 +712,57 @@ def pid_laps(track_table, lap_length, xcurv0, xglob0, steps, vt=0.5, eyt=0.0, ti
     """PidLaps run to the end: the logs stay on the device (r.x_log, r.u_log); r.identify(lamb) fits them."""
     return PidLaps(track_table, lap_length, xcurv0, xglob0, steps, vt=vt, eyt=eyt, timestep=timestep, noise_z=noise_z,
                    noise_seed=noise_seed, device=device).run()
+
+
+class LqrLaps:
+    """B cars under the reference's LQR tracking controller (car_racing/tests/control_test.py --ctrl-policy lqr: one car under
+    LQRTracking on its own), each on its own LTI model, device-resident.  The gain depends on the model only: ONE
+    crx_lqr_design_dev in the constructor, then per control step ONE crx_lqr_step_dev (u = -K (x - xt)) and ONE
+    crx_plant_step_wrap_dev.  A, B: one model (6,6), (6,2) for every car or per-car models [B,6,6], [B,6,2], host arrays or device
+    tensors as PidLaps.identify() returns them.  A car whose design is CRX_SINGULAR (a failed fit's NaN model) has a NaN gain
+    and drives NaN inputs: `design.status` says which."""
+
+    def __init__(self, track_table, lap_length, xcurv0, xglob0, A, B, Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]), R=np.diag([0.1, 0.1]),
+                 vt=0.8, eyt=0.0, max_iter=50, eps=0.01, timestep=0.1, device=None, noise_seed=None):
+        dev = torch.device(device if device is not None else "cuda")
+        f64 = dict(dtype=torch.float64, device=dev)
+        self.noise = _Noise(noise_seed, dev)
+        self.xc = torch.as_tensor(np.ascontiguousarray(xcurv0), **f64).clone()
+        self.xg = torch.as_tensor(np.ascontiguousarray(xglob0), **f64).clone()
+        Bn = self.xc.shape[0]
+        self.batch, self.lap_length, self.timestep = Bn, lap_length, timestep
+        self.tab = torch.as_tensor(np.ascontiguousarray(track_table), **f64)
+        self.A, self.B = _models(A, B, Bn, dev)
+        self.desc = abi.lqr_desc(Q=Q, R=R, max_iter=max_iter, eps=eps)
+        self.pdesc = abi.plant_desc(self.tab.shape[0], lap_length, timestep=timestep)
+        self.xt = torch.zeros((Bn, 6), **f64)
+        self.xt[:, 0] = torch.as_tensor(np.broadcast_to(np.asarray(vt, dtype=float), (Bn,)).copy(), **f64)
+        self.xt[:, 5] = torch.as_tensor(np.broadcast_to(np.asarray(eyt, dtype=float), (Bn,)).copy(), **f64)
+        self.design = torch_api.lqr_design_dev(self.desc, self.A, self.B)
+        self.K = self.design.K
+        self.u = torch.zeros((Bn, 2), **f64)
+        self.laps = torch.zeros(Bn, dtype=torch.int32, device=dev)
+        self.xg_next, self.xc_next = torch.empty_like(self.xg), torch.empty_like(self.xc)
+
+    def step(self):
+        torch_api.lqr_step_dev(self.K, self.xc, self.xt, self.u)
+        torch_api.plant_step_wrap_dev(self.pdesc, self.tab, self.xg, self.xc, self.u, 2, self.xg_next, self.xc_next, self.laps,
+                                      noise_z=self.noise.draw(self.batch))
+        self.xg, self.xg_next = self.xg_next, self.xg
+        self.xc, self.xc_next = self.xc_next, self.xc
+
+
+def lqr_laps(track_table, lap_length, xcurv0, xglob0, steps, A, B, Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]), R=np.diag([0.1, 0.1]),
+             vt=0.8, eyt=0.0, max_iter=50, eps=0.01, timestep=0.1, device=None, noise_seed=None, log_every=1):
+    """xcurv0, xglob0 [B,6]; A, B as in LqrLaps.  Returns host arrays: xcurv [T+1,B,6] (T = steps / log_every), u [T,B,2], K [B,2,6],
+    design_status [B], design_iters [B], laps [B]."""
+    r = LqrLaps(track_table, lap_length, xcurv0, xglob0, A, B, Q=Q, R=R, vt=vt, eyt=eyt, max_iter=max_iter, eps=eps, timestep=timestep,
+                device=device, noise_seed=noise_seed)
+    log_x, log_u = [r.xc.clone()], []
+    for k in range(steps):
+        r.step()
+        if (k + 1) % log_every == 0:
+            log_x.append(r.xc.clone())
+            log_u.append(r.u.clone())
+    return dict(xcurv=torch.stack(log_x).cpu().numpy(), u=torch.stack(log_u).cpu().numpy(), K=r.K.cpu().numpy(),
+                design_status=r.design.status.cpu().numpy(), design_iters=r.design.iters.cpu().numpy(), laps=r.laps.cpu().numpy())

@@ -168,9 +168,10 @@ class IlqrWorkspace:
         self.iters = torch.zeros(batch, **i32)
 
 
-def ilqr_solve_dev(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, ws=None, active=None):
+def ilqr_solve_dev(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, ws=None, active=None, models=None):
     """crx_ilqr_solve_dev: x0, xt [B,6]; obs_s, obs_ey [B,n_obs_max,N+1]; lap_off [B,n_obs_max]; n_obs int32 [B]; `active`
-    (int32 [B], 0 = leave the problem alone: status CRX_SKIPPED, outputs untouched) optional."""
+    (int32 [B], 0 = leave the problem alone: status CRX_SKIPPED, outputs untouched) optional.  models = (A [B,6,6], B [B,6,2]):
+    crx_ilqr_solve_models_dev, problem b on its own model (desc.A, desc.B are ignored)."""
     N, V, B = desc.N, desc.n_obs_max, x0.shape[0]
     _chk(x0, torch.float64, (B, 6), "x0")
     _chk(xt, torch.float64, (B, 6), "xt")
@@ -181,10 +182,58 @@ def ilqr_solve_dev(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, ws=None, active=
     if active is not None:
         _chk(active, torch.int32, (B,), "active")
     ws = ws or IlqrWorkspace(desc, B, x0.device)
+    if models is not None:
+        mA, mB = models
+        _chk(mA, torch.float64, (B, 6, 6), "models[0]")
+        _chk(mB, torch.float64, (B, 6, 2), "models[1]")
+        _call("crx_ilqr_solve_models_dev", C.byref(desc), C.c_int(B), _ptr(active) if active is not None else None, _ptr(x0),
+              _ptr(mA), _ptr(mB), _ptr(xt), _ptr(obs_s), _ptr(obs_ey), _ptr(lap_off), _ptr(n_obs), _ptr(ws.X), _ptr(ws.U),
+              _ptr(ws.cost), _ptr(ws.status), _ptr(ws.iters), _stream())
+        return ws
     _call("crx_ilqr_solve_dev", C.byref(desc), C.c_int(B), _ptr(active) if active is not None else None, _ptr(x0), _ptr(xt),
           _ptr(obs_s), _ptr(obs_ey), _ptr(lap_off), _ptr(n_obs), _ptr(ws.X), _ptr(ws.U), _ptr(ws.cost), _ptr(ws.status),
           _ptr(ws.iters), _stream())
     return ws
+
+
+class LqrWorkspace:
+    """Pre-allocated outputs for repeated lqr_design_dev calls of one batch; P None = the kernel skips it."""
+
+    def __init__(self, batch, device, want_P=True):
+        f64 = dict(dtype=torch.float64, device=device)
+        i32 = dict(dtype=torch.int32, device=device)
+        self.K = torch.zeros((batch, 2, 6), **f64)
+        self.P = torch.zeros((batch, 6, 6), **f64) if want_P else None
+        self.iters = torch.zeros(batch, **i32)
+        self.status = torch.zeros(batch, **i32)
+
+
+def lqr_design_dev(desc, A, B, ws=None, active=None):
+    """crx_lqr_design_dev: A [B,6,6], B [B,6,2] device tensors (as SysidWorkspace holds them); `active` (int32 [B], 0 = leave the
+    model alone: status CRX_SKIPPED, outputs untouched) optional.  Returns the workspace: K [B,2,6], P [B,6,6], iters, status."""
+    Bn = A.shape[0]
+    _chk(A, torch.float64, (Bn, 6, 6), "A")
+    _chk(B, torch.float64, (Bn, 6, 2), "B")
+    if active is not None:
+        _chk(active, torch.int32, (Bn,), "active")
+    ws = ws or LqrWorkspace(Bn, A.device)
+    _chk(ws.K, torch.float64, (Bn, 2, 6), "ws.K")
+    if ws.P is not None:
+        _chk(ws.P, torch.float64, (Bn, 6, 6), "ws.P")
+    _call("crx_lqr_design_dev", C.byref(desc), C.c_int(Bn), _ptr(active) if active is not None else None, _ptr(A), _ptr(B), _ptr(ws.K),
+          _ptr(ws.P), _ptr(ws.iters), _ptr(ws.status), _stream())
+    return ws
+
+
+def lqr_step_dev(K, xcurv, xt, u):
+    """crx_lqr_step_dev: u [B,2] = -K [B,2,6] (xcurv - xt), xcurv, xt [B,6]."""
+    Bn = xcurv.shape[0]
+    _chk(K, torch.float64, (Bn, 2, 6), "K")
+    _chk(xcurv, torch.float64, (Bn, 6), "xcurv")
+    _chk(xt, torch.float64, (Bn, 6), "xt")
+    _chk(u, torch.float64, (Bn, 2), "u")
+    _call("crx_lqr_step_dev", C.c_int(Bn), _ptr(K), _ptr(xcurv), _ptr(xt), _ptr(u), _stream())
+    return u
 
 
 class SysidWorkspace:

@@ -998,22 +998,40 @@ static int check_ilqr(crx_ilqr_kparams& kp, const crx_ilqr_desc* d, int batch, a
     return 0;
 }
 
-int crx_ilqr_solve_dev(const crx_ilqr_desc* d, int batch, const int32_t* active, const double* x0, const double* xt,
-                       const double* obs_s, const double* obs_ey, const double* lap_off, const int32_t* n_obs, double* X, double* U,
-                       double* cost, int32_t* status, int32_t* iters, void* stream) {
+// model_A, model_B [batch][36], [batch][12]: per-problem models, both or neither (neither: d->A, d->B for the whole batch)
+static int check_ilqr_models(int batch, arr model_A, arr model_B) {
+    if (batch > 0 && !model_A != !model_B) return fail(CRX_ERR_ARG, "NULL array argument (model_A and model_B go together)");
+    return 0;
+}
+
+int crx_ilqr_solve_models_dev(const crx_ilqr_desc* d, int batch, const int32_t* active, const double* x0, const double* model_A,
+                              const double* model_B, const double* xt, const double* obs_s, const double* obs_ey,
+                              const double* lap_off, const int32_t* n_obs, double* X, double* U, double* cost, int32_t* status,
+                              int32_t* iters, void* stream) {
     crx_ilqr_kparams kp;
     if (int rc = check_ilqr(kp, d, batch, x0, xt, obs_s, obs_ey, lap_off, n_obs, X, U, cost, status, iters)) return rc;
+    if (int rc = check_ilqr_models(batch, model_A, model_B)) return rc;
     if (int rc = ensure_init()) return rc;
     if (batch == 0) return CRX_OK;
     kp.x0 = x0; kp.xt = xt; kp.obs_s = obs_s; kp.obs_ey = obs_ey; kp.lap_off = lap_off; kp.n_obs = n_obs; kp.active = active;
     kp.X = X; kp.U = U; kp.cost = cost; kp.status = status; kp.iters = iters;
+    kp.model_A = model_A; kp.model_B = model_B;
     return launched(crx_launch_ilqr(kp, (hipStream_t)stream), "ilqr");
 }
 
-int crx_ilqr_solve(const crx_ilqr_desc* d, int batch, const double* x0, const double* xt, const double* obs_s, const double* obs_ey,
-                   const double* lap_off, const int32_t* n_obs, double* X, double* U, double* cost, int32_t* status, int32_t* iters) {
+int crx_ilqr_solve_dev(const crx_ilqr_desc* d, int batch, const int32_t* active, const double* x0, const double* xt,
+                       const double* obs_s, const double* obs_ey, const double* lap_off, const int32_t* n_obs, double* X, double* U,
+                       double* cost, int32_t* status, int32_t* iters, void* stream) {
+    return crx_ilqr_solve_models_dev(d, batch, active, x0, nullptr, nullptr, xt, obs_s, obs_ey, lap_off, n_obs, X, U, cost, status, iters,
+                                     stream);
+}
+
+int crx_ilqr_solve_models(const crx_ilqr_desc* d, int batch, const double* x0, const double* model_A, const double* model_B,
+                          const double* xt, const double* obs_s, const double* obs_ey, const double* lap_off, const int32_t* n_obs,
+                          double* X, double* U, double* cost, int32_t* status, int32_t* iters) {
     crx_ilqr_kparams chk;
     if (int rc = check_ilqr(chk, d, batch, x0, xt, obs_s, obs_ey, lap_off, n_obs, X, U, cost, status, iters)) return rc;
+    if (int rc = check_ilqr_models(batch, model_A, model_B)) return rc;
     for (int b = 0; b < batch; b++)
         if (n_obs[b] < 0 || n_obs[b] > d->n_obs_max) return fail(CRX_ERR_ARG, "n_obs[%d]=%d outside [0,%d]", b, n_obs[b], d->n_obs_max);
     if (int rc = ensure_init()) return rc;
@@ -1025,12 +1043,75 @@ int crx_ilqr_solve(const crx_ilqr_desc* d, int batch, const double* x0, const do
     auto dx0 = sg.in(x0, Bn * 6); auto dxt = sg.in(xt, Bn * 6);
     auto dos = sg.in(obs_s, Bn * V * (N + 1)); auto doe = sg.in(obs_ey, Bn * V * (N + 1)); auto dlo = sg.in(lap_off, Bn * V);
     auto dn = sg.in(n_obs, Bn);
+    auto dmA = model_A ? sg.in(model_A, Bn * 36) : Stage::Ref<double>{};
+    auto dmB = model_B ? sg.in(model_B, Bn * 12) : Stage::Ref<double>{};
     auto dX = sg.out(X, Bn * (N + 1) * 6); auto dU = sg.out(U, Bn * N * 2); auto dc = sg.out(cost, Bn);
     auto ds = sg.out(status, Bn); auto di = sg.out(iters, Bn);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_ilqr_solve_dev(d, batch, nullptr, sg[dx0], sg[dxt], sg[dos], sg[doe], sg[dlo], sg[dn], sg[dX], sg[dU], sg[dc], sg[ds],
-                                    sg[di], g_stream)) return rc;
+    if (int rc = crx_ilqr_solve_models_dev(d, batch, nullptr, sg[dx0], sg[dmA], sg[dmB], sg[dxt], sg[dos], sg[doe], sg[dlo], sg[dn], sg[dX],
+                                           sg[dU], sg[dc], sg[ds], sg[di], g_stream)) return rc;
     return sg.down(g_stream);
+}
+
+int crx_ilqr_solve(const crx_ilqr_desc* d, int batch, const double* x0, const double* xt, const double* obs_s, const double* obs_ey,
+                   const double* lap_off, const int32_t* n_obs, double* X, double* U, double* cost, int32_t* status, int32_t* iters) {
+    return crx_ilqr_solve_models(d, batch, x0, nullptr, nullptr, xt, obs_s, obs_ey, lap_off, n_obs, X, U, cost, status, iters);
+}
+
+// ---- LQR design and control law (control/control.py:28-61) ---------------------------------------------------------------
+void crx_lqr_desc_default(crx_lqr_desc* d) {
+    memset(d, 0, sizeof(*d));
+    d->max_iter = 50;
+    d->Q[0] = 10.0; d->Q[3 * 7] = 4.0; d->Q[5 * 7] = 40.0;
+    d->R[0] = 0.1; d->R[3] = 0.1;
+    d->eps = 0.01;
+}
+
+static int check_lqr(crx_lqr_kparams& kp, const crx_lqr_desc* d, int batch, arr A, arr B, arr K, arr iters, arr status) {
+    if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
+    if (d->max_iter < 0) return fail(CRX_ERR_ARG, "max_iter < 0");
+    if (batch < 0) return fail(CRX_ERR_ARG, "batch < 0");
+    if (batch > 0 && any_null(A, B, K, iters, status)) return fail(CRX_ERR_ARG, "NULL array argument");
+    memset(&kp, 0, sizeof(kp));
+    kp.batch = batch; kp.max_iter = d->max_iter; kp.eps = d->eps;
+    memcpy(kp.Q, d->Q, sizeof(kp.Q)); memcpy(kp.R, d->R, sizeof(kp.R));
+    return 0;
+}
+
+int crx_lqr_design_dev(const crx_lqr_desc* d, int batch, const int32_t* active, const double* A, const double* B, double* K, double* P,
+                       int32_t* iters, int32_t* status, void* stream) {
+    crx_lqr_kparams kp;
+    if (int rc = check_lqr(kp, d, batch, A, B, K, iters, status)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (batch == 0) return CRX_OK;
+    kp.A = A; kp.B = B; kp.active = active; kp.K = K; kp.P = P; kp.iters = iters; kp.status = status;
+    return launched(crx_launch_lqr_design(kp, (hipStream_t)stream), "lqr design");
+}
+
+int crx_lqr_design(const crx_lqr_desc* d, int batch, const double* A, const double* B, double* K, double* P, int32_t* iters,
+                   int32_t* status) {
+    crx_lqr_kparams chk;
+    if (int rc = check_lqr(chk, d, batch, A, B, K, iters, status)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (batch == 0) return CRX_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    const size_t Bn = (size_t)batch;
+    Stage sg;
+    auto dA = sg.in(A, Bn * 36); auto dB = sg.in(B, Bn * 12);
+    auto dK = sg.out(K, Bn * 12); auto dP = P ? sg.out(P, Bn * 36) : Stage::Ref<double>{};
+    auto di = sg.out(iters, Bn); auto ds = sg.out(status, Bn);
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_lqr_design_dev(d, batch, nullptr, sg[dA], sg[dB], sg[dK], sg[dP], sg[di], sg[ds], g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
+int crx_lqr_step_dev(int batch, const double* K, const double* xcurv, const double* xt, double* u, void* stream) {
+    if (batch < 0) return fail(CRX_ERR_ARG, "batch < 0");
+    if (batch > 0 && any_null(K, xcurv, xt, u)) return fail(CRX_ERR_ARG, "NULL array argument");
+    if (int rc = ensure_init()) return rc;
+    if (batch == 0) return CRX_OK;
+    return launched(crx_launch_lqr_step(batch, K, xcurv, xt, u, (hipStream_t)stream), "lqr step");
 }
 
 // ---- LTI system identification (system/system_identification.py:4-43) --------------------------------------------------

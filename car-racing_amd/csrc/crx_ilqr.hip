@@ -18,6 +18,8 @@
 // The cost sums run sequentially on lane 0 in the reference's order ((cost + l_state) + l_ctrl, stage by stage), so the accept and stop
 // tests see the reference's rounding of the sum, not a tree reduction's.
 // A, B, Q, R are uniform over the batch: the kernel argument block holds them (scalar loads), LDS a copy for lane-indexed reads.
+// Per-problem models (crx_ilqr_solve_models): crx_ilqr_models_kernel is the same body with the two LDS copies of A and B read from
+// model_A[b], model_B[b]; every later read goes through LDS.  The shared-model kernel is instantiated without that branch.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -82,9 +84,8 @@ __device__ __forceinline__ void stage_costs(double* sm, const IL& L, int N, int 
     SYNC();
 }
 
-}  // namespace
-
-__global__ void __launch_bounds__(WAVE) crx_ilqr_kernel(const crx_ilqr_kparams kp) {
+template <bool MODELS>
+__device__ __forceinline__ void ilqr_body(const crx_ilqr_kparams& kp) {
     extern __shared__ double sm[];
     const int b = blockIdx.x;
     if (b >= kp.batch) return;
@@ -95,8 +96,8 @@ __global__ void __launch_bounds__(WAVE) crx_ilqr_kernel(const crx_ilqr_kparams k
     }
     const int N = kp.N;
     const IL L(N);
-    if (lane < 36) { sm[L.A + lane] = kp.A[lane]; sm[L.Q + lane] = kp.Q[lane]; }
-    if (lane < 12) sm[L.B + lane] = kp.B[lane];
+    if (lane < 36) { sm[L.A + lane] = MODELS ? kp.model_A[(size_t)36 * b + lane] : kp.A[lane]; sm[L.Q + lane] = kp.Q[lane]; }
+    if (lane < 12) sm[L.B + lane] = MODELS ? kp.model_B[(size_t)12 * b + lane] : kp.B[lane];
     if (lane < 4) sm[L.R + lane] = kp.R[lane];
     double xt[6];
 #pragma unroll
@@ -318,6 +319,11 @@ __global__ void __launch_bounds__(WAVE) crx_ilqr_kernel(const crx_ilqr_kparams k
     }
 }
 
+}  // namespace
+
+__global__ void __launch_bounds__(WAVE) crx_ilqr_kernel(const crx_ilqr_kparams kp) { ilqr_body<false>(kp); }
+__global__ void __launch_bounds__(WAVE) crx_ilqr_models_kernel(const crx_ilqr_kparams kp) { ilqr_body<true>(kp); }
+
 size_t crx_ilqr_lds_bytes(int N) { return (size_t)IL(N).total * sizeof(double); }
 
 int crx_ilqr_resident_per_cu(int N) {
@@ -328,6 +334,9 @@ int crx_ilqr_resident_per_cu(int N) {
 
 hipError_t crx_launch_ilqr(const crx_ilqr_kparams& kp, hipStream_t st) {
     if (kp.batch == 0) return hipSuccess;
-    hipLaunchKernelGGL(crx_ilqr_kernel, dim3(kp.batch), dim3(WAVE), crx_ilqr_lds_bytes(kp.N), st, kp);
+    if (kp.model_A)
+        hipLaunchKernelGGL(crx_ilqr_models_kernel, dim3(kp.batch), dim3(WAVE), crx_ilqr_lds_bytes(kp.N), st, kp);
+    else
+        hipLaunchKernelGGL(crx_ilqr_kernel, dim3(kp.batch), dim3(WAVE), crx_ilqr_lds_bytes(kp.N), st, kp);
     return hipGetLastError();
 }

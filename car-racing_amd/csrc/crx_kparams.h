@@ -204,10 +204,23 @@ struct crx_ilqr_kparams {
     const int32_t *n_obs, *active;
     double *X, *U, *cost;
     int32_t *status, *iters;
+    // optional per-problem models [batch][36], [batch][12] (both or neither): the LDS copies of A, B come from them, A and B above are unused
+    const double *model_A, *model_B;
 };
 hipError_t crx_launch_ilqr(const crx_ilqr_kparams& kp, hipStream_t st);
 size_t crx_ilqr_lds_bytes(int N);
 int crx_ilqr_resident_per_cu(int N);
+// LQR design and control law (crx_lqr.hip)
+struct crx_lqr_kparams {
+    int batch, max_iter;
+    double Q[36], R[4], eps;
+    const double *A, *B;       // [batch][36], [batch][12]
+    const int32_t* active;     // optional [batch]: 0 = leave this model alone (status CRX_SKIPPED, outputs untouched)
+    double *K, *P;             // [batch][12]; [batch][36] or NULL
+    int32_t *status, *iters;
+};
+hipError_t crx_launch_lqr_design(const crx_lqr_kparams& kp, hipStream_t st);
+hipError_t crx_launch_lqr_step(int batch, const double* K, const double* xcurv, const double* xt, double* u, hipStream_t st);
 // system identification (crx_sysid.hip)
 struct crx_sysid_kparams {
     int n_logs, n_groups, first_row, chunk, tpl;   // tpl = tile slots per log in the workspace

@@ -44,7 +44,9 @@
 extern "C" {
 #endif
 
-#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_sysid_desc, crx_sysid_desc_default, crx_sysid_fit, crx_sysid_fit_dev,
+#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_lqr_desc, crx_lqr_desc_default, crx_lqr_design, crx_lqr_design_dev, crx_lqr_step_dev,
+                          crx_ilqr_solve_models, crx_ilqr_solve_models_dev; CRX_SINGULAR also from crx_lqr_design -- new entry points only.
+                          0.4.0 (additive, same number): crx_sysid_desc, crx_sysid_desc_default, crx_sysid_fit, crx_sysid_fit_dev,
                           crx_sysid_workspace_bytes, crx_pid_log_dev and status CRX_SINGULAR -- new entry points only.
                           0.4.0 (additive, same number): crx_ilqr_desc, crx_ilqr_desc_default, crx_ilqr_solve, crx_ilqr_solve_dev and
                           CRX_ILQR_MAX_N -- new entry points only, every earlier signature and struct layout unchanged.
@@ -104,8 +106,9 @@ typedef enum crx_status {
                               divergence heuristic).  libcrx <= 0.1.3 reported these as CRX_INFEASIBLE.  Like every status != 0 it
                               selects the reference's "solver failed" branch (control.py:600-603: keep the last iterate;
                               overtake_traj_planner.py:365-374: the fall-back trajectory). */
-    CRX_SINGULAR = 6       /* crx_sysid_fit only: a zero or non-finite pivot in the LU of X'X + lamb I, where numpy.linalg.inv raises
-                              LinAlgError; W, A, B and err are NaN */
+    CRX_SINGULAR = 6       /* crx_sysid_fit: a zero or non-finite pivot in the LU of X'X + lamb I, where numpy.linalg.inv raises
+                              LinAlgError; W, A, B and err are NaN.  crx_lqr_design: a non-finite model, iterate or gain, or a zero or
+                              non-finite determinant of R + B'PB; K and P are NaN */
 } crx_status;
 
 /* Interior-point options.  Defaults (crx_ipm_opts_default) restate IPOPT 3.x defaults that the
@@ -287,6 +290,57 @@ int crx_ilqr_solve(const crx_ilqr_desc* d, int batch, const double* x0, const do
 int crx_ilqr_solve_dev(const crx_ilqr_desc* d, int batch, const int32_t* active, const double* x0, const double* xt,
                        const double* obs_s, const double* obs_ey, const double* lap_off, const int32_t* n_obs, double* X, double* U,
                        double* cost, int32_t* status, int32_t* iters, void* stream);
+
+/* Per-problem models: crx_ilqr_solve / crx_ilqr_solve_dev with model_A [batch][6][6] and model_B [batch][6][2] after x0.  Problem b
+ * runs on (model_A[b], model_B[b]); d->A and d->B are ignored.  Both NULL: the shared launch of d->A, d->B, bit for bit; one NULL
+ * is CRX_ERR_ARG.  A problem fed a copy of d's model gives the bits of the shared launch. */
+int crx_ilqr_solve_models(const crx_ilqr_desc* d, int batch, const double* x0, const double* model_A, const double* model_B,
+                          const double* xt, const double* obs_s, const double* obs_ey, const double* lap_off, const int32_t* n_obs,
+                          double* X, double* U, double* cost, int32_t* status, int32_t* iters);
+int crx_ilqr_solve_models_dev(const crx_ilqr_desc* d, int batch, const int32_t* active, const double* x0, const double* model_A,
+                              const double* model_B, const double* xt, const double* obs_s, const double* obs_ey,
+                              const double* lap_off, const int32_t* n_obs, double* X, double* U, double* cost, int32_t* status,
+                              int32_t* iters, void* stream);
+
+/* ---- LQR tracking controller (control/control.py:28-61 lqr) for a batch of models --------------------------------------------
+ * The reference's Riccati fixed point, one design per model (A, B):
+ *     P = Q
+ *     repeat at most max_iter times:
+ *         P' = A'PA - A'(PB) inv(R + B'(PB)) B'P A + Q
+ *         if max|P' - P| < eps: stop, and discard P'
+ *         P = P'
+ *     K = inv(B'PB + R) B'P A
+ * in the operation order of the host mirror control._lqr_gain.  Semantics of the reference kept on purpose:
+ *   L1  the gain comes from the P in hand when the test passes, not from the iterate that passed it (:49-53); max_iter = 0 gives
+ *       the gain of P = Q.
+ *   L2  P is never symmetrised; A'(PB) and B'P are formed separately.  A transposed shortcut such as (B'PA)' for A'PB lets the
+ *       asymmetry of P grow and lands on other iterates and other iteration counts.
+ *   L3  the stop test is strict: < eps on the max-norm of the full 6x6 difference.  The 2x2 inverse is the plain adjugate over the
+ *       determinant.
+ *   L4  status: CRX_CONVERGED = the test passed; CRX_MAX_ITER = max_iter steps without passing, K is still the gain of the last P
+ *       (what the reference silently returns); CRX_SINGULAR = a non-finite entry in A, B, an iterate or K, or a zero or non-finite
+ *       determinant: K and P are NaN, no path leaves a finite wrong number.  The loop is bounded by max_iter whatever the data.
+ * iters = the Riccati steps computed (the reference's loop count; the step that passes or fails counts; 0 for a non-finite
+ * model).  A design is bit-identical whatever the batch and the model's position in it. */
+typedef struct crx_lqr_desc {
+    int32_t max_iter;      /* 50    LQRTrackingParam.max_iter (utils/base.py) */
+    int32_t pad_;
+    double Q[36];          /* matrix_Q, full: diag(10, 0, 0, 4, 0, 40) */
+    double R[4];           /* matrix_R, full: diag(0.1, 0.1) */
+    double eps;            /* 0.01  (control.py:44) */
+} crx_lqr_desc;
+
+/* Defaults above. */
+void crx_lqr_desc_default(crx_lqr_desc* d);
+/* Host pointers.  A [batch][6][6], B [batch][6][2] (always per problem; one model = batch 1); K [batch][2][6]; P [batch][6][6]
+ * (the P behind K) may be NULL; iters, status [batch]. */
+int crx_lqr_design(const crx_lqr_desc* d, int batch, const double* A, const double* B, double* K, double* P, int32_t* iters,
+                   int32_t* status);
+/* device pointers; active [batch] as in the masked launches (NULL = all; 0 = CRX_SKIPPED, outputs untouched) */
+int crx_lqr_design_dev(const crx_lqr_desc* d, int batch, const int32_t* active, const double* A, const double* B, double* K, double* P,
+                       int32_t* iters, int32_t* status, void* stream);
+/* u[b] = -K[b] (xcurv[b] - xt[b]): K [batch][2][6], xcurv, xt [batch][6], u [batch][2]; six-term sums in ascending index order. */
+int crx_lqr_step_dev(int batch, const double* K, const double* xcurv, const double* xt, double* u, void* stream);
 
 /* ---- LTI system identification (system/system_identification.py:4-43 linear_regression, get_udata) ------------------------
  * Batched ridge regression of x_{k+1} on (x_k, u_k) over packed logs, FP64 on the device.  Semantics of the reference kept:

@@ -297,6 +297,19 @@ def lqr_models(A, B, batch=None):
     return _in(A, _D, (Bn, 6, 6)), _in(B, _D, (Bn, 6, 2))
 
 
+def cbf_models(models, batch):
+    """(A [batch,6,6], B [batch,6,2]) contiguous float64 from a per-problem model pair of host arrays; anything else -- another
+    shape, another dtype, not a pair -- is a ValueError (no silent conversion: a float32 model is a caller's mistake)."""
+    try:
+        A, B = models
+    except (TypeError, ValueError):
+        raise ValueError("models must be a pair (A [batch,6,6], B [batch,6,2])")
+    A, B = np.asarray(A), np.asarray(B)
+    if A.dtype != np.float64 or B.dtype != np.float64:
+        raise ValueError("models must be float64, got %s, %s" % (A.dtype, B.dtype))
+    return _in(A, _D, (batch, 6, 6)), _in(B, _D, (batch, 6, 2))
+
+
 def sysid_desc(lamb=1e-9, first_row=1, chunk_rows=8192):
     """crx_sysid_desc_default: lamb of system_identification_test.py:42; first_row = 1 drops row 0 (S1)."""
     return SysidDesc(float(lamb), int(first_row), int(chunk_rows))
@@ -361,7 +374,7 @@ class Binding:
     def __init__(self, lib, prefix):
         self.lib, self.prefix = lib, prefix
         for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve", "ilqr_solve",
-                     "ilqr_solve_models", "lqr_design", "sysid_fit"):
+                     "ilqr_solve_models", "lqr_design", "sysid_fit", "cbf_solve_models"):
             if hasattr(lib, prefix + name):
                 getattr(lib, prefix + name).restype = C.c_int
         self._check = None
@@ -451,8 +464,10 @@ class Binding:
                    _p(u), _p(out["A"]), _p(out["B"]), _p(out["err"]), _p(out["n_pairs"]), _p(out["status"]))
         return out
 
-    def cbf_solve(self, desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, obs_dims=None):
-        """crx_cbf_solve; with obs_dims (Bn, V, 2) = (l_agent + l_obs, w_agent + w_obs) per obstacle slot: crx_cbf_solve_dims."""
+    def cbf_solve(self, desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, obs_dims=None, models=None):
+        """crx_cbf_solve; with obs_dims (Bn, V, 2) = (l_agent + l_obs, w_agent + w_obs) per obstacle slot: crx_cbf_solve_dims.
+        models = (A (Bn,6,6), B (Bn,6,2)) float64: crx_cbf_solve_models, problem b on its own model (desc.A, desc.B are ignored); a
+        problem whose model has a non-finite entry reports CRX_SINGULAR with NaN outputs."""
         N, V = desc.N, desc.n_obs_max
         x0 = np.ascontiguousarray(x0, dtype=_D)
         Bn = x0.shape[0]
@@ -467,6 +482,16 @@ class Binding:
             cost=np.zeros(Bn), status=np.zeros(Bn, dtype=_I), kkt=np.zeros(Bn),
             iters=np.zeros(Bn, dtype=_I),
         )
+        if models is not None:
+            mA, mB = cbf_models(models, Bn)
+            if obs_dims is not None:
+                obs_dims = _in(obs_dims, _D, (Bn, V, 2))
+            self._call(
+                "cbf_solve_models", C.byref(desc), C.c_int(Bn), _p(x0), _p(mA), _p(mB), _p(xt), _p(obs_s), _p(obs_ey),
+                _p(lap_off), _p(n_obs), _p(obs_dims) if obs_dims is not None else None, _p(out["X"]), _p(out["U"]), _p(out["sigma"]),
+                _p(out["cost"]), _p(out["status"]), _p(out["kkt"]), _p(out["iters"]),
+            )
+            return out
         if obs_dims is not None:
             obs_dims = _in(obs_dims, _D, (Bn, V, 2))
             self._call(

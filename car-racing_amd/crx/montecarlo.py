@@ -172,7 +172,7 @@ class MpccbfRaces:
     """State of B races on the device; step() advances all of them by one control step."""
 
     def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, car_s0, car_v, car_ey,
-                 vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1, device=None, noise_seed=None):
+                 vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1, device=None, noise_seed=None, models=None):
         dev = torch.device(device if device is not None else "cuda")
         f64 = dict(dtype=torch.float64, device=dev)
         self.noise = _Noise(noise_seed, dev)
@@ -188,6 +188,9 @@ class MpccbfRaces:
         self.pdesc = abi.plant_desc(self.tab.shape[0], lap_length, timestep=timestep)
         self.xt = torch.tensor([vt, 0, 0, 0, 0, eyt], **f64).repeat(Bn, 1).contiguous()
         self.ws = torch_api.CbfWorkspace(self.desc, Bn, dev)
+        # models = (A [B,6,6], B [B,6,2]), host arrays or device tensors (PidLaps.identify()): every race's controller on its own model
+        # (crx_cbf_solve_models_dev); A, B above are then unused.  The reach table is computed here, once
+        self.models = None if models is None else torch_api.CbfModels(self.desc, *_models(models[0], models[1], Bn, dev))
         self.jdt = torch.arange(N + 1, **f64) * timestep
         self.laps = torch.zeros(Bn, dtype=torch.int32, device=dev)
         self.ar = torch.arange(V, device=dev)
@@ -205,7 +208,7 @@ class MpccbfRaces:
         torch_api.cbf_prep_dev(N, self.lap_length, self.t, self.timestep, self.xc, self.s0, self.v, self.ey,
                                self.obs_s, self.obs_e, self.lap_off, self.n_obs)
         torch_api.cbf_solve_dev(self.desc, self.xc, self.xt, self.obs_s, self.obs_e, self.lap_off, self.n_obs, ws=self.ws,
-                                order=_order(self, self.ws.iters))
+                                order=_order(self, self.ws.iters), models=self.models)
         # the plant reads u_0 of every race straight out of the solver's U [B][N][2]
         torch_api.plant_step_wrap_dev(self.pdesc, self.tab, self.xg, self.xc, self.ws.U, 2 * N, self.xg_next, self.xc_next, self.laps,
                                       noise_z=self.noise.draw(self.batch))
@@ -235,7 +238,7 @@ class MpccbfRaces:
         pe = torch.gather(obs_e, 1, order[:, :, None].expand(-1, -1, N + 1)) * live[:, :, None]
         po = torch.gather(lap_off, 1, order) * live
         torch_api.cbf_solve_dev(self.desc, xc, self.xt, ps.contiguous(), pe.contiguous(), po.contiguous(), n_obs.contiguous(),
-                                ws=self.ws)
+                                ws=self.ws, models=self.models)
         self.u = self.ws.U[:, 0, :].contiguous()
         self.xg, xc = torch_api.plant_step_dev(self.pdesc, self.tab, self.xg, xc, self.u)
         crossed = xc[:, 4] > L
@@ -246,12 +249,12 @@ class MpccbfRaces:
 
 
 def mpccbf_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, steps,
-                 vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1, device=None, log_every=1, glue=False):
+                 vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1, device=None, log_every=1, glue=False, models=None):
     """xcurv0, xglob0 [B,6]; car_s0, car_v, car_ey [B,V] with V <= 3: scripted cars s(t) = v t + s0, ey(t) = ey
-    (NoDynamicsModel, utils/base.py:847-890).  Returns host arrays: xcurv [T+1,B,6] (T = steps/log_every), u [T,B,2],
+    (NoDynamicsModel, utils/base.py:847-890); models = (A [B,6,6], B [B,6,2]): one controller model per race.  Returns host arrays: xcurv [T+1,B,6] (T = steps/log_every), u [T,B,2],
     status [T,B], laps [B]."""
     r = MpccbfRaces(track_table, lap_length, track_width, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, vt=vt, eyt=eyt,
-                    N=N, alpha=alpha, timestep=timestep, device=device)
+                    N=N, alpha=alpha, timestep=timestep, device=device, models=models)
     log_x, log_u, log_st = [r.xc.clone()], [], []
     for k in range(steps):
         (r.step_glue if glue else r.step)()

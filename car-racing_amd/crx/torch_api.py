@@ -129,10 +129,30 @@ def cbf_order_dev(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, obs_dims=None, ac
     return order
 
 
-def cbf_solve_dev(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, ws=None, active=None, obs_dims=None, order=None):
+CBF_REACH_ROW = 25   # CRX_MAX_N + 1: stride of a row of the reach table (include/crx.h CRX_CBF_MODEL_REACH_DOUBLES)
+
+
+class CbfModels:
+    """One LTI model per problem for cbf_solve_dev(models=...): contiguous device A [B,6,6], B [B,6,2] (e.g. what PidLaps.identify()
+    returns: held, not copied) and the reach table crx_cbf_models_reach_dev computes from them -- here, once: it is valid for every solve
+    with desc's N, delta_max, a_max."""
+
+    def __init__(self, desc, A, B):
+        if not (torch.is_tensor(A) and torch.is_tensor(B)) or A.dim() != 3:
+            raise ValueError("CbfModels: A [B,6,6], B [B,6,2] device tensors expected")
+        Bn = A.shape[0]
+        self.A = _chk(A, torch.float64, (Bn, 6, 6), "models A")
+        self.B = _chk(B, torch.float64, (Bn, 6, 2), "models B")
+        self.batch, self.N, self.delta_max, self.a_max = Bn, desc.N, desc.delta_max, desc.a_max
+        self.reach = torch.empty((Bn, 2, CBF_REACH_ROW), dtype=torch.float64, device=A.device)
+        _call("crx_cbf_models_reach_dev", C.byref(desc), C.c_int(Bn), _ptr(self.A), _ptr(self.B), _ptr(self.reach), _stream())
+
+
+def cbf_solve_dev(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, ws=None, active=None, obs_dims=None, order=None, models=None):
     """crx_cbf_solve_ordered_dev, the superset entry point: `active` (int32 [batch], 0 = leave the problem alone), `obs_dims`
     ([batch, n_obs_max, 2]: l_agent + l_obs, w_agent + w_obs per obstacle slot), `order` (int32 [batch] permutation: workgroup i
-    solves problem order[i]; see longest_first) -- each optional."""
+    solves problem order[i]; see longest_first) -- each optional.  models (a CbfModels of this batch, built for a descriptor with the
+    same N, delta_max, a_max): crx_cbf_solve_models_dev, problem b on its own model (desc.A, desc.B are ignored)."""
     N, V, B = desc.N, desc.n_obs_max, x0.shape[0]
     _chk(x0, torch.float64, (B, 6), "x0")
     _chk(xt, torch.float64, (B, N + 1, 6) if desc.per_stage_target else (B, 6), "xt")
@@ -147,6 +167,17 @@ def cbf_solve_dev(desc, x0, xt, obs_s, obs_ey, lap_off, n_obs, ws=None, active=N
         _chk(obs_dims, torch.float64, (B, V, 2), "obs_dims")
     if order is not None:
         _chk(order, torch.int32, (B,), "order")
+    if models is not None:
+        if not isinstance(models, CbfModels):
+            raise ValueError("models: a CbfModels is expected (CbfModels(desc, A, B))")
+        if models.batch != B or (models.N, models.delta_max, models.a_max) != (desc.N, desc.delta_max, desc.a_max):
+            raise ValueError("models: built for batch %d, N %d, input box (%g, %g); this solve has batch %d, N %d, (%g, %g)" % (
+                models.batch, models.N, models.delta_max, models.a_max, B, desc.N, desc.delta_max, desc.a_max))
+        _call("crx_cbf_solve_models_dev", C.byref(desc), C.c_int(B), _ptr(active) if active is not None else None,
+              _ptr(order) if order is not None else None, _ptr(x0), _ptr(models.A), _ptr(models.B), _ptr(models.reach), _ptr(xt),
+              _ptr(obs_s), _ptr(obs_ey), _ptr(lap_off), _ptr(n_obs), _ptr(obs_dims), _ptr(ws.X), _ptr(ws.U), _ptr(ws.sigma), _ptr(ws.cost),
+              _ptr(ws.status), _ptr(ws.kkt), _ptr(ws.iters), _stream())
+        return ws
     _call("crx_cbf_solve_ordered_dev", C.byref(desc), C.c_int(B), _ptr(active) if active is not None else None,
           _ptr(order) if order is not None else None, _ptr(x0), _ptr(xt),
           _ptr(obs_s), _ptr(obs_ey), _ptr(lap_off), _ptr(n_obs), _ptr(obs_dims), _ptr(ws.X), _ptr(ws.U), _ptr(ws.sigma), _ptr(ws.cost),

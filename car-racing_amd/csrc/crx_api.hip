@@ -260,11 +260,17 @@ void apply_diagnostics(crx_lmpc_kparams& kp) {
     kp.poison = g_poison;
 }
 
-int launch_solve(const crx_kparams& kp, int tmpl, hipStream_t st) {
+// mdl: one LTI model per problem (crx_cbf_solve_models_dev; model_A, model_B, model_reach all set) -- NULL: the descriptor's model for all
+int launch_solve(const crx_kparams& kp, int tmpl, hipStream_t st, const crx_kparams_models* mdl = nullptr) {
     crx_kparams kq = kp;
     apply_diagnostics(kq);
     size_t lds = crx_solve_lds_bytes(kp.N, tmpl);
     if (lds > 160 * 1024) return fail(CRX_ERR_ARG, "N=%d with %d obstacles needs %zu B of LDS (> 160 KiB)", kp.N, tmpl, lds);
+    if (mdl) {   // (the two-wave kernels have no per-problem-model twin: crx_debug_speculation does not apply)
+        crx_kparams_models km = *mdl;
+        static_cast<crx_kparams&>(km) = kq;
+        return launched(crx_launch_solve_models(km, tmpl, st), "solver (per-problem models)");
+    }
     // [r6] The TWO-WAVE instantiation (one obstacle slot, the reference's exponent, N = 12 / 10; crx_kernels.hip SPEC): a second wave per problem factorises
     // with the next entry of the inertia-correction schedule while the first tries the current one.  OPT-IN (crx_debug_speculation), not the default:
     // measured on the headline batch (profiles/r06_speculation.txt) a doomed attempt costs 1.7 us, not a sweep's 5.8 -- the recursion stops at the
@@ -564,13 +570,41 @@ int crx_cbf_solve_ordered_dev(const crx_cbf_desc* d, int batch, const int32_t* a
                               const double* xt, const double* obs_s, const double* obs_ey, const double* lap_off,
                               const int32_t* n_obs, const double* obs_dims, double* X, double* U, double* sigma, double* cost,
                               int32_t* status, double* kkt, int32_t* iters, void* stream) {
-    crx_kparams kp;
+    return crx_cbf_solve_models_dev(d, batch, active, order, x0, nullptr, nullptr, nullptr, xt, obs_s, obs_ey, lap_off, n_obs, obs_dims, X, U, sigma,
+                                    cost, status, kkt, iters, stream);
+}
+
+// the one thing the models entry points refuse on top of check_cbf: all three model arrays, or none
+static int check_cbf_models(arr model_A, arr model_B, arr model_reach) {
+    const int n = (model_A != nullptr) + (model_B != nullptr) + (model_reach != nullptr);
+    if (n != 0 && n != 3) return fail(CRX_ERR_ARG, "model_A, model_B and model_reach go together: all three or none (%d of 3 given)", n);
+    return 0;
+}
+
+int crx_cbf_solve_models_dev(const crx_cbf_desc* d, int batch, const int32_t* active, const int32_t* order, const double* x0,
+                             const double* model_A, const double* model_B, const double* model_reach, const double* xt,
+                             const double* obs_s, const double* obs_ey, const double* lap_off, const int32_t* n_obs,
+                             const double* obs_dims, double* X, double* U, double* sigma, double* cost, int32_t* status, double* kkt,
+                             int32_t* iters, void* stream) {
+    crx_kparams_models km;
+    crx_kparams& kp = km;
     if (int rc = check_cbf(kp, d, batch, x0, xt, obs_s, obs_ey, lap_off, n_obs, X, U, sigma, cost, status, kkt, iters)) return rc;
+    if (int rc = check_cbf_models(model_A, model_B, model_reach)) return rc;
     if (batch == 0) return CRX_OK;
     kp.x0 = x0; kp.xt = xt; kp.obs_s = obs_s; kp.obs_ey = obs_ey; kp.lap_off = lap_off; kp.n_obs = n_obs;
     kp.X = X; kp.U = U; kp.sigma = sigma; kp.cost = cost; kp.status = status; kp.kkt = kkt; kp.iters = iters;
     kp.active = active; kp.order = order; kp.obs_dims = d->n_obs_max > 0 ? obs_dims : nullptr;
-    return launch_solve(kp, d->n_obs_max, (hipStream_t)stream);
+    km.model_A = model_A; km.model_B = model_B; km.model_reach = model_reach;
+    return launch_solve(kp, d->n_obs_max, (hipStream_t)stream, model_A ? &km : nullptr);
+}
+
+int crx_cbf_models_reach_dev(const crx_cbf_desc* d, int batch, const double* model_A, const double* model_B, double* model_reach, void* stream) {
+    if (int rc = ensure_init()) return rc;
+    crx_kparams kp;
+    if (int rc = fill_cbf(kp, d, batch)) return rc;
+    if (batch == 0) return CRX_OK;
+    if (any_null(model_A, model_B, model_reach)) return fail(CRX_ERR_ARG, "NULL array argument");
+    return launched(crx_launch_cbf_reach(d->N, batch, d->delta_max, d->a_max, model_A, model_B, model_reach, (hipStream_t)stream), "cbf reach");
 }
 
 int crx_cbf_solve(const crx_cbf_desc* d, int batch, const double* x0, const double* xt, const double* obs_s,
@@ -582,8 +616,17 @@ int crx_cbf_solve(const crx_cbf_desc* d, int batch, const double* x0, const doub
 int crx_cbf_solve_dims(const crx_cbf_desc* d, int batch, const double* x0, const double* xt, const double* obs_s,
                   const double* obs_ey, const double* lap_off, const int32_t* n_obs, const double* obs_dims, double* X, double* U,
                   double* sigma, double* cost, int32_t* status, double* kkt, int32_t* iters) {
+    return crx_cbf_solve_models(d, batch, x0, nullptr, nullptr, xt, obs_s, obs_ey, lap_off, n_obs, obs_dims, X, U, sigma, cost, status, kkt, iters);
+}
+
+// (non-finite model entries are no argument error: that problem reports CRX_SINGULAR, as on the device path)
+int crx_cbf_solve_models(const crx_cbf_desc* d, int batch, const double* x0, const double* model_A, const double* model_B, const double* xt,
+                         const double* obs_s, const double* obs_ey, const double* lap_off, const int32_t* n_obs, const double* obs_dims,
+                         double* X, double* U, double* sigma, double* cost, int32_t* status, double* kkt, int32_t* iters) {
     crx_kparams chk;
     if (int rc = check_cbf(chk, d, batch, x0, xt, obs_s, obs_ey, lap_off, n_obs, X, U, sigma, cost, status, kkt, iters)) return rc;
+    const bool models = model_A || model_B;
+    if (!model_A != !model_B) return fail(CRX_ERR_ARG, "model_A and model_B go together: both or neither (%s is NULL)", model_A ? "model_B" : "model_A");
     if (batch == 0) return CRX_OK;
     const size_t B = (size_t)batch, N = (size_t)d->N, V = (size_t)d->n_obs_max;
     if (V > 0) {
@@ -603,11 +646,16 @@ int crx_cbf_solve_dims(const crx_cbf_desc* d, int batch, const double* x0, const
     auto dos = sg.in(obs_s, n_ob); auto doe = sg.in(obs_ey, n_ob); auto dlo = sg.in(lap_off, B * V);
     auto ddm = (obs_dims && V > 0) ? sg.in(obs_dims, B * V * 2) : Stage::Ref<double>{};
     auto dno = sg.in(V > 0 ? n_obs : (const int32_t*)nullptr, B);
+    auto dmA = models ? sg.in(model_A, B * 36) : Stage::Ref<double>{};
+    auto dmB = models ? sg.in(model_B, B * 12) : Stage::Ref<double>{};
+    auto dmR = models ? sg.scratch(CRX_CBF_MODEL_REACH_DOUBLES(B) * sizeof(double)) : Stage::Ref<char>{};
     auto dX = sg.out(X, B * (N + 1) * 6); auto dU = sg.out(U, B * N * 2); auto dsg = sg.out(sigma, n_ob);
     auto dc = sg.out(cost, B); auto dk = sg.out(kkt, B); auto ds = sg.out(status, B); auto di = sg.out(iters, B);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_cbf_solve_dims_dev(d, batch, nullptr, sg[dx0], sg[dxt], sg[dos], sg[doe], sg[dlo], sg[dno], sg[ddm], sg[dX], sg[dU],
-                                        sg[dsg], sg[dc], sg[ds], sg[dk], sg[di], g_stream)) return rc;
+    if (models)
+        if (int rc = crx_cbf_models_reach_dev(d, batch, sg[dmA], sg[dmB], (double*)sg[dmR], g_stream)) return rc;
+    if (int rc = crx_cbf_solve_models_dev(d, batch, nullptr, nullptr, sg[dx0], sg[dmA], sg[dmB], (double*)sg[dmR], sg[dxt], sg[dos], sg[doe],
+                                          sg[dlo], sg[dno], sg[ddm], sg[dX], sg[dU], sg[dsg], sg[dc], sg[ds], sg[dk], sg[di], g_stream)) return rc;
     return sg.down(g_stream);
 }
 

@@ -46,6 +46,17 @@
 #ifndef CRX_TU_GENERAL
 #define CRX_TU_GENERAL 0   /* 1: crx_kernels_gen.hip -- the general instantiations, built conservatively (section (7)) */
 #endif
+#ifndef CRX_TU_MODELS
+#define CRX_TU_MODELS 0    /* 1..3: crx_kernels_models.hip -- the CBF NLP with one LTI model per problem (section (7)) */
+#endif
+// what crx_solve_kernel takes by value.  The models units read A, B and the reach tables of problem b through the three pointers of the derived
+// struct, in set-up only (the model matrix M, crash_search, the slack bounds); every other unit compiles exactly what it compiled before
+#if CRX_TU_MODELS
+using crx_solve_params = crx_kparams_models;
+#else
+using crx_solve_params = crx_kparams;
+#endif
+constexpr bool MODELS = CRX_TU_MODELS != 0;
 #ifndef CRX_OPAQUE_LANE
 #define CRX_OPAQUE_LANE 1 /* make EXTRA=-DCRX_OPAQUE_LANE=0: round-2 behaviour (lane maps hoisted out of the interior-point loop) */
 #endif
@@ -1385,6 +1396,17 @@ __device__ __forceinline__ bool restore_slacks(double* sm, const Ctx& c, double 
 // loop, for the problems that may need it (a provable crash state, or a CBF row violated at the zero start) -- inside the (re)start loop
 // its temporaries sat on top of the ~200 registers the sweeps hoist out of the loops (64 .. 164 B of scratch per lane).  crash_write()
 // is the light half and is what the restart runs.
+// A[i][j], B[i][j] for crash_search(): the descriptor's model, or (models units) the problem's own, read back from M, which set-up has filled
+template <class L>
+__device__ __forceinline__ double model_a(const double* sm, const crx_kparams& kp, int i, int j) {
+    if constexpr (MODELS) return sm[L::M + i * L::NZ + j];
+    else return kp.A[i * 6 + j];
+}
+template <class L>
+__device__ __forceinline__ double model_b(const double* sm, const crx_kparams& kp, int i, int j) {
+    if constexpr (MODELS) return sm[L::M + i * L::NZ + L::NX + j];
+    else return kp.B[i * 2 + j];
+}
 template <int NOBS, int NMAX>
 __device__ __forceinline__ int crash_search(double* sm, const Ctx& c, const crx_kparams& kp) {
     using L = Lay<NOBS, NMAX>;
@@ -1424,8 +1446,8 @@ __device__ __forceinline__ int crash_search(double* sm, const Ctx& c, const crx_
                 for (int i = 0; i < 6; i++) {
                     double t = 0.0;
 #pragma unroll
-                    for (int j = 0; j < 6; j++) t += kp.A[i * 6 + j] * x[j];
-                    t += kp.B[i * 2] * u0 + kp.B[i * 2 + 1] * u1;
+                    for (int j = 0; j < 6; j++) t += model_a<L>(sm, kp, i, j) * x[j];
+                    t += model_b<L>(sm, kp, i, 0) * u0 + model_b<L>(sm, kp, i, 1) * u1;
                     xn[i] = t;
                 }
 #pragma unroll
@@ -1596,7 +1618,7 @@ template <int NFIX> constexpr int StageUnroll = NFIX == 0 ? 1 : NFIX;
 // barrier + filter line search (what every problem ran up to libcrx 0.3; instantiations with obstacles ignore it).
 template <int NOBS, int NMAX, int DEG = 0, int NFIX = 0, int SPEC = 0, int QPM = 0>
 __global__ void __launch_bounds__(WAVE * (1 + SPEC)) __attribute__((amdgpu_waves_per_eu(MinWaves<NOBS, NMAX>::v))) CRX_KERNEL_EXTRA_ATTR
-crx_solve_kernel(const crx_kparams kp) {
+crx_solve_kernel(const crx_solve_params kp) {
     static_assert(NFIX <= NMAX, "fixed horizon inside the layout");
     using L = Lay<NOBS, NMAX>;
     static_assert(!SPEC || (NOBS > 0 && !L::SLIM && CRX_STATIC_LDS), "the speculating wave exists for the obstacle instantiations of the full, static layout");
@@ -1619,6 +1641,23 @@ crx_solve_kernel(const crx_kparams kp) {
         if (lane == 0) { kp.status[b] = CRX_SKIPPED; kp.iters[b] = 0; }
         return;
     }
+    const double *mdl_A = nullptr, *mdl_B = nullptr, *mdl_reach = nullptr;   // this problem's model and reach tables (models units; b is wave-uniform)
+#if CRX_TU_MODELS
+    {
+        mdl_A = kp.model_A + (size_t)36 * b; mdl_B = kp.model_B + (size_t)12 * b; mdl_reach = kp.model_reach + (size_t)2 * (CRX_MAX_N + 1) * b;
+        // a non-finite model (crx_sysid_fit writes NaN for a failed fit) never enters the iteration: all 48 entries, one ballot, before any set-up
+        const double v = lane < 36 ? mdl_A[lane] : (lane < 48 ? mdl_B[lane - 36] : 0.0);
+        if (__ballot(!isfinite(v)) != 0ull) {
+            const double nan = __longlong_as_double(0x7ff8000000000000LL);
+            for (int e = lane; e < (N + 1) * 6; e += WAVE) kp.X[(size_t)b * (N + 1) * 6 + e] = nan;
+            for (int e = lane; e < N * 2; e += WAVE) kp.U[(size_t)b * N * 2 + e] = nan;
+            if (kp.sigma)
+                for (int e = lane; e < kp.n_obs_max * (N + 1); e += WAVE) kp.sigma[(size_t)b * kp.n_obs_max * (N + 1) + e] = nan;
+            if (lane == 0) { kp.cost[b] = nan; kp.status[b] = CRX_SINGULAR; kp.kkt[b] = INFINITY; kp.iters[b] = 0; }
+            return;
+        }
+    }
+#endif
     // [r3] Reachability screen of the planner QP, before anything is set up.  41 % of the regions of the BASELINE draw ask for a
     // lateral offset the bicycle cannot reach (~0.25 m of authority over 1 s): ey_j = e_ey' A^j x0 + sum_m e_ey' A^m B
     // u_{j-1-m}, so with |delta| <= delta_max, |a| <= a_max NO input sequence moves ey_j further than reach_gain[j] from its free
@@ -1676,8 +1715,8 @@ crx_solve_kernel(const crx_kparams kp) {
         const int i = e / NZ, a = e - i * NZ;
         double v = 0.0;
         if (i < 6) {
-            if (a < 6) v = kp.A[i * 6 + a];
-            else if (a >= NX && a < NX + 2) v = kp.B[i * 2 + (a - NX)];
+            if (a < 6) v = MODELS ? mdl_A[i * 6 + a] : kp.A[i * 6 + a];
+            else if (a >= NX && a < NX + 2) v = MODELS ? mdl_B[i * 2 + (a - NX)] : kp.B[i * 2 + (a - NX)];
         } else if (a == NX + 2 + (i - 6)) v = 1.0;
         LD(L::M + e) = v;
     }
@@ -1860,7 +1899,9 @@ crx_solve_kernel(const crx_kparams kp) {
                 double dsc, dec, dsn, den;
                 cbf_dist<NOBS, NMAX>(sm, c, i, ob, 0.0, dsc, dec, dsn, den);
                 const double rLs = LD(L::cst + 16 + ob), rWs = LD(L::cst + 16 + L::NO + ob);
-                const double rsc = kp.reach_s[i] * rLs, rec = kp.reach_gain[i] * rWs, rsn = kp.reach_s[i + 1] * rLs, ren = kp.reach_gain[i + 1] * rWs;
+                const double* rch_s = MODELS ? mdl_reach : kp.reach_s;
+                const double* rch_e = MODELS ? mdl_reach + (CRX_MAX_N + 1) : kp.reach_gain;
+                const double rsc = rch_s[i] * rLs, rec = rch_e[i] * rWs, rsn = rch_s[i + 1] * rLs, ren = rch_e[i + 1] * rWs;
                 const double mx_sn = fmax(fabs(dsn - rsn), fabs(dsn + rsn)), mx_en = fmax(fabs(den - ren), fabs(den + ren));
                 const double mn_sc = fabs(dsc) > rsc ? fabs(dsc) - rsc : 0.0, mn_ec = fabs(dec) > rec ? fabs(dec) - rec : 0.0;
                 const double Gmax = ipow_d(mx_sn, q) + ipow_d(mx_en, q) - c.om * (ipow_d(mn_sc, q) + ipow_d(mn_ec, q)) - c.alpha * c.cm;
@@ -2653,13 +2694,13 @@ __global__ void __launch_bounds__(WAVE) crx_select_kernel(const crx_select_kpara
 
 #ifdef CRX_PROBE_ONE
 // tools/kernel_resources.py one NOBS NMAX DEG NFIX: ONE instantiation, compiled alone (seconds instead of minutes)
-template __global__ void crx_solve_kernel<CRX_PROBE_ONE>(const crx_kparams);
+template __global__ void crx_solve_kernel<CRX_PROBE_ONE>(const crx_solve_params);
 #else
 // ------------------------------------------------------------------------------------------------
 // (7) launchers (plain C++ linkage inside the library; the C ABI lives in crx_api.hip)
 // ------------------------------------------------------------------------------------------------
 template <int NOBS, int NMAX, int DEG = 0, int NFIX = 0, int SPEC = 0, int QPM = 0>
-static hipError_t launch_t(const crx_kparams& kp, hipStream_t st) {
+static hipError_t launch_t(const crx_solve_params& kp, hipStream_t st) {
     if constexpr (NOBS == 0 && QPM == 0) {   // the all-linear problems: crx_ipm_opts.qp_method picks the instantiation (0 = predictor-corrector, 1 = filter line search)
         if (kp.opts.qp_method != 0) return launch_t<NOBS, NMAX, DEG, NFIX, SPEC, 1>(kp, st);
     }
@@ -2766,6 +2807,42 @@ hipError_t crx_launch_solve_spec(const crx_kparams& kp, hipStream_t st) {
     if (kp.N == 12) return launch_t<1, 12, 6, 12, 1>(kp, st);
     if (kp.N == 10) return launch_t<1, 12, 6, 10, 1>(kp, st);
     return hipErrorInvalidValue;
+}
+#elif CRX_TU_MODELS
+// crx_kernels_models.hip: the CBF NLP with one LTI model per problem, compiled three times with the flags of the unit whose instantiations it
+// mirrors (Makefile).  1: zero obstacle slots at N = 10 / 12 (the mpc_lti form; the main unit's flags); 2: one slot at N = 10 / 12 and three at
+// N = 20 (the racing shapes; the obstacle unit's flags); 3: every other (N, slots, exponent) the shared launch accepts, on the general
+// instantiations, built as crx_kernels_gen.hip builds them.  A launch walks 1 -> 2 -> 3.  The planner QP and the two-wave kernels have no such twin.
+hipError_t crx_launch_solve_models_obs(const crx_kparams_models& kp, int nobs_template, hipStream_t st);
+hipError_t crx_launch_solve_models_general(const crx_kparams_models& kp, int nobs_template, hipStream_t st);
+#if CRX_TU_MODELS == 1
+#define CRX_UNIT(name) name##_models
+template <class F>
+static bool select_inst(int nobs_template, int N, int, F&& f) { return nobs_template == 0 && select_fixed<0, 0, 10, 12>(N, f); }
+static hipError_t next_unit_launch(const crx_kparams_models& kp, int nobs_template, hipStream_t st) { return crx_launch_solve_models_obs(kp, nobs_template, st); }
+#elif CRX_TU_MODELS == 2
+#define CRX_UNIT(name) name##_models_obs
+template <class F>
+static bool select_inst(int nobs_template, int N, int degree, F&& f) {
+    if (degree != 6) return false;
+    if (nobs_template == 1) return select_fixed<1, 6, 10, 12>(N, f);
+    if (nobs_template == 3) return select_fixed<3, 6, 20>(N, f);
+    return false;
+}
+static hipError_t next_unit_launch(const crx_kparams_models& kp, int nobs_template, hipStream_t st) { return crx_launch_solve_models_general(kp, nobs_template, st); }
+#else
+static_assert(CRX_TU_GENERAL, "the third models unit is built like the general unit");
+#define CRX_UNIT(name) name##_models_general
+template <class F>
+static bool select_inst(int nobs_template, int N, int degree, F&& f) { return select_general(nobs_template, N, degree, f); }
+static hipError_t next_unit_launch(const crx_kparams_models&, int, hipStream_t) { return hipErrorInvalidValue; }
+#endif
+hipError_t CRX_UNIT(crx_launch_solve)(const crx_kparams_models& kp, int nobs_template, hipStream_t st) {
+    if (kp.batch == 0) return hipSuccess;
+    if (kp.mode != 1) return hipErrorInvalidValue;
+    hipError_t e = hipSuccess;
+    if (select_inst(nobs_template, kp.N, kp.degree, [&](auto i) { e = launch_t<i.nobs, i.nmax, i.deg, i.nfix>(kp, st); })) return e;
+    return next_unit_launch(kp, nobs_template, st);
 }
 #else
 #if CRX_TU_GENERAL

@@ -1,0 +1,59 @@
+// libcrx: crx_solve_kernel with ONE LTI MODEL PER PROBLEM (MPC-CBF NLP, tracking NLP; crx_cbf_solve_models*) as its own translation units --
+// same source as the shared-model instantiations (crx_kernels.hip), whose kernels take the model in crx_kparams.  Here the kernel takes
+// crx_kparams_models and problem b reads A, B from model_A[36 b ..], model_B[12 b ..] and its reach tables from model_reach -- in set-up only:
+// the model matrix M, crash_search (which reads M back) and the slack bounds.  The interior-point loop is the shared kernels' loop.
+// Compiled three times (Makefile, -DCRX_MODELS_UNIT=1..3), each time as the unit whose instantiations it mirrors is compiled:
+//   1  zero obstacle slots, N = 10 / 12            the main unit's flags
+//   2  one slot at N = 10 / 12, three at N = 20    the obstacle unit's flags
+//   3  everything else the shared launch accepts   crx_kernels_gen.hip's conservative build
+#ifndef CRX_MODELS_UNIT
+#error "crx_kernels_models.hip is compiled with -DCRX_MODELS_UNIT=1, 2 or 3 (Makefile)"
+#endif
+#define CRX_TU_MODELS CRX_MODELS_UNIT
+#if CRX_MODELS_UNIT == 3
+#include "crx_kernels_gen.hip"
+#else
+#include "crx_kernels_obs.hip"
+#endif
+
+#if CRX_MODELS_UNIT == 1
+// (lives in this unit, not beside crx_cbfprep_kernel, so that no code object of the shared-model library changes)
+// crx_cbf_reach_kernel: the reach tables of the CBF NLP for one LTI model per problem (crx_cbf_models_reach_dev).  One thread per (problem, row):
+// r = 0 restates reach_bound (crx_api.hip) for state row 4 (s), r = 1 for row 5 (ey), stages 0 .. N, entries past N zero, into
+// model_reach [batch][2][CRX_MAX_N + 1].  Same operations in the same order as the host function, every product and sum rounded on its own
+// (contraction off for the whole body; HIP's __dmul_rn / __dadd_rn are plain operators and would be fused), so a copy of the descriptor's
+// model gives the descriptor's table bit for bit.
+__global__ void __launch_bounds__(256) crx_cbf_reach_kernel(int N, int batch, double delta_max, double a_max, const double* model_A,
+                                                            const double* model_B, double* model_reach) {
+#pragma clang fp contract(off)
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= 2 * batch) return;
+    const int b = t >> 1, r = t & 1;
+    const double* A = model_A + (size_t)36 * b;
+    const double* B = model_B + (size_t)12 * b;
+    double* gain = model_reach + ((size_t)2 * b + r) * (CRX_MAX_N + 1);
+    double w[6] = {0, 0, 0, 0, r ? 0.0 : 1.0, r ? 1.0 : 0.0}, acc = 0.0;
+    gain[0] = 0.0;
+    for (int j = 1; j <= N; j++) {
+        double v0 = 0.0, v1 = 0.0, wn[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 6; i++) { v0 += w[i] * B[i * 2]; v1 += w[i] * B[i * 2 + 1]; }
+        acc += fabs(v0) * delta_max + fabs(v1) * a_max;
+        gain[j] = acc;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int i = 0; i < 6; i++) wn[a] += w[i] * A[i * 6 + a];
+#pragma unroll
+        for (int a = 0; a < 6; a++) w[a] = wn[a];
+    }
+    for (int j = N + 1; j <= CRX_MAX_N; j++) gain[j] = 0.0;
+}
+
+hipError_t crx_launch_cbf_reach(int N, int batch, double delta_max, double a_max, const double* model_A, const double* model_B, double* model_reach,
+                                hipStream_t st) {
+    if (batch == 0) return hipSuccess;
+    hipLaunchKernelGGL(crx_cbf_reach_kernel, dim3((2 * batch + 255) / 256), dim3(256), 0, st, N, batch, delta_max, a_max, model_A, model_B, model_reach);
+    return hipGetLastError();
+}
+#endif

@@ -44,7 +44,9 @@
 extern "C" {
 #endif
 
-#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_lqr_desc, crx_lqr_desc_default, crx_lqr_design, crx_lqr_design_dev, crx_lqr_step_dev,
+#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_cbf_models_reach_dev, crx_cbf_solve_models, crx_cbf_solve_models_dev,
+                          CRX_CBF_MODEL_REACH_DOUBLES; CRX_SINGULAR also from these -- new entry points only.
+                          0.4.0 (additive, same number): crx_lqr_desc, crx_lqr_desc_default, crx_lqr_design, crx_lqr_design_dev, crx_lqr_step_dev,
                           crx_ilqr_solve_models, crx_ilqr_solve_models_dev; CRX_SINGULAR also from crx_lqr_design -- new entry points only.
                           0.4.0 (additive, same number): crx_sysid_desc, crx_sysid_desc_default, crx_sysid_fit, crx_sysid_fit_dev,
                           crx_sysid_workspace_bytes, crx_pid_log_dev and status CRX_SINGULAR -- new entry points only.
@@ -796,6 +798,31 @@ int crx_cbf_solve_ordered_dev(const crx_cbf_desc* d, int batch, const int32_t* a
                               const double* xt, const double* obs_s, const double* obs_ey, const double* lap_off,
                               const int32_t* n_obs, const double* obs_dims, double* X, double* U, double* sigma, double* cost,
                               int32_t* status, double* kkt, int32_t* iters, void* stream);
+/* One LTI model per problem (a fleet of identified cars: crx_sysid_fit leaves model_A [batch][6][6], model_B [batch][6][2] on the device).
+ * Problem b is solved with ITS model; d->A, d->B are not read.  Besides the model the solver needs how far the boxed inputs can move s and ey
+ * of every stage (what it computes on the host for the descriptor's model): model_reach, CRX_CBF_MODEL_REACH_DOUBLES(batch) doubles owned by
+ * the caller, filled by crx_cbf_models_reach_dev.  The table depends on the models and on d's N, delta_max, a_max only: a closed loop
+ * computes it once.  For copies of d's model it equals the descriptor's table bit for bit.  The solve then equals the shared launch bit for
+ * bit wherever both run the same instantiation class: tuned kernels exist with models for zero or one obstacle slot at N = 10 / 12 and
+ * three slots at N = 20 (exponent 6); every other shape runs the general (run-time horizon / exponent) kernels with models, also where
+ * the shared launch has a tuned one (two slots at N = 10 / 12 / 20, zero or one at N = 20, three at N = 10 / 12, other horizons of a
+ * custom CRX_NFIX_LIST): the same iteration through another instantiation, same KKT point to solver tolerance, at the general
+ * kernels' speed (1.5 .. 2x slower than tuned ones).
+ *   crx_cbf_solve_models_dev   = crx_cbf_solve_ordered_dev + (model_A, model_B, model_reach) after x0.  All three NULL: the shared launch;
+ *                                any other mix of NULLs is CRX_ERR_ARG.  Every (N, n_obs_max, degree, per_stage_target) of the shared launch.
+ *   crx_cbf_solve_models       host pointers (model_A, model_B both or neither); stages them and computes the table itself.
+ * A problem whose model has a non-finite entry (a failed fit) is not iterated: status CRX_SINGULAR, iters 0, kkt inf, X / U / sigma / cost NaN
+ * -- on both paths; it is not an argument error.  The planner QP and the two-wave diagnostics kernel stay single-model. */
+#define CRX_CBF_MODEL_REACH_DOUBLES(batch) ((size_t)(batch) * 2 * (CRX_MAX_N + 1))
+int crx_cbf_models_reach_dev(const crx_cbf_desc* d, int batch, const double* model_A, const double* model_B, double* model_reach, void* stream);
+int crx_cbf_solve_models_dev(const crx_cbf_desc* d, int batch, const int32_t* active, const int32_t* order, const double* x0,
+                             const double* model_A, const double* model_B, const double* model_reach, const double* xt,
+                             const double* obs_s, const double* obs_ey, const double* lap_off, const int32_t* n_obs,
+                             const double* obs_dims, double* X, double* U, double* sigma, double* cost, int32_t* status, double* kkt,
+                             int32_t* iters, void* stream);
+int crx_cbf_solve_models(const crx_cbf_desc* d, int batch, const double* x0, const double* model_A, const double* model_B, const double* xt,
+                         const double* obs_s, const double* obs_ey, const double* lap_off, const int32_t* n_obs, const double* obs_dims,
+                         double* X, double* U, double* sigma, double* cost, int32_t* status, double* kkt, int32_t* iters);
 /* The order itself, computed on the device (one launch, a stable counting sort; equal keys keep index order):
  *   crx_order_longest_first_dev  from the iteration counts of the previous solve of these problems (iters [batch], e.g. the iters
  *                                output of the previous control step), longest first;

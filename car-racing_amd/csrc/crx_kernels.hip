@@ -123,6 +123,17 @@ __device__ __forceinline__ double ipow_d(double a, int p) {
 #define ROW_IS_CBF(j, n_) (NOBS > 0 && (j) < (n_) * NR && (j) % NR >= 8 + NOBS)
 // nothing moves across: placed after the loads of a phase so that they are issued back to back
 #define LOADS_DONE() __builtin_amdgcn_sched_barrier(0)
+// [r8] Two-pass phases of the tuned one-obstacle instantiations <1,12,6,*> (124 rows, 127 coordinates: two passes over the 64 lanes): left alone,
+// pass 1 loads only after pass 0 has stored -- the SINK-selected store addresses may alias anything -- and the lone wave sits out one more LDS
+// round trip per phase.  A phase whose bit is set here loads the operands of BOTH passes into per-pass locals, LOADS_DONE(), then computes and
+// stores pass by pass with the expressions and the store order of the plain form (same bits: tests/test_gpu_obs1_bits.py).  All six
+// together measured -1 % on the headline at no cost in registers (the peak is the unrolled Riccati sweep; DESIGN.md 5.1, profiles/r08_*);
+// every other instantiation keeps the plain form.
+#ifndef CRX_LOADS_FIRST
+#define CRX_LOADS_FIRST 0x3F   /* A/B builds: make EXTRA=-DCRX_LOADS_FIRST=0 is the plain form everywhere */
+#endif
+enum : unsigned { LF_ROW_STEP = 1, LF_ROW_TRIAL = 2, LF_ROW_ACCEPT = 4, LF_ACCEPT_Z = 8, LF_FIRST_ORDER = 16, LF_ASSEMBLE = 32 };
+template <int NOBS, int NMAX> constexpr unsigned LoadsFirst = (NOBS == 1 && NMAX == 12 && !CRX_TU_GENERAL) ? (unsigned)(CRX_LOADS_FIRST) : 0u;
 // end of a stage of an UNROLLED sweep [r4]: without it the scheduler lifts the loads of all later stages to the top of the sweep and the
 // registers they occupy are paid for in scratch (a wave writes its spills once: 100 B per lane were x8 the algorithmic bytes written of a cfg2 launch)
 #define STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -451,7 +462,7 @@ __device__ __forceinline__ void eval_rows(double* sm, const int* si, const Ctx& 
 
 // First-order pieces at the iterate: CBF derivative table G, CBF Jacobians Jc (scaled, stage
 // coordinates) and the Lagrangian gradient ga = grad f - J' nu per stage coordinate.
-template <int NOBS, int NMAX>
+template <int NOBS, int NMAX, unsigned LF = 0>
 __device__ __forceinline__ void first_order(double* sm, const int* si, const Ctx& c) {
     using L = Lay<NOBS, NMAX>;
     const int N = c.N;
@@ -494,6 +505,45 @@ __device__ __forceinline__ void first_order(double* sm, const int* si, const Ctx
         }
         SYNC();
     }
+    if constexpr ((LF & LF_FIRST_ORDER) != 0) {   // [r8] both passes load, then both compute (same expressions as the plain form below)
+        static_assert(NOBS > 0, "written for the obstacle instantiations");
+        constexpr int CPASS = (L::NV + WAVE - 1) / WAVE;
+        int rl[CPASS], rh[CPASS];
+        double cw[CPASS], xrv[CPASS], ze[CPASS], nl[CPASS], nh[CPASS], nuv[CPASS][NOBS], jv2[CPASS][NOBS];
+        // the row-of-coordinate table entries first, the multipliers they point to last: the entries are back by the time the loads between have been issued
+        COORDS(e, ev, c.lane, N * L::NZ + L::NX) { (void)ev; const int k = e / L::NZ, a = e - k * L::NZ; coord_rows<L>(si, c, e, k, a, rl[q_], rh[q_]); }
+        __builtin_amdgcn_sched_barrier(0);
+        COORDS(e, ev, c.lane, N * L::NZ + L::NX) {
+            (void)ev;
+            const int k = e / L::NZ, a = e - k * L::NZ, kk = k < N ? k : N - 1;
+            const bool isx = a < 6, isu = a >= L::NX && a < L::NX + 2;
+            cw[q_] = LD(L::cst + (isx ? a : (isu ? 6 + a - L::NX : 0))); xrv[q_] = LD(L::xr + k * 6 + (isx ? a : 0)); ze[q_] = LD(L::Z + e);
+#pragma unroll
+            for (int ob = 0; ob < NOBS; ob++) { nuv[q_][ob] = LD(L::rnu + kk * L::NR + 8 + NOBS + ob); jv2[q_][ob] = LD(L::Jc + (kk * L::NO + ob) * L::NZ + a); }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q_ = 0; q_ < CPASS; q_++) { nl[q_] = LD(L::rnu + (rl[q_] >= 0 ? rl[q_] : 0)); nh[q_] = LD(L::rnu + (rh[q_] >= 0 ? rh[q_] : 0)); }
+        LOADS_DONE();
+        COORDS(e, ev, c.lane, N * L::NZ + L::NX) {
+            (void)ev;
+            const int k = e / L::NZ, a = e - k * L::NZ;
+            const bool isx = a < 6, isu = a >= L::NX && a < L::NX + 2, iss0 = a >= 6 && a < L::NX, iss1 = a >= L::NX + 2;
+            const int o = iss0 ? a - 6 : (iss1 ? a - L::NX - 2 : 0);
+            const bool sig_on = (o < c.nobs) && ((iss0 && k == 0) || (iss1 && k < N));
+            const double w2 = sel(isx || isu, 2.0 * cw[q_], 0.0);
+            const double ref = sel(isx, xrv[q_], 0.0);
+            double g = w2 * (ze[q_] - ref);
+            g += (k == N && a == 4) ? c.lin_sN : 0.0;
+            g += sig_on ? c.wsig : 0.0;
+            g -= sel(rl[q_] >= 0, nl[q_], 0.0);
+            g += sel(rh[q_] >= 0, nh[q_], 0.0);
+#pragma unroll
+            for (int ob = 0; ob < NOBS; ob++) g -= sel(k < N, nuv[q_][ob] * jv2[q_][ob], 0.0);
+            g = (k == N && a >= L::NX) ? 0.0 : g;
+            LD(L::ga + e) = g;
+        }
+    } else
     COORDS(e, ev, c.lane, N * L::NZ + L::NX) {   // stage N has states only (127 entries at N=12, 1 obstacle: two passes, not three)
         (void)ev;
         // selects instead of branches: every divergent region costs ~30 cycles on a lone wave
@@ -652,10 +702,26 @@ __device__ __forceinline__ double box_certificate(double* sm, const int* si, con
 //   per coord Hd = cost diag + Sigma of its bound rows + "current" CBF curvature,
 //             hg = ga (reduced form) + J'w
 //   per stage kS,kE = "next" CBF curvature  (- nu d hess g_{k+1}), added to P[4][4], P[5][5]
-template <int NOBS, int NMAX>
+template <int NOBS, int NMAX, unsigned LF = 0>
 __device__ __forceinline__ void assemble_newton(double* sm, const int* si, const Ctx& c, double mu) {
     using L = Lay<NOBS, NMAX>;
     const int N = c.N;
+    if constexpr ((LF & LF_ASSEMBLE) != 0) {   // [r8] both passes load, then both compute (full layout; same expressions as the plain form below)
+        static_assert(!L::SLIM, "written for the full layout");
+        constexpr int RPASS = (L::MR + WAVE - 1) / WAVE;
+        double t[RPASS], nu[RPASS], rs[RPASS], cj[RPASS];
+        ROWS(j, jv, c.lane, c.m) { (void)jv; t[q_] = LD(L::rt + j); nu[q_] = LD(L::rnu + j); rs[q_] = LD(L::rsc + j); cj[q_] = LD(L::rc + j); }
+        LOADS_DONE();
+        ROWS(j, jv, c.lane, c.m) {
+            (void)jv;
+            const double rti = frcp(t[q_]);
+            LD(L::rtt + j) = rti;
+            const double sig = nu[q_] * rti;
+            const bool on = rs[q_] != 0.0;
+            LD(L::rsig + j) = sel(on, sig, 0.0);
+            LD(L::rw + j) = sel(on, nu[q_] - mu * rti + sig * (cj[q_] - t[q_]), 0.0);
+        }
+    } else
     ROWS(j, jv, c.lane, c.m) {
         (void)jv;
         const double t = LD(L::rt + j), nu = LD(L::rnu + j);
@@ -1396,15 +1462,18 @@ __device__ __forceinline__ bool restore_slacks(double* sm, const Ctx& c, double 
 // loop, for the problems that may need it (a provable crash state, or a CBF row violated at the zero start) -- inside the (re)start loop
 // its temporaries sat on top of the ~200 registers the sweeps hoist out of the loops (64 .. 164 B of scratch per lane).  crash_write()
 // is the light half and is what the restart runs.
-// A[i][j], B[i][j] for crash_search(): the descriptor's model, or (models units) the problem's own, read back from M, which set-up has filled
-template <class L>
+// A[i][j], B[i][j] for crash_search(): the descriptor's model, or (models units) the problem's own, read back from M, which set-up has filled.
+// [r8] FROM_M: the tuned one-obstacle instantiations read M back as well (the same doubles).  Indexed with the constants of the unrolled
+// roll-out, kp.A and kp.B arrive whole in s_load_dwordx16 bursts and are parked in VGPR lanes at once: 96 SGPRs of set-up that cost
+// <1,12,6,12> the third of its spill-carrier VGPRs.
+template <class L, bool FROM_M>
 __device__ __forceinline__ double model_a(const double* sm, const crx_kparams& kp, int i, int j) {
-    if constexpr (MODELS) return sm[L::M + i * L::NZ + j];
+    if constexpr (MODELS || FROM_M) return sm[L::M + i * L::NZ + j];
     else return kp.A[i * 6 + j];
 }
-template <class L>
+template <class L, bool FROM_M>
 __device__ __forceinline__ double model_b(const double* sm, const crx_kparams& kp, int i, int j) {
-    if constexpr (MODELS) return sm[L::M + i * L::NZ + L::NX + j];
+    if constexpr (MODELS || FROM_M) return sm[L::M + i * L::NZ + L::NX + j];
     else return kp.B[i * 2 + j];
 }
 template <int NOBS, int NMAX>
@@ -1416,6 +1485,7 @@ __device__ __forceinline__ int crash_search(double* sm, const Ctx& c, const crx_
     // violates a row carries it]
     constexpr int NX = L::NX, NZ = L::NZ, G1 = 5;
     (void)NX; (void)NZ;
+    constexpr bool FROM_M = NOBS == 1 && NMAX == 12 && !CRX_TU_GENERAL;   // (model_a, model_b)
     constexpr int SPAN = (L::SLIM ? 5 : 7) * L::MR;
     constexpr int CH = 32 * 2 * (NMAX + 1) <= SPAN ? 32 : 16;
     static_assert(L::rnu == L::rt + L::MR && L::rtt == L::rt + 4 * L::MR && (L::SLIM || L::rw == L::rt + 6 * L::MR), "rt, rnu, rc, rdt, rtt, rsig, rw are contiguous");
@@ -1446,8 +1516,8 @@ __device__ __forceinline__ int crash_search(double* sm, const Ctx& c, const crx_
                 for (int i = 0; i < 6; i++) {
                     double t = 0.0;
 #pragma unroll
-                    for (int j = 0; j < 6; j++) t += model_a<L>(sm, kp, i, j) * x[j];
-                    t += model_b<L>(sm, kp, i, 0) * u0 + model_b<L>(sm, kp, i, 1) * u1;
+                    for (int j = 0; j < 6; j++) t += model_a<L, FROM_M>(sm, kp, i, j) * x[j];
+                    t += model_b<L, FROM_M>(sm, kp, i, 0) * u0 + model_b<L, FROM_M>(sm, kp, i, 1) * u1;
                     xn[i] = t;
                 }
 #pragma unroll
@@ -1623,6 +1693,10 @@ crx_solve_kernel(const crx_solve_params kp) {
     using L = Lay<NOBS, NMAX>;
     static_assert(!SPEC || (NOBS > 0 && !L::SLIM && CRX_STATIC_LDS), "the speculating wave exists for the obstacle instantiations of the full, static layout");
     constexpr int NX = L::NX, NZ = L::NZ, NR = L::NR;
+    // [r8] the phases of this instantiation that load both passes before they compute (LoadsFirst), and the passes of a row / coordinate phase
+    constexpr unsigned LF = (NFIX != 0 && QPM == 0) ? LoadsFirst<NOBS, NMAX> : 0u;
+    constexpr int RPASS = (L::MR + WAVE - 1) / WAVE, CPASS = (L::NV + WAVE - 1) / WAVE;
+    static_assert(LF == 0 || !L::SLIM, "the loads-first row passes are written for the full layout (row_scale, row_bound, row_sig_w are loads there)");
 #if CRX_STATIC_LDS
     // [r4] The layout is a compile-time constant, so the array is STATIC: the compiler then knows its address (0) and folds it into the
     // offset fields.  As `extern __shared__` the base stays a symbol until emission and every address computed at run time carries an
@@ -2281,7 +2355,7 @@ crx_solve_kernel(const crx_solve_params kp) {
         const double tau = ipm_tau(mu, o.tau_min);
         // ---- Newton step ---------------------------------------------------------------------------
         long long tc3 = CLK();
-        assemble_newton<NOBS, NMAX>(sm, si, c, mu);
+        assemble_newton<NOBS, NMAX, LF>(sm, si, c, mu);
         long long tc4 = CLK();
         // inertia correction: retry the sweep with a growing regularisation dw until every pivot is positive (one call
         // site: the sweep is inlined once)
@@ -2364,12 +2438,8 @@ crx_solve_kernel(const crx_solve_params kp) {
         // fraction-to-the-boundary without per-row divisions: a = min(1, tau / max_j(-d_j / v_j))
         double rp_max = 0.0, rd_max = 0.0, theta = 0.0, Dphi = 0.0;
         // (jd = J dz of the row; shared tail of the simple-row passes and of the CBF pass)
-        auto row_step = [&](int j, bool cnt, bool store, double sc, double jd) {
-            const bool on = sc != 0.0;
-            const double t = LD(L::rt + j), nu = LD(L::rnu + j), rti = LD(L::rtt + j), rcj = LD(L::rc + j);
-            double rwj, rsj;
-            row_sig_w<L>(sm, j, on, mu, t, nu, rti, rcj, rsj, rwj);
-            ROW_LOADS_DONE();
+        // (the part of a row step behind its loads: rsj, rwj = Sigma and w of the row, row_sig_w)
+        auto row_step_tail = [&](int j, bool cnt, bool store, bool on, double jd, double t, double nu, double rti, double rcj, double rsj, double rwj) {
             const double rp = rcj - t;
             const double dt = sel(on, jd + rp, 0.0);
             // dnu = (mu - t nu - nu dt)/t = mu/t - nu - Sigma dt = -w + Sigma (rp - dt)
@@ -2381,9 +2451,37 @@ crx_solve_kernel(const crx_solve_params kp) {
             theta += sel(cnt && on, fabs(rp), 0.0);
             Dphi -= sel(cnt && on, mu * dtr, 0.0);
         };
+        auto row_step = [&](int j, bool cnt, bool store, double sc, double jd) {
+            const bool on = sc != 0.0;
+            const double t = LD(L::rt + j), nu = LD(L::rnu + j), rti = LD(L::rtt + j), rcj = LD(L::rc + j);
+            double rwj, rsj;
+            row_sig_w<L>(sm, j, on, mu, t, nu, rti, rcj, rsj, rwj);
+            ROW_LOADS_DONE();
+            row_step_tail(j, cnt, store, on, jd, t, nu, rti, rcj, rsj, rwj);
+        };
+        // J dz straight from the step (differencing row values would lose eps*|x|, which the
+        // multiplier update amplifies by Sigma = nu/t ~ 1e10..1e13)
+        if constexpr ((LF & LF_ROW_STEP) != 0) {   // full layout: row_scale and row_sig_w are loads
+            int pk[RPASS];
+            double sc[RPASS], dz[RPASS], t[RPASS], nu[RPASS], rti[RPASS], rcj[RPASS], rsj[RPASS], rwj[RPASS];
+            ROWS(j, jv, lane, m) { (void)jv; pk[q_] = RIVT(si, j); }
+            __builtin_amdgcn_sched_barrier(0);   // the table entries first: they are back by the time the other loads have been issued
+            ROWS(j, jv, lane, m) {
+                (void)jv;
+                sc[q_] = row_scale<L>(sm, si, j, N);
+                t[q_] = LD(L::rt + j); nu[q_] = LD(L::rnu + j); rti[q_] = LD(L::rtt + j); rcj[q_] = LD(L::rc + j);
+                row_sig_w<L>(sm, j, true, mu, t[q_], nu[q_], rti[q_], rcj[q_], rsj[q_], rwj[q_]);
+            }
+            __builtin_amdgcn_sched_barrier(0);   // ... and the loads that need them go last
+#pragma unroll
+            for (int q_ = 0; q_ < RPASS; q_++) dz[q_] = LD(L::dZ + RIV_IDX(pk[q_]));
+            LOADS_DONE();
+            ROWS(j, jv, lane, m) {
+                const bool simple = !ROW_IS_CBF(j, N);
+                row_step_tail(j, jv && simple, simple, sc[q_] != 0.0, RIV_SGN(pk[q_]) * dz[q_], t[q_], nu[q_], rti[q_], rcj[q_], rsj[q_], rwj[q_]);
+            }
+        } else
         ROWS(j, jv, lane, m) {
-            // J dz straight from the step (differencing row values would lose eps*|x|, which the
-            // multiplier update amplifies by Sigma = nu/t ~ 1e10..1e13)
             const bool simple = !ROW_IS_CBF(j, N);
             const int pk = RIVT(si, j);
             const double sc = row_scale<L>(sm, si, j, N), jd = RIV_SGN(pk) * LD(L::dZ + RIV_IDX(pk));
@@ -2431,6 +2529,15 @@ crx_solve_kernel(const crx_solve_params kp) {
                 lg.mul(sel(cnt, tn, 1.0));
                 thn += sel(cnt, fabs(cn - tn), 0.0);
             };
+            if constexpr ((LF & LF_ROW_TRIAL) != 0) {
+                double sc[RPASS], t[RPASS], dt[RPASS], cj[RPASS];
+                ROWS(j, jv, lane, m) { (void)jv; sc[q_] = row_scale<L>(sm, si, j, N); t[q_] = LD(L::rt + j); dt[q_] = LD(L::rdt + j); cj[q_] = LD(L::rc + j); }
+                LOADS_DONE();
+                ROWS(j, jv, lane, m) {
+                    const bool simple = !ROW_IS_CBF(j, N);
+                    row_trial(j, jv && simple, simple, sc[q_], cj[q_] + al * (dt[q_] - (cj[q_] - t[q_])), t[q_], dt[q_]);
+                }
+            } else
             ROWS(j, jv, lane, m) {
                 const bool simple = !ROW_IS_CBF(j, N);
                 const double sc = row_scale<L>(sm, si, j, N), t = LD(L::rt + j), dt = LD(L::rdt + j), cj = LD(L::rc + j);
@@ -2487,6 +2594,15 @@ crx_solve_kernel(const crx_solve_params kp) {
         }
         // ---- accept ------------------------------------------------------------------------------------
         SYNC();
+        if constexpr ((LF & LF_ACCEPT_Z) != 0) {
+            double zo[CPASS], dz[CPASS];
+            COORDS(e, ev, lane, N * NZ + NX) { (void)ev; zo[q_] = LD(L::Z + e); dz[q_] = LD(L::dZ + e); }
+            LOADS_DONE();
+            COORDS(e, ev, lane, N * NZ + NX) {
+                const double zn = zo[q_] + al * dz[q_];
+                LD(SINK(ev, L::Z + e)) = zn;
+            }
+        } else
         COORDS(e, ev, lane, N * NZ + NX) {
             const double zn = LD(L::Z + e) + al * LD(L::dZ + e);
             LD(SINK(ev, L::Z + e)) = zn;                // read-modify-write
@@ -2498,13 +2614,9 @@ crx_solve_kernel(const crx_solve_params kp) {
         // iterate (simple rows exactly from Z, CBF rows evaluated), and the two divergence-test reductions
         double numax = 0.0, th = 0.0;
         nus = 0.0; cmax = 0.0; cmin = INFINITY;
-        auto row_accept = [&](int j, bool own, double sc, double v) {   // own: this lane is the one that updates row j
-            const bool on = sc != 0.0, cnt = own && on;
-            const double tn = LD(L::rtt + j), rcj = LD(L::rc + j), rtj = LD(L::rt + j);
-            const double rdj = LD(L::rdt + j), rnj = LD(L::rnu + j);
-            double rwj, rsj;   // (slim: 1/t is recomputed -- rtt holds the trial slack by now; frcp(t) returns what assemble_newton stored)
-            row_sig_w<L>(sm, j, on, mu, rtj, rnj, L::SLIM ? frcp(rtj) : 0.0, rcj, rsj, rwj);
-            ROW_LOADS_DONE();
+        // (the part of an accepted row behind its loads)
+        auto row_accept_tail = [&](int j, bool own, bool on, double v, double tn, double rcj, double rtj, double rdj, double rnj, double rsj, double rwj) {
+            const bool cnt = own && on;
             const double mut = mu * frcp(tn);
             const double rp = rcj - rtj;                       // dnu as in the row-step pass (rc, rt, rw, rsig still hold that state)
             const double dnu = -rwj + rsj * (rp - rdj);
@@ -2519,6 +2631,34 @@ crx_solve_kernel(const crx_solve_params kp) {
             cmin = fmin(cmin, sel(cnt, tn * nn, INFINITY));
             LD(SINK(own, L::rc + j)) = sel(on, v, 1.0);
         };
+        auto row_accept = [&](int j, bool own, double sc, double v) {   // own: this lane is the one that updates row j
+            const bool on = sc != 0.0;
+            const double tn = LD(L::rtt + j), rcj = LD(L::rc + j), rtj = LD(L::rt + j);
+            const double rdj = LD(L::rdt + j), rnj = LD(L::rnu + j);
+            double rwj, rsj;   // (slim: 1/t is recomputed -- rtt holds the trial slack by now; frcp(t) returns what assemble_newton stored)
+            row_sig_w<L>(sm, j, on, mu, rtj, rnj, L::SLIM ? frcp(rtj) : 0.0, rcj, rsj, rwj);
+            ROW_LOADS_DONE();
+            row_accept_tail(j, own, on, v, tn, rcj, rtj, rdj, rnj, rsj, rwj);
+        };
+        if constexpr ((LF & LF_ROW_ACCEPT) != 0) {   // full layout: row_scale, row_bound and row_sig_w are loads
+            int pk[RPASS];
+            double sc[RPASS], zv[RPASS], rb[RPASS], tn[RPASS], rcj[RPASS], rtj[RPASS], rdj[RPASS], rnj[RPASS], rsj[RPASS], rwj[RPASS];
+            ROWS(j, jv, lane, m) { (void)jv; pk[q_] = RIVT(si, j); }
+            __builtin_amdgcn_sched_barrier(0);   // the table entries first: they are back by the time the other loads have been issued
+            ROWS(j, jv, lane, m) {
+                (void)jv;
+                sc[q_] = row_scale<L>(sm, si, j, N); rb[q_] = row_bound<L>(sm, c, j);
+                tn[q_] = LD(L::rtt + j); rcj[q_] = LD(L::rc + j); rtj[q_] = LD(L::rt + j); rdj[q_] = LD(L::rdt + j); rnj[q_] = LD(L::rnu + j);
+                row_sig_w<L>(sm, j, true, mu, rtj[q_], rnj[q_], 0.0, rcj[q_], rsj[q_], rwj[q_]);
+            }
+            __builtin_amdgcn_sched_barrier(0);   // (as in the row steps: the loads that need the table entry go last)
+#pragma unroll
+            for (int q_ = 0; q_ < RPASS; q_++) zv[q_] = LD(L::Z + RIV_IDX(pk[q_]));
+            LOADS_DONE();
+            ROWS(j, jv, lane, m) {
+                row_accept_tail(j, jv && !ROW_IS_CBF(j, N), sc[q_] != 0.0, RIV_SGN(pk[q_]) * (zv[q_] - rb[q_]), tn[q_], rcj[q_], rtj[q_], rdj[q_], rnj[q_], rsj[q_], rwj[q_]);
+            }
+        } else
         ROWS(j, jv, lane, m) {
             const int pk = RIVT(si, j);
             const double sc = row_scale<L>(sm, si, j, N), v = RIV_SGN(pk) * (LD(L::Z + RIV_IDX(pk)) - row_bound<L>(sm, c, j));
@@ -2538,7 +2678,7 @@ crx_solve_kernel(const crx_solve_params kp) {
         }
         nus = wave_sum(nus);
         e_p = th;
-        first_order<NOBS, NMAX>(sm, si, c);
+        first_order<NOBS, NMAX, LF>(sm, si, c);
         if (kp.trace && b == kp.trace_problem && it < (kp.trace_rows < 0 ? -kp.trace_rows : kp.trace_rows) && lane == 0 && kp.trace_rows > 0)
             kp.trace[(size_t)it * 16 + 8] = (double)(tph[0] + (CLK() - tc8));   // slot 8: KKT rows + accept/first-order
         if (numax > 1e12 && th > 1e-6) { status = CRX_STALLED; it++; break; }   // IPOPT's divergence heuristic: not a proof

@@ -1,30 +1,61 @@
 """Registers, scratch and occupancy of the solver kernels, from the compiler's own remarks (no GPU needed):
-    python tools/kernel_resources.py [obs|plan|gen|lmpc|models_plan|models_obs|models_gen]     (recompiles the translation unit with -Rpass-analysis=kernel-resource-usage)"""
-import os, re, subprocess, sys
+    python tools/kernel_resources.py [obs|plan|gen|lmpc|models_plan|models_obs|models_gen]     (recompiles the translation unit with -Rpass-analysis=kernel-resource-usage)
+    python tools/kernel_resources.py lib [FILE.so]     what SHIPS: the kernel metadata of every code object embedded in the library (default: the in-tree
+                                                       libcrx.so), no recompilation -- shipped() below, which tests/test_kernel_budget_cpu.py asserts on"""
+import os, re, subprocess, sys, tempfile
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 S = os.path.join(ROOT, "car-racing_amd", "csrc")
-which = sys.argv[1] if len(sys.argv) > 1 else "obs"
-src, sched = {"one": (None, None), "obs": ("crx_kernels_obs.hip", ["-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]),
-              "plan": ("crx_kernels.hip", ["-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
-              "gen": ("crx_kernels_gen.hip", ["-mllvm", "-disable-machine-licm"]),
-              # one LTI model per problem (crx_kernels_models.hip): each unit with the flags of the unit it mirrors
-              "models_plan": ("crx_kernels_models.hip", ["-DCRX_MODELS_UNIT=1", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
-              "models_obs": ("crx_kernels_models.hip", ["-DCRX_MODELS_UNIT=2", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]),
-              "models_gen": ("crx_kernels_models.hip", ["-DCRX_MODELS_UNIT=3", "-mllvm", "-disable-machine-licm"]),
-              "lmpc": ("crx_lmpc.hip", ["-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"])}[which]
-extra = sys.argv[2:]
-if which == "one":   # python tools/kernel_resources.py one NOBS NMAX DEG NFIX [flags]
-    tpl = ",".join(sys.argv[2:6]); extra = sys.argv[6:]
-    src = "crx_kernels.hip"
-    sched = (["-DCRX_TU_OBSTACLES", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"] if sys.argv[2] != "0" else
-             ["-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]) + ["-DCRX_PROBE_ONE=" + tpl]
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function"] + sched + extra + [
-    "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(S, src), "-o", "/dev/null"]
-t = subprocess.run(cmd, capture_output=True, text=True).stderr
-def demangle(n):   # crx_solve_kernel<NOBS, NMAX, DEG, NFIX>: _Z16crx_solve_kernelILi1ELi12ELi6ELi12EEv10crx_kparams
+READELF = os.environ.get("LLVM_READELF", "/opt/rocm/lib/llvm/bin/llvm-readelf")
+def demangle(n):   # crx_solve_kernel<NOBS, NMAX, DEG, NFIX, ..>: _Z16crx_solve_kernelILi1ELi12ELi6ELi12ELi0ELi0EEv11crx_kparams
     m = re.match(r"_Z\d+([a-z_]+)I((?:Li\d+E|Lb[01]E)+)E", n)
     return "%s<%s>" % (m.group(1), ",".join(re.findall(r"L[ib](\d+)E", m.group(2)))) if m else n
-for b in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
-    g = lambda k: (re.search(k + r": (\d+)", b) or [0, "?"])[1]
-    print("%-44s vgpr %3s agpr %3s scratch %4s B/lane  waves/SIMD %s" % (demangle(b.split("\n")[0].split(" [")[0]), g("VGPRs"), g("AGPRs"),
-          g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]")))
+def shipped(lib=None):
+    """{mangled kernel name: {vgpr, agpr, sgpr, sgpr_spill, vgpr_spill, scratch (B/lane), lds (B)}} of every kernel embedded in the library, from the
+    metadata notes of its code objects (extracted as tools/exec_prologue_check.py extracts them)."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import exec_prologue_check as epc
+    lib = lib or os.path.join(ROOT, "car-racing_amd", "crx", "libcrx.so")
+    keys = {"vgpr_count": "vgpr", "agpr_count": "agpr", "sgpr_count": "sgpr", "sgpr_spill_count": "sgpr_spill", "vgpr_spill_count": "vgpr_spill",
+            "private_segment_fixed_size": "scratch", "group_segment_fixed_size": "lds"}
+    out = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for co in epc.code_objects(lib, tmp):
+            notes = subprocess.run([READELF, "--notes", co], capture_output=True, text=True, check=True).stdout
+            for blk in re.split(r"\n\s+- \.", notes):   # one list entry of amdhsa.kernels per kernel
+                name = re.search(r"\.name:\s+(\S+)", blk)
+                if not name or ".vgpr_count" not in blk:
+                    continue
+                out[name.group(1)] = {v: int(m.group(1)) for k, v in keys.items() if (m := re.search(r"\." + k + r":\s+(\d+)", blk))}
+    return out
+which = sys.argv[1] if len(sys.argv) > 1 else "obs"
+if __name__ != "__main__":
+    which = None
+elif which == "lib":
+    for n, r in sorted(shipped(sys.argv[2] if len(sys.argv) > 2 else None).items(), key=lambda kv: demangle(kv[0])):
+        print("%-52s vgpr %3d agpr %3d sgpr spills %3d scratch %4d B/lane  LDS %6d B" % (demangle(n) + (" [models]" if "models" in n else ""), r["vgpr"], r.get("agpr", 0),
+              r["sgpr_spill"], r["scratch"], r["lds"]))
+    sys.exit(0)
+def recompile():
+    src, sched = {"one": (None, None), "obs": ("crx_kernels_obs.hip", ["-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]),
+                  "plan": ("crx_kernels.hip", ["-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
+                  "gen": ("crx_kernels_gen.hip", ["-mllvm", "-disable-machine-licm"]),
+                  # one LTI model per problem (crx_kernels_models.hip): each unit with the flags of the unit it mirrors
+                  "models_plan": ("crx_kernels_models.hip", ["-DCRX_MODELS_UNIT=1", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
+                  "models_obs": ("crx_kernels_models.hip", ["-DCRX_MODELS_UNIT=2", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]),
+                  "models_gen": ("crx_kernels_models.hip", ["-DCRX_MODELS_UNIT=3", "-mllvm", "-disable-machine-licm"]),
+                  "lmpc": ("crx_lmpc.hip", ["-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"])}[which]
+    extra = sys.argv[2:]
+    if which == "one":   # python tools/kernel_resources.py one NOBS NMAX DEG NFIX [flags]
+        tpl = ",".join(sys.argv[2:6]); extra = sys.argv[6:]
+        src = "crx_kernels.hip"
+        sched = (["-DCRX_TU_OBSTACLES", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"] if sys.argv[2] != "0" else
+                 ["-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]) + ["-DCRX_PROBE_ONE=" + tpl]
+    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function"] + sched + extra + [
+        "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(S, src), "-o", "/dev/null"]
+    t = subprocess.run(cmd, capture_output=True, text=True).stderr
+    for b in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
+        g = lambda k: (re.search(k + r": (\d+)", b) or [0, "?"])[1]
+        print("%-44s vgpr %3s agpr %3s scratch %4s B/lane  waves/SIMD %s" % (demangle(b.split("\n")[0].split(" [")[0]), g("VGPRs"), g("AGPRs"),
+              g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]")))
+if __name__ == "__main__":
+    recompile()

@@ -268,7 +268,7 @@ def gen_cfg4_stopped(idx_file="/tmp/cfg4_stopped_idx.npy", procs=int(os.environ.
         d.opts.restore_iters = 25
         orc.lib.crx_oracle_set_knob(2, ctypes.c_double(50.0))
         r = orc.cbf_solve(d, *[p[k] for k in ("x0", "xt", "obs_s", "obs_ey", "lap_off", "n_obs")])
-        orc.lib.crx_oracle_set_knob(2, ctypes.c_double(100.0))
+        orc.lib.crx_oracle_set_knob(2, ctypes.c_double(0.0))     # the knob's default: 0 = the descriptor's stall_iters
         bad = np.nonzero(r["status"] != 0)[0]
         np.save(idx_file, bad)
         np.save(idx_file.replace("_idx", "_status"), r["status"][bad])

@@ -218,3 +218,93 @@ def oracle_planner_probe(orc, d, x0, bez_s, bez_ey, ey_lb, ey_ub, U):
     assert rc == 0, rc
     b = box[4:].reshape(4, N + 1)
     return dict(cost=cost.value, ulo=box[0:2], uhi=box[2:4], vlo=b[0], vhi=b[1], elo=b[2], ehi=b[3], X=X)
+
+
+def lmpcprep_abi_desc(desc):
+    """crx_lmpcprep_desc from the plain descriptor of tests/lmpcprep_model.py (bandwidth and scale are fields of it too)."""
+    d = abi.lmpcprep_desc(desc.N, desc.n_points, desc.n_laps, desc.n_seg, desc.dt, desc.lap_length, n_ss_per_lap=desc.n_ss_per_lap,
+                          n_ss_laps=desc.n_ss_laps, max_neighbours=desc.max_neighbours, shift=desc.shift)
+    d.bandwidth = float(desc.bandwidth)
+    for c in range(5):
+        d.scale[c] = float(desc.scale[c])
+    return d
+
+
+_LMPCPREP_CASES, _LMPCPREP_REF = {}, {}
+
+
+def lmpcprep_cases():
+    """The calls of tests/lmpcprep_model.all_cases(), generated once per process."""
+    import lmpcprep_model
+
+    if not _LMPCPREP_CASES:
+        _LMPCPREP_CASES.update(lmpcprep_model.all_cases())
+    return _LMPCPREP_CASES
+
+
+def lmpcprep_seed(case):
+    """The A, B, C a call of the prep starts from: what a singular stage must leave in its three regression rows."""
+    d = case["desc"]
+    Bn = len(case["args"][4])
+    rng = np.random.default_rng(len(case["name"]) + 7 * d.N + d.n_points)
+    return rng.normal(size=(Bn, d.N, 6, 6)), rng.normal(size=(Bn, d.N, 6, 2)), rng.normal(size=(Bn, d.N, 6))
+
+
+def lmpcprep_reference(orc, case):
+    """(oracle result, model result (A, B, C, ss, qfun, status, record)) of one call, computed once per process and shared."""
+    import lmpcprep_model
+
+    if case["name"] not in _LMPCPREP_REF:
+        seed = lmpcprep_seed(case)
+        ro = orc.lmpc_prep(lmpcprep_abi_desc(case["desc"]), *case["args"], from_plan=case["from_plan"], seed=seed)
+        _LMPCPREP_REF[case["name"]] = (ro, lmpcprep_model.run_model(case, seed=seed))
+    return _LMPCPREP_REF[case["name"]]
+
+
+# Largest |oracle - model| of a prediction over all well-posed stages of all calls of lmpcprep_cases(), measured on the CPU (float64
+# oracle in the kernel's summation order against the longdouble model; tests/test_lmpcprep_model_cpu.py::test_prediction_deviation
+# repeats and prints it): 1.23e-13 over 1265 stages -- the normal matrices of these synthetic laps have condition 1e2..1e4, the
+# predictions are of size 1, a float64 sum over up to 128 samples carries ~1e-16 into a solve of that condition.  The tolerance is ten
+# times that, rounded up to one digit.
+LMPCPREP_PRED_DEV_MEASURED = 1.23e-13
+LMPCPREP_PRED_TOL = 2e-12
+
+LMPCPREP_CASE_NAMES = ("a", "b", "c", "d", "e", "f")
+
+
+def lmpcprep_compare_with_model(res, model, case, label, tol=LMPCPREP_PRED_TOL):
+    """The rule of tests/test_lmpcprep_model_cpu.py (module docstring) for one call's result `res` (a dict as Binding.lmpc_prep returns
+    it) against the model's.  -> largest prediction deviation over the well-posed stages."""
+    import lmpcprep_model
+
+    A, B, C, ss_sel, q_sel, status, rec = model
+    lp, li = case["args"][6], case["args"][7]
+    np.testing.assert_array_equal(res["status"], status, err_msg=label)
+    np.testing.assert_array_equal(res["ss"], ss_sel, err_msg=label)
+    np.testing.assert_array_equal(res["qfun"], q_sel, err_msg=label)
+    np.testing.assert_allclose(res["A"][:, :, 3:], A[:, :, 3:], rtol=0, atol=1e-13, err_msg=label)
+    np.testing.assert_allclose(res["C"][:, :, 3:], C[:, :, 3:], rtol=0, atol=1e-12, err_msg=label)
+    np.testing.assert_array_equal(res["B"][:, :, 3:], 0.0, err_msg=label)
+    wp = lmpcprep_model.well_posed(rec)
+    pred = lmpcprep_model.predictions
+    dev = np.abs(pred(res["A"], res["B"], res["C"], lp, li, case["from_plan"]) - pred(A, B, C, lp, li, case["from_plan"]))
+    worst = float(dev[wp].max()) if wp.any() else 0.0
+    assert worst <= tol, (label, worst)
+    return worst
+
+
+def lmpcprep_oracle_addpoint(orc, case):
+    """crx_oracle_lmpc_addpoint race by race (it refuses a whole batch for one iter outside 1..L) -> (ss, us, rc per race)."""
+    import ctypes
+
+    d = lmpcprep_abi_desc(case["desc"])
+    ss, us = case["ss"].copy(), case["us"].copy()
+    fn = orc.lib.crx_oracle_lmpc_addpoint
+    fn.restype = ctypes.c_int
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    rc = []
+    for b in range(len(case["it"])):
+        ts, it, st = (np.ascontiguousarray(case[k][b:b + 1], dtype=np.int32) for k in ("time_ss", "it", "step"))
+        x, u = np.ascontiguousarray(case["x"][b:b + 1]), np.ascontiguousarray(case["u"][b])
+        rc.append(fn(ctypes.byref(d), ctypes.c_int(1), p(ss[b]), p(us[b]), p(ts), p(it), p(st), p(x), p(u), ctypes.c_int(case["u_stride"])))
+    return ss, us, np.array(rc)

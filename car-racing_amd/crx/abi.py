@@ -374,7 +374,8 @@ class Binding:
     def __init__(self, lib, prefix):
         self.lib, self.prefix = lib, prefix
         for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve", "ilqr_solve",
-                     "ilqr_solve_models", "lqr_design", "sysid_fit", "cbf_solve_models"):
+                     "ilqr_solve_models", "lqr_design", "sysid_fit", "cbf_solve_models", "planner_solve_models", "planner_plan",
+                     "planner_plan_models"):
             if hasattr(lib, prefix + name):
                 getattr(lib, prefix + name).restype = C.c_int
         self._check = None
@@ -389,7 +390,9 @@ class Binding:
                 msg = (f() or b"").decode()
             raise RuntimeError("%s%s failed: rc=%d %s" % (self.prefix, name, rc, msg))
 
-    def planner_solve(self, desc, x0, bez_s, bez_ey, ey_lb, ey_ub):
+    def planner_solve(self, desc, x0, bez_s, bez_ey, ey_lb, ey_ub, models=None):
+        """crx_planner_solve.  models = (A (Bn,6,6), B (Bn,6,2)) float64: crx_planner_solve_models, region QP b on its own model (desc.A,
+        desc.B are ignored); a QP whose model has a non-finite entry reports CRX_SINGULAR with the fall-back trajectory and cost inf."""
         N = desc.N
         x0 = np.ascontiguousarray(x0, dtype=_D)
         Bn = x0.shape[0]
@@ -402,6 +405,13 @@ class Binding:
             X=np.zeros((Bn, N + 1, 6)), U=np.zeros((Bn, N, 2)), cost=np.zeros(Bn),
             status=np.zeros(Bn, dtype=_I), kkt=np.zeros(Bn), iters=np.zeros(Bn, dtype=_I),
         )
+        if models is not None:
+            mA, mB = cbf_models(models, Bn)
+            self._call(
+                "planner_solve_models", C.byref(desc), C.c_int(Bn), _p(x0), _p(mA), _p(mB), _p(bez_s), _p(bez_ey), _p(ey_lb),
+                _p(ey_ub), _p(out["X"]), _p(out["U"]), _p(out["cost"]), _p(out["status"]), _p(out["kkt"]), _p(out["iters"]),
+            )
+            return out
         self._call(
             "planner_solve", C.byref(desc), C.c_int(Bn), _p(x0), _p(bez_s), _p(bez_ey), _p(ey_lb),
             _p(ey_ub), _p(out["X"]), _p(out["U"]), _p(out["cost"]), _p(out["status"]),
@@ -522,10 +532,12 @@ class Binding:
         )
         return out
 
-    def planner_plan(self, desc, sdesc, x0, bez_s, bez_ey, ey_lb, ey_ub, n_veh, obs_s, obs_ey, old_flag):
+    def planner_plan(self, desc, sdesc, x0, bez_s, bez_ey, ey_lb, ey_ub, n_veh, obs_s, obs_ey, old_flag, models=None):
         """Fused planner step (crx_planner_plan): all region QPs of every scenario + the selection.
         Arrays of the QP part have leading dimension S*(V+1), scenario-major.  Only libcrx exports it;
-        the oracle composes planner_solve + select (tests compare the two)."""
+        the oracle composes planner_solve + select (tests compare the two).
+        models = (A (S,6,6), B (S,6,2)) float64, one model per SCENARIO: crx_planner_plan_models, every region QP of scenario i on
+        model i (expanded here to the C ABI's one model per region QP; desc.A, desc.B are ignored)."""
         N, V = desc.N, sdesc.n_veh_max
         n_veh = np.ascontiguousarray(n_veh, dtype=_I)
         S = n_veh.shape[0]
@@ -543,8 +555,16 @@ class Binding:
             status=np.zeros(Bn, dtype=_I), kkt=np.zeros(Bn), iters=np.zeros(Bn, dtype=_I),
             flag=np.zeros(S, dtype=_I), sel_cost=np.zeros((S, V + 1)), best_X=np.zeros((S, N + 1, 6)),
         )
-        fn = getattr(self.lib, self.prefix + "planner_plan")
-        fn.restype = C.c_int
+        if models is not None:
+            mA, mB = cbf_models(models, S)
+            mA, mB = np.repeat(mA, V + 1, axis=0), np.repeat(mB, V + 1, axis=0)
+            self._call(
+                "planner_plan_models", C.byref(desc), C.byref(sdesc), C.c_int(S), _p(x0), _p(mA), _p(mB), _p(bez_s), _p(bez_ey),
+                _p(ey_lb), _p(ey_ub), _p(n_veh), _p(obs_s), _p(obs_ey), _p(old_flag), _p(out["X"]),
+                _p(out["U"]), _p(out["cost"]), _p(out["status"]), _p(out["kkt"]), _p(out["iters"]),
+                _p(out["flag"]), _p(out["sel_cost"]), _p(out["best_X"]),
+            )
+            return out
         self._call(
             "planner_plan", C.byref(desc), C.byref(sdesc), C.c_int(S), _p(x0), _p(bez_s), _p(bez_ey),
             _p(ey_lb), _p(ey_ub), _p(n_veh), _p(obs_s), _p(obs_ey), _p(old_flag), _p(out["X"]),

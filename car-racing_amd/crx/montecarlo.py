@@ -497,7 +497,7 @@ class GameLaps:
     in; no host round trip, no compaction.  Nine libcrx launches per step."""
 
     def __init__(self, track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0,
-                 lin_points, lin_input, car_s0, car_v, car_ey, N=12, N_plan=10, timestep=0.1, device=None, noise_seed=None):
+                 lin_points, lin_input, car_s0, car_v, car_ey, N=12, N_plan=10, timestep=0.1, device=None, noise_seed=None, models=None):
         self.lm = LmpcLaps(track_table, lap_length, track_width, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
                            N=N, timestep=timestep, device=device, noise_seed=noise_seed)
         lm = self.lm
@@ -509,6 +509,8 @@ class GameLaps:
         VA = self.s0.shape[1]
         V = min(VA, abi.CRX_MAX_VEH)
         self.Np, self.V, self.VA, self.L = N_plan, V, VA, lap_length
+        if models is not None and A is None and B is None:   # (the descriptors' own model is not read then)
+            A, B = np.zeros((6, 6)), np.zeros((6, 2))
         self.scene = abi.scene_desc(N_plan, VA, V, lap_length)
         self.prep = abi.prep_desc(N_plan, V, opt_xcurv.shape[0], track_width, lap_length)
         self.plan, self.sel = abi.planner_desc(N_plan, A, B), abi.select_desc(N_plan, V, lap_length)
@@ -521,6 +523,14 @@ class GameLaps:
         self.qws = torch_api.PlannerWorkspace(self.plan, Bn * (V + 1), dev)
         self.selws = torch_api.SelectWorkspace(self.sel, Bn, dev)
         self.tws = torch_api.CbfWorkspace(self.track_desc, Bn, dev)
+        # models = (A [B,6,6], B [B,6,2]), host arrays or device tensors (PidLaps.identify(): held, not copied): the overtake branch of race b
+        # on ITS model -- its V + 1 region QPs (crx_planner_plan_models_dev) and its tracking NLP (crx_cbf_solve_models_dev); A, B above are
+        # then unused.  Both reach tables are computed here, once.  The learning-MPC branch identifies its own stage models, as before
+        self.plan_models = self.track_models = None
+        if models is not None:
+            mA, mB = _models(models[0], models[1], Bn, dev)
+            self.plan_models = torch_api.PlannerModels(self.plan, mA, mB, regions=V + 1)
+            self.track_models = torch_api.CbfModels(self.track_desc, mA, mB)
         self.xt = torch.empty((Bn, N_plan + 1, 6), **f64)
         self.obs_s, self.obs_e = torch.empty((Bn, V, N_plan + 1), **f64), torch.empty((Bn, V, N_plan + 1), **f64)
         self.lap_off, self.n_obs = torch.empty((Bn, V), **f64), torch.empty((Bn,), **i32)
@@ -587,11 +597,11 @@ class GameLaps:
         torch_api.planner_prep_dev(self.prep, lm.xc, lm.xc, self.sws.n_veh, self.sws.veh_info, self.sws.max_dv, self.sws.obs_s, self.sws.obs_ey,
                                    self.opt_s, self.opt_ey, ws=self.pws)
         torch_api.planner_plan_dev(self.plan, self.sel, self.pws.x0, self.pws.bez_s, self.pws.bez_ey, self.pws.ey_lb, self.pws.ey_ub,
-                                   self.sws.n_veh, self.sws.obs_s, self.sws.obs_ey, self.old_flag, self.qws, self.selws, active=m_ot)
+                                   self.sws.n_veh, self.sws.obs_s, self.sws.obs_ey, self.old_flag, self.qws, self.selws, active=m_ot, models=self.plan_models)
         torch_api.track_prep_dev(self.Np, self.V, L, lm.xc, self.sws.n_veh, self.sws.obs_s, self.sws.obs_ey, self.selws.best_X, self.xt,
                                  self.obs_s, self.obs_e, self.lap_off, self.n_obs)
         torch_api.cbf_solve_dev(self.track_desc, lm.xc, self.xt, self.obs_s, self.obs_e, self.lap_off, self.n_obs, ws=self.tws, active=m_ot,
-                                order=_order(self, self.tws.iters, m_ot))
+                                order=_order(self, self.tws.iters, m_ot), models=self.track_models)
 
     def _branch_lmpc(self, m_lm):
         lm = self.lm
@@ -635,11 +645,12 @@ class GameLaps:
 
 
 def game_laps(track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
-              car_s0, car_v, car_ey, steps, device=None, noise_seed=None):
-    """Run `steps` control steps of B racing-game laps with scripted traffic.  Host logs: xcurv [steps+1, B, 6], u [steps, B, 2],
+              car_s0, car_v, car_ey, steps, device=None, noise_seed=None, models=None):
+    """Run `steps` control steps of B racing-game laps with scripted traffic; models = (A [B,6,6], B [B,6,2]): the overtake branch of
+    every race (region QPs, tracking NLP) on its own model.  Host logs: xcurv [steps+1, B, 6], u [steps, B, 2],
     overtake [steps, B] (which branch), flag [steps, B] (direction flag, -1 in the LMPC branch), cars_s [steps, B, V], laps [B]."""
     r = GameLaps(track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
-                 car_s0, car_v, car_ey, device=device, noise_seed=noise_seed)
+                 car_s0, car_v, car_ey, device=device, noise_seed=noise_seed, models=models)
     lx, lu, lo, lf, lc = [r.lm.xc.clone()], [], [], [], []
     for _ in range(steps):
         lc.append((r.v * r.t + r.s0).clone())

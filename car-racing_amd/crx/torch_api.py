@@ -335,7 +335,44 @@ class PlannerWorkspace:
         self.iters = torch.empty(batch, **i32)
 
 
-def planner_solve_dev(desc, x0, bez_s, bez_ey, ey_lb, ey_ub, ws=None):
+PLANNER_REACH_ROWS = 24   # CRX_MAX_N: stages of a problem's reach table (include/crx.h CRX_PLANNER_MODEL_REACH_DOUBLES)
+
+
+class PlannerModels:
+    """One LTI model per region QP for planner_solve_dev(models=...) / planner_plan_dev(models=...): contiguous device A [n,6,6], B [n,6,2]
+    (e.g. what PidLaps.identify() returns) and the reach table crx_planner_models_reach_dev computes from them -- here, once: it is valid for
+    every solve with desc's N, delta_max, a_max.  regions = V + 1 of a planner step: the n models are one per SCENARIO and every one is
+    repeated for its regions (the C ABI indexes the models like x0, one per region QP); regions = 1 holds A, B as they are, without a copy."""
+
+    def __init__(self, desc, A, B, regions=1):
+        if not (torch.is_tensor(A) and torch.is_tensor(B)) or A.dim() != 3:
+            raise ValueError("PlannerModels: A [n,6,6], B [n,6,2] device tensors expected")
+        n = A.shape[0]
+        _chk(A, torch.float64, (n, 6, 6), "models A")
+        _chk(B, torch.float64, (n, 6, 2), "models B")
+        if int(regions) < 1:
+            raise ValueError("PlannerModels: regions >= 1 expected, got %r" % (regions,))
+        self.regions = int(regions)
+        self.A = A.repeat_interleave(self.regions, dim=0).contiguous() if self.regions > 1 else A
+        self.B = B.repeat_interleave(self.regions, dim=0).contiguous() if self.regions > 1 else B
+        Bn = n * self.regions
+        self.batch, self.N, self.delta_max, self.a_max = Bn, desc.N, desc.delta_max, desc.a_max
+        self.reach = torch.empty((Bn, PLANNER_REACH_ROWS, 7), dtype=torch.float64, device=A.device)
+        _call("crx_planner_models_reach_dev", C.byref(desc), C.c_int(Bn), _ptr(self.A), _ptr(self.B), _ptr(self.reach), _stream())
+
+
+def _planner_models(models, desc, B):
+    if not isinstance(models, PlannerModels):
+        raise ValueError("models: a PlannerModels is expected (PlannerModels(desc, A, B, regions))")
+    if models.batch != B or (models.N, models.delta_max, models.a_max) != (desc.N, desc.delta_max, desc.a_max):
+        raise ValueError("models: built for batch %d, N %d, input box (%g, %g); this solve has batch %d, N %d, (%g, %g)" % (
+            models.batch, models.N, models.delta_max, models.a_max, B, desc.N, desc.delta_max, desc.a_max))
+    return models
+
+
+def planner_solve_dev(desc, x0, bez_s, bez_ey, ey_lb, ey_ub, ws=None, models=None, active=None):
+    """crx_planner_solve_dev.  models (a PlannerModels of this batch, built for a descriptor with the same N, delta_max, a_max) and / or
+    `active` (int32 [batch], 0 = leave the QP alone): crx_planner_solve_models_dev, QP b on its own model (desc.A, desc.B are ignored)."""
     N, B = desc.N, x0.shape[0]
     _chk(x0, torch.float64, (B, 6), "x0")
     _chk(bez_s, torch.float64, (B, N + 1), "bez_s")
@@ -343,6 +380,14 @@ def planner_solve_dev(desc, x0, bez_s, bez_ey, ey_lb, ey_ub, ws=None):
     _chk(ey_lb, torch.float64, (B, N), "ey_lb")
     _chk(ey_ub, torch.float64, (B,), "ey_ub")
     ws = ws or PlannerWorkspace(desc, B, x0.device)
+    if models is not None or active is not None:
+        m = _planner_models(models, desc, B) if models is not None else None
+        if active is not None:
+            _chk(active, torch.int32, (B,), "active")
+        _call("crx_planner_solve_models_dev", C.byref(desc), C.c_int(B), _ptr(active) if active is not None else None, _ptr(x0),
+              _ptr(m.A) if m else None, _ptr(m.B) if m else None, _ptr(m.reach) if m else None, _ptr(bez_s), _ptr(bez_ey), _ptr(ey_lb),
+              _ptr(ey_ub), _ptr(ws.X), _ptr(ws.U), _ptr(ws.cost), _ptr(ws.status), _ptr(ws.kkt), _ptr(ws.iters), _stream())
+        return ws
     _call("crx_planner_solve_dev", C.byref(desc), C.c_int(B), _ptr(x0), _ptr(bez_s), _ptr(bez_ey), _ptr(ey_lb),
           _ptr(ey_ub), _ptr(ws.X), _ptr(ws.U), _ptr(ws.cost), _ptr(ws.status), _ptr(ws.kkt), _ptr(ws.iters),
           _stream())
@@ -585,9 +630,10 @@ def planner_scene_dev(desc, ego_xcurv, n_all, veh_xcurv, pred_s, pred_ey, ws=Non
     return ws
 
 
-def planner_plan_dev(desc, sdesc, x0, bez_s, bez_ey, ey_lb, ey_ub, n_veh, obs_s, obs_ey, old_flag, ws, sws, active=None):
+def planner_plan_dev(desc, sdesc, x0, bez_s, bez_ey, ey_lb, ey_ub, n_veh, obs_s, obs_ey, old_flag, ws, sws, active=None, models=None):
     """crx_planner_plan_dev: all region QPs of every scenario + the selection, on one stream (with `active`, int32
-    [n_scen]: crx_planner_plan_masked_dev, the QPs of the scenarios with 0 are skipped)."""
+    [n_scen]: crx_planner_plan_masked_dev, the QPs of the scenarios with 0 are skipped).  models (a PlannerModels of n_scen models with
+    regions = n_veh_max + 1): crx_planner_plan_models_dev, the region QPs of scenario i on model i (desc.A, desc.B are ignored)."""
     S, N, V = n_veh.shape[0], desc.N, sdesc.n_veh_max
     R = V + 1
     _chk(x0, torch.float64, (S * R, 6), "x0")
@@ -610,6 +656,12 @@ def planner_plan_dev(desc, sdesc, x0, bez_s, bez_ey, ey_lb, ey_ub, n_veh, obs_s,
     _chk(sws.best_X, torch.float64, (S, N + 1, 6), "sws.best_X")
     if active is not None:
         _chk(active, torch.int32, (S,), "active")
+    if models is not None:
+        m = _planner_models(models, desc, S * R)
+        _call("crx_planner_plan_models_dev", C.byref(desc), C.byref(sdesc), C.c_int(S), _ptr(active), _ptr(x0), _ptr(m.A), _ptr(m.B), _ptr(m.reach),
+              _ptr(bez_s), _ptr(bez_ey), _ptr(ey_lb), _ptr(ey_ub), _ptr(n_veh), _ptr(obs_s), _ptr(obs_ey), _ptr(old_flag), _ptr(ws.X), _ptr(ws.U),
+              _ptr(ws.cost), _ptr(ws.status), _ptr(ws.kkt), _ptr(ws.iters), _ptr(sws.flag), _ptr(sws.sel_cost), _ptr(sws.best_X), _stream())
+        return
     _call("crx_planner_plan_masked_dev", C.byref(desc), C.byref(sdesc), C.c_int(S), _ptr(active), _ptr(x0), _ptr(bez_s), _ptr(bez_ey), _ptr(ey_lb), _ptr(ey_ub),
           _ptr(n_veh), _ptr(obs_s), _ptr(obs_ey), _ptr(old_flag), _ptr(ws.X), _ptr(ws.U), _ptr(ws.cost), _ptr(ws.status), _ptr(ws.kkt),
           _ptr(ws.iters), _ptr(sws.flag), _ptr(sws.sel_cost), _ptr(sws.best_X), _stream())

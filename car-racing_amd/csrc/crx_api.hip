@@ -201,7 +201,8 @@ void reach_bound(const double* A, const double* B, double delta_max, double a_ma
     }
 }
 
-int fill_planner(crx_kparams& kp, const crx_planner_desc* d, int batch) {
+// own_model = false: the launch brings one model per problem (crx_planner_solve_models*), d->A and d->B are not read
+int fill_planner(crx_kparams& kp, const crx_planner_desc* d, int batch, bool own_model = true) {
     if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
     if (d->N < 3 || d->N > CRX_MAX_N) return fail(CRX_ERR_ARG, "N=%d outside [3,%d]", d->N, CRX_MAX_N);
     if (batch < 0) return fail(CRX_ERR_ARG, "batch < 0");
@@ -216,7 +217,7 @@ int fill_planner(crx_kparams& kp, const crx_planner_desc* d, int batch) {
     kp.dt_ref = d->dt_ref; kp.fallback_gain = d->fallback_gain; kp.opts = d->opts;
     // reachability screen (crx_kernels.hip, set-up): the reach of ey at stages 0..N-1 and the rows of its free response
     kp.reach_screen = d->opts.reach_screen ? 1 : 0;
-    reach_bound(d->A, d->B, d->delta_max, d->a_max, 5, d->N - 1, kp.reach_gain, kp.reach_row);
+    if (own_model) reach_bound(d->A, d->B, d->delta_max, d->a_max, 5, d->N - 1, kp.reach_gain, kp.reach_row);
     return 0;
 }
 
@@ -484,42 +485,81 @@ static bool planner_null(arr x0, arr bez_s, arr bez_ey, arr ey_lb, arr ey_ub, ar
     return any_null(x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters);
 }
 
-static int check_planner(crx_kparams& kp, const crx_planner_desc* d, int batch, arr x0, arr bez_s, arr bez_ey, arr ey_lb, arr ey_ub, arr X, arr U,
-                         arr cost, arr status, arr kkt, arr iters) {
+// (own_model = false: one model per problem is given, d->A and d->B are not read)
+static int check_planner(crx_kparams& kp, const crx_planner_desc* d, int batch, bool own_model, arr x0, arr bez_s, arr bez_ey, arr ey_lb, arr ey_ub,
+                         arr X, arr U, arr cost, arr status, arr kkt, arr iters) {
     if (int rc = ensure_init()) return rc;
-    if (int rc = fill_planner(kp, d, batch)) return rc;
+    if (int rc = fill_planner(kp, d, batch, own_model)) return rc;
     if (batch > 0 && planner_null(x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters))
         return fail(CRX_ERR_ARG, "NULL array argument");
     return 0;
 }
 
-static int planner_solve_masked(const crx_planner_desc* d, int batch, const int32_t* active, int active_div, const double* x0,
-                                const double* bez_s, const double* bez_ey, const double* ey_lb, const double* ey_ub, double* X,
-                                double* U, double* cost, int32_t* status, double* kkt, int32_t* iters, void* stream);
-
-int crx_planner_solve_dev(const crx_planner_desc* d, int batch, const double* x0, const double* bez_s,
-                          const double* bez_ey, const double* ey_lb, const double* ey_ub, double* X, double* U,
-                          double* cost, int32_t* status, double* kkt, int32_t* iters, void* stream) {
-    return planner_solve_masked(d, batch, nullptr, 0, x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters, stream);
+// the one thing the models entry points refuse on top of check_planner: every model array, or none (n_given of n_all).  Pointers only, so it is
+// looked at before the device is
+static int check_planner_models(int n_given, int n_all) {
+    if (n_given != 0 && n_given != n_all)
+        return fail(CRX_ERR_ARG, n_all == 3 ? "model_A, model_B and model_reach go together: all three or none (%d of 3 given)"
+                                            : "model_A and model_B go together: both or neither (%d of 2 given)", n_given);
+    return 0;
 }
 
+// every planner launch: active_div problems share one entry of active (the regions of a scenario; 0: one each); models all three or none
 static int planner_solve_masked(const crx_planner_desc* d, int batch, const int32_t* active, int active_div, const double* x0,
-                                const double* bez_s, const double* bez_ey, const double* ey_lb, const double* ey_ub, double* X,
-                                double* U, double* cost, int32_t* status, double* kkt, int32_t* iters, void* stream) {
-    crx_kparams kp;
-    if (int rc = check_planner(kp, d, batch, x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters)) return rc;
+                                const double* model_A, const double* model_B, const double* model_reach, const double* bez_s,
+                                const double* bez_ey, const double* ey_lb, const double* ey_ub, double* X, double* U, double* cost,
+                                int32_t* status, double* kkt, int32_t* iters, void* stream) {
+    crx_kparams_models km;
+    crx_kparams& kp = km;
+    if (int rc = check_planner_models((model_A != nullptr) + (model_B != nullptr) + (model_reach != nullptr), 3)) return rc;
+    if (int rc = check_planner(kp, d, batch, !model_A, x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters)) return rc;
     if (batch == 0) return CRX_OK;
     kp.x0 = x0; kp.bez_s = bez_s; kp.bez_ey = bez_ey; kp.ey_lb = ey_lb; kp.ey_ub = ey_ub;
     kp.X = X; kp.U = U; kp.sigma = nullptr; kp.cost = cost; kp.status = status; kp.kkt = kkt; kp.iters = iters;
     kp.active = active; kp.active_div = active_div;
-    return launch_solve(kp, 0, (hipStream_t)stream);
+    km.model_A = model_A; km.model_B = model_B; km.model_reach = model_reach;
+    return launch_solve(kp, 0, (hipStream_t)stream, model_A ? &km : nullptr);
+}
+
+int crx_planner_solve_dev(const crx_planner_desc* d, int batch, const double* x0, const double* bez_s,
+                          const double* bez_ey, const double* ey_lb, const double* ey_ub, double* X, double* U,
+                          double* cost, int32_t* status, double* kkt, int32_t* iters, void* stream) {
+    return crx_planner_solve_models_dev(d, batch, nullptr, x0, nullptr, nullptr, nullptr, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters,
+                                        stream);
+}
+
+int crx_planner_solve_models_dev(const crx_planner_desc* d, int batch, const int32_t* active, const double* x0, const double* model_A,
+                                 const double* model_B, const double* model_reach, const double* bez_s, const double* bez_ey,
+                                 const double* ey_lb, const double* ey_ub, double* X, double* U, double* cost, int32_t* status, double* kkt,
+                                 int32_t* iters, void* stream) {
+    return planner_solve_masked(d, batch, active, 0, x0, model_A, model_B, model_reach, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters,
+                                stream);
+}
+
+int crx_planner_models_reach_dev(const crx_planner_desc* d, int batch, const double* model_A, const double* model_B, double* model_reach,
+                                 void* stream) {
+    if (int rc = ensure_init()) return rc;
+    crx_kparams kp;
+    if (int rc = fill_planner(kp, d, batch, false)) return rc;
+    if (batch == 0) return CRX_OK;
+    if (any_null(model_A, model_B, model_reach)) return fail(CRX_ERR_ARG, "NULL array argument");
+    return launched(crx_launch_planner_reach(d->N, batch, d->delta_max, d->a_max, model_A, model_B, model_reach, (hipStream_t)stream), "planner reach");
 }
 
 int crx_planner_solve(const crx_planner_desc* d, int batch, const double* x0, const double* bez_s,
                       const double* bez_ey, const double* ey_lb, const double* ey_ub, double* X, double* U,
                       double* cost, int32_t* status, double* kkt, int32_t* iters) {
+    return crx_planner_solve_models(d, batch, x0, nullptr, nullptr, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters);
+}
+
+// (non-finite model entries are no argument error: that problem reports CRX_SINGULAR with the fall-back trajectory, as on the device path)
+int crx_planner_solve_models(const crx_planner_desc* d, int batch, const double* x0, const double* model_A, const double* model_B,
+                             const double* bez_s, const double* bez_ey, const double* ey_lb, const double* ey_ub, double* X, double* U,
+                             double* cost, int32_t* status, double* kkt, int32_t* iters) {
     crx_kparams chk;
-    if (int rc = check_planner(chk, d, batch, x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters)) return rc;
+    const bool models = model_A || model_B;
+    if (int rc = check_planner_models((model_A != nullptr) + (model_B != nullptr), 2)) return rc;
+    if (int rc = check_planner(chk, d, batch, !models, x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters)) return rc;
     if (batch == 0) return CRX_OK;
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
@@ -527,11 +567,16 @@ int crx_planner_solve(const crx_planner_desc* d, int batch, const double* x0, co
     Stage sg;
     auto dx0 = sg.in(x0, B * 6); auto dbs = sg.in(bez_s, B * (N + 1)); auto dbe = sg.in(bez_ey, B * (N + 1));
     auto dlb = sg.in(ey_lb, B * N); auto dub = sg.in(ey_ub, B);
+    auto dmA = models ? sg.in(model_A, B * 36) : Stage::Ref<double>{};
+    auto dmB = models ? sg.in(model_B, B * 12) : Stage::Ref<double>{};
+    auto dmR = models ? sg.scratch(CRX_PLANNER_MODEL_REACH_DOUBLES(B) * sizeof(double)) : Stage::Ref<char>{};
     auto dX = sg.out(X, B * (N + 1) * 6); auto dU = sg.out(U, B * N * 2); auto dc = sg.out(cost, B);
     auto dk = sg.out(kkt, B); auto ds = sg.out(status, B); auto di = sg.out(iters, B);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_planner_solve_dev(d, batch, sg[dx0], sg[dbs], sg[dbe], sg[dlb], sg[dub], sg[dX], sg[dU], sg[dc], sg[ds], sg[dk],
-                                       sg[di], g_stream)) return rc;
+    if (models)
+        if (int rc = crx_planner_models_reach_dev(d, batch, sg[dmA], sg[dmB], (double*)sg[dmR], g_stream)) return rc;
+    if (int rc = crx_planner_solve_models_dev(d, batch, nullptr, sg[dx0], sg[dmA], sg[dmB], (double*)sg[dmR], sg[dbs], sg[dbe], sg[dlb], sg[dub],
+                                              sg[dX], sg[dU], sg[dc], sg[ds], sg[dk], sg[di], g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -1476,11 +1521,23 @@ int crx_planner_plan_masked_dev(const crx_planner_desc* d, const crx_select_desc
                                 const double* ey_ub, const int32_t* n_veh, const double* obs_s, const double* obs_ey,
                                 const int32_t* old_flag, double* X, double* U, double* cost, int32_t* status, double* kkt,
                                 int32_t* iters, int32_t* flag, double* sel_cost, double* best_X, void* stream) {
+    return crx_planner_plan_models_dev(d, sd, n_scen, active, x0, nullptr, nullptr, nullptr, bez_s, bez_ey, ey_lb, ey_ub, n_veh, obs_s, obs_ey,
+                                       old_flag, X, U, cost, status, kkt, iters, flag, sel_cost, best_X, stream);
+}
+
+// (the models are the region QPs': one per problem, [n_scen * (n_veh_max + 1)], indexed like x0)
+int crx_planner_plan_models_dev(const crx_planner_desc* d, const crx_select_desc* sd, int n_scen, const int32_t* active,
+                                const double* x0, const double* model_A, const double* model_B, const double* model_reach,
+                                const double* bez_s, const double* bez_ey, const double* ey_lb, const double* ey_ub,
+                                const int32_t* n_veh, const double* obs_s, const double* obs_ey, const int32_t* old_flag, double* X,
+                                double* U, double* cost, int32_t* status, double* kkt, int32_t* iters, int32_t* flag, double* sel_cost,
+                                double* best_X, void* stream) {
     if (int rc = check_plan_descs(d, sd)) return rc;
     if (int rc = check_select(sd, n_scen)) return rc;   // before R = n_veh_max + 1 sizes the QP launch
     const int R = sd->n_veh_max + 1;
     if ((long long)n_scen * R > 0x7fffffffLL) return fail(CRX_ERR_ARG, "n_scen * (n_veh_max + 1) overflows int");
-    if (int rc = planner_solve_masked(d, n_scen * R, active, R, x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters, stream)) return rc;
+    if (int rc = planner_solve_masked(d, n_scen * R, active, R, x0, model_A, model_B, model_reach, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status,
+                                      kkt, iters, stream)) return rc;
     return crx_select_dev(sd, n_scen, n_veh, X, obs_s, obs_ey, old_flag, flag, sel_cost, best_X, stream);
 }
 
@@ -1489,11 +1546,22 @@ int crx_planner_plan(const crx_planner_desc* d, const crx_select_desc* sd, int n
                      const int32_t* n_veh, const double* obs_s, const double* obs_ey, const int32_t* old_flag,
                      double* X, double* U, double* cost, int32_t* status, double* kkt, int32_t* iters,
                      int32_t* flag, double* sel_cost, double* best_X) {
+    return crx_planner_plan_models(d, sd, n_scen, x0, nullptr, nullptr, bez_s, bez_ey, ey_lb, ey_ub, n_veh, obs_s, obs_ey, old_flag, X, U, cost,
+                                   status, kkt, iters, flag, sel_cost, best_X);
+}
+
+int crx_planner_plan_models(const crx_planner_desc* d, const crx_select_desc* sd, int n_scen, const double* x0, const double* model_A,
+                            const double* model_B, const double* bez_s, const double* bez_ey, const double* ey_lb,
+                            const double* ey_ub, const int32_t* n_veh, const double* obs_s, const double* obs_ey,
+                            const int32_t* old_flag, double* X, double* U, double* cost, int32_t* status, double* kkt, int32_t* iters,
+                            int32_t* flag, double* sel_cost, double* best_X) {
     if (int rc = check_plan_descs(d, sd)) return rc;
     if (n_scen < 0) return fail(CRX_ERR_ARG, "n_scen < 0");
+    if (int rc = check_planner_models((model_A != nullptr) + (model_B != nullptr), 2)) return rc;
     if (int rc = ensure_init()) return rc;
     crx_kparams chk;
-    if (int rc = fill_planner(chk, d, 0)) return rc;
+    const bool models = model_A || model_B;
+    if (int rc = fill_planner(chk, d, 0, !models)) return rc;
     if (int rc = check_select(sd, n_scen)) return rc;
     if (n_scen == 0) return CRX_OK;
     if (planner_null(x0, bez_s, bez_ey, ey_lb, ey_ub, X, U, cost, status, kkt, iters) ||
@@ -1510,12 +1578,18 @@ int crx_planner_plan(const crx_planner_desc* d, const crx_select_desc* sd, int n
     auto dlb = sg.in(ey_lb, B * N); auto dub = sg.in(ey_ub, B);
     auto dos = sg.in(obs_s, S * V * (N + 1)); auto doe = sg.in(obs_ey, S * V * (N + 1));
     auto dnv = sg.in(n_veh, S); auto dof = sg.in(old_flag, S);
+    auto dmA = models ? sg.in(model_A, B * 36) : Stage::Ref<double>{};
+    auto dmB = models ? sg.in(model_B, B * 12) : Stage::Ref<double>{};
+    auto dmR = models ? sg.scratch(CRX_PLANNER_MODEL_REACH_DOUBLES(B) * sizeof(double)) : Stage::Ref<char>{};
     auto dX = sg.out(X, B * (N + 1) * 6); auto dU = sg.out(U, B * N * 2); auto dc = sg.out(cost, B); auto dk = sg.out(kkt, B);
     auto ds = sg.out(status, B); auto di = sg.out(iters, B);
     auto dfl = sg.out(flag, S); auto dsc = sg.out(sel_cost, S * R); auto dbX = sg.out(best_X, S * (N + 1) * 6);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_planner_plan_dev(d, sd, n_scen, sg[dx0], sg[dbs], sg[dbe], sg[dlb], sg[dub], sg[dnv], sg[dos], sg[doe], sg[dof], sg[dX],
-                                      sg[dU], sg[dc], sg[ds], sg[dk], sg[di], sg[dfl], sg[dsc], sg[dbX], g_stream)) return rc;
+    if (models)
+        if (int rc = crx_planner_models_reach_dev(d, (int)B, sg[dmA], sg[dmB], (double*)sg[dmR], g_stream)) return rc;
+    if (int rc = crx_planner_plan_models_dev(d, sd, n_scen, nullptr, sg[dx0], sg[dmA], sg[dmB], (double*)sg[dmR], sg[dbs], sg[dbe], sg[dlb], sg[dub],
+                                             sg[dnv], sg[dos], sg[doe], sg[dof], sg[dX], sg[dU], sg[dc], sg[ds], sg[dk], sg[di], sg[dfl], sg[dsc],
+                                             sg[dbX], g_stream)) return rc;
     return sg.down(g_stream);
 }
 

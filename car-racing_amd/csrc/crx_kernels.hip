@@ -47,7 +47,7 @@
 #define CRX_TU_GENERAL 0   /* 1: crx_kernels_gen.hip -- the general instantiations, built conservatively (section (7)) */
 #endif
 #ifndef CRX_TU_MODELS
-#define CRX_TU_MODELS 0    /* 1..3: crx_kernels_models.hip -- the CBF NLP with one LTI model per problem (section (7)) */
+#define CRX_TU_MODELS 0    /* 1..3: crx_kernels_models.hip -- the CBF NLP and the planner QP with one LTI model per problem (section (7)) */
 #endif
 // what crx_solve_kernel takes by value.  The models units read A, B and the reach tables of problem b through the three pointers of the derived
 // struct, in set-up only (the model matrix M, crash_search, the slack bounds); every other unit compiles exactly what it compiled before
@@ -1716,12 +1716,19 @@ crx_solve_kernel(const crx_solve_params kp) {
         return;
     }
     const double *mdl_A = nullptr, *mdl_B = nullptr, *mdl_reach = nullptr;   // this problem's model and reach tables (models units; b is wave-uniform)
+    const double* mdl_plan = nullptr;   // mode 0: model_reach holds the planner's table, [batch][CRX_MAX_N][7] (the reach screen below)
 #if CRX_TU_MODELS
     {
         mdl_A = kp.model_A + (size_t)36 * b; mdl_B = kp.model_B + (size_t)12 * b; mdl_reach = kp.model_reach + (size_t)2 * (CRX_MAX_N + 1) * b;
+        mdl_plan = kp.model_reach + (size_t)CRX_MAX_N * 7 * b;
         // a non-finite model (crx_sysid_fit writes NaN for a failed fit) never enters the iteration: all 48 entries, one ballot, before any set-up
         const double v = lane < 36 ? mdl_A[lane] : (lane < 48 ? mdl_B[lane - 36] : 0.0);
         if (__ballot(!isfinite(v)) != 0ull) {
+            if (NOBS == 0 && kp.mode == 0) {   // planner QP: the reference's failure branch (overtake_traj_planner.py:365-374), which every non-zero status selects
+                planner_fallback<L>(sm, kp, b, lane, N);
+                if (lane == 0) { kp.status[b] = CRX_SINGULAR; kp.kkt[b] = INFINITY; kp.iters[b] = 0; }
+                return;
+            }
             const double nan = __longlong_as_double(0x7ff8000000000000LL);
             for (int e = lane; e < (N + 1) * 6; e += WAVE) kp.X[(size_t)b * (N + 1) * 6 + e] = nan;
             for (int e = lane; e < N * 2; e += WAVE) kp.U[(size_t)b * N * 2 + e] = nan;
@@ -1743,10 +1750,12 @@ crx_solve_kernel(const crx_solve_params kp) {
     if (NOBS == 0 && kp.mode == 0 && kp.reach_screen) {
         bool out = false;
         for (int j = lane; j < N; j += WAVE) {
+            // (models units: stage j of this problem's table [CRX_MAX_N][7] = e_ey' A^j, then reach_gain[j]: crx_planner_reach_kernel)
+            const double* tab = MODELS ? mdl_plan + j * 7 : nullptr;
             double fr = 0.0;
 #pragma unroll
-            for (int i = 0; i < 6; i++) fr += kp.reach_row[j][i] * kp.x0[(size_t)b * 6 + i];
-            const double g = kp.reach_gain[j];
+            for (int i = 0; i < 6; i++) fr += (MODELS ? tab[i] : kp.reach_row[j][i]) * kp.x0[(size_t)b * 6 + i];
+            const double g = MODELS ? tab[6] : kp.reach_gain[j];
             out = out || kp.ey_lb[(size_t)b * N + j] > fr + g + 1e-6 || kp.ey_ub[b] < fr - g - 1e-6;
         }
         if (__ballot(out) != 0ull) {
@@ -2952,7 +2961,9 @@ hipError_t crx_launch_solve_spec(const crx_kparams& kp, hipStream_t st) {
 // crx_kernels_models.hip: the CBF NLP with one LTI model per problem, compiled three times with the flags of the unit whose instantiations it
 // mirrors (Makefile).  1: zero obstacle slots at N = 10 / 12 (the mpc_lti form; the main unit's flags); 2: one slot at N = 10 / 12 and three at
 // N = 20 (the racing shapes; the obstacle unit's flags); 3: every other (N, slots, exponent) the shared launch accepts, on the general
-// instantiations, built as crx_kernels_gen.hip builds them.  A launch walks 1 -> 2 -> 3.  The planner QP and the two-wave kernels have no such twin.
+// instantiations, built as crx_kernels_gen.hip builds them.  A launch walks 1 -> 2 -> 3.  The planner region QP (mode 0, no obstacle slots) runs
+// the same instantiations -- the tuned <0, 12, 0, {10, 12}> of unit 1, any other horizon on unit 3 -- with model_reach holding its own table
+// (crx_planner_reach_kernel).  The two-wave kernels have no such twin.
 hipError_t crx_launch_solve_models_obs(const crx_kparams_models& kp, int nobs_template, hipStream_t st);
 hipError_t crx_launch_solve_models_general(const crx_kparams_models& kp, int nobs_template, hipStream_t st);
 #if CRX_TU_MODELS == 1
@@ -2979,7 +2990,7 @@ static hipError_t next_unit_launch(const crx_kparams_models&, int, hipStream_t) 
 #endif
 hipError_t CRX_UNIT(crx_launch_solve)(const crx_kparams_models& kp, int nobs_template, hipStream_t st) {
     if (kp.batch == 0) return hipSuccess;
-    if (kp.mode != 1) return hipErrorInvalidValue;
+    if (kp.mode != 1 && !(kp.mode == 0 && nobs_template == 0)) return hipErrorInvalidValue;   // the planner QP has no obstacle slots
     hipError_t e = hipSuccess;
     if (select_inst(nobs_template, kp.N, kp.degree, [&](auto i) { e = launch_t<i.nobs, i.nmax, i.deg, i.nfix>(kp, st); })) return e;
     return next_unit_launch(kp, nobs_template, st);

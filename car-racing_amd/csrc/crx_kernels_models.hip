@@ -2,6 +2,8 @@
 // same source as the shared-model instantiations (crx_kernels.hip), whose kernels take the model in crx_kparams.  Here the kernel takes
 // crx_kparams_models and problem b reads A, B from model_A[36 b ..], model_B[12 b ..] and its reach tables from model_reach -- in set-up only:
 // the model matrix M, crash_search (which reads M back) and the slack bounds.  The interior-point loop is the shared kernels' loop.
+// The planner region QP (crx_planner_solve_models*; mode 0, no obstacle slots) runs the same instantiations: its reachability screen reads
+// problem b's table from model_reach, laid out for it by crx_planner_reach_kernel below.
 // Compiled three times (Makefile, -DCRX_MODELS_UNIT=1..3), each time as the unit whose instantiations it mirrors is compiled:
 //   1  zero obstacle slots, N = 10 / 12            the main unit's flags
 //   2  one slot at N = 10 / 12, three at N = 20    the obstacle unit's flags
@@ -54,6 +56,46 @@ hipError_t crx_launch_cbf_reach(int N, int batch, double delta_max, double a_max
                                 hipStream_t st) {
     if (batch == 0) return hipSuccess;
     hipLaunchKernelGGL(crx_cbf_reach_kernel, dim3((2 * batch + 255) / 256), dim3(256), 0, st, N, batch, delta_max, a_max, model_A, model_B, model_reach);
+    return hipGetLastError();
+}
+
+// crx_planner_reach_kernel: the reachability-screen table of the planner region QP for one LTI model per problem (crx_planner_models_reach_dev;
+// here for the reason above).  One thread per problem restates reach_bound(A, B, delta_max, a_max, 5, N - 1, gain, rows) of crx_api.hip, same
+// operations in the same order with contraction off, into model_reach [batch][CRX_MAX_N][7]: stage j holds rows[j] = e_ey' A^j (6 doubles), then
+// gain[j] -- the seven doubles lane j of the solver's screen reads.  Stages j >= N are zero.  A copy of the descriptor's model gives the
+// descriptor's reach_row / reach_gain bit for bit.
+__global__ void __launch_bounds__(256) crx_planner_reach_kernel(int N, int batch, double delta_max, double a_max, const double* model_A,
+                                                                const double* model_B, double* model_reach) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    const double* A = model_A + (size_t)36 * b;
+    const double* B = model_B + (size_t)12 * b;
+    double* tab = model_reach + (size_t)CRX_MAX_N * 7 * b;
+    double w[6] = {0, 0, 0, 0, 0, 1.0}, acc = 0.0;
+#pragma unroll
+    for (int a = 0; a < 6; a++) tab[a] = w[a];
+    tab[6] = 0.0;
+    for (int j = 1; j < N; j++) {
+        double v0 = 0.0, v1 = 0.0, wn[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 6; i++) { v0 += w[i] * B[i * 2]; v1 += w[i] * B[i * 2 + 1]; }
+        acc += fabs(v0) * delta_max + fabs(v1) * a_max;
+#pragma unroll
+        for (int a = 0; a < 6; a++)
+#pragma unroll
+            for (int i = 0; i < 6; i++) wn[a] += w[i] * A[i * 6 + a];
+#pragma unroll
+        for (int a = 0; a < 6; a++) { w[a] = wn[a]; tab[j * 7 + a] = wn[a]; }
+        tab[j * 7 + 6] = acc;
+    }
+    for (int e = N * 7; e < CRX_MAX_N * 7; e++) tab[e] = 0.0;
+}
+
+hipError_t crx_launch_planner_reach(int N, int batch, double delta_max, double a_max, const double* model_A, const double* model_B,
+                                    double* model_reach, hipStream_t st) {
+    if (batch == 0) return hipSuccess;
+    hipLaunchKernelGGL(crx_planner_reach_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, N, batch, delta_max, a_max, model_A, model_B, model_reach);
     return hipGetLastError();
 }
 #endif

@@ -44,12 +44,15 @@ struct crx_kparams {
     double reach_s[CRX_MAX_N + 1];
 };
 
-// crx_solve_kernel with ONE LTI model per problem (crx_kernels_models.hip; the CBF NLP only).  Derived, so that crx_kparams -- which every solver
-// kernel takes by value -- keeps its size and the shared-model code objects stay what they are; the helpers keep taking const crx_kparams&.
-// A, B, reach_s and reach_gain of the base are not read by these kernels.
+// crx_solve_kernel with ONE LTI model per problem (crx_kernels_models.hip; the CBF NLP, and the planner QP without obstacle slots).  Derived, so
+// that crx_kparams -- which every solver kernel takes by value -- keeps its size and the shared-model code objects stay what they are; the helpers
+// keep taking const crx_kparams&.  A, B, reach_s, reach_gain and reach_row of the base are not read by these kernels.
 struct crx_kparams_models : crx_kparams {
     const double *model_A, *model_B;   // [batch][36], [batch][12]
-    const double* model_reach;         // [batch][2][CRX_MAX_N + 1]: reach_s, reach_gain of each problem's model (crx_cbf_reach_kernel)
+    // mode says which layout model_reach holds (no second pointer):
+    //   1 (CBF NLP)     [batch][2][CRX_MAX_N + 1]: reach_s, reach_gain of each problem's model (crx_cbf_reach_kernel)
+    //   0 (planner QP)  [batch][CRX_MAX_N][7]: stage j = e_ey' A^j (6), then reach_gain[j] (crx_planner_reach_kernel)
+    const double* model_reach;
 };
 
 struct crx_lmpc_kparams {
@@ -147,6 +150,7 @@ struct crx_lmpcprep_kparams {
 hipError_t crx_launch_solve(const crx_kparams& kp, int nobs_template, hipStream_t st);
 hipError_t crx_launch_solve_models(const crx_kparams_models& kp, int nobs_template, hipStream_t st);   // crx_kernels_models.hip: plan -> obs -> general unit
 hipError_t crx_launch_cbf_reach(int N, int batch, double delta_max, double a_max, const double* model_A, const double* model_B, double* model_reach, hipStream_t st);
+hipError_t crx_launch_planner_reach(int N, int batch, double delta_max, double a_max, const double* model_A, const double* model_B, double* model_reach, hipStream_t st);
 hipError_t crx_launch_solve_spec(const crx_kparams& kp, hipStream_t st);   // crx_kernels_spec.hip: the two-wave instantiations <1, 12, 6, {12, 10}, 1>
 hipError_t crx_launch_select(const crx_select_kparams& sp, hipStream_t st);
 hipError_t crx_launch_debug_reduce(const double* in, double* out, hipStream_t st);

@@ -44,7 +44,9 @@
 extern "C" {
 #endif
 
-#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_cbf_models_reach_dev, crx_cbf_solve_models, crx_cbf_solve_models_dev,
+#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_planner_models_reach_dev, crx_planner_solve_models, crx_planner_solve_models_dev,
+                          crx_planner_plan_models, crx_planner_plan_models_dev, CRX_PLANNER_MODEL_REACH_DOUBLES -- new entry points only.
+                          0.4.0 (additive, same number): crx_cbf_models_reach_dev, crx_cbf_solve_models, crx_cbf_solve_models_dev,
                           CRX_CBF_MODEL_REACH_DOUBLES; CRX_SINGULAR also from these -- new entry points only.
                           0.4.0 (additive, same number): crx_lqr_desc, crx_lqr_desc_default, crx_lqr_design, crx_lqr_design_dev, crx_lqr_step_dev,
                           crx_ilqr_solve_models, crx_ilqr_solve_models_dev; CRX_SINGULAR also from crx_lqr_design -- new entry points only.
@@ -523,6 +525,45 @@ int crx_planner_plan_masked_dev(const crx_planner_desc* d, const crx_select_desc
                                 const double* ey_ub, const int32_t* n_veh, const double* obs_s, const double* obs_ey,
                                 const int32_t* old_flag, double* X, double* U, double* cost, int32_t* status, double* kkt,
                                 int32_t* iters, int32_t* flag, double* sel_cost, double* best_X, void* stream);
+/* One LTI model per region QP (a fleet of identified cars in the racing game: crx_sysid_fit leaves the models on the device).  Problem b is
+ * solved with model_A [b][6][6], model_B [b][6][2] -- indexed exactly like x0, so a planner step brings n_scen * (V + 1) models, each scenario's
+ * repeated for its V + 1 regions (there is no divisor: the caller expands once, 48 doubles per region).  d->A, d->B are not read.  Besides the
+ * model the reachability screen needs, per problem, the free-response rows and input reach of ey at stages 0 .. N - 1 (what the library computes
+ * on the host for the descriptor's model): model_reach, CRX_PLANNER_MODEL_REACH_DOUBLES(batch) doubles owned by the caller,
+ * [batch][CRX_MAX_N][7] = (e_ey' A^j (6), reach_gain[j]), zero for j >= N, filled by crx_planner_models_reach_dev.  It depends on the models
+ * and on d's N, delta_max, a_max only: a closed loop computes it once.  For copies of d's model it equals the descriptor's table bit for bit,
+ * and the solve then equals the shared launch bit for bit at N = 10 / 12 (tuned kernels on both sides); every other horizon runs the general
+ * (run-time horizon) kernel with models, also at N = 20 where the shared launch has a tuned one: same KKT point to solver tolerance.
+ *   crx_planner_models_reach_dev   the table, one launch.
+ *   crx_planner_solve_models_dev   = crx_planner_solve_dev + active ([batch], 0 = CRX_SKIPPED, outputs untouched; or NULL) and (model_A, model_B,
+ *                                  model_reach) after x0.  All three NULL: the shared launch; any other mix of NULLs is CRX_ERR_ARG.
+ *   crx_planner_solve_models       host pointers (model_A, model_B both or neither); stages them and computes the table itself.
+ *   crx_planner_plan_models_dev    = crx_planner_plan_masked_dev + the three arrays after x0, leading dimension n_scen * (V + 1).
+ *   crx_planner_plan_models        host pointers, as crx_planner_solve_models.
+ * A problem whose model has a non-finite entry (a failed fit) is not iterated and is not an argument error: it answers as every failed region
+ * QP does (overtake_traj_planner.py:365-374) -- X the fall-back trajectory, U 0, cost +inf -- with status CRX_SINGULAR, iters 0, kkt inf, so the
+ * selection treats it like an infeasible region. */
+#define CRX_PLANNER_MODEL_REACH_DOUBLES(batch) ((size_t)(batch) * CRX_MAX_N * 7)
+int crx_planner_models_reach_dev(const crx_planner_desc* d, int batch, const double* model_A, const double* model_B, double* model_reach,
+                                 void* stream);
+int crx_planner_solve_models_dev(const crx_planner_desc* d, int batch, const int32_t* active, const double* x0, const double* model_A,
+                                 const double* model_B, const double* model_reach, const double* bez_s, const double* bez_ey,
+                                 const double* ey_lb, const double* ey_ub, double* X, double* U, double* cost, int32_t* status, double* kkt,
+                                 int32_t* iters, void* stream);
+int crx_planner_solve_models(const crx_planner_desc* d, int batch, const double* x0, const double* model_A, const double* model_B,
+                             const double* bez_s, const double* bez_ey, const double* ey_lb, const double* ey_ub, double* X, double* U,
+                             double* cost, int32_t* status, double* kkt, int32_t* iters);
+int crx_planner_plan_models_dev(const crx_planner_desc* d, const crx_select_desc* sd, int n_scen, const int32_t* active,
+                                const double* x0, const double* model_A, const double* model_B, const double* model_reach,
+                                const double* bez_s, const double* bez_ey, const double* ey_lb, const double* ey_ub,
+                                const int32_t* n_veh, const double* obs_s, const double* obs_ey, const int32_t* old_flag, double* X,
+                                double* U, double* cost, int32_t* status, double* kkt, int32_t* iters, int32_t* flag, double* sel_cost,
+                                double* best_X, void* stream);
+int crx_planner_plan_models(const crx_planner_desc* d, const crx_select_desc* sd, int n_scen, const double* x0, const double* model_A,
+                            const double* model_B, const double* bez_s, const double* bez_ey, const double* ey_lb,
+                            const double* ey_ub, const int32_t* n_veh, const double* obs_s, const double* obs_ey,
+                            const int32_t* old_flag, double* X, double* U, double* cost, int32_t* status, double* kkt, int32_t* iters,
+                            int32_t* flag, double* sel_cost, double* best_X);
 
 /*
  * Planner host prep on the device: per scenario, the cubic Bezier reference of
@@ -812,7 +853,8 @@ int crx_cbf_solve_ordered_dev(const crx_cbf_desc* d, int batch, const int32_t* a
  *                                any other mix of NULLs is CRX_ERR_ARG.  Every (N, n_obs_max, degree, per_stage_target) of the shared launch.
  *   crx_cbf_solve_models       host pointers (model_A, model_B both or neither); stages them and computes the table itself.
  * A problem whose model has a non-finite entry (a failed fit) is not iterated: status CRX_SINGULAR, iters 0, kkt inf, X / U / sigma / cost NaN
- * -- on both paths; it is not an argument error.  The planner QP and the two-wave diagnostics kernel stay single-model. */
+ * -- on both paths; it is not an argument error.  The planner region QP takes per-problem models through crx_planner_solve_models* /
+ * crx_planner_plan_models*; the two-wave diagnostics kernel stays single-model. */
 #define CRX_CBF_MODEL_REACH_DOUBLES(batch) ((size_t)(batch) * 2 * (CRX_MAX_N + 1))
 int crx_cbf_models_reach_dev(const crx_cbf_desc* d, int batch, const double* model_A, const double* model_B, double* model_reach, void* stream);
 int crx_cbf_solve_models_dev(const crx_cbf_desc* d, int batch, const int32_t* active, const int32_t* order, const double* x0,

@@ -99,5 +99,15 @@ def path_solve(desc, opt, bez, lb, ub, e0, eN):
     return binding().path_solve(desc, opt, bez, lb, ub, e0, eN)
 
 
+def path_prep(desc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey):
+    """Path-planner prep (include/crx.h P1-P6) on host arrays: see abi.Binding.path_prep."""
+    return binding().path_prep(desc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey)
+
+
+def path_plan(desc, qdesc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey, opt_vx, active=None, target=None):
+    """One path-planner step (include/crx.h P1-P8) on host arrays: see abi.Binding.path_plan."""
+    return binding().path_plan(desc, qdesc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey, opt_vx, active, target)
+
+
 def plant_step(desc, track, xglob, xcurv, u):
     return binding().plant_step(desc, track, xglob, xcurv, u)

@@ -15,6 +15,7 @@ CRX_MAX_VEH = 6     # vehicles of interest per planner scenario (= CRX_MAX_OBS)
 
 CRX_CONVERGED, CRX_MAX_ITER, CRX_INFEASIBLE, CRX_RESTORED, CRX_SKIPPED, CRX_STALLED = 0, 1, 2, 3, 4, 5
 CRX_SINGULAR = 6    # crx_sysid_fit, crx_lqr_design
+CRX_OUT_OF_DOMAIN = 7   # crx_path_plan's plan_status: a look-up above the optimal-trajectory table (the reference raises) or a non-finite input
 
 
 class IpmOpts(C.Structure):
@@ -204,6 +205,21 @@ class PathDesc(C.Structure):
     _fields_ = [("N", C.c_int32), ("reserved0", C.c_int32), ("alpha", C.c_double), ("w_rate", C.c_double), ("opts", IpmOpts)]
 
 
+class PathPrepDesc(C.Structure):
+    _fields_ = [("N", C.c_int32), ("n_veh_max", C.c_int32), ("n_opt", C.c_int32), ("n_all_max", C.c_int32),
+                ("safety_factor", C.c_double), ("prediction_factor", C.c_double), ("lookahead", C.c_double), ("next_lap_range", C.c_double),
+                ("track_width", C.c_double), ("lap_length", C.c_double), ("veh_length", C.c_double), ("veh_width", C.c_double),
+                ("a_max_plan", C.c_double)]
+
+
+def pathprep_desc(N, n_veh_max, n_all_max, n_opt, track_width, lap_length, safety_factor=4.5, prediction_factor=0.5, veh_length=0.4,
+                  veh_width=0.2):
+    """RacingGameParam.safety_factor / planning_prediction_factor, CarParam (utils/base.py:379-408, :700) and the literals of
+    planner_helper.py:51-53, :178 and overtake_path_planner.py:140 (include/crx.h crx_pathprep_desc)."""
+    return PathPrepDesc(int(N), int(n_veh_max), int(n_opt), int(n_all_max), safety_factor, prediction_factor, 4.0, 20.0, float(track_width),
+                        float(lap_length), veh_length, veh_width, 1.5)
+
+
 class PlantDesc(C.Structure):
     _fields_ = [
         ("n_sub", C.c_int32),
@@ -375,7 +391,7 @@ class Binding:
         self.lib, self.prefix = lib, prefix
         for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve", "ilqr_solve",
                      "ilqr_solve_models", "lqr_design", "sysid_fit", "cbf_solve_models", "planner_solve_models", "planner_plan",
-                     "planner_plan_models"):
+                     "planner_plan_models", "path_prep", "path_plan"):
             if hasattr(lib, prefix + name):
                 getattr(lib, prefix + name).restype = C.c_int
         self._check = None
@@ -672,4 +688,39 @@ class Binding:
                    iters=np.zeros(Bn, dtype=_I))
         self._call("path_solve", C.byref(desc), C.c_int(Bn), _p(opt), _p(bez), _p(lb), _p(ub), _p(e0), _p(eN), _p(out["E"]),
                    _p(out["cost"]), _p(out["status"]), _p(out["kkt"]), _p(out["iters"]))
+        return out
+
+    def _path_inputs(self, desc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey):
+        N, V, VA, T = desc.N, desc.n_veh_max, desc.n_all_max, desc.n_opt
+        n_veh = np.ascontiguousarray(n_veh, dtype=_I)
+        S = n_veh.shape[0]
+        return S, (_in(x_wrapped, _D, (S, 6)), _in(x_raw, _D, (S, 6)), n_veh, _in(order, _I, (S, V)), _in(veh_xcurv, _D, (S, VA, 6)),
+                   _in(max_dv, _D, (S,)), _in(obs_ey, _D, (S, V, N + 1)), _in(opt_s, _D, (T,)), _in(opt_ey, _D, (T,)))
+
+    def path_prep(self, desc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey):
+        """crx_path_prep (include/crx.h P1-P6): from the outputs of planner_scene to the arrays of path_solve, every region of every
+        scenario.  Returns opt, bez, lb, ub (S*(V+1), N+1), e0, eN (S*(V+1),), span (S,); a scenario without vehicles keeps the NaN the
+        arrays are created with."""
+        S, ins = self._path_inputs(desc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey)
+        Bn, N1 = S * (desc.n_veh_max + 1), desc.N + 1
+        out = dict(opt=np.full((Bn, N1), np.nan), bez=np.full((Bn, N1), np.nan), lb=np.full((Bn, N1), np.nan), ub=np.full((Bn, N1), np.nan),
+                   e0=np.full(Bn, np.nan), eN=np.full(Bn, np.nan), span=np.full(S, np.nan))
+        self._call("path_prep", C.byref(desc), C.c_int(S), *[_p(a) for a in ins], *[_p(out[k]) for k in ("opt", "bez", "lb", "ub", "e0", "eN", "span")])
+        return out
+
+    def path_plan(self, desc, qdesc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey, opt_vx, active=None, target=None):
+        """crx_path_plan (include/crx.h P1-P8): prep, the region QPs and the selection with its target trajectory.  active (S,) int32 or
+        None; target (S, N+1, 6): what the skipped scenarios keep (default NaN).  Returns E (S*(V+1), N+1), cost, status, kkt, iters
+        (S*(V+1),), flag (S,), target (S, N+1, 6), plan_status (S,)."""
+        S, ins = self._path_inputs(desc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey)
+        Bn, N1 = S * (desc.n_veh_max + 1), desc.N + 1
+        opt_vx = _in(opt_vx, _D, (desc.n_opt,))
+        if active is not None:
+            active = _in(active, _I, (S,))
+        out = dict(E=np.full((Bn, N1), np.nan), cost=np.zeros(Bn), status=np.zeros(Bn, dtype=_I), kkt=np.full(Bn, np.nan),
+                   iters=np.zeros(Bn, dtype=_I), flag=np.zeros(S, dtype=_I),
+                   target=np.full((S, N1, 6), np.nan) if target is None else _in(target, _D, (S, N1, 6)).copy(),
+                   plan_status=np.zeros(S, dtype=_I))
+        self._call("path_plan", C.byref(desc), C.byref(qdesc), C.c_int(S), _p(active) if active is not None else None, *[_p(a) for a in ins],
+                   _p(opt_vx), *[_p(out[k]) for k in ("E", "cost", "status", "kkt", "iters", "flag", "target", "plan_status")])
         return out

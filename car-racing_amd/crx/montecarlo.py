@@ -494,10 +494,22 @@ class GameLaps:
     MASKED launches (crx_*_masked_dev): the wavefront of a race that is in the other branch returns at once -- the region
     QPs of the planner included; the cheap kernels around them (scene, prep, selection, tracking prep) run for every race.  The applied input, the
     plan hand-over (u_old, linearisation points), add_point and the direction flag are taken from the branch the race is
-    in; no host round trip, no compaction.  Nine libcrx launches per step."""
+    in; no host round trip, no compaction.  Nine libcrx launches per step.
+
+    planner = "path" (LMPCRacingGame(path_planner=True), planning/overtake_path_planner.py): the overtake branch becomes
+        crx_path_plan_dev          obstacle rows, control points, samples, side rows; the region QPs; arg-min + target (include/crx.h P1-P8)
+        crx_track_prep_dev         on the path planner's target trajectory
+        crx_cbf_solve_dev          the tracking NLP
+    with the scene, the masks, the commit (which takes the path planner's flag) and the learning-MPC branch as they are.  alpha =
+    racing_game_param.alpha, the weight of the Bezier reference in the path QPs.  models = only the tracking NLP has dynamics here.
+    planner = "traj" (default) is the loop above, call for call."""
 
     def __init__(self, track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0,
-                 lin_points, lin_input, car_s0, car_v, car_ey, N=12, N_plan=10, timestep=0.1, device=None, noise_seed=None, models=None):
+                 lin_points, lin_input, car_s0, car_v, car_ey, N=12, N_plan=10, timestep=0.1, device=None, noise_seed=None, models=None,
+                 planner="traj", alpha=0.98):
+        if planner not in ("traj", "path"):
+            raise ValueError("planner must be 'traj' or 'path', got %r" % (planner,))
+        self.planner = planner
         self.lm = LmpcLaps(track_table, lap_length, track_width, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
                            N=N, timestep=timestep, device=device, noise_seed=noise_seed)
         lm = self.lm
@@ -523,13 +535,23 @@ class GameLaps:
         self.qws = torch_api.PlannerWorkspace(self.plan, Bn * (V + 1), dev)
         self.selws = torch_api.SelectWorkspace(self.sel, Bn, dev)
         self.tws = torch_api.CbfWorkspace(self.track_desc, Bn, dev)
+        self.flag = self.selws.flag    # the direction flag the commit takes: the trajectory planner's selection, or the path planner's
+        if planner == "path":          # LMPCRacingGame(path_planner=True): alpha = racing_game_param.alpha (utils/base.py:379-408)
+            self.pathprep = abi.pathprep_desc(N_plan, V, VA, opt_xcurv.shape[0], track_width, lap_length)
+            self.pathqp = abi.path_desc(N_plan, alpha)
+            self.opt_vx = torch.as_tensor(np.ascontiguousarray(opt_xcurv[:, 0]), **f64)
+            self.ppws = torch_api.PathPlanWorkspace(self.pathprep, Bn, dev)
+            self.ppws.target.zero_()   # (a race that has never planned: its rows are read by the tracking prep, whose NLP is masked out)
+            self.flag = self.ppws.flag
         # models = (A [B,6,6], B [B,6,2]), host arrays or device tensors (PidLaps.identify(): held, not copied): the overtake branch of race b
         # on ITS model -- its V + 1 region QPs (crx_planner_plan_models_dev) and its tracking NLP (crx_cbf_solve_models_dev); A, B above are
-        # then unused.  Both reach tables are computed here, once.  The learning-MPC branch identifies its own stage models, as before
+        # then unused.  Both reach tables are computed here, once.  The learning-MPC branch identifies its own stage models, as before.
+        # planner="path": only the tracking NLP has dynamics (the path QPs are geometric)
         self.plan_models = self.track_models = None
         if models is not None:
             mA, mB = _models(models[0], models[1], Bn, dev)
-            self.plan_models = torch_api.PlannerModels(self.plan, mA, mB, regions=V + 1)
+            if planner == "traj":
+                self.plan_models = torch_api.PlannerModels(self.plan, mA, mB, regions=V + 1)
             self.track_models = torch_api.CbfModels(self.track_desc, mA, mB)
         self.xt = torch.empty((Bn, N_plan + 1, 6), **f64)
         self.obs_s, self.obs_e = torch.empty((Bn, V, N_plan + 1), **f64), torch.empty((Bn, V, N_plan + 1), **f64)
@@ -560,7 +582,7 @@ class GameLaps:
         torch_api.game_masks_dev(self.sws.n_veh, self.m_ot, self.m_lm, overflow=self.sws.overflow, overflow_seen=self.overflow_seen)
         self.overtake = self.m_ot                                  # int32 mask; bool(overtake[b]) = race b is in the overtake branch
         self._branches(self.m_ot, self.m_lm, overlap=self.overlap)
-        torch_api.game_commit_dev(N, self.Np, self.m_ot, self.tws.U, lm.ws.X, lm.ws.U, self.selws.flag, self.u, lm.u_old, lm.u_prev,
+        torch_api.game_commit_dev(N, self.Np, self.m_ot, self.tws.U, lm.ws.X, lm.ws.U, self.flag, self.u, lm.u_old, lm.u_prev,
                                   self.lin_points, self.lin_input, lm.step_no, lm.addpoint_step, self.old_flag)
         torch_api.lmpc_addpoint_dev(lm.pdesc, lm.ss, lm.us, lm.time_ss, lm.it, lm.addpoint_step, lm.xc, self.u, 2)
         torch_api.plant_step_wrap_dev(lm.plant, lm.tab, lm.xg, lm.xc, self.u, 2, lm.xg_next, lm.xc_next, lm.laps, noise_z=lm.noise.draw(lm.batch))
@@ -594,6 +616,15 @@ class GameLaps:
 
     def _branch_overtake(self, m_ot):
         lm, L = self.lm, self.L
+        if self.planner == "path":   # scene -> path plan (prep, region QPs, selection + target) -> tracking prep on the target -> tracking NLP
+            sw, pw = self.sws, self.ppws
+            torch_api.path_plan_dev(self.pathprep, self.pathqp, lm.xc, lm.xc, sw.n_veh, sw.order, self.veh, sw.max_dv, sw.obs_ey, self.opt_s,
+                                    self.opt_ey, self.opt_vx, ws=pw, active=m_ot)
+            torch_api.track_prep_dev(self.Np, self.V, L, lm.xc, sw.n_veh, sw.obs_s, sw.obs_ey, pw.target, self.xt, self.obs_s, self.obs_e,
+                                     self.lap_off, self.n_obs)
+            torch_api.cbf_solve_dev(self.track_desc, lm.xc, self.xt, self.obs_s, self.obs_e, self.lap_off, self.n_obs, ws=self.tws, active=m_ot,
+                                    order=_order(self, self.tws.iters, m_ot), models=self.track_models)
+            return
         torch_api.planner_prep_dev(self.prep, lm.xc, lm.xc, self.sws.n_veh, self.sws.veh_info, self.sws.max_dv, self.sws.obs_s, self.sws.obs_ey,
                                    self.opt_s, self.opt_ey, ws=self.pws)
         torch_api.planner_plan_dev(self.plan, self.sel, self.pws.x0, self.pws.bez_s, self.pws.bez_ey, self.pws.ey_lb, self.pws.ey_ub,
@@ -636,7 +667,7 @@ class GameLaps:
         self.lin_points.copy_(torch.where(ot[:, None, None], self.lin_points, torch.cat((X[:, 1:], X[:, -1:]), dim=1)))
         self.lin_input.copy_(torch.where(ot[:, None, None], self.lin_input, torch.cat((U[:, 1:], U[:, -1:]), dim=1)))
         lm.step_no += (~ot).to(torch.int32)
-        self.old_flag.copy_(torch.where(ot, self.selws.flag, torch.full_like(self.old_flag, -1)))
+        self.old_flag.copy_(torch.where(ot, self.flag, torch.full_like(self.old_flag, -1)))
         torch_api.plant_step_wrap_dev(lm.plant, lm.tab, lm.xg, lm.xc, self.u, 2, lm.xg_next, lm.xc_next, lm.laps, noise_z=lm.noise.draw(lm.batch))
         lm.xg, lm.xg_next = lm.xg_next, lm.xg
         lm.xc, lm.xc_next = lm.xc_next, lm.xc
@@ -645,12 +676,12 @@ class GameLaps:
 
 
 def game_laps(track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
-              car_s0, car_v, car_ey, steps, device=None, noise_seed=None, models=None):
+              car_s0, car_v, car_ey, steps, device=None, noise_seed=None, models=None, planner="traj", alpha=0.98):
     """Run `steps` control steps of B racing-game laps with scripted traffic; models = (A [B,6,6], B [B,6,2]): the overtake branch of
-    every race (region QPs, tracking NLP) on its own model.  Host logs: xcurv [steps+1, B, 6], u [steps, B, 2],
+    every race (region QPs, tracking NLP) on its own model.  planner = "path": the overtake path planner (GameLaps) in that branch.  Host logs: xcurv [steps+1, B, 6], u [steps, B, 2],
     overtake [steps, B] (which branch), flag [steps, B] (direction flag, -1 in the LMPC branch), cars_s [steps, B, V], laps [B]."""
     r = GameLaps(track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
-                 car_s0, car_v, car_ey, device=device, noise_seed=noise_seed, models=models)
+                 car_s0, car_v, car_ey, device=device, noise_seed=noise_seed, models=models, planner=planner, alpha=alpha)
     lx, lu, lo, lf, lc = [r.lm.xc.clone()], [], [], [], []
     for _ in range(steps):
         lc.append((r.v * r.t + r.s0).clone())

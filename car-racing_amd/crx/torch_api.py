@@ -667,6 +667,90 @@ def planner_plan_dev(desc, sdesc, x0, bez_s, bez_ey, ey_lb, ey_ub, n_veh, obs_s,
           _ptr(ws.iters), _ptr(sws.flag), _ptr(sws.sel_cost), _ptr(sws.best_X), _stream())
 
 
+class PathPlanWorkspace:
+    """Outputs of path_prep_dev (opt .. span: the inputs of the path QPs, same layout) and of path_plan_dev (the rest).  E, kkt and target
+    are what a skipped scenario leaves untouched: they start as NaN."""
+
+    def __init__(self, desc, n_scen, device):
+        N1, Bn = desc.N + 1, n_scen * (desc.n_veh_max + 1)
+        f64 = dict(dtype=torch.float64, device=device)
+        i32 = dict(dtype=torch.int32, device=device)
+        self.opt, self.bez, self.lb, self.ub = (torch.empty((Bn, N1), **f64) for _ in range(4))
+        self.e0, self.eN, self.span = torch.empty(Bn, **f64), torch.empty(Bn, **f64), torch.empty(n_scen, **f64)
+        self.qp_active = torch.empty(Bn, **i32)
+        self.E = torch.full((Bn, N1), float("nan"), **f64)
+        self.cost, self.kkt = torch.empty(Bn, **f64), torch.full((Bn,), float("nan"), **f64)
+        self.status, self.iters = torch.empty(Bn, **i32), torch.empty(Bn, **i32)
+        self.flag, self.plan_status = torch.empty(n_scen, **i32), torch.empty(n_scen, **i32)
+        self.target = torch.full((n_scen, N1, 6), float("nan"), **f64)
+
+
+def _path_inputs(desc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey):
+    N, V, VA, T, S = desc.N, desc.n_veh_max, desc.n_all_max, desc.n_opt, x_wrapped.shape[0]
+    _chk(x_wrapped, torch.float64, (S, 6), "x_wrapped")
+    _chk(x_raw, torch.float64, (S, 6), "x_raw")
+    _chk(n_veh, torch.int32, (S,), "n_veh")
+    _chk(order, torch.int32, (S, V), "order")
+    _chk(veh_xcurv, torch.float64, (S, VA, 6), "veh_xcurv")
+    _chk(max_dv, torch.float64, (S,), "max_dv")
+    _chk(obs_ey, torch.float64, (S, V, N + 1), "obs_ey")
+    _chk(opt_s, torch.float64, (T,), "opt_s")
+    _chk(opt_ey, torch.float64, (T,), "opt_ey")
+    return S, [_ptr(a) for a in (x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey)]
+
+
+def _path_ws(ws, desc, S, device):
+    ws = ws or PathPlanWorkspace(desc, S, device)
+    N1, Bn = desc.N + 1, S * (desc.n_veh_max + 1)
+    for name in ("opt", "bez", "lb", "ub", "E"):
+        _chk(getattr(ws, name), torch.float64, (Bn, N1), "ws." + name)
+    for name in ("e0", "eN", "cost", "kkt"):
+        _chk(getattr(ws, name), torch.float64, (Bn,), "ws." + name)
+    for name in ("qp_active", "status", "iters"):
+        _chk(getattr(ws, name), torch.int32, (Bn,), "ws." + name)
+    _chk(ws.span, torch.float64, (S,), "ws.span")
+    _chk(ws.flag, torch.int32, (S,), "ws.flag")
+    _chk(ws.plan_status, torch.int32, (S,), "ws.plan_status")
+    _chk(ws.target, torch.float64, (S, N1, 6), "ws.target")
+    return ws
+
+
+def path_prep_dev(desc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey, ws=None):
+    """crx_path_prep_dev (include/crx.h P1-P6): from the outputs of planner_scene_dev to ws.opt .. ws.span, the inputs of path_solve's
+    QPs for every region of every scenario.  A scenario without vehicles keeps what the workspace held."""
+    S, ins = _path_inputs(desc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey)
+    ws = _path_ws(ws, desc, S, x_wrapped.device)
+    _call("crx_path_prep_dev", C.byref(desc), C.c_int(S), *ins, _ptr(ws.opt), _ptr(ws.bez), _ptr(ws.lb), _ptr(ws.ub), _ptr(ws.e0), _ptr(ws.eN),
+          _ptr(ws.span), _stream())
+    return ws
+
+
+def path_solve_dev(qdesc, ws):
+    """crx_path_solve_dev on a PathPlanWorkspace: EVERY region QP of ws.opt .. ws.eN (path_prep_dev's outputs) into ws.E, ws.cost,
+    ws.status, ws.kkt, ws.iters -- the unmasked launch the fused step's middle stage is compared with."""
+    Bn, N1 = ws.opt.shape
+    if qdesc.N + 1 != N1:
+        raise ValueError("path_solve_dev: the workspace was made for N = %d, the descriptor says %d" % (N1 - 1, qdesc.N))
+    _call("crx_path_solve_dev", C.byref(qdesc), C.c_int(Bn), _ptr(ws.opt), _ptr(ws.bez), _ptr(ws.lb), _ptr(ws.ub), _ptr(ws.e0), _ptr(ws.eN),
+          _ptr(ws.E), _ptr(ws.cost), _ptr(ws.status), _ptr(ws.kkt), _ptr(ws.iters), _stream())
+    return ws
+
+
+def path_plan_dev(desc, qdesc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey, opt_vx, ws=None, active=None):
+    """crx_path_plan_dev (include/crx.h P1-P8): prep, the region QPs and the selection with its target, three launches on the current
+    stream.  active int32 [n_scen]: scenarios with 0 -- and those without vehicles -- are not planned (regions CRX_SKIPPED with cost inf,
+    ws.flag -1, ws.plan_status CRX_SKIPPED, ws.target untouched)."""
+    S, ins = _path_inputs(desc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey)
+    _chk(opt_vx, torch.float64, (desc.n_opt,), "opt_vx")
+    if active is not None:
+        _chk(active, torch.int32, (S,), "active")
+    ws = _path_ws(ws, desc, S, x_wrapped.device)
+    _call("crx_path_plan_dev", C.byref(desc), C.byref(qdesc), C.c_int(S), _ptr(active), *ins, _ptr(opt_vx), _ptr(ws.opt), _ptr(ws.bez), _ptr(ws.lb),
+          _ptr(ws.ub), _ptr(ws.e0), _ptr(ws.eN), _ptr(ws.span), _ptr(ws.qp_active), _ptr(ws.E), _ptr(ws.cost), _ptr(ws.status), _ptr(ws.kkt),
+          _ptr(ws.iters), _ptr(ws.flag), _ptr(ws.target), _ptr(ws.plan_status), _stream())
+    return ws
+
+
 def track_prep_dev(N, V, lap_length, x, n_veh, obs_s_in, obs_ey_in, traj, xt, obs_s, obs_ey, lap_off, n_obs, safety_time=2.0, dt_ref=0.1):
     """crx_track_prep_dev: per-stage targets and obstacle arrays of the tracking NLP from the planner's outputs."""
     Bn = x.shape[0]

@@ -816,6 +816,154 @@ int crx_path_solve(const crx_path_desc* d, int batch, const double* opt, const d
     return sg.down(g_stream);
 }
 
+// ---- overtake path planner around its QPs (crx_pathplan.hip) ------------------------------------------
+void crx_pathprep_desc_default(crx_pathprep_desc* d, int N, int n_veh_max, int n_all_max, int n_opt, double track_width, double lap_length) {
+    memset(d, 0, sizeof(*d));
+    d->N = N; d->n_veh_max = n_veh_max; d->n_opt = n_opt; d->n_all_max = n_all_max;
+    d->safety_factor = 4.5; d->prediction_factor = 0.5; d->lookahead = 4.0; d->next_lap_range = 20.0;
+    d->track_width = track_width; d->lap_length = lap_length; d->veh_length = 0.4; d->veh_width = 0.2; d->a_max_plan = 1.5;
+}
+
+// the family's one check.  The arguments are looked at BEFORE the library's state: a refusal needs no device.  qd / plan: the fused step
+static int check_pathplan(crx_pathplan_kparams& pp, const crx_pathprep_desc* d, const crx_path_desc* qd, bool plan, int n_scen, arr x_wrapped,
+                          arr x_raw, arr n_veh, arr order, arr veh_xcurv, arr max_dv, arr obs_ey, arr opt_s, arr opt_ey, arr opt_vx, arr opt, arr bez,
+                          arr lb, arr ub, arr e0, arr eN, arr span, arr qp_active, arr E, arr cost, arr status, arr kkt, arr iters, arr flag,
+                          arr target, arr plan_status) {
+    if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
+    if (d->N < 2 || d->N > CRX_MAX_N) return fail(CRX_ERR_ARG, "N=%d outside [2,%d]", d->N, CRX_MAX_N);
+    if (d->n_veh_max < 1 || d->n_veh_max > CRX_MAX_VEH) return fail(CRX_ERR_ARG, "n_veh_max=%d outside [1,%d]", d->n_veh_max, CRX_MAX_VEH);
+    if (d->n_all_max < 1) return fail(CRX_ERR_ARG, "n_all_max < 1");
+    if (d->n_opt < 2) return fail(CRX_ERR_ARG, "n_opt < 2");
+    if (n_scen < 0) return fail(CRX_ERR_ARG, "n_scen < 0");
+    if (!(d->lap_length > 0.0) || !(d->track_width > 0.0)) return fail(CRX_ERR_ARG, "lap_length and track_width must be positive");
+    if (plan) {
+        crx_path_kparams qp;
+        if (int rc = fill_path(qp, qd, n_scen)) return rc;
+        if (qd->N != d->N) return fail(CRX_ERR_ARG, "the two descriptors disagree on N (%d, %d)", d->N, qd->N);
+    }
+    if (n_scen > 0 && any_null(x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey, opt, bez, lb, ub, e0, eN, span))
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    if (n_scen > 0 && plan && any_null(opt_vx, qp_active, E, cost, status, kkt, iters, flag, target, plan_status))
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    if (int rc = ensure_init()) return rc;
+    memset(&pp, 0, sizeof(pp));
+    pp.d = *d; pp.n_scen = n_scen;
+    return 0;
+}
+
+int crx_path_prep_dev(const crx_pathprep_desc* d, int n_scen, const double* x_wrapped, const double* x_raw, const int32_t* n_veh,
+                      const int32_t* order, const double* veh_xcurv, const double* max_dv, const double* obs_ey, const double* opt_s,
+                      const double* opt_ey, double* opt, double* bez, double* lb, double* ub, double* e0, double* eN, double* span,
+                      void* stream) {
+    crx_pathplan_kparams pp;
+    if (int rc = check_pathplan(pp, d, nullptr, false, n_scen, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey, nullptr,
+                                opt, bez, lb, ub, e0, eN, span, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return rc;
+    if (n_scen == 0) return CRX_OK;
+    pp.x_wrapped = x_wrapped; pp.x_raw = x_raw; pp.n_veh = n_veh; pp.order = order; pp.veh_xcurv = veh_xcurv; pp.max_dv = max_dv;
+    pp.obs_ey = obs_ey; pp.opt_s = opt_s; pp.opt_ey = opt_ey;
+    pp.opt = opt; pp.bez = bez; pp.lb = lb; pp.ub = ub; pp.e0 = e0; pp.eN = eN; pp.span = span;
+    return launched(crx_launch_pathprep(pp, (hipStream_t)stream), "pathprep");
+}
+
+int crx_path_plan_dev(const crx_pathprep_desc* d, const crx_path_desc* qd, int n_scen, const int32_t* active, const double* x_wrapped,
+                      const double* x_raw, const int32_t* n_veh, const int32_t* order, const double* veh_xcurv, const double* max_dv,
+                      const double* obs_ey, const double* opt_s, const double* opt_ey, const double* opt_vx, double* opt, double* bez,
+                      double* lb, double* ub, double* e0, double* eN, double* span, int32_t* qp_active, double* E, double* cost,
+                      int32_t* status, double* kkt, int32_t* iters, int32_t* flag, double* target, int32_t* plan_status, void* stream) {
+    crx_pathplan_kparams pp;
+    if (int rc = check_pathplan(pp, d, qd, true, n_scen, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey, opt_vx, opt,
+                                bez, lb, ub, e0, eN, span, qp_active, E, cost, status, kkt, iters, flag, target, plan_status))
+        return rc;
+    if (n_scen == 0) return CRX_OK;
+    pp.x_wrapped = x_wrapped; pp.x_raw = x_raw; pp.n_veh = n_veh; pp.order = order; pp.veh_xcurv = veh_xcurv; pp.max_dv = max_dv;
+    pp.obs_ey = obs_ey; pp.opt_s = opt_s; pp.opt_ey = opt_ey; pp.opt_vx = opt_vx; pp.active = active;
+    pp.opt = opt; pp.bez = bez; pp.lb = lb; pp.ub = ub; pp.e0 = e0; pp.eN = eN; pp.span = span; pp.qp_active = qp_active;
+    pp.E = E; pp.cost = cost; pp.flag = flag; pp.target = target; pp.plan_status = plan_status;
+    crx_path_kparams_masked qp;
+    const int batch = n_scen * (d->n_veh_max + 1);
+    if (int rc = fill_path(qp, qd, batch)) return rc;
+    qp.opt = opt; qp.bez = bez; qp.lb = lb; qp.ub = ub; qp.e0 = e0; qp.eN = eN;
+    qp.E = E; qp.cost = cost; qp.status = status; qp.kkt = kkt; qp.iters = iters; qp.active = qp_active;
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = launched(crx_launch_pathprep(pp, st), "pathprep")) return rc;
+    if (int rc = launched(crx_launch_path_masked(qp, st), "path (masked)")) return rc;
+    return launched(crx_launch_pathselect(pp, st), "pathselect");
+}
+
+// host-pointer n_veh / order can be validated (the device entries clamp)
+static int check_pathplan_host(const crx_pathprep_desc* d, int n_scen, const int32_t* n_veh, const int32_t* order) {
+    for (int i = 0; i < n_scen; i++) {
+        if (n_veh[i] < 0 || n_veh[i] > d->n_veh_max) return fail(CRX_ERR_ARG, "n_veh[%d]=%d outside [0,%d]", i, n_veh[i], d->n_veh_max);
+        for (int k = 0; k < n_veh[i]; k++) {
+            const int v = order[(size_t)i * d->n_veh_max + k];
+            if (v < 0 || v >= d->n_all_max) return fail(CRX_ERR_ARG, "order[%d][%d]=%d outside [0,%d)", i, k, v, d->n_all_max);
+        }
+    }
+    return 0;
+}
+
+int crx_path_prep(const crx_pathprep_desc* d, int n_scen, const double* x_wrapped, const double* x_raw, const int32_t* n_veh,
+                  const int32_t* order, const double* veh_xcurv, const double* max_dv, const double* obs_ey, const double* opt_s,
+                  const double* opt_ey, double* opt, double* bez, double* lb, double* ub, double* e0, double* eN, double* span) {
+    crx_pathplan_kparams chk;
+    if (int rc = check_pathplan(chk, d, nullptr, false, n_scen, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey, nullptr,
+                                opt, bez, lb, ub, e0, eN, span, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr))
+        return rc;
+    if (n_scen == 0) return CRX_OK;
+    if (int rc = check_pathplan_host(d, n_scen, n_veh, order)) return rc;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    const size_t S = (size_t)n_scen, N1 = (size_t)d->N + 1, V = (size_t)d->n_veh_max, R = V + 1, T = (size_t)d->n_opt;
+    Stage sg;
+    auto dxw = sg.in(x_wrapped, S * 6); auto dxr = sg.in(x_raw, S * 6); auto dnv = sg.in(n_veh, S); auto dor = sg.in(order, S * V);
+    auto dvx = sg.in(veh_xcurv, S * (size_t)d->n_all_max * 6); auto dmd = sg.in(max_dv, S); auto doe = sg.in(obs_ey, S * V * N1);
+    auto dts = sg.in(opt_s, T); auto dte = sg.in(opt_ey, T);
+    // in/out: a scenario without vehicles keeps what the caller's arrays held
+    auto dop = sg.inout(opt, S * R * N1); auto dbz = sg.inout(bez, S * R * N1); auto dlb = sg.inout(lb, S * R * N1);
+    auto dub = sg.inout(ub, S * R * N1); auto d0 = sg.inout(e0, S * R); auto dN = sg.inout(eN, S * R); auto dsp = sg.inout(span, S);
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_path_prep_dev(d, n_scen, sg[dxw], sg[dxr], sg[dnv], sg[dor], sg[dvx], sg[dmd], sg[doe], sg[dts], sg[dte], sg[dop], sg[dbz],
+                                   sg[dlb], sg[dub], sg[d0], sg[dN], sg[dsp], g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
+int crx_path_plan(const crx_pathprep_desc* d, const crx_path_desc* qd, int n_scen, const int32_t* active, const double* x_wrapped,
+                  const double* x_raw, const int32_t* n_veh, const int32_t* order, const double* veh_xcurv, const double* max_dv,
+                  const double* obs_ey, const double* opt_s, const double* opt_ey, const double* opt_vx, double* E, double* cost,
+                  int32_t* status, double* kkt, int32_t* iters, int32_t* flag, double* target, int32_t* plan_status) {
+    crx_pathplan_kparams chk;
+    const arr own = &chk;   // the prep arrays and the QP mask are this call's staging: present by construction
+    if (int rc = check_pathplan(chk, d, qd, true, n_scen, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey, opt_vx, own,
+                                own, own, own, own, own, own, own, E, cost, status, kkt, iters, flag, target, plan_status))
+        return rc;
+    if (n_scen == 0) return CRX_OK;
+    if (int rc = check_pathplan_host(d, n_scen, n_veh, order)) return rc;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    const size_t S = (size_t)n_scen, N1 = (size_t)d->N + 1, V = (size_t)d->n_veh_max, R = V + 1, T = (size_t)d->n_opt;
+    const size_t row = (S * R * N1 * sizeof(double) + 255) & ~size_t(255), vec = (S * R * sizeof(double) + 255) & ~size_t(255);
+    Stage sg;
+    auto dxw = sg.in(x_wrapped, S * 6); auto dxr = sg.in(x_raw, S * 6); auto dnv = sg.in(n_veh, S); auto dor = sg.in(order, S * V);
+    auto dvx = sg.in(veh_xcurv, S * (size_t)d->n_all_max * 6); auto dmd = sg.in(max_dv, S); auto doe = sg.in(obs_ey, S * V * N1);
+    auto dts = sg.in(opt_s, T); auto dte = sg.in(opt_ey, T); auto dtv = sg.in(opt_vx, T);
+    auto dac = active ? sg.in(active, S) : Stage::Ref<int32_t>{};
+    // in/out: what a skipped scenario leaves untouched is the caller's data
+    auto dE = sg.inout(E, S * R * N1); auto dk = sg.inout(kkt, S * R); auto dtg = sg.inout(target, S * N1 * 6);
+    auto dc = sg.out(cost, S * R); auto ds = sg.out(status, S * R); auto di = sg.out(iters, S * R);
+    auto dfl = sg.out(flag, S); auto dps = sg.out(plan_status, S);
+    auto dws = sg.scratch(4 * row + 4 * vec);   // opt, bez, lb, ub | e0, eN, span (S <= S R), qp_active (4 B each)
+    if (int rc = sg.up(g_stream)) return rc;
+    char* w = sg[dws];
+    double *wopt = (double*)w, *wbez = (double*)(w + row), *wlb = (double*)(w + 2 * row), *wub = (double*)(w + 3 * row);
+    double *we0 = (double*)(w + 4 * row), *weN = (double*)(w + 4 * row + vec), *wsp = (double*)(w + 4 * row + 2 * vec);
+    int32_t* wqa = (int32_t*)(w + 4 * row + 3 * vec);
+    if (int rc = crx_path_plan_dev(d, qd, n_scen, sg[dac], sg[dxw], sg[dxr], sg[dnv], sg[dor], sg[dvx], sg[dmd], sg[doe], sg[dts], sg[dte],
+                                   sg[dtv], wopt, wbez, wlb, wub, we0, weN, wsp, wqa, sg[dE], sg[dc], sg[ds], sg[dk], sg[di], sg[dfl], sg[dtg],
+                                   sg[dps], g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
 // ---- plant ----------------------------------------------------------------------------------------
 void crx_plant_desc_default(crx_plant_desc* d, int n_seg, double lap_length) {
     memset(d, 0, sizeof(*d));

@@ -99,6 +99,27 @@ struct crx_path_kparams {
     int32_t *status, *iters;
 };
 
+// crx_path_masked_kernel (crx_pathplan.hip: crx_path_kernel's source compiled again with a per-QP mask).  Derived, so that crx_path_kparams --
+// which crx_path_kernel takes by value -- keeps its size and the code object behind crx_path_solve stays what it is.
+struct crx_path_kparams_masked : crx_path_kparams {
+    const int32_t* active;   // optional [batch]: 0 = this QP is not solved: status CRX_SKIPPED, cost +inf, iters 0, E and kkt untouched.  NULL: all
+};
+
+// crx_pathprep_kernel / crx_pathselect_kernel (crx_pathplan.hip): the overtake PATH planner around its QPs
+struct crx_pathplan_kparams {
+    crx_pathprep_desc d;
+    int n_scen;
+    const double *x_wrapped, *x_raw, *veh_xcurv, *max_dv, *obs_ey, *opt_s, *opt_ey, *opt_vx;
+    const int32_t *n_veh, *order, *active;   // active: optional [n_scen], fused step only
+    // prep outputs = inputs of the QP launch
+    double *opt, *bez, *lb, *ub, *e0, *eN, *span;
+    int32_t* qp_active;                      // optional [n_scen * (V + 1)]: the mask crx_path_masked_kernel runs under (fused step)
+    // selection
+    const double *E, *cost;
+    int32_t *flag, *plan_status;
+    double* target;
+};
+
 struct crx_plant_kparams {
     crx_plant_desc d;
     int batch, u_stride, wrap;
@@ -161,6 +182,10 @@ size_t crx_solve_lds_bytes(int N, int nobs_template);
 int crx_solve_resident_per_cu(int N, int nobs_template);
 hipError_t crx_launch_path(const crx_path_kparams& pp, hipStream_t st);
 hipError_t crx_launch_cbfprep(const crx_cbfprep_kparams& cp, hipStream_t st);
+// crx_pathplan.hip
+hipError_t crx_launch_path_masked(const crx_path_kparams_masked& pp, hipStream_t st);
+hipError_t crx_launch_pathprep(const crx_pathplan_kparams& pp, hipStream_t st);
+hipError_t crx_launch_pathselect(const crx_pathplan_kparams& pp, hipStream_t st);
 
 // dispatch order of a solver launch (include/crx.h, "Dispatch order"): a stable counting sort of the batch by a 257-valued key
 struct crx_order_kparams {

@@ -22,6 +22,14 @@
 #include "crx_num.h"
 #include "crx_ipm.h"
 
+// crx_pathplan.hip compiles this file a second time with CRX_TU_PATHPLAN defined, for the path QP ALONE and under another name, parameter
+// struct and with a per-QP mask (as crx_kernels_obs.hip does with crx_kernels.hip); every other kernel and launcher below is left out of that
+// unit.  Without the macro the three names below expand to what stood here before, token for token: this unit's code objects are unchanged.
+#ifndef CRX_TU_PATHPLAN
+#define CRX_PATH_KERNEL crx_path_kernel
+#define CRX_PATH_KPARAMS crx_path_kparams
+#define CRX_PATH_SKIP(pp, b, lane)
+
 __global__ void __launch_bounds__(WAVE) crx_prep_kernel(const crx_prep_kparams pp) {
     const int s = blockIdx.x, lane = threadIdx.x;
     if (s >= pp.n_scen) return;
@@ -347,6 +355,7 @@ hipError_t crx_launch_cbfprep(const crx_cbfprep_kparams& cp, hipStream_t st) {
     hipLaunchKernelGGL(crx_cbfprep_kernel, dim3((cp.batch + 255) / 256), dim3(256), 0, st, cp);
     return hipGetLastError();
 }
+#endif   // CRX_TU_PATHPLAN
 
 // ------------------------------------------------------------------------------------------------
 // Overtake PATH planner QP (planning/overtake_path_planner.py:199-318): one
@@ -357,13 +366,14 @@ hipError_t crx_launch_cbfprep(const crx_cbfprep_kparams& cp, hipStream_t st) {
 #define PATH_NV (CRX_MAX_N)
 #define PATH_LD (CRX_MAX_N + 1)
 
-__global__ void __launch_bounds__(WAVE) crx_path_kernel(const crx_path_kparams pp) {
+__global__ void __launch_bounds__(WAVE) CRX_PATH_KERNEL(const CRX_PATH_KPARAMS pp) {
     __shared__ double sh[(PATH_NV + 4) * PATH_LD + 3 * PATH_NV + 32];   // +3 rows: the blocked Cholesky reads (not uses) past the last row
     double* Km = sh;
     constexpr int IK = (PATH_NV + 4) * PATH_LD;
     double *v = sh + IK + PATH_NV, *dv = v + PATH_NV, *Fth = dv + PATH_NV, *Fph = Fth + 16;
     const int b = blockIdx.x, lane = threadIdx.x, N = pp.N, n = N - 1;
     if (b >= pp.batch) return;
+    CRX_PATH_SKIP(pp, b, lane)   // (crx_pathplan.hip: the per-QP mask; nothing here)
     const crx_ipm_opts& o = pp.opts;
     const double *op = pp.opt + (size_t)(N + 1) * b, *bz = pp.bez + (size_t)(N + 1) * b;
     const double *lo = pp.lb + (size_t)(N + 1) * b, *hi = pp.ub + (size_t)(N + 1) * b;
@@ -502,6 +512,7 @@ __global__ void __launch_bounds__(WAVE) crx_path_kernel(const crx_path_kparams p
     }
 }
 
+#ifndef CRX_TU_PATHPLAN
 hipError_t crx_launch_path(const crx_path_kparams& pp, hipStream_t st) {
     if (pp.batch == 0) return hipSuccess;
     hipLaunchKernelGGL(crx_path_kernel, dim3(pp.batch), dim3(WAVE), 0, st, pp);
@@ -754,3 +765,4 @@ hipError_t crx_launch_game(int which, const crx_game_kparams& gp, hipStream_t st
     }
     return hipGetLastError();
 }
+#endif   // CRX_TU_PATHPLAN

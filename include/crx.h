@@ -110,9 +110,12 @@ typedef enum crx_status {
                               divergence heuristic).  libcrx <= 0.1.3 reported these as CRX_INFEASIBLE.  Like every status != 0 it
                               selects the reference's "solver failed" branch (control.py:600-603: keep the last iterate;
                               overtake_traj_planner.py:365-374: the fall-back trajectory). */
-    CRX_SINGULAR = 6       /* crx_sysid_fit: a zero or non-finite pivot in the LU of X'X + lamb I, where numpy.linalg.inv raises
+    CRX_SINGULAR = 6,      /* crx_sysid_fit: a zero or non-finite pivot in the LU of X'X + lamb I, where numpy.linalg.inv raises
                               LinAlgError; W, A, B and err are NaN.  crx_lqr_design: a non-finite model, iterate or gain, or a zero or
                               non-finite determinant of R + B'PB; K and P are NaN */
+    CRX_OUT_OF_DOMAIN = 7  /* crx_path_plan (plan_status only): the scenario cannot be planned from its data -- a look-up falls above the
+                              optimal-trajectory table, where the reference raises (interp1d bounds_error: the Bezier end point, quirk P2,
+                              or the target speed, quirk P8), or an input it reads is not finite.  flag -1, target NaN */
 } crx_status;
 
 /* Interior-point options.  Defaults (crx_ipm_opts_default) restate IPOPT 3.x defaults that the
@@ -668,6 +671,87 @@ int crx_path_solve(const crx_path_desc* d, int batch, const double* opt, const d
 int crx_path_solve_dev(const crx_path_desc* d, int batch, const double* opt, const double* bez, const double* lb,
                        const double* ub, const double* e0, const double* eN, double* E, double* cost, int32_t* status,
                        double* kkt, int32_t* iters, void* stream);
+
+/*
+ * The overtake PATH planner around its QPs, on the device (remainder): from the outputs of
+ * crx_planner_scene to a flag and a target trajectory.  Restates planning/overtake_path_planner.py (line numbers into it unless another
+ * file is named) operation by operation, products and sums rounded separately (no contraction).  Its quirks are kept, not repaired:
+ *   P1  obstacle rows (s, max ey, min ey) are indexed by SORTED vehicle (:60-75; the trajectory planner's iteration order, quirk Q4, does
+ *       not apply): s = veh_xcurv[s][order[k]][4], the vehicle's current state; max / min over the sorted prediction obs_ey[s][k][0..N].
+ *   P2  control points: get_bezier_control_points (planner_helper.py:43-135) on the P1 rows and the WRAPPED ego state; the end point is
+ *       s3 = s0 + prediction_factor max_dv + lookahead (:78-87), its ey the optimal line's; polylines sampled at t = j (1/N) (:88-100).
+ *       An end point above the optimal-trajectory table raises in the reference: CRX_OUT_OF_DOMAIN here.
+ *   P3  span = max_s + safety_factor veh_length + prediction_factor max_dv - ego_s_raw (:117-127, :230-240); max_s from get_agent_info
+ *       (planner_helper.py:177-201): every s <= next_lap_range gets + lap_length (a literal 20 that fits l_shape, applied to every car),
+ *       the maximum is then wrapped with `while > lap_length`.
+ *   P4  sample position s_tmp = ego_s_raw + span j / N; `while >= lap_length` subtract; if <= opt_s[0] it becomes opt_s[0]; then it is
+ *       clipped into the s-range of REGION 0's polyline, for every region (:241-245).  opt[r][j] = the optimal line's ey at s_tmp,
+ *       bez[r][j] = the clipped linear interpolation of region r's polyline at s_tmp (:249-251).
+ *   P5  side rows (:266-299): front / rear = s +- safety_factor veh_length, each wrapped with `while > lap_length` (:184-197); a row is
+ *       active iff not (s_tmp < rear or s_tmp > front) -- no wrap awareness: rear > front is an empty window.  The left neighbour
+ *       (sorted[r-1]) bounds from above with min ey - safety_factor veh_width, the right one (sorted[r]) from below with
+ *       max ey + safety_factor veh_width; at j = 0 a row the raw ego ey is already beyond is skipped; strict inequalities are taken as
+ *       non-strict; rows are merged with the track box +-track_width.
+ *   P6  end points: e0 = the raw ego ey, eN = the Bezier end point's ey (cps[r][3][1]).
+ *   P7  selection (:313-317): the FIRST minimum of the region costs, +inf for every region that did not converge; all +inf: flag 0, and E
+ *       of region 0 is what crx_path_kernel wrote for a failed QP (its documented fall-back).
+ *   P8  target (:113-143, :173-182): target[j][5] = E[flag][j]; target[j][4] = ego_s_raw + span j / N, unwrapped; vx_target = the optimal
+ *       trajectory's vx at s_q (three-way case :129-137); delta_t = 2 (s_N - x_w[4]) / (vx_target + x_w[0]);
+ *       a = clip((vx_target - x_w[0]) / delta_t, +-a_max_plan); row 0 = the whole wrapped state x_w; vx_j = sqrt(x_w[0]^2 + 2 a
+ *       (target[j][4] - x_w[4])) for j = 0..N-1, AFTER row 0 was overwritten; row N's vx stays 0; every other column 0.  A negative
+ *       radicand is NaN, as in numpy.  s_q above the table raises in the reference: CRX_OUT_OF_DOMAIN here.
+ */
+typedef struct crx_pathprep_desc {
+    int32_t N;               /* num_horizon_planner */
+    int32_t n_veh_max;       /* V <= CRX_MAX_VEH: leading dimension of order / obs_ey; regions = V + 1 */
+    int32_t n_opt;           /* rows of the optimal-trajectory table */
+    int32_t n_all_max;       /* VA: leading dimension of veh_xcurv (crx_scene_desc.n_all_max) */
+    double safety_factor;    /* 4.5  P3, P5 */
+    double prediction_factor;/* 0.5  P2, P3 */
+    double lookahead;        /* 4.0  P2: the literal of planner_helper.py:51-53 */
+    double next_lap_range;   /* 20.0 P3: the literal of planner_helper.py:178 */
+    double track_width;      /* P2, P5 */
+    double lap_length;
+    double veh_length;       /* 0.4  P3, P5 */
+    double veh_width;        /* 0.2  P2, P5 */
+    double a_max_plan;       /* 1.5  P8: the literal of :140 */
+} crx_pathprep_desc;
+void crx_pathprep_desc_default(crx_pathprep_desc* d, int N, int n_veh_max, int n_all_max, int n_opt, double track_width, double lap_length);
+/*
+ * crx_path_prep: P1-P6, written directly in the layout crx_path_solve reads (leading dimension S (V+1), scenario-major).
+ *   x_wrapped, x_raw [S][6];  n_veh [S], order [S][V], max_dv [S], obs_ey [S][V][N+1]: outputs of crx_planner_scene;
+ *   veh_xcurv [S][VA][6]: the vehicles' current states (the scene's input);  opt_s, opt_ey [n_opt]: columns 4, 5 of the table
+ *   opt, bez, lb, ub [S(V+1)][N+1];  e0, eN [S(V+1)];  span [S]                                                         out
+ * Regions beyond n_veh[s] repeat region n_veh[s] (never selected).  A scenario with n_veh == 0 is not planned (the reference never plans
+ * then; max_s is undefined): its outputs keep their contents.  A CRX_OUT_OF_DOMAIN scenario (P2, or a non-finite input) gets NaN in
+ * every output, which its QPs answer with CRX_INFEASIBLE.  n_veh and order are clamped into range (device data cannot be validated).
+ */
+int crx_path_prep(const crx_pathprep_desc* d, int n_scen, const double* x_wrapped, const double* x_raw, const int32_t* n_veh,
+                  const int32_t* order, const double* veh_xcurv, const double* max_dv, const double* obs_ey, const double* opt_s,
+                  const double* opt_ey, double* opt, double* bez, double* lb, double* ub, double* e0, double* eN, double* span);
+int crx_path_prep_dev(const crx_pathprep_desc* d, int n_scen, const double* x_wrapped, const double* x_raw, const int32_t* n_veh,
+                      const int32_t* order, const double* veh_xcurv, const double* max_dv, const double* obs_ey, const double* opt_s,
+                      const double* opt_ey, double* opt, double* bez, double* lb, double* ub, double* e0, double* eN, double* span,
+                      void* stream);
+/*
+ * crx_path_plan: one path-planner step, crx_path_prep -> the region QPs (crx_path_kernel's source under a per-QP mask) -> P7, P8, three
+ * launches on one stream.  Inputs of crx_path_prep plus opt_vx [n_opt] (column 0 of the table) and active [S] (may be NULL = all).
+ *   E [S(V+1)][N+1], cost, status, kkt, iters [S(V+1)]   per region, as crx_path_solve
+ *   flag [S], target [S][N+1][6], plan_status [S]        per scenario; plan_status = 0, CRX_SKIPPED or CRX_OUT_OF_DOMAIN
+ * Scenarios that must not be planned -- n_veh[s] == 0 or active[s] == 0: every region answers status CRX_SKIPPED with cost +inf
+ * (iters 0; E, kkt untouched), flag -1, plan_status CRX_SKIPPED, target untouched.  CRX_OUT_OF_DOMAIN: flag -1, target NaN.
+ * The device entry leaves the prep arrays and the QP mask where the caller can read them: opt .. span as crx_path_prep_dev, and
+ * qp_active [S(V+1)] int32.  The host entry keeps them in its staging.
+ */
+int crx_path_plan(const crx_pathprep_desc* d, const crx_path_desc* qd, int n_scen, const int32_t* active, const double* x_wrapped,
+                  const double* x_raw, const int32_t* n_veh, const int32_t* order, const double* veh_xcurv, const double* max_dv,
+                  const double* obs_ey, const double* opt_s, const double* opt_ey, const double* opt_vx, double* E, double* cost,
+                  int32_t* status, double* kkt, int32_t* iters, int32_t* flag, double* target, int32_t* plan_status);
+int crx_path_plan_dev(const crx_pathprep_desc* d, const crx_path_desc* qd, int n_scen, const int32_t* active, const double* x_wrapped,
+                      const double* x_raw, const int32_t* n_veh, const int32_t* order, const double* veh_xcurv, const double* max_dv,
+                      const double* obs_ey, const double* opt_s, const double* opt_ey, const double* opt_vx, double* opt, double* bez,
+                      double* lb, double* ub, double* e0, double* eN, double* span, int32_t* qp_active, double* E, double* cost,
+                      int32_t* status, double* kkt, int32_t* iters, int32_t* flag, double* target, int32_t* plan_status, void* stream);
 
 /*
  * Obstacle arrays of control.mpccbf for scripted cars, built on the device (used by device-resident race loops):

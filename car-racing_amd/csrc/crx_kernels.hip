@@ -134,6 +134,14 @@ __device__ __forceinline__ double ipow_d(double a, int p) {
 #endif
 enum : unsigned { LF_ROW_STEP = 1, LF_ROW_TRIAL = 2, LF_ROW_ACCEPT = 4, LF_ACCEPT_Z = 8, LF_FIRST_ORDER = 16, LF_ASSEMBLE = 32 };
 template <int NOBS, int NMAX> constexpr unsigned LoadsFirst = (NOBS == 1 && NMAX == 12 && !CRX_TU_GENERAL) ? (unsigned)(CRX_LOADS_FIRST) : 0u;
+// [r9] The same instantiations (the reach of LoadsFirst) with NMAX * NOBS <= 64 -- one pass over the CBF rows, the row of a lane the same in every
+// pass -- hand the CBF row values of the accepted line-search trial to the accept step, which stores the point the trial evaluated them at and
+// would evaluate them there once more: the same expression on the same doubles (same bits: tests/test_gpu_obs1_retry_bits.py).  A/B builds: make
+// EXTRA=-DCRX_CBF_CARRY=0 is the form that evaluates twice; every other instantiation keeps it.
+#ifndef CRX_CBF_CARRY
+#define CRX_CBF_CARRY 1
+#endif
+template <int NOBS, int NMAX> constexpr bool CbfCarry = (CRX_CBF_CARRY) != 0 && NOBS == 1 && NMAX == 12 && !CRX_TU_GENERAL && NMAX * NOBS <= WAVE;
 // end of a stage of an UNROLLED sweep [r4]: without it the scheduler lifts the loads of all later stages to the top of the sweep and the
 // registers they occupy are paid for in scratch (a wave writes its spills once: 100 B per lane were x8 the algorithmic bytes written of a cfg2 launch)
 #define STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -1695,6 +1703,8 @@ crx_solve_kernel(const crx_solve_params kp) {
     constexpr int NX = L::NX, NZ = L::NZ, NR = L::NR;
     // [r8] the phases of this instantiation that load both passes before they compute (LoadsFirst), and the passes of a row / coordinate phase
     constexpr unsigned LF = (NFIX != 0 && QPM == 0) ? LoadsFirst<NOBS, NMAX> : 0u;
+    // [r9] ... and whether its accept step takes the CBF row values of the accepted trial (CbfCarry)
+    constexpr bool CBFC = NFIX != 0 && QPM == 0 && CbfCarry<NOBS, NMAX>;
     constexpr int RPASS = (L::MR + WAVE - 1) / WAVE, CPASS = (L::NV + WAVE - 1) / WAVE;
     static_assert(LF == 0 || !L::SLIM, "the loads-first row passes are written for the full layout (row_scale, row_bound, row_sig_w are loads there)");
 #if CRX_STATIC_LDS
@@ -2517,6 +2527,7 @@ crx_solve_kernel(const crx_solve_params kp) {
         long long tc7 = CLK();
         // ---- filter line search ----------------------------------------------------------------------
         double al = a_p, fn = f, lt_acc = logsum_t;
+        double cbf_tr = 0.0;   // CBFC: this lane's CBF row value of the last trial, unscaled (the accept step's, when the trial is accepted)
         int acc = 0, ftype = 0;
         // switching condition al * (-Dphi)^2.3 > theta^1.1 (only consulted when theta <= theta_min)
         const bool sw_try = (theta <= theta_min) && (Dphi < 0.0);
@@ -2556,7 +2567,9 @@ crx_solve_kernel(const crx_solve_params kp) {
             if (NOBS) {
                 CBF_ROWS(j, k, ob, ev, lane, N) {   // evaluated at Z + al dZ
                     const double sc = cbf_scale<L>(sm, k, ob), t = LD(L::rt + j), dt = LD(L::rdt + j);
-                    row_trial(j, ev, true, sc, sc * cbf_value<NOBS, NMAX>(sm, c, k, ob, al), t, dt);
+                    const double cv = cbf_value<NOBS, NMAX>(sm, c, k, ob, al);
+                    if constexpr (CBFC) cbf_tr = cv;
+                    row_trial(j, ev, true, sc, sc * cv, t, dt);
                 }
             }
             lt_acc = lg.wave_total_with(thn);                         // thn and the exponent sum share one reduction
@@ -2676,7 +2689,11 @@ crx_solve_kernel(const crx_solve_params kp) {
         if (NOBS) {
             CBF_ROWS(j, k, ob, ev, lane, N) {
                 const double sc = cbf_scale<L>(sm, k, ob);
-                row_accept(j, ev, sc, sc * cbf_value<NOBS, NMAX>(sm, c, k, ob, 0.0));
+                // (CBFC: Z now holds Z + al dZ of the accepted trial, rounded as the trial rounded it: evaluated here the row would be the trial's, bit for bit.
+                // The UNSCALED value is what is carried: the violation |sc v - t| below is formed with one rounding, fma(sc, v, -t), as it always was --
+                // carrying the rounded product sc v changed the last bits of e_p, and with it the reported KKT error: HISTORY.md, round 9)
+                if constexpr (CBFC) row_accept(j, ev, sc, sc * cbf_tr);
+                else row_accept(j, ev, sc, sc * cbf_value<NOBS, NMAX>(sm, c, k, ob, 0.0));
             }
         }
         SYNC();

@@ -9,6 +9,10 @@ inside the loop; torch only owns the device memory.
 
 The reference runs such sweeps one race at a time (car_racing/tests/overtake_planner_test.py
 --multi-tests); this is the same experiment with the race index as the batch dimension.
+
+Every loop steps its plant through _Plant._advance, the learning-MPC step is LmpcLaps._plan / _apply (GameLaps drives its
+`lm` through them), and the run-to-the-end functions share _run_and_log.  The launch sequence of each step() is stated in its
+docstring and pinned by tests/test_montecarlo_sequence_cpu.py.
 """
 import numpy as np
 import torch
@@ -36,12 +40,22 @@ class _Noise:
         return torch.randn((batch, 3), generator=self.gen, dtype=torch.float64, device=self.device)
 
 
+def _dev(a, dev, dtype=torch.float64, clone=False):
+    """Host array -> contiguous tensor of `dtype` on `dev`.  clone: the loop writes to it, so it must own its memory (on the CPU
+    torch.as_tensor shares the caller's array)."""
+    t = torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device=dev)
+    return t.clone() if clone else t
+
+
+def _per_race(v, batch, dev):
+    """[batch] float64 on `dev` from a scalar or one value per race."""
+    return _dev(np.broadcast_to(np.asarray(v, dtype=float), (batch,)).copy(), dev)
+
+
 def _models(A, B, batch, dev):
     """(A [batch,6,6], B [batch,6,2]) contiguous float64 on `dev` from one model (6,6), (6,2) or per-problem models, host arrays
     or device tensors (as PidLaps.identify() returns them)."""
-    f64 = dict(dtype=torch.float64, device=dev)
-    A = A.to(**f64) if torch.is_tensor(A) else torch.as_tensor(np.ascontiguousarray(A, dtype=float), **f64)
-    B = B.to(**f64) if torch.is_tensor(B) else torch.as_tensor(np.ascontiguousarray(B, dtype=float), **f64)
+    A, B = (m.to(dtype=torch.float64, device=dev) if torch.is_tensor(m) else _dev(m, dev) for m in (A, B))
     if A.dim() == 2 and B.dim() == 2:
         A, B = A.expand(batch, 6, 6), B.expand(batch, 6, 2)
     if tuple(A.shape) != (batch, 6, 6) or tuple(B.shape) != (batch, 6, 2):
@@ -168,52 +182,91 @@ class Concurrent:
         return torch.cat([get(p) for p in self.parts], dim=0)
 
 
-class MpccbfRaces:
+class _Plant:
+    """The plant side of a closed loop, held by the loop object itself: the cars' states xc (curvilinear) / xg (global) [B,6], the
+    buffers xc_next / xg_next the next plant launch writes, the lap counters, the track table, the plant descriptor and the
+    process noise.  _advance() is the one place a loop steps its plant.  The contract bench.py times the solver launches by:
+    after a step, xc_next is the state that step's solver launch was built for."""
+
+    def _plant_init(self, track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device):
+        dev = torch.device(device if device is not None else "cuda")
+        self.device, self.lap_length, self.timestep = dev, lap_length, timestep
+        self.noise = _Noise(noise_seed, dev)
+        self.xc, self.xg = _dev(xcurv0, dev, clone=True), _dev(xglob0, dev, clone=True)
+        self.xc_next, self.xg_next = torch.empty_like(self.xc), torch.empty_like(self.xg)
+        self.batch = self.xc.shape[0]
+        self.laps = torch.zeros(self.batch, dtype=torch.int32, device=dev)
+        self.tab = _dev(track_table, dev)
+        self.plant = abi.plant_desc(self.tab.shape[0], lap_length, timestep=timestep)
+        return dev
+
+    def _advance(self, u, u_stride, noise_z=None):
+        """ONE crx_plant_step_wrap_dev (plant + lap bookkeeping) with race b's input at u[b * u_stride], then xc / xc_next and
+        xg / xg_next exchange bindings.  noise_z None: the step's draws come from the loop's generator, which a given noise_z
+        leaves alone."""
+        if noise_z is None:
+            noise_z = self.noise.draw(self.batch)
+        torch_api.plant_step_wrap_dev(self.plant, self.tab, self.xg, self.xc, u, u_stride, self.xg_next, self.xc_next, self.laps,
+                                      noise_z=noise_z)
+        self.xg, self.xg_next = self.xg_next, self.xg
+        self.xc, self.xc_next = self.xc_next, self.xc
+
+
+def _run_and_log(step, steps, log_every, getters, before=()):
+    """`steps` calls of step(); at every log_every-th one, a clone of what each getter (name -> callable returning a device tensor)
+    returns after the step -- the names in `before` are read ahead of that step instead -- and "xcurv" once more at the start.
+    Returns name -> host array with the logged step as the first dimension."""
+    logs = {name: [] for name in getters}
+    logs["xcurv"].append(getters["xcurv"]().clone())
+    for k in range(steps):
+        logged = (k + 1) % log_every == 0
+        if logged:
+            for name in before:
+                logs[name].append(getters[name]().clone())
+        step()
+        if logged:
+            for name in getters:
+                if name not in before:
+                    logs[name].append(getters[name]().clone())
+    return {name: torch.stack(rows).cpu().numpy() for name, rows in logs.items()}
+
+
+class MpccbfRaces(_Plant):
     """State of B races on the device; step() advances all of them by one control step."""
 
     def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, car_s0, car_v, car_ey,
                  vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1, device=None, noise_seed=None, models=None):
-        dev = torch.device(device if device is not None else "cuda")
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device)
         f64 = dict(dtype=torch.float64, device=dev)
-        self.noise = _Noise(noise_seed, dev)
-        self.xc = torch.as_tensor(np.ascontiguousarray(xcurv0), **f64).clone()
-        self.xg = torch.as_tensor(np.ascontiguousarray(xglob0), **f64).clone()
-        self.s0, self.v, self.ey = (torch.as_tensor(np.ascontiguousarray(a), **f64) for a in (car_s0, car_v, car_ey))
+        self.s0, self.v, self.ey = (_dev(a, dev) for a in (car_s0, car_v, car_ey))
         Bn, V = self.s0.shape
         if V > abi.CRX_MAX_OBS:
             raise ValueError("at most %d scripted cars" % abi.CRX_MAX_OBS)
-        self.N, self.V, self.batch, self.lap_length, self.timestep = N, V, Bn, lap_length, timestep
-        self.tab = torch.as_tensor(np.ascontiguousarray(track_table), **f64)
+        self.N, self.V = N, V
         self.desc = abi.cbf_desc(N, V, A, B, alpha=alpha, margin=0.2, ey_max=track_width)
-        self.pdesc = abi.plant_desc(self.tab.shape[0], lap_length, timestep=timestep)
         self.xt = torch.tensor([vt, 0, 0, 0, 0, eyt], **f64).repeat(Bn, 1).contiguous()
         self.ws = torch_api.CbfWorkspace(self.desc, Bn, dev)
         # models = (A [B,6,6], B [B,6,2]), host arrays or device tensors (PidLaps.identify()): every race's controller on its own model
         # (crx_cbf_solve_models_dev); A, B above are then unused.  The reach table is computed here, once
         self.models = None if models is None else torch_api.CbfModels(self.desc, *_models(models[0], models[1], Bn, dev))
         self.jdt = torch.arange(N + 1, **f64) * timestep
-        self.laps = torch.zeros(Bn, dtype=torch.int32, device=dev)
         self.ar = torch.arange(V, device=dev)
         self.obs_s = torch.empty((Bn, V, N + 1), **f64)
         self.obs_e = torch.empty((Bn, V, N + 1), **f64)
         self.lap_off = torch.empty((Bn, V), **f64)
         self.n_obs = torch.empty((Bn,), dtype=torch.int32, device=dev)
-        self.xg_next, self.xc_next = torch.empty_like(self.xg), torch.empty_like(self.xc)
         self.t = 0.0   # every vehicle's own clock, advanced by `+= timestep` like the reference's (base.py:889,941)
         self.u = None
 
     def step(self):
-        """One control step of every race: three libcrx launches, nothing else."""
+        """One control step of every race, three libcrx launches and nothing else: cbf_prep_dev, cbf_solve_dev,
+        plant_step_wrap_dev (dispatch = "longest_first": one longest_first ahead of the solver launch)."""
         N = self.N
         torch_api.cbf_prep_dev(N, self.lap_length, self.t, self.timestep, self.xc, self.s0, self.v, self.ey,
                                self.obs_s, self.obs_e, self.lap_off, self.n_obs)
         torch_api.cbf_solve_dev(self.desc, self.xc, self.xt, self.obs_s, self.obs_e, self.lap_off, self.n_obs, ws=self.ws,
                                 order=_order(self, self.ws.iters), models=self.models)
-        # the plant reads u_0 of every race straight out of the solver's U [B][N][2]
-        torch_api.plant_step_wrap_dev(self.pdesc, self.tab, self.xg, self.xc, self.ws.U, 2 * N, self.xg_next, self.xc_next, self.laps,
-                                      noise_z=self.noise.draw(self.batch))
-        self.xg, self.xg_next = self.xg_next, self.xg
-        self.xc, self.xc_next = self.xc_next, self.xc
+        self._advance(self.ws.U, 2 * N)   # the plant reads u_0 of every race straight out of the solver's U [B][N][2]
         self.u = self.ws.U[:, 0, :]
         self.t += self.timestep
 
@@ -240,7 +293,7 @@ class MpccbfRaces:
         torch_api.cbf_solve_dev(self.desc, xc, self.xt, ps.contiguous(), pe.contiguous(), po.contiguous(), n_obs.contiguous(),
                                 ws=self.ws, models=self.models)
         self.u = self.ws.U[:, 0, :].contiguous()
-        self.xg, xc = torch_api.plant_step_dev(self.pdesc, self.tab, self.xg, xc, self.u)
+        self.xg, xc = torch_api.plant_step_dev(self.plant, self.tab, self.xg, xc, self.u)
         crossed = xc[:, 4] > L
         xc[:, 4] = torch.where(crossed, xc[:, 4] - L, xc[:, 4])
         self.laps += crossed.to(torch.int32)
@@ -255,18 +308,12 @@ def mpccbf_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, car
     status [T,B], laps [B]."""
     r = MpccbfRaces(track_table, lap_length, track_width, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, vt=vt, eyt=eyt,
                     N=N, alpha=alpha, timestep=timestep, device=device, models=models)
-    log_x, log_u, log_st = [r.xc.clone()], [], []
-    for k in range(steps):
-        (r.step_glue if glue else r.step)()
-        if (k + 1) % log_every == 0:
-            log_x.append(r.xc.clone())
-            log_u.append(r.u.clone())
-            log_st.append(r.ws.status.clone())
-    return dict(xcurv=torch.stack(log_x).cpu().numpy(), u=torch.stack(log_u).cpu().numpy(),
-                status=torch.stack(log_st).cpu().numpy(), laps=r.laps.cpu().numpy())
+    logs = _run_and_log(r.step_glue if glue else r.step, steps, log_every,
+                        dict(xcurv=lambda: r.xc, u=lambda: r.u, status=lambda: r.ws.status))
+    return dict(logs, laps=r.laps.cpu().numpy())
 
 
-class IlqrRaces:
+class IlqrRaces(_Plant):
     """B copies of the reference's iLQR racing scenario (car_racing/tests/ilqr_test.py: ego under iLQRRacing, one scripted car
     s(t) = v t + s0, ey(t) = ey), device-resident.  Per control step, without touching the host: the scripted car's N+1
     predictions from its own clock (utils/base.py:879-886; control.ilqr applies no distance window, quirk I1), the lap offset
@@ -274,25 +321,16 @@ class IlqrRaces:
 
     def __init__(self, track_table, lap_length, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, vt=0.8, eyt=0.0, N=50,
                  max_iter=150, timestep=0.1, ego_dims=(0.4, 0.2), car_dims=(0.4, 0.2), device=None, noise_seed=None, models=None):
-        dev = torch.device(device if device is not None else "cuda")
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device)
         f64 = dict(dtype=torch.float64, device=dev)
-        self.noise = _Noise(noise_seed, dev)
-        self.xc = torch.as_tensor(np.ascontiguousarray(xcurv0), **f64).clone()
-        self.xg = torch.as_tensor(np.ascontiguousarray(xglob0), **f64).clone()
-        self.s0, self.v, self.ey = (torch.as_tensor(np.ascontiguousarray(a, dtype=float).reshape(-1, 1), **f64)
-                                    for a in (car_s0, car_v, car_ey))
-        Bn = self.xc.shape[0]
-        self.N, self.batch, self.lap_length, self.timestep = N, Bn, lap_length, timestep
-        self.tab = torch.as_tensor(np.ascontiguousarray(track_table), **f64)
+        self.s0, self.v, self.ey = (_dev(np.asarray(a, dtype=float).reshape(-1, 1), dev) for a in (car_s0, car_v, car_ey))
+        self.N, Bn = N, self.batch
         self.desc = abi.ilqr_desc(N, A, B, max_iter=max_iter, n_obs_max=1, l_sum=ego_dims[0] / 2 + car_dims[0] / 2,
                                   w_sum=ego_dims[1] / 2 + car_dims[1] / 2)
-        self.pdesc = abi.plant_desc(self.tab.shape[0], lap_length, timestep=timestep)
         self.xt = torch.tensor([vt, 0, 0, 0, 0, eyt], **f64).repeat(Bn, 1).contiguous()
         self.ws = torch_api.IlqrWorkspace(self.desc, Bn, dev)
         self.jdt = torch.arange(N + 1, **f64) * timestep
-        self.laps = torch.zeros(Bn, dtype=torch.int32, device=dev)
         self.n_obs = torch.ones(Bn, dtype=torch.int32, device=dev)
-        self.xg_next, self.xc_next = torch.empty_like(self.xg), torch.empty_like(self.xc)
         self.t = 0.0   # the scripted car's clock, advanced by `+= timestep` like the reference's (base.py:889)
         self.u = None
         # models = (A [B,6,6], B [B,6,2]): every race on its own model (crx_ilqr_solve_models_dev); A, B above are then unused
@@ -308,12 +346,10 @@ class IlqrRaces:
         return obs_s, obs_e, lap_off
 
     def step(self):
+        """One control step of every race: predictions (torch ops), then ilqr_solve_dev, plant_step_wrap_dev."""
         obs_s, obs_e, lap_off = self.predictions()
         torch_api.ilqr_solve_dev(self.desc, self.xc, self.xt, obs_s, obs_e, lap_off, self.n_obs, ws=self.ws, models=self.models)
-        torch_api.plant_step_wrap_dev(self.pdesc, self.tab, self.xg, self.xc, self.ws.U, 2 * self.N, self.xg_next, self.xc_next,
-                                      self.laps, noise_z=self.noise.draw(self.batch))
-        self.xg, self.xg_next = self.xg_next, self.xg
-        self.xc, self.xc_next = self.xc_next, self.xc
+        self._advance(self.ws.U, 2 * self.N)
         self.u = self.ws.U[:, 0, :]
         self.t += self.timestep
 
@@ -325,30 +361,26 @@ def ilqr_races(track_table, lap_length, A, B, xcurv0, xglob0, car_s0, car_v, car
     iters [T,B], laps [B]."""
     r = IlqrRaces(track_table, lap_length, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, vt=vt, eyt=eyt, N=N, max_iter=max_iter,
                   timestep=timestep, device=device, models=models)
-    log_x, log_u, log_st, log_it = [r.xc.clone()], [], [], []
-    for k in range(steps):
-        r.step()
-        if (k + 1) % log_every == 0:
-            log_x.append(r.xc.clone())
-            log_u.append(r.u.clone())
-            log_st.append(r.ws.status.clone())
-            log_it.append(r.ws.iters.clone())
-    return dict(xcurv=torch.stack(log_x).cpu().numpy(), u=torch.stack(log_u).cpu().numpy(),
-                status=torch.stack(log_st).cpu().numpy(), iters=torch.stack(log_it).cpu().numpy(), laps=r.laps.cpu().numpy())
+    logs = _run_and_log(r.step, steps, log_every,
+                        dict(xcurv=lambda: r.xc, u=lambda: r.u, status=lambda: r.ws.status, iters=lambda: r.ws.iters))
+    return dict(logs, laps=r.laps.cpu().numpy())
 
 
-class LmpcLaps:
+class LmpcLaps(_Plant):
     """B learning-MPC laps at once, device-resident (SURVEY.md section 8f rows 1 + 4): the lap of the reference's racing
     game in which LMPCRacingGame drives alone (tests/auto_racing_game_test.py:60-66 -> utils/base.py:468-517), with the
     race index as the batch dimension.  Per control step and without touching the host:
 
         crx_lmpc_prep_dev      N stage models from the two previous laps + safe-set selection   (estimate_ABC, control.lmpc :625-639)
         crx_lmpc_solve_dev     the learning-MPC QP                                               (control.lmpc :640-730)
+        crx_game_commit_dev    the applied input, u_old and the step counter of add_point
         crx_lmpc_addpoint_dev  the applied (x, u) extends the previous lap's safe set            (add_point)
         crx_plant_step_wrap_dev  plant + lap bookkeeping                                         (forward_dynamics, update_memory)
+        crx_game_log_dev       the new state and the applied input join the race's lap log       (update_memory)
         crx_lmpc_addtraj_dev   a race that crossed the line: its logged lap becomes a safe-set lap (add_trajectory)
 
-    Five libcrx launches per step; torch owns the memory, copies u_old and appends the applied (x, u) to the race's lap log.
+    Seven libcrx launches per step, in this order; torch only owns the memory.  _plan() is the first two and _apply() is
+    add_point + plant: GameLaps builds its step from the same two, so the learning-MPC step is written once.
     Every race carries its own safe set (ss_xcurv [B, L, P, 6], u_ss [B, L, P, 2], qfun [B, L, P], time_ss [B, L]: the
     reference's arrays stored lap-major) and runs lap after lap: the lap hand-over (the reference's test script calls
     add_trajectory between laps, tests/auto_racing_game_test.py) happens per race on the device, until the race's L laps
@@ -356,33 +388,24 @@ class LmpcLaps:
 
     def __init__(self, track_table, lap_length, track_width, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
                  N=12, timestep=0.1, device=None, noise_seed=None):
-        dev = torch.device(device if device is not None else "cuda")
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device)
         f64 = dict(dtype=torch.float64, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
-        self.noise = _Noise(noise_seed, dev)
-
-        def t(a, kw):
-            return torch.as_tensor(np.ascontiguousarray(a), **kw).clone()
-
-        self.ss, self.us, self.qf = t(ss_xcurv, f64), t(u_ss, f64), t(qfun, f64)
-        self.time_ss, self.it = t(time_ss, i32), t(it, i32)
+        self.ss, self.us, self.qf = (_dev(a, dev, clone=True) for a in (ss_xcurv, u_ss, qfun))
+        self.time_ss, self.it = (_dev(a, dev, torch.int32, clone=True) for a in (time_ss, it))
         Bn, L, P, _ = self.ss.shape
-        self.batch, self.N, self.lap_length, self.timestep = Bn, N, lap_length, timestep
-        self.xc, self.xg = t(xcurv0, f64), t(xglob0, f64)
-        self.lin_points, self.lin_input = t(lin_points, f64), t(lin_input, f64)
-        self.tab = t(track_table, f64)
-        self.pdesc = abi.lmpcprep_desc(N, P, L, self.tab.shape[0], timestep, lap_length)
+        self.N = N
+        self.lin_points, self.lin_input = _dev(lin_points, dev, clone=True), _dev(lin_input, dev, clone=True)
+        self.pdesc = abi.lmpcprep_desc(N, P, L, self.tab.shape[0], timestep, lap_length)   # the prep's descriptor; the plant's is self.plant
         self.desc = abi.lmpc_desc(N=N, n_ss_max=self.pdesc.n_ss_per_lap * self.pdesc.n_ss_laps, ey_max=track_width)
-        self.plant = abi.plant_desc(self.tab.shape[0], lap_length, timestep=timestep)
         self.pws = torch_api.LmpcPrepWorkspace(self.pdesc, Bn, dev)
         self.ws = torch_api.LmpcWorkspace(self.desc, Bn, dev)
         self.n_ss = torch.full((Bn,), self.desc.n_ss_max, **i32)
         self.u_old = torch.zeros((Bn, 2), **f64)
         self.u_prev = torch.zeros((Bn, 2), **f64)     # u_old of the last QP launch (bench.py re-issues that launch to time it)
         self.step_no = torch.zeros((Bn,), **i32)
-        self.laps = torch.zeros((Bn,), **i32)
-        self.xg_next, self.xc_next = torch.empty_like(self.xg), torch.empty_like(self.xc)
-        self.k = 0
+        self.k = 0                     # steps taken by step(); a GameLaps driving this object leaves it at 0
+        self._dispatch_of = self       # the object whose `dispatch` orders the QP launch (_order): GameLaps puts itself here
         # the running lap as the simulator logs it (update_memory): states incl. the crossing one, inputs
         self.log_x = torch.zeros((Bn, P, 6), **f64)
         self.log_u = torch.zeros((Bn, P, 2), **f64)
@@ -417,25 +440,33 @@ class LmpcLaps:
         torch_api.lmpc_addtraj_dev(self.pdesc, crossed, self.log_x, self.log_u, self.n_log, self.ss, self.us, self.qf, self.time_ss, self.it,
                                    self.step_no, self.xc, self.traj_status)
 
+    def _plan(self, lin_points, lin_input, from_plan, active=None):
+        """The stage models and safe-set points around (lin_points, lin_input) -- from_plan: a previous plan, shifted by one stage
+        inside the kernel (control.py:726-728) -- and the learning-MPC QP on them: lmpc_prep_dev, lmpc_solve_dev, with one
+        longest_first between them under that dispatch.  active: int32 mask [B] for both launches."""
+        torch_api.lmpc_prep_dev(self.pdesc, self.ss, self.us, self.qf, self.time_ss, self.it, self.xc, lin_points, lin_input, self.tab,
+                                from_plan, ws=self.pws, active=active)
+        torch_api.lmpc_solve_dev(self.desc, self.xc, self.u_old, self.pws.A, self.pws.B, self.pws.C, self.pws.ss, self.pws.qfun, self.n_ss,
+                                 ws=self.ws, active=active, order=_order(self._dispatch_of, self.ws.iters, active))
+
+    def _apply(self, u, u_stride, addpoint_step):
+        """The applied (x, u) joins the safe set at addpoint_step [B] (negative: not for this race) and the plant moves:
+        lmpc_addpoint_dev, plant_step_wrap_dev."""
+        torch_api.lmpc_addpoint_dev(self.pdesc, self.ss, self.us, self.time_ss, self.it, addpoint_step, self.xc, u, u_stride)
+        self._advance(u, u_stride)
+
     def step(self, torch_glue=False):
-        """One control step of every race: six libcrx launches (regression, QP, commit, add_point, plant, log) + the lap hand-over.
+        """One control step of every race, seven libcrx launches: lmpc_prep_dev, lmpc_solve_dev, game_commit_dev, lmpc_addpoint_dev,
+        plant_step_wrap_dev, game_log_dev, lmpc_addtraj_dev (the lap hand-over).
         torch_glue = True: the bookkeeping as element-wise torch ops instead of crx_game_commit_dev / crx_game_log_dev (round 2's
-        formulation, kept for the tests: both must produce the same bits)."""
+        formulation, kept for the tests: both must produce the same bits), which leaves five."""
         N = self.N
         if self.k == 0:     # first call of the lap: linearisation points handed over by the previous controller (utils/base.py:651-653)
-            torch_api.lmpc_prep_dev(self.pdesc, self.ss, self.us, self.qf, self.time_ss, self.it, self.xc, self.lin_points, self.lin_input,
-                                    self.tab, False, ws=self.pws)
-        else:               # afterwards: the previous plan, shifted by one stage inside the kernel (control.py:726-728)
-            torch_api.lmpc_prep_dev(self.pdesc, self.ss, self.us, self.qf, self.time_ss, self.it, self.xc, self.ws.X, self.ws.U,
-                                    self.tab, True, ws=self.pws)
-        torch_api.lmpc_solve_dev(self.desc, self.xc, self.u_old, self.pws.A, self.pws.B, self.pws.C, self.pws.ss, self.pws.qfun, self.n_ss,
-                                 ws=self.ws, order=_order(self, self.ws.iters))
+            self._plan(self.lin_points, self.lin_input, False)
+        else:               # afterwards: the previous plan
+            self._plan(self.ws.X, self.ws.U, True)
         if torch_glue:
-            torch_api.lmpc_addpoint_dev(self.pdesc, self.ss, self.us, self.time_ss, self.it, self.step_no, self.xc, self.ws.U, 2 * N)
-            torch_api.plant_step_wrap_dev(self.plant, self.tab, self.xg, self.xc, self.ws.U, 2 * N, self.xg_next, self.xc_next, self.laps,
-                                          noise_z=self.noise.draw(self.batch))
-            self.xg, self.xg_next = self.xg_next, self.xg
-            self.xc, self.xc_next = self.xc_next, self.xc
+            self._apply(self.ws.U, 2 * N, self.step_no)
             self.u_prev.copy_(self.u_old)
             self.u_old.copy_(self.ws.U[:, 0, :])
             self.u.copy_(self.u_old)
@@ -446,11 +477,7 @@ class LmpcLaps:
         # applied input, plan hand-over (u_old; lin_points / lin_input are the shifted plan), step counter: one launch
         torch_api.game_commit_dev(N, N, None, None, self.ws.X, self.ws.U, None, self.u, self.u_old, self.u_prev, self.lin_points, self.lin_input,
                                   self.step_no, self.addpoint_step, None)
-        torch_api.lmpc_addpoint_dev(self.pdesc, self.ss, self.us, self.time_ss, self.it, self.addpoint_step, self.xc, self.u, 2)
-        torch_api.plant_step_wrap_dev(self.plant, self.tab, self.xg, self.xc, self.u, 2, self.xg_next, self.xc_next, self.laps,
-                                      noise_z=self.noise.draw(self.batch))
-        self.xg, self.xg_next = self.xg_next, self.xg
-        self.xc, self.xc_next = self.xc_next, self.xc
+        self._apply(self.u, 2, self.addpoint_step)
         self.k += 1
         self.log_and_handover(self.u)
 
@@ -462,15 +489,9 @@ def lmpc_laps(track_table, lap_length, track_width, ss_xcurv, u_ss, qfun, time_s
     traj_status [B] (lap hand-over: 1 = safe-set storage full)."""
     r = LmpcLaps(track_table, lap_length, track_width, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input, N=N,
                  timestep=timestep, device=device, noise_seed=noise_seed)
-    log_x, log_u, log_st, log_ps = [r.xc.clone()], [], [], []
-    for _ in range(steps):
-        r.step()
-        log_x.append(r.xc.clone())
-        log_u.append(r.u_old.clone())
-        log_st.append(r.ws.status.clone())
-        log_ps.append(r.pws.status.clone())
-    return dict(xcurv=torch.stack(log_x).cpu().numpy(), u=torch.stack(log_u).cpu().numpy(), status=torch.stack(log_st).cpu().numpy(),
-                prep_status=torch.stack(log_ps).cpu().numpy(), laps=r.laps.cpu().numpy(),
+    logs = _run_and_log(r.step, steps, 1, dict(xcurv=lambda: r.xc, u=lambda: r.u_old, status=lambda: r.ws.status,
+                                               prep_status=lambda: r.pws.status))
+    return dict(logs, laps=r.laps.cpu().numpy(),
                 traj_status=r.traj_status.cpu().numpy())   # 1: the race's n_laps of safe-set storage were full at its last hand-over
 
 
@@ -494,7 +515,8 @@ class GameLaps:
     MASKED launches (crx_*_masked_dev): the wavefront of a race that is in the other branch returns at once -- the region
     QPs of the planner included; the cheap kernels around them (scene, prep, selection, tracking prep) run for every race.  The applied input, the
     plan hand-over (u_old, linearisation points), add_point and the direction flag are taken from the branch the race is
-    in; no host round trip, no compaction.  Nine libcrx launches per step.
+    in; no host round trip, no compaction.  Fourteen libcrx launches per step (thirteen with planner = "path"), listed at step();
+    the learning-MPC ones are LmpcLaps._plan / _apply / log_and_handover of `lm`, which also holds the plant (lm.xc, lm.xc_next, ...).
 
     planner = "path" (LMPCRacingGame(path_planner=True), planning/overtake_path_planner.py): the overtake branch becomes
         crx_path_plan_dev          obstacle rows, control points, samples, side rows; the region QPs; arg-min + target (include/crx.h P1-P8)
@@ -513,11 +535,12 @@ class GameLaps:
         self.lm = LmpcLaps(track_table, lap_length, track_width, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
                            N=N, timestep=timestep, device=device, noise_seed=noise_seed)
         lm = self.lm
-        dev = lm.xc.device
+        lm._dispatch_of = self         # bench.py sets `dispatch` on the game
+        dev = lm.device
         f64 = dict(dtype=torch.float64, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         Bn = lm.batch
-        self.s0, self.v, self.ey = (torch.as_tensor(np.ascontiguousarray(a), **f64) for a in (car_s0, car_v, car_ey))
+        self.s0, self.v, self.ey = (_dev(a, dev) for a in (car_s0, car_v, car_ey))
         VA = self.s0.shape[1]
         V = min(VA, abi.CRX_MAX_VEH)
         self.Np, self.V, self.VA, self.L = N_plan, V, VA, lap_length
@@ -528,8 +551,7 @@ class GameLaps:
         self.plan, self.sel = abi.planner_desc(N_plan, A, B), abi.select_desc(N_plan, V, lap_length)
         self.track_desc = abi.cbf_desc(N_plan, V, A, B, Q=(10.0, 0, 0, 5.0, 0, 50.0), R=(0.1, 0.1), alpha=0.6, margin=0.15,
                                        ey_max=track_width, per_stage_target=True, l_sum=0.4, w_sum=0.2)
-        self.opt_s = torch.as_tensor(np.ascontiguousarray(opt_xcurv[:, 4]), **f64)
-        self.opt_ey = torch.as_tensor(np.ascontiguousarray(opt_xcurv[:, 5]), **f64)
+        self.opt_s, self.opt_ey = _dev(opt_xcurv[:, 4], dev), _dev(opt_xcurv[:, 5], dev)
         self.sws = torch_api.SceneWorkspace(self.scene, Bn, dev)
         self.pws = torch_api.PrepWorkspace(self.prep, Bn, dev)
         self.qws = torch_api.PlannerWorkspace(self.plan, Bn * (V + 1), dev)
@@ -539,7 +561,7 @@ class GameLaps:
         if planner == "path":          # LMPCRacingGame(path_planner=True): alpha = racing_game_param.alpha (utils/base.py:379-408)
             self.pathprep = abi.pathprep_desc(N_plan, V, VA, opt_xcurv.shape[0], track_width, lap_length)
             self.pathqp = abi.path_desc(N_plan, alpha)
-            self.opt_vx = torch.as_tensor(np.ascontiguousarray(opt_xcurv[:, 0]), **f64)
+            self.opt_vx = _dev(opt_xcurv[:, 0], dev)
             self.ppws = torch_api.PathPlanWorkspace(self.pathprep, Bn, dev)
             self.ppws.target.zero_()   # (a race that has never planned: its rows are read by the tracking prep, whose NLP is masked out)
             self.flag = self.ppws.flag
@@ -574,8 +596,11 @@ class GameLaps:
         self.t = 0.0
 
     def step(self):
-        """One control step of every race: thirteen libcrx launches (traffic, scene, masks, prep, plan = QPs + selection, track
-        prep, tracking NLP, regression, learning-MPC QP, commit, add_point, plant, log) + the lap hand-over."""
+        """One control step of every race, fourteen libcrx launches: game_traffic_dev, planner_scene_dev, game_masks_dev; the
+        overtake branch planner_prep_dev, planner_plan_dev (planner = "path": path_plan_dev for the two), track_prep_dev,
+        cbf_solve_dev; the learning-MPC branch lmpc_prep_dev, lmpc_solve_dev; game_commit_dev, lmpc_addpoint_dev,
+        plant_step_wrap_dev, game_log_dev, lmpc_addtraj_dev (the lap hand-over).  lm.k stays 0: the game plans from its own
+        linearisation points, which the commit keeps."""
         lm, L, N = self.lm, self.L, self.lm.N
         torch_api.game_traffic_dev(self.Np, L, self.t, lm.timestep, self.s0, self.v, self.ey, self.veh, self.pred_s, self.pred_e)
         torch_api.planner_scene_dev(self.scene, lm.xc, self.n_all, self.veh, self.pred_s, self.pred_e, ws=self.sws)
@@ -584,10 +609,7 @@ class GameLaps:
         self._branches(self.m_ot, self.m_lm, overlap=self.overlap)
         torch_api.game_commit_dev(N, self.Np, self.m_ot, self.tws.U, lm.ws.X, lm.ws.U, self.flag, self.u, lm.u_old, lm.u_prev,
                                   self.lin_points, self.lin_input, lm.step_no, lm.addpoint_step, self.old_flag)
-        torch_api.lmpc_addpoint_dev(lm.pdesc, lm.ss, lm.us, lm.time_ss, lm.it, lm.addpoint_step, lm.xc, self.u, 2)
-        torch_api.plant_step_wrap_dev(lm.plant, lm.tab, lm.xg, lm.xc, self.u, 2, lm.xg_next, lm.xc_next, lm.laps, noise_z=lm.noise.draw(lm.batch))
-        lm.xg, lm.xg_next = lm.xg_next, lm.xg
-        lm.xc, lm.xc_next = lm.xc_next, lm.xc
+        lm._apply(self.u, 2, lm.addpoint_step)
         self.t += lm.timestep
         lm.log_and_handover(self.u)
 
@@ -615,31 +637,25 @@ class GameLaps:
             self._branch_lmpc(m_lm)
 
     def _branch_overtake(self, m_ot):
-        lm, L = self.lm, self.L
-        if self.planner == "path":   # scene -> path plan (prep, region QPs, selection + target) -> tracking prep on the target -> tracking NLP
-            sw, pw = self.sws, self.ppws
-            torch_api.path_plan_dev(self.pathprep, self.pathqp, lm.xc, lm.xc, sw.n_veh, sw.order, self.veh, sw.max_dv, sw.obs_ey, self.opt_s,
-                                    self.opt_ey, self.opt_vx, ws=pw, active=m_ot)
-            torch_api.track_prep_dev(self.Np, self.V, L, lm.xc, sw.n_veh, sw.obs_s, sw.obs_ey, pw.target, self.xt, self.obs_s, self.obs_e,
-                                     self.lap_off, self.n_obs)
-            torch_api.cbf_solve_dev(self.track_desc, lm.xc, self.xt, self.obs_s, self.obs_e, self.lap_off, self.n_obs, ws=self.tws, active=m_ot,
-                                    order=_order(self, self.tws.iters, m_ot), models=self.track_models)
-            return
-        torch_api.planner_prep_dev(self.prep, lm.xc, lm.xc, self.sws.n_veh, self.sws.veh_info, self.sws.max_dv, self.sws.obs_s, self.sws.obs_ey,
-                                   self.opt_s, self.opt_ey, ws=self.pws)
-        torch_api.planner_plan_dev(self.plan, self.sel, self.pws.x0, self.pws.bez_s, self.pws.bez_ey, self.pws.ey_lb, self.pws.ey_ub,
-                                   self.sws.n_veh, self.sws.obs_s, self.sws.obs_ey, self.old_flag, self.qws, self.selws, active=m_ot, models=self.plan_models)
-        torch_api.track_prep_dev(self.Np, self.V, L, lm.xc, self.sws.n_veh, self.sws.obs_s, self.sws.obs_ey, self.selws.best_X, self.xt,
-                                 self.obs_s, self.obs_e, self.lap_off, self.n_obs)
-        torch_api.cbf_solve_dev(self.track_desc, lm.xc, self.xt, self.obs_s, self.obs_e, self.lap_off, self.n_obs, ws=self.tws, active=m_ot,
+        """The scene's planner produces the target trajectory; the tracking prep and the tracking NLP on it are the same for both."""
+        xc, sw = self.lm.xc, self.sws
+        if self.planner == "path":   # one launch: prep, region QPs, selection + target
+            torch_api.path_plan_dev(self.pathprep, self.pathqp, xc, xc, sw.n_veh, sw.order, self.veh, sw.max_dv, sw.obs_ey, self.opt_s,
+                                    self.opt_ey, self.opt_vx, ws=self.ppws, active=m_ot)
+            target = self.ppws.target
+        else:
+            torch_api.planner_prep_dev(self.prep, xc, xc, sw.n_veh, sw.veh_info, sw.max_dv, sw.obs_s, sw.obs_ey, self.opt_s, self.opt_ey,
+                                       ws=self.pws)
+            torch_api.planner_plan_dev(self.plan, self.sel, self.pws.x0, self.pws.bez_s, self.pws.bez_ey, self.pws.ey_lb, self.pws.ey_ub,
+                                       sw.n_veh, sw.obs_s, sw.obs_ey, self.old_flag, self.qws, self.selws, active=m_ot, models=self.plan_models)
+            target = self.selws.best_X
+        torch_api.track_prep_dev(self.Np, self.V, self.L, xc, sw.n_veh, sw.obs_s, sw.obs_ey, target, self.xt, self.obs_s, self.obs_e,
+                                 self.lap_off, self.n_obs)
+        torch_api.cbf_solve_dev(self.track_desc, xc, self.xt, self.obs_s, self.obs_e, self.lap_off, self.n_obs, ws=self.tws, active=m_ot,
                                 order=_order(self, self.tws.iters, m_ot), models=self.track_models)
 
     def _branch_lmpc(self, m_lm):
-        lm = self.lm
-        torch_api.lmpc_prep_dev(lm.pdesc, lm.ss, lm.us, lm.qf, lm.time_ss, lm.it, lm.xc, self.lin_points, self.lin_input, lm.tab, False, ws=lm.pws,
-                                active=m_lm)
-        torch_api.lmpc_solve_dev(lm.desc, lm.xc, lm.u_old, lm.pws.A, lm.pws.B, lm.pws.C, lm.pws.ss, lm.pws.qfun, lm.n_ss, ws=lm.ws, active=m_lm,
-                                 order=_order(self, lm.ws.iters, m_lm))
+        self.lm._plan(self.lin_points, self.lin_input, False, active=m_lm)
 
     def step_torch(self):
         """The same control step with the bookkeeping written as element-wise torch ops (round 2's formulation, ~40 small launches;
@@ -660,7 +676,7 @@ class GameLaps:
         # ---- the branch each race is in
         ot = self.overtake
         self.u.copy_(torch.where(ot[:, None], self.tws.U[:, 0, :], lm.ws.U[:, 0, :]))
-        torch_api.lmpc_addpoint_dev(lm.pdesc, lm.ss, lm.us, lm.time_ss, lm.it, torch.where(ot, self.neg, lm.step_no), lm.xc, self.u, 2)
+        addpoint_step = torch.where(ot, self.neg, lm.step_no)     # add_point's step: the counter before it advances below
         lm.u_prev.copy_(lm.u_old)
         lm.u_old.copy_(torch.where(ot[:, None], lm.u_old, lm.ws.U[:, 0, :]))
         X, U = lm.ws.X, lm.ws.U
@@ -668,9 +684,7 @@ class GameLaps:
         self.lin_input.copy_(torch.where(ot[:, None, None], self.lin_input, torch.cat((U[:, 1:], U[:, -1:]), dim=1)))
         lm.step_no += (~ot).to(torch.int32)
         self.old_flag.copy_(torch.where(ot, self.flag, torch.full_like(self.old_flag, -1)))
-        torch_api.plant_step_wrap_dev(lm.plant, lm.tab, lm.xg, lm.xc, self.u, 2, lm.xg_next, lm.xc_next, lm.laps, noise_z=lm.noise.draw(lm.batch))
-        lm.xg, lm.xg_next = lm.xg_next, lm.xg
-        lm.xc, lm.xc_next = lm.xc_next, lm.xc
+        lm._apply(self.u, 2, addpoint_step)
         self.t += lm.timestep
         lm.log_and_handover_torch(self.u)
 
@@ -682,17 +696,14 @@ def game_laps(track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u
     overtake [steps, B] (which branch), flag [steps, B] (direction flag, -1 in the LMPC branch), cars_s [steps, B, V], laps [B]."""
     r = GameLaps(track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
                  car_s0, car_v, car_ey, device=device, noise_seed=noise_seed, models=models, planner=planner, alpha=alpha)
-    lx, lu, lo, lf, lc = [r.lm.xc.clone()], [], [], [], []
-    for _ in range(steps):
-        lc.append((r.v * r.t + r.s0).clone())
-        r.step()
-        lx.append(r.lm.xc.clone()); lu.append(r.u.clone()); lo.append(r.overtake.clone().bool()); lf.append(r.old_flag.clone())
-    return dict(xcurv=torch.stack(lx).cpu().numpy(), u=torch.stack(lu).cpu().numpy(), overtake=torch.stack(lo).cpu().numpy(),
-                flag=torch.stack(lf).cpu().numpy(), cars_s=torch.stack(lc).cpu().numpy(), laps=r.lm.laps.cpu().numpy(),
-                traj_status=r.lm.traj_status.cpu().numpy(), scene_overflow=r.overflow_seen.cpu().numpy())
+    logs = _run_and_log(r.step, steps, 1, dict(xcurv=lambda: r.lm.xc, u=lambda: r.u, overtake=lambda: r.overtake.bool(),
+                                               flag=lambda: r.old_flag, cars_s=lambda: r.v * r.t + r.s0),
+                        before=("cars_s",))    # where the scripted cars are when the step plans
+    return dict(logs, laps=r.lm.laps.cpu().numpy(), traj_status=r.lm.traj_status.cpu().numpy(),
+                scene_overflow=r.overflow_seen.cpu().numpy())
 
 
-class PidLaps:
+class PidLaps(_Plant):
     """B copies of the reference's identification experiment (car_racing/tests/system_identification_test.py: one car under
     PIDTracking on its own, logged for `steps` control steps), device-resident, then identified without leaving the device.
     Per control step: ONE crx_plant_step_noise_dev (with the lap wrap of update_memory, base.py:795-819) and ONE crx_pid_log_dev
@@ -703,37 +714,26 @@ class PidLaps:
 
     def __init__(self, track_table, lap_length, xcurv0, xglob0, steps, vt=0.5, eyt=0.0, timestep=0.1, noise_z=None,
                  noise_seed=None, device=None):
-        dev = torch.device(device if device is not None else "cuda")
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device)
         f64 = dict(dtype=torch.float64, device=dev)
-        self.xc = torch.as_tensor(np.ascontiguousarray(xcurv0), **f64).clone()
-        self.xg = torch.as_tensor(np.ascontiguousarray(xglob0), **f64).clone()
-        Bn, T = self.xc.shape[0], int(steps)
-        self.batch, self.steps, self.device = Bn, T, dev
-        self.vt = torch.as_tensor(np.broadcast_to(np.asarray(vt, dtype=float), (Bn,)).copy(), **f64)
-        self.eyt = torch.as_tensor(np.broadcast_to(np.asarray(eyt, dtype=float), (Bn,)).copy(), **f64)
-        self.tab = torch.as_tensor(np.ascontiguousarray(track_table), **f64)
-        self.pdesc = abi.plant_desc(self.tab.shape[0], lap_length, timestep=timestep)
+        Bn, T = self.batch, int(steps)
+        self.steps = T
+        self.vt, self.eyt = _per_race(vt, Bn, dev), _per_race(eyt, Bn, dev)
         self.noise_z = None
         if noise_z is not None:
-            self.noise_z = torch.as_tensor(np.ascontiguousarray(noise_z), **f64) if not torch.is_tensor(noise_z) else noise_z.to(**f64)
+            self.noise_z = noise_z.to(**f64) if torch.is_tensor(noise_z) else _dev(noise_z, dev)
             if tuple(self.noise_z.shape) != (T, Bn, 3):
                 raise ValueError("noise_z: expected shape %s, got %s" % ((T, Bn, 3), tuple(self.noise_z.shape)))
-        self.noise = _Noise(noise_seed, dev)
         self.x_log = torch.zeros((Bn, T, 6), **f64)
         self.u_log = torch.zeros((Bn, T, 2), **f64)
-        self.laps = torch.zeros(Bn, dtype=torch.int32, device=dev)
         self.u, self.u_next = torch.zeros((Bn, 2), **f64), torch.zeros((Bn, 2), **f64)
-        self.xg_next, self.xc_next = torch.empty_like(self.xg), torch.empty_like(self.xc)
         self.k = 0
         torch_api.pid_log_dev(T, -1, self.vt, self.eyt, self.xc, None, self.u, self.x_log, self.u_log)
 
     def step(self):
+        """One control step of every car: plant_step_wrap_dev, pid_log_dev."""
         k = self.k
-        z = self.noise_z[k] if self.noise_z is not None else self.noise.draw(self.batch)
-        torch_api.plant_step_wrap_dev(self.pdesc, self.tab, self.xg, self.xc, self.u, 2, self.xg_next, self.xc_next, self.laps,
-                                      noise_z=z)
-        self.xg, self.xg_next = self.xg_next, self.xg
-        self.xc, self.xc_next = self.xc_next, self.xc
+        self._advance(self.u, 2, noise_z=None if self.noise_z is None else self.noise_z[k])
         torch_api.pid_log_dev(self.steps, k, self.vt, self.eyt, self.xc, self.u, self.u_next if k + 1 < self.steps else None,
                               self.x_log, self.u_log)
         self.u, self.u_next = self.u_next, self.u
@@ -759,7 +759,7 @@ def pid_laps(track_table, lap_length, xcurv0, xglob0, steps, vt=0.5, eyt=0.0, ti
                    noise_seed=noise_seed, device=device).run()
 
 
-class LqrLaps:
+class LqrLaps(_Plant):
     """B cars under the reference's LQR tracking controller (car_racing/tests/control_test.py --ctrl-policy lqr: one car under
     LQRTracking on its own), each on its own LTI model, device-resident.  The gain depends on the model only: ONE
     crx_lqr_design_dev in the constructor, then per control step ONE crx_lqr_step_dev (u = -K (x - xt)) and ONE
@@ -769,32 +769,21 @@ class LqrLaps:
 
     def __init__(self, track_table, lap_length, xcurv0, xglob0, A, B, Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]), R=np.diag([0.1, 0.1]),
                  vt=0.8, eyt=0.0, max_iter=50, eps=0.01, timestep=0.1, device=None, noise_seed=None):
-        dev = torch.device(device if device is not None else "cuda")
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device)
         f64 = dict(dtype=torch.float64, device=dev)
-        self.noise = _Noise(noise_seed, dev)
-        self.xc = torch.as_tensor(np.ascontiguousarray(xcurv0), **f64).clone()
-        self.xg = torch.as_tensor(np.ascontiguousarray(xglob0), **f64).clone()
-        Bn = self.xc.shape[0]
-        self.batch, self.lap_length, self.timestep = Bn, lap_length, timestep
-        self.tab = torch.as_tensor(np.ascontiguousarray(track_table), **f64)
+        Bn = self.batch
         self.A, self.B = _models(A, B, Bn, dev)
         self.desc = abi.lqr_desc(Q=Q, R=R, max_iter=max_iter, eps=eps)
-        self.pdesc = abi.plant_desc(self.tab.shape[0], lap_length, timestep=timestep)
         self.xt = torch.zeros((Bn, 6), **f64)
-        self.xt[:, 0] = torch.as_tensor(np.broadcast_to(np.asarray(vt, dtype=float), (Bn,)).copy(), **f64)
-        self.xt[:, 5] = torch.as_tensor(np.broadcast_to(np.asarray(eyt, dtype=float), (Bn,)).copy(), **f64)
+        self.xt[:, 0], self.xt[:, 5] = _per_race(vt, Bn, dev), _per_race(eyt, Bn, dev)
         self.design = torch_api.lqr_design_dev(self.desc, self.A, self.B)
         self.K = self.design.K
         self.u = torch.zeros((Bn, 2), **f64)
-        self.laps = torch.zeros(Bn, dtype=torch.int32, device=dev)
-        self.xg_next, self.xc_next = torch.empty_like(self.xg), torch.empty_like(self.xc)
 
     def step(self):
+        """One control step of every car: lqr_step_dev, plant_step_wrap_dev."""
         torch_api.lqr_step_dev(self.K, self.xc, self.xt, self.u)
-        torch_api.plant_step_wrap_dev(self.pdesc, self.tab, self.xg, self.xc, self.u, 2, self.xg_next, self.xc_next, self.laps,
-                                      noise_z=self.noise.draw(self.batch))
-        self.xg, self.xg_next = self.xg_next, self.xg
-        self.xc, self.xc_next = self.xc_next, self.xc
+        self._advance(self.u, 2)
 
 
 def lqr_laps(track_table, lap_length, xcurv0, xglob0, steps, A, B, Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]), R=np.diag([0.1, 0.1]),
@@ -803,11 +792,6 @@ def lqr_laps(track_table, lap_length, xcurv0, xglob0, steps, A, B, Q=np.diag([10
     design_status [B], design_iters [B], laps [B]."""
     r = LqrLaps(track_table, lap_length, xcurv0, xglob0, A, B, Q=Q, R=R, vt=vt, eyt=eyt, max_iter=max_iter, eps=eps, timestep=timestep,
                 device=device, noise_seed=noise_seed)
-    log_x, log_u = [r.xc.clone()], []
-    for k in range(steps):
-        r.step()
-        if (k + 1) % log_every == 0:
-            log_x.append(r.xc.clone())
-            log_u.append(r.u.clone())
-    return dict(xcurv=torch.stack(log_x).cpu().numpy(), u=torch.stack(log_u).cpu().numpy(), K=r.K.cpu().numpy(),
+    logs = _run_and_log(r.step, steps, log_every, dict(xcurv=lambda: r.xc, u=lambda: r.u))
+    return dict(logs, K=r.K.cpu().numpy(),
                 design_status=r.design.status.cpu().numpy(), design_iters=r.design.iters.cpu().numpy(), laps=r.laps.cpu().numpy())

@@ -20,11 +20,27 @@
 //   region selection    planning/overtake_traj_planner.py:205-246
 //
 // Structure of this file: build parameters and the switches that are still open, (2) compile-time LDS layout (the wave primitives
-// live in crx_wave.h), (3) set-up of the canonical stage problem, (4) per-iteration phases, (5) the solver kernel, (6) selection
-// kernel, (7) launchers: ONE selector per translation unit from (obstacle slots, horizon, exponent) to the instantiation that
-// serves it, and the entry points as callables over it.  The file is compiled four times -- as it stands, and through
-// crx_kernels_obs.hip, crx_kernels_gen.hip and crx_kernels_spec.hip (CRX_TU_OBSTACLES, CRX_TU_GENERAL, CRX_TU_SPEC) -- section (7)
-// says which unit holds which instantiations.  Stage coordinates everywhere:  z_k = [x_k (6), sigma_k (NOBS), u_k (2),
+// live in crx_wave.h), (3) set-up of the canonical stage problem, (4) per-iteration phases, (5) the solver kernel, (7) what every
+// unit's launchers are made of: launching and querying one instantiation, the selectors from (obstacle slots, horizon, exponent) to
+// an instantiation, and the two entry-point bodies over a unit's selector and its successor.
+//
+// This file is a SOURCE, not a translation unit: it is never compiled on its own and does not know which unit includes it.  Seven
+// units include it (Makefile: one row each, `make recipe` prints source and flags); each says in its own text which instantiations
+// it holds (its select_inst), where a launch goes next, and what else lives in it:
+//   unit (object)                          instantiations                                               built with                next
+//   crx_kernels_plan.hip (crx_kernels.o)   <0, *> at the horizons of CRX_NFIX_LIST, both qp_method       PLAN_SCHED (max-ilp)      obs
+//                                          + crx_select_kernel, crx_debug_reduce_kernel, crx_solve_lds_bytes
+//   crx_kernels_obs.hip                    <1..3, *>, exponent 6, at the horizons of CRX_NFIX_LIST       OBS_SCHED (iterative-ilp) gen
+//   crx_kernels_gen.hip [r5]               everything else: run-time horizon / exponent, 4..6 slots      GEN_FLAGS, general build  --
+//   crx_kernels_spec.hip [r6]              the two two-wave kernels <1, 12, 6, {12, 10}, SPEC = 1>       OBS_SCHED                 -- (crx_api.hip routes there)
+//   crx_kernels_models_plan.hip            models: <0, 12, 0, {10, 12}> + the two reach kernels          PLAN_SCHED                models_obs
+//   crx_kernels_models_obs.hip             models: <1, 12, 6, {10, 12}>, <3, 20, 6, 20>                  OBS_SCHED                 models_gen
+//   crx_kernels_models_gen.hip             models: everything else                                       GEN_FLAGS, general build  --
+// and crx_kernels_one.hip is ONE instantiation compiled alone (tools/kernel_resources.py one, tools/asm_census.py).  All of them are built
+// with MachineLICM off.  A launch walks plan -> obs -> gen (models: 1 -> 2 -> 3) until a unit holds its instantiation.  Two parameters
+// of the including unit change kernel code: CRX_TU_GENERAL (the general build) and CRX_TU_MODELS (one LTI model per problem), below.
+//
+// Stage coordinates everywhere:  z_k = [x_k (6), sigma_k (NOBS), u_k (2),
 // sigma_{k+1} (NOBS)];  the iterate is stored as Z[k][NZ], the Newton step as dZ[k][NZ]
 // (sigma_{k+1} therefore appears twice, as an input of stage k and as a state of stage k+1; the
 // two copies are kept identical).
@@ -38,16 +54,29 @@
 #include "crx_num.h"
 #include "crx_ipm.h"
 
-// Preprocessor switches of this file.  Translation unit: CRX_TU_GENERAL, CRX_TU_OBSTACLES, CRX_TU_SPEC (set by the including unit).  Code generation
-// forms that the general unit and the canary builds of tools/variants.sh still exercise, because the compiler defect of DESIGN.md section 8 is open:
+// Preprocessor switches of this file.  Set by the including unit, because they change kernel code: CRX_TU_GENERAL, CRX_TU_MODELS.  Code generation
+// forms that the general build and the canary builds of tools/variants.sh still exercise, because the compiler defect of DESIGN.md section 8 is open:
 // CRX_OPAQUE_LANE, CRX_STATIC_LDS, CRX_SWEEP_MASK, CRX_SWEEP_LOCAL_LANE, CRX_ROWDPP (section (4)).  Residency / build parameters: CRX_PLANNER_WAVES,
-// CRX_OBS1_WAVES, CRX_GEN_WAVES, CRX_KERNEL_EXTRA_ATTR (section (5)), CRX_NFIX_LIST (section (7)).  Diagnostic builds: CRX_PHASE_CLOCKS,
-// CRX_PROBE_ONE.  The A/B switches whose verdict is in were folded into the code; HISTORY.md lists them with the record of each verdict.
+// CRX_OBS1_WAVES, CRX_GEN_WAVES, CRX_KERNEL_EXTRA_ATTR (section (5)), CRX_NFIX_LIST (section (7)).  Diagnostic builds: CRX_PHASE_CLOCKS.
+// The A/B switches whose verdict is in were folded into the code; HISTORY.md lists them with the record of each verdict.
 #ifndef CRX_TU_GENERAL
-#define CRX_TU_GENERAL 0   /* 1: crx_kernels_gen.hip -- the general instantiations, built conservatively (section (7)) */
+#define CRX_TU_GENERAL 0   /* 1: the general build (crx_kernels_gen.hip, crx_kernels_models_gen.hip): conservative knobs below, no LoadsFirst / CbfCarry forms */
 #endif
 #ifndef CRX_TU_MODELS
-#define CRX_TU_MODELS 0    /* 1..3: crx_kernels_models.hip -- the CBF NLP and the planner QP with one LTI model per problem (section (7)) */
+#define CRX_TU_MODELS 0    /* 1: crx_kernels_models_*.hip -- the CBF NLP and the planner QP with one LTI model per problem */
+#endif
+#if CRX_TU_GENERAL
+// What the general build gives up (crx_kernels_gen.hip has the reasons): no inline-assembly DPP, the lane index made opaque once per iteration in
+// every instantiation, no sweep-local lane.  Stated here once, so that the general unit and the general models unit cannot drift apart.
+#ifndef CRX_ROWDPP
+#define CRX_ROWDPP 0
+#endif
+#ifndef CRX_OPAQUE_LANE
+#define CRX_OPAQUE_LANE 2
+#endif
+#ifndef CRX_SWEEP_LOCAL_LANE
+#define CRX_SWEEP_LOCAL_LANE 0
+#endif
 #endif
 // what crx_solve_kernel takes by value.  The models units read A, B and the reach tables of problem b through the three pointers of the derived
 // struct, in set-up only (the model matrix M, crash_search, the slack bounds); every other unit compiles exactly what it compiled before
@@ -2811,59 +2840,9 @@ crx_solve_kernel(const crx_solve_params kp) {
     }
 }
 
-// The tuned instantiations are compiled in TWO units (Makefile): this file as it stands for the planner instantiations <0, *> and everything else
-// in it, and crx_kernels_obs.hip (CRX_TU_OBSTACLES) for the obstacle instantiations <1..3, *> alone -- with the machine scheduler's
-// iterative-ilp strategy, which is worth +3.7 % on BASELINE configs[1] (0.991 -> 0.956 ms per 256 NLPs) and +7 % on configs[3] to
-// the obstacle kernels and costs the planner kernels 1 % (HISTORY.md, round 3: max-ilp, max-memory-clause, iterative-minreg
-// and the occupancy / latency bias were measured beside it).  Same arithmetic either way: the schedule does not re-associate.
-#ifndef CRX_TU_OBSTACLES
 // ------------------------------------------------------------------------------------------------
-// (6) region selection (planning/overtake_traj_planner.py:205-246): one wave per scenario, lanes
-// over (side, stage) collision tests.
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(WAVE) crx_select_kernel(const crx_select_kparams sp) {
-    const int s = blockIdx.x, lane = threadIdx.x;
-    if (s >= sp.n_scen) return;
-    const int N = sp.N, V = sp.V, R = V + 1;
-    const int nv = min(max(sp.n_veh[s], 0), V);   // the *_dev entry points cannot validate device-resident counts: clamp
-    const double r2 = sp.veh_length * sp.veh_length + sp.veh_width * sp.veh_width;
-    double best_c = INFINITY;
-    int best = 0;
-    for (int r = 0; r < R; r++) {
-        double cst = INFINITY;
-        if (r <= nv) {
-            const double* Xr = sp.X + (((size_t)s * R + r) * (N + 1)) * 6;
-            double hits = 0.0;
-            for (int e = lane; e < 2 * (N + 1); e += WAVE) {
-                const int side = e / (N + 1), j = e - side * (N + 1);
-                const int v = side == 0 ? r - 1 : r;                                          // :213, :227
-                if (v < 0 || v >= nv) continue;
-                double os = sp.obs_s[((size_t)s * V + v) * (N + 1) + j];
-                os = wrap_above(os, sp.lap_length);                                             // :216-217
-                const double ds = Xr[6 * j + 4] - os;
-                const double de = Xr[6 * j + 5] - sp.obs_ey[((size_t)s * V + v) * (N + 1) + j];
-                if (!(ds * ds + de * de - r2 >= 0.0)) hits += 1.0;                            // :220-223
-            }
-            hits = wave_sum(hits);
-            cst = -sp.w_prog * (Xr[6 * N + 4] - Xr[4]) + sp.w_coll * hits;                    // :209
-            if (sp.old_flag[s] >= 0 && sp.old_flag[s] != r) cst += sp.w_switch;               // :238-243
-            if (cst < best_c) { best_c = cst; best = r; }                                     // first arg-min :244
-        }
-        if (lane == 0) sp.sel_cost[(size_t)s * R + r] = cst;
-    }
-    if (lane == 0) sp.flag[s] = best;
-    const double* Xb = sp.X + (((size_t)s * R + best) * (N + 1)) * 6;
-    for (int e = lane; e < (N + 1) * 6; e += WAVE) sp.best_X[(size_t)s * (N + 1) * 6 + e] = Xb[e];
-}
-
-#endif  // !CRX_TU_OBSTACLES
-
-#ifdef CRX_PROBE_ONE
-// tools/kernel_resources.py one NOBS NMAX DEG NFIX: ONE instantiation, compiled alone (seconds instead of minutes)
-template __global__ void crx_solve_kernel<CRX_PROBE_ONE>(const crx_solve_params);
-#else
-// ------------------------------------------------------------------------------------------------
-// (7) launchers (plain C++ linkage inside the library; the C ABI lives in crx_api.hip)
+// (7) what the units' launchers are made of (plain C++ linkage inside the library; the C ABI lives
+// in crx_api.hip).  Nothing below names a unit: the entry points themselves are in the unit files.
 // ------------------------------------------------------------------------------------------------
 template <int NOBS, int NMAX, int DEG = 0, int NFIX = 0, int SPEC = 0, int QPM = 0>
 static hipError_t launch_t(const crx_solve_params& kp, hipStream_t st) {
@@ -2903,15 +2882,10 @@ static int occ_t() {
     return n;
 }
 
-// WHICH instantiation serves a problem is decided once per translation unit, by select_inst(nobs_template, N, degree, f): it calls f with the
-// instantiation as a type, Inst<NOBS, NMAX, DEG, NFIX>, and returns false where the unit holds none for the problem.  Launching, the occupancy
-// query and the LDS figure are callables over that one selection, so what bench.py reports as resident is the kernel that runs.  The units:
-//   this file as it stands     the planner instantiations <0, *> at the horizons of CRX_NFIX_LIST, the selection kernel, the entry points
-//   crx_kernels_obs.hip        <1..3, *>, exponent 6, at the horizons of CRX_NFIX_LIST
-//   crx_kernels_gen.hip [r5]   everything else -- run-time horizon (NFIX = 0), run-time exponent (DEG = 0), the generic 4..6-obstacle ones -- built
-//                              conservatively: no inline-assembly DPP, nothing lane-derived hoisted out of the interior-point loop
-//   crx_kernels_spec.hip [r6]  the two two-wave kernels; crx_api.hip routes a launch there by itself
-// A launch walks main -> obstacle -> general unit until one holds its instantiation.
+// WHICH instantiation serves a problem is decided once per translation unit, by its Unit::select_inst(nobs_template, N, degree, f): it calls f with
+// the instantiation as a type, Inst<NOBS, NMAX, DEG, NFIX>, and returns false where the unit holds none for the problem.  Launching, the occupancy
+// query and the LDS figure are callables over that one selection, so what bench.py reports as resident is the kernel that runs.  The table of the
+// units is at the head of this file; the building blocks of their selectors follow.
 template <int NOBS, int NMAX, int DEG, int NFIX> struct Inst { static constexpr int nobs = NOBS, nmax = NMAX, deg = DEG, nfix = NFIX; };
 // layout class of a horizon: <= 12 -> 12; <= 20 with three obstacle slots -> 20 (the slim layout, four problems per CU); otherwise CRX_MAX_N
 constexpr int horizon_class(int nobs, int N) { return N <= 12 ? 12 : ((nobs == 3 && N <= 20) ? 20 : CRX_MAX_N); }
@@ -2921,9 +2895,6 @@ constexpr int horizon_class(int nobs, int N) { return N <= 12 ? 12 : ((nobs == 3
 // defaults: utils/base.py:281, :390), 12 (BASELINE configs[1], [2], [4]), 20 (configs[3]).  Layout class of a horizon: <= 12 -> 12; <= 20 with three
 // obstacle slots -> 20 (the slim layout, four problems per CU); otherwise CRX_MAX_N.  Budget per entry: one kernel per obstacle count (two for the
 // planner: crx_ipm_opts.qp_method), ~100 KB of code and 15 .. 40 s of build time each; registers / LDS as its layout class.
-#ifndef CRX_NFIX_LIST
-#define CRX_NFIX_LIST 10, 12, 20
-#endif
 #ifndef CRX_NFIX_LIST
 #define CRX_NFIX_LIST 10, 12, 20
 #endif
@@ -2958,156 +2929,34 @@ static bool select_general(int nobs_template, int N, int degree, F&& f) {
 // the queries (crx_solve_lds_bytes, crx_solve_resident_per_cu*) answer for the reference's exponent whatever the descriptor says, and for the
 // six-slot instantiations when asked about a slot count that has none
 static int query_slots(int nobs_template) { return nobs_template >= 0 && nobs_template <= 3 ? nobs_template : CRX_MAX_OBS; }
-
-hipError_t crx_launch_solve_obs(const crx_kparams& kp, int nobs_template, hipStream_t st);
-int crx_solve_resident_per_cu_obs(int N, int nobs_template);
-hipError_t crx_launch_solve_general(const crx_kparams& kp, int nobs_template, hipStream_t st);
-int crx_solve_resident_per_cu_general(int N, int nobs_template);
-
-#if defined(CRX_TU_SPEC)
-// [r6] crx_kernels_spec.hip: the two-wave (speculating) instantiations of the one-obstacle, degree-6 kernel at the tuned horizons 12 and 10 --
-// BASELINE configs[1] and the reference's default horizon -- and nothing else.  crx_api.hip routes a launch here when it leaves SIMDs idle.
-hipError_t crx_launch_solve_spec(const crx_kparams& kp, hipStream_t st) {
-    if (kp.batch == 0) return hipSuccess;
-    if (kp.degree != 6) return hipErrorInvalidValue;
-    if (kp.N == 12) return launch_t<1, 12, 6, 12, 1>(kp, st);
-    if (kp.N == 10) return launch_t<1, 12, 6, 10, 1>(kp, st);
-    return hipErrorInvalidValue;
-}
-#elif CRX_TU_MODELS
-// crx_kernels_models.hip: the CBF NLP with one LTI model per problem, compiled three times with the flags of the unit whose instantiations it
-// mirrors (Makefile).  1: zero obstacle slots at N = 10 / 12 (the mpc_lti form; the main unit's flags); 2: one slot at N = 10 / 12 and three at
-// N = 20 (the racing shapes; the obstacle unit's flags); 3: every other (N, slots, exponent) the shared launch accepts, on the general
-// instantiations, built as crx_kernels_gen.hip builds them.  A launch walks 1 -> 2 -> 3.  The planner region QP (mode 0, no obstacle slots) runs
-// the same instantiations -- the tuned <0, 12, 0, {10, 12}> of unit 1, any other horizon on unit 3 -- with model_reach holding its own table
-// (crx_planner_reach_kernel).  The two-wave kernels have no such twin.
-hipError_t crx_launch_solve_models_obs(const crx_kparams_models& kp, int nobs_template, hipStream_t st);
-hipError_t crx_launch_solve_models_general(const crx_kparams_models& kp, int nobs_template, hipStream_t st);
-#if CRX_TU_MODELS == 1
-#define CRX_UNIT(name) name##_models
-template <class F>
-static bool select_inst(int nobs_template, int N, int, F&& f) { return nobs_template == 0 && select_fixed<0, 0, 10, 12>(N, f); }
-static hipError_t next_unit_launch(const crx_kparams_models& kp, int nobs_template, hipStream_t st) { return crx_launch_solve_models_obs(kp, nobs_template, st); }
-#elif CRX_TU_MODELS == 2
-#define CRX_UNIT(name) name##_models_obs
-template <class F>
-static bool select_inst(int nobs_template, int N, int degree, F&& f) {
-    if (degree != 6) return false;
-    if (nobs_template == 1) return select_fixed<1, 6, 10, 12>(N, f);
-    if (nobs_template == 3) return select_fixed<3, 6, 20>(N, f);
-    return false;
-}
-static hipError_t next_unit_launch(const crx_kparams_models& kp, int nobs_template, hipStream_t st) { return crx_launch_solve_models_general(kp, nobs_template, st); }
-#else
-static_assert(CRX_TU_GENERAL, "the third models unit is built like the general unit");
-#define CRX_UNIT(name) name##_models_general
-template <class F>
-static bool select_inst(int nobs_template, int N, int degree, F&& f) { return select_general(nobs_template, N, degree, f); }
-static hipError_t next_unit_launch(const crx_kparams_models&, int, hipStream_t) { return hipErrorInvalidValue; }
-#endif
-hipError_t CRX_UNIT(crx_launch_solve)(const crx_kparams_models& kp, int nobs_template, hipStream_t st) {
-    if (kp.batch == 0) return hipSuccess;
-    if (kp.mode != 1 && !(kp.mode == 0 && nobs_template == 0)) return hipErrorInvalidValue;   // the planner QP has no obstacle slots
-    hipError_t e = hipSuccess;
-    if (select_inst(nobs_template, kp.N, kp.degree, [&](auto i) { e = launch_t<i.nobs, i.nmax, i.deg, i.nfix>(kp, st); })) return e;
-    return next_unit_launch(kp, nobs_template, st);
-}
-#else
-#if CRX_TU_GENERAL
-#define CRX_UNIT(name) name##_general
-template <class F>
-static bool select_inst(int nobs_template, int N, int degree, F&& f) { return select_general(nobs_template, N, degree, f); }
-static hipError_t next_unit_launch(const crx_kparams&, int, hipStream_t) { return hipErrorInvalidValue; }
-static int next_unit_resident(int, int) { return -1; }
-#elif defined(CRX_TU_OBSTACLES)
-#define CRX_UNIT(name) name##_obs
-template <class F>
-static bool select_inst(int nobs_template, int N, int degree, F&& f) {
-    if (degree != 6) return false;   // (other exponents, 2 / 4 / 8, take the general unit)
-    switch (nobs_template) {
-        case 1: return select_fixed<1, 6, CRX_NFIX_LIST>(N, f);
-        case 2: return select_fixed<2, 6, CRX_NFIX_LIST>(N, f);
-        case 3: return select_fixed<3, 6, CRX_NFIX_LIST>(N, f);
-        default: return false;
-    }
-}
-static hipError_t next_unit_launch(const crx_kparams& kp, int nobs_template, hipStream_t st) { return crx_launch_solve_general(kp, nobs_template, st); }
-static int next_unit_resident(int N, int nobs_template) { return crx_solve_resident_per_cu_general(N, nobs_template); }
-#else
-#define CRX_UNIT(name) name
-template <class F>
-static bool select_inst(int nobs_template, int N, int, F&& f) { return nobs_template == 0 && select_fixed<0, 0, CRX_NFIX_LIST>(N, f); }
-static hipError_t next_unit_launch(const crx_kparams& kp, int nobs_template, hipStream_t st) { return crx_launch_solve_obs(kp, nobs_template, st); }
-static int next_unit_resident(int N, int nobs_template) { return crx_solve_resident_per_cu_obs(N, nobs_template); }
-#endif
-
-hipError_t CRX_UNIT(crx_launch_solve)(const crx_kparams& kp, int nobs_template, hipStream_t st) {
-    if (kp.batch == 0) return hipSuccess;
-    hipError_t e = hipSuccess;
-    if (select_inst(nobs_template, kp.N, kp.degree, [&](auto i) { e = launch_t<i.nobs, i.nmax, i.deg, i.nfix>(kp, st); })) return e;
-    return next_unit_launch(kp, nobs_template, st);
-}
-int CRX_UNIT(crx_solve_resident_per_cu)(int N, int nobs_template) {
-    int n = 0;
-    if (select_inst(query_slots(nobs_template), N, 6, [&](auto i) { n = occ_t<i.nobs, i.nmax, i.deg, i.nfix>(); })) return n;
-    return next_unit_resident(N, nobs_template);
-}
-
-#ifndef CRX_TU_OBSTACLES
 // LDS bytes of the layout a problem runs in (every instantiation of a horizon class has the same)
-size_t crx_solve_lds_bytes(int N, int nobs_template) {
+static size_t layout_bytes(int N, int nobs_template) {
     size_t bytes = 0;
     select_general(query_slots(nobs_template), N, 6, [&](auto i) { bytes = Lay<i.nobs, i.nmax>::BYTES; });
     return bytes;
 }
 
-hipError_t crx_launch_select(const crx_select_kparams& sp, hipStream_t st) {
-    if (sp.n_scen == 0) return hipSuccess;
-    hipLaunchKernelGGL(crx_select_kernel, dim3(sp.n_scen), dim3(WAVE), 0, st, sp);
-    return hipGetLastError();
-}
+// the links of the two walks (crx_launch_solve and crx_launch_solve_models head them: crx_kparams.h)
+hipError_t crx_launch_solve_obs(const crx_kparams& kp, int nobs_template, hipStream_t st);
+hipError_t crx_launch_solve_general(const crx_kparams& kp, int nobs_template, hipStream_t st);
+int crx_solve_resident_per_cu_obs(int N, int nobs_template);
+int crx_solve_resident_per_cu_general(int N, int nobs_template);
+hipError_t crx_launch_solve_models_obs(const crx_kparams_models& kp, int nobs_template, hipStream_t st);
+hipError_t crx_launch_solve_models_general(const crx_kparams_models& kp, int nobs_template, hipStream_t st);
 
-// diagnostics (crx_debug_wave_reduce, not in crx.h): the packed wave reductions of crx_wave.h on four 64-lane inputs.
-// out [16 + 3 * 64]: out[0..3] wave_sum4, [4..7] wave_max4, [8..9] wave_sum2 of inputs 0 and 1, [10..11] wave_max2 of inputs 2 and 3,
-// [12..15] the single-value reductions (sum of 0, max of 1, min of 2, product of the mantissas of 3).
-__global__ void __launch_bounds__(WAVE) crx_debug_reduce_kernel(const double* in, double* out) {
-    const int lane = threadIdx.x;
-    double a = in[lane], b = in[64 + lane], c = in[128 + lane], d = in[192 + lane];
-    double s0 = a, s1 = b, s2 = c, s3 = d;
-    wave_sum4(s0, s1, s2, s3);
-    double m0 = a, m1 = b, m2 = c, m3 = d;
-    wave_max4(m0, m1, m2, m3);
-    double p0 = a, p1 = b;
-    wave_sum2(p0, p1);
-    double q0 = c, q1 = d;
-    wave_max2(q0, q1);
-    int ex;
-    const double r0 = wave_sum(a), r1 = wave_max(b), r2 = wave_min(c), r3 = wave_prod(frexp(fabs(d) + 1.0, &ex));
-    if (lane == 0) {
-        out[0] = s0; out[1] = s1; out[2] = s2; out[3] = s3; out[4] = m0; out[5] = m1; out[6] = m2; out[7] = m3;
-        out[8] = p0; out[9] = p1; out[10] = q0; out[11] = q1; out[12] = r0; out[13] = r1; out[14] = r2; out[15] = r3;
-    }
-    // [r4] row_dot (v_fmac_f64_dpp row_newbcast): out[16 + lane] = c + sum_{i<7} m_i * (lane i of a's 16-lane row), m_i = (i + 1) b + d, under
-    // full EXEC; out[80 + lane] = the same with terms 3 .. 9 inside an `if (lane < 10)` region (the sweeps' predication; NaN elsewhere);
-    // out[144 + lane] = a three-term dot product of lanes 7 .. 9 whose x is the value just accumulated (the forward sweep's input term)
-    double m[7];
-#pragma unroll
-    for (int i = 0; i < 7; i++) m[i] = (double)(i + 1) * b + d;
-    out[16 + lane] = row_dot<7, 0>(a, m, c);
-    double masked = __longlong_as_double(0x7ff8000000000000LL), chained = masked;
-    if (lane < 10) {
-        masked = row_dot<7, 3>(a, m, c);
-        const double first = row_dot<7, 0>(a, m, c);
-        chained = row_dot<3, 7>(first, m, first);
-    }
-    out[80 + lane] = masked;
-    out[144 + lane] = chained;
+// The two entry-point bodies of a unit.  A unit file defines a struct Unit with select_inst (above) and its successors next_launch(kp, nobs_template,
+// st) / next_resident(N, nobs_template) -- the last unit of a walk answers hipErrorInvalidValue / -1 -- and its exported functions are one call each.
+template <class Unit>
+static hipError_t unit_launch(const crx_solve_params& kp, int nobs_template, hipStream_t st) {
+    if (kp.batch == 0) return hipSuccess;
+    if (MODELS && kp.mode != 1 && !(kp.mode == 0 && nobs_template == 0)) return hipErrorInvalidValue;   // models: the planner QP has no obstacle slots
+    hipError_t e = hipSuccess;
+    if (Unit::select_inst(nobs_template, kp.N, kp.degree, [&](auto i) { e = launch_t<i.nobs, i.nmax, i.deg, i.nfix>(kp, st); })) return e;
+    return Unit::next_launch(kp, nobs_template, st);
 }
-
-hipError_t crx_launch_debug_reduce(const double* in, double* out, hipStream_t st) {
-    hipLaunchKernelGGL(crx_debug_reduce_kernel, dim3(1), dim3(WAVE), 0, st, in, out);
-    return hipGetLastError();
+template <class Unit>
+static int unit_resident(int N, int nobs_template) {
+    int n = 0;
+    if (Unit::select_inst(query_slots(nobs_template), N, 6, [&](auto i) { n = occ_t<i.nobs, i.nmax, i.deg, i.nfix>(); })) return n;
+    return Unit::next_resident(N, nobs_template);
 }
-#endif  // !CRX_TU_OBSTACLES
-#endif  // !CRX_TU_SPEC
-#endif  // !CRX_PROBE_ONE

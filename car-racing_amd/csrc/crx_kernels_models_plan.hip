@@ -1,24 +1,24 @@
-// libcrx: crx_solve_kernel with ONE LTI MODEL PER PROBLEM (MPC-CBF NLP, tracking NLP; crx_cbf_solve_models*) as its own translation units --
-// same source as the shared-model instantiations (crx_kernels.hip), whose kernels take the model in crx_kparams.  Here the kernel takes
-// crx_kparams_models and problem b reads A, B from model_A[36 b ..], model_B[12 b ..] and its reach tables from model_reach -- in set-up only:
-// the model matrix M, crash_search (which reads M back) and the slack bounds.  The interior-point loop is the shared kernels' loop.
-// The planner region QP (crx_planner_solve_models*; mode 0, no obstacle slots) runs the same instantiations: its reachability screen reads
-// problem b's table from model_reach, laid out for it by crx_planner_reach_kernel below.
-// Compiled three times (Makefile, -DCRX_MODELS_UNIT=1..3), each time as the unit whose instantiations it mirrors is compiled:
-//   1  zero obstacle slots, N = 10 / 12            the main unit's flags
-//   2  one slot at N = 10 / 12, three at N = 20    the obstacle unit's flags
-//   3  everything else the shared launch accepts   crx_kernels_gen.hip's conservative build
-#ifndef CRX_MODELS_UNIT
-#error "crx_kernels_models.hip is compiled with -DCRX_MODELS_UNIT=1, 2 or 3 (Makefile)"
-#endif
-#define CRX_TU_MODELS CRX_MODELS_UNIT
-#if CRX_MODELS_UNIT == 3
-#include "crx_kernels_gen.hip"
-#else
-#include "crx_kernels_obs.hip"
-#endif
+// libcrx: the first MODELS unit -- crx_solve_kernel with ONE LTI MODEL PER PROBLEM (MPC-CBF NLP, tracking NLP: crx_cbf_solve_models*; planner region
+// QP: crx_planner_solve_models*), the head of the walk models_plan -> models_obs -> models_gen.  Same source as the shared-model instantiations
+// (crx_kernels.hip), whose kernels take the model in crx_kparams; under CRX_TU_MODELS the kernel takes crx_kparams_models and problem b reads A, B
+// from model_A[36 b ..], model_B[12 b ..] and its reach tables from model_reach -- in set-up only: the model matrix M, crash_search (which reads M
+// back) and the slack bounds.  The interior-point loop is the shared kernels' loop.  Each of the three units is built with the flags of the
+// shared-model unit whose instantiations it mirrors.  The two-wave kernels have no such twin.
+//   built with    as the main unit: MachineLICM off + PLAN_SCHED (max-ilp), CRX_TU_MODELS.  Makefile, row crx_kernels_models_plan.o
+//   holds         zero obstacle slots at N = 10 / 12: the mpc_lti form of the CBF NLP, and the planner region QP (mode 0), whose reachability screen
+//                 reads problem b's table from model_reach, laid out for it by crx_planner_reach_kernel below
+//   next          launches with obstacle slots go to crx_kernels_models_obs.hip
+//   also here     crx_cbf_reach_kernel and crx_planner_reach_kernel with their launchers: two small kernels that fill model_reach
+#define CRX_TU_MODELS 1
+#include "crx_kernels.hip"
 
-#if CRX_MODELS_UNIT == 1
+struct Unit {
+    template <class F>
+    static bool select_inst(int nobs_template, int N, int, F&& f) { return nobs_template == 0 && select_fixed<0, 0, 10, 12>(N, f); }
+    static hipError_t next_launch(const crx_kparams_models& kp, int nobs_template, hipStream_t st) { return crx_launch_solve_models_obs(kp, nobs_template, st); }
+};
+hipError_t crx_launch_solve_models(const crx_kparams_models& kp, int nobs_template, hipStream_t st) { return unit_launch<Unit>(kp, nobs_template, st); }
+
 // (lives in this unit, not beside crx_cbfprep_kernel, so that no code object of the shared-model library changes)
 // crx_cbf_reach_kernel: the reach tables of the CBF NLP for one LTI model per problem (crx_cbf_models_reach_dev).  One thread per (problem, row):
 // r = 0 restates reach_bound (crx_api.hip) for state row 4 (s), r = 1 for row 5 (ey), stages 0 .. N, entries past N zero, into
@@ -98,4 +98,3 @@ hipError_t crx_launch_planner_reach(int N, int batch, double delta_max, double a
     hipLaunchKernelGGL(crx_planner_reach_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, N, batch, delta_max, a_max, model_A, model_B, model_reach);
     return hipGetLastError();
 }
-#endif

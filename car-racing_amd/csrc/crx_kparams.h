@@ -169,7 +169,7 @@ struct crx_lmpcprep_kparams {
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
 hipError_t crx_launch_solve(const crx_kparams& kp, int nobs_template, hipStream_t st);
-hipError_t crx_launch_solve_models(const crx_kparams_models& kp, int nobs_template, hipStream_t st);   // crx_kernels_models.hip: plan -> obs -> general unit
+hipError_t crx_launch_solve_models(const crx_kparams_models& kp, int nobs_template, hipStream_t st);   // crx_kernels_models_{plan,obs,gen}.hip: plan -> obs -> general unit
 hipError_t crx_launch_cbf_reach(int N, int batch, double delta_max, double a_max, const double* model_A, const double* model_B, double* model_reach, hipStream_t st);
 hipError_t crx_launch_planner_reach(int N, int batch, double delta_max, double a_max, const double* model_A, const double* model_B, double* model_reach, hipStream_t st);
 hipError_t crx_launch_solve_spec(const crx_kparams& kp, hipStream_t st);   // crx_kernels_spec.hip: the two-wave instantiations <1, 12, 6, {12, 10}, 1>

@@ -9,13 +9,15 @@ of them by <= 3 instructions (a round trip with nothing to hide it: a lone wave 
 import os, re, subprocess, sys, tempfile
 from collections import Counter
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-src = os.path.join(ROOT, "car-racing_amd", "csrc", "crx_kernels.hip")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import recipe
 tpl = ",".join(sys.argv[1:5]); extra = sys.argv[5:]
-sched = (["-DCRX_TU_OBSTACLES", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"] if sys.argv[1] != "0" else ["-mllvm", "-amdgpu-sched-strategy=max-ilp"])
+# csrc/crx_kernels_one.hip with the flags of the unit that ships the instantiation, as the Makefile's recipe states them
+unit = "crx_kernels_one_obs.o" if sys.argv[1] != "0" else "crx_kernels_one_plan.o"
 def build(flags):
     out = tempfile.mktemp(suffix=".s")
-    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function", "-mllvm", "-disable-machine-licm"] + sched +
-                   ["-DCRX_PROBE_ONE=" + tpl] + flags + extra + ["--cuda-device-only", "-S", src, "-o", out], check=True, stderr=subprocess.DEVNULL)
+    cmd = recipe.command(unit, ["-DCRX_PROBE_ONE=" + tpl] + flags + extra)
+    subprocess.run(cmd[:-1] + ["--cuda-device-only", "-S", cmd[-1], "-o", out], check=True, stderr=subprocess.DEVNULL)
     t = open(out).read().split("\n"); os.unlink(out)
     return t
 def isins(x):

@@ -13,6 +13,7 @@ register-allocator artefact -- spill store / reload (scratch_*, buffer_*), AGPR 
   narrowing  the block is only reached with a non-empty, narrowed mask (an if-region without a skip branch): the lanes outside keep stale data, which
              is harmless exactly when the value is dead outside the region.  Listed, exit status 0 (`--strict`: 1).
     python tools/exec_prologue_check.py [--strict] [--list] [FILE.so | FILE.o ...]
+Exit status 2: the ROCm binutils are missing, nothing checked.  3: they are there and no code object could be extracted from the input.
 `make` runs it on libcrx.so right after linking (car-racing_amd/csrc/Makefile: a FATAL finding fails the build); tests/test_abi_cpu.py runs it on the
 shipped library (skipped when the ROCm binutils are absent).
 """
@@ -130,7 +131,7 @@ def main(argv):
         n_obj, ", ".join(os.path.basename(f) for f in files), fatal, narrowing))
     if n_obj == 0:
         print("exec_prologue_check: no gfx code object found in the input")
-        return 2
+        return 3   # the binutils are there and nothing could be extracted: not "nothing checked because nothing to check with" (2)
     return 1 if (fatal or (strict and narrowing)) else 0
 
 

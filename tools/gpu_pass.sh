@@ -116,7 +116,7 @@ issue)
   pmc cfg3_1 cfg3 16384 3 "" $A
   pmc cfg3_3 cfg3 16384 3 "" $B )
   ls $O | grep pmc_ ;;   # summarise locally: python3 profiles/summarize_issue.py $TAG it4,it2,it3 > profiles/rNN_pmc_issue.txt
-trace)   # needs tools/ab/libcrx_trace.so: tools/build_variant.sh trace "-DCRX_PHASE_CLOCKS" crx_kernels.hip crx_kernels_obs.hip crx_lmpc.hip (build container)
+trace)   # needs tools/ab/libcrx_trace.so: tools/build_variant.sh trace "-DCRX_PHASE_CLOCKS" crx_kernels_plan.hip crx_kernels_obs.hip crx_lmpc.hip (build container)
   ( export CRX_LIB=$R/tools/ab/libcrx_trace.so; for w in cfg2 cfg3 cfg4; do python tools/gpu_solve_trace.py $w; done; python tools/gpu_lmpc_trace.py ) 2>&1 | grep -v "amdgpu.ids\|Warning\|print(\|ret = " > $O/phase_cycles.txt
   cat $O/phase_cycles.txt ;;
 budget)

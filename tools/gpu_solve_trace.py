@@ -1,4 +1,4 @@
-"""(phase clocks need a library built with -DCRX_PHASE_CLOCKS -- `make TRACE=1`, or tools/build_variant.sh trace "-DCRX_PHASE_CLOCKS" crx_kernels.hip
+"""(phase clocks need a library built with -DCRX_PHASE_CLOCKS -- `make TRACE=1`, or tools/build_variant.sh trace "-DCRX_PHASE_CLOCKS" crx_kernels_plan.hip
 crx_kernels_obs.hip crx_lmpc.hip + CRX_LIB=tools/ab/libcrx_trace.so, which is what `tools/gpu_pass.sh TAG trace` uses; the default build compiles them out)
 Diagnostics: per-phase shader cycles of one crx_solve_kernel problem (hidden crx_trace_* entry points).
 usage: gpu_solve_trace.py [cfg2|cfg3|cfg4]"""

@@ -6,10 +6,11 @@ Every gfx950 code object embedded in the two files is extracted (exec_prologue_c
 (a function symbol NAME with a kernel descriptor NAME.kd):
     same      identical .text bytes, identical 64-byte kernel descriptor, identical metadata entry (VGPR / AGPR / SGPR counts, LDS and
               scratch sizes, arguments) -- whatever its position inside the code object or the order of the code objects
+    moved     as `same`, but for the descriptor's entry-offset field (bytes 16..23: the distance from the descriptor to the entry point) -- the
+              kernel sits elsewhere in its code object, or in another one.  Not a difference
     differs   names which of text / kd / meta differ
     missing   in one of the two files only
-A kernel that moved inside its code object has the same text and metadata but shows `differs (kd)`: the descriptor holds the distance to the entry point.
-Exit status 0 when every kernel is `same`, 1 otherwise, 2 when the ROCm binutils are absent.
+Exit status 0 when every kernel is `same` or `moved`, 1 otherwise, 2 when the ROCm binutils are absent.
 """
 import os
 import shutil
@@ -66,6 +67,14 @@ def metadata(path):
     return {k: sorted(v) for k, v in out.items()}
 
 
+def verdict_of(old, new):
+    """(text, kd, meta) of one kernel in the two builds -> `same`, `moved` or `differs (..)`"""
+    what = [w for w, a, b in zip(("text", "kd", "meta"), old, new) if a != b or a is None]
+    if what == ["kd"] and len(old[1]) == len(new[1]) == 64 and old[1][:16] + old[1][24:] == new[1][:16] + new[1][24:]:
+        return "moved"   # KERNEL_CODE_ENTRY_BYTE_OFFSET alone
+    return "differs (%s)" % ", ".join(what) if what else "same"
+
+
 def kernels(path):
     tmp = tempfile.mkdtemp(prefix="crx_kd_")
     try:
@@ -92,9 +101,8 @@ def main(argv):
         if n not in old or n not in new:
             verdict = "missing in " + (argv[0] if n not in old else argv[1])
         else:
-            what = [w for w, a, b in zip(("text", "kd", "meta"), old[n], new[n]) if a != b or a is None]
-            verdict = "differs (%s)" % ", ".join(what) if what else "same"
-        bad += verdict != "same"
+            verdict = verdict_of(old[n], new[n])
+        bad += verdict not in ("same", "moved")
         print("%-8s %s  [%d B]" % (verdict, demangle(n), len((new.get(n) or old[n])[0])))
     print("kernel_diff: %d kernel(s), %d not the same" % (len(set(old) | set(new)), bad))
     return 1 if bad or not old else 0

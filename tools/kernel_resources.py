@@ -1,5 +1,7 @@
 """Registers, scratch and occupancy of the solver kernels, from the compiler's own remarks (no GPU needed):
-    python tools/kernel_resources.py [obs|plan|gen|lmpc|models_plan|models_obs|models_gen]     (recompiles the translation unit with -Rpass-analysis=kernel-resource-usage)
+    python tools/kernel_resources.py [obs|plan|gen|spec|lmpc|models_plan|models_obs|models_gen] [flags]   (recompiles the unit as `make recipe` states it, with
+                                                       -Rpass-analysis=kernel-resource-usage)
+    python tools/kernel_resources.py one NOBS NMAX DEG NFIX [flags]     ONE instantiation compiled alone (csrc/crx_kernels_one.hip)
     python tools/kernel_resources.py lib [FILE.so]     what SHIPS: the kernel metadata of every code object embedded in the library (default: the in-tree
                                                        libcrx.so), no recompilation -- shipped() below, which tests/test_kernel_budget_cpu.py asserts on"""
 import os, re, subprocess, sys, tempfile
@@ -35,23 +37,19 @@ elif which == "lib":
         print("%-52s vgpr %3d agpr %3d sgpr spills %3d scratch %4d B/lane  LDS %6d B" % (demangle(n) + (" [models]" if "models" in n else ""), r["vgpr"], r.get("agpr", 0),
               r["sgpr_spill"], r["scratch"], r["lds"]))
     sys.exit(0)
+# unit name -> its object in the Makefile's recipe (tools/recipe.py: source and flags are read from `make recipe`, none is kept here)
+UNITS = {"plan": "crx_kernels.o", "obs": "crx_kernels_obs.o", "gen": "crx_kernels_gen.o", "spec": "crx_kernels_spec.o", "models_plan": "crx_kernels_models_plan.o",
+         "models_obs": "crx_kernels_models_obs.o", "models_gen": "crx_kernels_models_gen.o", "lmpc": "crx_lmpc.o"}
+def unit_command(which, args):
+    """-> the compile command of a unit name (UNITS, or `one NOBS NMAX DEG NFIX`: crx_kernels_one.hip as the unit that ships the instantiation is built)"""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import recipe
+    if which == "one":
+        return recipe.command("crx_kernels_one_obs.o" if args[0] != "0" else "crx_kernels_one_plan.o", ["-DCRX_PROBE_ONE=" + ",".join(args[:4])] + args[4:])
+    return recipe.command(UNITS[which], args)
 def recompile():
-    src, sched = {"one": (None, None), "obs": ("crx_kernels_obs.hip", ["-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]),
-                  "plan": ("crx_kernels.hip", ["-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
-                  "gen": ("crx_kernels_gen.hip", ["-mllvm", "-disable-machine-licm"]),
-                  # one LTI model per problem (crx_kernels_models.hip): each unit with the flags of the unit it mirrors
-                  "models_plan": ("crx_kernels_models.hip", ["-DCRX_MODELS_UNIT=1", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]),
-                  "models_obs": ("crx_kernels_models.hip", ["-DCRX_MODELS_UNIT=2", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]),
-                  "models_gen": ("crx_kernels_models.hip", ["-DCRX_MODELS_UNIT=3", "-mllvm", "-disable-machine-licm"]),
-                  "lmpc": ("crx_lmpc.hip", ["-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"])}[which]
-    extra = sys.argv[2:]
-    if which == "one":   # python tools/kernel_resources.py one NOBS NMAX DEG NFIX [flags]
-        tpl = ",".join(sys.argv[2:6]); extra = sys.argv[6:]
-        src = "crx_kernels.hip"
-        sched = (["-DCRX_TU_OBSTACLES", "-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"] if sys.argv[2] != "0" else
-                 ["-mllvm", "-disable-machine-licm", "-mllvm", "-amdgpu-sched-strategy=max-ilp"]) + ["-DCRX_PROBE_ONE=" + tpl]
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-Wno-unused-function"] + sched + extra + [
-        "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(S, src), "-o", "/dev/null"]
+    cmd = unit_command(which, sys.argv[2:])
+    cmd = cmd[:-1] + ["-Rpass-analysis=kernel-resource-usage", "-c", cmd[-1], "-o", "/dev/null"]
     t = subprocess.run(cmd, capture_output=True, text=True).stderr
     for b in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
         g = lambda k: (re.search(k + r": (\d+)", b) or [0, "?"])[1]

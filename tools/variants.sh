@@ -7,6 +7,7 @@
 # DPP dot products, M = masked sweeps (the shipped unit is g101: static LDS + AGPR copies, v_readlane, masked sweeps).  Every cell is first
 # passed through tools/exec_prologue_check.py (a spill store in front of an EXEC restore: the compiler bug of DESIGN.md section 8); the S = 0 cells
 # spill to scratch and are where it appears.
+# Units are named by their source files (car-racing_amd/csrc/Makefile has the table; tools/build_variant.sh is a thin call of its `variant` target).
 # Tuned units: fenceonly = SYNC() as up to 0.2.1 (fence without the wave barrier), opaqueall / nodpp as in round 4.
 cd "$(dirname "$0")/.."
 rm -rf tools/ab/g[01][01][01] tools/ab/libcrx_g[01][01][01].so
@@ -20,8 +21,12 @@ for c in 000 001 010 011 100 101 110 111; do
   S=${c:0:1}; D=${c:1:1}; M=${c:2:1}; W=2; [ $S = 1 ] && W=0
   echo "g$c: $(python tools/exec_prologue_check.py tools/ab/libcrx_g$c.so | tail -1)"     # [r6] on the code objects of the variant itself
 done | tee tools/ab/exec_prologue_matrix.txt
-bash tools/build_variant.sh fenceonly "-DCRX_SYNC_FENCE_ONLY" crx_kernels.hip crx_kernels_obs.hip crx_kernels_gen.hip crx_lmpc.hip crx_prep.hip crx_lmpcprep.hip > /dev/null &
+bash tools/build_variant.sh fenceonly "-DCRX_SYNC_FENCE_ONLY" crx_kernels_plan.hip crx_kernels_obs.hip crx_kernels_gen.hip crx_lmpc.hip crx_prep.hip crx_lmpcprep.hip > /dev/null &
 bash tools/build_variant.sh opaqueall "-DCRX_OPAQUE_LANE=2" crx_kernels_obs.hip > /dev/null &
-bash tools/build_variant.sh nodpp "-DCRX_ROWDPP=0" crx_kernels.hip crx_kernels_obs.hip > /dev/null &
+bash tools/build_variant.sh nodpp "-DCRX_ROWDPP=0" crx_kernels_plan.hip crx_kernels_obs.hip > /dev/null &
 wait
 ls -la tools/ab/*.so
+# every library of the list must be whole: it loads (needs no GPU) -- a variant that lacks a unit of the link line fails here with an undefined symbol
+for n in g000 g001 g010 g011 g100 g101 g110 g111 fenceonly opaqueall nodpp; do
+  python -c "import ctypes, sys; ctypes.CDLL(sys.argv[1]); print('loads', sys.argv[1])" tools/ab/libcrx_$n.so || exit 1
+done

@@ -163,14 +163,21 @@ __device__ __forceinline__ double ipow_d(double a, int p) {
 #endif
 enum : unsigned { LF_ROW_STEP = 1, LF_ROW_TRIAL = 2, LF_ROW_ACCEPT = 4, LF_ACCEPT_Z = 8, LF_FIRST_ORDER = 16, LF_ASSEMBLE = 32 };
 template <int NOBS, int NMAX> constexpr unsigned LoadsFirst = (NOBS == 1 && NMAX == 12 && !CRX_TU_GENERAL) ? (unsigned)(CRX_LOADS_FIRST) : 0u;
-// [r9] The same instantiations (the reach of LoadsFirst) with NMAX * NOBS <= 64 -- one pass over the CBF rows, the row of a lane the same in every
-// pass -- hand the CBF row values of the accepted line-search trial to the accept step, which stores the point the trial evaluated them at and
-// would evaluate them there once more: the same expression on the same doubles (same bits: tests/test_gpu_obs1_retry_bits.py).  A/B builds: make
-// EXTRA=-DCRX_CBF_CARRY=0 is the form that evaluates twice; every other instantiation keeps it.
+// [r9] The same instantiations (the reach of LoadsFirst) stop repeating two pieces of work, each behind a switch of its own (A/B builds: make
+// EXTRA=-DCRX_RETRY_SHARED=0 / -DCRX_CBF_CARRY=0 is the parent's code; every other instantiation compiles what it compiled before):
+//   CRX_RETRY_SHARED  the attempts of the inertia-correction schedule of ONE Newton system share the set-up of riccati_backward (lane maps, the
+//                     stage-invariant model operands, the opaque lane copy): the retry loop runs inside the sweep function, behind its set-up
+//   CRX_CBF_CARRY     the accept step takes the CBF row values from the accepted line-search trial, which evaluated them at the point accept stores
+//                     (NMAX * NOBS <= 64: one pass, the row of a lane is the same in both places)
+#ifndef CRX_RETRY_SHARED
+#define CRX_RETRY_SHARED 1
+#endif
 #ifndef CRX_CBF_CARRY
 #define CRX_CBF_CARRY 1
 #endif
-template <int NOBS, int NMAX> constexpr bool CbfCarry = (CRX_CBF_CARRY) != 0 && NOBS == 1 && NMAX == 12 && !CRX_TU_GENERAL && NMAX * NOBS <= WAVE;
+template <int NOBS, int NMAX> constexpr bool Obs1Tuned = NOBS == 1 && NMAX == 12 && !CRX_TU_GENERAL;
+template <int NOBS, int NMAX> constexpr bool RetryShared = (CRX_RETRY_SHARED) != 0 && Obs1Tuned<NOBS, NMAX>;
+template <int NOBS, int NMAX> constexpr bool CbfCarry = (CRX_CBF_CARRY) != 0 && Obs1Tuned<NOBS, NMAX> && NMAX * NOBS <= WAVE;
 // end of a stage of an UNROLLED sweep [r4]: without it the scheduler lifts the loads of all later stages to the top of the sweep and the
 // registers they occupy are paid for in scratch (a wave writes its spills once: 100 B per lane were x8 the algorithmic bytes written of a cfg2 launch)
 #define STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -849,8 +856,14 @@ __device__ __forceinline__ void assemble_newton(double* sm, const int* si, const
 // instead, which two concurrent sweeps cannot).
 // KEEPF [r6]: the factor of every stage's Huu (unit-lower L, reciprocal pivots) is left behind in the stage's slice of Hd -- consumed by this stage's H
 // phase, rewritten by the next assemble_newton -- for riccati_backward_vec, the second solve of the predictor-corrector iteration.
-template <int NOBS, int NMAX, int UNR = 1, int REG = 0, bool CVX = false, bool KEEPF = false>
-__device__ __forceinline__ bool riccati_backward(double* sm, const int* si, const Ctx& c, double dw, long long* tsub = nullptr, bool convex = false) {
+// SHARED [r9]: the attempts of the inertia-correction schedule of one Newton system run INSIDE this call, behind its set-up: after a sweep with the wrong
+// inertia `retry(dw)` (the caller's schedule: wave-uniform) either sets up the next attempt -- a new dw, or kS / kE zeroed in LDS -- and returns true, or
+// returns false.  An attempt is the terminal P_N (it reads kS / kE), the sweep and the sigma_0 solve; the lane maps, the stage-invariant model operands
+// and the opaque lane copy are made once per call.  Same operations on the same operands in the same order as one call per attempt.
+struct NoRetry { __device__ __forceinline__ bool operator()(double&) const { return false; } };
+template <int NOBS, int NMAX, int UNR = 1, int REG = 0, bool CVX = false, bool KEEPF = false, bool SHARED = false, class Retry = NoRetry>
+__device__ __forceinline__ bool riccati_backward(double* sm, const int* si, const Ctx& c, double dw, long long* tsub = nullptr, bool convex = false,
+                                                 Retry retry = Retry(), double* dw_used = nullptr) {
     using L = Lay<NOBS, NMAX>;
     constexpr int NX = L::NX, NU = L::NU, NZ = L::NZ, HS = L::HS;
     constexpr int oP = REG ? L::P2 : L::P, opv = REG ? L::pv2 : L::pv, oT = REG ? L::T2 : L::T, oH = REG ? L::H2 : L::H, oKk = REG ? L::Kk2 : L::Kk,
@@ -1008,6 +1021,12 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
         mSl[q] = exSl[q] ? 1.0 : 0.0; mEl[q] = exEl[q] ? 1.0 : 0.0;
     }
     if (tsub) tsub[2] += CLK() - qs;   // set-up of the sweep (terminal P, lane maps, stage-invariant operands)
+    int kst0[UCNT];   // (SHARED: kst walks down the horizon with the sweep; every attempt starts from stage N-1 again)
+    if constexpr (SHARED) {
+#pragma unroll
+        for (int q = 0; q < UCNT; q++) kst0[q] = kst[q];
+    }
+attempt: __attribute__((unused));   // (SHARED: a retry of the schedule comes back here, behind the set-up)
 #pragma unroll UNR
     for (int k = N - 1; k >= 0; k--) {
         long long q0 = CLK();
@@ -1217,7 +1236,13 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
         long long q4 = CLK();
         if (tsub) { tsub[0] += q1 - q0; tsub[1] += q2 - q1; tsub[3] += q4 - q2; }
     }
-    if (!ok) { SYNC(); return false; }
+    if constexpr (!SHARED) {
+        if (!ok) { SYNC(); return false; }
+    }
+    // (SHARED: after a sweep with the wrong inertia the sigma_0 solve is skipped and the schedule below goes on; a sigma_0 pivot that is not positive
+    // ends the attempt in the same way, as it does where every attempt is a call.  Every lane computed the same pivots: asked of the whole wave, the
+    // branches and the schedule behind them are uniform)
+    if (SHARED ? !__any(!ok) : true) {
     if constexpr (PTR && NOBS > 0) {   // (P_0 | p_0) of the sigma_0 solve below: the only reader of P and pv outside the sweep
         LD(SINK(isPm, oP + g8 * NX + c8)) = pn;
         LD(SINK(isPv, opv + c8)) = pn;
@@ -1267,6 +1292,41 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
                 for (int a = 0; a < NOBS; a++) LD(odZ + 6 + a) = y[a];
             }
         }
+    }
+    }
+    if constexpr (SHARED) {
+        if (__any(!ok)) {
+            SYNC();
+            if (__builtin_amdgcn_readfirstlane((int)retry(dw)) != 0) {   // (the caller's schedule is uniform: said so, the loop is a scalar one)
+                static_assert(!SHARED || (PTR && NOBS > 0 && !CVX), "the shared set-up is written for the register-resident (P | p) of the one-obstacle kernel");
+                const long long qt = CLK();
+                // the next attempt's terminal (P_N | p_N), as at the head of the call (PTR form; kS / kE may have been zeroed since), its lane sets from an
+                // opaque copy of the lane index: formed here, where an attempt has failed, they are not masks carried through every sweep
+                int lt = lo;
+                asm volatile("" : "+v"(lt));
+                const int g8t = lt >> 3, c8t = lt & 7;
+                const bool isPmt = g8t < NX && c8t < NX, isPvt = g8t == NX && c8t < NX;
+                const double kSn = LD(L::kS + 2 * (N - 1));
+                double kEn = LD(L::kE + 2 * (N - 1));
+                kEn += 2.0 * LD(L::wc + N - 1);
+                const double hd = LD(L::Hd + N * NZ + seli(isPmt, g8t, 0));
+                const double hgN = LD(L::hg + N * NZ + seli(c8t < NX, c8t, 0));
+                pn = sel(isPvt, hgN, sel(isPmt && g8t == c8t, hd + sel(g8t == 4, kSn, sel(g8t == 5, kEn, 0.0)), 0.0));
+                LD(SINK(lt < NX, oT + lt * L::TS + 6)) = 0.0;
+                LD(SINK(isPmt && c8t == 6, oT + g8t * L::TS + NX + 2)) = pn;
+                SYNC();
+                ok = true;
+                // (an opaque copy: the feedback addresses of the twelve unrolled stages -- invariant from attempt to attempt -- are then formed stage by stage
+                // as in the one-attempt form; hoisted in front of the attempts they were 36 registers carried through the whole sweep, 116 B of scratch per lane)
+#pragma unroll
+                for (int q = 0; q < UCNT; q++) { kst[q] = kst0[q]; asm volatile("" : "+v"(kst[q])); }
+                if (tsub) tsub[2] += CLK() - qt;
+                goto attempt;
+            }
+            *dw_used = dw;   // (the schedule is exhausted: the caller's delta_w is the last one tried)
+            return false;
+        }
+        *dw_used = dw;   // (the regularisation of the attempt that succeeded: the caller's delta_w)
     }
     SYNC();
     return ok;
@@ -1732,7 +1792,8 @@ crx_solve_kernel(const crx_solve_params kp) {
     constexpr int NX = L::NX, NZ = L::NZ, NR = L::NR;
     // [r8] the phases of this instantiation that load both passes before they compute (LoadsFirst), and the passes of a row / coordinate phase
     constexpr unsigned LF = (NFIX != 0 && QPM == 0) ? LoadsFirst<NOBS, NMAX> : 0u;
-    // [r9] ... and whether its accept step takes the CBF row values of the accepted trial (CbfCarry)
+    // [r9] ... and the two pieces of repeated work they leave out (RetryShared: the one-wave retry loop only; CbfCarry)
+    constexpr bool RSH = NFIX != 0 && QPM == 0 && SPEC == 0 && RetryShared<NOBS, NMAX>;
     constexpr bool CBFC = NFIX != 0 && QPM == 0 && CbfCarry<NOBS, NMAX>;
     constexpr int RPASS = (L::MR + WAVE - 1) / WAVE, CPASS = (L::NV + WAVE - 1) / WAVE;
     static_assert(LF == 0 || !L::SLIM, "the loads-first row passes are written for the full layout (row_scale, row_bound, row_sig_w are loads there)");
@@ -1745,7 +1806,16 @@ crx_solve_kernel(const crx_solve_params kp) {
     extern __shared__ __attribute__((aligned(16))) double sm[];
 #endif
     int* si = (int*)(sm + L::END_D);
-    const int lane = SPEC ? (int)(threadIdx.x & (WAVE - 1)) : (int)threadIdx.x, N = NFIX ? NFIX : kp.N;
+    // (SPEC [r12]: the two-wave kernel's lane index is to tell the compiler exactly what the one-wave kernel's does -- that it is not negative, and no
+    // more.  `threadIdx.x & 63` also says lane < 64, the first pass of every COORDS / ROWS loop then lies provably below stage N, selects such as
+    // sel(k < N, nuv * jv2, 0.0) of first_order fold away there and the product is FUSED into the sum it is subtracted from: one rounding where the
+    // one-wave kernel, which keeps the select, has two -- the last-bit differences between the two units (tests/test_gpu_obs1_routes_bits.py).)
+    int lane_ = SPEC ? (int)(threadIdx.x & (WAVE - 1)) : (int)threadIdx.x;
+    if constexpr (SPEC != 0) {
+        asm volatile("" : "+v"(lane_));
+        __builtin_assume(lane_ >= 0);
+    }
+    const int lane = lane_, N = NFIX ? NFIX : kp.N;
     if ((int)blockIdx.x >= kp.batch) return;
     // dispatch order [r3]: workgroups start in launch order, so a caller that knows which problems are long (the iteration counts of
     // the previous control step) lists them first and the launch does not end waiting for a straggler that started last
@@ -2458,6 +2528,24 @@ crx_solve_kernel(const crx_solve_params kp) {
                 dw = sdw;
                 if (sdw > 1e40) break;
             }
+        } else if constexpr (RSH) {
+            // [r9] the same schedule, run by the sweep function between its attempts (riccati_backward<.., SHARED>): one set-up per Newton system
+            // (no state of its own: the convexified retry is still ahead while crash && !used_convex, and the first step of delta_w is the one from 0)
+            auto retry = [&](double& dwr) -> bool {
+                if (NOBS && __builtin_amdgcn_readfirstlane((int)(crash && !used_convex)) != 0) {   // crash path (iii), as below
+                    used_convex = 1;
+                    for (int k = lane; k < N; k += WAVE) { LD(L::kS + 2 * k) = 0.0; LD(L::kE + 2 * k) = 0.0; }
+                    SYNC();
+                    return true;
+                }
+                // (from an opaque copy of dw_last: the first step and the factor of the schedule are formed when an attempt has failed, not in front
+                // of the attempts and carried through every sweep)
+                double dwl = dw_last;
+                asm volatile("" : "+v"(dwl));
+                dwr = dwr == 0.0 ? (dwl == 0.0 ? 1e-4 : fmax(1e-20, dwl / 3.0)) : dwr * (dwl == 0.0 ? 100.0 : 8.0);
+                return !(dwr > 1e40);
+            };
+            ok = riccati_backward<NOBS, NMAX, StageUnroll<NFIX>, 0, false, false, true>(sm, si, c, 0.0, tsub, false, retry, &dw);
         } else
         for (int tries = 0, convex = (NOBS > 0 && crash && !used_convex) ? 0 : 1;; ) {
             ok = riccati_backward<NOBS, NMAX, StageUnroll<NFIX>>(sm, si, c, dw, tsub);

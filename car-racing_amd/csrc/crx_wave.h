@@ -51,11 +51,20 @@ __device__ __forceinline__ double wrap_below(double s, double L) {   // `while (
 // as scalars -- ~10 VALU ops instead of the 12 ds_bpermute round trips __shfl_xor lowers to.
 // Every lane returns the full-wave result (wave-uniform).
 // ------------------------------------------------------------------------------------------------
+// CONTRACT of dpp_f64 [r12]: EVERY lane that CTRL reads is ACTIVE at the call.  The permutations of ROW_REDUCE stay inside a 16-lane row, so:
+// full EXEC -- the caller sits in wave-uniform control flow of a block made of whole waves.  The move has no tied `old` operand (bound_ctrl,
+// old = 0, as dpp_zfill_f64 below): a lane whose source lane is inactive gets a ZERO where `update_dpp(x, x, ..)` left it its own value, and
+// with every source active the two are the same move.  Untied, the destination is a fresh register and the source -- still live, it is the
+// other operand of the OP -- is not copied first (the tied form cost two v_mov_b32 per butterfly step, 64 per interior-point iteration).
+// Every caller was audited for this in round 12: all sit behind the reconvergence point of their lane loops, under
+// wave-uniform conditions only.  None could do otherwise before: every wave_* reads its result from lanes 0 / 16 / 32 / 48 with v_readlane, which
+// ignores EXEC, and a sum or product whose partner lane is missing counted the own value twice.  A future caller in divergent flow must not
+// use dpp_f64: it needs the tied form under a name of its own.
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v) {
     int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, 0xF, 0xF, false);
-    hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, 0xF, 0xF, false);
+    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
+    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
     return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ double lane_f64(double v, int l) {
@@ -111,8 +120,18 @@ __device__ __forceinline__ double halfrow_dot6(double x, const double* m, bool u
     v = OP(v, dpp_f64<0x140>(v)); /* row_mirror          */
 __device__ __forceinline__ double op_add(double a, double b) { return a + b; }
 __device__ __forceinline__ double op_mul(double a, double b) { return a * b; }
-__device__ __forceinline__ double op_max(double a, double b) { return fmax(a, b); }
-__device__ __forceinline__ double op_min(double a, double b) { return fmin(a, b); }
+// [r12] max / min as the bare instruction.  fmax / fmin on operands that arrive through integer DPP moves, v_permlane*_swap or v_readlane get a
+// canonicalising `v_max_f64 x, x, x` in front from the compiler (one full FP64 issue slot per operand): it no longer knows them to be quieted,
+// and in IEEE mode v_max_f64 / v_min_f64 answer a SIGNALLING NaN operand with a NaN instead of the other operand.  The kernels produce no
+// signalling NaNs: what they reduce are results of FP instructions, which are quiet if they are NaNs at all (a signalling NaN in caller data
+// that reached a reduction untouched would come out as a quiet NaN, not be dropped).  For everything else the bare instruction IS fmax / fmin:
+// a quiet NaN loses against a number, two NaNs give a NaN (tests/test_gpu_wave_prims.py: ties, signed zeros, NaNs).
+__device__ __forceinline__ double op_max(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ double op_min(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+// the same with the first operand in an SGPR pair (a VOP3 instruction may take one): the four-row combines below, whose operands are v_readlane
+// results -- two of the four then need no move into a VGPR (16 instructions for the combine, as with fmax; 21 with four "v" operands)
+__device__ __forceinline__ double op_max_sv(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "s"(a), "v"(b)); return r; }
+__device__ __forceinline__ double op_min_sv(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "s"(a), "v"(b)); return r; }
 __device__ __forceinline__ double wave_sum(double v) {
     ROW_REDUCE(v, op_add)
     return (lane_f64(v, 0) + lane_f64(v, 16)) + (lane_f64(v, 32) + lane_f64(v, 48));
@@ -123,11 +142,11 @@ __device__ __forceinline__ double wave_prod(double v) {
 }
 __device__ __forceinline__ double wave_max(double v) {
     ROW_REDUCE(v, op_max)
-    return fmax(fmax(lane_f64(v, 0), lane_f64(v, 16)), fmax(lane_f64(v, 32), lane_f64(v, 48)));
+    return op_max(op_max_sv(lane_f64(v, 0), lane_f64(v, 16)), op_max_sv(lane_f64(v, 32), lane_f64(v, 48)));
 }
 __device__ __forceinline__ double wave_min(double v) {
     ROW_REDUCE(v, op_min)
-    return fmin(fmin(lane_f64(v, 0), lane_f64(v, 16)), fmin(lane_f64(v, 32), lane_f64(v, 48)));
+    return op_min(op_min_sv(lane_f64(v, 0), lane_f64(v, 16)), op_min_sv(lane_f64(v, 32), lane_f64(v, 48)));
 }
 
 // Packed reductions [r2]: two or four wave reductions for little more than the price of one.  A single f64 reduction

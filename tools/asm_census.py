@@ -60,14 +60,18 @@ tr = build(["-DCRX_PHASE_CLOCKS"])
 CAR = carriers(tr)
 marks = [i for i, l in enumerate(tr) if "s_memtime" in l]
 # the clock reads in source order: five at the head of the iteration, two around the set-up of the backward sweep, four per stage of it (once for a
-# rolled stage loop, once per stage for an unrolled sweep), five behind it
-stages = (len(marks) - 12) // 4 if len(marks) >= 16 and (len(marks) - 12) % 4 == 0 else 0
+# rolled stage loop, once per stage for an unrolled sweep), five behind it; with the shared sweep set-up (riccati_backward<.., SHARED>) two more behind
+# the sweep, around the set-up of the next attempt, which is code of the failure path: not executed by an iteration whose first sweep succeeds
+RS = 2 if len(marks) >= 18 and (len(marks) - 12) % 4 == 2 else 0
+stages = (len(marks) - 12 - RS) // 4 if len(marks) >= 16 and (len(marks) - 12 - RS) % 4 == 0 else 0
 names = ["(loop top)", "adjoint (KKT error)", "barrier update", "assemble", "ric: retry schedule, terminal P", "ric: lane maps, stage-invariant operands", "ric: (set-up -> first stage)"]
 for s_ in range(stages):
     k = "k" if stages == 1 else "N-%d" % (s_ + 1)
     names += ["ric %s: T = P M" % k, "ric %s: H = M'T + .." % k, "ric %s: factor + update" % k, "ric %s: (-> next stage)" % k if s_ < stages - 1 or stages == 1 else "ric: sigma_0 / retry logic"]
 if stages == 1:
     names += ["ric: sigma_0 / retry logic"]
+if RS:
+    names += ["ric: retry, terminal P of the next attempt", "ric: (retry -> first stage | out)"]
 names += ["forward sweep" + (" (loop body once)" if stages == 1 else ""), "row steps", "line search (one trial)", "accept + first order"]
 print("%-36s %6s %5s %5s %5s %5s %5s %5s %5s %5s %5s %5s %5s %5s" % ("phase (between clock reads)", "instr", "f64", "ds_r", "ds_w", "rdln", "cndm", "vmov", "vint", "wait", "salu", "agpr", "spill", "xwait"))
 def loops(a, b):   # bodies of the loops that lie inside [a, b): (label, instructions), innermost first

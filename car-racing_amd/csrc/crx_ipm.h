@@ -68,6 +68,15 @@ __device__ __forceinline__ double ipm_dual_safeguard(double nu, double mu_t) {
     return fmin(fmax(nu, mu_t * (1.0 / IPM_KAPPA_SIGMA)), IPM_KAPPA_SIGMA * mu_t);
 }
 
+// ---- inertia correction --------------------------------------------------------------------------------------------------------
+// IPOPT's delta_w schedule (Alg. IC) for a Newton system whose factorisation shows the wrong inertia: the first delta_w is 1e-4 on a
+// cold start (dw_last == 0: no system of this solve has needed one yet) and a third of the last successful one otherwise, floored at
+// 1e-20; every further attempt multiplies it by 100 (cold) or 8 (warm); above IPM_DW_MAX the schedule is exhausted and the solve gives
+// up.  How the attempts are run (one sweep at a time, two at a time, inside the sweep function) is the kernel's.
+constexpr double IPM_DW_MAX = 1e40;
+__device__ __forceinline__ double ipm_dw_first(double dw_last) { return dw_last == 0.0 ? 1e-4 : fmax(1e-20, dw_last / 3.0); }
+__device__ __forceinline__ double ipm_dw_grow(double dw, double dw_last) { return dw * (dw_last == 0.0 ? 100.0 : 8.0); }
+
 // ---- Differences between the kernels that are NOT shared, and why each stays -----------------------------------------------------
 // "code changes" = with this one site alone routed through a function of this header (by-value scalars, the written-out expression
 // as its body), the kernel's machine code is no longer bit for bit what it was (tools/kernel_diff.py `differs (text)`), although
@@ -82,24 +91,25 @@ __device__ __forceinline__ double ipm_dual_safeguard(double nu, double mu_t) {
 //     phin <= phi0 + IPM_ETA_PHI al Dphi + 10 IPM_EPS |phi0|
 //
 //   rule                   kernel (file:line)                                  why it stays
-//   termination test       crx_solve_kernel, Mehrotra (crx_kernels.hip:2030)   code changes in 5 of 39 solver instantiations
-//                          crx_solve_kernel, NLP (crx_kernels.hip:2209-2225)   code changes in 32 of 39 (the E0 test guards the lazy row pass for vu)
+//   termination test       crx_solve_kernel, Mehrotra (crx_kernels.hip:2263)   code changes in 5 of 39 solver instantiations
+//                          crx_solve_kernel, NLP (crx_kernels.hip:2430-2446)   code changes in 32 of 39 (the E0 test guards the lazy row pass for vu)
 //                          crx_lmpc_kernel (crx_lmpc.hip:499)                  code changes in all six instantiations
 //                          crx_path_kernel (crx_prep.hip:413)                  code changes (the products e_d * sd, e_c * sd are evaluated lazily there)
 //   barrier update         crx_lmpc_kernel (crx_lmpc.hip:530-531)              code changes in <12,0,44,*>; same arithmetic as ipm_mu_reached / ipm_next_mu<true>
 //   mu^theta_mu            crx_path_kernel (crx_prep.hip:418)                  DIFFERENT ARITHMETIC: ipm_next_mu<false>, pow() for every theta_mu; the other
 //                                                                              two kernels mu sqrt(mu) at 1.5
 //   theta_min / theta_max  crx_lmpc_kernel (crx_lmpc.hip:791-794)              code changes in all six instantiations
-//   switching condition    crx_solve_kernel (crx_kernels.hip:2374-2378, :2415) DIFFERENT ARITHMETIC, three forms: log2 domain with the al-independent part
+//   switching condition    crx_solve_kernel (crx_kernels.hip:2644-2648, :2699) DIFFERENT ARITHMETIC, three forms: log2 domain with the al-independent part
 //                          crx_lmpc_kernel (crx_lmpc.hip:819)                  hoisted (solver), log2 domain inline (learning MPC), two pow() (path).  The
 //                          crx_path_kernel (crx_prep.hip:473)                  exponents are IPM_S_PHI / IPM_S_THETA in all three.
-//   Armijo condition       crx_solve_kernel (crx_kernels.hip:2416)             code changes in 32 of 39 solver instantiations
+//   Armijo condition       crx_solve_kernel (crx_kernels.hip:2700)             code changes in 32 of 39 solver instantiations
 //                          crx_lmpc_kernel (crx_lmpc.hip:821)                  code changes in all six instantiations
 //                          crx_path_kernel (crx_prep.hip:475)                  code changes
 //   dual safeguard         crx_path_kernel (crx_prep.hip:492-493)              DIFFERENT ARITHMETIC: mu / (kappa_sigma t) and kappa_sigma mu / t; the other
 //                                                                              two kernels clamp against mu_t = mu * rcp(t): ipm_dual_safeguard
 // Shared by all three kernels: tau, sufficient decrease, the filter entry, alpha_min and the backtrack count, every constant.  By the
 // solver and the path kernel: the barrier update, theta_min / theta_max.  By the solver and the learning-MPC kernel: the dual
-// safeguard.
+// safeguard.  By the four sites of the solver that walk it (the other two kernels factorise convex QPs and have none): the delta_w
+// schedule of the inertia correction, ipm_dw_first / ipm_dw_grow / IPM_DW_MAX.
 
 #endif

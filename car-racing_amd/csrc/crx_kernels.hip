@@ -155,7 +155,9 @@ __device__ __forceinline__ double ipow_d(double a, int p) {
 // [r8] Two-pass phases of the tuned one-obstacle instantiations <1,12,6,*> (124 rows, 127 coordinates: two passes over the 64 lanes): left alone,
 // pass 1 loads only after pass 0 has stored -- the SINK-selected store addresses may alias anything -- and the lone wave sits out one more LDS
 // round trip per phase.  A phase whose bit is set here loads the operands of BOTH passes into per-pass locals, LOADS_DONE(), then computes and
-// stores pass by pass with the expressions and the store order of the plain form (same bits: tests/test_gpu_obs1_bits.py).  All six
+// stores pass by pass.  [r13] Both forms are made of the SAME text: each phase states its operands and its arithmetic with its stores once (macros
+// in front of the `if constexpr ((LF & LF_x) != 0)`; DESIGN.md 5.1 lists them) and the two arms keep only the schedule of the loads -- same bits:
+// tests/test_gpu_obs1_bits.py for the loads-first forms, tests/test_gpu_plain_bits.py for the plain ones.  All six
 // together measured -1 % on the headline at no cost in registers (the peak is the unrolled Riccati sweep; DESIGN.md 5.1, profiles/r08_*);
 // every other instantiation keeps the plain form.
 #ifndef CRX_LOADS_FIRST
@@ -383,6 +385,18 @@ __device__ __forceinline__ void tri_decode(int e, int& r, int& a) {
 #endif
 // the adjoint / forward sweeps keep a stage's NZ numbers in lanes 0 .. NZ-1: inside one 16-lane row up to four obstacles
 template <class L> constexpr bool ROWDPP = CRX_ROWDPP && L::NZ <= 16;
+// acc + sum_i m[i] * (lane FIRST + i of x), i = 0 .. CNT-1 in that order: one DPP instruction per term where the stage fits a row (crx_wave.h
+// row_dot), v_readlane broadcasts otherwise.  Same products, same order, same bits
+template <class L, int CNT, int FIRST>
+__device__ __forceinline__ double stage_dot(double x, const double* m, double acc) {
+    if constexpr (ROWDPP<L>) {
+        acc = row_dot<CNT, FIRST>(x, m, acc);
+    } else {
+#pragma unroll
+        for (int i = 0; i < CNT; i++) acc += m[i] * lane_f64(x, FIRST + i);
+    }
+    return acc;
+}
 
 // phase clocks of the crx_trace_enable diagnostics.  s_memtime shares lgkmcnt with the LDS and returns out of order, so
 // every clock read in a sweep turns the partial waits around it into full drains: compiled in only by `make TRACE=1`
@@ -391,6 +405,10 @@ template <class L> constexpr bool ROWDPP = CRX_ROWDPP && L::NZ <= 16;
 #else
 #define CLK() 0LL
 #endif
+// the lane that writes row `it` of the crx_trace_enable diagnostics: lane 0 of the traced problem, while rows are left (trace_rows < 0: the
+// same number of rows, with the sweep's sub-phase clocks in them).  In crx_solve_kernel, over its kp and b.  (A macro: through a function or a
+// lambda the same predicate moves the code of every instantiation -- tools/kernel_diff.py, HISTORY.md round 13)
+#define TRACE_ROW(it, lane) (kp.trace && b == kp.trace_problem && (it) < (kp.trace_rows < 0 ? -kp.trace_rows : kp.trace_rows) && (lane) == 0)
 
 // ------------------------------------------------------------------------------------------------
 // (4) phases
@@ -549,7 +567,47 @@ __device__ __forceinline__ void first_order(double* sm, const int* si, const Ctx
         }
         SYNC();
     }
-    if constexpr ((LF & LF_FIRST_ORDER) != 0) {   // [r8] both passes load, then both compute (same expressions as the plain form below)
+    // The coordinate pass, stated once: the operands of coordinate e (FO_*: loads, each on a clamped index) and the gradient with its store
+    // (FO_GRADIENT).  Selects instead of branches: every divergent region costs ~30 cycles on a lone wave.  Every load is unconditional on a
+    // clamped index and selected afterwards: `cond ? LD(..) : 0` compiles to a branch around the load (LDS loads are not speculated), i.e. one
+    // more serialized LDS round trip each.  FO_GRADIENT takes its operands as expressions and reads each once, where the plain form has always
+    // loaded it: the plain form passes the loads themselves (ROWS_: the statement that yields rl, rh), the loads-first form what it loaded before.
+#define FO_CW LD(L::cst + (isx ? a : (isu ? 6 + a - L::NX : 0)))
+#define FO_XR LD(L::xr + k * 6 + (isx ? a : 0))
+#define FO_Z LD(L::Z + e)
+#define FO_NU(r) LD(L::rnu + ((r) >= 0 ? (r) : 0))
+#define FO_CBF_NU(ob) LD(L::rnu + kk * L::NR + 8 + NOBS + ob)
+#define FO_CBF_J(ob) LD(L::Jc + (kk * L::NO + ob) * L::NZ + a)
+#define FO_GRADIENT(cw_, xr_, z_, rl, rh, nl_, nh_, cnu_, cj_, ...) do { \
+        const int k = e / L::NZ, a = e - k * L::NZ; \
+        const bool isx = a < 6, isu = a >= L::NX && a < L::NX + 2, iss0 = a >= 6 && a < L::NX, iss1 = a >= L::NX + 2; \
+        const int o = iss0 ? a - 6 : (iss1 ? a - L::NX - 2 : 0); \
+        const bool sig_on = (o < c.nobs) && ((iss0 && k == 0) || (iss1 && k < N)); \
+        const double cwe = cw_, xre = xr_; \
+        const double w2 = sel(isx || isu, 2.0 * cwe, 0.0); \
+        const double ref = sel(isx, xre, 0.0); \
+        double g = w2 * (z_ - ref); \
+        g += (k == N && a == 4) ? c.lin_sN : 0.0; \
+        g += sig_on ? c.wsig : 0.0; \
+        __VA_ARGS__; \
+        const double nlo = nl_, nhi = nh_; \
+        g -= sel(rl >= 0, nlo, 0.0); \
+        g += sel(rh >= 0, nhi, 0.0); \
+        const int kk = k < N ? k : N - 1;                      /* stage terms exist for k < N only */ \
+        if (NOBS == 0) { \
+            const double de = LD(L::Z + (kk + 1) * L::NZ + 5) - LD(L::Z + kk * L::NZ + 5); \
+            const double wck = LD(L::wc + kk), m5 = LD(L::M + 5 * L::NZ + a); \
+            g += sel(k < N, 2.0 * wck * de * (m5 - (a == 5 ? 1.0 : 0.0)), 0.0); \
+        } else { \
+            _Pragma("unroll") for (int ob = 0; ob < NOBS; ob++) { \
+                const double cnu = cnu_, cje = cj_; \
+                g -= sel(k < N, cnu * cje, 0.0); \
+            } \
+        } \
+        g = (k == N && a >= L::NX) ? 0.0 : g; \
+        LD(L::ga + e) = g; \
+    } while (0)
+    if constexpr ((LF & LF_FIRST_ORDER) != 0) {   // [r8] both passes load, then both compute
         static_assert(NOBS > 0, "written for the obstacle instantiations");
         constexpr int CPASS = (L::NV + WAVE - 1) / WAVE;
         int rl[CPASS], rh[CPASS];
@@ -561,67 +619,23 @@ __device__ __forceinline__ void first_order(double* sm, const int* si, const Ctx
             (void)ev;
             const int k = e / L::NZ, a = e - k * L::NZ, kk = k < N ? k : N - 1;
             const bool isx = a < 6, isu = a >= L::NX && a < L::NX + 2;
-            cw[q_] = LD(L::cst + (isx ? a : (isu ? 6 + a - L::NX : 0))); xrv[q_] = LD(L::xr + k * 6 + (isx ? a : 0)); ze[q_] = LD(L::Z + e);
+            cw[q_] = FO_CW; xrv[q_] = FO_XR; ze[q_] = FO_Z;
 #pragma unroll
-            for (int ob = 0; ob < NOBS; ob++) { nuv[q_][ob] = LD(L::rnu + kk * L::NR + 8 + NOBS + ob); jv2[q_][ob] = LD(L::Jc + (kk * L::NO + ob) * L::NZ + a); }
+            for (int ob = 0; ob < NOBS; ob++) { nuv[q_][ob] = FO_CBF_NU(ob); jv2[q_][ob] = FO_CBF_J(ob); }
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int q_ = 0; q_ < CPASS; q_++) { nl[q_] = LD(L::rnu + (rl[q_] >= 0 ? rl[q_] : 0)); nh[q_] = LD(L::rnu + (rh[q_] >= 0 ? rh[q_] : 0)); }
+        for (int q_ = 0; q_ < CPASS; q_++) { nl[q_] = FO_NU(rl[q_]); nh[q_] = FO_NU(rh[q_]); }
         LOADS_DONE();
         COORDS(e, ev, c.lane, N * L::NZ + L::NX) {
             (void)ev;
-            const int k = e / L::NZ, a = e - k * L::NZ;
-            const bool isx = a < 6, isu = a >= L::NX && a < L::NX + 2, iss0 = a >= 6 && a < L::NX, iss1 = a >= L::NX + 2;
-            const int o = iss0 ? a - 6 : (iss1 ? a - L::NX - 2 : 0);
-            const bool sig_on = (o < c.nobs) && ((iss0 && k == 0) || (iss1 && k < N));
-            const double w2 = sel(isx || isu, 2.0 * cw[q_], 0.0);
-            const double ref = sel(isx, xrv[q_], 0.0);
-            double g = w2 * (ze[q_] - ref);
-            g += (k == N && a == 4) ? c.lin_sN : 0.0;
-            g += sig_on ? c.wsig : 0.0;
-            g -= sel(rl[q_] >= 0, nl[q_], 0.0);
-            g += sel(rh[q_] >= 0, nh[q_], 0.0);
-#pragma unroll
-            for (int ob = 0; ob < NOBS; ob++) g -= sel(k < N, nuv[q_][ob] * jv2[q_][ob], 0.0);
-            g = (k == N && a >= L::NX) ? 0.0 : g;
-            LD(L::ga + e) = g;
+            FO_GRADIENT(cw[q_], xrv[q_], ze[q_], rl[q_], rh[q_], nl[q_], nh[q_], nuv[q_][ob], jv2[q_][ob], (void)0);
         }
     } else
     COORDS(e, ev, c.lane, N * L::NZ + L::NX) {   // stage N has states only (127 entries at N=12, 1 obstacle: two passes, not three)
         (void)ev;
-        // selects instead of branches: every divergent region costs ~30 cycles on a lone wave
-        const int k = e / L::NZ, a = e - k * L::NZ;
-        const bool isx = a < 6, isu = a >= L::NX && a < L::NX + 2, iss0 = a >= 6 && a < L::NX, iss1 = a >= L::NX + 2;
-        const int o = iss0 ? a - 6 : (iss1 ? a - L::NX - 2 : 0);
-        const bool sig_on = (o < c.nobs) && ((iss0 && k == 0) || (iss1 && k < N));
-        // every load is unconditional on a clamped index and selected afterwards: `cond ? LD(..) : 0` compiles to a
-        // branch around the load (LDS loads are not speculated), i.e. one more serialized LDS round trip each
-        const double cw = LD(L::cst + (isx ? a : (isu ? 6 + a - L::NX : 0))), xrv = LD(L::xr + k * 6 + (isx ? a : 0));
-        const double w2 = sel(isx || isu, 2.0 * cw, 0.0);
-        const double ref = sel(isx, xrv, 0.0);
-        double g = w2 * (LD(L::Z + e) - ref);
-        g += (k == N && a == 4) ? c.lin_sN : 0.0;
-        g += sig_on ? c.wsig : 0.0;
         int rl, rh;
-        coord_rows<L>(si, c, e, k, a, rl, rh);
-        const double nl = LD(L::rnu + (rl >= 0 ? rl : 0)), nh = LD(L::rnu + (rh >= 0 ? rh : 0));
-        g -= sel(rl >= 0, nl, 0.0);
-        g += sel(rh >= 0, nh, 0.0);
-        const int kk = k < N ? k : N - 1;                      // stage terms exist for k < N only
-        if (NOBS == 0) {
-            const double de = LD(L::Z + (kk + 1) * L::NZ + 5) - LD(L::Z + kk * L::NZ + 5);
-            const double wck = LD(L::wc + kk), m5 = LD(L::M + 5 * L::NZ + a);
-            g += sel(k < N, 2.0 * wck * de * (m5 - (a == 5 ? 1.0 : 0.0)), 0.0);
-        } else {
-#pragma unroll
-            for (int ob = 0; ob < NOBS; ob++) {
-                const double nuv = LD(L::rnu + kk * L::NR + 8 + NOBS + ob), jv2 = LD(L::Jc + (kk * L::NO + ob) * L::NZ + a);
-                g -= sel(k < N, nuv * jv2, 0.0);
-            }
-        }
-        g = (k == N && a >= L::NX) ? 0.0 : g;
-        LD(L::ga + e) = g;
+        FO_GRADIENT(FO_CW, FO_XR, FO_Z, rl, rh, FO_NU(rl), FO_NU(rh), FO_CBF_NU(ob), FO_CBF_J(ob), coord_rows<L>(si, c, e, k, a, rl, rh));
     }
     SYNC();
 }
@@ -660,14 +674,8 @@ __device__ __forceinline__ double dual_infeasibility(double* sm, const Ctx& c) {
     LD(SINK(in, L::ga + N * L::NZ + lane)) = 0.0;
     auto stage = [&](int k) {
         const double gn = LD(L::ga + (k >= 1 ? k - 1 : 0) * L::NZ + la);   // next stage's gradient, in flight during this one
-        double t = gk;
-        if constexpr (ROWDPP<L>) {
-            t = row_dot<L::NX, 0>(tot, mcol, t);
-        } else {
-#pragma unroll
-            for (int i = 0; i < L::NX; i++) t += mcol[i] * lane_f64(tot, i);
-        }
-        tot = t;
+        const double t = gk;
+        tot = stage_dot<L, L::NX, 0>(tot, mcol, t);
         emax = fmax(emax, sel(lane >= L::NX && in, fabs(tot), 0.0));
         const bool keep = lane >= L::NX || (k == 0 && lane >= 6);
         LD(SINK(in, L::ga + k * L::NZ + lane)) = sel(keep, tot, 0.0);
@@ -725,14 +733,8 @@ __device__ __forceinline__ double box_certificate(double* sm, const int* si, con
     for (int k = N - 1; k >= 0; k--) {
         const int kn = k >= 1 ? k - 1 : 0;
         const double gn = LD(L::dZ + kn * L::NZ + la), un = LD(L::Z + kn * L::NZ + la);
-        double t = gk;
-        if constexpr (ROWDPP<L>) {
-            t = row_dot<L::NX, 0>(tot, mcol, t);
-        } else {
-#pragma unroll
-            for (int i = 0; i < L::NX; i++) t += mcol[i] * lane_f64(tot, i);
-        }
-        tot = t;
+        const double t = gk;
+        tot = stage_dot<L, L::NX, 0>(tot, mcol, t);
         const double w = -tot;                            // input lanes: (J_s' y) of input a at stage k
         S += sel(isu, w * (sel(w > 0.0, hi, -hi) - uk), 0.0);
         gk = gn; uk = un;
@@ -750,41 +752,36 @@ template <int NOBS, int NMAX, unsigned LF = 0>
 __device__ __forceinline__ void assemble_newton(double* sm, const int* si, const Ctx& c, double mu) {
     using L = Lay<NOBS, NMAX>;
     const int N = c.N;
-    if constexpr ((LF & LF_ASSEMBLE) != 0) {   // [r8] both passes load, then both compute (full layout; same expressions as the plain form below)
-        static_assert(!L::SLIM, "written for the full layout");
+    // the row pass: operands, then arithmetic and stores.  rtt = 1/t for the row-step pass (rtt is free until the line search); w = the expression
+    // of row_sig_w.  slim [r4b]: no Sigma array, and w of the row is parked in rdt for the coordinate pass below (dead from the accept pass until
+    // the row steps that follow the forward sweep; the backward sweep's P / T move in only after this function) -- the coordinate pass recomputed it
+    // per coordinate and obstacle from four LDS reads
+    // (the plain form hands ASM_ROW the loads of rs and cj themselves: each is used once, behind the store of rtt, where that form has always had them)
+#define ASM_T_NU(t, nu) t = LD(L::rt + j), nu = LD(L::rnu + j)
+#define ASM_RS row_scale<L>(sm, si, j, N)
+#define ASM_CJ LD(L::rc + j)
+#define ASM_ROW(t, nu, rs, cj) do { \
+        const double rti = frcp(t); \
+        LD(L::rtt + j) = rti; \
+        bool on; \
+        if constexpr (L::SLIM) on = (rs) != 0.0;    /* (where each layout has always looked at the row's presence: the slim one in front of */ \
+        const double sig = nu * rti; \
+        if constexpr (!L::SLIM) on = (rs) != 0.0;   /*  Sigma, the full one behind it -- the general instantiations' code moves otherwise) */ \
+        if constexpr (!L::SLIM) LD(L::rsig + j) = sel(on, sig, 0.0); \
+        const double cjv = cj; \
+        LD((L::SLIM ? L::rdt : L::rw) + j) = sel(on, nu - mu * rti + sig * (cjv - t), 0.0); \
+    } while (0)
+    if constexpr ((LF & LF_ASSEMBLE) != 0) {   // [r8] both passes load, then both compute
         constexpr int RPASS = (L::MR + WAVE - 1) / WAVE;
         double t[RPASS], nu[RPASS], rs[RPASS], cj[RPASS];
-        ROWS(j, jv, c.lane, c.m) { (void)jv; t[q_] = LD(L::rt + j); nu[q_] = LD(L::rnu + j); rs[q_] = LD(L::rsc + j); cj[q_] = LD(L::rc + j); }
+        ROWS(j, jv, c.lane, c.m) { (void)jv; ASM_T_NU(t[q_], nu[q_]); rs[q_] = ASM_RS; cj[q_] = ASM_CJ; }
         LOADS_DONE();
-        ROWS(j, jv, c.lane, c.m) {
-            (void)jv;
-            const double rti = frcp(t[q_]);
-            LD(L::rtt + j) = rti;
-            const double sig = nu[q_] * rti;
-            const bool on = rs[q_] != 0.0;
-            LD(L::rsig + j) = sel(on, sig, 0.0);
-            LD(L::rw + j) = sel(on, nu[q_] - mu * rti + sig * (cj[q_] - t[q_]), 0.0);
-        }
+        ROWS(j, jv, c.lane, c.m) { (void)jv; ASM_ROW(t[q_], nu[q_], rs[q_], cj[q_]); }
     } else
     ROWS(j, jv, c.lane, c.m) {
         (void)jv;
-        const double t = LD(L::rt + j), nu = LD(L::rnu + j);
-        const double rti = frcp(t);
-        LD(L::rtt + j) = rti;                       // 1/t for the row-step pass (rtt is free until the line search)
-        if constexpr (!L::SLIM) {
-            const double sig = nu * rti;
-            const bool on = LD(L::rsc + j) != 0.0;
-            LD(L::rsig + j) = sel(on, sig, 0.0);
-            const double cj = LD(L::rc + j);
-            LD(L::rw + j) = sel(on, nu - mu * rti + sig * (cj - t), 0.0);
-        } else {
-            // slim [r4b]: w of the row for the coordinate pass below, parked in rdt (dead from the accept pass until the row steps that
-            // follow the forward sweep; the backward sweep's P / T move in only after this function) -- the coordinate pass recomputed it per
-            // coordinate and obstacle from four LDS reads.  Same expression as row_sig_w.
-            const bool on = row_scale<L>(sm, si, j, N) != 0.0;
-            const double sg = nu * rti, cj = LD(L::rc + j);
-            LD(L::rdt + j) = sel(on, nu - mu * rti + sg * (cj - t), 0.0);
-        }
+        const double ASM_T_NU(t, nu);
+        ASM_ROW(t, nu, ASM_RS, ASM_CJ);
     }
     SYNC();
     COORDS(e, ev, c.lane, N * L::NZ + L::NX) {   // stage N has states only (127 entries at N=12, 1 obstacle: two passes, not three)
@@ -1355,12 +1352,7 @@ __device__ __forceinline__ void riccati_backward_vec(double* sm, const Ctx& c) {
             const double rD0 = LD(L::Hd + k * NZ + 0), rD1 = LD(L::Hd + k * NZ + 1), L10 = LD(L::Hd + k * NZ + 2);
             const double k0 = LD(L::Kk + (k * NU + 0) * NX + lx), k1 = LD(L::Kk + (k * NU + 1) * NX + lx);
             double hv = gk;
-            if constexpr (ROWDPP<L>) {
-                hv = row_dot<NX, 0>(p, mcol, hv);
-            } else {
-#pragma unroll
-                for (int i = 0; i < NX; i++) hv += mcol[i] * lane_f64(p, i);
-            }
+            hv = stage_dot<L, NX, 0>(p, mcol, hv);
             const double hu0 = lane_f64(hv, NX), hu1 = lane_f64(hv, NX + 1);
             const double y1 = hu1 - L10 * hu0;
             const double z1 = y1 * rD1;
@@ -1469,6 +1461,7 @@ __device__ __forceinline__ void riccati_forward(double* sm, const Ctx& c) {
         for (int j = 0; j < NX; j++) krn[j] = LD(L::Kk + (kn * NU + ua) * NX + j);
         kfn = LD(L::kf + kn * NU + ua);
         double du = kfa, xn = 0.0;
+        // (not through stage_dot: the v_readlane form broadcasts dx once for both products, and the general instantiations' code moves when it does not)
         if constexpr (ROWDPP<L>) {   // broadcast and FMA in one instruction (crx_wave.h row_dot): same terms in the same order
             du = row_dot<NX, 0>(zx, kr, du);
             xn = row_dot<NX, 0>(zx, mrow, xn);
@@ -2240,6 +2233,13 @@ crx_solve_kernel(const crx_solve_params kp) {
         if ((crash_state || kp.slack_start == 3) && crash_cand >= 0) { crash_write<NOBS, NMAX, true>(sm, c, kp, crash_cand); crash = 1; n_restore = 1; it_limit = 1 + 3 * o.restore_iters; }
     }
     init_point();
+    // the end of an iteration in both arms below, after the accepted step (numax: its largest multiplier, th: its constraint violation): IPOPT's
+    // divergence heuristic -- not a proof: CRX_STALLED -- and, where the rows are all linear and still violated after the step, the proof that they
+    // must be (box_certificate: CRX_INFEASIBLE).  Either LEAVES THE ITERATION LOOP it stands in, and the step counts as an iteration.  (A macro: as a
+    // lambda that returns the verdict the same test adds instructions to the planner instantiations -- HISTORY.md round 13)
+#define BREAK_IF_HOPELESS(numax, th) \
+        if (numax > 1e12 && th > 1e-6) { status = CRX_STALLED; it++; break; } \
+        if (NOBS == 0 && th > 1e-6) { if (box_certificate<NOBS, NMAX>(sm, si, c, kp.delta_max, kp.a_max) < -1e-8 * numax) { status = 2; it++; break; } }
     if constexpr (NOBS == 0 && QPM == 0) {
     // ---- [r6] Mehrotra's predictor-corrector for the all-linear problems (planner region QPs, MPC-CBF NLPs without an obstacle slot): a convex QP has
     // ONE solution, so the path to it is free (oracle/crx_oracle.c qp_pc_solve has the algorithm note and runs the same arithmetic
@@ -2268,21 +2268,26 @@ crx_solve_kernel(const crx_solve_params kp) {
         if (!riccati_backward<NOBS, NMAX, StageUnroll<NFIX>, 0, false, true>(sm, si, c, 0.0)) break;   // (a convex QP: cannot happen short of overflow)
         riccati_forward<NOBS, NMAX, StageUnroll<NFIX>>(sm, c);
         double dta[RP], dna[RP], rpm = 0.0, rdm = 0.0;
-#pragma unroll
-        for (int q_ = 0; q_ < RP; q_++) {
-            const bool jv = lane + q_ * WAVE < m;
-            const int j = jv ? lane + q_ * WAVE : 0;
-            const int pk = RIVT(si, j);
-            const bool on = jv && LD(L::rsc + j) != 0.0;
-            const double jd = RIV_SGN(pk) * LD(L::dZ + RIV_IDX(pk));
-            const double t = LD(L::rt + j), nu = LD(L::rnu + j), rti = LD(L::rtt + j), rcj = LD(L::rc + j), rsj = LD(L::rsig + j), rwj = LD(L::rw + j);
-            const double rp = rcj - t;
-            dta[q_] = sel(on, jd + rp, 0.0);
-            dna[q_] = sel(on, -rwj + rsj * (rp - dta[q_]), 0.0);
-            rpm = fmax(rpm, -dta[q_] * rti);                  // (absent rows: dt = 0)
-            rdm = fmax(rdm, sel(on, -dna[q_] * frcp(nu), 0.0));
-        }
-        wave_max2(rpm, rdm);
+        // the step of every row's slack and multiplier that belongs to the step dZ (the affine one, then the corrected one), and the largest
+        // -dt / t and -dnu / nu over the rows, from rpm = rdm = 0.  (A macro: as a lambda the pass costs the planner instantiations two more
+        // s_waitcnt -- HISTORY.md round 13)
+#define PC_ROW_STEPS() do { \
+        _Pragma("unroll") for (int q_ = 0; q_ < RP; q_++) { \
+            const bool jv = lane + q_ * WAVE < m; \
+            const int j = jv ? lane + q_ * WAVE : 0; \
+            const int pk = RIVT(si, j); \
+            const bool on = jv && LD(L::rsc + j) != 0.0; \
+            const double jd = RIV_SGN(pk) * LD(L::dZ + RIV_IDX(pk)); \
+            const double t = LD(L::rt + j), nu = LD(L::rnu + j), rti = LD(L::rtt + j), rcj = LD(L::rc + j), rsj = LD(L::rsig + j), rwj = LD(L::rw + j); \
+            const double rp = rcj - t; \
+            dta[q_] = sel(on, jd + rp, 0.0); \
+            dna[q_] = sel(on, -rwj + rsj * (rp - dta[q_]), 0.0); \
+            rpm = fmax(rpm, -dta[q_] * rti);                  /* (absent rows: dt = 0) */ \
+            rdm = fmax(rdm, sel(on, -dna[q_] * frcp(nu), 0.0)); \
+        } \
+        wave_max2(rpm, rdm); \
+    } while (0)
+        PC_ROW_STEPS();
         const double apa = rpm > 1.0 ? 1.0 / rpm : 1.0, ada = rdm > 1.0 ? 1.0 / rdm : 1.0;      // to the boundary
         double ga_ = 0.0;
 #pragma unroll
@@ -2330,27 +2335,13 @@ crx_solve_kernel(const crx_solve_params kp) {
             riccati_backward_vec<NOBS, NMAX, StageUnroll<NFIX>>(sm, c);
             riccati_forward<NOBS, NMAX, StageUnroll<NFIX>>(sm, c);
             rpm = 0.0; rdm = 0.0;
-#pragma unroll
-            for (int q_ = 0; q_ < RP; q_++) {
-                const bool jv = lane + q_ * WAVE < m;
-                const int j = jv ? lane + q_ * WAVE : 0;
-                const int pk = RIVT(si, j);
-                const bool on = jv && LD(L::rsc + j) != 0.0;
-                const double jd = RIV_SGN(pk) * LD(L::dZ + RIV_IDX(pk));
-                const double t = LD(L::rt + j), nu = LD(L::rnu + j), rti = LD(L::rtt + j), rcj = LD(L::rc + j), rsj = LD(L::rsig + j), rwj = LD(L::rw + j);
-                const double rp = rcj - t;
-                dta[q_] = sel(on, jd + rp, 0.0);              // the corrected step of the row's slack / multiplier
-                dna[q_] = sel(on, -rwj + rsj * (rp - dta[q_]), 0.0);
-                rpm = fmax(rpm, -dta[q_] * rti);
-                rdm = fmax(rdm, sel(on, -dna[q_] * frcp(nu), 0.0));
-            }
-            wave_max2(rpm, rdm);
+            PC_ROW_STEPS();                                   // the corrected step of the rows' slacks / multipliers
             a_p = rpm > tau ? tau / rpm : 1.0; a_d = rdm > tau ? tau / rdm : 1.0;
             if (pass == 0 && fmin(a_p, a_d) < PC_SHORT_STEP) { s_old = s_new; c_old = 1.0; s_new = fmax(mu_k, o.tol / 10.0); continue; }
             break;
         }
         static_assert(L::MR <= L::NV, "row scratch inside dZ");
-        if (kp.trace && b == kp.trace_problem && it < (kp.trace_rows < 0 ? -kp.trace_rows : kp.trace_rows) && lane == 0) {
+        if (TRACE_ROW(it, lane)) {
             double* tr = kp.trace + (size_t)it * 16;
             tr[0] = e_du / sd; tr[1] = e_p; tr[2] = cmax / sd; tr[3] = mu_k; tr[4] = a_p; tr[5] = a_d; tr[6] = sigma; tr[7] = 1.0;
         }
@@ -2392,10 +2383,7 @@ crx_solve_kernel(const crx_solve_params kp) {
         gap = gs;
         e_p = th;
         first_order<NOBS, NMAX>(sm, si, c);
-        if (numax > 1e12 && th > 1e-6) { status = CRX_STALLED; it++; break; }   // IPOPT's divergence heuristic: not a proof
-        if (th > 1e-6) {   // still violated after the step: look for the proof that it must be
-            if (box_certificate<NOBS, NMAX>(sm, si, c, kp.delta_max, kp.a_max) < -1e-8 * numax) { status = 2; it++; break; }
-        }
+        BREAK_IF_HOPELESS(numax, th)
     }
     f = cost_value<NOBS, NMAX>(sm, c, 0.0);
     } else {
@@ -2485,11 +2473,11 @@ crx_solve_kernel(const crx_solve_params kp) {
         // iterations in a row, and the sweep notices at its far end: the longest solve of the headline batch spent 17 % of its clocks on
         // attempts that were bound to fail.  Same rule in oracle/crx_oracle.c; problems off the crash path never get here.)
         int used_convex = 0;
+        // the convexified matrix: WITHOUT the reverse-convex part of the CBF curvature (-nu hess g_{k+1}, the kS / kE terms; the next assemble_newton
+        // rebuilds them).  (A macro: as a lambda or a function the loop moves code and registers of the 2- and 3-obstacle instantiations -- HISTORY.md round 13)
+#define CONVEXIFY() do { for (int k = lane; k < N; k += WAVE) { LD(L::kS + 2 * k) = 0.0; LD(L::kE + 2 * k) = 0.0; } SYNC(); } while (0)
         if (NOBS && crash && cvx_run > 0 && (cvx_run % CVX_PROBE) != 0) {
-            if constexpr (!SPEC) {
-                for (int k = lane; k < N; k += WAVE) { LD(L::kS + 2 * k) = 0.0; LD(L::kE + 2 * k) = 0.0; }
-                SYNC();
-            }
+            if constexpr (!SPEC) CONVEXIFY();
             used_convex = 1;
         }
         if constexpr (SPEC) {
@@ -2503,8 +2491,8 @@ crx_solve_kernel(const crx_solve_params kp) {
                 double ndw = sdw;
                 int ncz = cz, ntries = tries;
                 if (avail) ncz = 1;
-                else { ndw = tries == 0 ? (dw_last == 0.0 ? 1e-4 : fmax(1e-20, dw_last / 3.0)) : sdw * (dw_last == 0.0 ? 100.0 : 8.0); ntries = tries + 1; }
-                const bool nvalid = !(ndw > 1e40);
+                else { ndw = tries == 0 ? ipm_dw_first(dw_last) : ipm_dw_grow(sdw, dw_last); ntries = tries + 1; }
+                const bool nvalid = !(ndw > IPM_DW_MAX);
                 const bool post = nvalid && kp.spec_idle == 0;      // (spec_idle: diagnostics -- the second wave is never asked: the schedule runs one attempt at a time)
                 if (lane == 0) { LD(L::ctl) = post ? 1.0 : 2.0; LD(L::ctl + 1) = ndw; LD(L::ctl + 2) = ncz ? 1.0 : 0.0; }
                 __syncthreads();
@@ -2512,7 +2500,7 @@ crx_solve_kernel(const crx_solve_params kp) {
                 __syncthreads();
                 if (ok) { dw = sdw; used_convex = cz; break; }
                 dw = ndw;
-                if (!nvalid) break;                               // the schedule is exhausted (sequential: dw > 1e40)
+                if (!nvalid) break;                               // the schedule is exhausted (sequential: dw > IPM_DW_MAX)
                 if (!post) { sdw = ndw; cz = ncz; avail = 0; tries = ntries; continue; }
                 if (__builtin_amdgcn_readfirstlane((int)LD(L::ctl + 3)) != 0) {
                     for (int e = lane; e < N * L::NU * NX; e += WAVE) LD(L::Kk + e) = LD(L::Kk2 + e);
@@ -2523,10 +2511,10 @@ crx_solve_kernel(const crx_solve_params kp) {
                     break;
                 }
                 // both have the wrong inertia: two steps down the schedule (after S' the convexified retry is behind us)
-                sdw = ntries == 0 ? (dw_last == 0.0 ? 1e-4 : fmax(1e-20, dw_last / 3.0)) : ndw * (dw_last == 0.0 ? 100.0 : 8.0);
+                sdw = ntries == 0 ? ipm_dw_first(dw_last) : ipm_dw_grow(ndw, dw_last);
                 cz = ncz; avail = 0; tries = ntries + 1;
                 dw = sdw;
-                if (sdw > 1e40) break;
+                if (sdw > IPM_DW_MAX) break;
             }
         } else if constexpr (RSH) {
             // [r9] the same schedule, run by the sweep function between its attempts (riccati_backward<.., SHARED>): one set-up per Newton system
@@ -2534,16 +2522,15 @@ crx_solve_kernel(const crx_solve_params kp) {
             auto retry = [&](double& dwr) -> bool {
                 if (NOBS && __builtin_amdgcn_readfirstlane((int)(crash && !used_convex)) != 0) {   // crash path (iii), as below
                     used_convex = 1;
-                    for (int k = lane; k < N; k += WAVE) { LD(L::kS + 2 * k) = 0.0; LD(L::kE + 2 * k) = 0.0; }
-                    SYNC();
+                    CONVEXIFY();
                     return true;
                 }
                 // (from an opaque copy of dw_last: the first step and the factor of the schedule are formed when an attempt has failed, not in front
                 // of the attempts and carried through every sweep)
                 double dwl = dw_last;
                 asm volatile("" : "+v"(dwl));
-                dwr = dwr == 0.0 ? (dwl == 0.0 ? 1e-4 : fmax(1e-20, dwl / 3.0)) : dwr * (dwl == 0.0 ? 100.0 : 8.0);
-                return !(dwr > 1e40);
+                dwr = dwr == 0.0 ? ipm_dw_first(dwl) : ipm_dw_grow(dwr, dwl);
+                return !(dwr > IPM_DW_MAX);
             };
             ok = riccati_backward<NOBS, NMAX, StageUnroll<NFIX>, 0, false, false, true>(sm, si, c, 0.0, tsub, false, retry, &dw);
         } else
@@ -2552,17 +2539,15 @@ crx_solve_kernel(const crx_solve_params kp) {
             if (ok) break;
             if (NOBS && !convex) {
                 used_convex = 1;
-                // [r4] crash path (iii): first retry WITHOUT the reverse-convex part of the CBF curvature (-nu hess g_{k+1}, the kS / kE
-                // terms): what remains -- cost, J' Sigma J, the "current" curvature -- is positive definite by construction; IPOPT's
-                // delta_w schedule only if rounding makes even that fail.  (kS / kE are rebuilt by the next assemble_newton.)
+                // [r4] crash path (iii): first retry convexified: what remains -- cost, J' Sigma J, the "current" curvature -- is positive
+                // definite by construction; IPOPT's delta_w schedule only if rounding makes even that fail.
                 convex = 1;
-                for (int k = lane; k < N; k += WAVE) { LD(L::kS + 2 * k) = 0.0; LD(L::kE + 2 * k) = 0.0; }
-                SYNC();
+                CONVEXIFY();
                 continue;
             }
-            dw = tries == 0 ? (dw_last == 0.0 ? 1e-4 : fmax(1e-20, dw_last / 3.0)) : dw * (dw_last == 0.0 ? 100.0 : 8.0);
+            dw = tries == 0 ? ipm_dw_first(dw_last) : ipm_dw_grow(dw, dw_last);
             tries++;
-            if (dw > 1e40) break;
+            if (dw > IPM_DW_MAX) break;
         }
         if (!ok) break;
         if (dw != 0.0) dw_last = dw;
@@ -2587,11 +2572,20 @@ crx_solve_kernel(const crx_solve_params kp) {
             theta += sel(cnt && on, fabs(rp), 0.0);
             Dphi -= sel(cnt && on, mu * dtr, 0.0);
         };
+        // the operands of a row step, each stated once: the row's own state with Sigma and w (on_: what row_sig_w is told about the row's presence -- the
+        // loads-first form loads for every row and selects in the tail), and for a simple row its table entry, its scale and J dz from the step
+        // entry the table points to
+#define STEP_ROW_STATE(on_, t, nu, rti, rcj, rsj, rwj) \
+        t = LD(L::rt + j), nu = LD(L::rnu + j), rti = LD(L::rtt + j), rcj = LD(L::rc + j); row_sig_w<L>(sm, j, on_, mu, t, nu, rti, rcj, rsj, rwj)
+#define ROW_PK RIVT(si, j)
+#define ROW_SC row_scale<L>(sm, si, j, N)
+#define STEP_DZ(pk) LD(L::dZ + RIV_IDX(pk))
+#define STEP_JD(pk, dz) (RIV_SGN(pk) * dz)
+#define ROW_ON(sc) (sc != 0.0)
         auto row_step = [&](int j, bool cnt, bool store, double sc, double jd) {
-            const bool on = sc != 0.0;
-            const double t = LD(L::rt + j), nu = LD(L::rnu + j), rti = LD(L::rtt + j), rcj = LD(L::rc + j);
+            const bool on = ROW_ON(sc);
             double rwj, rsj;
-            row_sig_w<L>(sm, j, on, mu, t, nu, rti, rcj, rsj, rwj);
+            const double STEP_ROW_STATE(on, t, nu, rti, rcj, rsj, rwj);
             ROW_LOADS_DONE();
             row_step_tail(j, cnt, store, on, jd, t, nu, rti, rcj, rsj, rwj);
         };
@@ -2600,27 +2594,26 @@ crx_solve_kernel(const crx_solve_params kp) {
         if constexpr ((LF & LF_ROW_STEP) != 0) {   // full layout: row_scale and row_sig_w are loads
             int pk[RPASS];
             double sc[RPASS], dz[RPASS], t[RPASS], nu[RPASS], rti[RPASS], rcj[RPASS], rsj[RPASS], rwj[RPASS];
-            ROWS(j, jv, lane, m) { (void)jv; pk[q_] = RIVT(si, j); }
+            ROWS(j, jv, lane, m) { (void)jv; pk[q_] = ROW_PK; }
             __builtin_amdgcn_sched_barrier(0);   // the table entries first: they are back by the time the other loads have been issued
             ROWS(j, jv, lane, m) {
                 (void)jv;
-                sc[q_] = row_scale<L>(sm, si, j, N);
-                t[q_] = LD(L::rt + j); nu[q_] = LD(L::rnu + j); rti[q_] = LD(L::rtt + j); rcj[q_] = LD(L::rc + j);
-                row_sig_w<L>(sm, j, true, mu, t[q_], nu[q_], rti[q_], rcj[q_], rsj[q_], rwj[q_]);
+                sc[q_] = ROW_SC;
+                STEP_ROW_STATE(true, t[q_], nu[q_], rti[q_], rcj[q_], rsj[q_], rwj[q_]);
             }
             __builtin_amdgcn_sched_barrier(0);   // ... and the loads that need them go last
 #pragma unroll
-            for (int q_ = 0; q_ < RPASS; q_++) dz[q_] = LD(L::dZ + RIV_IDX(pk[q_]));
+            for (int q_ = 0; q_ < RPASS; q_++) dz[q_] = STEP_DZ(pk[q_]);
             LOADS_DONE();
             ROWS(j, jv, lane, m) {
                 const bool simple = !ROW_IS_CBF(j, N);
-                row_step_tail(j, jv && simple, simple, sc[q_] != 0.0, RIV_SGN(pk[q_]) * dz[q_], t[q_], nu[q_], rti[q_], rcj[q_], rsj[q_], rwj[q_]);
+                row_step_tail(j, jv && simple, simple, ROW_ON(sc[q_]), STEP_JD(pk[q_], dz[q_]), t[q_], nu[q_], rti[q_], rcj[q_], rsj[q_], rwj[q_]);
             }
         } else
         ROWS(j, jv, lane, m) {
             const bool simple = !ROW_IS_CBF(j, N);
-            const int pk = RIVT(si, j);
-            const double sc = row_scale<L>(sm, si, j, N), jd = RIV_SGN(pk) * LD(L::dZ + RIV_IDX(pk));
+            const int pk = ROW_PK;
+            const double sc = ROW_SC, jd = STEP_JD(pk, STEP_DZ(pk));
             row_step(j, jv && simple, simple, sc, jd);
         }
         if (NOBS) {
@@ -2666,20 +2659,23 @@ crx_solve_kernel(const crx_solve_params kp) {
                 lg.mul(sel(cnt, tn, 1.0));
                 thn += sel(cnt, fabs(cn - tn), 0.0);
             };
+            // the simple rows: operands, then arithmetic and stores (linear rows: the trial value is exact)
+#define TRIAL_LOADS(sc, t, dt, cj) sc = row_scale<L>(sm, si, j, N), t = LD(L::rt + j), dt = LD(L::rdt + j), cj = LD(L::rc + j)
+#define TRIAL_SIMPLE(sc, t, dt, cj) row_trial(j, jv && simple, simple, sc, cj + al * (dt - (cj - t)), t, dt)
             if constexpr ((LF & LF_ROW_TRIAL) != 0) {
                 double sc[RPASS], t[RPASS], dt[RPASS], cj[RPASS];
-                ROWS(j, jv, lane, m) { (void)jv; sc[q_] = row_scale<L>(sm, si, j, N); t[q_] = LD(L::rt + j); dt[q_] = LD(L::rdt + j); cj[q_] = LD(L::rc + j); }
+                ROWS(j, jv, lane, m) { (void)jv; TRIAL_LOADS(sc[q_], t[q_], dt[q_], cj[q_]); }
                 LOADS_DONE();
                 ROWS(j, jv, lane, m) {
                     const bool simple = !ROW_IS_CBF(j, N);
-                    row_trial(j, jv && simple, simple, sc[q_], cj[q_] + al * (dt[q_] - (cj[q_] - t[q_])), t[q_], dt[q_]);
+                    TRIAL_SIMPLE(sc[q_], t[q_], dt[q_], cj[q_]);
                 }
             } else
             ROWS(j, jv, lane, m) {
                 const bool simple = !ROW_IS_CBF(j, N);
-                const double sc = row_scale<L>(sm, si, j, N), t = LD(L::rt + j), dt = LD(L::rdt + j), cj = LD(L::rc + j);
+                const double TRIAL_LOADS(sc, t, dt, cj);
                 ROW_LOADS_DONE();
-                row_trial(j, jv && simple, simple, sc, cj + al * (dt - (cj - t)), t, dt);   // linear rows: exact
+                TRIAL_SIMPLE(sc, t, dt, cj);
             }
             if (NOBS) {
                 CBF_ROWS(j, k, ob, ev, lane, N) {   // evaluated at Z + al dZ
@@ -2712,7 +2708,7 @@ crx_solve_kernel(const crx_solve_params kp) {
         tph[0] = tc1 - tc0; tph[1] = tc2 - tc1; tph[2] = tc3 - tc2; tph[3] = tc4 - tc3; tph[4] = tc5 - tc4;
         tph[5] = tc6 - tc5; tph[6] = tc7 - tc6; tph[7] = tc8 - tc7;
         if (kp.trace_rows < 0) { tph[0] = tsub[0]; tph[1] = tsub[1]; tph[2] = tsub[2]; tph[3] = tsub[3]; }
-        if (kp.trace && b == kp.trace_problem && it < (kp.trace_rows < 0 ? -kp.trace_rows : kp.trace_rows) && lane == 0) {
+        if (TRACE_ROW(it, lane)) {
             double* tr = kp.trace + (size_t)it * 16;
             for (int q = 0; q < 8; q++) tr[8 + q] = (double)(tph[q]);
             tr[0] = e_d; tr[1] = e_p; tr[2] = e_c; tr[3] = mu; tr[4] = al; tr[5] = a_d; tr[6] = dw; tr[7] = acc ? (ftype ? 2.0 : 1.0) : 0.0;
@@ -2733,18 +2729,17 @@ crx_solve_kernel(const crx_solve_params kp) {
         }
         // ---- accept ------------------------------------------------------------------------------------
         SYNC();
+#define Z_LOADS(zo, dz) zo = LD(L::Z + e), dz = LD(L::dZ + e)
+#define Z_STEP(zo, dz) do { const double zn = zo + al * dz; LD(SINK(ev, L::Z + e)) = zn; } while (0)   /* read-modify-write */
         if constexpr ((LF & LF_ACCEPT_Z) != 0) {
             double zo[CPASS], dz[CPASS];
-            COORDS(e, ev, lane, N * NZ + NX) { (void)ev; zo[q_] = LD(L::Z + e); dz[q_] = LD(L::dZ + e); }
+            COORDS(e, ev, lane, N * NZ + NX) { (void)ev; Z_LOADS(zo[q_], dz[q_]); }
             LOADS_DONE();
-            COORDS(e, ev, lane, N * NZ + NX) {
-                const double zn = zo[q_] + al * dz[q_];
-                LD(SINK(ev, L::Z + e)) = zn;
-            }
+            COORDS(e, ev, lane, N * NZ + NX) Z_STEP(zo[q_], dz[q_]);
         } else
         COORDS(e, ev, lane, N * NZ + NX) {
-            const double zn = LD(L::Z + e) + al * LD(L::dZ + e);
-            LD(SINK(ev, L::Z + e)) = zn;                // read-modify-write
+            const double Z_LOADS(zo, dz);
+            Z_STEP(zo, dz);
         }
         SYNC();
         f = fn;
@@ -2770,37 +2765,43 @@ crx_solve_kernel(const crx_solve_params kp) {
             cmin = fmin(cmin, sel(cnt, tn * nn, INFINITY));
             LD(SINK(own, L::rc + j)) = sel(on, v, 1.0);
         };
+        // the operands of an accepted row, each stated once: the row's pre-step state with Sigma and w (on_ as in the row steps; slim: 1/t is
+        // recomputed -- rtt holds the trial slack by now; frcp(t) returns what assemble_newton stored -- the full layout does not read it), and for
+        // a simple row (ROW_PK, ROW_SC above) its value at the new iterate from the entry of Z the table points to and its bound
+#define ACCEPT_ROW_STATE(on_, tn, rcj, rtj, rdj, rnj, rsj, rwj) \
+        tn = LD(L::rtt + j), rcj = LD(L::rc + j), rtj = LD(L::rt + j), rdj = LD(L::rdt + j), rnj = LD(L::rnu + j); \
+        row_sig_w<L>(sm, j, on_, mu, rtj, rnj, L::SLIM ? frcp(rtj) : 0.0, rcj, rsj, rwj)
+#define ACCEPT_Z(pk) LD(L::Z + RIV_IDX(pk))
+#define ACCEPT_RB row_bound<L>(sm, c, j)
+#define ACCEPT_V(pk, z, rb) (RIV_SGN(pk) * (z - rb))
         auto row_accept = [&](int j, bool own, double sc, double v) {   // own: this lane is the one that updates row j
-            const bool on = sc != 0.0;
-            const double tn = LD(L::rtt + j), rcj = LD(L::rc + j), rtj = LD(L::rt + j);
-            const double rdj = LD(L::rdt + j), rnj = LD(L::rnu + j);
-            double rwj, rsj;   // (slim: 1/t is recomputed -- rtt holds the trial slack by now; frcp(t) returns what assemble_newton stored)
-            row_sig_w<L>(sm, j, on, mu, rtj, rnj, L::SLIM ? frcp(rtj) : 0.0, rcj, rsj, rwj);
+            const bool on = ROW_ON(sc);
+            double rwj, rsj;
+            const double ACCEPT_ROW_STATE(on, tn, rcj, rtj, rdj, rnj, rsj, rwj);
             ROW_LOADS_DONE();
             row_accept_tail(j, own, on, v, tn, rcj, rtj, rdj, rnj, rsj, rwj);
         };
         if constexpr ((LF & LF_ROW_ACCEPT) != 0) {   // full layout: row_scale, row_bound and row_sig_w are loads
             int pk[RPASS];
             double sc[RPASS], zv[RPASS], rb[RPASS], tn[RPASS], rcj[RPASS], rtj[RPASS], rdj[RPASS], rnj[RPASS], rsj[RPASS], rwj[RPASS];
-            ROWS(j, jv, lane, m) { (void)jv; pk[q_] = RIVT(si, j); }
+            ROWS(j, jv, lane, m) { (void)jv; pk[q_] = ROW_PK; }
             __builtin_amdgcn_sched_barrier(0);   // the table entries first: they are back by the time the other loads have been issued
             ROWS(j, jv, lane, m) {
                 (void)jv;
-                sc[q_] = row_scale<L>(sm, si, j, N); rb[q_] = row_bound<L>(sm, c, j);
-                tn[q_] = LD(L::rtt + j); rcj[q_] = LD(L::rc + j); rtj[q_] = LD(L::rt + j); rdj[q_] = LD(L::rdt + j); rnj[q_] = LD(L::rnu + j);
-                row_sig_w<L>(sm, j, true, mu, rtj[q_], rnj[q_], 0.0, rcj[q_], rsj[q_], rwj[q_]);
+                sc[q_] = ROW_SC; rb[q_] = ACCEPT_RB;
+                ACCEPT_ROW_STATE(true, tn[q_], rcj[q_], rtj[q_], rdj[q_], rnj[q_], rsj[q_], rwj[q_]);
             }
             __builtin_amdgcn_sched_barrier(0);   // (as in the row steps: the loads that need the table entry go last)
 #pragma unroll
-            for (int q_ = 0; q_ < RPASS; q_++) zv[q_] = LD(L::Z + RIV_IDX(pk[q_]));
+            for (int q_ = 0; q_ < RPASS; q_++) zv[q_] = ACCEPT_Z(pk[q_]);
             LOADS_DONE();
             ROWS(j, jv, lane, m) {
-                row_accept_tail(j, jv && !ROW_IS_CBF(j, N), sc[q_] != 0.0, RIV_SGN(pk[q_]) * (zv[q_] - rb[q_]), tn[q_], rcj[q_], rtj[q_], rdj[q_], rnj[q_], rsj[q_], rwj[q_]);
+                row_accept_tail(j, jv && !ROW_IS_CBF(j, N), ROW_ON(sc[q_]), ACCEPT_V(pk[q_], zv[q_], rb[q_]), tn[q_], rcj[q_], rtj[q_], rdj[q_], rnj[q_], rsj[q_], rwj[q_]);
             }
         } else
         ROWS(j, jv, lane, m) {
-            const int pk = RIVT(si, j);
-            const double sc = row_scale<L>(sm, si, j, N), v = RIV_SGN(pk) * (LD(L::Z + RIV_IDX(pk)) - row_bound<L>(sm, c, j));
+            const int pk = ROW_PK;
+            const double sc = ROW_SC, v = ACCEPT_V(pk, ACCEPT_Z(pk), ACCEPT_RB);
             row_accept(j, jv && !ROW_IS_CBF(j, N), sc, v);
         }
         if (NOBS) {
@@ -2822,13 +2823,9 @@ crx_solve_kernel(const crx_solve_params kp) {
         nus = wave_sum(nus);
         e_p = th;
         first_order<NOBS, NMAX, LF>(sm, si, c);
-        if (kp.trace && b == kp.trace_problem && it < (kp.trace_rows < 0 ? -kp.trace_rows : kp.trace_rows) && lane == 0 && kp.trace_rows > 0)
+        if (TRACE_ROW(it, lane) && kp.trace_rows > 0)
             kp.trace[(size_t)it * 16 + 8] = (double)(tph[0] + (CLK() - tc8));   // slot 8: KKT rows + accept/first-order
-        if (numax > 1e12 && th > 1e-6) { status = CRX_STALLED; it++; break; }   // IPOPT's divergence heuristic: not a proof
-        // still violated after the step: look for the proof that it must be (linear rows only)
-        if (NOBS == 0 && th > 1e-6) {
-            if (box_certificate<NOBS, NMAX>(sm, si, c, kp.delta_max, kp.a_max) < -1e-8 * numax) { status = 2; it++; break; }
-        }
+        BREAK_IF_HOPELESS(numax, th)
     }
     if (!ls_failed) break;
     // [r4] crash path (ii): the solve started at the reference's zero point and stalls on violated CBF rows -- restart ONCE from the

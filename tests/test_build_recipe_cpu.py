@@ -87,6 +87,26 @@ def test_kernel_diff_tells_moved_from_differs():
     assert kd.verdict_of((text, desc, None), (text, desc, None)) == "differs (meta)"                                # no metadata entry: not comparable
 
 
+def test_kernel_diff_tells_renamed_from_differs():
+    """Other .text bytes under the same mnemonic at every position, with descriptor (but for the entry offset) and metadata equal: `renamed`."""
+    import kernel_diff as kd
+
+    meta, desc = [".name: k", ".vgpr_count: 7"], bytes(range(64))
+    moved = desc[:16] + (0x1234).to_bytes(8, "little") + desc[24:]
+    mn = ["s_load_dword", "v_mov_b32_e32", "v_fma_f64", "s_endpgm"]
+    old = (b"\x01\x02\x03\x04", desc, meta, mn)
+    assert kd.verdict_of(old, (b"\x01\x02\x03\x05", desc, meta, list(mn))) == "renamed"
+    assert kd.verdict_of(old, (b"\x01\x02\x03\x05", moved, meta, list(mn))) == "renamed"
+    assert kd.verdict_of(old, (b"\x01\x02\x03\x05", desc, meta, [mn[0], mn[2], mn[1], mn[3]])) == "differs (text)"       # the same instructions in another order
+    assert kd.verdict_of(old, (b"\x01\x02\x03\x05", desc, meta, mn + ["s_nop"])) == "differs (text)"
+    assert kd.verdict_of(old, (b"\x01\x02\x03\x05", desc, meta[:1], list(mn))) == "differs (text, meta)"                  # a resource changed
+    assert kd.verdict_of(old, (b"\x01\x02\x03\x05", desc[:48] + b"\xff" + desc[49:], meta, list(mn))) == "differs (text, kd)"
+    assert kd.verdict_of(old[:3], (b"\x01\x02\x03\x05", desc, meta)) == "differs (text)"                                 # not disassembled: no claim
+    # the disassembly is read per function symbol, mnemonics only
+    txt = "\nDisassembly of section .text:\n\n0000000000001700 <k>:\n\ts_load_dword s3, s[0:1], 0x4      // 000000001700: C00200C0\n\ts_endpgm\n\n0000000000001800 <f>:\n\tv_mov_b32_e32 v0, v1\n"
+    assert kd.mnemonics_of(txt) == {"k": ["s_load_dword", "s_endpgm"], "f": ["v_mov_b32_e32"]}
+
+
 def _dynsyms(lib):
     out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
     return sorted(l.split()[-1] for l in out.splitlines() if l.split() and "__hip_cuid_" not in l)

@@ -109,5 +109,5 @@ def path_plan(desc, qdesc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, ob
     return binding().path_plan(desc, qdesc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey, opt_vx, active, target)
 
 
-def plant_step(desc, track, xglob, xcurv, u):
-    return binding().plant_step(desc, track, xglob, xcurv, u)
+def plant_step(desc, track, xglob, xcurv, u, params=None):
+    return binding().plant_step(desc, track, xglob, xcurv, u, params=params)

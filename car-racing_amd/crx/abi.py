@@ -364,6 +364,26 @@ def plant_desc(n_seg, lap_length, timestep=0.1, dt_sub=0.001):
     return PlantDesc(n_sub, int(n_seg), dt_sub, lap_length, 1.98, 0.125, 0.125, 0.024, D, 1.25, 1.0, D, 1.25, 1.0)
 
 
+CRX_PLANT_NPARAM = 10
+PLANT_PARAM_NAMES = ("m", "lf", "lr", "Iz", "Df", "Cf", "Bf", "Dr", "Cr", "Br")   # BicycleDynamicsParam.get_params() (utils/base.py), = the PlantDesc fields
+
+
+def plant_params(batch, dynamics_params=None):
+    """[batch, 10] float64 rows (m, lf, lr, Iz, Df, Cf, Bf, Dr, Cr, Br) for the `params` argument of the plant entries: None = the
+    BicycleDynamicsParam defaults for every car (the ten values of plant_desc), one object with get_params() = that set for every car, a
+    sequence of `batch` such objects = one set per car."""
+    if dynamics_params is None:
+        d = plant_desc(1, 1.0)
+        rows = [[getattr(d, n) for n in PLANT_PARAM_NAMES]] * batch
+    elif hasattr(dynamics_params, "get_params"):
+        rows = [list(dynamics_params.get_params())] * batch
+    else:
+        rows = [list(p.get_params()) for p in dynamics_params]
+        if len(rows) != batch:
+            raise ValueError("plant_params: %d parameter sets for %d cars" % (len(rows), batch))
+    return _in(np.array(rows, dtype=np.float64).reshape(batch, CRX_PLANT_NPARAM), _D, (batch, CRX_PLANT_NPARAM))
+
+
 def select_desc(N, n_veh_max, lap_length, veh_length=0.4, veh_width=0.2):
     """overtake_traj_planner.py:209,223,243 literals."""
     return SelectDesc(int(N), int(n_veh_max), veh_length, veh_width, lap_length, 10.0, 100.0, 100.0)
@@ -391,7 +411,7 @@ class Binding:
         self.lib, self.prefix = lib, prefix
         for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve", "ilqr_solve",
                      "ilqr_solve_models", "lqr_design", "sysid_fit", "cbf_solve_models", "planner_solve_models", "planner_plan",
-                     "planner_plan_models", "path_prep", "path_plan"):
+                     "planner_plan_models", "path_prep", "path_plan", "plant_step_params"):
             if hasattr(lib, prefix + name):
                 getattr(lib, prefix + name).restype = C.c_int
         self._check = None
@@ -666,13 +686,20 @@ class Binding:
                    _p(out["bez_ey"]), _p(out["ey_lb"]), _p(out["ey_ub"]))
         return out
 
-    def plant_step(self, desc, track, xglob, xcurv, u):
-        """crx_plant_step: one control step of the zero-noise plant for a batch of vehicles."""
+    def plant_step(self, desc, track, xglob, xcurv, u, params=None):
+        """crx_plant_step: one control step of the zero-noise plant for a batch of vehicles.  params [Bn,10] float64 (plant_params):
+        crx_plant_step_params, vehicle b on its own BicycleDynamicsParam set (desc's ten values are ignored); a row with m <= 0, Iz <= 0
+        or a non-finite value is refused."""
         xglob = np.ascontiguousarray(xglob, dtype=_D)
         Bn = xglob.shape[0]
         track = _in(track, _D, (desc.n_seg, 6))
         xglob, xcurv, u = _in(xglob, _D, (Bn, 6)), _in(xcurv, _D, (Bn, 6)), _in(u, _D, (Bn, 2))
         out = dict(xglob=np.zeros((Bn, 6)), xcurv=np.zeros((Bn, 6)))
+        if params is not None:
+            params = _in(params, _D, (Bn, CRX_PLANT_NPARAM))
+            self._call("plant_step_params", C.byref(desc), C.c_int(Bn), _p(track), _p(xglob), _p(xcurv), _p(u), _p(params),
+                       _p(out["xglob"]), _p(out["xcurv"]))
+            return out
         self._call("plant_step", C.byref(desc), C.c_int(Bn), _p(track), _p(xglob), _p(xcurv), _p(u), _p(out["xglob"]),
                    _p(out["xcurv"]))
         return out

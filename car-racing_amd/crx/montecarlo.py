@@ -185,10 +185,10 @@ class Concurrent:
 class _Plant:
     """The plant side of a closed loop, held by the loop object itself: the cars' states xc (curvilinear) / xg (global) [B,6], the
     buffers xc_next / xg_next the next plant launch writes, the lap counters, the track table, the plant descriptor and the
-    process noise.  _advance() is the one place a loop steps its plant.  The contract bench.py times the solver launches by:
+    process noise, and plant_params: one parameter set per car [B,10], or None.  _advance() is the one place a loop steps its plant.  The contract bench.py times the solver launches by:
     after a step, xc_next is the state that step's solver launch was built for."""
 
-    def _plant_init(self, track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device):
+    def _plant_init(self, track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params=None):
         dev = torch.device(device if device is not None else "cuda")
         self.device, self.lap_length, self.timestep = dev, lap_length, timestep
         self.noise = _Noise(noise_seed, dev)
@@ -198,6 +198,14 @@ class _Plant:
         self.laps = torch.zeros(self.batch, dtype=torch.int32, device=dev)
         self.tab = _dev(track_table, dev)
         self.plant = abi.plant_desc(self.tab.shape[0], lap_length, timestep=timestep)
+        # plant_params [B,10] (abi.plant_params, synth.fleet_plant_params), host array or device tensor: every car its own BicycleDynamicsParam
+        # set (crx_plant_step_params_dev).  None: the one set of self.plant for all of them
+        self.plant_params = None
+        if plant_params is not None:
+            P = plant_params.to(dtype=torch.float64, device=dev) if torch.is_tensor(plant_params) else _dev(plant_params, dev)
+            if tuple(P.shape) != (self.batch, abi.CRX_PLANT_NPARAM):
+                raise ValueError("plant_params: expected shape %s, got %s" % ((self.batch, abi.CRX_PLANT_NPARAM), tuple(P.shape)))
+            self.plant_params = P.contiguous()
         return dev
 
     def _advance(self, u, u_stride, noise_z=None):
@@ -207,7 +215,7 @@ class _Plant:
         if noise_z is None:
             noise_z = self.noise.draw(self.batch)
         torch_api.plant_step_wrap_dev(self.plant, self.tab, self.xg, self.xc, u, u_stride, self.xg_next, self.xc_next, self.laps,
-                                      noise_z=noise_z)
+                                      noise_z=noise_z, params=self.plant_params)
         self.xg, self.xg_next = self.xg_next, self.xg
         self.xc, self.xc_next = self.xc_next, self.xc
 
@@ -235,8 +243,8 @@ class MpccbfRaces(_Plant):
     """State of B races on the device; step() advances all of them by one control step."""
 
     def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, car_s0, car_v, car_ey,
-                 vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1, device=None, noise_seed=None, models=None):
-        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device)
+                 vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1, device=None, noise_seed=None, models=None, plant_params=None):
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params)
         f64 = dict(dtype=torch.float64, device=dev)
         self.s0, self.v, self.ey = (_dev(a, dev) for a in (car_s0, car_v, car_ey))
         Bn, V = self.s0.shape
@@ -293,7 +301,7 @@ class MpccbfRaces(_Plant):
         torch_api.cbf_solve_dev(self.desc, xc, self.xt, ps.contiguous(), pe.contiguous(), po.contiguous(), n_obs.contiguous(),
                                 ws=self.ws, models=self.models)
         self.u = self.ws.U[:, 0, :].contiguous()
-        self.xg, xc = torch_api.plant_step_dev(self.plant, self.tab, self.xg, xc, self.u)
+        self.xg, xc = torch_api.plant_step_dev(self.plant, self.tab, self.xg, xc, self.u, params=self.plant_params)
         crossed = xc[:, 4] > L
         xc[:, 4] = torch.where(crossed, xc[:, 4] - L, xc[:, 4])
         self.laps += crossed.to(torch.int32)
@@ -302,12 +310,12 @@ class MpccbfRaces(_Plant):
 
 
 def mpccbf_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, steps,
-                 vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1, device=None, log_every=1, glue=False, models=None):
+                 vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1, device=None, log_every=1, glue=False, models=None, plant_params=None):
     """xcurv0, xglob0 [B,6]; car_s0, car_v, car_ey [B,V] with V <= 3: scripted cars s(t) = v t + s0, ey(t) = ey
-    (NoDynamicsModel, utils/base.py:847-890); models = (A [B,6,6], B [B,6,2]): one controller model per race.  Returns host arrays: xcurv [T+1,B,6] (T = steps/log_every), u [T,B,2],
+    (NoDynamicsModel, utils/base.py:847-890); models = (A [B,6,6], B [B,6,2]): one controller model per race; plant_params [B,10]: one car per race.  Returns host arrays: xcurv [T+1,B,6] (T = steps/log_every), u [T,B,2],
     status [T,B], laps [B]."""
     r = MpccbfRaces(track_table, lap_length, track_width, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, vt=vt, eyt=eyt,
-                    N=N, alpha=alpha, timestep=timestep, device=device, models=models)
+                    N=N, alpha=alpha, timestep=timestep, device=device, models=models, plant_params=plant_params)
     logs = _run_and_log(r.step_glue if glue else r.step, steps, log_every,
                         dict(xcurv=lambda: r.xc, u=lambda: r.u, status=lambda: r.ws.status))
     return dict(logs, laps=r.laps.cpu().numpy())
@@ -320,8 +328,9 @@ class IlqrRaces(_Plant):
     (int(s_ego / L) - int(s_obs,0 / L)) L (quirk I5), ONE crx_ilqr_solve_dev over all races, ONE crx_plant_step_wrap_dev."""
 
     def __init__(self, track_table, lap_length, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, vt=0.8, eyt=0.0, N=50,
-                 max_iter=150, timestep=0.1, ego_dims=(0.4, 0.2), car_dims=(0.4, 0.2), device=None, noise_seed=None, models=None):
-        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device)
+                 max_iter=150, timestep=0.1, ego_dims=(0.4, 0.2), car_dims=(0.4, 0.2), device=None, noise_seed=None, models=None,
+                 plant_params=None):
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params)
         f64 = dict(dtype=torch.float64, device=dev)
         self.s0, self.v, self.ey = (_dev(np.asarray(a, dtype=float).reshape(-1, 1), dev) for a in (car_s0, car_v, car_ey))
         self.N, Bn = N, self.batch
@@ -355,12 +364,12 @@ class IlqrRaces(_Plant):
 
 
 def ilqr_races(track_table, lap_length, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, steps, vt=0.8, eyt=0.0, N=50, max_iter=150,
-               timestep=0.1, device=None, log_every=1, models=None):
+               timestep=0.1, device=None, log_every=1, models=None, plant_params=None):
     """xcurv0, xglob0 [B,6]; car_s0, car_v, car_ey [B]: one scripted car per race; models = (A [B,6,6], B [B,6,2]): one model per
-    race (host arrays or device tensors).  Returns host arrays: xcurv [T+1,B,6] (T = steps / log_every), u [T,B,2], status [T,B],
+    race (host arrays or device tensors); plant_params [B,10]: one car per race.  Returns host arrays: xcurv [T+1,B,6] (T = steps / log_every), u [T,B,2], status [T,B],
     iters [T,B], laps [B]."""
     r = IlqrRaces(track_table, lap_length, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, vt=vt, eyt=eyt, N=N, max_iter=max_iter,
-                  timestep=timestep, device=device, models=models)
+                  timestep=timestep, device=device, models=models, plant_params=plant_params)
     logs = _run_and_log(r.step, steps, log_every,
                         dict(xcurv=lambda: r.xc, u=lambda: r.u, status=lambda: r.ws.status, iters=lambda: r.ws.iters))
     return dict(logs, laps=r.laps.cpu().numpy())
@@ -387,8 +396,8 @@ class LmpcLaps(_Plant):
     of safe-set storage are full (it then keeps racing on its last two laps)."""
 
     def __init__(self, track_table, lap_length, track_width, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
-                 N=12, timestep=0.1, device=None, noise_seed=None):
-        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device)
+                 N=12, timestep=0.1, device=None, noise_seed=None, plant_params=None):
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params)
         f64 = dict(dtype=torch.float64, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         self.ss, self.us, self.qf = (_dev(a, dev, clone=True) for a in (ss_xcurv, u_ss, qfun))
@@ -483,12 +492,12 @@ class LmpcLaps(_Plant):
 
 
 def lmpc_laps(track_table, lap_length, track_width, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input, steps,
-              N=12, timestep=0.1, device=None, noise_seed=None):
-    """Run `steps` control steps of B learning-MPC laps; returns host logs xcurv [steps+1, B, 6], u [steps, B, 2], status [steps, B]
+              N=12, timestep=0.1, device=None, noise_seed=None, plant_params=None):
+    """Run `steps` control steps of B learning-MPC laps (plant_params [B,10]: one car per lap); returns host logs xcurv [steps+1, B, 6], u [steps, B, 2], status [steps, B]
     (QP status), prep_status [steps, B] (singular regression: the stage keeps its previous / zero model rows), laps [B],
     traj_status [B] (lap hand-over: 1 = safe-set storage full)."""
     r = LmpcLaps(track_table, lap_length, track_width, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input, N=N,
-                 timestep=timestep, device=device, noise_seed=noise_seed)
+                 timestep=timestep, device=device, noise_seed=noise_seed, plant_params=plant_params)
     logs = _run_and_log(r.step, steps, 1, dict(xcurv=lambda: r.xc, u=lambda: r.u_old, status=lambda: r.ws.status,
                                                prep_status=lambda: r.pws.status))
     return dict(logs, laps=r.laps.cpu().numpy(),
@@ -524,16 +533,16 @@ class GameLaps:
         crx_cbf_solve_dev          the tracking NLP
     with the scene, the masks, the commit (which takes the path planner's flag) and the learning-MPC branch as they are.  alpha =
     racing_game_param.alpha, the weight of the Bezier reference in the path QPs.  models = only the tracking NLP has dynamics here.
-    planner = "traj" (default) is the loop above, call for call."""
+    planner = "traj" (default) is the loop above, call for call.  plant_params [B,10]: one car per race, handed to `lm`, which holds the plant."""
 
     def __init__(self, track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0,
                  lin_points, lin_input, car_s0, car_v, car_ey, N=12, N_plan=10, timestep=0.1, device=None, noise_seed=None, models=None,
-                 planner="traj", alpha=0.98):
+                 planner="traj", alpha=0.98, plant_params=None):
         if planner not in ("traj", "path"):
             raise ValueError("planner must be 'traj' or 'path', got %r" % (planner,))
         self.planner = planner
         self.lm = LmpcLaps(track_table, lap_length, track_width, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
-                           N=N, timestep=timestep, device=device, noise_seed=noise_seed)
+                           N=N, timestep=timestep, device=device, noise_seed=noise_seed, plant_params=plant_params)
         lm = self.lm
         lm._dispatch_of = self         # bench.py sets `dispatch` on the game
         dev = lm.device
@@ -690,12 +699,13 @@ class GameLaps:
 
 
 def game_laps(track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
-              car_s0, car_v, car_ey, steps, device=None, noise_seed=None, models=None, planner="traj", alpha=0.98):
+              car_s0, car_v, car_ey, steps, device=None, noise_seed=None, models=None, planner="traj", alpha=0.98, plant_params=None):
     """Run `steps` control steps of B racing-game laps with scripted traffic; models = (A [B,6,6], B [B,6,2]): the overtake branch of
     every race (region QPs, tracking NLP) on its own model.  planner = "path": the overtake path planner (GameLaps) in that branch.  Host logs: xcurv [steps+1, B, 6], u [steps, B, 2],
     overtake [steps, B] (which branch), flag [steps, B] (direction flag, -1 in the LMPC branch), cars_s [steps, B, V], laps [B]."""
     r = GameLaps(track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
-                 car_s0, car_v, car_ey, device=device, noise_seed=noise_seed, models=models, planner=planner, alpha=alpha)
+                 car_s0, car_v, car_ey, device=device, noise_seed=noise_seed, models=models, planner=planner, alpha=alpha,
+                 plant_params=plant_params)
     logs = _run_and_log(r.step, steps, 1, dict(xcurv=lambda: r.lm.xc, u=lambda: r.u, overtake=lambda: r.overtake.bool(),
                                                flag=lambda: r.old_flag, cars_s=lambda: r.v * r.t + r.s0),
                         before=("cars_s",))    # where the scripted cars are when the step plans
@@ -710,11 +720,12 @@ class PidLaps(_Plant):
     that logs the step's row and computes the next input.  x_log [B,T,6] holds xcurv_log (s wrapped, S2) and u_log [B,T,2]
     what get_udata assembles from it (S5: u[k] = the input applied in the step that produced x[k]).
     Noise: noise_z [T,B,3] standard-normal draws (the reference's three randn per step, in call order), else a device generator
-    seeded with noise_seed; both None = zero noise."""
+    seeded with noise_seed; both None = zero noise.  plant_params [B,10]: every car its own BicycleDynamicsParam set, so that identify()
+    returns the models of B different cars."""
 
     def __init__(self, track_table, lap_length, xcurv0, xglob0, steps, vt=0.5, eyt=0.0, timestep=0.1, noise_z=None,
-                 noise_seed=None, device=None):
-        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device)
+                 noise_seed=None, device=None, plant_params=None):
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params)
         f64 = dict(dtype=torch.float64, device=dev)
         Bn, T = self.batch, int(steps)
         self.steps = T
@@ -753,10 +764,10 @@ class PidLaps(_Plant):
 
 
 def pid_laps(track_table, lap_length, xcurv0, xglob0, steps, vt=0.5, eyt=0.0, timestep=0.1, noise_z=None, noise_seed=None,
-             device=None):
+             device=None, plant_params=None):
     """PidLaps run to the end: the logs stay on the device (r.x_log, r.u_log); r.identify(lamb) fits them."""
     return PidLaps(track_table, lap_length, xcurv0, xglob0, steps, vt=vt, eyt=eyt, timestep=timestep, noise_z=noise_z,
-                   noise_seed=noise_seed, device=device).run()
+                   noise_seed=noise_seed, device=device, plant_params=plant_params).run()
 
 
 class LqrLaps(_Plant):
@@ -768,8 +779,8 @@ class LqrLaps(_Plant):
     and drives NaN inputs: `design.status` says which."""
 
     def __init__(self, track_table, lap_length, xcurv0, xglob0, A, B, Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]), R=np.diag([0.1, 0.1]),
-                 vt=0.8, eyt=0.0, max_iter=50, eps=0.01, timestep=0.1, device=None, noise_seed=None):
-        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device)
+                 vt=0.8, eyt=0.0, max_iter=50, eps=0.01, timestep=0.1, device=None, noise_seed=None, plant_params=None):
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params)
         f64 = dict(dtype=torch.float64, device=dev)
         Bn = self.batch
         self.A, self.B = _models(A, B, Bn, dev)
@@ -787,11 +798,11 @@ class LqrLaps(_Plant):
 
 
 def lqr_laps(track_table, lap_length, xcurv0, xglob0, steps, A, B, Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]), R=np.diag([0.1, 0.1]),
-             vt=0.8, eyt=0.0, max_iter=50, eps=0.01, timestep=0.1, device=None, noise_seed=None, log_every=1):
-    """xcurv0, xglob0 [B,6]; A, B as in LqrLaps.  Returns host arrays: xcurv [T+1,B,6] (T = steps / log_every), u [T,B,2], K [B,2,6],
+             vt=0.8, eyt=0.0, max_iter=50, eps=0.01, timestep=0.1, device=None, noise_seed=None, log_every=1, plant_params=None):
+    """xcurv0, xglob0 [B,6]; A, B as in LqrLaps; plant_params [B,10]: one car per row.  Returns host arrays: xcurv [T+1,B,6] (T = steps / log_every), u [T,B,2], K [B,2,6],
     design_status [B], design_iters [B], laps [B]."""
     r = LqrLaps(track_table, lap_length, xcurv0, xglob0, A, B, Q=Q, R=R, vt=vt, eyt=eyt, max_iter=max_iter, eps=eps, timestep=timestep,
-                device=device, noise_seed=noise_seed)
+                device=device, noise_seed=noise_seed, plant_params=plant_params)
     logs = _run_and_log(r.step, steps, log_every, dict(xcurv=lambda: r.xc, u=lambda: r.u))
     return dict(logs, K=r.K.cpu().numpy(),
                 design_status=r.design.status.cpu().numpy(), design_iters=r.design.iters.cpu().numpy(), laps=r.laps.cpu().numpy())

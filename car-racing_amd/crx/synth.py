@@ -231,3 +231,13 @@ def multi_tests_traffic(n, num_veh=3, seed=0):
     s0 = 3.0 + rng.integers(0, 15, (n, num_veh))
     ey = 0.7 - 0.1 * rng.integers(0, 15, (n, num_veh))
     return s0.astype(float), v.astype(float), ey.astype(float)
+
+
+def fleet_plant_params(batch, spread, seed):
+    """A fleet of `batch` different cars for the `plant_params` argument of the closed loops (crx.montecarlo): [batch, 10] float64 rows
+    (m, lf, lr, Iz, Df, Cf, Bf, Dr, Cr, Br), every entry its BicycleDynamicsParam default times 1 + spread * U(-1, 1), drawn
+    independently.  spread = 0: `batch` copies of the defaults, bit for bit."""
+    from . import abi
+
+    rng = np.random.Generator(np.random.PCG64(seed))
+    return abi.plant_params(batch) * (1.0 + spread * rng.uniform(-1.0, 1.0, (batch, abi.CRX_PLANT_NPARAM)))

@@ -484,8 +484,9 @@ def planner_prep_dev(desc, x_wrapped, x_raw, n_veh, veh_info, max_dv, obs_s, obs
     return ws
 
 
-def plant_step_dev(desc, track, xglob, xcurv, u, xglob_next=None, xcurv_next=None):
-    """crx_plant_step_dev; returns (xglob_next, xcurv_next) (allocated unless given)."""
+def plant_step_dev(desc, track, xglob, xcurv, u, xglob_next=None, xcurv_next=None, params=None):
+    """crx_plant_step_dev; returns (xglob_next, xcurv_next) (allocated unless given).  params [B,10]: one BicycleDynamicsParam set per
+    vehicle (abi.plant_params; crx_plant_step_params_plain_dev), None = desc's ten values for every vehicle."""
     Bn = xglob.shape[0]
     _chk(track, torch.float64, (desc.n_seg, 6), "track")
     _chk(xglob, torch.float64, (Bn, 6), "xglob")
@@ -493,6 +494,11 @@ def plant_step_dev(desc, track, xglob, xcurv, u, xglob_next=None, xcurv_next=Non
     _chk(u, torch.float64, (Bn, 2), "u")
     xglob_next = torch.empty_like(xglob) if xglob_next is None else xglob_next
     xcurv_next = torch.empty_like(xcurv) if xcurv_next is None else xcurv_next
+    if params is not None:
+        _chk(params, torch.float64, (Bn, 10), "params")
+        _call("crx_plant_step_params_plain_dev", C.byref(desc), C.c_int(Bn), _ptr(track), _ptr(xglob), _ptr(xcurv), _ptr(u), _ptr(params),
+              _ptr(xglob_next), _ptr(xcurv_next), _stream())
+        return xglob_next, xcurv_next
     _call("crx_plant_step_dev", C.byref(desc), C.c_int(Bn), _ptr(track), _ptr(xglob), _ptr(xcurv), _ptr(u),
           _ptr(xglob_next), _ptr(xcurv_next), _stream())
     return xglob_next, xcurv_next
@@ -512,10 +518,11 @@ def cbf_prep_dev(N, lap_length, t, dt, xcurv, car_s0, car_v, car_ey, obs_s, obs_
           _ptr(obs_ey), _ptr(lap_off), _ptr(n_obs), _stream())
 
 
-def plant_step_wrap_dev(desc, track, xglob, xcurv, u, u_stride, xglob_next, xcurv_next, laps, noise_z=None):
+def plant_step_wrap_dev(desc, track, xglob, xcurv, u, u_stride, xglob_next, xcurv_next, laps, noise_z=None, params=None):
     """crx_plant_step_wrap_dev: plant step + lap bookkeeping; `u` may be a strided view's base tensor (u_stride doubles
     between vehicles, e.g. the U output of cbf_solve_dev with u_stride = 2 N).  noise_z [B,3]: standard-normal draws for the
-    reference's bounded process noise (utils/base.py:929-939; crx_plant_step_noise_dev), None = zero noise."""
+    reference's bounded process noise (utils/base.py:929-939; crx_plant_step_noise_dev), None = zero noise.  params [B,10]: one
+    BicycleDynamicsParam set per vehicle (abi.plant_params; crx_plant_step_params_dev), None = desc's ten values for every vehicle."""
     Bn = xglob.shape[0]
     _chk(track, torch.float64, (desc.n_seg, 6), "track")
     _chk(xglob, torch.float64, (Bn, 6), "xglob")
@@ -527,6 +534,11 @@ def plant_step_wrap_dev(desc, track, xglob, xcurv, u, u_stride, xglob_next, xcur
         raise ValueError("u: expected a contiguous cuda float64 tensor holding %d inputs at stride %d" % (Bn, u_stride))
     if noise_z is not None:
         _chk(noise_z, torch.float64, (Bn, 3), "noise_z")
+    if params is not None:
+        _chk(params, torch.float64, (Bn, 10), "params")
+        _call("crx_plant_step_params_dev", C.byref(desc), C.c_int(Bn), _ptr(track), _ptr(xglob), _ptr(xcurv), _ptr(u), C.c_int(u_stride),
+              _ptr(noise_z), _ptr(params), _ptr(xglob_next), _ptr(xcurv_next), _ptr(laps), _stream())
+        return
     _call("crx_plant_step_noise_dev", C.byref(desc), C.c_int(Bn), _ptr(track), _ptr(xglob), _ptr(xcurv), _ptr(u),
           C.c_int(u_stride), _ptr(noise_z), _ptr(xglob_next), _ptr(xcurv_next), _ptr(laps), _stream())
 

@@ -973,7 +973,10 @@ void crx_plant_desc_default(crx_plant_desc* d, int n_seg, double lap_length) {
     d->Dr = 0.8 * 1.98 * 9.81 / 2.0; d->Cr = 1.25; d->Br = 1.0;
 }
 
-static int check_plant(const crx_plant_desc* d, int batch, int u_stride, arr track, arr xglob, arr xcurv, arr u, arr xglob_next, arr xcurv_next) {
+// host_params: the [batch][CRX_PLANT_NPARAM] rows of a host-pointer entry (NULL: none, or on the device where they cannot be read), held to what
+// the descriptor's own ten values are held to, and finite
+static int check_plant(const crx_plant_desc* d, int batch, int u_stride, arr track, arr xglob, arr xcurv, arr u, arr xglob_next, arr xcurv_next,
+                       const double* host_params = nullptr) {
     if (int rc = ensure_init()) return rc;
     if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
     if (d->n_sub < 0 || d->n_seg < 1 || d->n_seg > 64) return fail(CRX_ERR_ARG, "n_sub < 0 or n_seg outside [1,64]");
@@ -981,33 +984,54 @@ static int check_plant(const crx_plant_desc* d, int batch, int u_stride, arr tra
     if (batch < 0) return fail(CRX_ERR_ARG, "batch < 0");
     if (u_stride < 2) return fail(CRX_ERR_ARG, "u_stride < 2");
     if (batch > 0 && any_null(track, xglob, xcurv, u, xglob_next, xcurv_next)) return fail(CRX_ERR_ARG, "NULL array argument");
+    for (int b = 0; host_params && b < batch; b++) {
+        const double* r = host_params + (size_t)CRX_PLANT_NPARAM * b;
+        bool ok = r[0] > 0.0 && r[3] > 0.0;
+        for (int i = 0; i < CRX_PLANT_NPARAM; i++) ok = ok && isfinite(r[i]);
+        if (!ok) return fail(CRX_ERR_ARG, "params of car %d: m and Iz must be positive, all %d values finite", b, CRX_PLANT_NPARAM);
+    }
     return 0;
+}
+
+// the one launch behind every plant entry: params NULL = the descriptor's ten values for every vehicle (crx_plant_kernel), else one row per
+// vehicle (crx_plant_cars_kernel)
+static int plant_launch(const crx_plant_desc* d, int batch, int wrap, const double* track, const double* xglob, const double* xcurv,
+                        const double* u, int u_stride, const double* noise_z, const double* params, double* xglob_next, double* xcurv_next,
+                        int32_t* laps, void* stream) {
+    if (int rc = check_plant(d, batch, u_stride, track, xglob, xcurv, u, xglob_next, xcurv_next)) return rc;
+    if (batch == 0) return CRX_OK;
+    crx_plant_kparams_cars pk;
+    pk.d = *d; pk.batch = batch; pk.u_stride = u_stride; pk.wrap = wrap; pk.track = track; pk.xglob = xglob; pk.xcurv = xcurv; pk.u = u;
+    pk.xglob_next = xglob_next; pk.xcurv_next = xcurv_next; pk.laps = laps; pk.noise_z = noise_z; pk.params = params;
+    if (params) return launched(crx_launch_plant_cars(pk, (hipStream_t)stream), "plant (per-car parameters)");
+    return launched(crx_launch_plant(pk, (hipStream_t)stream), "plant");
 }
 
 int crx_plant_step_dev(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
                        const double* u, double* xglob_next, double* xcurv_next, void* stream) {
-    if (int rc = check_plant(d, batch, 2, track, xglob, xcurv, u, xglob_next, xcurv_next)) return rc;
-    if (batch == 0) return CRX_OK;
-    crx_plant_kparams pk;
-    pk.d = *d; pk.batch = batch; pk.u_stride = 2; pk.wrap = 0; pk.track = track; pk.xglob = xglob; pk.xcurv = xcurv; pk.u = u;
-    pk.xglob_next = xglob_next; pk.xcurv_next = xcurv_next; pk.laps = nullptr; pk.noise_z = nullptr;
-    return launched(crx_launch_plant(pk, (hipStream_t)stream), "plant");
+    return plant_launch(d, batch, 0, track, xglob, xcurv, u, 2, nullptr, nullptr, xglob_next, xcurv_next, nullptr, stream);
 }
 
 int crx_plant_step_wrap_dev(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
                             const double* u, int u_stride, double* xglob_next, double* xcurv_next, int32_t* laps, void* stream) {
-    return crx_plant_step_noise_dev(d, batch, track, xglob, xcurv, u, u_stride, nullptr, xglob_next, xcurv_next, laps, stream);
+    return plant_launch(d, batch, 1, track, xglob, xcurv, u, u_stride, nullptr, nullptr, xglob_next, xcurv_next, laps, stream);
 }
 
 int crx_plant_step_noise_dev(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
                              const double* u, int u_stride, const double* noise_z, double* xglob_next, double* xcurv_next,
                              int32_t* laps, void* stream) {
-    if (int rc = check_plant(d, batch, u_stride, track, xglob, xcurv, u, xglob_next, xcurv_next)) return rc;
-    if (batch == 0) return CRX_OK;
-    crx_plant_kparams pk;
-    pk.d = *d; pk.batch = batch; pk.u_stride = u_stride; pk.wrap = 1; pk.track = track; pk.xglob = xglob; pk.xcurv = xcurv; pk.u = u;
-    pk.xglob_next = xglob_next; pk.xcurv_next = xcurv_next; pk.laps = laps; pk.noise_z = noise_z;
-    return launched(crx_launch_plant(pk, (hipStream_t)stream), "plant");
+    return plant_launch(d, batch, 1, track, xglob, xcurv, u, u_stride, noise_z, nullptr, xglob_next, xcurv_next, laps, stream);
+}
+
+int crx_plant_step_params_dev(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
+                              const double* u, int u_stride, const double* noise_z, const double* params, double* xglob_next,
+                              double* xcurv_next, int32_t* laps, void* stream) {
+    return plant_launch(d, batch, 1, track, xglob, xcurv, u, u_stride, noise_z, params, xglob_next, xcurv_next, laps, stream);
+}
+
+int crx_plant_step_params_plain_dev(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
+                                    const double* u, const double* params, double* xglob_next, double* xcurv_next, void* stream) {
+    return plant_launch(d, batch, 0, track, xglob, xcurv, u, 2, nullptr, params, xglob_next, xcurv_next, nullptr, stream);
 }
 
 int crx_cbf_prep_dev(int N, int V, double lap_length, double t, double dt, double safety_time, int batch,
@@ -1026,16 +1050,22 @@ int crx_cbf_prep_dev(int N, int V, double lap_length, double t, double dt, doubl
 
 int crx_plant_step(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
                    const double* u, double* xglob_next, double* xcurv_next) {
-    if (int rc = check_plant(d, batch, 2, track, xglob, xcurv, u, xglob_next, xcurv_next)) return rc;
+    return crx_plant_step_params(d, batch, track, xglob, xcurv, u, nullptr, xglob_next, xcurv_next);
+}
+
+int crx_plant_step_params(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
+                          const double* u, const double* params, double* xglob_next, double* xcurv_next) {
+    if (int rc = check_plant(d, batch, 2, track, xglob, xcurv, u, xglob_next, xcurv_next, params)) return rc;
     if (batch == 0) return CRX_OK;
+    const size_t B = (size_t)batch;
     std::lock_guard<std::mutex> lk(g_mu);
     HIP_TRY(hipSetDevice(g_device));
-    const size_t B = (size_t)batch;
     Stage sg;
     auto dtr = sg.in(track, (size_t)d->n_seg * 6); auto dg = sg.in(xglob, B * 6); auto dc = sg.in(xcurv, B * 6); auto du = sg.in(u, B * 2);
+    auto dpr = params ? sg.in(params, B * CRX_PLANT_NPARAM) : Stage::Ref<double>{};   // unused: sg[dpr] is NULL
     auto dgn = sg.out(xglob_next, B * 6); auto dcn = sg.out(xcurv_next, B * 6);
     if (int rc = sg.up(g_stream)) return rc;
-    if (int rc = crx_plant_step_dev(d, batch, sg[dtr], sg[dg], sg[dc], sg[du], sg[dgn], sg[dcn], g_stream)) return rc;
+    if (int rc = crx_plant_step_params_plain_dev(d, batch, sg[dtr], sg[dg], sg[dc], sg[du], sg[dpr], sg[dgn], sg[dcn], g_stream)) return rc;
     return sg.down(g_stream);
 }
 

@@ -129,6 +129,12 @@ struct crx_plant_kparams {
     const double* noise_z;   // optional [batch][3] standard-normal draws: the bounded process noise of base.py:929-939
 };
 
+// crx_plant_cars_kernel (crx_prep.hip).  Derived, so that crx_plant_kparams -- which crx_plant_kernel takes by value -- keeps its size and
+// the code object behind the shared-parameter launches stays what it is.
+struct crx_plant_kparams_cars : crx_plant_kparams {
+    const double* params;   // [batch][CRX_PLANT_NPARAM]: m, lf, lr, Iz, Df, Cf, Bf, Dr, Cr, Br of each vehicle; d's ten values are unused
+};
+
 struct crx_cbfprep_kparams {
     int N, V, batch;
     double lap_length, t, dt, safety_time;
@@ -223,6 +229,7 @@ struct crx_game_kparams {
 };
 hipError_t crx_launch_game(int which, const crx_game_kparams& gp, hipStream_t st);
 hipError_t crx_launch_plant(const crx_plant_kparams& pk, hipStream_t st);
+hipError_t crx_launch_plant_cars(const crx_plant_kparams_cars& pk, hipStream_t st);
 hipError_t crx_launch_prep(const crx_prep_kparams& pp, hipStream_t st);
 hipError_t crx_launch_scene(const crx_scene_kparams& sp, hipStream_t st);
 hipError_t crx_launch_trackprep(const crx_trackprep_kparams& tp, hipStream_t st);

@@ -1,6 +1,7 @@
 // crx_prep.hip -- the small kernels around the solvers:
 //   crx_prep_kernel     planner host prep: Bezier references and per-stage ey bounds of every region of a scenario
 //   crx_plant_kernel    one control step of the plant for a batch of vehicles
+//   crx_plant_cars_kernel   the same step with one BicycleDynamicsParam set per vehicle (params[batch][10])
 //   crx_cbfprep_kernel  obstacle arrays of control.mpccbf for scripted cars
 //   crx_path_kernel     the 1-D QPs of the overtake PATH planner
 //
@@ -247,68 +248,41 @@ hipError_t crx_launch_prep(const crx_prep_kparams& pp, hipStream_t st) {
 // ------------------------------------------------------------------------------------------------
 #define CRX_PLANT_MAX_SEG 64
 
-__global__ void __launch_bounds__(256) crx_plant_kernel(const crx_plant_kparams pk) {
-    __shared__ double seg_lo[CRX_PLANT_MAX_SEG], seg_hi[CRX_PLANT_MAX_SEG], seg_cv[CRX_PLANT_MAX_SEG];
-    const crx_plant_desc& d = pk.d;
-    for (int i = threadIdx.x; i < d.n_seg; i += blockDim.x) {
-        seg_lo[i] = pk.track[6 * i + 3];
-        seg_hi[i] = pk.track[6 * i + 3] + pk.track[6 * i + 4];
-        seg_cv[i] = pk.track[6 * i + 5];
-    }
-    __syncthreads();
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= pk.batch) return;
-    double vx = pk.xcurv[6 * b], vy = pk.xcurv[6 * b + 1], wz = pk.xcurv[6 * b + 2];
-    double epsi = pk.xcurv[6 * b + 3], s = pk.xcurv[6 * b + 4], ey = pk.xcurv[6 * b + 5];
-    double psi = pk.xglob[6 * b + 3], X = pk.xglob[6 * b + 4], Y = pk.xglob[6 * b + 5];
-    const double delta = pk.u[(size_t)pk.u_stride * b], acc = pk.u[(size_t)pk.u_stride * b + 1], dt = d.dt_sub;
-    const double sd = sin(delta), cd = cos(delta);
-    for (int it = 0; it < d.n_sub; it++) {
-        // curvature at s (wrapped into one lap), first segment with lo <= s <= hi
-        double sw = s;
-        sw = wrap_below(wrap_above(sw, d.lap_length), d.lap_length);
-        double curv = 0.0;
-        for (int i = 0; i < d.n_seg; i++)
-            if (sw >= seg_lo[i] && sw <= seg_hi[i]) { curv = seg_cv[i]; break; }
-        // tyre slip angles and lateral forces (the reference uses lf for the rear axle too, :25)
-        const double slip_f = delta - atan2(vy + d.lf * wz, vx);
-        const double slip_r = -atan2(vy - d.lf * wz, vx);
-        const double Fyf = 2 * d.Df * sin(d.Cf * atan(d.Bf * slip_f));
-        const double Fyr = 2 * d.Dr * sin(d.Cr * atan(d.Br * slip_r));
-        const double dvx = acc - 1 / d.m * Fyf * sd + wz * vy;
-        const double dvy = 1 / d.m * (Fyf * cd + Fyr) - wz * vx;
-        const double dwz = 1 / d.Iz * (d.lf * Fyf * cd - d.lr * Fyr);
-        const double ce = cos(epsi), se = sin(epsi), cp = cos(psi), sp = sin(psi);
-        const double v_long = (vx * ce - vy * se) / (1 - curv * ey);
-        const double psi_n = psi + dt * wz;
-        const double X_n = X + dt * (vx * cp - vy * sp), Y_n = Y + dt * (vx * sp + vy * cp);
-        const double epsi_n = epsi + dt * (wz - v_long * curv);
-        const double s_n = s + dt * v_long;
-        const double ey_n = ey + dt * (vx * se + vy * ce);
-        const double vx_n = vx + dt * dvx, vy_n = vy + dt * dvy, wz_n = wz + dt * dwz;
-        vx = vx_n; vy = vy_n; wz = wz_n; epsi = epsi_n; s = s_n; ey = ey_n; psi = psi_n; X = X_n; Y = Y_n;
-    }
-    if (pk.wrap && s > d.lap_length) {   // ModelBase.update_memory (base.py:795-819)
-        s -= d.lap_length;
-        if (pk.laps) pk.laps[b] += 1;
-    }
-    double* g = pk.xglob_next + 6 * (size_t)b;
-    double* c = pk.xcurv_next + 6 * (size_t)b;
-    g[0] = vx; g[1] = vy; g[2] = wz; g[3] = psi; g[4] = X; g[5] = Y;
-    if (pk.noise_z) {
-        // bounded process noise (utils/base.py:929-939): clip(z sigma, +-lim), HALF of it added to the curvilinear velocities
-        // only -- the global-frame copy stays clean (the next step reads its velocities from xcurv, vehicle_dynamics.py:17-19)
-        const double* z = pk.noise_z + 3 * (size_t)b;
-        vx += 0.5 * fmax(-0.05, fmin(z[0] * 0.01, 0.05));
-        vy += 0.5 * fmax(-0.1, fmin(z[1] * 0.01, 0.1));
-        wz += 0.5 * fmax(-0.05, fmin(z[2] * 0.005, 0.05));
-    }
-    c[0] = vx; c[1] = vy; c[2] = wz; c[3] = epsi; c[4] = s; c[5] = ey;
-}
+// The step is written once, in crx_plant_step.h.  crx_plant_kernel: the ten BicycleDynamicsParam values are the descriptor's, uniform over the
+// launch.  crx_plant_cars_kernel (crx_plant_step_params_dev): car b's own row params[10 b ..], in the order of BicycleDynamicsParam.get_params()
+// (m, lf, lr, Iz, Df, Cf, Bf, Dr, Cr, Br), read into registers before the sub-step loop.  Everything else comes from the descriptor either way.
+#define CRX_PLANT_KERNEL crx_plant_kernel
+#define CRX_PLANT_KPARAMS crx_plant_kparams
+#define CRX_PLANT_READ_PARAMS(pk, b)
+#define CRX_PLANT_P(name) d.name
+#include "crx_plant_step.h"
+#undef CRX_PLANT_KERNEL
+#undef CRX_PLANT_KPARAMS
+#undef CRX_PLANT_READ_PARAMS
+#undef CRX_PLANT_P
+
+#define CRX_PLANT_KERNEL crx_plant_cars_kernel
+#define CRX_PLANT_KPARAMS crx_plant_kparams_cars
+#define CRX_PLANT_READ_PARAMS(pk, b)                                                                                                  \
+    const double* row = pk.params + CRX_PLANT_NPARAM * (size_t)b;                                                                     \
+    const double car_m = row[0], car_lf = row[1], car_lr = row[2], car_Iz = row[3], car_Df = row[4], car_Cf = row[5], car_Bf = row[6], \
+                 car_Dr = row[7], car_Cr = row[8], car_Br = row[9];
+#define CRX_PLANT_P(name) car_##name
+#include "crx_plant_step.h"
+#undef CRX_PLANT_KERNEL
+#undef CRX_PLANT_KPARAMS
+#undef CRX_PLANT_READ_PARAMS
+#undef CRX_PLANT_P
 
 hipError_t crx_launch_plant(const crx_plant_kparams& pk, hipStream_t st) {
     if (pk.batch == 0) return hipSuccess;
     hipLaunchKernelGGL(crx_plant_kernel, dim3((pk.batch + 255) / 256), dim3(256), 0, st, pk);
+    return hipGetLastError();
+}
+
+hipError_t crx_launch_plant_cars(const crx_plant_kparams_cars& pk, hipStream_t st) {
+    if (pk.batch == 0) return hipSuccess;
+    hipLaunchKernelGGL(crx_plant_cars_kernel, dim3((pk.batch + 255) / 256), dim3(256), 0, st, pk);
     return hipGetLastError();
 }
 

@@ -44,7 +44,9 @@
 extern "C" {
 #endif
 
-#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_planner_models_reach_dev, crx_planner_solve_models, crx_planner_solve_models_dev,
+#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_plant_step_params, crx_plant_step_params_dev, crx_plant_step_params_plain_dev and
+                          CRX_PLANT_NPARAM (one BicycleDynamicsParam set per vehicle) -- new entry points only.
+                          0.4.0 (additive, same number): crx_planner_models_reach_dev, crx_planner_solve_models, crx_planner_solve_models_dev,
                           crx_planner_plan_models, crx_planner_plan_models_dev, CRX_PLANNER_MODEL_REACH_DOUBLES -- new entry points only.
                           0.4.0 (additive, same number): crx_cbf_models_reach_dev, crx_cbf_solve_models, crx_cbf_solve_models_dev,
                           CRX_CBF_MODEL_REACH_DOUBLES; CRX_SINGULAR also from these -- new entry points only.
@@ -425,6 +427,7 @@ typedef struct crx_prep_desc {
 } crx_prep_desc;
 
 /* ---- plant of the simulator (system/vehicle_dynamics.py:4-49, utils/base.py:897-942) ------------------ */
+#define CRX_PLANT_NPARAM 10 /* doubles per vehicle of a `params` array: m, lf, lr, Iz, Df, Cf, Bf, Dr, Cr, Br (BicycleDynamicsParam.get_params()) */
 typedef struct crx_plant_desc {
     int32_t n_sub;         /* 100: explicit Euler sub-steps per control step (`while (i+1)*0.001 <= timestep`, base.py:905) */
     int32_t n_seg;         /* rows of the track table point_and_tangent (racing_env.py:17-120) */
@@ -654,6 +657,27 @@ int crx_plant_step(const crx_plant_desc* d, int batch, const double* track, cons
                    const double* u, double* xglob_next, double* xcurv_next);
 int crx_plant_step_dev(const crx_plant_desc* d, int batch, const double* track, const double* xglob,
                        const double* xcurv, const double* u, double* xglob_next, double* xcurv_next, void* stream);
+/*
+ * The same step with one parameter set per vehicle (system/vehicle_dynamics.py:6 takes the set as its first argument; the
+ * reference's simulator always passes the defaults, base.py:906):
+ *   params [batch][CRX_PLANT_NPARAM] or NULL   row b = (m, lf, lr, Iz, Df, Cf, Bf, Dr, Cr, Br) of vehicle b, the order of
+ *                                              BicycleDynamicsParam.get_params().  With params given, the descriptor's ten values
+ *                                              are not used by the step, but the descriptor must still be a valid one.
+ * crx_plant_step_params_dev is crx_plant_step_noise_dev with `params` (lap bookkeeping, optional noise_z and laps); with
+ * params == NULL it IS crx_plant_step_noise_dev.  crx_plant_step_params_plain_dev and the host-pointer crx_plant_step_params are
+ * crx_plant_step_dev / crx_plant_step with `params` (no lap bookkeeping, no noise); with params == NULL they are those.
+ * crx_plant_step_params reads the rows and refuses (CRX_ERR_ARG, the first offending vehicle in crx_last_error()) one with
+ * m <= 0, Iz <= 0 or a non-finite value.  The `_dev` entries cannot read device memory: a bad row gives THAT vehicle non-finite
+ * states (1 / m, 1 / Iz and the tyre forces enter its own lane only) and touches no other vehicle.
+ */
+int crx_plant_step_params_dev(const crx_plant_desc* d, int batch, const double* track, const double* xglob,
+                              const double* xcurv, const double* u, int u_stride, const double* noise_z, const double* params,
+                              double* xglob_next, double* xcurv_next, int32_t* laps, void* stream);
+int crx_plant_step_params_plain_dev(const crx_plant_desc* d, int batch, const double* track, const double* xglob,
+                                    const double* xcurv, const double* u, const double* params, double* xglob_next,
+                                    double* xcurv_next, void* stream);
+int crx_plant_step_params(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
+                          const double* u, const double* params, double* xglob_next, double* xcurv_next);
 
 /*
  * Overtake PATH planner: one 1-D QP per candidate region

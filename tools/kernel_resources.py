@@ -1,5 +1,5 @@
 """Registers, scratch and occupancy of the solver kernels, from the compiler's own remarks (no GPU needed):
-    python tools/kernel_resources.py [obs|plan|gen|spec|lmpc|models_plan|models_obs|models_gen] [flags]   (recompiles the unit as `make recipe` states it, with
+    python tools/kernel_resources.py [obs|plan|gen|spec|lmpc|models_plan|models_obs|models_gen|prep] [flags]   (recompiles the unit as `make recipe` states it, with
                                                        -Rpass-analysis=kernel-resource-usage)
     python tools/kernel_resources.py one NOBS NMAX DEG NFIX [flags]     ONE instantiation compiled alone (csrc/crx_kernels_one.hip)
     python tools/kernel_resources.py lib [FILE.so]     what SHIPS: the kernel metadata of every code object embedded in the library (default: the in-tree
@@ -39,7 +39,7 @@ elif which == "lib":
     sys.exit(0)
 # unit name -> its object in the Makefile's recipe (tools/recipe.py: source and flags are read from `make recipe`, none is kept here)
 UNITS = {"plan": "crx_kernels.o", "obs": "crx_kernels_obs.o", "gen": "crx_kernels_gen.o", "spec": "crx_kernels_spec.o", "models_plan": "crx_kernels_models_plan.o",
-         "models_obs": "crx_kernels_models_obs.o", "models_gen": "crx_kernels_models_gen.o", "lmpc": "crx_lmpc.o"}
+         "models_obs": "crx_kernels_models_obs.o", "models_gen": "crx_kernels_models_gen.o", "lmpc": "crx_lmpc.o", "prep": "crx_prep.o"}
 def unit_command(which, args):
     """-> the compile command of a unit name (UNITS, or `one NOBS NMAX DEG NFIX`: crx_kernels_one.hip as the unit that ships the instantiation is built)"""
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -53,7 +53,7 @@ def recompile():
     t = subprocess.run(cmd, capture_output=True, text=True).stderr
     for b in re.split(r"remark: [^\n]*Function Name: ", t)[1:]:
         g = lambda k: (re.search(k + r": (\d+)", b) or [0, "?"])[1]
-        print("%-44s vgpr %3s agpr %3s scratch %4s B/lane  waves/SIMD %s" % (demangle(b.split("\n")[0].split(" [")[0]), g("VGPRs"), g("AGPRs"),
+        print("%-44s vgpr %3s agpr %3s sgpr %3s scratch %4s B/lane  waves/SIMD %s" % (demangle(b.split("\n")[0].split(" [")[0]), g("VGPRs"), g("AGPRs"), g("SGPRs"),
               g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]")))
 if __name__ == "__main__":
     recompile()

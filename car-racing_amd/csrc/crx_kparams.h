@@ -82,6 +82,7 @@ struct crx_select_kparams {
     double *sel_cost, *best_X;
 };
 
+// ---- crx_prep.hip: what turns raw scenarios into the arrays a solver reads ----
 struct crx_prep_kparams {
     int N, V, n_scen, n_opt;
     double prediction_factor, lookahead, track_width, lap_length, veh_length, veh_width, safety_margin, dt_ref;
@@ -90,6 +91,33 @@ struct crx_prep_kparams {
     double *x0, *bez_s, *bez_ey, *ey_lb, *ey_ub;
 };
 
+struct crx_scene_kparams {
+    crx_scene_desc d;
+    int n_scen;
+    const double *ego_xcurv, *veh_xcurv, *pred_s, *pred_ey;
+    const int32_t* n_all;
+    int32_t *n_veh, *overflow, *order;
+    double *veh_info, *max_dv, *obs_s, *obs_ey;
+};
+
+struct crx_trackprep_kparams {
+    int N, V, batch;
+    double lap_length, safety_time, dt_ref;
+    const double *x, *obs_s_in, *obs_ey_in, *traj;
+    const int32_t* n_veh;
+    double *xt, *obs_s, *obs_ey, *lap_off;
+    int32_t* n_obs;
+};
+
+struct crx_cbfprep_kparams {
+    int N, V, batch;
+    double lap_length, t, dt, safety_time;
+    const double *xcurv, *car_s0, *car_v, *car_ey;
+    double *obs_s, *obs_ey, *lap_off;
+    int32_t* n_obs;
+};
+
+// ---- crx_path.hip: crx_path_kernel, the path QP (crx_path_qp.h) without a mask ----
 struct crx_path_kparams {
     int N, batch;
     double alpha, w_rate;
@@ -99,13 +127,14 @@ struct crx_path_kparams {
     int32_t *status, *iters;
 };
 
-// crx_path_masked_kernel (crx_pathplan.hip: crx_path_kernel's source compiled again with a per-QP mask).  Derived, so that crx_path_kparams --
-// which crx_path_kernel takes by value -- keeps its size and the code object behind crx_path_solve stays what it is.
+// ---- crx_pathplan.hip: the overtake PATH planner around its QPs ----
+// crx_path_masked_kernel (crx_path_qp.h once more, with a per-QP mask).  Derived, so that crx_path_kparams -- which crx_path_kernel takes by
+// value -- keeps its size and the code object behind crx_path_solve stays what it is.
 struct crx_path_kparams_masked : crx_path_kparams {
     const int32_t* active;   // optional [batch]: 0 = this QP is not solved: status CRX_SKIPPED, cost +inf, iters 0, E and kkt untouched.  NULL: all
 };
 
-// crx_pathprep_kernel / crx_pathselect_kernel (crx_pathplan.hip): the overtake PATH planner around its QPs
+// crx_pathprep_kernel / crx_pathselect_kernel
 struct crx_pathplan_kparams {
     crx_pathprep_desc d;
     int n_scen;
@@ -120,6 +149,7 @@ struct crx_pathplan_kparams {
     double* target;
 };
 
+// ---- crx_plant.hip: the two inclusions of crx_plant_step.h ----
 struct crx_plant_kparams {
     crx_plant_desc d;
     int batch, u_stride, wrap;
@@ -129,38 +159,13 @@ struct crx_plant_kparams {
     const double* noise_z;   // optional [batch][3] standard-normal draws: the bounded process noise of base.py:929-939
 };
 
-// crx_plant_cars_kernel (crx_prep.hip).  Derived, so that crx_plant_kparams -- which crx_plant_kernel takes by value -- keeps its size and
+// crx_plant_cars_kernel.  Derived, so that crx_plant_kparams -- which crx_plant_kernel takes by value -- keeps its size and
 // the code object behind the shared-parameter launches stays what it is.
 struct crx_plant_kparams_cars : crx_plant_kparams {
     const double* params;   // [batch][CRX_PLANT_NPARAM]: m, lf, lr, Iz, Df, Cf, Bf, Dr, Cr, Br of each vehicle; d's ten values are unused
 };
 
-struct crx_cbfprep_kparams {
-    int N, V, batch;
-    double lap_length, t, dt, safety_time;
-    const double *xcurv, *car_s0, *car_v, *car_ey;
-    double *obs_s, *obs_ey, *lap_off;
-    int32_t* n_obs;
-};
-
-struct crx_trackprep_kparams {
-    int N, V, batch;
-    double lap_length, safety_time, dt_ref;
-    const double *x, *obs_s_in, *obs_ey_in, *traj;
-    const int32_t* n_veh;
-    double *xt, *obs_s, *obs_ey, *lap_off;
-    int32_t* n_obs;
-};
-
-struct crx_scene_kparams {
-    crx_scene_desc d;
-    int n_scen;
-    const double *ego_xcurv, *veh_xcurv, *pred_s, *pred_ey;
-    const int32_t* n_all;
-    int32_t *n_veh, *overflow, *order;
-    double *veh_info, *max_dv, *obs_s, *obs_ey;
-};
-
+// ---- crx_lmpcprep.hip ----
 struct crx_lmpcprep_kparams {
     crx_lmpcprep_desc d;
     int batch, from_plan;
@@ -186,14 +191,22 @@ hipError_t crx_launch_lmpc_addtraj(const crx_lmpcprep_desc& d, int batch, const 
                                    int32_t* step, const double* x, int32_t* status, hipStream_t st);
 size_t crx_solve_lds_bytes(int N, int nobs_template);
 int crx_solve_resident_per_cu(int N, int nobs_template);
-hipError_t crx_launch_path(const crx_path_kparams& pp, hipStream_t st);
+// crx_prep.hip
+hipError_t crx_launch_prep(const crx_prep_kparams& pp, hipStream_t st);
+hipError_t crx_launch_scene(const crx_scene_kparams& sp, hipStream_t st);
+hipError_t crx_launch_trackprep(const crx_trackprep_kparams& tp, hipStream_t st);
 hipError_t crx_launch_cbfprep(const crx_cbfprep_kparams& cp, hipStream_t st);
+// crx_plant.hip
+hipError_t crx_launch_plant(const crx_plant_kparams& pk, hipStream_t st);
+hipError_t crx_launch_plant_cars(const crx_plant_kparams_cars& pk, hipStream_t st);
+// crx_path.hip
+hipError_t crx_launch_path(const crx_path_kparams& pp, hipStream_t st);
 // crx_pathplan.hip
 hipError_t crx_launch_path_masked(const crx_path_kparams_masked& pp, hipStream_t st);
 hipError_t crx_launch_pathprep(const crx_pathplan_kparams& pp, hipStream_t st);
 hipError_t crx_launch_pathselect(const crx_pathplan_kparams& pp, hipStream_t st);
 
-// dispatch order of a solver launch (include/crx.h, "Dispatch order"): a stable counting sort of the batch by a 257-valued key
+// crx_order.hip: dispatch order of a solver launch (include/crx.h, "Dispatch order"): a stable counting sort of the batch by a 257-valued key
 struct crx_order_kparams {
     int batch, mode;             // mode 0: iteration counts of the previous solve, descending; 1: smallest start barrier, ascending
     const int32_t *iters, *active;
@@ -205,7 +218,7 @@ struct crx_order_kparams {
 };
 hipError_t crx_launch_order(const crx_order_kparams& op, hipStream_t st);
 
-// device-resident racing-game loop: the bookkeeping between the solver launches (crx.montecarlo.GameLaps / LmpcLaps)
+// crx_game.hip: device-resident racing-game loop: the bookkeeping between the solver launches (crx.montecarlo.GameLaps / LmpcLaps)
 struct crx_game_kparams {
     int N, Np, batch, n_cars, n_points;
     double lap_length, t, dt;
@@ -228,11 +241,7 @@ struct crx_game_kparams {
     double *log_x, *log_u;
 };
 hipError_t crx_launch_game(int which, const crx_game_kparams& gp, hipStream_t st);
-hipError_t crx_launch_plant(const crx_plant_kparams& pk, hipStream_t st);
-hipError_t crx_launch_plant_cars(const crx_plant_kparams_cars& pk, hipStream_t st);
-hipError_t crx_launch_prep(const crx_prep_kparams& pp, hipStream_t st);
-hipError_t crx_launch_scene(const crx_scene_kparams& sp, hipStream_t st);
-hipError_t crx_launch_trackprep(const crx_trackprep_kparams& tp, hipStream_t st);
+// crx_lmpc.hip, crx_lmpcprep.hip
 hipError_t crx_launch_lmpc(const crx_lmpc_kparams& kp, hipStream_t st);
 hipError_t crx_launch_lmpcprep(const crx_lmpcprep_kparams& kp, hipStream_t st);
 size_t crx_lmpcprep_lds_bytes(int n_points);
@@ -286,5 +295,14 @@ struct crx_pid_kparams {
     double *u_next, *x_log, *u_log;
 };
 hipError_t crx_launch_pid_log(const crx_pid_kparams& kp, hipStream_t st);
+
+// the launch the small kernels share (crx_prep, crx_plant, crx_path, crx_pathplan): nothing for n = 0, else a 1-D grid with `per_block` of the n
+// elements to a block of `threads` threads (a thread each: per_block = threads; a wavefront per problem: per_block = 1, threads = WAVE)
+template <typename P>
+static inline hipError_t crx_launch_1d(void (*kernel)(const P), int n, int per_block, int threads, hipStream_t st, const P& p) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(kernel, dim3((n + per_block - 1) / per_block), dim3(threads), 0, st, p);
+    return hipGetLastError();
+}
 #endif
 #endif

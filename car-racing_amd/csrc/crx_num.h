@@ -1,10 +1,10 @@
-// crx_num.h -- small numerics that the prep kernels (crx_prep.hip) and the solver's set-up (crx_kernels.hip) share, each stated once.
+// crx_num.h -- small numerics that the prep kernels (crx_prep.hip), the dispatch-order key (crx_order.hip) and the solver's set-up (crx_kernels.hip) share, each stated once.
 // Plain per-thread functions over pointers and scalars; not wave primitives (those are crx_wave.h, pinned by tests/wave_model.py).
 //
 // A site goes through a function here only where the kernel's machine code stayed bit for bit what it was (tools/kernel_diff.py);
 // the table at the end lists the others.
 //
-// Floating-point contraction: both units include this header at their head, in the compiler's default state (hipcc: contraction
+// Floating-point contraction: every including unit includes this header at its head, in the compiler's default state (hipcc: contraction
 // on).  interp1d() (slope * dx + y) and lap_fold() (s - laps * L) contain a multiply-add and may fuse, as the written-out
 // copies did; none of them is called from under `#pragma clang fp contract(off)` (crx_game_traffic_kernel, crx_lmpcprep.hip).
 #ifndef CRX_NUM_H
@@ -61,11 +61,11 @@ __device__ __forceinline__ double dim_or_default(double v, double dflt) { return
 // ---- Sites that are NOT shared, and why each stays ---------------------------------------------------------------------------------
 // "code changes": as in crx_ipm.h -- same arithmetic, but through a function the kernel's machine code is no longer what it was.
 // Lines as of this header's last edit; the kernel and its comment "crx_num.h" find the site.
-//   strided interp1d        crx_trackprep_kernel (crx_prep.hip:171-185)      the scan over the trajectory's rows (stride 6): code changes through a
+//   strided interp1d        crx_trackprep_kernel (crx_prep.hip:168-183)      the scan over the trajectory's rows (stride 6): code changes through a
 //                                                                            strided interp1d, also with the column offsets as template parameters
-//   zeroed obstacle slots   crx_trackprep_kernel (crx_prep.hip:205-210)      code changes in crx_trackprep_kernel with any shared form, down to the inner
-//                           crx_cbfprep_kernel (crx_prep.hip:336-341)        loop alone; a function with one caller is no sharing, so both copies stay
-//   super-ellipse value     crx_order_key (crx_prep.hip:632-634, :648-650)   code changes as a lambda and as a function (the loop over the degree)
-//   curvature lookup        the plant of crx_prep.hip (LDS tables), crx_lmpcprep.hip (global table, contraction off): two storage forms; left alone
+//   zeroed obstacle slots   crx_trackprep_kernel (crx_prep.hip:202-207)      code changes in crx_trackprep_kernel with any shared form, down to the inner
+//                           crx_cbfprep_kernel (crx_prep.hip:240-245)        loop alone; a function with one caller is no sharing, so both copies stay
+//   super-ellipse value     crx_order_key (crx_order.hip:46-48, :62-64)      code changes as a lambda and as a function (the loop over the degree)
+//   curvature lookup        the plant (crx_plant_step.h: LDS tables), crx_lmpcprep.hip (global table, contraction off): two storage forms; left alone
 
 #endif

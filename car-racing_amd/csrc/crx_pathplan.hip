@@ -1,15 +1,23 @@
 // crx_pathplan.hip -- the overtake PATH planner around its QPs (remainder):
 //   crx_pathprep_kernel     obstacle rows, Bezier control points and polylines, s samples, the two references, side rows and end points of
 //                           every region of a scenario, written in the layout crx_path_kernel reads
-//   crx_path_masked_kernel  crx_path_kernel's source (crx_prep.hip) compiled once more, with a per-QP mask
+//   crx_path_masked_kernel  the path QP (crx_path_qp.h, as crx_path.hip's crx_path_kernel) with a per-QP mask
 //   crx_pathselect_kernel   first arg-min of the region costs and the target trajectory with its speed profile
 //
 // Restates (paths into the reference's car_racing/; quirks P1-P8 are spelled out at crx_pathprep_desc in include/crx.h):
-//   planning/overtake_path_planner.py:60-100, :113-143, :173-197, :199-318
+//   planning/overtake_path_planner.py:60-100, :113-143, :173-197 (prep and selection), :199-318 (the QP)
 //   planning/planner_helper.py:43-135 get_bezier_control_points, :138-153 get_bezier_curve, :177-201 get_agent_info
-// The host mirror (planning/overtake_path_planner.py of this package) is the yardstick: every product and sum below is rounded on its
-// own, in the mirror's order -- contraction is off for the whole unit, the shared headers' helpers that may fuse are not used.
-#define CRX_TU_PATHPLAN 1
+// The host mirror (planning/overtake_path_planner.py of this package) is the yardstick: every product and sum of the prep and selection
+// kernels is rounded on its own, in the mirror's order -- contraction is off from the pragma below on (AFTER the QP's text, which keeps the
+// compiler's default as in crx_path.hip), the shared headers' helpers that may fuse are not used.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "crx_kparams.h"
+#include "crx_wave.h"
+#include "crx_ipm.h"
+
 #define CRX_PATH_KERNEL crx_path_masked_kernel
 #define CRX_PATH_KPARAMS crx_path_kparams_masked
 #define CRX_PATH_SKIP(pp, b, lane)                                                                          \
@@ -17,15 +25,9 @@
         if (lane == 0) { pp.cost[b] = INFINITY; pp.status[b] = CRX_SKIPPED; pp.iters[b] = 0; }              \
         return;                                                                                              \
     }
-#include "crx_prep.hip"
+#include "crx_path_qp.h"
 
 #pragma clang fp contract(off)
-
-hipError_t crx_launch_path_masked(const crx_path_kparams_masked& pp, hipStream_t st) {
-    if (pp.batch == 0) return hipSuccess;
-    hipLaunchKernelGGL(crx_path_masked_kernel, dim3(pp.batch), dim3(WAVE), 0, st, pp);
-    return hipGetLastError();
-}
 
 namespace {
 // `while (s >= L) s -= L` (:233-234) / `while (s > L) s -= L` (:184-197, planner_helper.py:39-42) with a bounded trip count: four laps by
@@ -223,14 +225,10 @@ __global__ void __launch_bounds__(256) crx_pathselect_kernel(const crx_pathplan_
     pp.flag[s] = flag; pp.plan_status[s] = CRX_CONVERGED;
 }
 
-hipError_t crx_launch_pathprep(const crx_pathplan_kparams& pp, hipStream_t st) {
-    if (pp.n_scen == 0) return hipSuccess;
-    hipLaunchKernelGGL(crx_pathprep_kernel, dim3(pp.n_scen), dim3(WAVE), 0, st, pp);
-    return hipGetLastError();
+hipError_t crx_launch_path_masked(const crx_path_kparams_masked& pp, hipStream_t st) {
+    return crx_launch_1d(crx_path_masked_kernel, pp.batch, 1, WAVE, st, pp);
 }
-
+hipError_t crx_launch_pathprep(const crx_pathplan_kparams& pp, hipStream_t st) { return crx_launch_1d(crx_pathprep_kernel, pp.n_scen, 1, WAVE, st, pp); }
 hipError_t crx_launch_pathselect(const crx_pathplan_kparams& pp, hipStream_t st) {
-    if (pp.n_scen == 0) return hipSuccess;
-    hipLaunchKernelGGL(crx_pathselect_kernel, dim3((pp.n_scen + 255) / 256), dim3(256), 0, st, pp);
-    return hipGetLastError();
+    return crx_launch_1d(crx_pathselect_kernel, pp.n_scen, 256, 256, st, pp);
 }

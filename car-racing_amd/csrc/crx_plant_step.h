@@ -1,4 +1,4 @@
-// crx_plant_step.h -- the plant kernel's text, included by crx_prep.hip once per instantiation (no include guard).  The includer defines
+// crx_plant_step.h -- the plant kernel's text, included by crx_plant.hip once per instantiation (no include guard).  The includer defines
 //   CRX_PLANT_KERNEL, CRX_PLANT_KPARAMS   the kernel's name and its parameter struct (crx_plant_kparams or derived from it)
 //   CRX_PLANT_READ_PARAMS(pk, b)          statements after the bounds check that bring car b's BicycleDynamicsParam values into registers
 //   CRX_PLANT_P(name)                     how the sub-step loop names one of m, lf, lr, Iz, Df, Cf, Bf, Dr, Cr, Br

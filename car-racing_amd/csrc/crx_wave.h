@@ -286,7 +286,7 @@ __device__ __forceinline__ double excl_suffix(double v, int lane) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// dense factorisations in LDS, one matrix row per lane (crx_lmpc.hip, crx_path kernel in crx_prep.hip)
+// dense factorisations in LDS, one matrix row per lane (crx_lmpc.hip, the path QP of crx_path_qp.h)
 // ------------------------------------------------------------------------------------------------
 // left-looking Cholesky, in place, of the leading n x n block (lower triangle) of a row-major array
 // (stride LD); rows n..n+extra-1 are carried along, i.e. forward-substituted right-hand sides.

@@ -1,5 +1,5 @@
 """Registers, scratch and occupancy of the solver kernels, from the compiler's own remarks (no GPU needed):
-    python tools/kernel_resources.py [obs|plan|gen|spec|lmpc|models_plan|models_obs|models_gen|prep] [flags]   (recompiles the unit as `make recipe` states it, with
+    python tools/kernel_resources.py [obs|plan|gen|spec|lmpc|models_plan|models_obs|models_gen|prep|plant|game|order|path|pathplan] [flags]   (recompiles the unit as `make recipe` states it, with
                                                        -Rpass-analysis=kernel-resource-usage)
     python tools/kernel_resources.py one NOBS NMAX DEG NFIX [flags]     ONE instantiation compiled alone (csrc/crx_kernels_one.hip)
     python tools/kernel_resources.py lib [FILE.so]     what SHIPS: the kernel metadata of every code object embedded in the library (default: the in-tree
@@ -39,7 +39,8 @@ elif which == "lib":
     sys.exit(0)
 # unit name -> its object in the Makefile's recipe (tools/recipe.py: source and flags are read from `make recipe`, none is kept here)
 UNITS = {"plan": "crx_kernels.o", "obs": "crx_kernels_obs.o", "gen": "crx_kernels_gen.o", "spec": "crx_kernels_spec.o", "models_plan": "crx_kernels_models_plan.o",
-         "models_obs": "crx_kernels_models_obs.o", "models_gen": "crx_kernels_models_gen.o", "lmpc": "crx_lmpc.o", "prep": "crx_prep.o"}
+         "models_obs": "crx_kernels_models_obs.o", "models_gen": "crx_kernels_models_gen.o", "lmpc": "crx_lmpc.o", "prep": "crx_prep.o",
+         "plant": "crx_plant.o", "game": "crx_game.o", "order": "crx_order.o", "path": "crx_path.o", "pathplan": "crx_pathplan.o"}
 def unit_command(which, args):
     """-> the compile command of a unit name (UNITS, or `one NOBS NMAX DEG NFIX`: crx_kernels_one.hip as the unit that ships the instantiation is built)"""
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))

@@ -21,7 +21,10 @@ for c in 000 001 010 011 100 101 110 111; do
   S=${c:0:1}; D=${c:1:1}; M=${c:2:1}; W=2; [ $S = 1 ] && W=0
   echo "g$c: $(python tools/exec_prologue_check.py tools/ab/libcrx_g$c.so | tail -1)"     # [r6] on the code objects of the variant itself
 done | tee tools/ab/exec_prologue_matrix.txt
-bash tools/build_variant.sh fenceonly "-DCRX_SYNC_FENCE_ONLY" crx_kernels_plan.hip crx_kernels_obs.hip crx_kernels_gen.hip crx_lmpc.hip crx_prep.hip crx_lmpcprep.hip > /dev/null &
+# fenceonly: EVERY unit whose source, or the kernel text it includes (crx_kernels.hip, crx_path_qp.h), uses SYNC() -- grep -l 'SYNC()' csrc
+FENCE_UNITS="crx_kernels_plan.hip crx_kernels_obs.hip crx_kernels_spec.hip crx_kernels_gen.hip crx_kernels_models_plan.hip crx_kernels_models_obs.hip"
+FENCE_UNITS="$FENCE_UNITS crx_kernels_models_gen.hip crx_lmpc.hip crx_lmpcprep.hip crx_path.hip crx_pathplan.hip crx_ilqr.hip crx_lqr.hip crx_sysid.hip crx_debug_wave.hip"
+bash tools/build_variant.sh fenceonly "-DCRX_SYNC_FENCE_ONLY" $FENCE_UNITS > /dev/null &
 bash tools/build_variant.sh opaqueall "-DCRX_OPAQUE_LANE=2" crx_kernels_obs.hip > /dev/null &
 # (nodpp goes with the shared retry set-up off: riccati_backward<.., SHARED> is written for the register-resident (P | p), which needs the DPP form --
 # since round 12 the variant stopped at that static_assert and left no library)

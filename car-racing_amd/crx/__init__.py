@@ -109,5 +109,10 @@ def path_plan(desc, qdesc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, ob
     return binding().path_plan(desc, qdesc, x_wrapped, x_raw, n_veh, order, veh_xcurv, max_dv, obs_ey, opt_s, opt_ey, opt_vx, active, target)
 
 
+def field_prep(desc, track, xcurv, car_dims=None):
+    """Field-race prep (include/crx.h F1-F7) on host arrays: see abi.Binding.field_prep."""
+    return binding().field_prep(desc, track, xcurv, car_dims)
+
+
 def plant_step(desc, track, xglob, xcurv, u, params=None):
     return binding().plant_step(desc, track, xglob, xcurv, u, params=params)

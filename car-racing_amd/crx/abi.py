@@ -232,6 +232,16 @@ class PlantDesc(C.Structure):
     ]
 
 
+class FieldDesc(C.Structure):
+    _fields_ = [("N", C.c_int32), ("n_cars", C.c_int32), ("n_seg", C.c_int32), ("degree", C.c_int32), ("lap_length", C.c_double),
+                ("dt", C.c_double), ("safety_time", C.c_double), ("l_sum", C.c_double), ("w_sum", C.c_double)]
+
+
+def field_desc(N, n_cars, n_seg, lap_length, dt=0.1, safety_time=2.0, degree=6, l_sum=0.4, w_sum=0.2):
+    """crx_field_desc_default: the literal safety_time of control.mpccbf (control.py:499), degree of :528, CarParam's dimensions."""
+    return FieldDesc(int(N), int(n_cars), int(n_seg), int(degree), float(lap_length), float(dt), float(safety_time), float(l_sum), float(w_sum))
+
+
 class SelectDesc(C.Structure):
     _fields_ = [
         ("N", C.c_int32),
@@ -411,7 +421,7 @@ class Binding:
         self.lib, self.prefix = lib, prefix
         for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve", "ilqr_solve",
                      "ilqr_solve_models", "lqr_design", "sysid_fit", "cbf_solve_models", "planner_solve_models", "planner_plan",
-                     "planner_plan_models", "path_prep", "path_plan", "plant_step_params"):
+                     "planner_plan_models", "path_prep", "path_plan", "plant_step_params", "field_prep"):
             if hasattr(lib, prefix + name):
                 getattr(lib, prefix + name).restype = C.c_int
         self._check = None
@@ -702,6 +712,29 @@ class Binding:
             return out
         self._call("plant_step", C.byref(desc), C.c_int(Bn), _p(track), _p(xglob), _p(xcurv), _p(u), _p(out["xglob"]),
                    _p(out["xcurv"]))
+        return out
+
+    def field_prep(self, desc, track, xcurv, car_dims=None, clear=True):
+        """crx_field_prep (include/crx.h F1-F7): the predictions of every car of every race and the obstacle arrays of the R * C NLPs.
+        track (n_seg,6); xcurv (R,C,6) or (R*C,6); car_dims (R,C,2) = (length, width) per car, or None.  Returns pred_s, pred_ey
+        (R,C,N+1), obs_s, obs_ey (R,C,V,N+1), lap_off (R,C,V), n_obs (R,C) with V = C - 1; obs_dims (R,C,V,2) with car_dims; clear (R,C)
+        unless clear is False."""
+        N1, Cn = desc.N + 1, desc.n_cars
+        V = Cn - 1
+        track = _in(track, _D, (desc.n_seg, 6))
+        xcurv = np.ascontiguousarray(xcurv, dtype=_D)
+        R = xcurv.size // (6 * Cn)
+        xcurv = _in(xcurv.reshape(R, Cn, 6), _D, (R, Cn, 6))
+        out = dict(pred_s=np.zeros((R, Cn, N1)), pred_ey=np.zeros((R, Cn, N1)), obs_s=np.zeros((R, Cn, V, N1)), obs_ey=np.zeros((R, Cn, V, N1)),
+                   lap_off=np.zeros((R, Cn, V)), n_obs=np.zeros((R, Cn), dtype=_I))
+        if car_dims is not None:
+            car_dims = _in(car_dims, _D, (R, Cn, 2))
+            out["obs_dims"] = np.zeros((R, Cn, V, 2))
+        if clear:
+            out["clear"] = np.zeros((R, Cn))
+        self._call("field_prep", C.byref(desc), C.c_int(R), _p(track), _p(xcurv), _p(car_dims) if car_dims is not None else None,
+                   *[_p(out[k]) for k in ("pred_s", "pred_ey", "obs_s", "obs_ey", "lap_off", "n_obs")],
+                   _p(out["obs_dims"]) if car_dims is not None else None, _p(out["clear"]) if clear else None)
         return out
 
     def path_solve(self, desc, opt, bez, lb, ub, e0, eN):

@@ -321,6 +321,64 @@ def mpccbf_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, car
     return dict(logs, laps=r.laps.cpu().numpy())
 
 
+class FieldRaces(_Plant):
+    """R races of C cars that ALL drive themselves under MPC-CBF: every car is the ego of its own NLP and an obstacle of the C - 1
+    others, predicted by the zero-input roll-out of the reference's driven model (racing/offboard.py:51-94) as control.mpccbf consumes it
+    with realtime_flag == True (control/control.py:512-514).  The plant batch is R*C, race-major, car-minor; all cars of a step see
+    the states at the start of the step (include/crx.h, crx_field_prep_dev, quirks F1-F7).  min_clear [R*C]: each car's smallest
+    super-ellipse value against the cars of its race over the states the steps so far STARTED from (below 1: contact)."""
+
+    def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, n_cars, vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1,
+                 device=None, noise_seed=None, models=None, plant_params=None, car_dims=None):
+        Cn = int(n_cars)
+        if not 1 <= Cn <= abi.CRX_MAX_OBS + 1:
+            raise ValueError("1 .. %d cars per race" % (abi.CRX_MAX_OBS + 1))
+        x0, g0 = (np.asarray(a, dtype=float).reshape(-1, 6) for a in (xcurv0, xglob0))   # [R*C,6] or [R,C,6]
+        if x0.shape[0] % Cn or g0.shape != x0.shape:
+            raise ValueError("xcurv0, xglob0: %d and %d cars do not make races of %d" % (x0.shape[0], g0.shape[0], Cn))
+        dev = self._plant_init(track_table, lap_length, timestep, x0, g0, noise_seed, device, plant_params)
+        Bn, R = self.batch, self.batch // Cn
+        self.N, self.n_races, self.n_cars = N, R, Cn
+        self.desc = abi.cbf_desc(N, Cn - 1, A, B, alpha=alpha, margin=0.2, ey_max=track_width)
+        self.fdesc = abi.field_desc(N, Cn, self.tab.shape[0], lap_length, dt=timestep)
+        # vt, eyt: scalars or one value per car [R,C] -- different target speeds are what makes the cars meet
+        xt = np.zeros((Bn, 6))
+        xt[:, 0] = np.broadcast_to(np.asarray(vt, dtype=float), (R, Cn)).reshape(-1)
+        xt[:, 5] = np.broadcast_to(np.asarray(eyt, dtype=float), (R, Cn)).reshape(-1)
+        self.xt = _dev(xt, dev)
+        self.ws = torch_api.CbfWorkspace(self.desc, Bn, dev)
+        # models = (A [R*C,6,6], B [R*C,6,2]): every car's controller on its own model, as in MpccbfRaces
+        self.models = None if models is None else torch_api.CbfModels(self.desc, *_models(models[0], models[1], Bn, dev))
+        # car_dims [R,C,2]: (length, width) of every car; None: the descriptor's l_sum, w_sum for every pair
+        self.car_dims = None if car_dims is None else _dev(np.asarray(car_dims, dtype=float).reshape(R, Cn, 2), dev)
+        self.fws = torch_api.FieldWorkspace(self.fdesc, R, dev, dims=car_dims is not None)
+        self.min_clear = torch.full((Bn,), float("inf"), dtype=torch.float64, device=dev)
+        self.u = None
+
+    def step(self):
+        """One control step of every car of every race, three libcrx launches: field_prep_dev, cbf_solve_dev, plant_step_wrap_dev
+        (dispatch = "longest_first": one longest_first ahead of the solver launch); then `clear` joins the running minimum."""
+        f = self.fws
+        torch_api.field_prep_dev(self.fdesc, self.tab, self.xc, f, car_dims=self.car_dims)
+        torch_api.cbf_solve_dev(self.desc, self.xc, self.xt, f.obs_s, f.obs_ey, f.lap_off, f.n_obs, ws=self.ws,
+                                order=_order(self, self.ws.iters), models=self.models, obs_dims=f.obs_dims)
+        self._advance(self.ws.U, 2 * self.N)
+        self.u = self.ws.U[:, 0, :]
+        torch.minimum(self.min_clear, f.clear, out=self.min_clear)
+
+
+def field_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, n_cars, steps, vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1,
+                device=None, log_every=1, noise_seed=None, models=None, plant_params=None, car_dims=None):
+    """xcurv0, xglob0 [R*C,6] or [R,C,6]; vt, eyt scalars or [R,C]; models = (A [R*C,6,6], B [R*C,6,2]); plant_params [R*C,10]; car_dims
+    [R,C,2].  Returns host arrays: xcurv [T+1,R*C,6] (T = steps / log_every), u [T,R*C,2], status, iters, n_obs [T,R*C], laps [R*C],
+    min_clear [R*C]."""
+    r = FieldRaces(track_table, lap_length, track_width, A, B, xcurv0, xglob0, n_cars, vt=vt, eyt=eyt, N=N, alpha=alpha, timestep=timestep,
+                   device=device, noise_seed=noise_seed, models=models, plant_params=plant_params, car_dims=car_dims)
+    logs = _run_and_log(r.step, steps, log_every, dict(xcurv=lambda: r.xc, u=lambda: r.u, status=lambda: r.ws.status,
+                                                       iters=lambda: r.ws.iters, n_obs=lambda: r.fws.n_obs))
+    return dict(logs, laps=r.laps.cpu().numpy(), min_clear=r.min_clear.cpu().numpy())
+
+
 class IlqrRaces(_Plant):
     """B copies of the reference's iLQR racing scenario (car_racing/tests/ilqr_test.py: ego under iLQRRacing, one scripted car
     s(t) = v t + s0, ey(t) = ey), device-resident.  Per control step, without touching the host: the scripted car's N+1

@@ -518,6 +518,49 @@ def cbf_prep_dev(N, lap_length, t, dt, xcurv, car_s0, car_v, car_ey, obs_s, obs_
           _ptr(obs_ey), _ptr(lap_off), _ptr(n_obs), _stream())
 
 
+class FieldWorkspace:
+    """Outputs of field_prep_dev for n_races races of desc.n_cars cars: the predictions pred_s, pred_ey [R,C,N+1] and the obstacle
+    inputs of cbf_solve_dev for the R*C problems, in its layout (batch R*C, race-major, car-minor): obs_s, obs_ey [R*C,V,N+1], lap_off
+    [R*C,V], n_obs [R*C] with V = C - 1; clear [R*C] (None with clear=False: not computed); obs_dims [R*C,V,2] with dims=True (the cars bring their own
+    dimensions), else None."""
+
+    def __init__(self, desc, n_races, device, dims=False, clear=True):
+        N1, Cn = desc.N + 1, desc.n_cars
+        Bn, V = n_races * Cn, Cn - 1
+        f64 = dict(dtype=torch.float64, device=device)
+        self.n_races = n_races
+        self.pred_s = torch.zeros((n_races, Cn, N1), **f64)
+        self.pred_ey = torch.zeros((n_races, Cn, N1), **f64)
+        self.obs_s = torch.zeros((Bn, V, N1), **f64)
+        self.obs_ey = torch.zeros((Bn, V, N1), **f64)
+        self.lap_off = torch.zeros((Bn, V), **f64)
+        self.n_obs = torch.zeros(Bn, dtype=torch.int32, device=device)
+        self.obs_dims = torch.zeros((Bn, V, 2), **f64) if dims else None
+        self.clear = torch.zeros(Bn, **f64) if clear else None
+
+
+def field_prep_dev(desc, track, xcurv, ws, car_dims=None):
+    """crx_field_prep_dev (include/crx.h F1-F7): xcurv [R*C,6] (race-major, car-minor), track [n_seg,6], car_dims [R,C,2] (length, width
+    per car) with a FieldWorkspace(dims=True), None with dims=False.  Writes ws and returns it."""
+    R, Cn, N1 = ws.n_races, desc.n_cars, desc.N + 1
+    Bn, V = R * Cn, Cn - 1
+    _chk(track, torch.float64, (desc.n_seg, 6), "track")
+    _chk(xcurv, torch.float64, (Bn, 6), "xcurv")
+    if (car_dims is None) != (ws.obs_dims is None):
+        raise ValueError("car_dims goes with a FieldWorkspace(dims=True), no car_dims with dims=False")
+    if car_dims is not None:
+        _chk(car_dims, torch.float64, (R, Cn, 2), "car_dims")
+        _chk(ws.obs_dims, torch.float64, (Bn, V, 2), "ws.obs_dims")
+    for name, shape in (("pred_s", (R, Cn, N1)), ("pred_ey", (R, Cn, N1)), ("obs_s", (Bn, V, N1)), ("obs_ey", (Bn, V, N1)), ("lap_off", (Bn, V)),
+                        ("clear", (Bn,))):
+        if getattr(ws, name) is not None:
+            _chk(getattr(ws, name), torch.float64, shape, "ws." + name)
+    _chk(ws.n_obs, torch.int32, (Bn,), "ws.n_obs")
+    _call("crx_field_prep_dev", C.byref(desc), C.c_int(R), _ptr(track), _ptr(xcurv), _ptr(car_dims), _ptr(ws.pred_s), _ptr(ws.pred_ey),
+          _ptr(ws.obs_s), _ptr(ws.obs_ey), _ptr(ws.lap_off), _ptr(ws.n_obs), _ptr(ws.obs_dims), _ptr(ws.clear), _stream())
+    return ws
+
+
 def plant_step_wrap_dev(desc, track, xglob, xcurv, u, u_stride, xglob_next, xcurv_next, laps, noise_z=None, params=None):
     """crx_plant_step_wrap_dev: plant step + lap bookkeeping; `u` may be a strided view's base tensor (u_stride doubles
     between vehicles, e.g. the U output of cbf_solve_dev with u_stride = 2 N).  noise_z [B,3]: standard-normal draws for the

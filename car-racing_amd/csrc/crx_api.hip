@@ -1048,6 +1048,73 @@ int crx_cbf_prep_dev(int N, int V, double lap_length, double t, double dt, doubl
     return launched(crx_launch_cbfprep(cp, (hipStream_t)stream), "cbf prep");
 }
 
+// ---- field races: every car of a race drives itself (crx_field_prep_kernel, crx_prep.hip) ------------------------------------
+void crx_field_desc_default(crx_field_desc* d, int N, int n_cars, int n_seg, double lap_length) {
+    memset(d, 0, sizeof(*d));
+    d->N = N; d->n_cars = n_cars; d->n_seg = n_seg; d->degree = 6;
+    d->lap_length = lap_length; d->dt = 0.1; d->safety_time = 2.0; d->l_sum = 0.4; d->w_sum = 0.2;
+}
+
+// Arguments alone, before the library's state is looked at (the answer is the same with and without a device).  host_dims: the
+// [n_races][n_cars][2] rows of the host-pointer entry (NULL: none, or on the device where they cannot be read)
+static int check_field(crx_field_kparams& fp, const crx_field_desc* d, int n_races, arr track, arr xcurv, arr car_dims, arr pred_s, arr pred_ey,
+                       arr obs_s, arr obs_ey, arr lap_off, arr n_obs, arr obs_dims, const double* host_dims = nullptr) {
+    auto positive = [](double v) { return v > 0.0 && isfinite(v); };
+    if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
+    if (d->N < 1 || d->N > CRX_MAX_N) return fail(CRX_ERR_ARG, "N=%d outside [1,%d]", d->N, CRX_MAX_N);
+    if (d->n_cars < 1 || d->n_cars > CRX_MAX_OBS + 1) return fail(CRX_ERR_ARG, "n_cars=%d outside [1,%d]", d->n_cars, CRX_MAX_OBS + 1);
+    if (d->n_seg < 1 || d->n_seg > CRX_PLANT_MAX_SEG) return fail(CRX_ERR_ARG, "n_seg=%d outside [1,%d]", d->n_seg, CRX_PLANT_MAX_SEG);
+    if (d->degree < 2 || d->degree > 8 || (d->degree & 1)) return fail(CRX_ERR_ARG, "degree must be 2, 4, 6 or 8");
+    if (!positive(d->lap_length) || !positive(d->dt) || !positive(d->l_sum) || !positive(d->w_sum))
+        return fail(CRX_ERR_ARG, "lap_length, dt, l_sum and w_sum must be positive and finite");
+    if (n_races < 0) return fail(CRX_ERR_ARG, "n_races < 0");
+    if (d->n_cars > 1 && !car_dims != !obs_dims)   // (one car: obs_dims holds nothing, like the other obs_* arrays)
+        return fail(CRX_ERR_ARG, "car_dims and obs_dims go together: both or neither (%s is NULL)", car_dims ? "obs_dims" : "car_dims");
+    if (n_races > 0 && (any_null(track, xcurv, pred_s, pred_ey, n_obs) || (d->n_cars > 1 && any_null(obs_s, obs_ey, lap_off))))
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    for (size_t i = 0; host_dims && i < (size_t)n_races * d->n_cars; i++)
+        if (!positive(host_dims[2 * i]) || !positive(host_dims[2 * i + 1]))
+            return fail(CRX_ERR_ARG, "car_dims of car %zu of race %zu: length and width must be positive and finite", i % d->n_cars, i / d->n_cars);
+    memset(&fp, 0, sizeof(fp));
+    fp.d = *d; fp.n_races = n_races;
+    return 0;
+}
+
+int crx_field_prep_dev(const crx_field_desc* d, int n_races, const double* track, const double* xcurv, const double* car_dims, double* pred_s,
+                       double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims, double* clear,
+                       void* stream) {
+    crx_field_kparams fp;
+    if (int rc = check_field(fp, d, n_races, track, xcurv, car_dims, pred_s, pred_ey, obs_s, obs_ey, lap_off, n_obs, obs_dims)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (n_races == 0) return CRX_OK;
+    fp.track = track; fp.xcurv = xcurv; fp.car_dims = car_dims; fp.pred_s = pred_s; fp.pred_ey = pred_ey; fp.obs_s = obs_s; fp.obs_ey = obs_ey;
+    fp.lap_off = lap_off; fp.n_obs = n_obs; fp.obs_dims = d->n_cars > 1 ? obs_dims : nullptr; fp.clear = clear;
+    return launched(crx_launch_field_prep(fp, (hipStream_t)stream), "field prep");
+}
+
+int crx_field_prep(const crx_field_desc* d, int n_races, const double* track, const double* xcurv, const double* car_dims, double* pred_s,
+                   double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims, double* clear) {
+    crx_field_kparams chk;
+    if (int rc = check_field(chk, d, n_races, track, xcurv, car_dims, pred_s, pred_ey, obs_s, obs_ey, lap_off, n_obs, obs_dims, car_dims)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (n_races == 0) return CRX_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    const size_t RC = (size_t)n_races * d->n_cars, V = (size_t)d->n_cars - 1, N1 = (size_t)d->N + 1;
+    Stage sg;
+    auto dtr = sg.in(track, (size_t)d->n_seg * 6); auto dx = sg.in(xcurv, RC * 6);
+    auto dcd = car_dims ? sg.in(car_dims, RC * 2) : Stage::Ref<double>{};   // unused: sg[dcd] is NULL
+    auto dps = sg.out(pred_s, RC * N1); auto dpe = sg.out(pred_ey, RC * N1);
+    auto dos = sg.out(obs_s, RC * V * N1); auto doe = sg.out(obs_ey, RC * V * N1); auto dlo = sg.out(lap_off, RC * V);
+    auto dno = sg.out(n_obs, RC);
+    auto dod = obs_dims ? sg.out(obs_dims, RC * V * 2) : Stage::Ref<double>{};
+    auto dcl = clear ? sg.out(clear, RC) : Stage::Ref<double>{};
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_field_prep_dev(d, n_races, sg[dtr], sg[dx], sg[dcd], sg[dps], sg[dpe], sg[dos], sg[doe], sg[dlo], sg[dno], sg[dod], sg[dcl],
+                                    g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
 int crx_plant_step(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
                    const double* u, double* xglob_next, double* xcurv_next) {
     return crx_plant_step_params(d, batch, track, xglob, xcurv, u, nullptr, xglob_next, xcurv_next);

@@ -117,6 +117,16 @@ struct crx_cbfprep_kparams {
     int32_t* n_obs;
 };
 
+// crx_field_prep_kernel (crx_prep.hip): predictions of every car of every race and the obstacle arrays of the n_races * n_cars NLPs
+struct crx_field_kparams {
+    crx_field_desc d;
+    int n_races;
+    const double *track, *xcurv, *car_dims;   // car_dims: optional [n_races][n_cars][2] (length, width); NULL: d.l_sum, d.w_sum for every pair
+    double *pred_s, *pred_ey, *obs_s, *obs_ey, *lap_off;
+    int32_t* n_obs;
+    double *obs_dims, *clear;                 // obs_dims: written iff car_dims; clear: optional
+};
+
 // ---- crx_path.hip: crx_path_kernel, the path QP (crx_path_qp.h) without a mask ----
 struct crx_path_kparams {
     int N, batch;
@@ -150,6 +160,7 @@ struct crx_pathplan_kparams {
 };
 
 // ---- crx_plant.hip: the two inclusions of crx_plant_step.h ----
+#define CRX_PLANT_MAX_SEG 64   // rows of a track's segment table a kernel keeps in LDS (the plant, crx_field_prep_kernel)
 struct crx_plant_kparams {
     crx_plant_desc d;
     int batch, u_stride, wrap;
@@ -196,6 +207,7 @@ hipError_t crx_launch_prep(const crx_prep_kparams& pp, hipStream_t st);
 hipError_t crx_launch_scene(const crx_scene_kparams& sp, hipStream_t st);
 hipError_t crx_launch_trackprep(const crx_trackprep_kparams& tp, hipStream_t st);
 hipError_t crx_launch_cbfprep(const crx_cbfprep_kparams& cp, hipStream_t st);
+hipError_t crx_launch_field_prep(const crx_field_kparams& fp, hipStream_t st);
 // crx_plant.hip
 hipError_t crx_launch_plant(const crx_plant_kparams& pk, hipStream_t st);
 hipError_t crx_launch_plant_cars(const crx_plant_kparams_cars& pk, hipStream_t st);

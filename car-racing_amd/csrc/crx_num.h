@@ -61,10 +61,10 @@ __device__ __forceinline__ double dim_or_default(double v, double dflt) { return
 // ---- Sites that are NOT shared, and why each stays ---------------------------------------------------------------------------------
 // "code changes": as in crx_ipm.h -- same arithmetic, but through a function the kernel's machine code is no longer what it was.
 // Lines as of this header's last edit; the kernel and its comment "crx_num.h" find the site.
-//   strided interp1d        crx_trackprep_kernel (crx_prep.hip:168-183)      the scan over the trajectory's rows (stride 6): code changes through a
+//   strided interp1d        crx_trackprep_kernel (crx_prep.hip:170-185)      the scan over the trajectory's rows (stride 6): code changes through a
 //                                                                            strided interp1d, also with the column offsets as template parameters
-//   zeroed obstacle slots   crx_trackprep_kernel (crx_prep.hip:202-207)      code changes in crx_trackprep_kernel with any shared form, down to the inner
-//                           crx_cbfprep_kernel (crx_prep.hip:240-245)        loop alone; a function with one caller is no sharing, so both copies stay
+//   zeroed obstacle slots   crx_trackprep_kernel (crx_prep.hip:204-209)      code changes in crx_trackprep_kernel with any shared form, down to the inner
+//                           crx_cbfprep_kernel (crx_prep.hip:242-247)        loop alone; a function with one caller is no sharing, so both copies stay
 //   super-ellipse value     crx_order_key (crx_order.hip:46-48, :62-64)      code changes as a lambda and as a function (the loop over the degree)
 //   curvature lookup        the plant (crx_plant_step.h: LDS tables), crx_lmpcprep.hip (global table, contraction off): two storage forms; left alone
 

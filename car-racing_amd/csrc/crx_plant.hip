@@ -17,8 +17,6 @@
 #include "crx_kparams.h"
 #include "crx_wave.h"
 
-#define CRX_PLANT_MAX_SEG 64
-
 // The step is written once, in crx_plant_step.h.  crx_plant_kernel: the ten BicycleDynamicsParam values are the descriptor's, uniform over the
 // launch.  crx_plant_cars_kernel (crx_plant_step_params_dev): car b's own row params[10 b ..], in the order of BicycleDynamicsParam.get_params()
 // (m, lf, lr, Iz, Df, Cf, Bf, Dr, Cr, Br), read into registers before the sub-step loop.  Everything else comes from the descriptor either way.

@@ -10,6 +10,8 @@
 //   crx_trackprep_kernel   the inputs of control.mpc_multi_agents' NLP from the planner's outputs: per-stage targets, window filter, lap offsets
 //                          and packing of the sorted vehicles' predictions.  control/control.py:373-382, :293-309
 //   crx_cbfprep_kernel     obstacle arrays of control.mpccbf for scripted cars.  control/control.py:500, :519
+//   crx_field_prep_kernel  the same arrays for a field of driven cars: every car of a race predicted by the zero-input roll-out of
+//                          racing/offboard.py:51-94, every car the ego of its own NLP.  control/control.py:499-540 (realtime_flag == True)
 // The comment in front of each kernel has the rest.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -246,9 +248,115 @@ __global__ void __launch_bounds__(256) crx_cbfprep_kernel(const crx_cbfprep_kpar
     cp.n_obs[b] = n;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Obstacle arrays of control.mpccbf for a FIELD: n_races races of C = n_cars driven cars, every car the ego of its own NLP and an
+// obstacle of the C - 1 others (see crx_field_prep_dev in include/crx.h, quirks F1-F7).  One thread per (race, car); a workgroup owns
+// 256 / C WHOLE races, so what a car reads of the others was written inside its own workgroup and one block barrier separates the
+// two phases (the threads past the last whole race of a block, and the races past n_races of the last block, only take the barrier).
+//   phase 1  racing/offboard.py:51-94: N + 1 zero-input Euler steps of the curvilinear state along the track's curvature (the plant's
+//            lookup over LDS tables, crx_plant_step.h), `while s > L: s -= L` after every step (:90-91) as wrap_above -- no loop here
+//            runs on device data.  Trig-bound: 2 (N + 1) sin / cos per car.
+//   phase 2  control/control.py:499-540 with realtime_flag == True: the window test and the lap offset on column 0 of each other car's
+//            prediction, kept cars packed to the front in car order, the rest zero; (l_e / 2 + l_o / 2, w_e / 2 + w_o / 2) per kept
+//            slot (:532-535) when the cars bring their own dimensions; the smallest super-ellipse value against the others at the
+//            CURRENT states (below 1: contact).
+// A car with a non-finite state predicts non-finite rows, passes nobody's window test (every comparison with a NaN is false), keeps
+// nobody itself, and never lowers a `clear`.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) crx_field_prep_kernel(const crx_field_kparams fp) {
+    __shared__ double seg_lo[CRX_PLANT_MAX_SEG], seg_hi[CRX_PLANT_MAX_SEG], seg_cv[CRX_PLANT_MAX_SEG];
+    const crx_field_desc& d = fp.d;
+    for (int i = threadIdx.x; i < d.n_seg; i += blockDim.x) {
+        seg_lo[i] = fp.track[6 * i + 3];
+        seg_hi[i] = fp.track[6 * i + 3] + fp.track[6 * i + 4];
+        seg_cv[i] = fp.track[6 * i + 5];
+    }
+    __syncthreads();
+    const int C = d.n_cars, V = C - 1, N1 = d.N + 1, per_block = 256 / C;
+    const int rl = threadIdx.x / C, c = threadIdx.x - rl * C, r = blockIdx.x * per_block + rl;
+    const bool live = rl < per_block && r < fp.n_races;
+    const size_t rc = (size_t)r * C + c;   // this thread's car = problem rc of the solver launch (race-major, car-minor)
+    const double L = d.lap_length, dt = d.dt;
+    if (live) {
+        const double* x = fp.xcurv + 6 * rc;
+        const double vx = x[0], vy = x[1], wz = x[2];
+        double epsi = x[3], s = x[4], ey = x[5];
+        double* ps = fp.pred_s + rc * N1;
+        double* pe = fp.pred_ey + rc * N1;
+        for (int j = 0; j < N1; j++) {
+            // curvature at s (wrapped into one lap), first segment with lo <= s <= hi (quirk F6)
+            const double sw = wrap_below(wrap_above(s, L), L);
+            double curv = 0.0;
+            for (int i = 0; i < d.n_seg; i++)
+                if (sw >= seg_lo[i] && sw <= seg_hi[i]) { curv = seg_cv[i]; break; }
+            const double ce = cos(epsi), se = sin(epsi);
+            const double v_long = (vx * ce - vy * se) / (1 - curv * ey);
+            const double epsi_n = epsi + dt * (wz - v_long * curv);
+            const double s_n = s + dt * v_long;
+            const double ey_n = ey + dt * (vx * se + vy * ce);
+            epsi = epsi_n; s = wrap_above(s_n, L); ey = ey_n;   // the roll-out continues from the wrapped value (quirk F3)
+            ps[j] = s; pe[j] = ey;
+        }
+    }
+    __syncthreads();   // the predictions of this block's races are in memory; workgroup scope is all phase 2 needs
+    if (!live) return;
+    const double* xe = fp.xcurv + 6 * rc;
+    const double s_e = xe[4], ey_e = xe[5], margin = d.safety_time * xe[0];
+    double nce;
+    const double dist_ego = lap_fold(s_e, L, nce);
+    // a car's own (length, width); device-resident dimensions cannot be validated on the host: dim_or_default (crx_num.h)
+    const double l_e = fp.car_dims ? dim_or_default(fp.car_dims[2 * rc], d.l_sum) : 0.0;
+    const double w_e = fp.car_dims ? dim_or_default(fp.car_dims[2 * rc + 1], d.w_sum) : 0.0;
+    int n = 0;
+    double clr = INFINITY;
+    for (int o = 0; o < C; o++) {   // car order, skipping the ego (quirk F5)
+        if (o == c) continue;
+        const size_t ro = (size_t)r * C + o;
+        double l_sum = d.l_sum, w_sum = d.w_sum;
+        if (fp.car_dims) {
+            l_sum = l_e / 2 + dim_or_default(fp.car_dims[2 * ro], d.l_sum) / 2;
+            w_sum = w_e / 2 + dim_or_default(fp.car_dims[2 * ro + 1], d.w_sum) / 2;
+        }
+        if (fp.clear) {
+            const double* xo = fp.xcurv + 6 * ro;
+            double m = fmod(s_e - xo[4] + L / 2, L);   // Python's %: the sign of the divisor
+            if (m < 0.0) m += L;
+            const double a = (m - L / 2) / l_sum, b = (ey_e - xo[5]) / w_sum;
+            double pa = 1.0, pb = 1.0;
+            for (int k = 0; k < d.degree; k++) { pa *= a; pb *= b; }
+            const double h = pa + pb;
+            clr = h < clr ? h : clr;
+        }
+        const double* is = fp.pred_s + ro * N1;
+        const double* ie = fp.pred_ey + ro * N1;
+        double off;
+        if (safety_window(dist_ego, nce, is[0], margin, L, off)) {   // column 0: one estimated step ahead (quirk F2)
+            double* os = fp.obs_s + (rc * V + n) * N1;
+            double* oe = fp.obs_ey + (rc * V + n) * N1;
+            for (int j = 0; j < N1; j++) { os[j] = is[j]; oe[j] = ie[j]; }
+            fp.lap_off[rc * V + n] = off;
+            if (fp.obs_dims) { fp.obs_dims[(rc * V + n) * 2] = l_sum; fp.obs_dims[(rc * V + n) * 2 + 1] = w_sum; }
+            n++;
+        }
+    }
+    for (int v = n; v < V; v++) {
+        double* os = fp.obs_s + (rc * V + v) * N1;
+        double* oe = fp.obs_ey + (rc * V + v) * N1;
+        for (int j = 0; j < N1; j++) { os[j] = 0.0; oe[j] = 0.0; }
+        fp.lap_off[rc * V + v] = 0.0;
+        if (fp.obs_dims) { fp.obs_dims[(rc * V + v) * 2] = 0.0; fp.obs_dims[(rc * V + v) * 2 + 1] = 0.0; }
+    }
+    fp.n_obs[rc] = n;
+    if (fp.clear) fp.clear[rc] = clr;
+}
+
 hipError_t crx_launch_prep(const crx_prep_kparams& pp, hipStream_t st) { return crx_launch_1d(crx_prep_kernel, pp.n_scen, 1, WAVE, st, pp); }
 hipError_t crx_launch_scene(const crx_scene_kparams& sp, hipStream_t st) { return crx_launch_1d(crx_scene_kernel, sp.n_scen, 1, WAVE, st, sp); }
 hipError_t crx_launch_trackprep(const crx_trackprep_kparams& tp, hipStream_t st) {
     return crx_launch_1d(crx_trackprep_kernel, tp.batch, 256, 256, st, tp);
 }
 hipError_t crx_launch_cbfprep(const crx_cbfprep_kparams& cp, hipStream_t st) { return crx_launch_1d(crx_cbfprep_kernel, cp.batch, 256, 256, st, cp); }
+// whole races per block: 256 / n_cars of them (n_cars in 1 .. CRX_MAX_OBS + 1, checked by the caller)
+hipError_t crx_launch_field_prep(const crx_field_kparams& fp, hipStream_t st) {
+    return crx_launch_1d(crx_field_prep_kernel, fp.n_races, 256 / fp.d.n_cars, 256, st, fp);
+}

@@ -44,7 +44,9 @@
 extern "C" {
 #endif
 
-#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_plant_step_params, crx_plant_step_params_dev, crx_plant_step_params_plain_dev and
+#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_field_desc, crx_field_desc_default, crx_field_prep, crx_field_prep_dev (field races: every
+                          car of a race drives itself) -- new entry points only.
+                          0.4.0 (additive, same number): crx_plant_step_params, crx_plant_step_params_dev, crx_plant_step_params_plain_dev and
                           CRX_PLANT_NPARAM (one BicycleDynamicsParam set per vehicle) -- new entry points only.
                           0.4.0 (additive, same number): crx_planner_models_reach_dev, crx_planner_solve_models, crx_planner_solve_models_dev,
                           crx_planner_plan_models, crx_planner_plan_models_dev, CRX_PLANNER_MODEL_REACH_DOUBLES -- new entry points only.
@@ -789,6 +791,66 @@ int crx_path_plan_dev(const crx_pathprep_desc* d, const crx_path_desc* qd, int n
 int crx_cbf_prep_dev(int N, int V, double lap_length, double t, double dt, double safety_time, int batch,
                      const double* xcurv, const double* car_s0, const double* car_v, const double* car_ey,
                      double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, void* stream);
+
+/*
+ * Field races: the obstacle arrays of control.mpccbf when EVERY car of a race drives itself.  n_races races of C = n_cars cars
+ * (1 <= C <= CRX_MAX_OBS + 1, V = C - 1): each car is the ego of its own NLP and an obstacle of the V others, so one call prepares
+ * the n_races * C problems of ONE crx_cbf_solve* launch, race-major, car-minor.  One kernel launch, two phases:
+ *   predictions   every car by the zero-input roll-out the reference's driven model offers its opponents
+ *                 (racing/offboard.py:51-94, DynamicBicycleModel.get_estimation / get_trajectory_nsteps(N + 1)): N + 1 times
+ *                   v_long = (vx cos(epsi) - vy sin(epsi)) / (1 - curv ey);  epsi += dt (wz - v_long curv);  s += dt v_long;
+ *                   ey += dt (vx sin(epsi) + vy cos(epsi))          (every right-hand side on the old state; vx, vy, wz constant)
+ *                 with curv looked up at the old s folded into one lap, and `while s > L: s -= L` after every step (:90-91)
+ *   obstacles     per ego, the other cars in car order: window test dist_obs - safety_time vx < dist_ego < dist_obs + safety_time vx on
+ *                 the lap-folded positions and lap offset (num_cycle_ego - num_cycle_obs) lap_length, both from column 0 of the
+ *                 prediction (control/control.py:499-523, 538-540; int() truncates toward zero); kept cars packed to the front, the rest zero
+ *   track [n_seg][6] (the plant's segment table);  xcurv [R][C][6];  car_dims [R][C][2] (length, width of every car) or NULL
+ *   pred_s, pred_ey [R][C][N+1]                                                     out: what the reference logs as the prediction
+ *   obs_s, obs_ey [R][C][V][N+1];  lap_off [R][C][V];  n_obs [R][C]                 out: the obstacle inputs of crx_cbf_solve*, batch R C
+ *   obs_dims [R][C][V][2]    out, non-NULL iff car_dims (with C == 1 it holds nothing and may be NULL either way): kept slot = (l_ego / 2 + l_obs / 2, w_ego / 2 + w_obs / 2) (control.py:532-535),
+ *                            slots >= n_obs zero; the obs_dims argument of crx_cbf_solve_dims / crx_cbf_solve_models*
+ *   clear [R][C]             out, may be NULL: min over the other cars of (ds / l_sum)^degree + (dey / w_sum)^degree at the CURRENT states,
+ *                            ds = (s_ego - s_obs + L / 2) mod L - L / 2 (the sign of L), l_sum, w_sum from car_dims or the descriptor's
+ *                            pair; below 1 is contact; +inf when C == 1
+ * With C == 1 the obs_* / lap_off arrays hold nothing and may be NULL.  Device-resident car_dims cannot be validated: a non-positive or
+ * non-finite length / width counts as the descriptor's l_sum / w_sum; the host-pointer entry refuses such rows.  A car with a
+ * non-finite state gets non-finite predictions, is kept by nobody and keeps nobody; it touches no other car.
+ * Accuracy: the roll-out is the reference's float64 arithmetic up to the rounding of sin / cos and of fused multiply-adds (1e-12 against
+ * the reference's own rows, tests/golden/field_pred.npz) -- wherever the expression is well conditioned.  It divides by 1 - curv ey: a
+ * roll-out that drifts towards the centre of a curve (ey -> 1 / curv, off any track) amplifies every rounding error without bound, here
+ * as in the reference.
+ * Quirks kept:
+ *   F1  all cars of a step see the same snapshot, the states at the start of the step.  The reference's off-board simulator steps its
+ *       vehicles one after the other (offboard.py:124-127) and its real-time nodes run asynchronously: neither defines a lockstep field.
+ *       The snapshot is this library's definition; it is what lets one solver launch serve a whole step.
+ *   F2  column 0 of a prediction is one estimated step AHEAD of the current state (offboard.py:83-89); the window test and the lap
+ *       offset use that column (control.py:518-519).
+ *   F3  the wrap after every step: an opponent that crosses the line inside the horizon jumps by -L in obs_s, and the rows reach the
+ *       solver as the reference builds them (together with quirk Q1).
+ *   F4  the global half of get_estimation is not computed (its doubled assignment of component 4 included): mpccbf discards it.
+ *   F5  obstacles come in car-index order, skipping the ego: the reference's dict order.
+ *   F6  s exactly on a segment boundary takes the first matching segment, like the plant; the reference raises there (int() of a
+ *       two-element index array).
+ *   F7  this is the realtime_flag == True construction of control.mpccbf; with realtime_flag == False the reference calls
+ *       get_trajectory_nsteps(time, timestep, n), which its DynamicBicycleModel does not accept.
+ */
+typedef struct crx_field_desc {
+    int32_t N;            /* horizon, 1 .. CRX_MAX_N: N + 1 prediction columns */
+    int32_t n_cars;       /* C, 1 .. CRX_MAX_OBS + 1 */
+    int32_t n_seg;        /* rows of the track table, 1 .. 64 */
+    int32_t degree;       /* 6: exponent of `clear` (2, 4, 6 or 8) */
+    double lap_length;
+    double dt;            /* 0.1 */
+    double safety_time;   /* 2.0 (control.py:499) */
+    double l_sum;         /* 0.4: l_ego / 2 + l_obs / 2 where no car_dims are given */
+    double w_sum;         /* 0.2 */
+} crx_field_desc;
+void crx_field_desc_default(crx_field_desc* d, int N, int n_cars, int n_seg, double lap_length);
+int crx_field_prep(const crx_field_desc* d, int n_races, const double* track, const double* xcurv, const double* car_dims, double* pred_s,
+                   double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims, double* clear);
+int crx_field_prep_dev(const crx_field_desc* d, int n_races, const double* track, const double* xcurv, const double* car_dims, double* pred_s,
+                       double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims, double* clear,
+                       void* stream);
 
 /*
  * Inputs of control.mpc_multi_agents' NLP (crx_cbf_solve with per_stage_target = 1) from the planner's outputs, on the device

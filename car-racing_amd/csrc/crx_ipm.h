@@ -93,17 +93,17 @@ __device__ __forceinline__ double ipm_dw_grow(double dw, double dw_last) { retur
 //   rule                   kernel (file:line)                                  why it stays
 //   termination test       crx_solve_kernel, Mehrotra (crx_kernels.hip:2263)   code changes in 5 of 39 solver instantiations
 //                          crx_solve_kernel, NLP (crx_kernels.hip:2430-2446)   code changes in 32 of 39 (the E0 test guards the lazy row pass for vu)
-//                          crx_lmpc_kernel (crx_lmpc.hip:499)                  code changes in all six instantiations
+//                          crx_lmpc_kernel (crx_lmpc.hip:529)                  code changes in all six instantiations
 //                          crx_path_kernel (crx_path_qp.h:71)                  code changes (the products e_d * sd, e_c * sd are evaluated lazily there)
-//   barrier update         crx_lmpc_kernel (crx_lmpc.hip:530-531)              code changes in <12,0,44,*>; same arithmetic as ipm_mu_reached / ipm_next_mu<true>
+//   barrier update         crx_lmpc_kernel (crx_lmpc.hip:560-561)              code changes in <12,0,44,*>; same arithmetic as ipm_mu_reached / ipm_next_mu<true>
 //   mu^theta_mu            crx_path_kernel (crx_path_qp.h:76)                  DIFFERENT ARITHMETIC: ipm_next_mu<false>, pow() for every theta_mu; the other
 //                                                                              two kernels mu sqrt(mu) at 1.5
-//   theta_min / theta_max  crx_lmpc_kernel (crx_lmpc.hip:791-794)              code changes in all six instantiations
+//   theta_min / theta_max  crx_lmpc_kernel (crx_lmpc.hip:801-804)              code changes in all six instantiations
 //   switching condition    crx_solve_kernel (crx_kernels.hip:2644-2648, :2699) DIFFERENT ARITHMETIC, three forms: log2 domain with the al-independent part
-//                          crx_lmpc_kernel (crx_lmpc.hip:819)                  hoisted (solver), log2 domain inline (learning MPC), two pow() (path).  The
+//                          crx_lmpc_kernel (crx_lmpc.hip:826)                  hoisted (solver), log2 domain inline (learning MPC), two pow() (path).  The
 //                          crx_path_kernel (crx_path_qp.h:131)                 exponents are IPM_S_PHI / IPM_S_THETA in all three.
 //   Armijo condition       crx_solve_kernel (crx_kernels.hip:2700)             code changes in 32 of 39 solver instantiations
-//                          crx_lmpc_kernel (crx_lmpc.hip:821)                  code changes in all six instantiations
+//                          crx_lmpc_kernel (crx_lmpc.hip:828)                  code changes in all six instantiations
 //                          crx_path_kernel (crx_path_qp.h:133)                 code changes
 //   dual safeguard         crx_path_kernel (crx_path_qp.h:150-151)             DIFFERENT ARITHMETIC: mu / (kappa_sigma t) and kappa_sigma mu / t; the other
 //                                                                              two kernels clamp against mu_t = mu * rcp(t): ipm_dual_safeguard

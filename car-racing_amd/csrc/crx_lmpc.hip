@@ -85,7 +85,7 @@ struct LL {
 };
 
 struct LCtx {
-    int N, nu2, nv, M, m, el, lane;
+    int N, nu2, nv, M, m, lane;
     int r_st, r_lam, r_el;
 };
 
@@ -128,53 +128,71 @@ __device__ __forceinline__ double hu_dot(const double* sm, const LCtx& x, const 
     return even ? acc + 0.0 : init + acc;
 }
 
-
 #define LDS(i) sm[(i)]
 #define LSINK(cond, off) seli((cond), (off), L::dmy)
 // all rows of the problem, uniform trip count: a lane past the last row recomputes row 0 (rv = false); pure stores rewrite
 // row 0 with the same value, read-modify-write stores go to the sink, sums and products are masked with rv
 #define LROWS(r, rv, lane_, m_) for (int r0_ = 0; r0_ < (m_); r0_ += WAVE) \
-    if (const bool rv = r0_ + (lane_) < (m_); true) if (const int r = rv ? r0_ + (lane_) : 0; true)
+    if ([[maybe_unused]] const bool rv = r0_ + (lane_) < (m_); true) if (const int r = rv ? r0_ + (lane_) : 0; true)
+
+// THE ROW MAP, stated once: row r is an input-box row (r < r_st: input 2 (r >> 2) + ((r & 3) >> 1) against its bound ub, lower bound for even r,
+// upper for odd), a state row (r < r_lam: stage k = (r - r_st) / 3 + 1, kind q3 = 0 vx <= v_max, 1 ey <= w, 2 -ey <= w) or a lambd row.  Every lane
+// decodes all three kinds on clamped indices and selects (straight-line).  For the vector at `vo` with its lambd part at `lo`:
+//     bv = the input of a box row -> vbox = BOX(bv, rb, ub);   lv = the lambd of a lambd row;   rowv = the value of row r's kind;
+//     sx = init(k, q3) + S_row . v of a state row, two accumulators over ALL inputs (S[k][.][a] is zero for a >= 2k) -> vst = ST(sx, q3).
+// l_rows applies it to the iterate (u, lam), the row-step pass to the step (du, dlam).  Loads and arithmetic stand in the order both passes
+// had them: the compiler's schedule follows the source order (HISTORY.md, round 15).
+#define LROW_MAP(r, vo, lo, init, BOX, ST)                                                                     \
+    const bool isbox = r < x.r_st, isst = !isbox && r < x.r_lam;                                               \
+    const int rb = isbox ? r : 0;                                                                              \
+    [[maybe_unused]] const double ub = (rb & 2) ? kp.a_max : kp.delta_max;                                     \
+    const double bv = LDS((vo) + 2 * (rb >> 2) + ((rb & 3) >> 1));                                             \
+    const double vbox = (BOX);                                                                                 \
+    const int rr = isst ? r - x.r_st : 0, k = rr / 3 + 1, q3 = rr - 3 * (k - 1);                               \
+    const int so = L::S + L::srow(k, q3 ? 1 : 0) * L::NU2;                                                     \
+    double s0 = (init), s1 = 0.0;                                                                              \
+    _Pragma("unroll 4") for (int a = 0; a < x.nv; a += 2) {                                                    \
+        s0 = fma(LDS(so + a), LDS((vo) + a), s0);                                                              \
+        s1 = fma(LDS(so + a + 1), LDS((vo) + a + 1), s1);                                                      \
+    }                                                                                                          \
+    const double sx = s0 + s1, vst = (ST);                                                                     \
+    const double lv = LDS((lo) + ((!isbox && !isst) ? r - x.r_lam : 0));                                       \
+    const double rowv = sel(isbox, vbox, sel(isst, vst, lv))
 
 // rows c_j(v) for the current iterate; rp = c - t
 template <int NMAX, bool DENSE, int MSS>
 __device__ __forceinline__ void l_rows(double* sm, const LCtx& x, const crx_lmpc_kparams& kp) {
     using L = LL<NMAX, DENSE, MSS>;
-    // straight-line: every lane evaluates all three row kinds on clamped indices and selects; lanes past the last row
-    // recompute row 0.  The state rows sum over ALL inputs -- S[k][.][a] is zero for a >= 2k, the bound was a shortcut.
-    for (int r0 = 0; r0 < x.m; r0 += WAVE) {
-        const int r = r0 + x.lane < x.m ? r0 + x.lane : 0;
-        const bool isbox = r < x.r_st, isst = !isbox && r < x.r_lam;
-        const int rb = isbox ? r : 0, q = rb & 3;
-        const double ub = (q & 2) ? kp.a_max : kp.delta_max, uv = LDS(L::u + 2 * (rb >> 2) + (q >> 1));
-        const double cbox = (q & 1) ? ub - uv : uv + ub;
-        const int rr = isst ? r - x.r_st : 0, k = rr / 3 + 1, q3 = rr - 3 * (k - 1);
-        const int so = L::S + L::srow(k, q3 ? 1 : 0) * L::NU2;
-        double s0 = LDS(L::xf + 6 * k + (q3 ? 5 : 0)), s1 = 0.0;
-#pragma unroll 4
-        for (int a = 0; a < x.nv; a += 2) {
-            s0 = fma(LDS(so + a), LDS(L::u + a), s0);
-            s1 = fma(LDS(so + a + 1), LDS(L::u + a + 1), s1);
-        }
-        const double sx = s0 + s1;
-        const double cst = q3 == 0 ? kp.v_max - sx : (q3 == 1 ? kp.ey_max - sx : sx + kp.ey_max);
-        const double clam = LDS(L::lam + ((!isbox && !isst) ? r - x.r_lam : 0));
-        const double cv = sel(isbox, cbox, sel(isst, cst, clam));
-        LDS(L::c + r) = cv;
+    LROWS(r, rv, x.lane, x.m) {
+        LROW_MAP(r, L::u, L::lam, LDS(L::xf + 6 * k + (q3 ? 5 : 0)), (rb & 1) ? ub - bv : bv + ub,
+                 q3 == 0 ? kp.v_max - sx : (q3 == 1 ? kp.ey_max - sx : sx + kp.ey_max));
+        LDS(L::c + r) = rowv;
     }
 }
+
+// THE TRIAL POINT of row r at step length al (all rows linear: c(v + al dv) = c + al J dv, J dv in wv): the row value cj and the slack
+// tn = max(t + al dt, cj) with dt = rp + J dv formed where it is read.  The line search evaluates it, the accept pass takes it over.
+#define LTRIAL(r, al)                                                                                          \
+    const double tt = LDS(L::t + r), jd = LDS(L::wv + r), rpr = LDS(L::c + r) - tt;                             \
+    const double cj = (rpr + tt) + (al) * jd;                                                                  \
+    const double tn = fmax(fma((al), rpr + jd, tt), cj)
+
+// the three state rows of stage k = lane of the row array at `wo`, packed per stage: w0[k] = the vx row's entry, w5[k] = the two ey rows' entries
+// combined by OP (-: J'w of l_lagr, c = bound -/+ x_k; +: the stage weights of K_u)
+#define LPACK_STATE_ROWS(wo, OP)                                                                               \
+    {                                                                                                          \
+        const bool kv = x.lane >= 1 && x.lane < x.N;                                                           \
+        const int k = kv ? x.lane : 1, r = x.r_st + 3 * (k - 1);                                               \
+        const double a0 = LDS((wo) + r), a1 = LDS((wo) + r + 1), a2 = LDS((wo) + r + 2);                        \
+        LDS(LSINK(kv, L::w0 + k)) = a0;                                                                        \
+        LDS(LSINK(kv, L::w5 + k)) = a1 OP a2;                                                                  \
+    }
 
 // (ru, rl) = g + E'y - J'w   with w = the row array at offset `wo`
 template <int NMAX, bool DENSE, int MSS>
 __device__ __forceinline__ void l_lagr(double* sm, const LCtx& x, const crx_lmpc_kparams& kp, int wo) {
     using L = LL<NMAX, DENSE, MSS>;
-    {
-        const bool kv = x.lane >= 1 && x.lane < x.N;
-        const int k = kv ? x.lane : 1, r = x.r_st + 3 * (k - 1);
-        const double a0 = LDS(wo + r), a1 = LDS(wo + r + 1), a2 = LDS(wo + r + 2);
-        LDS(LSINK(kv, L::w0 + k)) = a0;
-        LDS(LSINK(kv, L::w5 + k)) = a1 - a2;
-    }
+    LPACK_STATE_ROWS(wo, -)
     SYNC();
     {
         const bool av = x.lane < x.nv;
@@ -204,6 +222,27 @@ __device__ __forceinline__ void l_lagr(double* sm, const LCtx& x, const crx_lmpc
     SYNC();
 }
 
+// the stage models A, B, C of problem pb from HBM into the K region (coalesced): at set-up, and again for the write-back's roll-out
+#define LLOAD_MODEL()                                                                                          \
+    for (int i = lane; i < 36 * N; i += WAVE) LDS(L::A + i) = kp.A[(size_t)36 * N * pb + i];                    \
+    for (int i = lane; i < 12 * N; i += WAVE) LDS(L::B + i) = kp.B[(size_t)12 * N * pb + i];                    \
+    for (int i = lane; i < 6 * N; i += WAVE) LDS(L::C + i) = kp.C[(size_t)6 * N * pb + i]
+// the model rolled out over the stages from the state at `xo`: x_{k+1} = A_k x_k (+ B_k u_k) + C_k into xo + 6 (k + 1), lane = component.
+// Without the input term it is the free response xf of the set-up, with it the plan that is written back.
+#define LROLLOUT(xo, INPUTS)                                                                                   \
+    for (int k = 0; k < N; k++) {                                                                              \
+        if (lane < 6) {                                                                                        \
+            double s = LDS(L::C + 6 * k + lane);                                                               \
+            for (int c6 = 0; c6 < 6; c6++) s = fma(LDS(L::A + 36 * k + 6 * lane + c6), LDS((xo) + 6 * k + c6), s); \
+            if (INPUTS) {                                                                                      \
+                s = fma(LDS(L::B + 12 * k + 2 * lane), LDS(L::u + 2 * k), s);                                  \
+                s = fma(LDS(L::B + 12 * k + 2 * lane + 1), LDS(L::u + 2 * k + 1), s);                          \
+            }                                                                                                  \
+            LDS((xo) + 6 * (k + 1) + lane) = s;                                                                \
+        }                                                                                                      \
+        SYNC();                                                                                                \
+    }
+
 // NFIX [r3]: the horizon as a compile-time constant (12, the reference's lmpc_param.num_horizon; 0 = read kp.N), as in crx_solve_kernel:
 // +3 % on the stand-alone launch and on the closed-loop step (HISTORY.md, round 3), identical bits (tools/lmpc_ab.py).  The safe-set
 // count as a constant too was measured beside it and does not pay.
@@ -213,6 +252,10 @@ __device__ __forceinline__ void l_lagr(double* sm, const LCtx& x, const crx_lmpc
 // compiler also sees how many waves the LDS admits per CU, rounds five or six per CU down to ONE per SIMD and takes > 256 registers (four per
 // CU); and an amdgpu_waves_per_eu(2) floor against that costs the tuned instantiation 8 % (1.654 ms) -- both measured, tools/gpu_pass.sh game:NAME.
 // [r5] The unit is built with MachineLICM off + max-ilp scheduling (Makefile has the numbers): 216 / 222 VGPRs, two waves per SIMD everywhere.
+// The kernel phase by phase, as its banners name them ([n]: the TICK() that ends the phase, column n - 1 of the trace row, tools/gpu_lmpc_trace.py):
+//   SET-UP (load, free response, cost, sensitivities), REACH SCREEN, then per attempt the START POINT and the iteration --
+//   [1] rows, gradient, residual  [2] error measure (termination, certificate)  [3] barrier update  [4] Sigma, omega, rhs  [5] K_u  [6] Cholesky
+//   [7..9] W~, L_w, G in product form  [10] dy, dlambd, du  [11] row steps  [12] filter line search  [13] accept -- and the WRITE-BACK.
 template <int NFIX> struct LmpcStaticLds { static constexpr bool v = NFIX != 0; };
 template <int NMAX, bool DENSE, int MSS, int NFIX = 0>
 __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams kp) {
@@ -244,10 +287,8 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
         SYNC();
     }
 
-    // ---- load the problem (coalesced) --------------------------------------------------------------
-    for (int i = lane; i < 36 * N; i += WAVE) LDS(L::A + i) = kp.A[(size_t)36 * N * pb + i];
-    for (int i = lane; i < 12 * N; i += WAVE) LDS(L::B + i) = kp.B[(size_t)12 * N * pb + i];
-    for (int i = lane; i < 6 * N; i += WAVE) LDS(L::C + i) = kp.C[(size_t)6 * N * pb + i];
+    // ---- SET-UP: load the problem (coalesced) --------------------------------------------------------
+    LLOAD_MODEL();
     for (int i = lane; i < 6 * Mx; i += WAVE) {
         int c6 = i / Mx, j = i - c6 * Mx;
         if (j < M) LDS(L::SS + c6 * L::MS + j) = kp.ss[(size_t)6 * Mx * pb + i];
@@ -259,28 +300,18 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
     if (DENSE)
         for (int i = lane; i < L::NU2 * L::NU2; i += WAVE) LDS(L::Hu + i) = 0.0;
     SYNC();
-    // free response
-    for (int k = 0; k < N; k++) {
-        if (lane < 6) {
-            double s = LDS(L::C + 6 * k + lane);
-            for (int c6 = 0; c6 < 6; c6++) s = fma(LDS(L::A + 36 * k + 6 * lane + c6), LDS(L::xf + 6 * k + c6), s);
-            LDS(L::xf + 6 * (k + 1) + lane) = s;
-        }
-        SYNC();
-    }
+    LROLLOUT(L::xf, false)   // free response
     // cost: f = 1/2 u'Hu u + g0u'u + f0 + qf'lambd; the R / dR part first, the tracking part (Q) stage by stage below
     double f0 = kp.dR[0] * uold0 * uold0 + kp.dR[1] * uold1 * uold1;
     const bool anyQ = kp.Q[0] != 0.0 || kp.Q[1] != 0.0 || kp.Q[2] != 0.0 || kp.Q[3] != 0.0 || kp.Q[4] != 0.0 || kp.Q[5] != 0.0;
     if (lane < nu2) {
         const int a = lane, i = a >> 1, cc = a & 1;
         const double R = cc ? kp.R[1] : kp.R[0], dR = cc ? kp.dR[1] : kp.dR[0];
-        double dd = 2.0 * R + 2.0 * dR + (i + 1 < N ? 2.0 * dR : 0.0);
         if (DENSE) {
-            LDS(L::Hu + a * L::NU2 + a) = dd;
+            LDS(L::Hu + a * L::NU2 + a) = 2.0 * R + 2.0 * dR + (i + 1 < N ? 2.0 * dR : 0.0);   // (= hu_band_diag: through it the dense code moves)
             if (i > 0) LDS(L::Hu + a * L::NU2 + a - 2) = -2.0 * dR;
             if (i + 1 < N) LDS(L::Hu + a * L::NU2 + a + 2) = -2.0 * dR;
         }
-        (void)dd;
         LDS(L::g0u + a) = i == 0 ? -2.0 * dR * (cc ? uold1 : uold0) : 0.0;
     } else if (lane < nu2 + 6) {
         if (DENSE) LDS(L::Hu + lane * L::NU2 + lane) = 2.0 * kp.w_x0;
@@ -352,7 +383,7 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
     x.r_lam = x.r_st + 3 * (N - 1);
     x.r_el = x.r_lam + M;
 
-    // [r3] Reachability screen of the first attempt.  The inputs are boxed, so component c of x_N stays within g_c = sum_a |dx_N,c / du_a|
+    // ---- REACH SCREEN [r3]: reachability screen of the first attempt.  The inputs are boxed, so component c of x_N stays within g_c = sum_a |dx_N,c / du_a|
     // umax_a of its free response (both are on the table after the set-up: xf, the stage-N rows of S), and the terminal equality
     // x_N = SS lambd with lambd in the unit simplex needs x_N,c inside [min_j SS_cj, max_j SS_cj].  Disjoint intervals (by more than
     // 1e-6 of their scale) in ANY component prove that the reference's QP has no feasible point, whatever its other rows say: the
@@ -391,11 +422,10 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
     int proved = first_attempt | bad0;   // CRX_INFEASIBLE is only ever a PROOF (include/crx.h): the screen / a bound the fixed x_0 violates, or the certificate below
     double E0 = HUGE_VAL, f = 0.0;
     for (int attempt = first_attempt; attempt < 2; attempt++) {
-        x.el = attempt;
         x.nv = nu2 + (attempt ? 6 : 0);
         x.m = x.r_el;
         const int m = x.m, nv = x.nv;
-        // ---- start point: v = 0, y = 0, t = max(|c|, push), nu = 1 (lambd / elastic rows: cost gradient) ----
+        // ---- START POINT: v = 0, y = 0, t = max(|c|, push), nu = 1 (lambd / elastic rows: cost gradient) ----
         if (lane < L::NU2) LDS(L::u + lane) = 0.0;
         if (lane < L::MS) LDS(L::lam + lane) = 0.0;
         if (lane < 8) LDS(L::y + lane) = 0.0;
@@ -437,7 +467,7 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
 #define TICK() do { } while (0)
 #endif
             TICK();
-            // ---- rows, gradient, equality residual ----
+            // ---- [1] rows, gradient, equality residual ----
             l_rows<NMAX, DENSE, MSS>(sm, x, kp);
             {   // gu = g0u + Hu u (lane = row); lanes past nv run row 0 and store to the sink.  Two accumulators.
                 const bool av = lane < nv;
@@ -466,7 +496,7 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
             }
             SYNC();
             TICK();   // 1
-            // ---- error measure ----
+            // ---- [2] error measure ----
             l_lagr<NMAX, DENSE, MSS>(sm, x, kp, L::nu);
             double nus = 0.0, e_p = 0.0, e_c = 0.0, theta = 0.0;
             LROWS(r, rv, lane, m) {
@@ -522,10 +552,10 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
                 if (F < -1e-8 * (nus + ys)) { status = CRX_INFEASIBLE; break; }
             }
             TICK();   // 2
-            // ---- barrier update ----
+            // ---- [3] barrier update ----
             for (;;) {
                 double e_cm = 0.0;
-                LROWS(r, rv, lane, m) { (void)rv; e_cm = fmax(e_cm, fabs(LDS(L::t + r) * LDS(L::nu + r) - mu)); }
+                LROWS(r, rv, lane, m) { e_cm = fmax(e_cm, fabs(LDS(L::t + r) * LDS(L::nu + r) - mu)); }
                 e_cm = wave_max(e_cm) / sc;
                 if (fmax(e_d, fmax(e_p, e_cm)) <= o.kappa_eps * mu && mu > o.tol / 10.0) {   // barrier update, written out: crx_ipm.h, table
                     mu = fmax(o.tol / 10.0, fmin(o.kappa_mu * mu, o.theta_mu == 1.5 ? mu * sqrt(mu) : pow(mu, o.theta_mu)));
@@ -535,9 +565,8 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
             }
             TICK();   // 3
             const double tau = ipm_tau(mu, o.tau_min);
-            // ---- Sigma (in dnu), omega = mu/t - Sigma rp (in wv); rhs = -(g + E'y - J'omega) ----
+            // ---- [4] Sigma (in dnu), omega = mu/t - Sigma rp (in wv); rhs = -(g + E'y - J'omega) ----
             LROWS(r, rv, lane, m) {
-                (void)rv;
                 const double tt = LDS(L::t + r), ti = frcp(tt), sg = LDS(L::nu + r) * ti;
                 const double rpr = LDS(L::c + r) - tt;
                 LDS(L::dnu + r) = sg;
@@ -545,17 +574,10 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
             }
             SYNC();
             l_lagr<NMAX, DENSE, MSS>(sm, x, kp, L::wv);   // ru, rl = -(rhs)
-            // stage weights of the state rows for K_u
-            {
-                const bool kv = lane >= 1 && lane < N;
-                const int k = kv ? lane : 1, r = x.r_st + 3 * (k - 1);
-                const double d0 = LDS(L::dnu + r), d1 = LDS(L::dnu + r + 1), d2 = LDS(L::dnu + r + 2);
-                LDS(LSINK(kv, L::w0 + k)) = d0;
-                LDS(LSINK(kv, L::w5 + k)) = d1 + d2;
-            }
+            LPACK_STATE_ROWS(L::dnu, +)   // stage weights of the state rows for K_u
             SYNC();
             TICK();   // 4
-            // ---- K_u (lower triangle) + extra rows Phi (6) and rhs_u ----
+            // ---- [5] K_u (lower triangle) + extra rows Phi (6) and rhs_u ----
             // One lane per (row a, chunk of 6 columns b0..b0+5): the row's S entries and weights are loaded once per stage
             // and feed six accumulators (an entry-per-lane map re-loaded them for every entry: 3x the LDS reads).  Rows
             // 6g..6g+5 have g+1 chunks each, 3g(g+1) chunks precede group g.  Lanes past the last chunk recompute chunk 0;
@@ -596,10 +618,10 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
             }
             SYNC();
             TICK();   // 5
-            int ok = l_chol(sm, L::K, L::LDK, L::ik, nv, 7, lane, L::IKS);
+            int ok = l_chol(sm, L::K, L::LDK, L::ik, nv, 7, lane, L::IKS);   // ---- [6] Cholesky of K_u, with Phi and rhs_u as extra rows ----
             TICK();   // 6
             if (!ok) break;
-            // ---- W~ and b_x ----
+            // ---- [7..9] W~ and b_x ----
             if (lane < 27) {
                 double s = 0.0;
                 if (lane < 21) {
@@ -658,7 +680,7 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
             //   of a 44 x 44 Cholesky (30 % of the iteration), its assembly and its back substitution.  All sums are of
             //   one sign or short; measured componentwise backward error 4e-14 for d spanning 1e-16..1e16 (dense
             //   Cholesky: 8e-15), tools/ubench note in DESIGN.md section 5.3.  The oracle keeps the dense Cholesky.
-            double b2[2];
+            double bl0, bl1;   // G^-1 (T tbx - rl) and G^-1 1
             {
                 const bool lv = lane < M;
                 const int lc = lv ? lane : 0;
@@ -699,18 +721,18 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
                     y0 = fma(-pd[c6], e0, y0);
                     y1 = fma(-pd[c6], e1, y1);
                 }
-                b2[0] = y0;
-                b2[1] = y1;
+                bl0 = y0;
+                bl1 = y1;
             }
             TICK();   // 7
             TICK();   // 8
             TICK();   // 9
             if (!ok) break;
-            {
-                double s1 = sel(lane < M, b2[0], 0.0), s2 = sel(lane < M, b2[1], 0.0);
+            {   // ---- [10] dy_1 from 1'dlambd = -e_1, then dlambd, dy_x, du by back substitution ----
+                double s1 = sel(lane < M, bl0, 0.0), s2 = sel(lane < M, bl1, 0.0);
                 wave_sum2(s1, s2);
                 const double dy1 = (s1 + LDS(L::e + 6)) / s2;
-                const double dl = sel(lane < M, b2[0] - b2[1] * dy1, 0.0);
+                const double dl = sel(lane < M, bl0 - bl1 * dy1, 0.0);
                 LDS(LSINK(lane < M, L::dlam + lane)) = dl;
                 double tb[6], dyx[6];
                 {
@@ -735,36 +757,24 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
                     LDS(L::dy + 6) = dy1;
                 }
                 // du = L_u^-T (z - Y' dy_x)
-                double b1[1];
+                double bu;
                 {
                     const int a = lane < nv ? lane : 0;
                     double s = LDS(L::K + (nv + 6) * L::LDK + a);
 #pragma unroll
                     for (int r = 0; r < 6; r++) s = fma(-LDS(L::K + (nv + r) * L::LDK + a), dyx[r], s);
-                    b1[0] = sel(lane < nv, s, 0.0);
+                    bu = sel(lane < nv, s, 0.0);
                 }
-                l_backsub<1>(sm, L::K, L::LDK, L::ik, nv, lane, b1, L::IKS);
-                LDS(LSINK(lane < nv, L::du + lane)) = b1[0];
+                l_backsub<1>(sm, L::K, L::LDK, L::ik, nv, lane, &bu, L::IKS);
+                LDS(LSINK(lane < nv, L::du + lane)) = bu;
             }
             SYNC();
             TICK();   // 10
-            // ---- row steps ----
+            // ---- [11] row steps ----
             double rp_max = 0.0, rd_max = 0.0, Dphi = 0.0;
             LROWS(r, rv, lane, m) {
-                const bool isbox = r < x.r_st, isst = !isbox && r < x.r_lam;
-                const int rb = isbox ? r : 0;
-                const double db = LDS(L::du + 2 * (rb >> 2) + ((rb & 3) >> 1));
-                const double jbox = (rb & 1) ? -db : db;
-                const int rr = isst ? r - x.r_st : 0, k = rr / 3 + 1, q = rr - 3 * (k - 1), so = L::S + L::srow(k, q ? 1 : 0) * L::NU2;
-                double s0 = 0.0, s1 = 0.0;     // all inputs: S is zero for a >= 2k
-#pragma unroll 4
-                for (int a = 0; a < nv; a += 2) {
-                    s0 = fma(LDS(so + a), LDS(L::du + a), s0);
-                    s1 = fma(LDS(so + a + 1), LDS(L::du + a + 1), s1);
-                }
-                const double sx = s0 + s1, jst = q == 2 ? sx : -sx;
-                const double jlam = LDS(L::dlam + ((!isbox && !isst) ? r - x.r_lam : 0));
-                const double jd = sel(isbox, jbox, sel(isst, jst, jlam));
+                LROW_MAP(r, L::du, L::dlam, 0.0, (rb & 1) ? -bv : bv, q3 == 2 ? sx : -sx);
+                const double jd = rowv;
                 const double tt = LDS(L::t + r), nn = LDS(L::nu + r), ti = frcp(tt);
                 const double dtt = (LDS(L::c + r) - tt) + jd;
                 const double dn = (mu - tt * nn - nn * dtt) * ti;
@@ -793,7 +803,7 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
                 theta_max = 1e4 * fmax(1.0, theta);
             }
             TICK();   // 11
-            // ---- filter line search (all rows linear: c(v + al dv) = c + al J dv) ----
+            // ---- [12] filter line search (all rows linear: c(v + al dv) = c + al J dv) ----
             double al = a_p, fn = f, lt = logsum_t;
             int acc = 0, ftype = 0;
             for (int ls = 0; ls < IPM_MAX_BACKTRACK && al >= IPM_ALPHA_MIN; ls++) {   // alpha_min: see crx_ipm.h
@@ -801,10 +811,7 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
                 double thn = 0.0;
                 LogAcc la;
                 LROWS(r, rv, lane, m) {
-                    const double tt = LDS(L::t + r), jd = LDS(L::wv + r), rpr = LDS(L::c + r) - tt;
-                    const double cj = (rpr + tt) + al * jd;
-                    double tn = fma(al, rpr + jd, tt);
-                    tn = fmax(tn, cj);
+                    LTRIAL(r, al);
                     la.mul(sel(rv, tn, 1.0));
                     thn += sel(rv, fabs(cj - tn), 0.0);
                 }
@@ -835,13 +842,11 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
             }
             if (!acc) break;
             TICK();   // 12
-            // ---- accept ----
+            // ---- [13] accept ----
             logsum_t = lt;
             double numax = 0.0;
             LROWS(r, rv, lane, m) {
-                const double tt = LDS(L::t + r), jd = LDS(L::wv + r), rpr = LDS(L::c + r) - tt;
-                const double cj = (rpr + tt) + al * jd;
-                const double tn = fmax(fma(al, rpr + jd, tt), cj);
+                LTRIAL(r, al);
                 double nn = fma(a_d, LDS(L::dnu + r), LDS(L::nu + r));
                 const double mut = mu * frcp(tn);
                 nn = ipm_dual_safeguard(nn, mut);
@@ -878,30 +883,16 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
         // relaxed plan is reported CRX_STALLED: same plan, no claim about the pinned QP
         if (attempt == 1 && status == CRX_CONVERGED) status = proved ? CRX_INFEASIBLE : CRX_STALLED;
     }
-    // ---- write back: the plan by a roll-out of the model from x_0 (+ w in the second attempt) with the optimal inputs;
+    // ---- WRITE-BACK: the plan by a roll-out of the model from x_0 (+ w in the second attempt) with the optimal inputs;
     // A, B, C come back from HBM into the K region, the states go through the scratch TB ----
-    for (int i = lane; i < 36 * N; i += WAVE) LDS(L::A + i) = kp.A[(size_t)36 * N * pb + i];
-    for (int i = lane; i < 12 * N; i += WAVE) LDS(L::B + i) = kp.B[(size_t)12 * N * pb + i];
-    for (int i = lane; i < 6 * N; i += WAVE) LDS(L::C + i) = kp.C[(size_t)6 * N * pb + i];
+    LLOAD_MODEL();
     if (lane < 6) LDS(L::TB + lane) = LDS(L::xf + lane) + (x.nv > nu2 ? LDS(L::u + nu2 + lane) : 0.0);
     SYNC();
-    for (int k = 0; k < N; k++) {
-        if (lane < 6) {
-            double s = LDS(L::C + 6 * k + lane);
-            for (int c6 = 0; c6 < 6; c6++) s = fma(LDS(L::A + 36 * k + 6 * lane + c6), LDS(L::TB + 6 * k + c6), s);
-            s = fma(LDS(L::B + 12 * k + 2 * lane), LDS(L::u + 2 * k), s);
-            s = fma(LDS(L::B + 12 * k + 2 * lane + 1), LDS(L::u + 2 * k + 1), s);
-            LDS(L::TB + 6 * (k + 1) + lane) = s;
-        }
-        SYNC();
-    }
+    LROLLOUT(L::TB, true)
     for (int i = lane; i < 6 * (N + 1); i += WAVE) kp.X[(size_t)6 * (N + 1) * pb + i] = LDS(L::TB + i);
     if (lane < nu2) kp.U[(size_t)nu2 * pb + lane] = LDS(L::u + lane);
     if (lane < Mx) kp.lambda[(size_t)Mx * pb + lane] = lane < M ? LDS(L::lam + lane) : 0.0;
     if (lane == 0) {
-        double ql = 0.0;
-        for (int j = 0; j < M; j++) ql = fma(LDS(L::qf + j), LDS(L::lam + j), ql);
-        (void)ql;
         kp.cost[pb] = f;
         kp.status[pb] = status;
         kp.kkt[pb] = E0;
@@ -909,62 +900,70 @@ __global__ void __launch_bounds__(WAVE) crx_lmpc_kernel(const crx_lmpc_kparams k
     }
 }
 
-template <int NMAX, bool DENSE, int MSS = CRX_MAX_SS, int NFIX = 0>
+// WHICH instantiation serves (N, n_ss_max, dense) is decided in ONE place, select_lmpc: it calls f with the instantiation as a type, LInst<..>
+// (the form of crx_kernels.hip's Inst / select_*).  Launching, the occupancy query and the LDS figure are callables over that one selection.
+template <int NMAX, bool DENSE, int MSS, int NFIX> struct LInst {
+    using L = LL<NMAX, DENSE, MSS>;
+    static constexpr bool static_lds = LmpcStaticLds<NFIX>::v;
+    static constexpr auto kernel = crx_lmpc_kernel<NMAX, DENSE, MSS, NFIX>;
+};
+template <class F>
+static void select_lmpc(int N, int n_ss_max, bool dense, F&& f) {
+    // a tracking cost (Q != 0) stores Hu: one dense instantiation per horizon class
+    if (dense) return N <= 12 ? f(LInst<12, true, CRX_MAX_SS, 0>{}) : f(LInst<CRX_LMPC_MAX_N, true, CRX_MAX_SS, 0>{});
+    // the reference's configuration (N = 12, Q = 0, 44 safe-set points: utils/base.py:350-376) has its own instantiation: six per CU
+    if (N == 12 && n_ss_max <= CRX_LMPC_SS44) return f(LInst<12, false, CRX_LMPC_SS44, 12>{});
+    if (N <= 12 && n_ss_max <= CRX_LMPC_SS44) return f(LInst<12, false, CRX_LMPC_SS44, 0>{});
+    return N <= 12 ? f(LInst<12, false, CRX_MAX_SS, 0>{}) : f(LInst<CRX_LMPC_MAX_N, false, CRX_MAX_SS, 0>{});
+}
+
+template <class I>
 static hipError_t launch_l(const crx_lmpc_kparams& kp, hipStream_t st) {
-    if constexpr (LmpcStaticLds<NFIX>::v) {
-        hipLaunchKernelGGL((crx_lmpc_kernel<NMAX, DENSE, MSS, NFIX>), dim3(kp.batch), dim3(WAVE), 0, st, kp);   // the layout is a static array of the kernel
+    if constexpr (I::static_lds) {
+        hipLaunchKernelGGL(I::kernel, dim3(kp.batch), dim3(WAVE), 0, st, kp);   // the layout is a static array of the kernel
         return hipGetLastError();
     }
-    const size_t bytes = LL<NMAX, DENSE, MSS>::bytes(kp.n_ss_max);
+    const size_t bytes = I::L::bytes(kp.n_ss_max);
     // the opt-in to > 64 KiB of dynamic LDS is a property of the (function, device) pair: set once per device
     static int attr_set_on = -1;
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) return hipErrorInvalidDevice;
     if (attr_set_on != dev) {
-        hipError_t e = hipFuncSetAttribute((const void*)crx_lmpc_kernel<NMAX, DENSE, MSS, NFIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        hipError_t e = hipFuncSetAttribute((const void*)I::kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) return e;
         attr_set_on = dev;
     }
-    hipLaunchKernelGGL((crx_lmpc_kernel<NMAX, DENSE, MSS, NFIX>), dim3(kp.batch), dim3(WAVE), bytes, st, kp);
+    hipLaunchKernelGGL(I::kernel, dim3(kp.batch), dim3(WAVE), bytes, st, kp);
     return hipGetLastError();
 }
-
-// Q == 0 (no tracking cost: the reference's LMPCRacingParam default): the instantiation that does not store Hu
-static bool lmpc_dense(const crx_lmpc_kparams& kp) {
-    for (int c = 0; c < 6; c++)
-        if (kp.Q[c] != 0.0) return true;
-    return false;
+template <class I>
+static int occ_l(int n_ss_max) {
+    int n = 0;
+    const size_t bytes = I::static_lds ? 0 : I::L::bytes(n_ss_max);   // static LDS: the runtime counts it by itself
+    if (!I::static_lds && hipFuncSetAttribute((const void*)I::kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return -1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, I::kernel, WAVE, bytes) != hipSuccess) return -1;
+    return n;
 }
 
 hipError_t crx_launch_lmpc(const crx_lmpc_kparams& kp, hipStream_t st) {
     if (kp.batch == 0) return hipSuccess;
-    if (lmpc_dense(kp)) return kp.N <= 12 ? launch_l<12, true>(kp, st) : launch_l<CRX_LMPC_MAX_N, true>(kp, st);
-    // the reference's configuration (N = 12, Q = 0, 44 safe-set points: utils/base.py:350-376) has its own instantiation: six per CU
-    if (kp.N == 12 && kp.n_ss_max <= CRX_LMPC_SS44) return launch_l<12, false, CRX_LMPC_SS44, 12>(kp, st);
-    if (kp.N <= 12 && kp.n_ss_max <= CRX_LMPC_SS44) return launch_l<12, false, CRX_LMPC_SS44>(kp, st);
-    return kp.N <= 12 ? launch_l<12, false>(kp, st) : launch_l<CRX_LMPC_MAX_N, false>(kp, st);
+    bool dense = false;   // Q == 0 (no tracking cost: the reference's LMPCRacingParam default): the instantiation that does not store Hu
+    for (int c = 0; c < 6; c++) dense = dense || kp.Q[c] != 0.0;
+    hipError_t e = hipSuccess;
+    select_lmpc(kp.N, kp.n_ss_max, dense, [&](auto i) { e = launch_l<decltype(i)>(kp, st); });
+    return e;
 }
-
-template <int NMAX, bool DENSE, int MSS = CRX_MAX_SS, int NFIX = 0>
-static int occ_l(int n_ss_max) {
-    int n = 0;
-    const size_t bytes = LmpcStaticLds<NFIX>::v ? 0 : LL<NMAX, DENSE, MSS>::bytes(n_ss_max);   // static LDS: the runtime counts it by itself
-    if (!LmpcStaticLds<NFIX>::v &&
-        hipFuncSetAttribute((const void*)crx_lmpc_kernel<NMAX, DENSE, MSS, NFIX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) return -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, crx_lmpc_kernel<NMAX, DENSE, MSS, NFIX>, WAVE, bytes) != hipSuccess) return -1;
+// (diagnostics: the Q == 0 instantiation the launcher would pick for (N, n_ss_max) -- the reference's parameters select it; fixed-horizon
+// instantiation included: the occupancy of the kernel that is timed)
+int crx_lmpc_resident_per_cu(int N, int n_ss_max) {
+    int n = -1;
+    select_lmpc(N, n_ss_max, false, [&](auto i) { n = occ_l<decltype(i)>(n_ss_max); });
     return n;
 }
-// (diagnostics: the Q == 0 instantiation the launcher would pick for (N, n_ss_max) -- the reference's parameters select it; the
-// same selection as crx_launch_lmpc, fixed-horizon instantiation included: the occupancy of the kernel that is timed)
-int crx_lmpc_resident_per_cu(int N, int n_ss_max) {
-    if (N == 12 && n_ss_max <= CRX_LMPC_SS44) return occ_l<12, false, CRX_LMPC_SS44, 12>(n_ss_max);
-    if (N <= 12 && n_ss_max <= CRX_LMPC_SS44) return occ_l<12, false, CRX_LMPC_SS44>(n_ss_max);
-    return N <= 12 ? occ_l<12, false>(n_ss_max) : occ_l<CRX_LMPC_MAX_N, false>(n_ss_max);
-}
-
 size_t crx_lmpc_lds_bytes(int N, int n_ss_max) {
-    if (N <= 12 && n_ss_max <= CRX_LMPC_SS44) return LL<12, false, CRX_LMPC_SS44>::bytes(n_ss_max);
-    return N <= 12 ? LL<12, false>::bytes(n_ss_max) : LL<CRX_LMPC_MAX_N, false>::bytes(n_ss_max);
+    size_t bytes = 0;
+    select_lmpc(N, n_ss_max, false, [&](auto i) { bytes = decltype(i)::L::bytes(n_ss_max); });
+    return bytes;
 }
 static_assert(LL<12, false, CRX_LMPC_SS44>::bytes(CRX_LMPC_SS44) <= 27264, "six learning-MPC QPs per CU");
 static_assert(LL<CRX_LMPC_MAX_N, true>::bytes(CRX_MAX_SS) <= 160 * 1024, "LDS budget");

@@ -242,6 +242,58 @@ def field_desc(N, n_cars, n_seg, lap_length, dt=0.1, safety_time=2.0, degree=6, 
     return FieldDesc(int(N), int(n_cars), int(n_seg), int(degree), float(lap_length), float(dt), float(safety_time), float(l_sum), float(w_sum))
 
 
+class StatsDesc(C.Structure):
+    _fields_ = [("n_opp_max", C.c_int32), ("n_cars", C.c_int32), ("degree", C.c_int32), ("pad", C.c_int32), ("lap_length", C.c_double),
+                ("track_width", C.c_double), ("l_sum", C.c_double), ("w_sum", C.c_double)]
+
+
+def stats_desc(n_opp_max, n_cars, lap_length, track_width, degree=6, l_sum=0.4, w_sum=0.2):
+    """crx_stats_desc_default.  n_cars = 0: scripted opponents, n_opp_max of them per car; n_cars = C >= 1: field mode, n_opp_max >= C - 1."""
+    return StatsDesc(int(n_opp_max), int(n_cars), int(degree), 0, float(lap_length), float(track_width), float(l_sum), float(w_sum))
+
+
+# include/crx.h "Race statistics": the rows of stat_i [STATS_NI, batch] int32 and stat_d [STATS_ND + n_opp_max, batch] float64 ...
+CRX_STATS_MAX_LAPS, CRX_STATS_MAX_OPP = 8, 32
+STATS_I = dict(n_samples=0, nonfinite_step=1, off_step=2, off_samples=3, contact_step=4, contact_samples=5, n_laps=6, laps_prev=7,
+               lap_step=8, passes=16, passed=17, flag_samples=18)          # lap_step: CRX_STATS_MAX_LAPS rows
+STATS_NI = 19
+STATS_D = dict(min_clear=0, ey_max=1, sum_ey2=2, sum_dv2=3, ds_prev=4)     # ds_prev: n_opp_max rows
+STATS_ND = 4
+# ... and of the summary record sum_i [n_groups, STATS_SUM_NI] int64, sum_d [n_groups, STATS_SUM_ND] float64
+STATS_SUM_I = dict(cars=0, nonfinite=1, off=2, contact=3, clean=4, laps_hist=5, passes=14, passed=15, flag_samples=16, n_samples=17,
+                   lap1_sum=18, lap1_min=19, lap1_max=20, lap1_count=21, lap2_sum=22, lap2_min=23, lap2_max=24, lap2_count=25)   # laps_hist: 9 bins
+STATS_SUM_NI = 26
+STATS_SUM_D = dict(min_clear=0, ey_max=1)
+STATS_SUM_ND = 2
+
+_PV, _PD = C.c_void_p, C.POINTER(StatsDesc)
+STATS_ARGTYPES = {
+    "stats_desc_default": [_PD, C.c_int, C.c_int, C.c_double, C.c_double],
+    "race_stats_reset_dev": [_PD, C.c_int, _PV, _PV, _PV, _PV],
+    "race_stats_dev": [_PD, C.c_int, C.c_int, C.c_double] + [_PV] * 12,
+    "race_stats_summary_dev": [_PD, C.c_int, _PV, C.c_int, _PV, _PV, _PV, _PV, _PV],
+    "race_stats_reset": [_PD, C.c_int, _PV, _PV, _PV],
+    "race_stats": [_PD, C.c_int, C.c_int, C.c_double] + [_PV] * 11,
+    "race_stats_summary": [_PD, C.c_int, _PV, C.c_int, _PV, _PV, _PV, _PV],
+}
+
+
+def bind_stats(lib, prefix="crx_"):
+    """argtypes / restype of the race-statistics family on a loaded library (the clock t travels as a double by value)."""
+    for name, argtypes in STATS_ARGTYPES.items():
+        fn = getattr(lib, prefix + name)
+        fn.argtypes = argtypes
+        fn.restype = None if name == "stats_desc_default" else C.c_int
+
+
+def stats_summary_record(sum_i, sum_d):
+    """The summary arrays of one group as a dict by field name (laps_hist: the 9 bins)."""
+    rec = {k: int(sum_i[i]) for k, i in STATS_SUM_I.items() if k != "laps_hist"}
+    rec["laps_hist"] = [int(v) for v in sum_i[STATS_SUM_I["laps_hist"]:STATS_SUM_I["laps_hist"] + CRX_STATS_MAX_LAPS + 1]]
+    rec.update({k: float(sum_d[i]) for k, i in STATS_SUM_D.items()})
+    return rec
+
+
 class SelectDesc(C.Structure):
     _fields_ = [
         ("N", C.c_int32),
@@ -424,7 +476,42 @@ class Binding:
                      "planner_plan_models", "path_prep", "path_plan", "plant_step_params", "field_prep"):
             if hasattr(lib, prefix + name):
                 getattr(lib, prefix + name).restype = C.c_int
+        if hasattr(lib, prefix + "race_stats_dev"):
+            bind_stats(lib, prefix)
         self._check = None
+
+    def race_stats_reset(self, desc, laps):
+        """crx_race_stats_reset: (stat_i [STATS_NI, Bn] int32, stat_d [STATS_ND + n_opp_max, Bn] float64) at their reset values."""
+        laps = np.ascontiguousarray(laps, dtype=_I)
+        Bn = laps.shape[0]
+        stat_i, stat_d = np.zeros((STATS_NI, Bn), dtype=_I), np.zeros((STATS_ND + desc.n_opp_max, Bn))
+        self._call("race_stats_reset", C.byref(desc), Bn, _p(laps), _p(stat_i), _p(stat_d))
+        return stat_i, stat_d
+
+    def race_stats(self, desc, sample, t, xcurv, laps, stat_i, stat_d, car_s0=None, car_v=None, car_ey=None, n_opp=None, car_dims=None,
+                   xt=None, flag=None):
+        """crx_race_stats (include/crx.h S1-S4): one sample of every car; stat_i, stat_d (C-contiguous, as race_stats_reset returns
+        them) are updated in place.  Optional arrays are passed as they are given -- the library refuses the combinations it does not take."""
+        xcurv = np.ascontiguousarray(xcurv, dtype=_D).reshape(-1, 6)
+        Bn, V = xcurv.shape[0], desc.n_opp_max
+        opt = lambda a, dtype, shape: None if a is None else _p(_in(a, dtype, shape))   # noqa: E731
+        if stat_i.dtype != _I or stat_d.dtype != _D or not stat_i.flags.c_contiguous or not stat_d.flags.c_contiguous \
+                or stat_i.shape != (STATS_NI, Bn) or stat_d.shape != (STATS_ND + V, Bn):
+            raise ValueError("stat_i, stat_d: expected C-contiguous int32 %s and float64 %s" % ((STATS_NI, Bn), (STATS_ND + V, Bn)))
+        self._call("race_stats", C.byref(desc), Bn, int(sample), float(t), _p(xcurv), _p(_in(laps, _I, (Bn,))), opt(car_s0, _D, (Bn, V)),
+                   opt(car_v, _D, (Bn, V)), opt(car_ey, _D, (Bn, V)), opt(n_opp, _I, (Bn,)),
+                   None if car_dims is None else _p(_in(np.asarray(car_dims, dtype=_D).reshape(-1, 2), _D, (Bn, 2))), opt(xt, _D, (Bn, 6)),
+                   opt(flag, _I, (Bn,)), _p(stat_i), _p(stat_d))
+        return stat_i, stat_d
+
+    def race_stats_summary(self, desc, stat_i, stat_d, group=None, n_groups=1):
+        """crx_race_stats_summary: (sum_i [G, STATS_SUM_NI] int64, sum_d [G, STATS_SUM_ND] float64), G = n_groups with a group array, else 1."""
+        Bn = stat_i.shape[1]
+        G = max(int(n_groups), 1) if group is not None else 1
+        sum_i, sum_d = np.zeros((G, STATS_SUM_NI), dtype=np.int64), np.zeros((G, STATS_SUM_ND))
+        self._call("race_stats_summary", C.byref(desc), Bn, None if group is None else _p(_in(group, _I, (Bn,))), int(n_groups),
+                   _p(np.ascontiguousarray(stat_i, dtype=_I)), _p(np.ascontiguousarray(stat_d, dtype=_D)), _p(sum_i), _p(sum_d))
+        return sum_i, sum_d
 
     def _call(self, name, *args):
         rc = getattr(self.lib, self.prefix + name)(*args)

@@ -13,6 +13,9 @@ The reference runs such sweeps one race at a time (car_racing/tests/overtake_pla
 Every loop steps its plant through _Plant._advance, the learning-MPC step is LmpcLaps._plan / _apply (GameLaps drives its
 `lm` through them), and the run-to-the-end functions share _run_and_log.  The launch sequence of each step() is stated in its
 docstring and pinned by tests/test_montecarlo_sequence_cpu.py.
+
+What the loops are run for -- contacts, cars off the track, lap times, overtakes -- is RaceStats (end of this module): per-car
+statistics on the device, one launch per sample, attached to any loop through the loop's stats_inputs().
 """
 import numpy as np
 import torch
@@ -219,6 +222,15 @@ class _Plant:
         self.xg, self.xg_next = self.xg_next, self.xg
         self.xc, self.xc_next = self.xc_next, self.xc
 
+    def stats_inputs(self, **more):
+        """What RaceStats samples, read at call time (xc and xc_next exchange bindings every step): the cars' states and lap counters,
+        the clock of the scripted cars, the track, the speed targets; the loops add their opponents (scripted: car_s0, car_v, car_ey
+        [B,V]; a field: n_cars, car_dims), a flag [B] int32 and the half-sums of their cars' dimensions where they have them."""
+        inp = dict(xcurv=self.xc, laps=self.laps, t=getattr(self, "t", 0.0), lap_length=self.lap_length,
+                   track_width=getattr(self, "track_width", None), xt=getattr(self, "xt", None))
+        inp.update(more)
+        return inp
+
 
 def _run_and_log(step, steps, log_every, getters, before=()):
     """`steps` calls of step(); at every log_every-th one, a clone of what each getter (name -> callable returning a device tensor)
@@ -250,7 +262,7 @@ class MpccbfRaces(_Plant):
         Bn, V = self.s0.shape
         if V > abi.CRX_MAX_OBS:
             raise ValueError("at most %d scripted cars" % abi.CRX_MAX_OBS)
-        self.N, self.V = N, V
+        self.N, self.V, self.track_width = N, V, track_width
         self.desc = abi.cbf_desc(N, V, A, B, alpha=alpha, margin=0.2, ey_max=track_width)
         self.xt = torch.tensor([vt, 0, 0, 0, 0, eyt], **f64).repeat(Bn, 1).contiguous()
         self.ws = torch_api.CbfWorkspace(self.desc, Bn, dev)
@@ -277,6 +289,9 @@ class MpccbfRaces(_Plant):
         self._advance(self.ws.U, 2 * N)   # the plant reads u_0 of every race straight out of the solver's U [B][N][2]
         self.u = self.ws.U[:, 0, :]
         self.t += self.timestep
+
+    def stats_inputs(self):
+        return super().stats_inputs(car_s0=self.s0, car_v=self.v, car_ey=self.ey)
 
     def step_glue(self):
         """The same control step with the prediction / window filter / packing / lap wrap written as element-wise
@@ -338,7 +353,7 @@ class FieldRaces(_Plant):
             raise ValueError("xcurv0, xglob0: %d and %d cars do not make races of %d" % (x0.shape[0], g0.shape[0], Cn))
         dev = self._plant_init(track_table, lap_length, timestep, x0, g0, noise_seed, device, plant_params)
         Bn, R = self.batch, self.batch // Cn
-        self.N, self.n_races, self.n_cars = N, R, Cn
+        self.N, self.n_races, self.n_cars, self.track_width = N, R, Cn, track_width
         self.desc = abi.cbf_desc(N, Cn - 1, A, B, alpha=alpha, margin=0.2, ey_max=track_width)
         self.fdesc = abi.field_desc(N, Cn, self.tab.shape[0], lap_length, dt=timestep)
         # vt, eyt: scalars or one value per car [R,C] -- different target speeds are what makes the cars meet
@@ -365,6 +380,9 @@ class FieldRaces(_Plant):
         self._advance(self.ws.U, 2 * self.N)
         self.u = self.ws.U[:, 0, :]
         torch.minimum(self.min_clear, f.clear, out=self.min_clear)
+
+    def stats_inputs(self):
+        return super().stats_inputs(n_cars=self.n_cars, car_dims=self.car_dims, l_sum=self.fdesc.l_sum, w_sum=self.fdesc.w_sum)
 
 
 def field_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, n_cars, steps, vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1,
@@ -411,6 +429,9 @@ class IlqrRaces(_Plant):
         obs_e = (self.ey + 0.0 * tt[None, :])[:, None, :].contiguous()
         lap_off = ((_LAP_TRUNC(self.xc[:, 4:5] / L) - _LAP_TRUNC(obs_s[:, :, 0] / L)) * L).contiguous()
         return obs_s, obs_e, lap_off
+
+    def stats_inputs(self):
+        return super().stats_inputs(car_s0=self.s0, car_v=self.v, car_ey=self.ey, l_sum=self.desc.l_sum, w_sum=self.desc.w_sum)
 
     def step(self):
         """One control step of every race: predictions (torch ops), then ilqr_solve_dev, plant_step_wrap_dev."""
@@ -461,7 +482,7 @@ class LmpcLaps(_Plant):
         self.ss, self.us, self.qf = (_dev(a, dev, clone=True) for a in (ss_xcurv, u_ss, qfun))
         self.time_ss, self.it = (_dev(a, dev, torch.int32, clone=True) for a in (time_ss, it))
         Bn, L, P, _ = self.ss.shape
-        self.N = N
+        self.N, self.track_width = N, track_width
         self.lin_points, self.lin_input = _dev(lin_points, dev, clone=True), _dev(lin_input, dev, clone=True)
         self.pdesc = abi.lmpcprep_desc(N, P, L, self.tab.shape[0], timestep, lap_length)   # the prep's descriptor; the plant's is self.plant
         self.desc = abi.lmpc_desc(N=N, n_ss_max=self.pdesc.n_ss_per_lap * self.pdesc.n_ss_laps, ey_max=track_width)
@@ -611,6 +632,7 @@ class GameLaps:
         VA = self.s0.shape[1]
         V = min(VA, abi.CRX_MAX_VEH)
         self.Np, self.V, self.VA, self.L = N_plan, V, VA, lap_length
+        self.track_width = track_width
         if models is not None and A is None and B is None:   # (the descriptors' own model is not read then)
             A, B = np.zeros((6, 6)), np.zeros((6, 2))
         self.scene = abi.scene_desc(N_plan, VA, V, lap_length)
@@ -679,6 +701,11 @@ class GameLaps:
         lm._apply(self.u, 2, lm.addpoint_step)
         self.t += lm.timestep
         lm.log_and_handover(self.u)
+
+    def stats_inputs(self):
+        """As _Plant.stats_inputs, answered from `lm` (which holds the plant): the scripted cars at the game's clock, and the branch
+        mask of the last step as the flag (RaceStats counts the samples a race spent in the overtake branch)."""
+        return self.lm.stats_inputs(t=self.t, car_s0=self.s0, car_v=self.v, car_ey=self.ey, flag=self.m_ot)
 
     def set_branch_streams(self, s_ot, s_lm):
         """The two streams the branches of a step run on (crx.montecarlo.Concurrent hands out streams it measured to overlap)."""
@@ -864,3 +891,64 @@ def lqr_laps(track_table, lap_length, xcurv0, xglob0, steps, A, B, Q=np.diag([10
     logs = _run_and_log(r.step, steps, log_every, dict(xcurv=lambda: r.xc, u=lambda: r.u))
     return dict(logs, K=r.K.cpu().numpy(),
                 design_status=r.design.status.cpu().numpy(), design_iters=r.design.iters.cpu().numpy(), laps=r.laps.cpu().numpy())
+
+
+class RaceStats:
+    """Per-car race statistics of a closed loop, on the device (include/crx.h "Race statistics"): contacts, cars that left the track,
+    lap times, overtakes made and suffered, samples under a flag, min clearance, max |ey| and the sums behind the RMS figures.
+    Attaches to every loop of this module through its stats_inputs(); nothing here runs unless asked, and a loop without a RaceStats
+    launches exactly what it launched before.
+
+        st = RaceStats(loop)      # one reset launch
+        st.update()               # sample 0: the initial states
+        for k in range(steps):
+            st.step()             # loop.step(), then ONE race_stats_dev: sample k + 1, the states after the step
+        st.summary(), st.per_car()
+
+    A sample shows the kernel the loop as it is at that moment: the states after the step against the scripted cars at the clock
+    after the step (or the other cars of the race, same snapshot).  group [B] int32 in [0, n_groups) splits the summary.  All launches
+    go to the current stream: construct and step a sub-batch's RaceStats under the stream the sub-batch runs on.  track_width
+    overrides the loop's (the loops without a track width -- IlqrRaces, PidLaps, LqrLaps -- never count a car as off track without it).
+    first_sample = 1: for a caller that takes no sample of the initial states, so that the sample after step k is still k + 1."""
+
+    def __init__(self, loop, group=None, n_groups=1, track_width=None, first_sample=0):
+        self.loop = loop
+        inp = loop.stats_inputs()
+        xc = inp["xcurv"]
+        Bn, dev = xc.shape[0], xc.device
+        n_cars = int(inp.get("n_cars") or 0)
+        V = n_cars - 1 if n_cars else (inp["car_s0"].shape[1] if inp.get("car_s0") is not None else 0)
+        if track_width is None:
+            track_width = inp.get("track_width")
+        self.desc = abi.stats_desc(V, n_cars, inp["lap_length"], float("inf") if track_width is None else track_width,
+                                   l_sum=inp.get("l_sum") or 0.4, w_sum=inp.get("w_sum") or 0.2)
+        self.ws = torch_api.RaceStatsWorkspace(self.desc, Bn, dev)
+        self.group, self.n_groups = None, int(n_groups)
+        if group is not None:
+            self.group = group.to(dtype=torch.int32, device=dev).contiguous() if torch.is_tensor(group) else _dev(group, dev, torch.int32)
+        self.n_updates = int(first_sample)
+        torch_api.race_stats_reset_dev(self.desc, inp["laps"], self.ws)
+
+    def update(self):
+        """ONE race_stats_dev on the current stream; the sample index is the number of updates so far."""
+        inp = self.loop.stats_inputs()
+        torch_api.race_stats_dev(self.desc, self.n_updates, inp["t"], inp["xcurv"], inp["laps"], self.ws, car_s0=inp.get("car_s0"),
+                                 car_v=inp.get("car_v"), car_ey=inp.get("car_ey"), n_opp=inp.get("n_opp"), car_dims=inp.get("car_dims"),
+                                 xt=inp.get("xt"), flag=inp.get("flag"))
+        self.n_updates += 1
+
+    def step(self):
+        self.loop.step()
+        self.update()
+
+    def summary(self):
+        """The host record(s) by field name (abi.STATS_SUM_I, abi.STATS_SUM_D; laps_hist: 9 bins): a dict, or with a group array a list
+        of n_groups dicts.  Synchronises."""
+        sum_i, sum_d = torch_api.race_stats_summary_dev(self.desc, self.ws, self.group, self.n_groups)
+        sum_i, sum_d = sum_i.cpu().numpy(), sum_d.cpu().numpy()
+        recs = [abi.stats_summary_record(sum_i[g], sum_d[g]) for g in range(sum_i.shape[0])]
+        return recs if self.group is not None else recs[0]
+
+    def per_car(self):
+        """Host arrays by field name: [B] each, lap_step [8,B], ds_prev [n_opp_max,B].  Synchronises."""
+        return {name: v.cpu().numpy() for name, v in self.ws.fields().items()}

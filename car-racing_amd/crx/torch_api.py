@@ -7,7 +7,7 @@ import ctypes as C
 
 import torch
 
-from . import _state, binding, lib
+from . import _state, abi, binding, lib
 
 
 def _ptr(t):
@@ -559,6 +559,79 @@ def field_prep_dev(desc, track, xcurv, ws, car_dims=None):
     _call("crx_field_prep_dev", C.byref(desc), C.c_int(R), _ptr(track), _ptr(xcurv), _ptr(car_dims), _ptr(ws.pred_s), _ptr(ws.pred_ey),
           _ptr(ws.obs_s), _ptr(ws.obs_ey), _ptr(ws.lap_off), _ptr(ws.n_obs), _ptr(ws.obs_dims), _ptr(ws.clear), _stream())
     return ws
+
+
+class RaceStatsWorkspace:
+    """State of race_stats_dev for `batch` cars (include/crx.h "Race statistics"): stat_i [STATS_NI, batch] int32 and stat_d
+    [STATS_ND + n_opp_max, batch] float64, field-major, and every field as a named view of them: n_samples, nonfinite_step, off_step,
+    off_samples, contact_step, contact_samples, n_laps, laps_prev, passes, passed, flag_samples [batch]; lap_step [8, batch];
+    min_clear, ey_max, sum_ey2, sum_dv2 [batch]; ds_prev [n_opp_max, batch].  sum_i / sum_d: the records of the last summary."""
+
+    def __init__(self, desc, batch, device):
+        self.batch = batch
+        self.stat_i = torch.zeros((abi.STATS_NI, batch), dtype=torch.int32, device=device)
+        self.stat_d = torch.zeros((abi.STATS_ND + desc.n_opp_max, batch), dtype=torch.float64, device=device)
+        for name, row in abi.STATS_I.items():
+            setattr(self, name, self.stat_i[row:row + abi.CRX_STATS_MAX_LAPS] if name == "lap_step" else self.stat_i[row])
+        for name, row in abi.STATS_D.items():
+            setattr(self, name, self.stat_d[row:] if name == "ds_prev" else self.stat_d[row])
+        self.sum_i = self.sum_d = None
+
+    def fields(self):
+        """name -> view, every field."""
+        return {name: getattr(self, name) for name in list(abi.STATS_I) + list(abi.STATS_D)}
+
+
+def _stats_ws(desc, ws, laps):
+    Bn = ws.batch
+    _chk(ws.stat_i, torch.int32, (abi.STATS_NI, Bn), "ws.stat_i")
+    _chk(ws.stat_d, torch.float64, (abi.STATS_ND + desc.n_opp_max, Bn), "ws.stat_d")
+    if laps is not None:
+        _chk(laps, torch.int32, (Bn,), "laps")
+    return Bn
+
+
+def race_stats_reset_dev(desc, laps, ws):
+    """crx_race_stats_reset_dev: every field of ws at its reset value, laps_prev = laps [batch] int32."""
+    Bn = _stats_ws(desc, ws, laps)
+    _call("crx_race_stats_reset_dev", C.byref(desc), Bn, _ptr(laps), _ptr(ws.stat_i), _ptr(ws.stat_d), _stream())
+    return ws
+
+
+def race_stats_dev(desc, sample, t, xcurv, laps, ws, car_s0=None, car_v=None, car_ey=None, n_opp=None, car_dims=None, xt=None, flag=None):
+    """crx_race_stats_dev (include/crx.h S1-S4): one sample of every car, ONE launch.  xcurv [batch,6], laps [batch] int32; scripted mode
+    (desc.n_cars == 0): car_s0, car_v, car_ey [batch, n_opp_max] at the clock t, n_opp [batch] int32 optional; field mode: car_dims
+    [batch / n_cars, n_cars, 2] optional; xt [batch,6] and flag [batch] int32 optional.  Updates ws in place and returns it."""
+    Bn, V = _stats_ws(desc, ws, laps), desc.n_opp_max
+    _chk(xcurv, torch.float64, (Bn, 6), "xcurv")
+    for name, a in (("car_s0", car_s0), ("car_v", car_v), ("car_ey", car_ey)):
+        if a is not None:
+            _chk(a, torch.float64, (Bn, V), name)
+    for name, a in (("n_opp", n_opp), ("flag", flag)):
+        if a is not None:
+            _chk(a, torch.int32, (Bn,), name)
+    if car_dims is not None:
+        _chk(car_dims, torch.float64, (Bn // max(desc.n_cars, 1), max(desc.n_cars, 1), 2), "car_dims")
+    if xt is not None:
+        _chk(xt, torch.float64, (Bn, 6), "xt")
+    _call("crx_race_stats_dev", C.byref(desc), Bn, int(sample), float(t), _ptr(xcurv), _ptr(laps), _ptr(car_s0), _ptr(car_v), _ptr(car_ey),
+          _ptr(n_opp), _ptr(car_dims), _ptr(xt), _ptr(flag), _ptr(ws.stat_i), _ptr(ws.stat_d), _stream())
+    return ws
+
+
+def race_stats_summary_dev(desc, ws, group=None, n_groups=1):
+    """crx_race_stats_summary_dev: the cars of ws reduced to one record per group (group [batch] int32 in [0, n_groups); None: one group).
+    Writes ws.sum_i [G, STATS_SUM_NI] int64 and ws.sum_d [G, STATS_SUM_ND] float64 (abi.stats_summary_record names a row) and returns them."""
+    Bn = _stats_ws(desc, ws, None)
+    G = int(n_groups) if group is not None else 1
+    if group is not None:
+        _chk(group, torch.int32, (Bn,), "group")
+    if ws.sum_i is None or ws.sum_i.shape[0] != max(G, 1):
+        ws.sum_i = torch.zeros((max(G, 1), abi.STATS_SUM_NI), dtype=torch.int64, device=ws.stat_i.device)
+        ws.sum_d = torch.zeros((max(G, 1), abi.STATS_SUM_ND), dtype=torch.float64, device=ws.stat_i.device)
+    _call("crx_race_stats_summary_dev", C.byref(desc), Bn, _ptr(group), G, _ptr(ws.stat_i), _ptr(ws.stat_d), _ptr(ws.sum_i), _ptr(ws.sum_d),
+          _stream())
+    return ws.sum_i, ws.sum_d
 
 
 def plant_step_wrap_dev(desc, track, xglob, xcurv, u, u_stride, xglob_next, xcurv_next, laps, noise_z=None, params=None):

@@ -1935,6 +1935,135 @@ int crx_game_log_dev(int batch, int n_points, double lap_length, const double* x
 
 }  // extern "C"
 
+// ---- race statistics: per-car outcomes of every closed loop (crx_race_stats_*_kernel, crx_game.hip) -------------------------------
+extern "C" void crx_stats_desc_default(crx_stats_desc* d, int n_opp_max, int n_cars, double lap_length, double track_width) {
+    memset(d, 0, sizeof(*d));
+    d->n_opp_max = n_opp_max; d->n_cars = n_cars; d->degree = 6;
+    d->lap_length = lap_length; d->track_width = track_width; d->l_sum = 0.4; d->w_sum = 0.2;
+}
+
+// The family's one argument check: arguments alone, before the library's state is looked at.  `which`: 0 reset, 1 one sample, 2 summary;
+// a call passes the arrays it has and NULL for the rest.
+static int check_stats(crx_stats_kparams& sp, int which, const crx_stats_desc* d, int batch, arr stat_i, arr stat_d, arr laps = nullptr,
+                       arr xcurv = nullptr, arr car_s0 = nullptr, arr car_v = nullptr, arr car_ey = nullptr, arr n_opp = nullptr,
+                       arr car_dims = nullptr, arr group = nullptr, int n_groups = 1, arr sum_i = nullptr, arr sum_d = nullptr) {
+    auto positive = [](double v) { return v > 0.0 && isfinite(v); };
+    if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
+    if (d->n_opp_max < 0 || d->n_opp_max > CRX_STATS_MAX_OPP) return fail(CRX_ERR_ARG, "n_opp_max=%d outside [0,%d]", d->n_opp_max, CRX_STATS_MAX_OPP);
+    if (d->n_cars < 0 || d->n_cars > CRX_MAX_OBS + 1) return fail(CRX_ERR_ARG, "n_cars=%d outside [0,%d]", d->n_cars, CRX_MAX_OBS + 1);
+    if (d->n_cars > 0 && d->n_opp_max < d->n_cars - 1) return fail(CRX_ERR_ARG, "field mode: n_opp_max=%d < n_cars - 1 = %d", d->n_opp_max, d->n_cars - 1);
+    if (d->degree < 2 || d->degree > 8 || (d->degree & 1)) return fail(CRX_ERR_ARG, "degree must be 2, 4, 6 or 8");
+    if (!positive(d->lap_length) || !positive(d->l_sum) || !positive(d->w_sum) || !(d->track_width > 0.0))
+        return fail(CRX_ERR_ARG, "lap_length, l_sum and w_sum must be positive and finite, track_width positive");
+    if (batch < 0) return fail(CRX_ERR_ARG, "batch < 0");
+    if (d->n_cars > 0 && batch % d->n_cars) return fail(CRX_ERR_ARG, "field mode: batch=%d is not a multiple of n_cars=%d", batch, d->n_cars);
+    if (which == 1) {
+        if (d->n_cars > 0 && (car_s0 || car_v || car_ey || n_opp)) return fail(CRX_ERR_ARG, "field mode takes no scripted-car arrays (car_s0, car_v, car_ey, n_opp)");
+        if (d->n_cars == 0 && car_dims) return fail(CRX_ERR_ARG, "scripted mode takes no car_dims");
+        if (d->n_cars == 0 && d->n_opp_max > 0 && any_null(car_s0, car_v, car_ey))
+            return fail(CRX_ERR_ARG, "scripted mode with n_opp_max=%d needs car_s0, car_v and car_ey", d->n_opp_max);
+    }
+    if (which == 2 && group && n_groups < 1) return fail(CRX_ERR_ARG, "group given with n_groups=%d < 1", n_groups);
+    if (batch > 0 && (any_null(stat_i, stat_d) || (which < 2 && !laps) || (which == 1 && !xcurv))) return fail(CRX_ERR_ARG, "NULL array argument");
+    if (which == 2 && any_null(sum_i, sum_d)) return fail(CRX_ERR_ARG, "NULL array argument");
+    memset(&sp, 0, sizeof(sp));
+    sp.d = *d; sp.batch = batch; sp.n_groups = group ? n_groups : 1;
+    return 0;
+}
+
+extern "C" {
+
+int crx_race_stats_reset_dev(const crx_stats_desc* d, int batch, const int32_t* laps, int32_t* stat_i, double* stat_d, void* stream) {
+    crx_stats_kparams sp;
+    if (int rc = check_stats(sp, 0, d, batch, stat_i, stat_d, laps)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (batch == 0) return CRX_OK;
+    sp.laps = laps; sp.stat_i = stat_i; sp.stat_d = stat_d;
+    return launched(crx_launch_race_stats(0, sp, (hipStream_t)stream), "race stats reset");
+}
+
+int crx_race_stats_dev(const crx_stats_desc* d, int batch, int sample, double t, const double* xcurv, const int32_t* laps,
+                       const double* car_s0, const double* car_v, const double* car_ey, const int32_t* n_opp, const double* car_dims,
+                       const double* xt, const int32_t* flag, int32_t* stat_i, double* stat_d, void* stream) {
+    crx_stats_kparams sp;
+    if (int rc = check_stats(sp, 1, d, batch, stat_i, stat_d, laps, xcurv, car_s0, car_v, car_ey, n_opp, car_dims)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (batch == 0) return CRX_OK;
+    sp.sample = sample; sp.t = t; sp.xcurv = xcurv; sp.laps = laps; sp.car_s0 = car_s0; sp.car_v = car_v; sp.car_ey = car_ey; sp.n_opp = n_opp;
+    sp.car_dims = car_dims; sp.xt = xt; sp.flag = flag; sp.stat_i = stat_i; sp.stat_d = stat_d;
+    return launched(crx_launch_race_stats(1, sp, (hipStream_t)stream), "race stats");
+}
+
+int crx_race_stats_summary_dev(const crx_stats_desc* d, int batch, const int32_t* group, int n_groups, const int32_t* stat_i,
+                               const double* stat_d, int64_t* sum_i, double* sum_d, void* stream) {
+    crx_stats_kparams sp;
+    if (int rc = check_stats(sp, 2, d, batch, stat_i, stat_d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, group, n_groups,
+                             sum_i, sum_d)) return rc;
+    if (int rc = ensure_init()) return rc;
+    sp.group = group; sp.stat_i = (int32_t*)stat_i; sp.stat_d = (double*)stat_d; sp.sum_i = (long long*)sum_i; sp.sum_d = sum_d;
+    return launched(crx_launch_race_stats(2, sp, (hipStream_t)stream), "race stats summary");   // (batch == 0: the records of empty groups)
+}
+
+// host-pointer twins: stat_i / stat_d travel both ways
+int crx_race_stats_reset(const crx_stats_desc* d, int batch, const int32_t* laps, int32_t* stat_i, double* stat_d) {
+    crx_stats_kparams chk;
+    if (int rc = check_stats(chk, 0, d, batch, stat_i, stat_d, laps)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (batch == 0) return CRX_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    const size_t Bn = (size_t)batch;
+    Stage sg;
+    auto dl = sg.in(laps, Bn);
+    auto dsi = sg.out(stat_i, Bn * CRX_STATS_NI); auto dsd = sg.out(stat_d, Bn * (CRX_STATS_ND + d->n_opp_max));
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_race_stats_reset_dev(d, batch, sg[dl], sg[dsi], sg[dsd], g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
+int crx_race_stats(const crx_stats_desc* d, int batch, int sample, double t, const double* xcurv, const int32_t* laps, const double* car_s0,
+                   const double* car_v, const double* car_ey, const int32_t* n_opp, const double* car_dims, const double* xt,
+                   const int32_t* flag, int32_t* stat_i, double* stat_d) {
+    crx_stats_kparams chk;
+    if (int rc = check_stats(chk, 1, d, batch, stat_i, stat_d, laps, xcurv, car_s0, car_v, car_ey, n_opp, car_dims)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (batch == 0) return CRX_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    const size_t Bn = (size_t)batch, V = (size_t)d->n_opp_max;
+    Stage sg;
+    auto opt_d = [&](const double* p, size_t n) { return p ? sg.in(p, n) : Stage::Ref<double>{}; };   // unused: sg[ref] is NULL
+    auto opt_i = [&](const int32_t* p, size_t n) { return p ? sg.in(p, n) : Stage::Ref<int32_t>{}; };
+    auto dx = sg.in(xcurv, Bn * 6); auto dl = sg.in(laps, Bn);
+    auto ds0 = opt_d(car_s0, Bn * V), dv = opt_d(car_v, Bn * V), dey = opt_d(car_ey, Bn * V), dcd = opt_d(car_dims, Bn * 2), dxt = opt_d(xt, Bn * 6);
+    auto dno = opt_i(n_opp, Bn), dfl = opt_i(flag, Bn);
+    auto dsi = sg.inout(stat_i, Bn * CRX_STATS_NI); auto dsd = sg.inout(stat_d, Bn * (CRX_STATS_ND + V));
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_race_stats_dev(d, batch, sample, t, sg[dx], sg[dl], sg[ds0], sg[dv], sg[dey], sg[dno], sg[dcd], sg[dxt], sg[dfl], sg[dsi],
+                                    sg[dsd], g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
+int crx_race_stats_summary(const crx_stats_desc* d, int batch, const int32_t* group, int n_groups, const int32_t* stat_i, const double* stat_d,
+                           int64_t* sum_i, double* sum_d) {
+    crx_stats_kparams chk;
+    if (int rc = check_stats(chk, 2, d, batch, stat_i, stat_d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, group, n_groups,
+                             sum_i, sum_d)) return rc;
+    if (int rc = ensure_init()) return rc;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    const size_t Bn = (size_t)batch, G = (size_t)chk.n_groups;
+    Stage sg;
+    auto dg = group ? sg.in(group, Bn) : Stage::Ref<int32_t>{};
+    auto dsi = sg.in(stat_i, Bn * CRX_STATS_NI); auto dsd = sg.in(stat_d, Bn * (CRX_STATS_ND + d->n_opp_max));
+    auto doi = sg.out(sum_i, G * CRX_STATS_SUM_NI); auto dod = sg.out(sum_d, G * CRX_STATS_SUM_ND);
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_race_stats_summary_dev(d, batch, sg[dg], chk.n_groups, sg[dsi], sg[dsd], sg[doi], sg[dod], g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
+}  // extern "C"
+
 // ---- multi-GPU: the ONE collective of the planner sweep, on RCCL directly ----------------------------------------
 // One process per GPU; the caller owns the rendezvous (it carries the 128-byte id from rank 0 to the others by whatever
 // it has: MPI, a file, torch.distributed's store).  RCCL is resolved at run time: if the process already holds a librccl

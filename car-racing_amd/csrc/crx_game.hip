@@ -3,6 +3,8 @@
 //   crx_game_masks_kernel     which branch a race takes this step, as the masks of the masked launches      utils/base.py:463-467
 //   crx_game_commit_kernel    the applied input and the learning MPC's hand-over of its plan      control/control.py:726-728, utils/base.py:504-515, :546-551
 //   crx_game_log_kernel       the simulator's lap log and the races that completed a lap      utils/base.py:780-819, racing/offboard.py:114-131
+// and what the closed loops are run for (include/crx.h, "Race statistics"):
+//   crx_race_stats_reset_kernel, crx_race_stats_kernel, crx_race_stats_summary_kernel      per-car outcomes, one launch per sample; the batch summary
 //
 // ------------------------------------------------------------------------------------------------
 // Device-resident racing-game loop (crx.montecarlo.GameLaps): the bookkeeping of
@@ -15,6 +17,7 @@
 #include <stdint.h>
 
 #include "crx_kparams.h"
+#include "crx_num.h"
 
 // scripted cars at their own clock t (NoDynamicsModel, base.py:847-890): s = v t + s0 wrapped once past the line like
 // update_memory keeps it (base.py:795-819), predictions v (t + j dt) + s0 unwrapped (get_trajectory_nsteps: quirk Q6)
@@ -95,6 +98,199 @@ __global__ void __launch_bounds__(256) crx_game_log_kernel(const crx_game_kparam
     double* lu = gp.log_u + ((size_t)b * P + iu) * 2;
     lu[0] = gp.u[2 * b]; lu[1] = gp.u[2 * b + 1];
     gp.n_log[b] = n + 1;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Race statistics (crx.montecarlo.RaceStats, include/crx.h S1-S4): what the closed loops are run for, accumulated per car.  The
+// outcome arithmetic used to be ~15 element-wise torch launches per step in tools/multi_tests.py; here one sample of every car is one
+// launch, one thread per car, state field-major ([field][batch]) so that a wave's accesses coalesce.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) crx_race_stats_reset_kernel(const crx_stats_kparams sp) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= sp.batch) return;
+    const size_t Bn = (size_t)sp.batch;
+    int32_t* si = sp.stat_i + b;
+    double* sd = sp.stat_d + b;
+    for (int f = 0; f < CRX_STATS_NI; f++) si[f * Bn] = 0;
+    si[CRX_STATS_I_NONFINITE_STEP * Bn] = -1; si[CRX_STATS_I_OFF_STEP * Bn] = -1; si[CRX_STATS_I_CONTACT_STEP * Bn] = -1;
+    si[CRX_STATS_I_LAPS_PREV * Bn] = sp.laps[b];
+    for (int k = 0; k < CRX_STATS_MAX_LAPS; k++) si[(CRX_STATS_I_LAP_STEP + k) * Bn] = -1;
+    sd[CRX_STATS_D_MIN_CLEAR * Bn] = INFINITY; sd[CRX_STATS_D_EY_MAX * Bn] = 0.0;
+    sd[CRX_STATS_D_SUM_EY2 * Bn] = 0.0; sd[CRX_STATS_D_SUM_DV2 * Bn] = 0.0;
+    for (int j = 0; j < sp.d.n_opp_max; j++) sd[(CRX_STATS_D_DS_PREV + j) * Bn] = NAN;
+}
+
+// one sample: the lap counters, then (finite rows only) the track limits, the running sums, and per opponent the super-ellipse value
+// of crx_field_prep_kernel's `clear` and the sign change of the lap-folded gap (include/crx.h S2, S3)
+__global__ void __launch_bounds__(256) crx_race_stats_kernel(const crx_stats_kparams sp) {
+#pragma clang fp contract(off)   // every operation rounded on its own: tests/race_stats_model.py reproduces the bits in NumPy
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= sp.batch) return;
+    const crx_stats_desc& d = sp.d;
+    const size_t Bn = (size_t)sp.batch;
+    int32_t* si = sp.stat_i + b;
+    double* sd = sp.stat_d + b;
+    const double* x = sp.xcurv + (size_t)6 * b;
+    const double vx = x[0], s_e = x[4], ey_e = x[5], L = d.lap_length;
+    bool finite = true;
+    for (int c = 0; c < 6; c++) finite = finite && isfinite(x[c]);
+    // line crossings: integers, whatever the state is
+    const int lp = sp.laps[b], n_laps = si[CRX_STATS_I_N_LAPS * Bn];
+    const long long crossings = (long long)lp - si[CRX_STATS_I_LAPS_PREV * Bn];
+    si[CRX_STATS_I_LAPS_PREV * Bn] = lp;
+    if (crossings > 0) {
+        for (long long k = n_laps; k < n_laps + crossings && k < CRX_STATS_MAX_LAPS; k++) si[(CRX_STATS_I_LAP_STEP + k) * Bn] = sp.sample;
+        si[CRX_STATS_I_N_LAPS * Bn] = (int32_t)(n_laps + crossings);
+    }
+    const int C = d.n_cars, V = C > 0 ? C - 1 : d.n_opp_max;
+    if (!finite) {
+        if (si[CRX_STATS_I_NONFINITE_STEP * Bn] < 0) si[CRX_STATS_I_NONFINITE_STEP * Bn] = sp.sample;
+        for (int j = 0; j < d.n_opp_max; j++) sd[(CRX_STATS_D_DS_PREV + j) * Bn] = NAN;
+        return;
+    }
+    si[CRX_STATS_I_N_SAMPLES * Bn] += 1;
+    const double aey = fabs(ey_e);
+    if (aey > d.track_width) {
+        if (si[CRX_STATS_I_OFF_STEP * Bn] < 0) si[CRX_STATS_I_OFF_STEP * Bn] = sp.sample;
+        si[CRX_STATS_I_OFF_SAMPLES * Bn] += 1;
+    }
+    if (aey > sd[CRX_STATS_D_EY_MAX * Bn]) sd[CRX_STATS_D_EY_MAX * Bn] = aey;
+    sd[CRX_STATS_D_SUM_EY2 * Bn] += ey_e * ey_e;
+    if (sp.xt) {
+        const double dv = vx - sp.xt[(size_t)6 * b];
+        sd[CRX_STATS_D_SUM_DV2 * Bn] += dv * dv;
+    }
+    // field mode: this car's race and its own (length, width), as crx_field_prep_kernel takes them
+    const int r = C > 0 ? b / C : 0, c = C > 0 ? b - r * C : -1;
+    const double l_e = sp.car_dims ? dim_or_default(sp.car_dims[2 * (size_t)b], d.l_sum) : 0.0;
+    const double w_e = sp.car_dims ? dim_or_default(sp.car_dims[2 * (size_t)b + 1], d.w_sum) : 0.0;
+    int n = V;
+    if (C == 0 && sp.n_opp) { n = sp.n_opp[b]; n = n < 0 ? 0 : (n > V ? V : n); }
+    double clr = INFINITY;
+    int passes = 0, passed = 0;
+    for (int j = 0; j < n; j++) {
+        double s_o, ey_o, l_sum = d.l_sum, w_sum = d.w_sum;
+        if (C > 0) {                       // the other cars of the race in car order, skipping the ego
+            const size_t ro = (size_t)r * C + (j < c ? j : j + 1);
+            s_o = sp.xcurv[6 * ro + 4]; ey_o = sp.xcurv[6 * ro + 5];
+            if (sp.car_dims) {
+                l_sum = l_e / 2 + dim_or_default(sp.car_dims[2 * ro], d.l_sum) / 2;
+                w_sum = w_e / 2 + dim_or_default(sp.car_dims[2 * ro + 1], d.w_sum) / 2;
+            }
+        } else {                           // the scripted cars at their clock
+            const size_t io = (size_t)b * V + j;
+            s_o = sp.car_v[io] * sp.t + sp.car_s0[io]; ey_o = sp.car_ey[io];
+        }
+        double* prev = sd + (CRX_STATS_D_DS_PREV + j) * Bn;
+        if (!isfinite(s_o) || !isfinite(ey_o)) { *prev = NAN; continue; }
+        double m = fmod(s_e - s_o + L / 2, L);   // Python's %: the sign of the divisor
+        if (m < 0.0) m += L;
+        const double ds = m - L / 2;
+        const double a = ds / l_sum, bb = (ey_e - ey_o) / w_sum;
+        double pa = 1.0, pb = 1.0;
+        for (int k = 0; k < d.degree; k++) { pa *= a; pb *= bb; }
+        const double h = pa + pb;
+        clr = h < clr ? h : clr;
+        const double p = *prev;
+        if (isfinite(p) && isfinite(ds)) {
+            if (p < 0.0 && ds >= 0.0 && ds - p < L / 2) passes++;
+            if (p >= 0.0 && ds < 0.0 && p - ds < L / 2) passed++;
+        }
+        *prev = ds;
+    }
+    if (clr < sd[CRX_STATS_D_MIN_CLEAR * Bn]) sd[CRX_STATS_D_MIN_CLEAR * Bn] = clr;
+    if (clr < 1.0) {
+        if (si[CRX_STATS_I_CONTACT_STEP * Bn] < 0) si[CRX_STATS_I_CONTACT_STEP * Bn] = sp.sample;
+        si[CRX_STATS_I_CONTACT_SAMPLES * Bn] += 1;
+    }
+    if (passes) si[CRX_STATS_I_PASSES * Bn] += passes;
+    if (passed) si[CRX_STATS_I_PASSED * Bn] += passed;
+    if (sp.flag && sp.flag[b] != 0) si[CRX_STATS_I_FLAG_SAMPLES * Bn] += 1;
+}
+
+// the cars of one group to one record: a workgroup per group, every thread strides over the batch, then one tree per field over LDS.
+// Integer sums, minima and maxima only, so the record does not depend on the order of the cars
+enum StatsOp { STATS_ADD, STATS_MIN, STATS_MAX };
+template <StatsOp OP, typename T>
+__device__ T stats_block_reduce(T v, T* red) {
+    __syncthreads();   // the previous field's tree has been read
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            const T o = red[threadIdx.x + w], m = red[threadIdx.x];
+            red[threadIdx.x] = OP == STATS_ADD ? m + o : (OP == STATS_MIN ? (o < m ? o : m) : (o > m ? o : m));
+        }
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__global__ void __launch_bounds__(256) crx_race_stats_summary_kernel(const crx_stats_kparams sp) {
+    __shared__ long long red_i[256];
+    __shared__ double red_d[256];
+    const int g = blockIdx.x;
+    const size_t Bn = (size_t)sp.batch;
+    long long acc[CRX_STATS_SUM_NI];
+    for (int f = 0; f < CRX_STATS_SUM_NI; f++) acc[f] = 0;
+    acc[CRX_STATS_SUM_LAP1_MIN] = acc[CRX_STATS_SUM_LAP2_MIN] = INT64_MAX;
+    acc[CRX_STATS_SUM_LAP1_MAX] = acc[CRX_STATS_SUM_LAP2_MAX] = -1;
+    double min_clear = INFINITY, ey_max = 0.0;
+    for (int b = threadIdx.x; b < sp.batch; b += blockDim.x) {
+        if (sp.group && sp.group[b] != g) continue;
+        const int32_t* si = sp.stat_i + b;
+        const bool nf = si[CRX_STATS_I_NONFINITE_STEP * Bn] >= 0, off = si[CRX_STATS_I_OFF_STEP * Bn] >= 0;
+        const bool hit = si[CRX_STATS_I_CONTACT_STEP * Bn] >= 0;
+        acc[CRX_STATS_SUM_CARS] += 1;
+        acc[CRX_STATS_SUM_NONFINITE] += nf; acc[CRX_STATS_SUM_OFF] += off; acc[CRX_STATS_SUM_CONTACT] += hit;
+        acc[CRX_STATS_SUM_CLEAN] += !(nf || off || hit);
+        const int nl = si[CRX_STATS_I_N_LAPS * Bn];
+        for (int k = 0; k <= CRX_STATS_MAX_LAPS; k++)   // (no run-time index into acc: it stays in registers)
+            acc[CRX_STATS_SUM_LAPS_HIST + k] += (nl < CRX_STATS_MAX_LAPS ? nl : CRX_STATS_MAX_LAPS) == k;
+        acc[CRX_STATS_SUM_PASSES] += si[CRX_STATS_I_PASSES * Bn];
+        acc[CRX_STATS_SUM_PASSED] += si[CRX_STATS_I_PASSED * Bn];
+        acc[CRX_STATS_SUM_FLAG_SAMPLES] += si[CRX_STATS_I_FLAG_SAMPLES * Bn];
+        acc[CRX_STATS_SUM_N_SAMPLES] += si[CRX_STATS_I_N_SAMPLES * Bn];
+        const long long t0 = si[CRX_STATS_I_LAP_STEP * Bn], t1 = si[(CRX_STATS_I_LAP_STEP + 1) * Bn];
+        if (t0 >= 0) {
+            acc[CRX_STATS_SUM_LAP1_SUM] += t0; acc[CRX_STATS_SUM_LAP1_COUNT] += 1;
+            if (t0 < acc[CRX_STATS_SUM_LAP1_MIN]) acc[CRX_STATS_SUM_LAP1_MIN] = t0;
+            if (t0 > acc[CRX_STATS_SUM_LAP1_MAX]) acc[CRX_STATS_SUM_LAP1_MAX] = t0;
+        }
+        if (t0 >= 0 && t1 >= 0) {
+            const long long t2 = t1 - t0;
+            acc[CRX_STATS_SUM_LAP2_SUM] += t2; acc[CRX_STATS_SUM_LAP2_COUNT] += 1;
+            if (t2 < acc[CRX_STATS_SUM_LAP2_MIN]) acc[CRX_STATS_SUM_LAP2_MIN] = t2;
+            if (t2 > acc[CRX_STATS_SUM_LAP2_MAX]) acc[CRX_STATS_SUM_LAP2_MAX] = t2;
+        }
+        const double mc = sp.stat_d[CRX_STATS_D_MIN_CLEAR * Bn + b], em = sp.stat_d[CRX_STATS_D_EY_MAX * Bn + b];
+        min_clear = mc < min_clear ? mc : min_clear;
+        ey_max = em > ey_max ? em : ey_max;
+    }
+    long long* out = sp.sum_i + (size_t)g * CRX_STATS_SUM_NI;
+#pragma unroll
+    for (int f = 0; f < CRX_STATS_SUM_NI; f++) {
+        const bool lo = f == CRX_STATS_SUM_LAP1_MIN || f == CRX_STATS_SUM_LAP2_MIN, hi = f == CRX_STATS_SUM_LAP1_MAX || f == CRX_STATS_SUM_LAP2_MAX;
+        long long v = lo ? stats_block_reduce<STATS_MIN>(acc[f], red_i) : (hi ? stats_block_reduce<STATS_MAX>(acc[f], red_i) : stats_block_reduce<STATS_ADD>(acc[f], red_i));
+        if (lo && v == INT64_MAX) v = -1;   // no car of the group has that lap
+        if (threadIdx.x == 0) out[f] = v;
+    }
+    const double mc = stats_block_reduce<STATS_MIN>(min_clear, red_d), em = stats_block_reduce<STATS_MAX>(ey_max, red_d);
+    if (threadIdx.x == 0) {
+        sp.sum_d[(size_t)g * CRX_STATS_SUM_ND + CRX_STATS_SUM_D_MIN_CLEAR] = mc;
+        sp.sum_d[(size_t)g * CRX_STATS_SUM_ND + CRX_STATS_SUM_D_EY_MAX] = em;
+    }
+}
+
+hipError_t crx_launch_race_stats(int which, const crx_stats_kparams& sp, hipStream_t st) {
+    const dim3 grid(which == 2 ? (unsigned)sp.n_groups : (unsigned)((sp.batch + 255) / 256)), block(256);
+    if (grid.x == 0) return hipSuccess;
+    switch (which) {
+        case 0: hipLaunchKernelGGL(crx_race_stats_reset_kernel, grid, block, 0, st, sp); break;
+        case 1: hipLaunchKernelGGL(crx_race_stats_kernel, grid, block, 0, st, sp); break;
+        default: hipLaunchKernelGGL(crx_race_stats_summary_kernel, grid, block, 0, st, sp); break;
+    }
+    return hipGetLastError();
 }
 
 hipError_t crx_launch_game(int which, const crx_game_kparams& gp, hipStream_t st) {

@@ -253,6 +253,20 @@ struct crx_game_kparams {
     double *log_x, *log_u;
 };
 hipError_t crx_launch_game(int which, const crx_game_kparams& gp, hipStream_t st);
+// crx_game.hip: per-car race statistics of every closed loop (crx.montecarlo.RaceStats): reset, one sample, the batch summary
+struct crx_stats_kparams {
+    crx_stats_desc d;
+    int batch, sample, n_groups;
+    double t;                                          // scripted mode: the scripted cars' clock at this sample
+    const double *xcurv, *car_s0, *car_v, *car_ey;     // xcurv [batch][6]; scripted mode: [batch][n_opp_max] each
+    const double *car_dims, *xt;                       // optional: field mode [n_races][n_cars][2] (length, width); [batch][6]
+    const int32_t *laps, *n_opp, *flag, *group;        // n_opp, flag, group: optional [batch]
+    int32_t* stat_i;                                   // [CRX_STATS_NI][batch]
+    double* stat_d;                                    // [CRX_STATS_ND + n_opp_max][batch]
+    long long* sum_i;                                  // summary: [n_groups][CRX_STATS_SUM_NI]
+    double* sum_d;                                     //          [n_groups][CRX_STATS_SUM_ND]
+};
+hipError_t crx_launch_race_stats(int which, const crx_stats_kparams& sp, hipStream_t st);   // 0 reset, 1 one sample, 2 summary
 // crx_lmpc.hip, crx_lmpcprep.hip
 hipError_t crx_launch_lmpc(const crx_lmpc_kparams& kp, hipStream_t st);
 hipError_t crx_launch_lmpcprep(const crx_lmpcprep_kparams& kp, hipStream_t st);

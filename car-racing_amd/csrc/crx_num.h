@@ -6,7 +6,8 @@
 //
 // Floating-point contraction: every including unit includes this header at its head, in the compiler's default state (hipcc: contraction
 // on).  interp1d() (slope * dx + y) and lap_fold() (s - laps * L) contain a multiply-add and may fuse, as the written-out
-// copies did; none of them is called from under `#pragma clang fp contract(off)` (crx_game_traffic_kernel, crx_lmpcprep.hip).
+// copies did; none of them is called from under `#pragma clang fp contract(off)` (crx_game_traffic_kernel, crx_lmpcprep.hip;
+// crx_race_stats_kernel in crx_game.hip takes dim_or_default() only, which has no arithmetic).
 #ifndef CRX_NUM_H
 #define CRX_NUM_H
 #include <hip/hip_runtime.h>

@@ -44,7 +44,10 @@
 extern "C" {
 #endif
 
-#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_field_desc, crx_field_desc_default, crx_field_prep, crx_field_prep_dev (field races: every
+#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_stats_desc, crx_stats_desc_default, crx_race_stats_reset, crx_race_stats_reset_dev,
+                          crx_race_stats, crx_race_stats_dev, crx_race_stats_summary, crx_race_stats_summary_dev and the CRX_STATS_* layout
+                          (per-car race statistics of every closed loop) -- new entry points only.
+                          0.4.0 (additive, same number): crx_field_desc, crx_field_desc_default, crx_field_prep, crx_field_prep_dev (field races: every
                           car of a race drives itself) -- new entry points only.
                           0.4.0 (additive, same number): crx_plant_step_params, crx_plant_step_params_dev, crx_plant_step_params_plain_dev and
                           CRX_PLANT_NPARAM (one BicycleDynamicsParam set per vehicle) -- new entry points only.
@@ -1094,6 +1097,130 @@ int crx_game_commit_dev(int N, int Np, int batch, const int32_t* overtake, const
                         double* lin_input, int32_t* step_no, int32_t* addpoint_step, int32_t* old_flag, void* stream);
 int crx_game_log_dev(int batch, int n_points, double lap_length, const double* xcurv, const double* u, const int32_t* laps,
                      int32_t* laps_prev, double* log_x, double* log_u, int32_t* n_log, int32_t* crossed, void* stream);
+
+/*
+ * Race statistics (crx.montecarlo.RaceStats): what a closed-loop Monte-Carlo is run for -- contacts, cars that left the track, lap
+ * times, overtakes -- accumulated per car on the device, ONE launch per sample, and reduced to one fixed record per group of cars by
+ * one more.  A sample shows the kernel the cars' states as they are: the caller takes sample 0 on the initial states and one sample
+ * after every control step.  Thread b owns car b; no car's bad state touches another car's statistics.
+ *
+ * State: two caller-owned device arrays, FIELD-major (field f of car b at [f * batch + b]):
+ *   stat_i [CRX_STATS_NI][batch] int32                   stat_d [CRX_STATS_ND + n_opp_max][batch] float64
+ * with the fields below; "(v)" is the value crx_race_stats_reset_dev writes.
+ *   N_SAMPLES        samples taken on a finite state (0)
+ *   NONFINITE_STEP   first sample whose xcurv row had a non-finite entry (-1)
+ *   OFF_STEP, OFF_SAMPLES          first sample with |ey| > track_width, strictly (-1); how many such samples (0)
+ *   CONTACT_STEP, CONTACT_SAMPLES  first sample with clear < 1, strictly (-1); how many such samples (0)
+ *   N_LAPS, LAPS_PREV              line crossings seen since the reset (0); laps[b] at the last sample (laps[b] at the reset)
+ *   LAP_STEP + k, k < CRX_STATS_MAX_LAPS   sample at which crossing number k was seen (-1); later crossings only count in N_LAPS.
+ *                    A lap counter that advanced by d > 1 between two samples is d crossings seen at that sample
+ *   PASSES, PASSED   overtakes made and suffered, S3 (0)
+ *   FLAG_SAMPLES     samples with flag[b] != 0, when a flag array is given (0)
+ *   MIN_CLEAR        running minimum of clear, S2 (+inf)          EY_MAX   running maximum of |ey| (0)
+ *   SUM_EY2, SUM_DV2 running sums of ey * ey and of (vx - xt[b][0])^2, the latter only when xt is given (0); summed per car in
+ *                    sample order
+ *   DS_PREV + j, j < n_opp_max     lap-folded signed gap to opponent j at the previous sample (NaN)
+ *
+ * S1  Opponents.  Scripted mode (n_cars == 0): opponent j of car b is the scripted car (car_s0, car_v, car_ey)[b][j] at the clock t,
+ *     s_opp = car_v * t + car_s0 (multiply, then add), ey_opp = car_ey; j < n_opp[b] clipped to [0, n_opp_max] (n_opp NULL: all
+ *     n_opp_max); l_sum, w_sum from the descriptor.  n_opp_max == 0: a car on its own (clear = +inf, no passes).
+ *     Field mode (n_cars = C >= 1): batch = n_races * C, race-major and car-minor; the opponents of a car are the C - 1 other cars of
+ *     its race in car order, skipping itself, all read from the same xcurv; n_opp_max >= C - 1.  With car_dims [n_races][C][2] the
+ *     pair (ego, o) has l_sum = l_e / 2 + l_o / 2, w_sum = w_e / 2 + w_o / 2 as in crx_field_prep (a non-positive or non-finite
+ *     entry takes the descriptor's value).
+ * S2  clear, the `clear` of crx_field_prep restated, every operation rounded on its own (no fused multiply-add):
+ *     m = fmod(s_ego - s_opp + L/2, L); if (m < 0) m += L; ds = m - L/2; a = ds / l_sum; b = (ey_ego - ey_opp) / w_sum;
+ *     pa, pb = the `degree`-fold products of a and of b, starting from 1.0; h = pa + pb; clear = the minimum of h over the
+ *     opponents, +inf with none.
+ * S3  Overtakes compare p = DS_PREV[j] with the new ds when both are finite: p < 0 && ds >= 0 && ds - p < L/2 counts one in PASSES,
+ *     p >= 0 && ds < 0 && p - ds < L/2 one in PASSED (the `< L/2` keeps the sign flip of a car half a lap away from counting); then
+ *     DS_PREV[j] = ds.
+ * S4  Non-finite data.  A car whose own row is non-finite at a sample records NONFINITE_STEP if that is still -1; its lap counters
+ *     update all the same (they are integers); its DS_PREV[*] become NaN; nothing else changes at that sample.  An opponent whose s
+ *     or ey is non-finite is skipped for clear and gets DS_PREV = NaN.
+ *
+ * crx_race_stats_summary_dev reduces the cars of each group (group [batch] int32 in [0, n_groups), a car with another value belongs to
+ * no group; NULL: one group of all cars) to sum_i [n_groups][CRX_STATS_SUM_NI] int64 and sum_d [n_groups][CRX_STATS_SUM_ND] float64.
+ * Every sum is an integer sum, so the record is exact and independent of the order of the cars:
+ *   CARS; NONFINITE, OFF, CONTACT = cars whose ..._STEP >= 0; CLEAN = cars with none of the three; LAPS_HIST + k, k = 0..8 = cars with
+ *   N_LAPS == k (the last bin: 8 or more); PASSES, PASSED, FLAG_SAMPLES, N_SAMPLES = sums over the cars;
+ *   LAP1_SUM, _MIN, _MAX, _COUNT over the first lap time LAP_STEP[0] of the cars that have one; LAP2_* over the second lap time
+ *   LAP_STEP[1] - LAP_STEP[0] of the cars that have one (count 0: sum 0, min and max -1);
+ *   sum_d: MIN_CLEAR = the group's minimum of MIN_CLEAR (+inf without cars), EY_MAX = its maximum of EY_MAX (0 without cars).
+ * Percentiles stay with the caller: one copy of `batch` int32.
+ *
+ * Refused with CRX_ERR_ARG (before the library's state is looked at): a bad descriptor, batch < 0, scripted arrays (car_s0, car_v,
+ * car_ey, n_opp) in field mode or car_dims in scripted mode, n_opp_max > 0 in scripted mode without all three car arrays, batch not a
+ * multiple of n_cars in field mode, a group without n_groups >= 1, a NULL array that the call needs.  The host-pointer entries stage
+ * through the _dev ones; stat_i and stat_d are updated in place.
+ */
+#define CRX_STATS_MAX_LAPS 8
+#define CRX_STATS_I_N_SAMPLES 0
+#define CRX_STATS_I_NONFINITE_STEP 1
+#define CRX_STATS_I_OFF_STEP 2
+#define CRX_STATS_I_OFF_SAMPLES 3
+#define CRX_STATS_I_CONTACT_STEP 4
+#define CRX_STATS_I_CONTACT_SAMPLES 5
+#define CRX_STATS_I_N_LAPS 6
+#define CRX_STATS_I_LAPS_PREV 7
+#define CRX_STATS_I_LAP_STEP 8   /* .. 8 + CRX_STATS_MAX_LAPS - 1 */
+#define CRX_STATS_I_PASSES 16
+#define CRX_STATS_I_PASSED 17
+#define CRX_STATS_I_FLAG_SAMPLES 18
+#define CRX_STATS_NI 19
+#define CRX_STATS_D_MIN_CLEAR 0
+#define CRX_STATS_D_EY_MAX 1
+#define CRX_STATS_D_SUM_EY2 2
+#define CRX_STATS_D_SUM_DV2 3
+#define CRX_STATS_D_DS_PREV 4    /* .. 4 + n_opp_max - 1 */
+#define CRX_STATS_ND 4
+#define CRX_STATS_MAX_OPP 32
+#define CRX_STATS_SUM_CARS 0
+#define CRX_STATS_SUM_NONFINITE 1
+#define CRX_STATS_SUM_OFF 2
+#define CRX_STATS_SUM_CONTACT 3
+#define CRX_STATS_SUM_CLEAN 4
+#define CRX_STATS_SUM_LAPS_HIST 5   /* .. 5 + CRX_STATS_MAX_LAPS */
+#define CRX_STATS_SUM_PASSES 14
+#define CRX_STATS_SUM_PASSED 15
+#define CRX_STATS_SUM_FLAG_SAMPLES 16
+#define CRX_STATS_SUM_N_SAMPLES 17
+#define CRX_STATS_SUM_LAP1_SUM 18
+#define CRX_STATS_SUM_LAP1_MIN 19
+#define CRX_STATS_SUM_LAP1_MAX 20
+#define CRX_STATS_SUM_LAP1_COUNT 21
+#define CRX_STATS_SUM_LAP2_SUM 22
+#define CRX_STATS_SUM_LAP2_MIN 23
+#define CRX_STATS_SUM_LAP2_MAX 24
+#define CRX_STATS_SUM_LAP2_COUNT 25
+#define CRX_STATS_SUM_NI 26
+#define CRX_STATS_SUM_D_MIN_CLEAR 0
+#define CRX_STATS_SUM_D_EY_MAX 1
+#define CRX_STATS_SUM_ND 2
+typedef struct crx_stats_desc {
+    int32_t n_opp_max;    /* opponent slots per car, 0 .. CRX_STATS_MAX_OPP: rows of DS_PREV */
+    int32_t n_cars;       /* 0: scripted mode; 1 .. CRX_MAX_OBS + 1: field mode, cars per race */
+    int32_t degree;       /* exponent of the super-ellipse: 2, 4, 6 or 8 */
+    int32_t pad;
+    double lap_length;    /* L */
+    double track_width;   /* off track: |ey| > track_width (+inf: never) */
+    double l_sum, w_sum;  /* half-sums of the lengths and widths of a pair of cars */
+} crx_stats_desc;
+/* degree 6, l_sum 0.4, w_sum 0.2 */
+void crx_stats_desc_default(crx_stats_desc* d, int n_opp_max, int n_cars, double lap_length, double track_width);
+int crx_race_stats_reset_dev(const crx_stats_desc* d, int batch, const int32_t* laps, int32_t* stat_i, double* stat_d, void* stream);
+int crx_race_stats_dev(const crx_stats_desc* d, int batch, int sample, double t, const double* xcurv, const int32_t* laps,
+                       const double* car_s0, const double* car_v, const double* car_ey, const int32_t* n_opp,
+                       const double* car_dims, const double* xt, const int32_t* flag, int32_t* stat_i, double* stat_d,
+                       void* stream);
+int crx_race_stats_summary_dev(const crx_stats_desc* d, int batch, const int32_t* group, int n_groups, const int32_t* stat_i,
+                               const double* stat_d, int64_t* sum_i, double* sum_d, void* stream);
+int crx_race_stats_reset(const crx_stats_desc* d, int batch, const int32_t* laps, int32_t* stat_i, double* stat_d);
+int crx_race_stats(const crx_stats_desc* d, int batch, int sample, double t, const double* xcurv, const int32_t* laps,
+                   const double* car_s0, const double* car_v, const double* car_ey, const int32_t* n_opp, const double* car_dims,
+                   const double* xt, const int32_t* flag, int32_t* stat_i, double* stat_d);
+int crx_race_stats_summary(const crx_stats_desc* d, int batch, const int32_t* group, int n_groups, const int32_t* stat_i,
+                           const double* stat_d, int64_t* sum_i, double* sum_d);
 
 /*
  * Multi-GPU: problems are independent and a planner sweep is sharded by scenario, so the path has

@@ -8,8 +8,9 @@ One GPU pass on the track l_shape, two loops of the same solver batch B = R C, o
   scripted   montecarlo.MpccbfRaces as it stands: B independent egos from the same states, each with V scripted cars 1.5 m apart ahead
              of it at 0.2 .. 0.4 m/s -- the loop every release so far shipped, as the yardstick for the prep launch and the step.
 Reported:
-  outcome    of `field` over --steps control steps from the start: share of converged solves, cars with min_clear < 1 (contact at some
-             step), laps, mean obstacle count per NLP.
+  outcome    of `field` over --steps control steps from the start: share of converged solves, laps, mean obstacle count per NLP, and from
+             crx.montecarlo.RaceStats (sampled on the states the steps start from): cars with contact at some step (clear < 1), cars
+             that left the track, cars with a non-finite state, overtakes made, the smallest clear.
   step_ms    per loop, the free-running step() by device events (crx_timer_*): --windows windows of --steps / --windows steps each,
              alternating between the loops after one warm-up window each; median of the window means, with min, max and spread
              (max - min) / median.
@@ -109,14 +110,19 @@ def main():
     x0[..., 5] = rng.choice([-0.3, -0.1, 0.1, 0.3], (R, C))
     vt = rng.uniform(0.5, 1.0, (R, C))
     field = montecarlo.FieldRaces(tab, L, track.width, A, B, x0, x0, C, vt=vt, N=a.N, noise_seed=a.seed)
+    # the outcome figures come from crx.montecarlo.RaceStats, one launch per step, sampled on the states each step STARTS from (the
+    # states FieldRaces.min_clear covers)
+    stats = montecarlo.RaceStats(field)
     conv = n_obs = 0
     for _ in range(a.steps):
+        stats.update()
         field.step()
         conv += (field.ws.status == 0).sum()
         n_obs += field.fws.n_obs.sum()
-    torch.cuda.synchronize()
+    rec = stats.summary()
     out = dict(R=R, C=C, N=a.N, steps=a.steps, seed=a.seed,
-               outcome=dict(converged=round(float(conv) / (a.steps * R * C), 5), contacts=int((field.min_clear < 1).sum()), cars=R * C,
+               outcome=dict(converged=round(float(conv) / (a.steps * R * C), 5), contacts=rec["contact"], off_track=rec["off"],
+                            non_finite=rec["nonfinite"], overtakes=rec["passes"], min_clear=rec["min_clear"], cars=R * C,
                             laps_min=int(field.laps.min()), laps_max=int(field.laps.max()), mean_n_obs=round(float(n_obs) / (a.steps * R * C), 4)))
     loops = dict(field=field)
     if V >= 1:

@@ -37,32 +37,28 @@ def _track():
 
 
 def _lqr_arm(track, x0, A, B, P, steps, vt, noise_seed):
-    import torch
-
     from crx import abi, montecarlo
 
     r = montecarlo.LqrLaps(track.point_and_tangent, track.lap_length, x0, x0, A, B, vt=vt, noise_seed=noise_seed, plant_params=P)
-    Bn = r.batch
-    f64 = dict(dtype=torch.float64, device=r.device)
-    ey2, dv2 = torch.zeros(Bn, **f64), torch.zeros(Bn, **f64)
-    ey_max = torch.zeros(Bn, **f64)
-    finite = torch.ones(Bn, dtype=torch.bool, device=r.device)
+    # two crx.montecarlo.RaceStats on the one loop, sampled after every step: `whole` over the run (off track, non-finite), `tail` reset
+    # where the last half begins (the sums behind the RMS figures; LqrLaps' xt carries vt)
     half = steps // 2
+    whole, tail = montecarlo.RaceStats(r, track_width=track.width, first_sample=1), None
     for k in range(steps):
-        r.step()
-        finite &= torch.isfinite(r.xc).all(dim=1)
-        ey_max = torch.maximum(ey_max, torch.nan_to_num(r.xc[:, 5].abs(), nan=0.0, posinf=0.0))
-        if k >= steps - half:
-            ey2 += r.xc[:, 5] ** 2
-            dv2 += (r.xc[:, 0] - vt) ** 2
-    torch.cuda.synchronize()
-    off = finite & (ey_max > track.width)
-    ok = (finite & ~off).cpu().numpy()
-    rms_ey, rms_dv = torch.sqrt(ey2 / half).cpu().numpy()[ok], torch.sqrt(dv2 / half).cpu().numpy()[ok]
+        whole.step()
+        if k == steps - half:
+            tail = montecarlo.RaceStats(r, track_width=track.width)
+        if tail is not None:
+            tail.update()
+    w, t = whole.per_car(), tail.per_car()
+    finite = w["nonfinite_step"] < 0
+    off = finite & (w["off_step"] >= 0)
+    ok = finite & ~off
+    rms_ey, rms_dv = np.sqrt(t["sum_ey2"] / half)[ok], np.sqrt(t["sum_dv2"] / half)[ok]
     st = r.design.status.cpu().numpy()
     pct = lambda v, q: round(float(np.percentile(v, q)), 5) if v.size else None   # noqa: E731
     return dict(rms_ey_p50=pct(rms_ey, 50), rms_ey_p95=pct(rms_ey, 95), rms_dv_p50=pct(rms_dv, 50), rms_dv_p95=pct(rms_dv, 95),
-                off_track=int(off.sum().item()), non_finite=int((~finite).sum().item()), laps_p50=float(np.median(r.laps.cpu().numpy())),
+                off_track=int(off.sum()), non_finite=int((~finite).sum()), laps_p50=float(np.median(r.laps.cpu().numpy())),
                 design_failed=int((~np.isin(st, (abi.CRX_CONVERGED, abi.CRX_MAX_ITER))).sum()))
 
 

@@ -286,6 +286,23 @@ def bind_stats(lib, prefix="crx_"):
         fn.restype = None if name == "stats_desc_default" else C.c_int
 
 
+# include/crx.h "Seed laps": the per-car phase and the bits of seed_status
+SEED_PID, SEED_MPC, SEED_DONE, SEED_FAILED = 0, 1, 2, 3
+CRX_SEED_MPC_FAILED, CRX_SEED_LOG_FULL = 1, 2
+SEED_ARGTYPES = {
+    "seed_commit_dev": [C.c_int, C.c_int] + [_PV] * 9,
+    "seed_log_dev": [C.c_int, C.c_int, C.c_double] + [_PV] * 15,
+}
+
+
+def bind_seed(lib, prefix="crx_"):
+    """argtypes / restype of the seed-lap entries on a loaded library (lap_length travels as a double by value)."""
+    for name, argtypes in SEED_ARGTYPES.items():
+        fn = getattr(lib, prefix + name)
+        fn.argtypes = argtypes
+        fn.restype = C.c_int
+
+
 def stats_summary_record(sum_i, sum_d):
     """The summary arrays of one group as a dict by field name (laps_hist: the 9 bins)."""
     rec = {k: int(sum_i[i]) for k, i in STATS_SUM_I.items() if k != "laps_hist"}
@@ -478,6 +495,8 @@ class Binding:
                 getattr(lib, prefix + name).restype = C.c_int
         if hasattr(lib, prefix + "race_stats_dev"):
             bind_stats(lib, prefix)
+        if hasattr(lib, prefix + "seed_log_dev"):
+            bind_seed(lib, prefix)
         self._check = None
 
     def race_stats_reset(self, desc, laps):

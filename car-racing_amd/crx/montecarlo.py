@@ -14,6 +14,10 @@ Every loop steps its plant through _Plant._advance, the learning-MPC step is Lmp
 `lm` through them), and the run-to-the-end functions share _run_and_log.  The launch sequence of each step() is stated in its
 docstring and pinned by tests/test_montecarlo_sequence_cpu.py.
 
+SeedLaps is what comes before the learning MPC: every car's own PID lap and MPC-LTI lap become its own safe set on the device, and
+its lmpc_inputs() are the constructor arguments of LmpcLaps / GameLaps as device tensors (PidLaps -> identify -> SeedLaps -> LmpcLaps |
+GameLaps runs a fleet from standstill to racing without a host array in between).
+
 What the loops are run for -- contacts, cars off the track, lap times, overtakes -- is RaceStats (end of this module): per-car
 statistics on the device, one launch per sample, attached to any loop through the loop's stats_inputs().
 """
@@ -45,7 +49,11 @@ class _Noise:
 
 def _dev(a, dev, dtype=torch.float64, clone=False):
     """Host array -> contiguous tensor of `dtype` on `dev`.  clone: the loop writes to it, so it must own its memory (on the CPU
-    torch.as_tensor shares the caller's array)."""
+    torch.as_tensor shares the caller's array).  A tensor (what SeedLaps.lmpc_inputs() hands over) is cast, moved and made contiguous
+    without passing through the host, and cloned when asked."""
+    if torch.is_tensor(a):
+        t = a.to(dtype=dtype, device=dev).contiguous()
+        return t.clone() if clone else t
     t = torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device=dev)
     return t.clone() if clone else t
 
@@ -853,6 +861,105 @@ def pid_laps(track_table, lap_length, xcurv0, xglob0, steps, vt=0.5, eyt=0.0, ti
     """PidLaps run to the end: the logs stay on the device (r.x_log, r.u_log); r.identify(lamb) fits them."""
     return PidLaps(track_table, lap_length, xcurv0, xglob0, steps, vt=vt, eyt=eyt, timestep=timestep, noise_z=noise_z,
                    noise_seed=noise_seed, device=device, plant_params=plant_params).run()
+
+
+class SeedLaps(_Plant):
+    """The two laps in front of the learning MPC, for B cars at once and per car, device-resident: every car drives lap 0 under PID and
+    lap 1 under MPC-LTI from its own start state, with its own plant parameters and on its own controller model, and both laps become ITS
+    safe set (tests/auto_racing_game_test.py:48-73: PID lap, MPC-LTI lap, add_trajectory(ego, 0), add_trajectory(ego, 1)).  The learning
+    MPC's stage models are regressions over these laps, its terminal set is their points and its cost-to-go their step counts, so a fleet of
+    different cars must not share them.  Per control step, without touching the host (include/crx.h "Seed laps", S1-S6):
+
+        crx_cbf_solve_dev        zero obstacle slots = control.mpc_lti, masked: only the cars in their MPC-LTI lap solve
+        crx_seed_commit_dev      the applied input: PID law, u_0 of the plan, or zero for a car that is done
+        crx_plant_step_wrap_dev  plant + lap bookkeeping
+        crx_seed_log_dev         a driving car logs the step and changes phase at the line; a seeded car is put back where it stood
+        crx_lmpc_addtraj_dev     a car that crossed: its logged lap becomes a safe-set lap
+
+    The cars finish at different steps; a car that has handed over (phase 2) stands at its hand-over state, so after run() xc / xg are
+    the start states of every car's first learning-MPC lap and lmpc_inputs() is what LmpcLaps / GameLaps take -- device tensors, no host
+    array in between.  vt, eyt: scalars or one value per car, the target of both laps (tests/auto_racing_game_test.py:122,131).  models =
+    (A [B,6,6], B [B,6,2]), host arrays or device tensors (PidLaps.identify()): every car's MPC-LTI lap on its own model; A, B are then
+    unused.  phase [B]: 0 PID lap, 1 MPC-LTI lap, 2 seeded, 3 failed; seed_status [B]: bit abi.CRX_SEED_MPC_FAILED = a step of the
+    MPC-LTI lap applied an iterate that had not converged, abi.CRX_SEED_LOG_FULL = a lap did not reach the line within n_points - 1 steps."""
+
+    def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, vt=0.7, eyt=0.0, N=10, n_points=600, n_laps=4, timestep=0.1,
+                 device=None, noise_seed=None, models=None, plant_params=None):
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params)
+        f64 = dict(dtype=torch.float64, device=dev)
+        i32 = dict(dtype=torch.int32, device=dev)
+        Bn, P, L = self.batch, int(n_points), int(n_laps)
+        if L < 2 or P < 2:
+            raise ValueError("SeedLaps: two laps of safe set and two log rows at least (n_laps %d, n_points %d)" % (L, P))
+        self.N, self.track_width = N, track_width
+        if models is not None and A is None and B is None:   # (the descriptor's own model is not read then)
+            A, B = np.zeros((6, 6)), np.zeros((6, 2))
+        # control.mpc_lti's descriptor (control/control.py:71-76): MPCTrackingParam's weights, no obstacle slot
+        self.desc = abi.cbf_desc(N, 0, A, B, Q=(10.0, 0.0, 0.0, 4.0, 0.0, 40.0), R=(0.1, 0.1), ey_max=track_width)
+        self.vt, self.eyt = _per_race(vt, Bn, dev), _per_race(eyt, Bn, dev)
+        self.xt = torch.zeros((Bn, 6), **f64)
+        self.xt[:, 0], self.xt[:, 5] = self.vt, self.eyt
+        self.ws = torch_api.CbfWorkspace(self.desc, Bn, dev)
+        self.models = None if models is None else torch_api.CbfModels(self.desc, *_models(models[0], models[1], Bn, dev))
+        self.obs_s, self.obs_e = torch.empty((Bn, 0, N + 1), **f64), torch.empty((Bn, 0, N + 1), **f64)
+        self.lap_off, self.n_obs = torch.empty((Bn, 0), **f64), torch.zeros((Bn,), **i32)
+        # the safe set as LMPCRacingGame.__init__ leaves it (utils/base.py:430-441), stored lap-major as LmpcLaps keeps it
+        self.ss, self.us = torch.full((Bn, L, P, 6), 10000.0, **f64), torch.full((Bn, L, P, 2), 10000.0, **f64)
+        self.qf = torch.zeros((Bn, L, P), **f64)
+        self.time_ss, self.it = torch.full((Bn, L), 10000, **i32), torch.zeros((Bn,), **i32)
+        self.pdesc = abi.lmpcprep_desc(12, P, L, self.tab.shape[0], timestep, lap_length)   # the hand-over reads n_points, n_laps, lap_length
+        # the running lap as the simulator logs it, as in LmpcLaps
+        self.log_x, self.log_u = torch.zeros((Bn, P, 6), **f64), torch.zeros((Bn, P, 2), **f64)
+        self.log_x[:, 0] = self.xc
+        self.n_log = torch.ones((Bn,), **i32)
+        self.laps_prev, self.crossed = torch.zeros((Bn,), **i32), torch.zeros((Bn,), **i32)
+        self.step_no, self.traj_status = torch.zeros((Bn,), **i32), torch.zeros((Bn,), **i32)
+        self.phase, self.seed_status, self.m_mpc = torch.zeros((Bn,), **i32), torch.zeros((Bn,), **i32), torch.zeros((Bn,), **i32)
+        self.u = torch.zeros((Bn, 2), **f64)
+        self.k = 0
+
+    def step(self):
+        """One control step of every car, five libcrx launches: cbf_solve_dev (active = m_mpc), seed_commit_dev, plant_step_wrap_dev,
+        seed_log_dev, lmpc_addtraj_dev (dispatch = "longest_first": one longest_first ahead of the solver launch)."""
+        torch_api.cbf_solve_dev(self.desc, self.xc, self.xt, self.obs_s, self.obs_e, self.lap_off, self.n_obs, ws=self.ws, active=self.m_mpc,
+                                order=_order(self, self.ws.iters, self.m_mpc), models=self.models)
+        torch_api.seed_commit_dev(self.N, self.phase, self.vt, self.eyt, self.xc, self.ws.U, self.ws.status, self.seed_status, self.u)
+        xc_prev, xg_prev = self.xc, self.xg
+        self._advance(self.u, 2)
+        torch_api.seed_log_dev(self.lap_length, xc_prev, xg_prev, self.xc, self.xg, self.u, self.laps, self.laps_prev, self.log_x, self.log_u,
+                               self.n_log, self.crossed, self.phase, self.seed_status, self.m_mpc)
+        torch_api.lmpc_addtraj_dev(self.pdesc, self.crossed, self.log_x, self.log_u, self.n_log, self.ss, self.us, self.qf, self.time_ss, self.it,
+                                   self.step_no, self.xc, self.traj_status)
+        self.k += 1
+
+    def n_driving(self):
+        """How many cars are still in their PID or MPC-LTI lap.  Synchronises: one count comes back from the device."""
+        return int((self.phase < 2).sum())
+
+    def run(self, max_steps, check_every=32):
+        """step() until no car is in phase 0 or 1, max_steps at most.  One count is read from the device every check_every steps and
+        nothing else returns to the host; the steps a finished batch takes until the next read change nothing (S4)."""
+        while self.k < max_steps:
+            self.step()
+            if self.k % check_every == 0 and self.n_driving() == 0:
+                break
+        return self
+
+    def lmpc_inputs(self, N=12):
+        """What LmpcLaps / GameLaps are constructed from, by parameter name and as device tensors: the cars' safe sets and their hand-over
+        states, and the linearisation points add_trajectory hands over from lap 0 (utils/base.py:651-653) for a learning MPC of horizon N.
+        Nothing is read back here: a car whose phase is not 2 (check phase / seed_status) has no complete safe set, and a learning MPC
+        started on it regresses over 10000-filled rows."""
+        return dict(ss_xcurv=self.ss, u_ss=self.us, qfun=self.qf, time_ss=self.time_ss, it=self.it, xcurv0=self.xc, xglob0=self.xg,
+                    lin_points=self.ss[:, 0, 1:N + 2], lin_input=self.us[:, 0, 1:N + 1])
+
+
+def seed_laps(track_table, lap_length, track_width, A, B, xcurv0, xglob0, max_steps, vt=0.7, eyt=0.0, N=10, n_points=600, n_laps=4, timestep=0.1,
+              device=None, noise_seed=None, models=None, plant_params=None, check_every=32):
+    """SeedLaps run until every car has handed over (or max_steps): everything stays on the device (r.lmpc_inputs(), r.phase,
+    r.seed_status)."""
+    return SeedLaps(track_table, lap_length, track_width, A, B, xcurv0, xglob0, vt=vt, eyt=eyt, N=N, n_points=n_points, n_laps=n_laps,
+                    timestep=timestep, device=device, noise_seed=noise_seed, models=models, plant_params=plant_params).run(max_steps, check_every)
 
 
 class LqrLaps(_Plant):

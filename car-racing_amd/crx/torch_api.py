@@ -943,3 +943,38 @@ def game_log_dev(lap_length, xcurv, u, laps, laps_prev, log_x, log_u, n_log, cro
     _chk(log_u, torch.float64, (Bn, P, 2), "log_u")
     _call("crx_game_log_dev", C.c_int(Bn), C.c_int(P), C.c_double(lap_length), _ptr(xcurv), _ptr(u), _ptr(laps), _ptr(laps_prev), _ptr(log_x),
           _ptr(log_u), _ptr(n_log), _ptr(crossed), _stream())
+
+
+# ---- seed laps: each car's PID lap and MPC-LTI lap into its own safe set (include/crx.h "Seed laps", S1-S6) ------------------------------
+def seed_commit_dev(N, phase, vt, eyt, x, U_mpc, mpc_status, seed_status, u):
+    """crx_seed_commit_dev, after the solver launch and before the plant: u [B,2] <- control.pid of x (phase 0), U_mpc[:, 0] (phase 1; a
+    solver status other than converged sets bit CRX_SEED_MPC_FAILED of seed_status) or zero (phase >= 2)."""
+    Bn = u.shape[0]
+    for name, a in (("phase", phase), ("mpc_status", mpc_status), ("seed_status", seed_status)):
+        _chk(a, torch.int32, (Bn,), name)
+    _chk(vt, torch.float64, (Bn,), "vt")
+    _chk(eyt, torch.float64, (Bn,), "eyt")
+    _chk(x, torch.float64, (Bn, 6), "x")
+    _chk(U_mpc, torch.float64, (Bn, N, 2), "U_mpc")
+    _chk(u, torch.float64, (Bn, 2), "u")
+    _call("crx_seed_commit_dev", C.c_int(N), C.c_int(Bn), _ptr(phase), _ptr(vt), _ptr(eyt), _ptr(x), _ptr(U_mpc), _ptr(mpc_status),
+          _ptr(seed_status), _ptr(u), _stream())
+
+
+def seed_log_dev(lap_length, xcurv_prev, xglob_prev, xcurv, xglob, u, laps, laps_prev, log_x, log_u, n_log, crossed, phase, seed_status, m_mpc):
+    """crx_seed_log_dev, after the plant and before lmpc_addtraj_dev: a car in phase >= 2 is put back to (xcurv_prev, xglob_prev, laps_prev);
+    a driving car logs the step as game_log_dev does and its phase moves on; m_mpc <- (phase == 1)."""
+    Bn, P = log_x.shape[0], log_x.shape[1]
+    for name, a in (("xcurv_prev", xcurv_prev), ("xglob_prev", xglob_prev), ("xcurv", xcurv), ("xglob", xglob)):
+        _chk(a, torch.float64, (Bn, 6), name)
+    _chk(u, torch.float64, (Bn, 2), "u")
+    for name, a in (("laps", laps), ("laps_prev", laps_prev), ("n_log", n_log), ("crossed", crossed), ("phase", phase),
+                    ("seed_status", seed_status), ("m_mpc", m_mpc)):
+        _chk(a, torch.int32, (Bn,), name)
+    _chk(log_x, torch.float64, (Bn, P, 6), "log_x")
+    _chk(log_u, torch.float64, (Bn, P, 2), "log_u")
+    if xcurv_prev.data_ptr() == xcurv.data_ptr() or xglob_prev.data_ptr() == xglob.data_ptr():
+        raise ValueError("seed_log_dev: the plant's two state pairs must be different tensors")
+    _call("crx_seed_log_dev", C.c_int(Bn), C.c_int(P), C.c_double(lap_length), _ptr(xcurv_prev), _ptr(xglob_prev), _ptr(xcurv), _ptr(xglob),
+          _ptr(u), _ptr(laps), _ptr(laps_prev), _ptr(log_x), _ptr(log_u), _ptr(n_log), _ptr(crossed), _ptr(phase), _ptr(seed_status),
+          _ptr(m_mpc), _stream())

@@ -1933,6 +1933,38 @@ int crx_game_log_dev(int batch, int n_points, double lap_length, const double* x
     return launched(crx_launch_game(3, gp, (hipStream_t)stream), "game log");
 }
 
+// seed laps (include/crx.h S1-S6): device-pointer entries only, like the rest of the family
+int crx_seed_commit_dev(int N, int batch, const int32_t* phase, const double* vt, const double* eyt, const double* x, const double* U_mpc,
+                        const int32_t* mpc_status, int32_t* seed_status, double* u, void* stream) {
+    if (int rc = ensure_init()) return rc;
+    if (N < 1 || N > CRX_MAX_N || batch < 0) return fail(CRX_ERR_ARG, "bad seed commit dimensions");
+    if (batch == 0) return CRX_OK;
+    if (!phase || !vt || !eyt || !x || !U_mpc || !mpc_status || !seed_status || !u) return fail(CRX_ERR_ARG, "NULL array argument");
+    crx_seed_kparams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.batch = batch; sp.u_stride = 2 * N; sp.phase = (int32_t*)phase; sp.vt = vt; sp.eyt = eyt; sp.x = x; sp.U_mpc = U_mpc;
+    sp.mpc_status = mpc_status; sp.seed_status = seed_status; sp.u = u;
+    return launched(crx_launch_seed(0, sp, (hipStream_t)stream), "seed commit");
+}
+
+int crx_seed_log_dev(int batch, int n_points, double lap_length, const double* xcurv_prev, const double* xglob_prev, double* xcurv,
+                     double* xglob, const double* u, int32_t* laps, int32_t* laps_prev, double* log_x, double* log_u, int32_t* n_log,
+                     int32_t* crossed, int32_t* phase, int32_t* seed_status, int32_t* m_mpc, void* stream) {
+    if (int rc = ensure_init()) return rc;
+    if (batch < 0 || n_points < 2) return fail(CRX_ERR_ARG, "bad seed log dimensions");
+    if (batch == 0) return CRX_OK;
+    if (!xcurv_prev || !xglob_prev || !xcurv || !xglob || !u || !laps || !laps_prev || !log_x || !log_u || !n_log || !crossed || !phase ||
+        !seed_status || !m_mpc)
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    if (xcurv_prev == xcurv || xglob_prev == xglob) return fail(CRX_ERR_ARG, "the plant's two state pairs must be different arrays");
+    crx_seed_kparams sp;
+    memset(&sp, 0, sizeof(sp));
+    sp.batch = batch; sp.n_points = n_points; sp.lap_length = lap_length; sp.xcurv_prev = xcurv_prev; sp.xglob_prev = xglob_prev;
+    sp.xcurv = xcurv; sp.xglob = xglob; sp.u = (double*)u; sp.laps = laps; sp.laps_prev = laps_prev; sp.log_x = log_x; sp.log_u = log_u;
+    sp.n_log = n_log; sp.crossed = crossed; sp.phase = phase; sp.seed_status = seed_status; sp.m_mpc = m_mpc;
+    return launched(crx_launch_seed(1, sp, (hipStream_t)stream), "seed log");
+}
+
 }  // extern "C"
 
 // ---- race statistics: per-car outcomes of every closed loop (crx_race_stats_*_kernel, crx_game.hip) -------------------------------

@@ -3,6 +3,8 @@
 //   crx_game_masks_kernel     which branch a race takes this step, as the masks of the masked launches      utils/base.py:463-467
 //   crx_game_commit_kernel    the applied input and the learning MPC's hand-over of its plan      control/control.py:726-728, utils/base.py:504-515, :546-551
 //   crx_game_log_kernel       the simulator's lap log and the races that completed a lap      utils/base.py:780-819, racing/offboard.py:114-131
+// the seed laps in front of the learning MPC (include/crx.h, "Seed laps" S1-S6):
+//   crx_seed_commit_kernel, crx_seed_log_kernel      each car's PID lap, then its MPC-LTI lap, logged into its own safe set      tests/auto_racing_game_test.py:48-73
 // and what the closed loops are run for (include/crx.h, "Race statistics"):
 //   crx_race_stats_reset_kernel, crx_race_stats_kernel, crx_race_stats_summary_kernel      per-car outcomes, one launch per sample; the batch summary
 //
@@ -80,24 +82,82 @@ __global__ void __launch_bounds__(256) crx_game_commit_kernel(const crx_game_kpa
 }
 
 // after the plant: the lap log the simulator keeps (ModelBase.update_memory: the new state -- the one that crossed the line
-// with its s unwrapped -- and the applied input) and which races have just completed a lap (-> crx_lmpc_addtraj_dev)
+// with its s unwrapped -- and the applied input) and which races have just completed a lap (-> crx_lmpc_addtraj_dev).
+// One car's assignments, shared by crx_game_log_kernel and crx_seed_log_kernel (include/crx.h S5); returns `crossed`
+__device__ __forceinline__ int game_log_car(int b, int P, double lap_length, const double* xcurv, const double* u, const int32_t* laps,
+                                            int32_t* laps_prev, int32_t* crossed, double* log_x, double* log_u, int32_t* n_log) {
+    const int cr = laps[b] > laps_prev[b] ? 1 : 0;
+    laps_prev[b] = laps[b];
+    crossed[b] = cr;
+    const int n = n_log[b];
+    const int ix = n < P - 1 ? n : P - 1;
+    int iu = n - 1; iu = iu < 0 ? 0 : (iu > P - 1 ? P - 1 : iu);
+    const double* x = xcurv + (size_t)6 * b;
+    double* lx = log_x + ((size_t)b * P + ix) * 6;
+    for (int c = 0; c < 6; c++) lx[c] = x[c];
+    lx[4] = x[4] + lap_length * (double)cr;
+    double* lu = log_u + ((size_t)b * P + iu) * 2;
+    lu[0] = u[2 * b]; lu[1] = u[2 * b + 1];
+    n_log[b] = n + 1;
+    return cr;
+}
+
 __global__ void __launch_bounds__(256) crx_game_log_kernel(const crx_game_kparams gp) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= gp.batch) return;
-    const int P = gp.n_points;
-    const int cr = gp.laps[b] > gp.laps_prev[b] ? 1 : 0;
-    gp.laps_prev[b] = gp.laps[b];
-    gp.crossed[b] = cr;
-    const int n = gp.n_log[b];
-    const int ix = n < P - 1 ? n : P - 1;
-    int iu = n - 1; iu = iu < 0 ? 0 : (iu > P - 1 ? P - 1 : iu);
-    const double* x = gp.xcurv + (size_t)6 * b;
-    double* lx = gp.log_x + ((size_t)b * P + ix) * 6;
-    for (int c = 0; c < 6; c++) lx[c] = x[c];
-    lx[4] = x[4] + gp.lap_length * (double)cr;
-    double* lu = gp.log_u + ((size_t)b * P + iu) * 2;
-    lu[0] = gp.u[2 * b]; lu[1] = gp.u[2 * b + 1];
-    gp.n_log[b] = n + 1;
+    game_log_car(b, gp.n_points, gp.lap_length, gp.xcurv, gp.u, gp.laps, gp.laps_prev, gp.crossed, gp.log_x, gp.log_u, gp.n_log);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Seed laps (crx.montecarlo.SeedLaps, include/crx.h S1-S6): every car drives its own PID lap and its own MPC-LTI lap
+// (tests/auto_racing_game_test.py:48-73) and crx_lmpc_addtraj_dev turns both into the car's own safe set.  The cars finish at
+// different steps, so each carries its phase: 0 PID lap, 1 MPC-LTI lap, 2 seeded, 3 failed.  One thread per car; thread b touches
+// car b's elements only.
+// ------------------------------------------------------------------------------------------------
+// after the solver launch, before the plant: the input the car applies in the lap it is in.  The PID law is restated here, not shared with
+// pid_log_kernel (crx_sysid.hip): HIP's __dmul_rn / __dsub_rn are plain operators, so that kernel's law is compiled WITH contraction
+// (one of the two products fuses into the subtraction: a v_fmac_f64) and is up to an ulp from NumPy's; giving it this form would change crx_pid_log_dev's bits
+__global__ void __launch_bounds__(256) crx_seed_commit_kernel(const crx_seed_kparams sp) {
+#pragma clang fp contract(off)   // every operation rounded on its own: tests/seed_model.py reproduces the bits in NumPy
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= sp.batch) return;
+    const int ph = sp.phase[b];
+    double u0 = 0.0, u1 = 0.0;                                       // S3: a seeded or failed car applies nothing
+    if (ph == 0) {                                                   // S1: control.pid (control/control.py:15-25)
+        const double* x = sp.x + (size_t)6 * b;
+        u0 = -0.6 * (x[5] - sp.eyt[b]) - 0.9 * x[3];
+        u1 = 1.5 * (sp.vt[b] - x[0]);
+    } else if (ph == 1) {                                            // S2: u_0 of the MPC-LTI plan; a failed solve is flagged, its last iterate applied
+        u0 = sp.U_mpc[(size_t)b * sp.u_stride]; u1 = sp.U_mpc[(size_t)b * sp.u_stride + 1];
+        if (sp.mpc_status[b] != CRX_CONVERGED) sp.seed_status[b] |= CRX_SEED_MPC_FAILED;
+    }
+    sp.u[2 * b] = u0; sp.u[2 * b + 1] = u1;
+}
+
+// after the plant, before crx_lmpc_addtraj_dev: a seeded car stands where it was handed over, a driving car logs the step as the
+// racing game does and moves on to its next lap when it crossed the line
+__global__ void __launch_bounds__(256) crx_seed_log_kernel(const crx_seed_kparams sp) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= sp.batch) return;
+    int ph = sp.phase[b];
+    if (ph >= 2) {                                                   // S4: frozen
+        for (int c = 0; c < 6; c++) {
+            sp.xcurv[(size_t)6 * b + c] = sp.xcurv_prev[(size_t)6 * b + c];
+            sp.xglob[(size_t)6 * b + c] = sp.xglob_prev[(size_t)6 * b + c];
+        }
+        sp.laps[b] = sp.laps_prev[b];
+        sp.crossed[b] = 0;
+        return;
+    }
+    const int cr = game_log_car(b, sp.n_points, sp.lap_length, sp.xcurv, sp.u, sp.laps, sp.laps_prev, sp.crossed, sp.log_x, sp.log_u, sp.n_log);   // S5
+    if (cr) {                                                        // S6
+        ph += 1;
+    } else if (sp.n_log[b] == sp.n_points) {                         // no row is left for the next state
+        ph = 3;
+        sp.seed_status[b] |= CRX_SEED_LOG_FULL;
+    }
+    sp.phase[b] = ph;
+    sp.m_mpc[b] = ph == 1 ? 1 : 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -290,6 +350,14 @@ hipError_t crx_launch_race_stats(int which, const crx_stats_kparams& sp, hipStre
         case 1: hipLaunchKernelGGL(crx_race_stats_kernel, grid, block, 0, st, sp); break;
         default: hipLaunchKernelGGL(crx_race_stats_summary_kernel, grid, block, 0, st, sp); break;
     }
+    return hipGetLastError();
+}
+
+hipError_t crx_launch_seed(int which, const crx_seed_kparams& sp, hipStream_t st) {
+    if (sp.batch == 0) return hipSuccess;
+    const dim3 grid((unsigned)((sp.batch + 255) / 256)), block(256);
+    if (which == 0) hipLaunchKernelGGL(crx_seed_commit_kernel, grid, block, 0, st, sp);
+    else hipLaunchKernelGGL(crx_seed_log_kernel, grid, block, 0, st, sp);
     return hipGetLastError();
 }
 

@@ -253,6 +253,22 @@ struct crx_game_kparams {
     double *log_x, *log_u;
 };
 hipError_t crx_launch_game(int which, const crx_game_kparams& gp, hipStream_t st);
+// crx_game.hip: seed laps (crx.montecarlo.SeedLaps, include/crx.h S1-S6): each car's PID lap and MPC-LTI lap become its own safe set
+struct crx_seed_kparams {
+    int batch, n_points, u_stride;                     // u_stride: doubles between the plans of two cars in U_mpc (2 N)
+    double lap_length;
+    int32_t *phase, *seed_status, *m_mpc;              // [batch] each
+    // commit
+    const double *vt, *eyt, *x, *U_mpc;                // x [batch][6]: the state the step starts from
+    const int32_t* mpc_status;
+    double* u;                                         // [batch][2]; the log reads it
+    // log
+    const double *xcurv_prev, *xglob_prev;             // what the plant read
+    double *xcurv, *xglob;                             // what the plant wrote
+    int32_t *laps, *laps_prev, *n_log, *crossed;
+    double *log_x, *log_u;
+};
+hipError_t crx_launch_seed(int which, const crx_seed_kparams& sp, hipStream_t st);   // 0 commit, 1 log
 // crx_game.hip: per-car race statistics of every closed loop (crx.montecarlo.RaceStats): reset, one sample, the batch summary
 struct crx_stats_kparams {
     crx_stats_desc d;

@@ -44,7 +44,9 @@
 extern "C" {
 #endif
 
-#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_stats_desc, crx_stats_desc_default, crx_race_stats_reset, crx_race_stats_reset_dev,
+#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_seed_commit_dev, crx_seed_log_dev and CRX_SEED_* (seed laps: every car's own PID lap and
+                          MPC-LTI lap become its own safe set) -- new entry points only.
+                          0.4.0 (additive, same number): crx_stats_desc, crx_stats_desc_default, crx_race_stats_reset, crx_race_stats_reset_dev,
                           crx_race_stats, crx_race_stats_dev, crx_race_stats_summary, crx_race_stats_summary_dev and the CRX_STATS_* layout
                           (per-car race statistics of every closed loop) -- new entry points only.
                           0.4.0 (additive, same number): crx_field_desc, crx_field_desc_default, crx_field_prep, crx_field_prep_dev (field races: every
@@ -1097,6 +1099,48 @@ int crx_game_commit_dev(int N, int Np, int batch, const int32_t* overtake, const
                         double* lin_input, int32_t* step_no, int32_t* addpoint_step, int32_t* old_flag, void* stream);
 int crx_game_log_dev(int batch, int n_points, double lap_length, const double* xcurv, const double* u, const int32_t* laps,
                      int32_t* laps_prev, double* log_x, double* log_u, int32_t* n_log, int32_t* crossed, void* stream);
+
+/*
+ * Seed laps (crx.montecarlo.SeedLaps): the two laps in front of the learning MPC, per car.  The reference's racing game drives lap 0
+ * under PID and lap 1 under MPC-LTI and hands both to LMPCRacingGame.add_trajectory before the first learning-MPC lap
+ * (tests/auto_racing_game_test.py:48-73); the learning MPC's stage models, terminal set and cost-to-go are those two laps.  Here every
+ * car of a batch does that with ITS plant parameters and ITS controller model, so that a fleet of different cars learns from its own
+ * data.  One control step is crx_cbf_solve[_models]_dev with zero obstacle slots (= control.mpc_lti) under active = m_mpc ->
+ * crx_seed_commit_dev -> crx_plant_step_wrap_dev -> crx_seed_log_dev -> crx_lmpc_addtraj_dev(crossed, ...), the last one unchanged: lap 0
+ * becomes safe-set lap 0 (iter 0 -> 1), lap 1 becomes lap 1 (iter -> 2), and it restarts the log from the wrapped state.
+ *
+ * Per-car state, [batch] int32 each, owned by the caller: phase (0 = PID lap, 1 = MPC-LTI lap, 2 = seeded, 3 = failed; start: 0),
+ * seed_status (bit flags CRX_SEED_*; start: 0), m_mpc (the `active` mask of the NEXT solver launch; start: 0).  Thread b touches car b's
+ * elements only; the cars finish at different steps and do not wait for each other.
+ *
+ * crx_seed_commit_dev, after the solver launch and before the plant, writes u [batch][2] from x [batch][6], the state the step starts from:
+ *   S1  phase 0: u = control.pid (control/control.py:15-25): u0 = -0.6 * (ey - eyt) - 0.9 * epsi, u1 = 1.5 * (vt - vx), with vt, eyt [batch]
+ *       per car, every operation rounded on its own as NumPy does (crx_pid_log_dev states the same law but is compiled with
+ *       contraction and can differ from this by an ulp; it is left as it is, for its bits).
+ *   S2  phase 1: u = U_mpc[b][0] (U_mpc [batch][N][2], the solver's plan).  mpc_status[b] != CRX_CONVERGED sets seed_status |=
+ *       CRX_SEED_MPC_FAILED: the reference has no handler there (control/control.py:242, the solver's exception propagates and ends the
+ *       run); a batch cannot raise for one car, so the last iterate is applied and the flag says so.
+ *   S3  phase >= 2: u = (0, 0).
+ * crx_seed_log_dev, after the plant and before crx_lmpc_addtraj_dev, is given both state pairs of the plant's ping-pong: xcurv_prev,
+ * xglob_prev (what the plant read) and xcurv, xglob (what it wrote, which this entry may overwrite), all [batch][6]:
+ *   S4  a car in phase >= 2 at entry is frozen: xcurv[b] <- xcurv_prev[b], xglob[b] <- xglob_prev[b], laps[b] <- laps_prev[b],
+ *       crossed[b] = 0, and nothing else of the car is touched.  (It is stepped from the same state every step, so a car that stands
+ *       next to the line would otherwise "cross" at every step.)  A seeded car therefore stands at its hand-over state: the start state
+ *       of its first learning-MPC lap.
+ *   S5  a car in phase 0 or 1: exactly the assignments of crx_game_log_dev (one device function serves both): crossed[b] = laps[b] >
+ *       laps_prev[b]; laps_prev[b] <- laps[b]; the new state, with s unwrapped by lap_length if it crossed, to log_x[b][min(n_log,
+ *       n_points - 1)]; the applied input to log_u[b][n_log - 1]; n_log += 1 (ModelBase.update_memory, utils/base.py:795-819).
+ *   S6  then the phase: on a crossing, phase += 1 (0 -> 1: racing/offboard.py's one_lap sim ends, the test script changes the
+ *       controller, tests/auto_racing_game_test.py:50-52; 1 -> 2: :58-68).  Otherwise, if n_log == n_points after the append -- no row
+ *       is left for the next state -- phase = 3 and seed_status |= CRX_SEED_LOG_FULL.  Finally m_mpc[b] = (phase == 1).
+ */
+#define CRX_SEED_MPC_FAILED 1   /* S2: a step of the MPC-LTI lap applied an iterate that had not converged */
+#define CRX_SEED_LOG_FULL 2     /* S6: a lap did not reach the line within n_points - 1 steps */
+int crx_seed_commit_dev(int N, int batch, const int32_t* phase, const double* vt, const double* eyt, const double* x, const double* U_mpc,
+                        const int32_t* mpc_status, int32_t* seed_status, double* u, void* stream);
+int crx_seed_log_dev(int batch, int n_points, double lap_length, const double* xcurv_prev, const double* xglob_prev, double* xcurv,
+                     double* xglob, const double* u, int32_t* laps, int32_t* laps_prev, double* log_x, double* log_u, int32_t* n_log,
+                     int32_t* crossed, int32_t* phase, int32_t* seed_status, int32_t* m_mpc, void* stream);
 
 /*
  * Race statistics (crx.montecarlo.RaceStats): what a closed-loop Monte-Carlo is run for -- contacts, cars that left the track, lap

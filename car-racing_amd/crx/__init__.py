@@ -114,5 +114,10 @@ def field_prep(desc, track, xcurv, car_dims=None):
     return binding().field_prep(desc, track, xcurv, car_dims)
 
 
+def field_traffic(desc, track, xcurv):
+    """Field-game traffic arrays (include/crx.h "Field games") on host arrays: see abi.Binding.field_traffic."""
+    return binding().field_traffic(desc, track, xcurv)
+
+
 def plant_step(desc, track, xglob, xcurv, u, params=None):
     return binding().plant_step(desc, track, xglob, xcurv, u, params=params)

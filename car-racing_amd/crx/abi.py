@@ -490,7 +490,7 @@ class Binding:
         self.lib, self.prefix = lib, prefix
         for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve", "ilqr_solve",
                      "ilqr_solve_models", "lqr_design", "sysid_fit", "cbf_solve_models", "planner_solve_models", "planner_plan",
-                     "planner_plan_models", "path_prep", "path_plan", "plant_step_params", "field_prep"):
+                     "planner_plan_models", "path_prep", "path_plan", "plant_step_params", "field_prep", "field_traffic"):
             if hasattr(lib, prefix + name):
                 getattr(lib, prefix + name).restype = C.c_int
         if hasattr(lib, prefix + "race_stats_dev"):
@@ -841,6 +841,23 @@ class Binding:
         self._call("field_prep", C.byref(desc), C.c_int(R), _p(track), _p(xcurv), _p(car_dims) if car_dims is not None else None,
                    *[_p(out[k]) for k in ("pred_s", "pred_ey", "obs_s", "obs_ey", "lap_off", "n_obs")],
                    _p(out["obs_dims"]) if car_dims is not None else None, _p(out["clear"]) if clear else None)
+        return out
+
+    def field_traffic(self, desc, track, xcurv):
+        """crx_field_traffic (include/crx.h "Field games", F1-F3, F6, G1-G3): the racing game's traffic arrays when every car of a race plays
+        it.  track (n_seg,6); xcurv (R,C,6) or (R*C,6).  Returns pred_s_car, pred_ey_car (R,C,N+1): every car's zero-input roll-out; veh_xcurv
+        (R*C,V,6), pred_s, pred_ey (R*C,V,N+1), n_all (R*C,) with V = C - 1: per ego the other cars of its race in car order, the inputs of
+        planner_scene for R*C scenarios."""
+        N1, Cn = desc.N + 1, desc.n_cars
+        V = Cn - 1
+        track = _in(track, _D, (desc.n_seg, 6))
+        xcurv = np.ascontiguousarray(xcurv, dtype=_D)
+        R = xcurv.size // (6 * Cn)
+        xcurv = _in(xcurv.reshape(R, Cn, 6), _D, (R, Cn, 6))
+        out = dict(pred_s_car=np.zeros((R, Cn, N1)), pred_ey_car=np.zeros((R, Cn, N1)), veh_xcurv=np.zeros((R * Cn, V, 6)),
+                   pred_s=np.zeros((R * Cn, V, N1)), pred_ey=np.zeros((R * Cn, V, N1)), n_all=np.zeros(R * Cn, dtype=_I))
+        self._call("field_traffic", C.byref(desc), C.c_int(R), _p(track), _p(xcurv),
+                   *[_p(out[k]) for k in ("pred_s_car", "pred_ey_car", "veh_xcurv", "pred_s", "pred_ey", "n_all")])
         return out
 
     def path_solve(self, desc, opt, bez, lb, ub, e0, eN):

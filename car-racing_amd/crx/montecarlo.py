@@ -18,6 +18,10 @@ SeedLaps is what comes before the learning MPC: every car's own PID lap and MPC-
 its lmpc_inputs() are the constructor arguments of LmpcLaps / GameLaps as device tensors (PidLaps -> identify -> SeedLaps -> LmpcLaps |
 GameLaps runs a fleet from standstill to racing without a host array in between).
 
+FieldGames is GameLaps for a field: every car of a race plays the racing game and is a vehicle of the others (its first launch is
+crx_field_traffic_dev); grid_start() is what puts several learning-MPC cars on one track: PidLaps -> identify -> SeedLaps -> grid_start ->
+FieldGames.
+
 What the loops are run for -- contacts, cars off the track, lap times, overtakes -- is RaceStats (end of this module): per-car
 statistics on the device, one launch per sample, attached to any loop through the loop's stats_inputs().
 """
@@ -693,13 +697,13 @@ class GameLaps:
         self.t = 0.0
 
     def step(self):
-        """One control step of every race, fourteen libcrx launches: game_traffic_dev, planner_scene_dev, game_masks_dev; the
+        """One control step of every race, fourteen libcrx launches: game_traffic_dev (_traffic()), planner_scene_dev, game_masks_dev; the
         overtake branch planner_prep_dev, planner_plan_dev (planner = "path": path_plan_dev for the two), track_prep_dev,
         cbf_solve_dev; the learning-MPC branch lmpc_prep_dev, lmpc_solve_dev; game_commit_dev, lmpc_addpoint_dev,
         plant_step_wrap_dev, game_log_dev, lmpc_addtraj_dev (the lap hand-over).  lm.k stays 0: the game plans from its own
         linearisation points, which the commit keeps."""
         lm, L, N = self.lm, self.L, self.lm.N
-        torch_api.game_traffic_dev(self.Np, L, self.t, lm.timestep, self.s0, self.v, self.ey, self.veh, self.pred_s, self.pred_e)
+        self._traffic()
         torch_api.planner_scene_dev(self.scene, lm.xc, self.n_all, self.veh, self.pred_s, self.pred_e, ws=self.sws)
         torch_api.game_masks_dev(self.sws.n_veh, self.m_ot, self.m_lm, overflow=self.sws.overflow, overflow_seen=self.overflow_seen)
         self.overtake = self.m_ot                                  # int32 mask; bool(overtake[b]) = race b is in the overtake branch
@@ -709,6 +713,11 @@ class GameLaps:
         lm._apply(self.u, 2, lm.addpoint_step)
         self.t += lm.timestep
         lm.log_and_handover(self.u)
+
+    def _traffic(self):
+        """The step's first launch: the other vehicles' states veh and predictions pred_s, pred_e [B,VA,..] that the scene reads with n_all --
+        here the scripted cars at the game's clock (game_traffic_dev).  FieldGames puts the other driven cars of the race there."""
+        torch_api.game_traffic_dev(self.Np, self.L, self.t, self.lm.timestep, self.s0, self.v, self.ey, self.veh, self.pred_s, self.pred_e)
 
     def stats_inputs(self):
         """As _Plant.stats_inputs, answered from `lm` (which holds the plant): the scripted cars at the game's clock, and the branch
@@ -804,6 +813,139 @@ def game_laps(track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u
                         before=("cars_s",))    # where the scripted cars are when the step plans
     return dict(logs, laps=r.lm.laps.cpu().numpy(), traj_status=r.lm.traj_status.cpu().numpy(),
                 scene_overflow=r.overflow_seen.cpu().numpy())
+
+
+class FieldGames(GameLaps):
+    """R races of C cars that ALL play the racing game: every car is the ego of its own LMPCRacingGame.calc_input -- its own safe set, its
+    own learning MPC, its own overtake planner and tracking NLP -- and a vehicle of the C - 1 others, which it sees as the reference's
+    planner sees a driven opponent: the current state and the zero-input roll-out get_trajectory_nsteps(N + 1)
+    (planning/overtake_traj_planner.py:77-85, racing/offboard.py:51-94).  The loop is GameLaps with batch R*C (race-major, car-minor) whose
+    first launch is crx_field_traffic_dev (include/crx.h "Field games", F1-F3, F6, G1-G3) where GameLaps has crx_game_traffic_dev; every
+    launch after it is GameLaps', call for call.  All cars of a step see the states at the start of the step (F1).
+
+    The per-car learning-MPC inputs [R*C, ...] are those of LmpcLaps / GameLaps, host arrays or device tensors.  A learning-MPC lap begins
+    at the line and every seeded car stands there, so a field is built from grid_start(SeedLaps.lmpc_inputs(), k, track), which also
+    returns step_no, n_log, log_x, log_u, u_old, u_prev: the bookkeeping of a car that is k steps into its lap; they are applied to `lm`
+    after it is built (None: the lap has just begun, as LmpcLaps starts).  FieldGames(..., n_cars, **grid_start(...)) takes them all.
+    models = (A [R*C,6,6], B [R*C,6,2]), plant_params [R*C,10], planner = "traj" | "path": as GameLaps."""
+
+    def __init__(self, track_table, lap_length, track_width, A, B, opt_xcurv, n_cars, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0,
+                 lin_points, lin_input, step_no=None, n_log=None, log_x=None, log_u=None, u_old=None, u_prev=None, N=12, N_plan=10,
+                 timestep=0.1, device=None, noise_seed=None, models=None, planner="traj", alpha=0.98, plant_params=None):
+        Cn = int(n_cars)
+        if not 1 <= Cn <= abi.CRX_MAX_VEH + 1:
+            raise ValueError("1 .. %d cars per race" % (abi.CRX_MAX_VEH + 1))
+        Bn = int(xcurv0.shape[0])
+        if Bn % Cn:
+            raise ValueError("xcurv0: %d cars do not make races of %d" % (Bn, Cn))
+        none = np.zeros((Bn, max(Cn - 1, 1)))      # no scripted car: the slots of the scene are the other cars of the race (one idle slot with C = 1)
+        super().__init__(track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points,
+                         lin_input, none, none, none, N=N, N_plan=N_plan, timestep=timestep, device=device, noise_seed=noise_seed, models=models,
+                         planner=planner, alpha=alpha, plant_params=plant_params)
+        del self.s0, self.v, self.ey
+        lm = self.lm
+        self.n_cars, self.n_races = Cn, Bn // Cn
+        self.fdesc = abi.field_desc(N_plan, Cn, lm.tab.shape[0], lap_length, dt=timestep)
+        self.fws = torch_api.FieldTrafficWorkspace(self.fdesc, self.n_races, lm.device)
+        # what the scene and the path planner read of the other vehicles is what the traffic launch writes
+        self.veh, self.pred_s, self.pred_e, self.n_all = self.fws.veh_xcurv, self.fws.pred_s, self.fws.pred_ey, self.fws.n_all
+        # the grid fields: a car that is k steps into its lap (grid_start)
+        for dst, src, dtype in ((lm.step_no, step_no, torch.int32), (lm.n_log, n_log, torch.int32), (lm.log_x, log_x, torch.float64),
+                                (lm.log_u, log_u, torch.float64), (lm.u_old, u_old, torch.float64), (lm.u_prev, u_prev, torch.float64)):
+            if src is not None:
+                dst.copy_(_dev(src, lm.device, dtype).reshape(dst.shape))
+
+    def _traffic(self):
+        """field_traffic_dev: every car's roll-out, and per ego the other cars of its race as the scene's vehicles."""
+        torch_api.field_traffic_dev(self.fdesc, self.lm.tab, self.lm.xc, self.fws)
+
+    def stats_inputs(self):
+        """The field form: the opponents of a car are the other cars of its race, CarParam's dimensions for every pair, and the branch
+        mask of the last step as the flag."""
+        return self.lm.stats_inputs(n_cars=self.n_cars, l_sum=0.4, w_sum=0.2, flag=self.m_ot)
+
+
+def field_games(track_table, lap_length, track_width, A, B, opt_xcurv, n_cars, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points,
+                lin_input, steps, device=None, noise_seed=None, models=None, planner="traj", alpha=0.98, plant_params=None, **grid):
+    """Run `steps` control steps of R races of n_cars cars that all play the racing game (FieldGames; **grid: the grid fields of
+    grid_start).  Host logs: xcurv [steps+1, R*C, 6], u [steps, R*C, 2], overtake [steps, R*C] (which branch), flag [steps, R*C] (direction
+    flag, -1 in the LMPC branch), laps [R*C], traj_status [R*C]."""
+    r = FieldGames(track_table, lap_length, track_width, A, B, opt_xcurv, n_cars, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points,
+                   lin_input, device=device, noise_seed=noise_seed, models=models, planner=planner, alpha=alpha, plant_params=plant_params, **grid)
+    logs = _run_and_log(r.step, steps, 1, dict(xcurv=lambda: r.lm.xc, u=lambda: r.u, overtake=lambda: r.overtake.bool(),
+                                               flag=lambda: r.old_flag))
+    return dict(logs, laps=r.lm.laps.cpu().numpy(), traj_status=r.lm.traj_status.cpu().numpy())
+
+
+def grid_start(inputs, k, track):
+    """Several learning-MPC cars on one track.  A learning-MPC lap must begin at the line (the lap log, add_point's row index, time_ss and
+    Qfun all count from the crossing) and every seeded car stands there; grid_start puts car b where it was k[b] steps into its OWN last
+    safe-set lap, j = it[b] - 1, with every piece of per-car bookkeeping as if it had just driven those k[b] steps again and reproduced
+    that lap: the arrays equal, bit for bit, what game_commit_dev (with the plan X[m] = ss[b,j,i+m], U[m] = us[b,j,i+m] at step i),
+    lmpc_addpoint_dev and game_log_dev (with the new state ss[b,j,i+1]) leave behind after k[b] steps from ss[b,j,0]
+    (tests/test_gpu_field_game.py replays them).  Cars of a race get different k and so stand apart.
+
+    inputs: the dict of SeedLaps.lmpc_inputs(), tensors or host arrays; k [B] integers, 0 <= k[b] <= time_ss[b,j] - N - 1; track: the
+    mirror's ClosedTrack (lap_length, get_global_position, get_orientation).  Set-up work, torch index operations on the inputs' device and
+    one host pass for the global poses; no kernel.  Returns the inputs' names plus step_no, n_log, log_x, log_u, u_old, u_prev -- the
+    arguments of FieldGames.  For car b with k = k[b] > 0 (a car with k = 0 keeps every input and the fields of a lap just begun):
+        xcurv0 = ss[b,j,k];  xglob0: velocities copied, pose from the track at (s, ey, epsi)
+        lin_points[m] = ss[b,j,k-1+min(m+1,N)], lin_input[m] = us[b,j,k-1+min(m+1,N-1)]   (the plan shifted by a stage, its last one repeated)
+        step_no = k, n_log = k + 1, log_x[:k+1] = ss[b,j,:k+1], log_u[:k] = us[b,j,:k], u_old = us[b,j,k-1], u_prev = us[b,j,k-2] (zero for k = 1)
+        for i < k, row time_ss[b,j] + i + 1 of lap j (while below n_points): ss[b,j,i] + (0,0,0,0,L,0) and us[b,j,i]   (add_point)"""
+    t = {name: (a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a))) for name, a in inputs.items()}
+    ss, us = t["ss_xcurv"].to(torch.float64), t["u_ss"].to(torch.float64)
+    dev = ss.device
+    Bn, _, P, _ = ss.shape
+    N = t["lin_input"].shape[1]
+    ar = torch.arange(Bn, device=dev)
+    k = torch.as_tensor(np.asarray(k.cpu() if torch.is_tensor(k) else k), dtype=torch.int64, device=dev).reshape(-1)
+    j = t["it"].to(torch.int64) - 1
+    if k.shape[0] != Bn or bool((j < 0).any()) or bool((j >= ss.shape[1]).any()):
+        raise ValueError("grid_start: one k per car and at least one safe-set lap per car (it >= 1)")
+    T = t["time_ss"].to(torch.int64)[ar, j]
+    if bool(((k < 0) | (k > T - N - 1)).any()):
+        raise ValueError("grid_start: 0 <= k[b] <= time_ss[b, it[b]-1] - N - 1 = %s, got %s" % ((T - N - 1).tolist(), k.tolist()))
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    xcurv0 = t["xcurv0"].to(torch.float64)
+    log_x, log_u = torch.zeros((Bn, P, 6), **f64), torch.zeros((Bn, P, 2), **f64)
+    log_x[:, 0] = xcurv0
+    out = dict(t, step_no=torch.zeros(Bn, **i32), n_log=torch.ones(Bn, **i32), log_x=log_x, log_u=log_u, u_old=torch.zeros((Bn, 2), **f64),
+               u_prev=torch.zeros((Bn, 2), **f64))
+    moved = k > 0
+    if not bool(moved.any()):
+        return out
+    lapx, lapu = ss[ar, j], us[ar, j]                                      # [B,P,6], [B,P,2]: every car's lap j
+    m1, m2 = moved[:, None], moved[:, None, None]
+    out["xcurv0"] = torch.where(m1, lapx[ar, k], xcurv0)
+    rows_x = (k - 1)[:, None] + torch.clamp(torch.arange(N + 1, device=dev) + 1, max=N)[None, :]
+    rows_u = (k - 1)[:, None] + torch.clamp(torch.arange(N, device=dev) + 1, max=N - 1)[None, :]
+    out["lin_points"] = torch.where(m2, lapx[ar[:, None], rows_x.clamp(min=0)], t["lin_points"].to(torch.float64))
+    out["lin_input"] = torch.where(m2, lapu[ar[:, None], rows_u.clamp(min=0)], t["lin_input"].to(torch.float64))
+    out["step_no"], out["n_log"] = k.to(torch.int32), (k + 1).to(torch.int32)
+    row = torch.arange(P, device=dev)[None, :]
+    out["log_x"] = torch.where(m2 & (row <= k[:, None])[:, :, None], lapx, log_x)
+    out["log_u"] = torch.where((row < k[:, None])[:, :, None], lapu, log_u)
+    out["u_old"] = torch.where(k[:, None] >= 1, lapu[ar, (k - 1).clamp(min=0)], out["u_old"])
+    out["u_prev"] = torch.where(k[:, None] >= 2, lapu[ar, (k - 2).clamp(min=0)], out["u_prev"])
+    # the rows add_point would have written (crx_lmpc_addpoint_dev: row time_ss + step + 1 of lap j, dropped at n_points)
+    i = torch.arange(int(k.max()), device=dev)[None, :]
+    b_idx, i_idx = torch.nonzero((i < k[:, None]) & (T[:, None] + i + 1 < P), as_tuple=True)
+    off = torch.zeros(6, **f64)
+    off[4] = float(track.lap_length)
+    ss2, us2 = ss.clone(), us.clone()
+    ss2[b_idx, j[b_idx], T[b_idx] + i_idx + 1] = lapx[b_idx, i_idx] + off
+    us2[b_idx, j[b_idx], T[b_idx] + i_idx + 1] = lapu[b_idx, i_idx]
+    out["ss_xcurv"], out["u_ss"] = ss2, us2
+    # the global pose that goes with the curvilinear state: the host's one pass
+    xc = out["xcurv0"].cpu().numpy()
+    xg = np.array(t["xglob0"].cpu().numpy(), dtype=float)
+    for b in np.nonzero(moved.cpu().numpy())[0]:
+        xg[b, 0:3] = xc[b, 0:3]
+        xg[b, 3] = track.get_orientation(xc[b, 4], xc[b, 5]) + xc[b, 3]
+        xg[b, 4], xg[b, 5] = track.get_global_position(xc[b, 4], xc[b, 5])
+    out["xglob0"] = torch.as_tensor(xg, **f64)
+    return out
 
 
 class PidLaps(_Plant):

@@ -561,6 +561,41 @@ def field_prep_dev(desc, track, xcurv, ws, car_dims=None):
     return ws
 
 
+class FieldTrafficWorkspace:
+    """Outputs of field_traffic_dev for n_races races of desc.n_cars cars: every car's roll-out pred_s_car, pred_ey_car [R,C,N+1], and per
+    ego the inputs of planner_scene_dev for the R*C scenarios (race-major, car-minor): veh_xcurv [R*C,V,6], pred_s, pred_ey [R*C,V,N+1],
+    n_all [R*C] with V = C - 1.  With one car per race the per-ego arrays hold nothing; they are allocated with ONE zero slot (the kernel
+    never writes it) so that a scene launch of n_all_max = 1 has arrays to take, and n_all is 0.  n_slots = max(V, 1)."""
+
+    def __init__(self, desc, n_races, device):
+        N1, Cn = desc.N + 1, desc.n_cars
+        Bn, S = n_races * Cn, max(Cn - 1, 1)
+        f64 = dict(dtype=torch.float64, device=device)
+        self.n_races, self.n_slots = n_races, S
+        self.pred_s_car = torch.zeros((n_races, Cn, N1), **f64)
+        self.pred_ey_car = torch.zeros((n_races, Cn, N1), **f64)
+        self.veh_xcurv = torch.zeros((Bn, S, 6), **f64)
+        self.pred_s = torch.zeros((Bn, S, N1), **f64)
+        self.pred_ey = torch.zeros((Bn, S, N1), **f64)
+        self.n_all = torch.zeros(Bn, dtype=torch.int32, device=device)
+
+
+def field_traffic_dev(desc, track, xcurv, ws):
+    """crx_field_traffic_dev (include/crx.h "Field games", F1-F3, F6, G1-G3): xcurv [R*C,6] (race-major, car-minor), track [n_seg,6].
+    Writes ws (a FieldTrafficWorkspace) and returns it."""
+    R, Cn, N1 = ws.n_races, desc.n_cars, desc.N + 1
+    Bn, S = R * Cn, max(Cn - 1, 1)
+    _chk(track, torch.float64, (desc.n_seg, 6), "track")
+    _chk(xcurv, torch.float64, (Bn, 6), "xcurv")
+    for name, shape in (("pred_s_car", (R, Cn, N1)), ("pred_ey_car", (R, Cn, N1)), ("veh_xcurv", (Bn, S, 6)), ("pred_s", (Bn, S, N1)),
+                        ("pred_ey", (Bn, S, N1))):
+        _chk(getattr(ws, name), torch.float64, shape, "ws." + name)
+    _chk(ws.n_all, torch.int32, (Bn,), "ws.n_all")
+    _call("crx_field_traffic_dev", C.byref(desc), C.c_int(R), _ptr(track), _ptr(xcurv), _ptr(ws.pred_s_car), _ptr(ws.pred_ey_car),
+          _ptr(ws.veh_xcurv), _ptr(ws.pred_s), _ptr(ws.pred_ey), _ptr(ws.n_all), _stream())
+    return ws
+
+
 class RaceStatsWorkspace:
     """State of race_stats_dev for `batch` cars (include/crx.h "Race statistics"): stat_i [STATS_NI, batch] int32 and stat_d
     [STATS_ND + n_opp_max, batch] float64, field-major, and every field as a named view of them: n_samples, nonfinite_step, off_step,

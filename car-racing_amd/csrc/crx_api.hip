@@ -1055,10 +1055,8 @@ void crx_field_desc_default(crx_field_desc* d, int N, int n_cars, int n_seg, dou
     d->lap_length = lap_length; d->dt = 0.1; d->safety_time = 2.0; d->l_sum = 0.4; d->w_sum = 0.2;
 }
 
-// Arguments alone, before the library's state is looked at (the answer is the same with and without a device).  host_dims: the
-// [n_races][n_cars][2] rows of the host-pointer entry (NULL: none, or on the device where they cannot be read)
-static int check_field(crx_field_kparams& fp, const crx_field_desc* d, int n_races, arr track, arr xcurv, arr car_dims, arr pred_s, arr pred_ey,
-                       arr obs_s, arr obs_ey, arr lap_off, arr n_obs, arr obs_dims, const double* host_dims = nullptr) {
+// The descriptor and the race count of both field entry families (crx_field_prep*, crx_field_traffic*)
+static int check_field_desc(const crx_field_desc* d, int n_races) {
     auto positive = [](double v) { return v > 0.0 && isfinite(v); };
     if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
     if (d->N < 1 || d->N > CRX_MAX_N) return fail(CRX_ERR_ARG, "N=%d outside [1,%d]", d->N, CRX_MAX_N);
@@ -1068,6 +1066,15 @@ static int check_field(crx_field_kparams& fp, const crx_field_desc* d, int n_rac
     if (!positive(d->lap_length) || !positive(d->dt) || !positive(d->l_sum) || !positive(d->w_sum))
         return fail(CRX_ERR_ARG, "lap_length, dt, l_sum and w_sum must be positive and finite");
     if (n_races < 0) return fail(CRX_ERR_ARG, "n_races < 0");
+    return 0;
+}
+
+// Arguments alone, before the library's state is looked at (the answer is the same with and without a device).  host_dims: the
+// [n_races][n_cars][2] rows of the host-pointer entry (NULL: none, or on the device where they cannot be read)
+static int check_field(crx_field_kparams& fp, const crx_field_desc* d, int n_races, arr track, arr xcurv, arr car_dims, arr pred_s, arr pred_ey,
+                       arr obs_s, arr obs_ey, arr lap_off, arr n_obs, arr obs_dims, const double* host_dims = nullptr) {
+    auto positive = [](double v) { return v > 0.0 && isfinite(v); };
+    if (int rc = check_field_desc(d, n_races)) return rc;
     if (d->n_cars > 1 && !car_dims != !obs_dims)   // (one car: obs_dims holds nothing, like the other obs_* arrays)
         return fail(CRX_ERR_ARG, "car_dims and obs_dims go together: both or neither (%s is NULL)", car_dims ? "obs_dims" : "car_dims");
     if (n_races > 0 && (any_null(track, xcurv, pred_s, pred_ey, n_obs) || (d->n_cars > 1 && any_null(obs_s, obs_ey, lap_off))))
@@ -1112,6 +1119,48 @@ int crx_field_prep(const crx_field_desc* d, int n_races, const double* track, co
     if (int rc = sg.up(g_stream)) return rc;
     if (int rc = crx_field_prep_dev(d, n_races, sg[dtr], sg[dx], sg[dcd], sg[dps], sg[dpe], sg[dos], sg[doe], sg[dlo], sg[dno], sg[dod], sg[dcl],
                                     g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
+// ---- field games: the racing game's traffic arrays of a field (crx_field_traffic_kernel, crx_prep.hip) ------------------------------------
+static_assert(CRX_MAX_VEH == CRX_MAX_OBS, "check_field_desc bounds n_cars by CRX_MAX_OBS + 1; the scene takes CRX_MAX_VEH vehicles");
+static int check_field_traffic(crx_field_traffic_kparams& tp, const crx_field_desc* d, int n_races, arr track, arr xcurv, arr pred_s_car,
+                               arr pred_ey_car, arr veh_xcurv, arr pred_s, arr pred_ey, arr n_all) {
+    if (int rc = check_field_desc(d, n_races)) return rc;
+    if (n_races > 0 && (any_null(track, xcurv, pred_s_car, pred_ey_car, n_all) || (d->n_cars > 1 && any_null(veh_xcurv, pred_s, pred_ey))))
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    memset(&tp, 0, sizeof(tp));
+    tp.d = *d; tp.n_races = n_races;
+    return 0;
+}
+
+int crx_field_traffic_dev(const crx_field_desc* d, int n_races, const double* track, const double* xcurv, double* pred_s_car,
+                          double* pred_ey_car, double* veh_xcurv, double* pred_s, double* pred_ey, int32_t* n_all, void* stream) {
+    crx_field_traffic_kparams tp;
+    if (int rc = check_field_traffic(tp, d, n_races, track, xcurv, pred_s_car, pred_ey_car, veh_xcurv, pred_s, pred_ey, n_all)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (n_races == 0) return CRX_OK;
+    tp.track = track; tp.xcurv = xcurv; tp.pred_s_car = pred_s_car; tp.pred_ey_car = pred_ey_car;
+    tp.veh_xcurv = veh_xcurv; tp.pred_s = pred_s; tp.pred_ey = pred_ey; tp.n_all = n_all;
+    return launched(crx_launch_field_traffic(tp, (hipStream_t)stream), "field traffic");
+}
+
+int crx_field_traffic(const crx_field_desc* d, int n_races, const double* track, const double* xcurv, double* pred_s_car, double* pred_ey_car,
+                      double* veh_xcurv, double* pred_s, double* pred_ey, int32_t* n_all) {
+    crx_field_traffic_kparams chk;
+    if (int rc = check_field_traffic(chk, d, n_races, track, xcurv, pred_s_car, pred_ey_car, veh_xcurv, pred_s, pred_ey, n_all)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (n_races == 0) return CRX_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    const size_t RC = (size_t)n_races * d->n_cars, V = (size_t)d->n_cars - 1, N1 = (size_t)d->N + 1;
+    Stage sg;
+    auto dtr = sg.in(track, (size_t)d->n_seg * 6); auto dx = sg.in(xcurv, RC * 6);
+    auto dpsc = sg.out(pred_s_car, RC * N1); auto dpec = sg.out(pred_ey_car, RC * N1);
+    auto dvx = sg.out(veh_xcurv, RC * V * 6); auto dps = sg.out(pred_s, RC * V * N1); auto dpe = sg.out(pred_ey, RC * V * N1);
+    auto dna = sg.out(n_all, RC);
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_field_traffic_dev(d, n_races, sg[dtr], sg[dx], sg[dpsc], sg[dpec], sg[dvx], sg[dps], sg[dpe], sg[dna], g_stream)) return rc;
     return sg.down(g_stream);
 }
 

@@ -127,6 +127,16 @@ struct crx_field_kparams {
     double *obs_dims, *clear;                 // obs_dims: written iff car_dims; clear: optional
 };
 
+// crx_field_traffic_kernel (crx_prep.hip): predictions of every car of every race and, per ego, the other cars of its race as the scene's inputs
+struct crx_field_traffic_kparams {
+    crx_field_desc d;                          // safety_time, degree, l_sum, w_sum are not read
+    int n_races;
+    const double *track, *xcurv;
+    double *pred_s_car, *pred_ey_car;          // [n_races][n_cars][N+1]
+    double *veh_xcurv, *pred_s, *pred_ey;      // [n_races * n_cars][n_cars - 1][6], [..][n_cars - 1][N+1] twice; hold nothing (may be NULL) with one car
+    int32_t* n_all;                            // [n_races * n_cars] = n_cars - 1
+};
+
 // ---- crx_path.hip: crx_path_kernel, the path QP (crx_path_qp.h) without a mask ----
 struct crx_path_kparams {
     int N, batch;
@@ -160,7 +170,7 @@ struct crx_pathplan_kparams {
 };
 
 // ---- crx_plant.hip: the two inclusions of crx_plant_step.h ----
-#define CRX_PLANT_MAX_SEG 64   // rows of a track's segment table a kernel keeps in LDS (the plant, crx_field_prep_kernel)
+#define CRX_PLANT_MAX_SEG 64   // rows of a track's segment table a kernel keeps in LDS (the plant, crx_field_prep_kernel, crx_field_traffic_kernel)
 struct crx_plant_kparams {
     crx_plant_desc d;
     int batch, u_stride, wrap;
@@ -208,6 +218,7 @@ hipError_t crx_launch_scene(const crx_scene_kparams& sp, hipStream_t st);
 hipError_t crx_launch_trackprep(const crx_trackprep_kparams& tp, hipStream_t st);
 hipError_t crx_launch_cbfprep(const crx_cbfprep_kparams& cp, hipStream_t st);
 hipError_t crx_launch_field_prep(const crx_field_kparams& fp, hipStream_t st);
+hipError_t crx_launch_field_traffic(const crx_field_traffic_kparams& tp, hipStream_t st);
 // crx_plant.hip
 hipError_t crx_launch_plant(const crx_plant_kparams& pk, hipStream_t st);
 hipError_t crx_launch_plant_cars(const crx_plant_kparams_cars& pk, hipStream_t st);

@@ -12,6 +12,8 @@
 //   crx_cbfprep_kernel     obstacle arrays of control.mpccbf for scripted cars.  control/control.py:500, :519
 //   crx_field_prep_kernel  the same arrays for a field of driven cars: every car of a race predicted by the zero-input roll-out of
 //                          racing/offboard.py:51-94, every car the ego of its own NLP.  control/control.py:499-540 (realtime_flag == True)
+//   crx_field_traffic_kernel  the racing game's traffic arrays for such a field: the same roll-out, then per ego the other cars of its race
+//                          as crx_scene_kernel takes them.  planning/overtake_traj_planner.py:77-85
 // The comment in front of each kernel has the rest.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -277,27 +279,8 @@ __global__ void __launch_bounds__(256) crx_field_prep_kernel(const crx_field_kpa
     const bool live = rl < per_block && r < fp.n_races;
     const size_t rc = (size_t)r * C + c;   // this thread's car = problem rc of the solver launch (race-major, car-minor)
     const double L = d.lap_length, dt = d.dt;
-    if (live) {
-        const double* x = fp.xcurv + 6 * rc;
-        const double vx = x[0], vy = x[1], wz = x[2];
-        double epsi = x[3], s = x[4], ey = x[5];
-        double* ps = fp.pred_s + rc * N1;
-        double* pe = fp.pred_ey + rc * N1;
-        for (int j = 0; j < N1; j++) {
-            // curvature at s (wrapped into one lap), first segment with lo <= s <= hi (quirk F6)
-            const double sw = wrap_below(wrap_above(s, L), L);
-            double curv = 0.0;
-            for (int i = 0; i < d.n_seg; i++)
-                if (sw >= seg_lo[i] && sw <= seg_hi[i]) { curv = seg_cv[i]; break; }
-            const double ce = cos(epsi), se = sin(epsi);
-            const double v_long = (vx * ce - vy * se) / (1 - curv * ey);
-            const double epsi_n = epsi + dt * (wz - v_long * curv);
-            const double s_n = s + dt * v_long;
-            const double ey_n = ey + dt * (vx * se + vy * ce);
-            epsi = epsi_n; s = wrap_above(s_n, L); ey = ey_n;   // the roll-out continues from the wrapped value (quirk F3)
-            ps[j] = s; pe[j] = ey;
-        }
-    }
+    if (live)   // phase 1, written once: zero_input_rollout (crx_num.h)
+        zero_input_rollout(fp.xcurv + 6 * rc, seg_lo, seg_hi, seg_cv, d.n_seg, L, dt, N1, fp.pred_s + rc * N1, fp.pred_ey + rc * N1);
     __syncthreads();   // the predictions of this block's races are in memory; workgroup scope is all phase 2 needs
     if (!live) return;
     const double* xe = fp.xcurv + 6 * rc;
@@ -350,6 +333,58 @@ __global__ void __launch_bounds__(256) crx_field_prep_kernel(const crx_field_kpa
     if (fp.clear) fp.clear[rc] = clr;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The racing game's traffic arrays for a FIELD (see crx_field_traffic_dev in include/crx.h, quirks F1-F3, F6, G1-G3): what
+// crx_game_traffic_kernel makes of scripted cars, made of the other DRIVEN cars of the race -- the inputs of crx_scene_kernel for the
+// n_races * C scenarios with n_all_max = n_veh_max = V = C - 1.  The block shape is crx_field_prep_kernel's: one thread per (race, car), a
+// workgroup owns 256 / C whole races, the threads past the last whole race and the races past n_races only take the barrier.
+//   phase 1  zero_input_rollout (crx_num.h): pred_s_car, pred_ey_car [R][C][N+1], the bits of crx_field_prep_kernel's pred_s, pred_ey
+//   phase 2  overtake_traj_planner.py:77-85 (the `else` branch: a driven opponent's get_trajectory_nsteps(N + 1)) per ego, the other
+//            cars in car order (F5): slot v of ego c is car o = v + (v >= c).  Pure copies.  The [V][6] and [V][N+1] rows of one ego are
+//            contiguous and consecutive threads are consecutive egos, so what a block writes to each array is ONE contiguous range; its
+//            live threads stride over that range element by element (a wave stores 512 consecutive bytes; its loads are consecutive
+//            inside a row) instead of each walking its own ego's rows at a stride of V (N + 1) doubles.  The trip counts come from the
+//            descriptor and n_races: no loop runs on device data.
+// A car with a non-finite state has non-finite rows and a non-finite veh_xcurv row in the other cars' arrays, as bits; nothing here
+// computes on them.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) crx_field_traffic_kernel(const crx_field_traffic_kparams tp) {
+    __shared__ double seg_lo[CRX_PLANT_MAX_SEG], seg_hi[CRX_PLANT_MAX_SEG], seg_cv[CRX_PLANT_MAX_SEG];
+    const crx_field_desc& d = tp.d;
+    for (int i = threadIdx.x; i < d.n_seg; i += blockDim.x) {
+        seg_lo[i] = tp.track[6 * i + 3];
+        seg_hi[i] = tp.track[6 * i + 3] + tp.track[6 * i + 4];
+        seg_cv[i] = tp.track[6 * i + 5];
+    }
+    __syncthreads();
+    const int C = d.n_cars, V = C - 1, N1 = d.N + 1, per_block = 256 / C;
+    const int r0 = blockIdx.x * per_block;                               // first race of this block
+    const int n_live = min(per_block, tp.n_races - r0) * C;              // its live threads = its cars; r0 < n_races by the grid's size
+    const int t = threadIdx.x;
+    const bool live = t < n_live;
+    const size_t rc0 = (size_t)r0 * C, rc = rc0 + t;                     // this thread's car = scenario rc of the scene launch
+    if (live)
+        zero_input_rollout(tp.xcurv + 6 * rc, seg_lo, seg_hi, seg_cv, d.n_seg, d.lap_length, d.dt, N1, tp.pred_s_car + rc * N1, tp.pred_ey_car + rc * N1);
+    __syncthreads();   // the predictions of this block's races are in memory; workgroup scope is all phase 2 needs
+    if (!live) return;
+    tp.n_all[rc] = V;
+    // element e of the block's range of a [R C][V][W] array: ego q = e / (V W) of the block, slot v, word w; its source row is car
+    // o = v + (v >= c) of the ego's race
+    const int row_x = V * 6, row_p = V * N1;
+    for (int e = t; e < n_live * row_x; e += n_live) {
+        const int q = e / row_x, m = e - q * row_x, v = m / 6, w = m - 6 * v;
+        const int c = q % C, o = v + (v >= c ? 1 : 0);
+        tp.veh_xcurv[rc0 * row_x + e] = tp.xcurv[(rc0 + (q - c) + o) * 6 + w];
+    }
+    for (int e = t; e < n_live * row_p; e += n_live) {
+        const int q = e / row_p, m = e - q * row_p, v = m / N1, j = m - N1 * v;
+        const int c = q % C, o = v + (v >= c ? 1 : 0);
+        const size_t src = (rc0 + (q - c) + o) * N1 + j;
+        tp.pred_s[rc0 * row_p + e] = tp.pred_s_car[src];
+        tp.pred_ey[rc0 * row_p + e] = tp.pred_ey_car[src];
+    }
+}
+
 hipError_t crx_launch_prep(const crx_prep_kparams& pp, hipStream_t st) { return crx_launch_1d(crx_prep_kernel, pp.n_scen, 1, WAVE, st, pp); }
 hipError_t crx_launch_scene(const crx_scene_kparams& sp, hipStream_t st) { return crx_launch_1d(crx_scene_kernel, sp.n_scen, 1, WAVE, st, sp); }
 hipError_t crx_launch_trackprep(const crx_trackprep_kparams& tp, hipStream_t st) {
@@ -359,4 +394,8 @@ hipError_t crx_launch_cbfprep(const crx_cbfprep_kparams& cp, hipStream_t st) { r
 // whole races per block: 256 / n_cars of them (n_cars in 1 .. CRX_MAX_OBS + 1, checked by the caller)
 hipError_t crx_launch_field_prep(const crx_field_kparams& fp, hipStream_t st) {
     return crx_launch_1d(crx_field_prep_kernel, fp.n_races, 256 / fp.d.n_cars, 256, st, fp);
+}
+// the same shape (n_cars in 1 .. CRX_MAX_VEH + 1, checked by the caller)
+hipError_t crx_launch_field_traffic(const crx_field_traffic_kparams& tp, hipStream_t st) {
+    return crx_launch_1d(crx_field_traffic_kernel, tp.n_races, 256 / tp.d.n_cars, 256, st, tp);
 }

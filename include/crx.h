@@ -44,7 +44,9 @@
 extern "C" {
 #endif
 
-#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_seed_commit_dev, crx_seed_log_dev and CRX_SEED_* (seed laps: every car's own PID lap and
+#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_field_traffic, crx_field_traffic_dev (field games: the racing game's traffic arrays when every car of
+                          a race plays it) -- new entry points only.
+                          0.4.0 (additive, same number): crx_seed_commit_dev, crx_seed_log_dev and CRX_SEED_* (seed laps: every car's own PID lap and
                           MPC-LTI lap become its own safe set) -- new entry points only.
                           0.4.0 (additive, same number): crx_stats_desc, crx_stats_desc_default, crx_race_stats_reset, crx_race_stats_reset_dev,
                           crx_race_stats, crx_race_stats_dev, crx_race_stats_summary, crx_race_stats_summary_dev and the CRX_STATS_* layout
@@ -856,6 +858,42 @@ int crx_field_prep(const crx_field_desc* d, int n_races, const double* track, co
 int crx_field_prep_dev(const crx_field_desc* d, int n_races, const double* track, const double* xcurv, const double* car_dims, double* pred_s,
                        double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims, double* clear,
                        void* stream);
+
+/*
+ * Field games: the traffic arrays of the racing game (LMPCRacingGame.calc_input: learning MPC, overtake planner + tracking NLP when a car
+ * is near) when EVERY car of a race plays it.  n_races races of C = n_cars cars (1 <= C <= CRX_MAX_VEH + 1, V = C - 1), race-major and
+ * car-minor as in crx_field_prep: each car is the ego of its own scenario and a vehicle of the V others.  One kernel launch, two phases:
+ *   predictions   every car by the zero-input roll-out of crx_field_prep (racing/offboard.py:51-94), the same code: the same bits
+ *   traffic       per ego, the other cars in car order, skipping the ego (F5): the car's current state and its roll-out rows, copied --
+ *                 what OvertakeTrajPlanner.get_local_traj takes of a driven opponent on its `else` branch, get_trajectory_nsteps(N + 1)
+ *                 (planning/overtake_traj_planner.py:77-85)
+ *   track [n_seg][6];  xcurv [R][C][6]
+ *   pred_s_car, pred_ey_car [R][C][N+1]                       out: every car's own roll-out (= pred_s, pred_ey of crx_field_prep)
+ *   veh_xcurv [R C][V][6];  pred_s, pred_ey [R C][V][N+1]     out: slot v of ego c is car v + (v >= c) of its race
+ *   n_all [R C]                                               out: V
+ * The outputs are the veh_xcurv, pred_s, pred_ey, n_all inputs of crx_planner_scene_dev for n_scen = R C, n_all_max = n_veh_max = V
+ * (V <= CRX_MAX_VEH: the scene never overflows), where crx_game_traffic_dev supplies them for scripted cars.  With C == 1 the per-ego
+ * arrays hold nothing and may be NULL, and n_all is 0.  The descriptor is crx_field_prep's, validated as there; safety_time, degree,
+ * l_sum and w_sum are not read.
+ * Quirks kept (F1-F3, F6 as in crx_field_prep):
+ *   F1  snapshot: all cars see the states at the start of the step; the reference steps its vehicles one after the other.
+ *   F2  column 0 of a prediction is one estimated step AHEAD of the current state.
+ *   F3  the prediction is wrapped after every roll-out step: an opponent that crosses the line inside the horizon jumps by -L, where the
+ *       scripted cars of crx_game_traffic_dev are unwrapped (Q6).  The rows reach the planner and the tracking prep as the reference
+ *       builds them.
+ *   F6  s exactly on a segment boundary takes the first matching segment, like the plant.
+ *   G1  every car is "ego" in its own problem, although the reference's helpers hard-code vehicles["ego"] (planner_helper.py:185).
+ *   G2  the tracking NLP behind the planner consumes the same roll-out rows through the scene and crx_track_prep_dev.
+ *       control.mpc_multi_agents hard-codes realtime_flag = False (control.py:288-298) and its call form there,
+ *       get_trajectory_nsteps(time, timestep, n), is one the driven model does not accept; the roll-out is the realtime_flag == True form
+ *       of the same lines.
+ *   G3  a car with a non-finite state has non-finite rows.  check_ego_agent_distance is all comparisons, so nobody counts it as a vehicle
+ *       of interest, and it touches no other car's outputs.
+ */
+int crx_field_traffic(const crx_field_desc* d, int n_races, const double* track, const double* xcurv, double* pred_s_car, double* pred_ey_car,
+                      double* veh_xcurv, double* pred_s, double* pred_ey, int32_t* n_all);
+int crx_field_traffic_dev(const crx_field_desc* d, int n_races, const double* track, const double* xcurv, double* pred_s_car,
+                          double* pred_ey_car, double* veh_xcurv, double* pred_s, double* pred_ey, int32_t* n_all, void* stream);
 
 /*
  * Inputs of control.mpc_multi_agents' NLP (crx_cbf_solve with per_stage_target = 1) from the planner's outputs, on the device

@@ -119,5 +119,10 @@ def field_traffic(desc, track, xcurv):
     return binding().field_traffic(desc, track, xcurv)
 
 
+def mixed_prep(desc, track, xcurv, policy, car_dims=None):
+    """Mixed-field prep (include/crx.h "Mixed fields") on host arrays: see abi.Binding.mixed_prep."""
+    return binding().mixed_prep(desc, track, xcurv, policy, car_dims)
+
+
 def plant_step(desc, track, xglob, xcurv, u, params=None):
     return binding().plant_step(desc, track, xglob, xcurv, u, params=params)

@@ -242,6 +242,37 @@ def field_desc(N, n_cars, n_seg, lap_length, dt=0.1, safety_time=2.0, degree=6, 
     return FieldDesc(int(N), int(n_cars), int(n_seg), int(degree), float(lap_length), float(dt), float(safety_time), float(l_sum), float(w_sum))
 
 
+# include/crx.h "Mixed fields": one policy code per car
+POLICY_NONE, POLICY_PID, POLICY_LQR, POLICY_MPC_LTI, POLICY_MPCCBF, POLICY_ILQR = range(6)
+POLICY_NAMES = ("none", "pid", "lqr", "mpc_lti", "mpccbf", "ilqr")
+
+
+def policy_codes(policy):
+    """int32 array of CRX_POLICY_* codes, in the shape given, from codes or names (POLICY_NAMES, any case); anything else is a ValueError."""
+    a = np.asarray(policy)
+    if a.dtype.kind in "US":
+        names = [str(s).lower() for s in a.reshape(-1)]
+        bad = sorted(set(names) - set(POLICY_NAMES))
+        if bad:
+            raise ValueError("unknown policy name(s) %s: one of %s" % (bad, POLICY_NAMES))
+        return np.array([POLICY_NAMES.index(s) for s in names], dtype=np.int32).reshape(a.shape)
+    if a.dtype.kind not in "iu" or a.size and (a.min() < 0 or a.max() >= len(POLICY_NAMES)):
+        raise ValueError("policy: integer codes 0 .. %d or names %s" % (len(POLICY_NAMES) - 1, POLICY_NAMES))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+class MixedDesc(C.Structure):
+    _fields_ = [("N", C.c_int32), ("N_ilqr", C.c_int32), ("n_cars", C.c_int32), ("n_seg", C.c_int32), ("degree", C.c_int32),
+                ("ilqr_obstacles", C.c_int32), ("lap_length", C.c_double), ("dt", C.c_double), ("safety_time", C.c_double), ("l_sum", C.c_double),
+                ("w_sum", C.c_double)]
+
+
+def mixed_desc(N, N_ilqr, n_cars, n_seg, lap_length, ilqr_obstacles=0, dt=0.1, safety_time=2.0, degree=6, l_sum=0.4, w_sum=0.2):
+    """crx_mixed_desc_default: field_desc's values; N_ilqr = 0: no iLQR arrays; ilqr_obstacles = 0: the last other car only (quirk I1), 1: all."""
+    return MixedDesc(int(N), int(N_ilqr), int(n_cars), int(n_seg), int(degree), int(ilqr_obstacles), float(lap_length), float(dt),
+                     float(safety_time), float(l_sum), float(w_sum))
+
+
 class StatsDesc(C.Structure):
     _fields_ = [("n_opp_max", C.c_int32), ("n_cars", C.c_int32), ("degree", C.c_int32), ("pad", C.c_int32), ("lap_length", C.c_double),
                 ("track_width", C.c_double), ("l_sum", C.c_double), ("w_sum", C.c_double)]
@@ -490,7 +521,7 @@ class Binding:
         self.lib, self.prefix = lib, prefix
         for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve", "ilqr_solve",
                      "ilqr_solve_models", "lqr_design", "sysid_fit", "cbf_solve_models", "planner_solve_models", "planner_plan",
-                     "planner_plan_models", "path_prep", "path_plan", "plant_step_params", "field_prep", "field_traffic"):
+                     "planner_plan_models", "path_prep", "path_plan", "plant_step_params", "field_prep", "field_traffic", "mixed_prep"):
             if hasattr(lib, prefix + name):
                 getattr(lib, prefix + name).restype = C.c_int
         if hasattr(lib, prefix + "race_stats_dev"):
@@ -858,6 +889,34 @@ class Binding:
                    pred_s=np.zeros((R * Cn, V, N1)), pred_ey=np.zeros((R * Cn, V, N1)), n_all=np.zeros(R * Cn, dtype=_I))
         self._call("field_traffic", C.byref(desc), C.c_int(R), _p(track), _p(xcurv),
                    *[_p(out[k]) for k in ("pred_s_car", "pred_ey_car", "veh_xcurv", "pred_s", "pred_ey", "n_all")])
+        return out
+
+    def mixed_prep(self, desc, track, xcurv, policy, car_dims=None, clear=True):
+        """crx_mixed_prep (include/crx.h "Mixed fields"): the roll-out of every car of every race and the solver inputs of each car's own policy.
+        track (n_seg,6); xcurv (R,C,6) or (R*C,6); policy (R,C) codes or names; car_dims (R,C,2) or None.  Returns pred_s, pred_ey
+        (R,C,NP+1), NP = max(N, N_ilqr); obs_s, obs_ey (R,C,V,N+1), lap_off (R,C,V), n_obs, m_nlp (R,C), obs_dims (R,C,V,2) with car_dims; with
+        N_ilqr > 0 il_obs_s, il_obs_ey (R,C,V,N_ilqr+1), il_lap_off (R,C,V), il_n_obs, m_ilqr (R,C); clear (R,C) unless clear is False."""
+        N1, NI1, Cn = desc.N + 1, desc.N_ilqr + 1, desc.n_cars
+        V, NP1 = Cn - 1, max(N1, NI1)
+        track = _in(track, _D, (desc.n_seg, 6))
+        xcurv = np.ascontiguousarray(xcurv, dtype=_D)
+        R = xcurv.size // (6 * Cn)
+        xcurv = _in(xcurv.reshape(R, Cn, 6), _D, (R, Cn, 6))
+        policy = _in(policy_codes(policy), _I, (R, Cn))
+        out = dict(pred_s=np.zeros((R, Cn, NP1)), pred_ey=np.zeros((R, Cn, NP1)), obs_s=np.zeros((R, Cn, V, N1)), obs_ey=np.zeros((R, Cn, V, N1)),
+                   lap_off=np.zeros((R, Cn, V)), n_obs=np.zeros((R, Cn), dtype=_I), m_nlp=np.zeros((R, Cn), dtype=_I))
+        if car_dims is not None:
+            car_dims = _in(car_dims, _D, (R, Cn, 2))
+            out["obs_dims"] = np.zeros((R, Cn, V, 2))
+        if desc.N_ilqr > 0:
+            out.update(il_obs_s=np.zeros((R, Cn, V, NI1)), il_obs_ey=np.zeros((R, Cn, V, NI1)), il_lap_off=np.zeros((R, Cn, V)),
+                       il_n_obs=np.zeros((R, Cn), dtype=_I), m_ilqr=np.zeros((R, Cn), dtype=_I))
+        if clear:
+            out["clear"] = np.zeros((R, Cn))
+        opt = lambda k: _p(out[k]) if k in out else None   # noqa: E731
+        self._call("mixed_prep", C.byref(desc), C.c_int(R), _p(track), _p(xcurv), _p(policy), _p(car_dims) if car_dims is not None else None,
+                   *[opt(k) for k in ("pred_s", "pred_ey", "obs_s", "obs_ey", "lap_off", "n_obs", "obs_dims", "m_nlp", "il_obs_s", "il_obs_ey",
+                                      "il_lap_off", "il_n_obs", "m_ilqr", "clear")])
         return out
 
     def path_solve(self, desc, opt, bez, lb, ub, e0, eN):

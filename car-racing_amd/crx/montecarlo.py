@@ -22,6 +22,9 @@ FieldGames is GameLaps for a field: every car of a race plays the racing game an
 crx_field_traffic_dev); grid_start() is what puts several learning-MPC cars on one track: PidLaps -> identify -> SeedLaps -> grid_start ->
 FieldGames.
 
+MixedRaces is the field whose cars differ in controller: a policy code per car (none, pid, lqr, mpc_lti, mpccbf, ilqr), one prep launch
+for all of them (crx_mixed_prep_dev), the two solver launches under masks, one commit launch that applies each car's own law.
+
 What the loops are run for -- contacts, cars off the track, lap times, overtakes -- is RaceStats (end of this module): per-car
 statistics on the device, one launch per sample, attached to any loop through the loop's stats_inputs().
 """
@@ -406,6 +409,95 @@ def field_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, n_ca
                    device=device, noise_seed=noise_seed, models=models, plant_params=plant_params, car_dims=car_dims)
     logs = _run_and_log(r.step, steps, log_every, dict(xcurv=lambda: r.xc, u=lambda: r.u, status=lambda: r.ws.status,
                                                        iters=lambda: r.ws.iters, n_obs=lambda: r.fws.n_obs))
+    return dict(logs, laps=r.laps.cpu().numpy(), min_clear=r.min_clear.cpu().numpy())
+
+
+class MixedRaces(_Plant):
+    """R races of C cars, every car under its OWN controller, as the reference's simulator holds its vehicles (CarRacingSim.add_vehicle +
+    ModelBase.set_ctrl_policy, racing/offboard.py:14-45; sim() steps them together, :114-131): policy [R,C] of abi.POLICY_* codes or names
+    ("none", "pid", "lqr", "mpc_lti", "mpccbf", "ilqr").  The plant batch is R*C, race-major, car-minor; all cars of a step see the states at
+    the start of the step (include/crx.h "Mixed fields", quirks F1-F3, F6, M1, M2).  One NLP launch serves the mpc_lti and mpccbf cars (they
+    share Q and R; an mpc_lti car has no obstacles), one iLQR launch the ilqr cars, each under its mask; a launch whose policy no car has
+    is not issued -- decided here, from the host `policy`.  status [R*C]: the solve's status for the solver policies, CRX_CONVERGED for pid
+    and lqr, CRX_SKIPPED for none.  min_clear [R*C] as in FieldRaces."""
+
+    def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, policy, vt=0.8, eyt=0.0, N=10, ilqr_N=50, ilqr_max_iter=150,
+                 ilqr_obstacles=0, alpha=0.8, timestep=0.1, device=None, noise_seed=None, models=None, plant_params=None, car_dims=None):
+        pol = abi.policy_codes(policy)
+        if pol.ndim != 2 or not 1 <= pol.shape[1] <= abi.CRX_MAX_OBS + 1:
+            raise ValueError("policy: [R,C] with 1 .. %d cars per race" % (abi.CRX_MAX_OBS + 1))
+        R, Cn = pol.shape
+        x0, g0 = (np.asarray(a, dtype=float).reshape(-1, 6) for a in (xcurv0, xglob0))   # [R*C,6] or [R,C,6]
+        if x0.shape[0] != R * Cn or g0.shape != x0.shape:
+            raise ValueError("xcurv0, xglob0: %d and %d cars, policy has %d x %d" % (x0.shape[0], g0.shape[0], R, Cn))
+        dev = self._plant_init(track_table, lap_length, timestep, x0, g0, noise_seed, device, plant_params)
+        Bn = self.batch
+        self.N, self.n_races, self.n_cars, self.track_width = N, R, Cn, track_width
+        has = lambda *codes: bool(np.isin(pol, codes).any())   # noqa: E731
+        has_nlp, has_ilqr, has_lqr, has_pid = has(abi.POLICY_MPC_LTI, abi.POLICY_MPCCBF), has(abi.POLICY_ILQR), has(abi.POLICY_LQR), has(abi.POLICY_PID)
+        self.policy = _dev(pol.reshape(-1), dev, dtype=torch.int32)
+        self.mdesc = abi.mixed_desc(N, ilqr_N if has_ilqr else 0, Cn, self.tab.shape[0], lap_length, ilqr_obstacles=ilqr_obstacles, dt=timestep)
+        # vt, eyt: scalars or one value per car [R,C], as in FieldRaces; xt is the target of the NLP, iLQR and LQR cars, (vt, eyt) the PID cars'
+        xt = np.zeros((Bn, 6))
+        xt[:, 0] = np.broadcast_to(np.asarray(vt, dtype=float), (R, Cn)).reshape(-1)
+        xt[:, 5] = np.broadcast_to(np.asarray(eyt, dtype=float), (R, Cn)).reshape(-1)
+        self.xt = _dev(xt, dev)
+        self.vt, self.eyt = (_dev(xt[:, 0], dev), _dev(xt[:, 5], dev)) if has_pid else (None, None)
+        # models = (A [R*C,6,6], B [R*C,6,2]): every car's controller on its own model -- the NLP's, the iLQR's and the LQR design's
+        mAB = None if models is None else _models(models[0], models[1], Bn, dev)
+        self.desc = self.ws = self.models = None
+        if has_nlp:
+            self.desc = abi.cbf_desc(N, Cn - 1, A, B, alpha=alpha, margin=0.2, ey_max=track_width)
+            self.ws = torch_api.CbfWorkspace(self.desc, Bn, dev)
+            self.models = None if mAB is None else torch_api.CbfModels(self.desc, *mAB)
+        self.idesc = self.iws = self.ilqr_models = None
+        if has_ilqr:
+            self.idesc = abi.ilqr_desc(ilqr_N, A, B, max_iter=ilqr_max_iter, n_obs_max=Cn - 1, l_sum=self.mdesc.l_sum, w_sum=self.mdesc.w_sum)
+            self.iws = torch_api.IlqrWorkspace(self.idesc, Bn, dev)
+            self.ilqr_models = mAB
+        self.K = None
+        if has_lqr:   # one design launch, here: the LQR cars' gains (the other cars' rows stay zero)
+            m_lqr = _dev((pol.reshape(-1) == abi.POLICY_LQR).astype(np.int32), dev, dtype=torch.int32)
+            self.K = torch_api.lqr_design_dev(abi.lqr_desc(), *(mAB if mAB is not None else _models(A, B, Bn, dev)), active=m_lqr).K
+        # car_dims [R,C,2]: (length, width) of every car, for the NLP family and `clear` (M2); None: the descriptor's l_sum, w_sum
+        self.car_dims = None if car_dims is None else _dev(np.asarray(car_dims, dtype=float).reshape(R, Cn, 2), dev)
+        self.mws = torch_api.MixedWorkspace(self.mdesc, R, dev, dims=car_dims is not None)
+        self.min_clear = torch.full((Bn,), float("inf"), dtype=torch.float64, device=dev)
+        self.u = torch.zeros((Bn, 2), dtype=torch.float64, device=dev)
+        self.status = torch.zeros(Bn, dtype=torch.int32, device=dev)
+
+    def step(self):
+        """One control step of every car of every race: mixed_prep_dev, cbf_solve_dev (active = m_nlp), ilqr_solve_dev (active = m_ilqr),
+        mixed_commit_dev, plant_step_wrap_dev -- a solver launch whose policy no car has is left out and its family given as None
+        (dispatch = "longest_first": one longest_first ahead of the NLP launch); then `clear` joins the running minimum."""
+        m = self.mws
+        torch_api.mixed_prep_dev(self.mdesc, self.tab, self.xc, self.policy, m, car_dims=self.car_dims)
+        if self.ws is not None:
+            torch_api.cbf_solve_dev(self.desc, self.xc, self.xt, m.obs_s, m.obs_ey, m.lap_off, m.n_obs, ws=self.ws, active=m.m_nlp,
+                                    order=_order(self, self.ws.iters, m.m_nlp), models=self.models, obs_dims=m.obs_dims)
+        if self.iws is not None:
+            torch_api.ilqr_solve_dev(self.idesc, self.xc, self.xt, m.il_obs_s, m.il_obs_ey, m.il_lap_off, m.il_n_obs, ws=self.iws,
+                                     active=m.m_ilqr, models=self.ilqr_models)
+        torch_api.mixed_commit_dev(self.policy, self.xc, self.u, self.status,
+                                   pid=None if self.vt is None else (self.vt, self.eyt), lqr=None if self.K is None else (self.K, self.xt),
+                                   nlp=None if self.ws is None else (self.ws.U, self.ws.status),
+                                   ilqr=None if self.iws is None else (self.iws.U, self.iws.status))
+        self._advance(self.u, 2)
+        torch.minimum(self.min_clear, m.clear, out=self.min_clear)
+
+    def stats_inputs(self):
+        return super().stats_inputs(n_cars=self.n_cars, car_dims=self.car_dims, l_sum=self.mdesc.l_sum, w_sum=self.mdesc.w_sum)
+
+
+def mixed_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, policy, steps, vt=0.8, eyt=0.0, N=10, ilqr_N=50, ilqr_max_iter=150,
+                ilqr_obstacles=0, alpha=0.8, timestep=0.1, device=None, log_every=1, noise_seed=None, models=None, plant_params=None, car_dims=None):
+    """policy [R,C] codes or names; xcurv0, xglob0 [R*C,6] or [R,C,6]; vt, eyt scalars or [R,C]; models = (A [R*C,6,6], B [R*C,6,2]);
+    plant_params [R*C,10]; car_dims [R,C,2].  Returns host arrays: xcurv [T+1,R*C,6] (T = steps / log_every), u [T,R*C,2], status [T,R*C],
+    laps [R*C], min_clear [R*C]."""
+    r = MixedRaces(track_table, lap_length, track_width, A, B, xcurv0, xglob0, policy, vt=vt, eyt=eyt, N=N, ilqr_N=ilqr_N, ilqr_max_iter=ilqr_max_iter,
+                   ilqr_obstacles=ilqr_obstacles, alpha=alpha, timestep=timestep, device=device, noise_seed=noise_seed, models=models,
+                   plant_params=plant_params, car_dims=car_dims)
+    logs = _run_and_log(r.step, steps, log_every, dict(xcurv=lambda: r.xc, u=lambda: r.u, status=lambda: r.status))
     return dict(logs, laps=r.laps.cpu().numpy(), min_clear=r.min_clear.cpu().numpy())
 
 

@@ -596,6 +596,95 @@ def field_traffic_dev(desc, track, xcurv, ws):
     return ws
 
 
+class MixedWorkspace:
+    """Outputs of mixed_prep_dev for n_races races of desc.n_cars cars, batch R*C race-major and car-minor, V = C - 1: the roll-outs pred_s,
+    pred_ey [R,C,NP+1] (NP = max(N, N_ilqr)); the NLP family in cbf_solve_dev's layout -- obs_s, obs_ey [R*C,V,N+1], lap_off [R*C,V], n_obs,
+    m_nlp [R*C], obs_dims [R*C,V,2] with dims=True, else None; the iLQR family in ilqr_solve_dev's layout when desc.N_ilqr > 0, else None --
+    il_obs_s, il_obs_ey [R*C,V,N_ilqr+1], il_lap_off [R*C,V], il_n_obs, m_ilqr [R*C]; clear [R*C] (None with clear=False)."""
+
+    def __init__(self, desc, n_races, device, dims=False, clear=True):
+        N1, NI1, Cn = desc.N + 1, desc.N_ilqr + 1, desc.n_cars
+        Bn, V, NP1 = n_races * Cn, Cn - 1, max(N1, NI1)
+        f64 = dict(dtype=torch.float64, device=device)
+        i32 = dict(dtype=torch.int32, device=device)
+        self.n_races = n_races
+        self.pred_s = torch.zeros((n_races, Cn, NP1), **f64)
+        self.pred_ey = torch.zeros((n_races, Cn, NP1), **f64)
+        self.obs_s = torch.zeros((Bn, V, N1), **f64)
+        self.obs_ey = torch.zeros((Bn, V, N1), **f64)
+        self.lap_off = torch.zeros((Bn, V), **f64)
+        self.n_obs = torch.zeros(Bn, **i32)
+        self.m_nlp = torch.zeros(Bn, **i32)
+        self.obs_dims = torch.zeros((Bn, V, 2), **f64) if dims else None
+        il = desc.N_ilqr > 0
+        self.il_obs_s = torch.zeros((Bn, V, NI1), **f64) if il else None
+        self.il_obs_ey = torch.zeros((Bn, V, NI1), **f64) if il else None
+        self.il_lap_off = torch.zeros((Bn, V), **f64) if il else None
+        self.il_n_obs = torch.zeros(Bn, **i32) if il else None
+        self.m_ilqr = torch.zeros(Bn, **i32) if il else None
+        self.clear = torch.zeros(Bn, **f64) if clear else None
+
+
+def mixed_prep_dev(desc, track, xcurv, policy, ws, car_dims=None):
+    """crx_mixed_prep_dev (include/crx.h "Mixed fields"): xcurv [R*C,6] (race-major, car-minor), track [n_seg,6], policy int32 [R*C] of
+    abi.POLICY_* codes, car_dims [R,C,2] with a MixedWorkspace(dims=True), None with dims=False.  Writes ws and returns it."""
+    R, Cn, N1, NI1 = ws.n_races, desc.n_cars, desc.N + 1, desc.N_ilqr + 1
+    Bn, V, NP1 = R * Cn, Cn - 1, max(N1, NI1)
+    _chk(track, torch.float64, (desc.n_seg, 6), "track")
+    _chk(xcurv, torch.float64, (Bn, 6), "xcurv")
+    _chk(policy, torch.int32, (Bn,), "policy")
+    if (car_dims is None) != (ws.obs_dims is None):
+        raise ValueError("car_dims goes with a MixedWorkspace(dims=True), no car_dims with dims=False")
+    if (desc.N_ilqr > 0) != (ws.m_ilqr is not None):
+        raise ValueError("the workspace was built for another N_ilqr: its iLQR arrays go with desc.N_ilqr > 0")
+    if car_dims is not None:
+        _chk(car_dims, torch.float64, (R, Cn, 2), "car_dims")
+    f64s = [("pred_s", (R, Cn, NP1)), ("pred_ey", (R, Cn, NP1)), ("obs_s", (Bn, V, N1)), ("obs_ey", (Bn, V, N1)), ("lap_off", (Bn, V)),
+            ("obs_dims", (Bn, V, 2)), ("il_obs_s", (Bn, V, NI1)), ("il_obs_ey", (Bn, V, NI1)), ("il_lap_off", (Bn, V)), ("clear", (Bn,))]
+    for name, shape in f64s:
+        if getattr(ws, name) is not None:
+            _chk(getattr(ws, name), torch.float64, shape, "ws." + name)
+    for name in ("n_obs", "m_nlp", "il_n_obs", "m_ilqr"):
+        if getattr(ws, name) is not None:
+            _chk(getattr(ws, name), torch.int32, (Bn,), "ws." + name)
+    _call("crx_mixed_prep_dev", C.byref(desc), C.c_int(R), _ptr(track), _ptr(xcurv), _ptr(policy), _ptr(car_dims), _ptr(ws.pred_s), _ptr(ws.pred_ey),
+          _ptr(ws.obs_s), _ptr(ws.obs_ey), _ptr(ws.lap_off), _ptr(ws.n_obs), _ptr(ws.obs_dims), _ptr(ws.m_nlp), _ptr(ws.il_obs_s), _ptr(ws.il_obs_ey),
+          _ptr(ws.il_lap_off), _ptr(ws.il_n_obs), _ptr(ws.m_ilqr), _ptr(ws.clear), _stream())
+    return ws
+
+
+def mixed_commit_dev(policy, x, u, ctrl_status, pid=None, lqr=None, nlp=None, ilqr=None):
+    """crx_mixed_commit_dev: u [B,2] and ctrl_status int32 [B] from each car's own law; policy int32 [B], x [B,6] the state the step starts
+    from.  The families, each a pair or None (its cars then apply zero and report CRX_SKIPPED): pid = (vt, eyt) [B] each; lqr = (K [B,2,6],
+    xt [B,6]); nlp = (U [B,N,2], status int32 [B]) of cbf_solve_dev; ilqr = (U [B,N_ilqr,2], status) of ilqr_solve_dev."""
+    Bn = x.shape[0]
+    _chk(policy, torch.int32, (Bn,), "policy")
+    _chk(x, torch.float64, (Bn, 6), "x")
+    _chk(u, torch.float64, (Bn, 2), "u")
+    _chk(ctrl_status, torch.int32, (Bn,), "ctrl_status")
+    vt, eyt = pid if pid is not None else (None, None)
+    K, xt = lqr if lqr is not None else (None, None)
+    Un, sn = nlp if nlp is not None else (None, None)
+    Ui, si = ilqr if ilqr is not None else (None, None)
+    if pid is not None:
+        _chk(vt, torch.float64, (Bn,), "pid vt")
+        _chk(eyt, torch.float64, (Bn,), "pid eyt")
+    if lqr is not None:
+        _chk(K, torch.float64, (Bn, 2, 6), "lqr K")
+        _chk(xt, torch.float64, (Bn, 6), "lqr xt")
+    strides = []
+    for name, U, st in (("nlp", Un, sn), ("ilqr", Ui, si)):
+        if U is not None:
+            if U.dim() != 3 or U.shape[1] < 1:
+                raise ValueError("%s U: expected [B,N,2]" % name)
+            _chk(U, torch.float64, (Bn, U.shape[1], 2), name + " U")
+            _chk(st, torch.int32, (Bn,), name + " status")
+        strides.append(0 if U is None else 2 * U.shape[1])
+    _call("crx_mixed_commit_dev", C.c_int(Bn), _ptr(policy), _ptr(x), _ptr(vt), _ptr(eyt), _ptr(K), _ptr(xt), _ptr(Un), C.c_int(strides[0]), _ptr(sn),
+          _ptr(Ui), C.c_int(strides[1]), _ptr(si), _ptr(u), _ptr(ctrl_status), _stream())
+    return u
+
+
 class RaceStatsWorkspace:
     """State of race_stats_dev for `batch` cars (include/crx.h "Race statistics"): stat_i [STATS_NI, batch] int32 and stat_d
     [STATS_ND + n_opp_max, batch] float64, field-major, and every field as a named view of them: n_samples, nonfinite_step, off_step,

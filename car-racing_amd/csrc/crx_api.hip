@@ -1164,6 +1164,113 @@ int crx_field_traffic(const crx_field_desc* d, int n_races, const double* track,
     return sg.down(g_stream);
 }
 
+// ---- mixed fields: every car of a race under its own controller (crx_mixed_prep_kernel, crx_prep.hip; crx_mixed_commit_kernel, crx_game.hip) ----
+void crx_mixed_desc_default(crx_mixed_desc* d, int N, int N_ilqr, int n_cars, int n_seg, double lap_length) {
+    memset(d, 0, sizeof(*d));
+    d->N = N; d->N_ilqr = N_ilqr; d->n_cars = n_cars; d->n_seg = n_seg; d->degree = 6; d->ilqr_obstacles = 0;
+    d->lap_length = lap_length; d->dt = 0.1; d->safety_time = 2.0; d->l_sum = 0.4; d->w_sum = 0.2;
+}
+
+// The descriptor and the race count of crx_mixed_prep*
+static int check_mixed_desc(const crx_mixed_desc* d, int n_races) {
+    auto positive = [](double v) { return v > 0.0 && isfinite(v); };
+    if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
+    if (d->N < 1 || d->N > CRX_MAX_N) return fail(CRX_ERR_ARG, "N=%d outside [1,%d]", d->N, CRX_MAX_N);
+    if (d->N_ilqr < 0 || d->N_ilqr > CRX_ILQR_MAX_N) return fail(CRX_ERR_ARG, "N_ilqr=%d outside [0,%d]", d->N_ilqr, CRX_ILQR_MAX_N);
+    if (d->n_cars < 1 || d->n_cars > CRX_MAX_OBS + 1) return fail(CRX_ERR_ARG, "n_cars=%d outside [1,%d]", d->n_cars, CRX_MAX_OBS + 1);
+    if (d->n_seg < 1 || d->n_seg > CRX_PLANT_MAX_SEG) return fail(CRX_ERR_ARG, "n_seg=%d outside [1,%d]", d->n_seg, CRX_PLANT_MAX_SEG);
+    if (d->degree < 2 || d->degree > 8 || (d->degree & 1)) return fail(CRX_ERR_ARG, "degree must be 2, 4, 6 or 8");
+    if (d->ilqr_obstacles != 0 && d->ilqr_obstacles != 1) return fail(CRX_ERR_ARG, "ilqr_obstacles=%d must be 0 or 1", d->ilqr_obstacles);
+    if (!positive(d->lap_length) || !positive(d->dt) || !positive(d->l_sum) || !positive(d->w_sum))
+        return fail(CRX_ERR_ARG, "lap_length, dt, l_sum and w_sum must be positive and finite");
+    if (n_races < 0) return fail(CRX_ERR_ARG, "n_races < 0");
+    return 0;
+}
+
+// Arguments alone, before the library's state is looked at.  host_dims, host_policy: the rows of the host-pointer entry (NULL: on the device)
+static int check_mixed(crx_mixed_kparams& mp, const crx_mixed_desc* d, int n_races, arr track, arr xcurv, arr policy, arr car_dims, arr pred_s,
+                       arr pred_ey, arr obs_s, arr obs_ey, arr lap_off, arr n_obs, arr obs_dims, arr m_nlp, arr il_obs_s, arr il_obs_ey,
+                       arr il_lap_off, arr il_n_obs, arr m_ilqr, const double* host_dims = nullptr, const int32_t* host_policy = nullptr) {
+    auto positive = [](double v) { return v > 0.0 && isfinite(v); };
+    if (int rc = check_mixed_desc(d, n_races)) return rc;
+    if (d->n_cars > 1 && !car_dims != !obs_dims)   // (one car: obs_dims holds nothing, like the other [V] arrays)
+        return fail(CRX_ERR_ARG, "car_dims and obs_dims go together: both or neither (%s is NULL)", car_dims ? "obs_dims" : "car_dims");
+    if (n_races > 0 && (any_null(track, xcurv, policy, pred_s, pred_ey, n_obs, m_nlp) || (d->n_cars > 1 && any_null(obs_s, obs_ey, lap_off))))
+        return fail(CRX_ERR_ARG, "NULL array argument");
+    if (n_races > 0 && d->N_ilqr > 0 && (any_null(il_n_obs, m_ilqr) || (d->n_cars > 1 && any_null(il_obs_s, il_obs_ey, il_lap_off))))
+        return fail(CRX_ERR_ARG, "NULL array argument of the iLQR family (N_ilqr=%d)", d->N_ilqr);
+    for (size_t i = 0; host_dims && i < (size_t)n_races * d->n_cars; i++)
+        if (!positive(host_dims[2 * i]) || !positive(host_dims[2 * i + 1]))
+            return fail(CRX_ERR_ARG, "car_dims of car %zu of race %zu: length and width must be positive and finite", i % d->n_cars, i / d->n_cars);
+    for (size_t i = 0; host_policy && i < (size_t)n_races * d->n_cars; i++)
+        if (host_policy[i] < 0 || host_policy[i] >= CRX_POLICY_COUNT)
+            return fail(CRX_ERR_ARG, "policy=%d of car %zu of race %zu outside [0,%d]", host_policy[i], i % d->n_cars, i / d->n_cars, CRX_POLICY_COUNT - 1);
+    memset(&mp, 0, sizeof(mp));
+    mp.d = *d; mp.n_races = n_races;
+    return 0;
+}
+
+int crx_mixed_prep_dev(const crx_mixed_desc* d, int n_races, const double* track, const double* xcurv, const int32_t* policy,
+                       const double* car_dims, double* pred_s, double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs,
+                       double* obs_dims, int32_t* m_nlp, double* il_obs_s, double* il_obs_ey, double* il_lap_off, int32_t* il_n_obs,
+                       int32_t* m_ilqr, double* clear, void* stream) {
+    crx_mixed_kparams mp;
+    if (int rc = check_mixed(mp, d, n_races, track, xcurv, policy, car_dims, pred_s, pred_ey, obs_s, obs_ey, lap_off, n_obs, obs_dims, m_nlp,
+                             il_obs_s, il_obs_ey, il_lap_off, il_n_obs, m_ilqr)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (n_races == 0) return CRX_OK;
+    mp.track = track; mp.xcurv = xcurv; mp.policy = policy; mp.car_dims = car_dims; mp.pred_s = pred_s; mp.pred_ey = pred_ey;
+    mp.obs_s = obs_s; mp.obs_ey = obs_ey; mp.lap_off = lap_off; mp.n_obs = n_obs; mp.obs_dims = d->n_cars > 1 ? obs_dims : nullptr; mp.m_nlp = m_nlp;
+    mp.il_obs_s = il_obs_s; mp.il_obs_ey = il_obs_ey; mp.il_lap_off = il_lap_off; mp.il_n_obs = il_n_obs; mp.m_ilqr = m_ilqr; mp.clear = clear;
+    return launched(crx_launch_mixed_prep(mp, (hipStream_t)stream), "mixed prep");
+}
+
+int crx_mixed_prep(const crx_mixed_desc* d, int n_races, const double* track, const double* xcurv, const int32_t* policy, const double* car_dims,
+                   double* pred_s, double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims,
+                   int32_t* m_nlp, double* il_obs_s, double* il_obs_ey, double* il_lap_off, int32_t* il_n_obs, int32_t* m_ilqr, double* clear) {
+    crx_mixed_kparams chk;
+    if (int rc = check_mixed(chk, d, n_races, track, xcurv, policy, car_dims, pred_s, pred_ey, obs_s, obs_ey, lap_off, n_obs, obs_dims, m_nlp,
+                             il_obs_s, il_obs_ey, il_lap_off, il_n_obs, m_ilqr, car_dims, n_races > 0 ? policy : nullptr)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (n_races == 0) return CRX_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    const size_t RC = (size_t)n_races * d->n_cars, V = (size_t)d->n_cars - 1, N1 = (size_t)d->N + 1, NI1 = (size_t)d->N_ilqr + 1;
+    const size_t NP1 = N1 > NI1 ? N1 : NI1, il = d->N_ilqr > 0 ? 1 : 0;   // il = 0: the iLQR family is not staged (the kernel leaves it alone)
+    Stage sg;
+    auto dtr = sg.in(track, (size_t)d->n_seg * 6); auto dx = sg.in(xcurv, RC * 6); auto dpo = sg.in(policy, RC);
+    auto dcd = car_dims ? sg.in(car_dims, RC * 2) : Stage::Ref<double>{};   // unused: sg[dcd] is NULL
+    auto dps = sg.out(pred_s, RC * NP1); auto dpe = sg.out(pred_ey, RC * NP1);
+    auto dos = sg.out(obs_s, RC * V * N1); auto doe = sg.out(obs_ey, RC * V * N1); auto dlo = sg.out(lap_off, RC * V);
+    auto dno = sg.out(n_obs, RC); auto dmn = sg.out(m_nlp, RC);
+    auto dod = obs_dims ? sg.out(obs_dims, RC * V * 2) : Stage::Ref<double>{};
+    auto dis = il ? sg.out(il_obs_s, RC * V * NI1) : Stage::Ref<double>{}; auto die = il ? sg.out(il_obs_ey, RC * V * NI1) : Stage::Ref<double>{};
+    auto dil = il ? sg.out(il_lap_off, RC * V) : Stage::Ref<double>{};
+    auto din = il ? sg.out(il_n_obs, RC) : Stage::Ref<int32_t>{}; auto dmi = il ? sg.out(m_ilqr, RC) : Stage::Ref<int32_t>{};
+    auto dcl = clear ? sg.out(clear, RC) : Stage::Ref<double>{};
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_mixed_prep_dev(d, n_races, sg[dtr], sg[dx], sg[dpo], sg[dcd], sg[dps], sg[dpe], sg[dos], sg[doe], sg[dlo], sg[dno], sg[dod],
+                                    sg[dmn], sg[dis], sg[die], sg[dil], sg[din], sg[dmi], sg[dcl], g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
+int crx_mixed_commit_dev(int batch, const int32_t* policy, const double* x, const double* vt, const double* eyt, const double* K,
+                         const double* xt, const double* U_nlp, int nlp_stride, const int32_t* nlp_status, const double* U_ilqr,
+                         int ilqr_stride, const int32_t* ilqr_status, double* u, int32_t* ctrl_status, void* stream) {
+    if (batch < 0) return fail(CRX_ERR_ARG, "batch < 0");
+    if (!vt != !eyt || !K != !xt || !U_nlp != !nlp_status || !U_ilqr != !ilqr_status)
+        return fail(CRX_ERR_ARG, "the arrays of a family go together: (vt, eyt), (K, xt), (U_nlp, nlp_status), (U_ilqr, ilqr_status), both or neither");
+    if ((U_nlp && nlp_stride < 2) || (U_ilqr && ilqr_stride < 2)) return fail(CRX_ERR_ARG, "nlp_stride=%d, ilqr_stride=%d: a given plan has stride >= 2", nlp_stride, ilqr_stride);
+    if (batch > 0 && any_null(policy, x, u, ctrl_status)) return fail(CRX_ERR_ARG, "NULL array argument");
+    if (int rc = ensure_init()) return rc;
+    if (batch == 0) return CRX_OK;
+    crx_mixed_commit_kparams cp;
+    memset(&cp, 0, sizeof(cp));
+    cp.batch = batch; cp.nlp_stride = nlp_stride; cp.ilqr_stride = ilqr_stride; cp.policy = policy; cp.x = x; cp.vt = vt; cp.eyt = eyt; cp.K = K;
+    cp.xt = xt; cp.U_nlp = U_nlp; cp.U_ilqr = U_ilqr; cp.nlp_status = nlp_status; cp.ilqr_status = ilqr_status; cp.u = u; cp.ctrl_status = ctrl_status;
+    return launched(crx_launch_mixed_commit(cp, (hipStream_t)stream), "mixed commit");
+}
+
 int crx_plant_step(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
                    const double* u, double* xglob_next, double* xcurv_next) {
     return crx_plant_step_params(d, batch, track, xglob, xcurv, u, nullptr, xglob_next, xcurv_next);

@@ -5,6 +5,8 @@
 //   crx_game_log_kernel       the simulator's lap log and the races that completed a lap      utils/base.py:780-819, racing/offboard.py:114-131
 // the seed laps in front of the learning MPC (include/crx.h, "Seed laps" S1-S6):
 //   crx_seed_commit_kernel, crx_seed_log_kernel      each car's PID lap, then its MPC-LTI lap, logged into its own safe set      tests/auto_racing_game_test.py:48-73
+// the commit of a mixed field (include/crx.h, "Mixed fields"):
+//   crx_mixed_commit_kernel      each car's input from its own controller's law: PID, LQR, stage 0 of its NLP or iLQR plan, or nothing      racing/offboard.py:14-45
 // and what the closed loops are run for (include/crx.h, "Race statistics"):
 //   crx_race_stats_reset_kernel, crx_race_stats_kernel, crx_race_stats_summary_kernel      per-car outcomes, one launch per sample; the batch summary
 //
@@ -158,6 +160,47 @@ __global__ void __launch_bounds__(256) crx_seed_log_kernel(const crx_seed_kparam
     }
     sp.phase[b] = ph;
     sp.m_mpc[b] = ph == 1 ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Mixed fields (crx.montecarlo.MixedRaces, include/crx.h "Mixed fields"): after the solver launches, before the plant, the input each car
+// applies under its OWN controller.  One thread per car; thread b touches car b's elements only.  The policy code is compared, never
+// used as an index; a code out of range, NONE, and a car whose family's arrays are not given apply zero and report CRX_SKIPPED.
+// The PID law is crx_seed_commit_kernel's, the LQR sum crx_lqr_step_kernel's order (c = 0 .. 5) without its contraction.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) crx_mixed_commit_kernel(const crx_mixed_commit_kparams cp) {
+#pragma clang fp contract(off)   // every operation rounded on its own: tests/mixed_model.py reproduces the bits in NumPy
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= cp.batch) return;
+    const int pol = cp.policy[b];
+    const double* x = cp.x + (size_t)6 * b;
+    double u0 = 0.0, u1 = 0.0;
+    int st = CRX_SKIPPED;
+    if (pol == CRX_POLICY_PID && cp.vt) {                             // control.pid (control/control.py:15-25)
+        u0 = -0.6 * (x[5] - cp.eyt[b]) - 0.9 * x[3];
+        u1 = 1.5 * (cp.vt[b] - x[0]);
+        st = CRX_CONVERGED;
+    } else if (pol == CRX_POLICY_LQR && cp.K) {                       // control.lqr: u = -K (x - xt)
+        const double* K = cp.K + (size_t)12 * b;
+        const double* xt = cp.xt + (size_t)6 * b;
+        double v0 = 0.0, v1 = 0.0;
+#pragma unroll
+        for (int c = 0; c < 6; c++) {
+            const double dc = x[c] - xt[c];
+            v0 += K[c] * dc;
+            v1 += K[6 + c] * dc;
+        }
+        u0 = -v0; u1 = -v1;
+        st = CRX_CONVERGED;
+    } else if ((pol == CRX_POLICY_MPC_LTI || pol == CRX_POLICY_MPCCBF) && cp.U_nlp) {   // u_0 of the plan; a failed solve's last iterate (control.py:600-603)
+        u0 = cp.U_nlp[(size_t)b * cp.nlp_stride]; u1 = cp.U_nlp[(size_t)b * cp.nlp_stride + 1];
+        st = cp.nlp_status[b];
+    } else if (pol == CRX_POLICY_ILQR && cp.U_ilqr) {
+        u0 = cp.U_ilqr[(size_t)b * cp.ilqr_stride]; u1 = cp.U_ilqr[(size_t)b * cp.ilqr_stride + 1];
+        st = cp.ilqr_status[b];
+    }
+    cp.u[2 * b] = u0; cp.u[2 * b + 1] = u1;
+    cp.ctrl_status[b] = st;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -358,6 +401,12 @@ hipError_t crx_launch_seed(int which, const crx_seed_kparams& sp, hipStream_t st
     const dim3 grid((unsigned)((sp.batch + 255) / 256)), block(256);
     if (which == 0) hipLaunchKernelGGL(crx_seed_commit_kernel, grid, block, 0, st, sp);
     else hipLaunchKernelGGL(crx_seed_log_kernel, grid, block, 0, st, sp);
+    return hipGetLastError();
+}
+
+hipError_t crx_launch_mixed_commit(const crx_mixed_commit_kparams& cp, hipStream_t st) {
+    if (cp.batch == 0) return hipSuccess;
+    hipLaunchKernelGGL(crx_mixed_commit_kernel, dim3((unsigned)((cp.batch + 255) / 256)), dim3(256), 0, st, cp);
     return hipGetLastError();
 }
 

@@ -137,6 +137,20 @@ struct crx_field_traffic_kparams {
     int32_t* n_all;                            // [n_races * n_cars] = n_cars - 1
 };
 
+// crx_mixed_prep_kernel (crx_prep.hip): the roll-out of every car of every race and, per ego, the obstacle arrays of the solver family its policy names
+struct crx_mixed_kparams {
+    crx_mixed_desc d;
+    int n_races;
+    const double *track, *xcurv, *car_dims;    // car_dims: optional, as in crx_field_kparams
+    const int32_t* policy;                     // [n_races][n_cars] CRX_POLICY_*
+    double *pred_s, *pred_ey;                  // [n_races][n_cars][max(N, N_ilqr) + 1]
+    double *obs_s, *obs_ey, *lap_off, *obs_dims;   // the NLP family, [..][n_cars - 1][N + 1] ...; obs_dims: written iff car_dims
+    int32_t *n_obs, *m_nlp;
+    double *il_obs_s, *il_obs_ey, *il_lap_off; // the iLQR family, [..][n_cars - 1][N_ilqr + 1] ...; touched iff N_ilqr > 0
+    int32_t *il_n_obs, *m_ilqr;
+    double* clear;                             // optional
+};
+
 // ---- crx_path.hip: crx_path_kernel, the path QP (crx_path_qp.h) without a mask ----
 struct crx_path_kparams {
     int N, batch;
@@ -219,6 +233,7 @@ hipError_t crx_launch_trackprep(const crx_trackprep_kparams& tp, hipStream_t st)
 hipError_t crx_launch_cbfprep(const crx_cbfprep_kparams& cp, hipStream_t st);
 hipError_t crx_launch_field_prep(const crx_field_kparams& fp, hipStream_t st);
 hipError_t crx_launch_field_traffic(const crx_field_traffic_kparams& tp, hipStream_t st);
+hipError_t crx_launch_mixed_prep(const crx_mixed_kparams& mp, hipStream_t st);
 // crx_plant.hip
 hipError_t crx_launch_plant(const crx_plant_kparams& pk, hipStream_t st);
 hipError_t crx_launch_plant_cars(const crx_plant_kparams_cars& pk, hipStream_t st);
@@ -280,6 +295,19 @@ struct crx_seed_kparams {
     double *log_x, *log_u;
 };
 hipError_t crx_launch_seed(int which, const crx_seed_kparams& sp, hipStream_t st);   // 0 commit, 1 log
+// crx_game.hip: mixed fields (crx.montecarlo.MixedRaces, include/crx.h "Mixed fields"): each car's input from its own controller's law
+struct crx_mixed_commit_kparams {
+    int batch, nlp_stride, ilqr_stride;                // strides: doubles between the plans of two cars in U_nlp / U_ilqr
+    const int32_t* policy;                             // [batch] CRX_POLICY_*
+    const double* x;                                   // [batch][6]: the state the step starts from
+    const double *vt, *eyt;                            // PID: [batch] each, both or neither
+    const double *K, *xt;                              // LQR: [batch][2][6], [batch][6], both or neither
+    const double *U_nlp, *U_ilqr;                      // the solver families' plans
+    const int32_t *nlp_status, *ilqr_status;           // [batch] each; each goes with its plan
+    double* u;                                         // [batch][2]
+    int32_t* ctrl_status;                              // [batch]
+};
+hipError_t crx_launch_mixed_commit(const crx_mixed_commit_kparams& cp, hipStream_t st);
 // crx_game.hip: per-car race statistics of every closed loop (crx.montecarlo.RaceStats): reset, one sample, the batch summary
 struct crx_stats_kparams {
     crx_stats_desc d;

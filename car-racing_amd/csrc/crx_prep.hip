@@ -14,6 +14,8 @@
 //                          racing/offboard.py:51-94, every car the ego of its own NLP.  control/control.py:499-540 (realtime_flag == True)
 //   crx_field_traffic_kernel  the racing game's traffic arrays for such a field: the same roll-out, then per ego the other cars of its race
 //                          as crx_scene_kernel takes them.  planning/overtake_traj_planner.py:77-85
+//   crx_mixed_prep_kernel  a field whose cars each run their own controller: the same roll-out, crx_field_prep_kernel's arrays for the
+//                          MPC-CBF cars, the iLQR family's for the iLQR cars (control/control.py:99-104), and the masks of both launches
 // The comment in front of each kernel has the rest.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -385,6 +387,132 @@ __global__ void __launch_bounds__(256) crx_field_traffic_kernel(const crx_field_
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The solver inputs of a MIXED field (see crx_mixed_prep_dev in include/crx.h, quirks F1-F3, F6, M1, M2): every car of a race under its own
+// policy, so one launch prepares what crx_field_prep_kernel prepares for the MPC-CBF cars, the iLQR family's arrays for the iLQR cars, and the
+// two masks the solver launches run under.  The block shape is the field kernels': one thread per (race, car), a workgroup owns 256 / C whole
+// races, the threads past the last whole race and the races past n_races only take the barriers.
+//   phase 1  zero_input_rollout (crx_num.h), max(N, N_ilqr) + 1 steps: columns 0 .. N are the bits of crx_field_prep_kernel's pred_s, pred_ey.
+//            Before the barrier each ego also decides, from the INPUTS alone (policies, finiteness of the states), which cars its iLQR slots
+//            hold, and leaves that in LDS (il_src: a car index, or -1) -- so the one barrier that publishes the roll-outs publishes the slot
+//            map too.
+//   phase 2  per ego: `clear` and the NLP family as crx_field_prep_kernel writes them (an ego that is not MPCCBF keeps nobody); the iLQR
+//            family's lap offsets and counts; then the wide iLQR rows ([V][N_ilqr + 1] per ego, contiguous over the block's egos) by the
+//            block-strided copy of crx_field_traffic_kernel, each element's source looked up in il_src.
+// The trip counts come from the descriptor and n_races: no loop runs on device data.  Policy codes are compared, never used as an index.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) crx_mixed_prep_kernel(const crx_mixed_kparams mp) {
+    __shared__ double seg_lo[CRX_PLANT_MAX_SEG], seg_hi[CRX_PLANT_MAX_SEG], seg_cv[CRX_PLANT_MAX_SEG];
+    __shared__ signed char il_src[256 * CRX_MAX_OBS];   // [ego of the block][slot]: the car of the ego's race in that slot, -1: empty
+    const crx_mixed_desc& d = mp.d;
+    for (int i = threadIdx.x; i < d.n_seg; i += blockDim.x) {
+        seg_lo[i] = mp.track[6 * i + 3];
+        seg_hi[i] = mp.track[6 * i + 3] + mp.track[6 * i + 4];
+        seg_cv[i] = mp.track[6 * i + 5];
+    }
+    __syncthreads();
+    const int C = d.n_cars, V = C - 1, N1 = d.N + 1, NI1 = d.N_ilqr + 1, NP1 = max(d.N, d.N_ilqr) + 1, per_block = 256 / C;
+    const int r0 = blockIdx.x * per_block;                               // first race of this block
+    const int n_live = min(per_block, mp.n_races - r0) * C;              // its live threads = its cars; r0 < n_races by the grid's size
+    const int t = threadIdx.x;
+    const bool live = t < n_live;
+    const size_t rc0 = (size_t)r0 * C, rc = rc0 + t;                     // this thread's car = problem rc of both solver launches
+    const int c = t % C;
+    const bool ilqr_on = d.N_ilqr > 0;
+    const double L = d.lap_length;
+    int pol = CRX_POLICY_NONE;
+    bool fin_e = true;
+    if (live) {
+        zero_input_rollout(mp.xcurv + 6 * rc, seg_lo, seg_hi, seg_cv, d.n_seg, L, d.dt, NP1, mp.pred_s + rc * NP1, mp.pred_ey + rc * NP1);
+        pol = mp.policy[rc];
+        for (int k = 0; k < 6; k++) fin_e = fin_e && isfinite(mp.xcurv[6 * rc + k]);
+        if (ilqr_on) {   // the slot map of this ego: the finite other cars in car order (all of them, or the last one alone: quirk I1)
+            const bool il_e = pol == CRX_POLICY_ILQR && fin_e;
+            const int o_last = c == C - 1 ? C - 2 : C - 1;
+            int n = 0;
+            for (int o = 0; o < C; o++) {
+                if (o == c) continue;
+                bool fin_o = true;
+                for (int k = 0; k < 6; k++) fin_o = fin_o && isfinite(mp.xcurv[6 * (rc - c + o) + k]);
+                if (il_e && fin_o && (d.ilqr_obstacles != 0 || o == o_last)) il_src[t * V + n++] = (signed char)o;
+            }
+            for (int v = n; v < V; v++) il_src[t * V + v] = -1;
+        }
+    }
+    __syncthreads();   // the predictions and the slot maps of this block's races are written; workgroup scope is all phase 2 needs
+    if (!live) return;
+    const double* xe = mp.xcurv + 6 * rc;
+    const double s_e = xe[4], ey_e = xe[5], margin = d.safety_time * xe[0];
+    double nce;
+    const double dist_ego = lap_fold(s_e, L, nce);
+    const bool cbf = pol == CRX_POLICY_MPCCBF;
+    // a car's own (length, width): dim_or_default (crx_num.h), as crx_field_prep_kernel takes them
+    const double l_e = mp.car_dims ? dim_or_default(mp.car_dims[2 * rc], d.l_sum) : 0.0;
+    const double w_e = mp.car_dims ? dim_or_default(mp.car_dims[2 * rc + 1], d.w_sum) : 0.0;
+    int n = 0;
+    double clr = INFINITY;
+    for (int o = 0; o < C; o++) {   // car order, skipping the ego (quirk F5)
+        if (o == c) continue;
+        const size_t ro = rc - c + o;
+        double l_sum = d.l_sum, w_sum = d.w_sum;
+        if (mp.car_dims) {
+            l_sum = l_e / 2 + dim_or_default(mp.car_dims[2 * ro], d.l_sum) / 2;
+            w_sum = w_e / 2 + dim_or_default(mp.car_dims[2 * ro + 1], d.w_sum) / 2;
+        }
+        if (mp.clear) {
+            const double* xo = mp.xcurv + 6 * ro;
+            double m = fmod(s_e - xo[4] + L / 2, L);   // Python's %: the sign of the divisor
+            if (m < 0.0) m += L;
+            const double a = (m - L / 2) / l_sum, b = (ey_e - xo[5]) / w_sum;
+            double pa = 1.0, pb = 1.0;
+            for (int k = 0; k < d.degree; k++) { pa *= a; pb *= b; }
+            const double h = pa + pb;
+            clr = h < clr ? h : clr;
+        }
+        const double* is = mp.pred_s + ro * NP1;
+        const double* ie = mp.pred_ey + ro * NP1;
+        double off;
+        if (cbf && safety_window(dist_ego, nce, is[0], margin, L, off)) {   // column 0: one estimated step ahead (quirk F2)
+            double* os = mp.obs_s + (rc * V + n) * N1;
+            double* oe = mp.obs_ey + (rc * V + n) * N1;
+            for (int j = 0; j < N1; j++) { os[j] = is[j]; oe[j] = ie[j]; }
+            mp.lap_off[rc * V + n] = off;
+            if (mp.obs_dims) { mp.obs_dims[(rc * V + n) * 2] = l_sum; mp.obs_dims[(rc * V + n) * 2 + 1] = w_sum; }
+            n++;
+        }
+    }
+    for (int v = n; v < V; v++) {
+        double* os = mp.obs_s + (rc * V + v) * N1;
+        double* oe = mp.obs_ey + (rc * V + v) * N1;
+        for (int j = 0; j < N1; j++) { os[j] = 0.0; oe[j] = 0.0; }
+        mp.lap_off[rc * V + v] = 0.0;
+        if (mp.obs_dims) { mp.obs_dims[(rc * V + v) * 2] = 0.0; mp.obs_dims[(rc * V + v) * 2 + 1] = 0.0; }
+    }
+    mp.n_obs[rc] = n;
+    mp.m_nlp[rc] = (pol == CRX_POLICY_MPC_LTI || cbf) ? 1 : 0;
+    if (mp.clear) mp.clear[rc] = clr;
+    if (!ilqr_on) return;
+    // the iLQR family: lap offsets (quirk I5: the obstacle's cycle from column 0 of its roll-out) and the count, from this ego's slot map
+    int ni = 0;
+    for (int v = 0; v < V; v++) {
+        const int o = il_src[t * V + v];
+        double off = 0.0;
+        if (o >= 0) { off = (trunc(s_e / L) - trunc(mp.pred_s[(rc - c + o) * NP1] / L)) * L; ni++; }
+        mp.il_lap_off[rc * V + v] = off;
+    }
+    mp.il_n_obs[rc] = ni;
+    mp.m_ilqr[rc] = pol == CRX_POLICY_ILQR ? 1 : 0;
+    // element e of the block's range of il_obs_s / il_obs_ey [R C][V][N_ilqr + 1]: ego q = e / (V NI1) of the block, slot v, column j
+    const int row_i = V * NI1;
+    for (int e = t; e < n_live * row_i; e += n_live) {
+        const int q = e / row_i, m = e - q * row_i, v = m / NI1, j = m - NI1 * v;
+        const int o = il_src[q * V + v];
+        const size_t src = (rc0 + (q - q % C) + (o >= 0 ? o : 0)) * NP1 + j;
+        mp.il_obs_s[rc0 * row_i + e] = o >= 0 ? mp.pred_s[src] : 0.0;
+        mp.il_obs_ey[rc0 * row_i + e] = o >= 0 ? mp.pred_ey[src] : 0.0;
+    }
+}
+
 hipError_t crx_launch_prep(const crx_prep_kparams& pp, hipStream_t st) { return crx_launch_1d(crx_prep_kernel, pp.n_scen, 1, WAVE, st, pp); }
 hipError_t crx_launch_scene(const crx_scene_kparams& sp, hipStream_t st) { return crx_launch_1d(crx_scene_kernel, sp.n_scen, 1, WAVE, st, sp); }
 hipError_t crx_launch_trackprep(const crx_trackprep_kparams& tp, hipStream_t st) {
@@ -398,4 +526,8 @@ hipError_t crx_launch_field_prep(const crx_field_kparams& fp, hipStream_t st) {
 // the same shape (n_cars in 1 .. CRX_MAX_VEH + 1, checked by the caller)
 hipError_t crx_launch_field_traffic(const crx_field_traffic_kparams& tp, hipStream_t st) {
     return crx_launch_1d(crx_field_traffic_kernel, tp.n_races, 256 / tp.d.n_cars, 256, st, tp);
+}
+// the same shape (n_cars in 1 .. CRX_MAX_OBS + 1, checked by the caller)
+hipError_t crx_launch_mixed_prep(const crx_mixed_kparams& mp, hipStream_t st) {
+    return crx_launch_1d(crx_mixed_prep_kernel, mp.n_races, 256 / mp.d.n_cars, 256, st, mp);
 }

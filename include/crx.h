@@ -44,7 +44,9 @@
 extern "C" {
 #endif
 
-#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_field_traffic, crx_field_traffic_dev (field games: the racing game's traffic arrays when every car of
+#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_mixed_desc, crx_mixed_desc_default, crx_mixed_prep, crx_mixed_prep_dev, crx_mixed_commit_dev and
+                          CRX_POLICY_* (mixed fields: every car of a race under its own controller) -- new entry points only.
+                          0.4.0 (additive, same number): crx_field_traffic, crx_field_traffic_dev (field games: the racing game's traffic arrays when every car of
                           a race plays it) -- new entry points only.
                           0.4.0 (additive, same number): crx_seed_commit_dev, crx_seed_log_dev and CRX_SEED_* (seed laps: every car's own PID lap and
                           MPC-LTI lap become its own safe set) -- new entry points only.
@@ -894,6 +896,83 @@ int crx_field_traffic(const crx_field_desc* d, int n_races, const double* track,
                       double* veh_xcurv, double* pred_s, double* pred_ey, int32_t* n_all);
 int crx_field_traffic_dev(const crx_field_desc* d, int n_races, const double* track, const double* xcurv, double* pred_s_car,
                           double* pred_ey_car, double* veh_xcurv, double* pred_s, double* pred_ey, int32_t* n_all, void* stream);
+
+/*
+ * Mixed fields: every car of a race under its OWN controller, as the reference's simulator holds them (CarRacingSim.add_vehicle,
+ * ModelBase.set_ctrl_policy with PIDTracking / LQRTracking / MPCTracking / iLQRRacing / MPCCBFRacing, racing/offboard.py:14-45; sim()
+ * steps all of them together, :114-131).  policy [R][C], int32, one code per car:
+ */
+#define CRX_POLICY_NONE 0     /* applies zero input: a car that coasts */
+#define CRX_POLICY_PID 1      /* control.pid (control/control.py:15-25) */
+#define CRX_POLICY_LQR 2      /* control.lqr: u = -K (x - xt) */
+#define CRX_POLICY_MPC_LTI 3  /* control.mpc_lti: the MPC-CBF NLP with its obstacle count forced to 0 (MPCTrackingParam and MPCCBFRacingParam share Q and R) */
+#define CRX_POLICY_MPCCBF 4   /* control.mpccbf */
+#define CRX_POLICY_ILQR 5     /* control.ilqr */
+#define CRX_POLICY_COUNT 6
+/*
+ * crx_mixed_prep[_dev]: ONE launch for n_races races of C = n_cars cars (race-major, car-minor, as in crx_field_prep) that serves every
+ * policy of the step: the roll-out of every car, the obstacle arrays of one crx_cbf_solve* launch over all R C cars (mask m_nlp) and
+ * those of one crx_ilqr_solve* launch over all R C cars (mask m_ilqr).  V = C - 1, NP = max(N, N_ilqr).
+ *   track [n_seg][6];  xcurv [R][C][6];  policy [R][C];  car_dims [R][C][2] or NULL
+ *   pred_s, pred_ey [R][C][NP+1]     out: every car's zero-input roll-out, whatever its policy; columns 0 .. N are pred_s, pred_ey of
+ *                                    crx_field_prep (the same function, run further)
+ *   the NLP family      obs_s, obs_ey [R C][V][N+1];  lap_off [R C][V];  n_obs [R C];  obs_dims [R C][V][2] iff car_dims;  m_nlp [R C]
+ *                       An MPCCBF car gets exactly crx_field_prep's arrays (window test, lap offset, packing: F1-F7).  Every other
+ *                       car gets n_obs = 0 and zero slots.  m_nlp = 1 for MPC_LTI and MPCCBF cars, else 0.
+ *   the iLQR family     (N_ilqr > 0; with N_ilqr == 0 all five may be NULL and none is written)
+ *                       il_obs_s, il_obs_ey [R C][V][N_ilqr+1];  il_lap_off [R C][V];  il_n_obs [R C];  m_ilqr [R C]
+ *                       An ILQR car gets the other cars of its race in car order with NO distance window (control.ilqr applies
+ *                       none), columns 0 .. N_ilqr of their roll-outs, lap_off = (trunc(s_ego / L) - trunc(pred_s[o][0] / L)) L (I5),
+ *                       packed to the front: all of them with ilqr_obstacles = 1, the LAST other car in car order alone with
+ *                       ilqr_obstacles = 0 (quirk I1).  A car whose state has a non-finite component is kept by nobody -- with
+ *                       ilqr_obstacles = 0, a non-finite last other car leaves il_n_obs = 0 -- and an ILQR car with such a state keeps
+ *                       nobody.  Every other car gets il_n_obs = 0 and zero slots.  m_ilqr = 1 for ILQR cars, else 0.
+ *   clear [R C]         out, may be NULL: as crx_field_prep's
+ * With C == 1 the [V] arrays hold nothing and may be NULL.  A policy code outside 0 .. CRX_POLICY_COUNT - 1 counts as CRX_POLICY_NONE;
+ * device-resident codes cannot be validated on the host (the host-pointer entry refuses them), they are compared and index nothing.
+ * Quirks kept:
+ *   F1-F3, F6  as in crx_field_prep: snapshot, column 0 one step ahead, the wrap after every roll-out step, the first matching segment.
+ *   M1  the roll-out handed to iLQR is the realtime_flag == True form.  control.ilqr calls get_trajectory_nsteps(time, timestep, n)
+ *       (control.py:99-104), which the driven model does not accept: the situation of G2.
+ *   M2  iLQR has ONE l_sum / w_sum per launch, its descriptor's (I1: the reference takes them from "car1"); car_dims feeds the NLP
+ *       family and `clear` only.
+ */
+typedef struct crx_mixed_desc {
+    int32_t N;               /* horizon of the NLP family, 1 .. CRX_MAX_N */
+    int32_t N_ilqr;          /* horizon of the iLQR family, 0 .. CRX_ILQR_MAX_N; 0: no iLQR arrays */
+    int32_t n_cars;          /* C, 1 .. CRX_MAX_OBS + 1 */
+    int32_t n_seg;           /* rows of the track table, 1 .. 64 */
+    int32_t degree;          /* 6: exponent of `clear` (2, 4, 6 or 8) */
+    int32_t ilqr_obstacles;  /* 0: quirk I1, the last other car in car order only (control.py:99-104); 1: all others */
+    double lap_length;
+    double dt;               /* 0.1 */
+    double safety_time;      /* 2.0 (control.py:499) */
+    double l_sum;            /* 0.4 */
+    double w_sum;            /* 0.2 */
+} crx_mixed_desc;
+void crx_mixed_desc_default(crx_mixed_desc* d, int N, int N_ilqr, int n_cars, int n_seg, double lap_length);
+int crx_mixed_prep(const crx_mixed_desc* d, int n_races, const double* track, const double* xcurv, const int32_t* policy, const double* car_dims,
+                   double* pred_s, double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims,
+                   int32_t* m_nlp, double* il_obs_s, double* il_obs_ey, double* il_lap_off, int32_t* il_n_obs, int32_t* m_ilqr, double* clear);
+int crx_mixed_prep_dev(const crx_mixed_desc* d, int n_races, const double* track, const double* xcurv, const int32_t* policy,
+                       const double* car_dims, double* pred_s, double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs,
+                       double* obs_dims, int32_t* m_nlp, double* il_obs_s, double* il_obs_ey, double* il_lap_off, int32_t* il_n_obs,
+                       int32_t* m_ilqr, double* clear, void* stream);
+/*
+ * crx_mixed_commit_dev: after the solver launches, before the plant: u [batch][2] and ctrl_status [batch] from each car's own law, every
+ * operation rounded on its own (no fused multiply-add).  x [batch][6] is the state the step starts from.
+ *   PID               u = (-0.6 (x[5] - eyt) - 0.9 x[3], 1.5 (vt - x[0])), vt, eyt [batch]: crx_seed_commit_dev's law      CRX_CONVERGED
+ *   LQR               u = -K (x - xt), K [batch][2][6], xt [batch][6]; the sum runs c = 0 .. 5 as crx_lqr_step_dev's      CRX_CONVERGED
+ *   MPC_LTI, MPCCBF   U_nlp[b * nlp_stride + 0, 1]: stage 0 of the plan (nlp_stride = 2 N for a solver's U)                 nlp_status[b]
+ *   ILQR              U_ilqr[b * ilqr_stride + 0, 1]                                                                        ilqr_status[b]
+ *   NONE              zero                                                                                                  CRX_SKIPPED
+ * The last iterate of a failed solve is applied, as control.py:600-603 does.  A policy code out of range applies zero and reports
+ * CRX_SKIPPED.  Each family's pair of arrays -- (vt, eyt), (K, xt), (U_nlp, nlp_status), (U_ilqr, ilqr_status) -- may be NULL, both or
+ * neither: a car whose family is NULL applies zero and reports CRX_SKIPPED.  Strides of given families are >= 2.
+ */
+int crx_mixed_commit_dev(int batch, const int32_t* policy, const double* x, const double* vt, const double* eyt, const double* K,
+                         const double* xt, const double* U_nlp, int nlp_stride, const int32_t* nlp_status, const double* U_ilqr,
+                         int ilqr_stride, const int32_t* ilqr_status, double* u, int32_t* ctrl_status, void* stream);
 
 /*
  * Inputs of control.mpc_multi_agents' NLP (crx_cbf_solve with per_stage_target = 1) from the planner's outputs, on the device

@@ -351,38 +351,58 @@ def mpccbf_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, car
     return dict(logs, laps=r.laps.cpu().numpy())
 
 
-class FieldRaces(_Plant):
-    """R races of C cars that ALL drive themselves under MPC-CBF: every car is the ego of its own NLP and an obstacle of the C - 1
-    others, predicted by the zero-input roll-out of the reference's driven model (racing/offboard.py:51-94) as control.mpccbf consumes it
-    with realtime_flag == True (control/control.py:512-514).  The plant batch is R*C, race-major, car-minor; all cars of a step see
-    the states at the start of the step (include/crx.h, crx_field_prep_dev, quirks F1-F7).  min_clear [R*C]: each car's smallest
-    super-ellipse value against the cars of its race over the states the steps so far STARTED from (below 1: contact)."""
+class _Field(_Plant):
+    """What FieldRaces and MixedRaces share: R races of C cars, the plant batch R*C race-major and car-minor; xt [R*C,6], the cars' targets;
+    min_clear [R*C]: each car's smallest super-ellipse value against the cars of its race over the states the steps so far STARTED from
+    (below 1: contact); fd: the loop's field or mixed descriptor, for its l_sum, w_sum."""
 
-    def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, n_cars, vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1,
-                 device=None, noise_seed=None, models=None, plant_params=None, car_dims=None):
+    def _field_init(self, track_table, lap_length, track_width, timestep, xcurv0, xglob0, n_cars, vt, eyt, N, car_dims, noise_seed, device,
+                    plant_params, n_races=None):
+        """n_races: the races the caller's other arguments make (MixedRaces' policy); None: as many as xcurv0 holds.  Returns the device."""
         Cn = int(n_cars)
         if not 1 <= Cn <= abi.CRX_MAX_OBS + 1:
             raise ValueError("1 .. %d cars per race" % (abi.CRX_MAX_OBS + 1))
         x0, g0 = (np.asarray(a, dtype=float).reshape(-1, 6) for a in (xcurv0, xglob0))   # [R*C,6] or [R,C,6]
-        if x0.shape[0] % Cn or g0.shape != x0.shape:
-            raise ValueError("xcurv0, xglob0: %d and %d cars do not make races of %d" % (x0.shape[0], g0.shape[0], Cn))
+        R = x0.shape[0] // Cn if n_races is None else n_races
+        if x0.shape[0] != R * Cn or g0.shape != x0.shape:
+            raise ValueError("xcurv0, xglob0: %d and %d cars" % (x0.shape[0], g0.shape[0])
+                             + (" do not make races of %d" % Cn if n_races is None else ", policy has %d x %d" % (R, Cn)))
         dev = self._plant_init(track_table, lap_length, timestep, x0, g0, noise_seed, device, plant_params)
-        Bn, R = self.batch, self.batch // Cn
         self.N, self.n_races, self.n_cars, self.track_width = N, R, Cn, track_width
-        self.desc = abi.cbf_desc(N, Cn - 1, A, B, alpha=alpha, margin=0.2, ey_max=track_width)
-        self.fdesc = abi.field_desc(N, Cn, self.tab.shape[0], lap_length, dt=timestep)
         # vt, eyt: scalars or one value per car [R,C] -- different target speeds are what makes the cars meet
-        xt = np.zeros((Bn, 6))
+        xt = np.zeros((self.batch, 6))
         xt[:, 0] = np.broadcast_to(np.asarray(vt, dtype=float), (R, Cn)).reshape(-1)
         xt[:, 5] = np.broadcast_to(np.asarray(eyt, dtype=float), (R, Cn)).reshape(-1)
         self.xt = _dev(xt, dev)
+        # car_dims [R,C,2]: (length, width) of every car; None: the descriptor's l_sum, w_sum for every pair
+        self.car_dims = None if car_dims is None else _dev(np.asarray(car_dims, dtype=float).reshape(R, Cn, 2), dev)
+        self.min_clear = torch.full((self.batch,), float("inf"), dtype=torch.float64, device=dev)
+        return dev
+
+    def _join_clear(self, clear):
+        torch.minimum(self.min_clear, clear, out=self.min_clear)
+
+    def stats_inputs(self):
+        return super().stats_inputs(n_cars=self.n_cars, car_dims=self.car_dims, l_sum=self.fd.l_sum, w_sum=self.fd.w_sum)
+
+
+class FieldRaces(_Field):
+    """R races of C cars that ALL drive themselves under MPC-CBF: every car is the ego of its own NLP and an obstacle of the C - 1
+    others, predicted by the zero-input roll-out of the reference's driven model (racing/offboard.py:51-94) as control.mpccbf consumes it
+    with realtime_flag == True (control/control.py:512-514).  The plant batch is R*C, race-major, car-minor; all cars of a step see
+    the states at the start of the step (include/crx.h, crx_field_prep_dev, quirks F1-F7).  min_clear [R*C]: see _Field."""
+
+    def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, n_cars, vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1,
+                 device=None, noise_seed=None, models=None, plant_params=None, car_dims=None):
+        dev = self._field_init(track_table, lap_length, track_width, timestep, xcurv0, xglob0, n_cars, vt, eyt, N, car_dims, noise_seed,
+                               device, plant_params)
+        Bn, R, Cn = self.batch, self.n_races, self.n_cars
+        self.desc = abi.cbf_desc(N, Cn - 1, A, B, alpha=alpha, margin=0.2, ey_max=track_width)
+        self.fdesc = self.fd = abi.field_desc(N, Cn, self.tab.shape[0], lap_length, dt=timestep)
         self.ws = torch_api.CbfWorkspace(self.desc, Bn, dev)
         # models = (A [R*C,6,6], B [R*C,6,2]): every car's controller on its own model, as in MpccbfRaces
         self.models = None if models is None else torch_api.CbfModels(self.desc, *_models(models[0], models[1], Bn, dev))
-        # car_dims [R,C,2]: (length, width) of every car; None: the descriptor's l_sum, w_sum for every pair
-        self.car_dims = None if car_dims is None else _dev(np.asarray(car_dims, dtype=float).reshape(R, Cn, 2), dev)
         self.fws = torch_api.FieldWorkspace(self.fdesc, R, dev, dims=car_dims is not None)
-        self.min_clear = torch.full((Bn,), float("inf"), dtype=torch.float64, device=dev)
         self.u = None
 
     def step(self):
@@ -394,10 +414,7 @@ class FieldRaces(_Plant):
                                 order=_order(self, self.ws.iters), models=self.models, obs_dims=f.obs_dims)
         self._advance(self.ws.U, 2 * self.N)
         self.u = self.ws.U[:, 0, :]
-        torch.minimum(self.min_clear, f.clear, out=self.min_clear)
-
-    def stats_inputs(self):
-        return super().stats_inputs(n_cars=self.n_cars, car_dims=self.car_dims, l_sum=self.fdesc.l_sum, w_sum=self.fdesc.w_sum)
+        self._join_clear(f.clear)
 
 
 def field_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, n_cars, steps, vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1,
@@ -412,7 +429,7 @@ def field_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, n_ca
     return dict(logs, laps=r.laps.cpu().numpy(), min_clear=r.min_clear.cpu().numpy())
 
 
-class MixedRaces(_Plant):
+class MixedRaces(_Field):
     """R races of C cars, every car under its OWN controller, as the reference's simulator holds its vehicles (CarRacingSim.add_vehicle +
     ModelBase.set_ctrl_policy, racing/offboard.py:14-45; sim() steps them together, :114-131): policy [R,C] of abi.POLICY_* codes or names
     ("none", "pid", "lqr", "mpc_lti", "mpccbf", "ilqr").  The plant batch is R*C, race-major, car-minor; all cars of a step see the states at
@@ -427,22 +444,15 @@ class MixedRaces(_Plant):
         if pol.ndim != 2 or not 1 <= pol.shape[1] <= abi.CRX_MAX_OBS + 1:
             raise ValueError("policy: [R,C] with 1 .. %d cars per race" % (abi.CRX_MAX_OBS + 1))
         R, Cn = pol.shape
-        x0, g0 = (np.asarray(a, dtype=float).reshape(-1, 6) for a in (xcurv0, xglob0))   # [R*C,6] or [R,C,6]
-        if x0.shape[0] != R * Cn or g0.shape != x0.shape:
-            raise ValueError("xcurv0, xglob0: %d and %d cars, policy has %d x %d" % (x0.shape[0], g0.shape[0], R, Cn))
-        dev = self._plant_init(track_table, lap_length, timestep, x0, g0, noise_seed, device, plant_params)
+        # xt is the target of the NLP, iLQR and LQR cars, (vt, eyt) the PID cars'
+        dev = self._field_init(track_table, lap_length, track_width, timestep, xcurv0, xglob0, Cn, vt, eyt, N, car_dims, noise_seed, device,
+                               plant_params, n_races=R)
         Bn = self.batch
-        self.N, self.n_races, self.n_cars, self.track_width = N, R, Cn, track_width
         has = lambda *codes: bool(np.isin(pol, codes).any())   # noqa: E731
         has_nlp, has_ilqr, has_lqr, has_pid = has(abi.POLICY_MPC_LTI, abi.POLICY_MPCCBF), has(abi.POLICY_ILQR), has(abi.POLICY_LQR), has(abi.POLICY_PID)
         self.policy = _dev(pol.reshape(-1), dev, dtype=torch.int32)
-        self.mdesc = abi.mixed_desc(N, ilqr_N if has_ilqr else 0, Cn, self.tab.shape[0], lap_length, ilqr_obstacles=ilqr_obstacles, dt=timestep)
-        # vt, eyt: scalars or one value per car [R,C], as in FieldRaces; xt is the target of the NLP, iLQR and LQR cars, (vt, eyt) the PID cars'
-        xt = np.zeros((Bn, 6))
-        xt[:, 0] = np.broadcast_to(np.asarray(vt, dtype=float), (R, Cn)).reshape(-1)
-        xt[:, 5] = np.broadcast_to(np.asarray(eyt, dtype=float), (R, Cn)).reshape(-1)
-        self.xt = _dev(xt, dev)
-        self.vt, self.eyt = (_dev(xt[:, 0], dev), _dev(xt[:, 5], dev)) if has_pid else (None, None)
+        self.mdesc = self.fd = abi.mixed_desc(N, ilqr_N if has_ilqr else 0, Cn, self.tab.shape[0], lap_length, ilqr_obstacles=ilqr_obstacles, dt=timestep)
+        self.vt, self.eyt = (self.xt[:, 0].contiguous(), self.xt[:, 5].contiguous()) if has_pid else (None, None)
         # models = (A [R*C,6,6], B [R*C,6,2]): every car's controller on its own model -- the NLP's, the iLQR's and the LQR design's
         mAB = None if models is None else _models(models[0], models[1], Bn, dev)
         self.desc = self.ws = self.models = None
@@ -459,10 +469,8 @@ class MixedRaces(_Plant):
         if has_lqr:   # one design launch, here: the LQR cars' gains (the other cars' rows stay zero)
             m_lqr = _dev((pol.reshape(-1) == abi.POLICY_LQR).astype(np.int32), dev, dtype=torch.int32)
             self.K = torch_api.lqr_design_dev(abi.lqr_desc(), *(mAB if mAB is not None else _models(A, B, Bn, dev)), active=m_lqr).K
-        # car_dims [R,C,2]: (length, width) of every car, for the NLP family and `clear` (M2); None: the descriptor's l_sum, w_sum
-        self.car_dims = None if car_dims is None else _dev(np.asarray(car_dims, dtype=float).reshape(R, Cn, 2), dev)
+        # car_dims serves the NLP family and `clear` (M2)
         self.mws = torch_api.MixedWorkspace(self.mdesc, R, dev, dims=car_dims is not None)
-        self.min_clear = torch.full((Bn,), float("inf"), dtype=torch.float64, device=dev)
         self.u = torch.zeros((Bn, 2), dtype=torch.float64, device=dev)
         self.status = torch.zeros(Bn, dtype=torch.int32, device=dev)
 
@@ -483,10 +491,7 @@ class MixedRaces(_Plant):
                                    nlp=None if self.ws is None else (self.ws.U, self.ws.status),
                                    ilqr=None if self.iws is None else (self.iws.U, self.iws.status))
         self._advance(self.u, 2)
-        torch.minimum(self.min_clear, m.clear, out=self.min_clear)
-
-    def stats_inputs(self):
-        return super().stats_inputs(n_cars=self.n_cars, car_dims=self.car_dims, l_sum=self.mdesc.l_sum, w_sum=self.mdesc.w_sum)
+        self._join_clear(m.clear)
 
 
 def mixed_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, policy, steps, vt=0.8, eyt=0.0, N=10, ilqr_N=50, ilqr_max_iter=150,

@@ -522,15 +522,15 @@ class FieldWorkspace:
     """Outputs of field_prep_dev for n_races races of desc.n_cars cars: the predictions pred_s, pred_ey [R,C,N+1] and the obstacle
     inputs of cbf_solve_dev for the R*C problems, in its layout (batch R*C, race-major, car-minor): obs_s, obs_ey [R*C,V,N+1], lap_off
     [R*C,V], n_obs [R*C] with V = C - 1; clear [R*C] (None with clear=False: not computed); obs_dims [R*C,V,2] with dims=True (the cars bring their own
-    dimensions), else None."""
+    dimensions), else None.  n_pred: the columns of pred_s, pred_ey (None: N + 1; MixedWorkspace rolls out further)."""
 
-    def __init__(self, desc, n_races, device, dims=False, clear=True):
+    def __init__(self, desc, n_races, device, dims=False, clear=True, n_pred=None):
         N1, Cn = desc.N + 1, desc.n_cars
         Bn, V = n_races * Cn, Cn - 1
         f64 = dict(dtype=torch.float64, device=device)
         self.n_races = n_races
-        self.pred_s = torch.zeros((n_races, Cn, N1), **f64)
-        self.pred_ey = torch.zeros((n_races, Cn, N1), **f64)
+        self.pred_s = torch.zeros((n_races, Cn, n_pred or N1), **f64)
+        self.pred_ey = torch.zeros((n_races, Cn, n_pred or N1), **f64)
         self.obs_s = torch.zeros((Bn, V, N1), **f64)
         self.obs_ey = torch.zeros((Bn, V, N1), **f64)
         self.lap_off = torch.zeros((Bn, V), **f64)
@@ -539,23 +539,28 @@ class FieldWorkspace:
         self.clear = torch.zeros(Bn, **f64) if clear else None
 
 
+def _chk_field_ws(desc, ws, n_pred):
+    """The arrays FieldWorkspace allocates, as field_prep_dev and mixed_prep_dev take them (n_pred: the roll-out's columns)."""
+    R, Cn, N1 = ws.n_races, desc.n_cars, desc.N + 1
+    Bn, V = R * Cn, Cn - 1
+    for name, shape in (("pred_s", (R, Cn, n_pred)), ("pred_ey", (R, Cn, n_pred)), ("obs_s", (Bn, V, N1)), ("obs_ey", (Bn, V, N1)),
+                        ("lap_off", (Bn, V)), ("obs_dims", (Bn, V, 2)), ("clear", (Bn,))):
+        if getattr(ws, name) is not None:
+            _chk(getattr(ws, name), torch.float64, shape, "ws." + name)
+    _chk(ws.n_obs, torch.int32, (Bn,), "ws.n_obs")
+
+
 def field_prep_dev(desc, track, xcurv, ws, car_dims=None):
     """crx_field_prep_dev (include/crx.h F1-F7): xcurv [R*C,6] (race-major, car-minor), track [n_seg,6], car_dims [R,C,2] (length, width
     per car) with a FieldWorkspace(dims=True), None with dims=False.  Writes ws and returns it."""
-    R, Cn, N1 = ws.n_races, desc.n_cars, desc.N + 1
-    Bn, V = R * Cn, Cn - 1
+    R, Cn = ws.n_races, desc.n_cars
     _chk(track, torch.float64, (desc.n_seg, 6), "track")
-    _chk(xcurv, torch.float64, (Bn, 6), "xcurv")
+    _chk(xcurv, torch.float64, (R * Cn, 6), "xcurv")
     if (car_dims is None) != (ws.obs_dims is None):
         raise ValueError("car_dims goes with a FieldWorkspace(dims=True), no car_dims with dims=False")
     if car_dims is not None:
         _chk(car_dims, torch.float64, (R, Cn, 2), "car_dims")
-        _chk(ws.obs_dims, torch.float64, (Bn, V, 2), "ws.obs_dims")
-    for name, shape in (("pred_s", (R, Cn, N1)), ("pred_ey", (R, Cn, N1)), ("obs_s", (Bn, V, N1)), ("obs_ey", (Bn, V, N1)), ("lap_off", (Bn, V)),
-                        ("clear", (Bn,))):
-        if getattr(ws, name) is not None:
-            _chk(getattr(ws, name), torch.float64, shape, "ws." + name)
-    _chk(ws.n_obs, torch.int32, (Bn,), "ws.n_obs")
+    _chk_field_ws(desc, ws, desc.N + 1)
     _call("crx_field_prep_dev", C.byref(desc), C.c_int(R), _ptr(track), _ptr(xcurv), _ptr(car_dims), _ptr(ws.pred_s), _ptr(ws.pred_ey),
           _ptr(ws.obs_s), _ptr(ws.obs_ey), _ptr(ws.lap_off), _ptr(ws.n_obs), _ptr(ws.obs_dims), _ptr(ws.clear), _stream())
     return ws
@@ -596,40 +601,32 @@ def field_traffic_dev(desc, track, xcurv, ws):
     return ws
 
 
-class MixedWorkspace:
+class MixedWorkspace(FieldWorkspace):
     """Outputs of mixed_prep_dev for n_races races of desc.n_cars cars, batch R*C race-major and car-minor, V = C - 1: the roll-outs pred_s,
     pred_ey [R,C,NP+1] (NP = max(N, N_ilqr)); the NLP family in cbf_solve_dev's layout -- obs_s, obs_ey [R*C,V,N+1], lap_off [R*C,V], n_obs,
     m_nlp [R*C], obs_dims [R*C,V,2] with dims=True, else None; the iLQR family in ilqr_solve_dev's layout when desc.N_ilqr > 0, else None --
     il_obs_s, il_obs_ey [R*C,V,N_ilqr+1], il_lap_off [R*C,V], il_n_obs, m_ilqr [R*C]; clear [R*C] (None with clear=False)."""
 
     def __init__(self, desc, n_races, device, dims=False, clear=True):
-        N1, NI1, Cn = desc.N + 1, desc.N_ilqr + 1, desc.n_cars
-        Bn, V, NP1 = n_races * Cn, Cn - 1, max(N1, NI1)
+        NI1, Cn = desc.N_ilqr + 1, desc.n_cars
+        Bn, V = n_races * Cn, Cn - 1
+        super().__init__(desc, n_races, device, dims=dims, clear=clear, n_pred=max(desc.N + 1, NI1))
         f64 = dict(dtype=torch.float64, device=device)
         i32 = dict(dtype=torch.int32, device=device)
-        self.n_races = n_races
-        self.pred_s = torch.zeros((n_races, Cn, NP1), **f64)
-        self.pred_ey = torch.zeros((n_races, Cn, NP1), **f64)
-        self.obs_s = torch.zeros((Bn, V, N1), **f64)
-        self.obs_ey = torch.zeros((Bn, V, N1), **f64)
-        self.lap_off = torch.zeros((Bn, V), **f64)
-        self.n_obs = torch.zeros(Bn, **i32)
         self.m_nlp = torch.zeros(Bn, **i32)
-        self.obs_dims = torch.zeros((Bn, V, 2), **f64) if dims else None
         il = desc.N_ilqr > 0
         self.il_obs_s = torch.zeros((Bn, V, NI1), **f64) if il else None
         self.il_obs_ey = torch.zeros((Bn, V, NI1), **f64) if il else None
         self.il_lap_off = torch.zeros((Bn, V), **f64) if il else None
         self.il_n_obs = torch.zeros(Bn, **i32) if il else None
         self.m_ilqr = torch.zeros(Bn, **i32) if il else None
-        self.clear = torch.zeros(Bn, **f64) if clear else None
 
 
 def mixed_prep_dev(desc, track, xcurv, policy, ws, car_dims=None):
     """crx_mixed_prep_dev (include/crx.h "Mixed fields"): xcurv [R*C,6] (race-major, car-minor), track [n_seg,6], policy int32 [R*C] of
     abi.POLICY_* codes, car_dims [R,C,2] with a MixedWorkspace(dims=True), None with dims=False.  Writes ws and returns it."""
-    R, Cn, N1, NI1 = ws.n_races, desc.n_cars, desc.N + 1, desc.N_ilqr + 1
-    Bn, V, NP1 = R * Cn, Cn - 1, max(N1, NI1)
+    R, Cn, NI1 = ws.n_races, desc.n_cars, desc.N_ilqr + 1
+    Bn, V = R * Cn, Cn - 1
     _chk(track, torch.float64, (desc.n_seg, 6), "track")
     _chk(xcurv, torch.float64, (Bn, 6), "xcurv")
     _chk(policy, torch.int32, (Bn,), "policy")
@@ -639,12 +636,11 @@ def mixed_prep_dev(desc, track, xcurv, policy, ws, car_dims=None):
         raise ValueError("the workspace was built for another N_ilqr: its iLQR arrays go with desc.N_ilqr > 0")
     if car_dims is not None:
         _chk(car_dims, torch.float64, (R, Cn, 2), "car_dims")
-    f64s = [("pred_s", (R, Cn, NP1)), ("pred_ey", (R, Cn, NP1)), ("obs_s", (Bn, V, N1)), ("obs_ey", (Bn, V, N1)), ("lap_off", (Bn, V)),
-            ("obs_dims", (Bn, V, 2)), ("il_obs_s", (Bn, V, NI1)), ("il_obs_ey", (Bn, V, NI1)), ("il_lap_off", (Bn, V)), ("clear", (Bn,))]
-    for name, shape in f64s:
+    _chk_field_ws(desc, ws, max(desc.N + 1, NI1))
+    for name, shape in (("il_obs_s", (Bn, V, NI1)), ("il_obs_ey", (Bn, V, NI1)), ("il_lap_off", (Bn, V))):
         if getattr(ws, name) is not None:
             _chk(getattr(ws, name), torch.float64, shape, "ws." + name)
-    for name in ("n_obs", "m_nlp", "il_n_obs", "m_ilqr"):
+    for name in ("m_nlp", "il_n_obs", "m_ilqr"):
         if getattr(ws, name) is not None:
             _chk(getattr(ws, name), torch.int32, (Bn,), "ws." + name)
     _call("crx_mixed_prep_dev", C.byref(desc), C.c_int(R), _ptr(track), _ptr(xcurv), _ptr(policy), _ptr(car_dims), _ptr(ws.pred_s), _ptr(ws.pred_ey),

@@ -1055,33 +1055,49 @@ void crx_field_desc_default(crx_field_desc* d, int N, int n_cars, int n_seg, dou
     d->lap_length = lap_length; d->dt = 0.1; d->safety_time = 2.0; d->l_sum = 0.4; d->w_sum = 0.2;
 }
 
-// The descriptor and the race count of both field entry families (crx_field_prep*, crx_field_traffic*)
-static int check_field_desc(const crx_field_desc* d, int n_races) {
-    auto positive = [](double v) { return v > 0.0 && isfinite(v); };
-    if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
-    if (d->N < 1 || d->N > CRX_MAX_N) return fail(CRX_ERR_ARG, "N=%d outside [1,%d]", d->N, CRX_MAX_N);
-    if (d->n_cars < 1 || d->n_cars > CRX_MAX_OBS + 1) return fail(CRX_ERR_ARG, "n_cars=%d outside [1,%d]", d->n_cars, CRX_MAX_OBS + 1);
-    if (d->n_seg < 1 || d->n_seg > CRX_PLANT_MAX_SEG) return fail(CRX_ERR_ARG, "n_seg=%d outside [1,%d]", d->n_seg, CRX_PLANT_MAX_SEG);
-    if (d->degree < 2 || d->degree > 8 || (d->degree & 1)) return fail(CRX_ERR_ARG, "degree must be 2, 4, 6 or 8");
-    if (!positive(d->lap_length) || !positive(d->dt) || !positive(d->l_sum) || !positive(d->w_sum))
+static bool positive(double v) { return v > 0.0 && isfinite(v); }
+// The scalars of crx_field_desc and crx_mixed_desc and the race count, in the order both families refuse them.  A field is a mixed field
+// without iLQR cars: its N_ilqr = 0 and ilqr_obstacles = 0 pass the two checks it does not have.
+static int check_field_scalars(int N, int N_ilqr, int n_cars, int n_seg, int degree, int ilqr_obstacles, double lap_length, double dt, double l_sum,
+                               double w_sum, int n_races) {
+    if (N < 1 || N > CRX_MAX_N) return fail(CRX_ERR_ARG, "N=%d outside [1,%d]", N, CRX_MAX_N);
+    if (N_ilqr < 0 || N_ilqr > CRX_ILQR_MAX_N) return fail(CRX_ERR_ARG, "N_ilqr=%d outside [0,%d]", N_ilqr, CRX_ILQR_MAX_N);
+    if (n_cars < 1 || n_cars > CRX_MAX_OBS + 1) return fail(CRX_ERR_ARG, "n_cars=%d outside [1,%d]", n_cars, CRX_MAX_OBS + 1);
+    if (n_seg < 1 || n_seg > CRX_PLANT_MAX_SEG) return fail(CRX_ERR_ARG, "n_seg=%d outside [1,%d]", n_seg, CRX_PLANT_MAX_SEG);
+    if (degree < 2 || degree > 8 || (degree & 1)) return fail(CRX_ERR_ARG, "degree must be 2, 4, 6 or 8");
+    if (ilqr_obstacles != 0 && ilqr_obstacles != 1) return fail(CRX_ERR_ARG, "ilqr_obstacles=%d must be 0 or 1", ilqr_obstacles);
+    if (!positive(lap_length) || !positive(dt) || !positive(l_sum) || !positive(w_sum))
         return fail(CRX_ERR_ARG, "lap_length, dt, l_sum and w_sum must be positive and finite");
     if (n_races < 0) return fail(CRX_ERR_ARG, "n_races < 0");
     return 0;
 }
 
-// Arguments alone, before the library's state is looked at (the answer is the same with and without a device).  host_dims: the
-// [n_races][n_cars][2] rows of the host-pointer entry (NULL: none, or on the device where they cannot be read)
+// The arrays of the NLP family (crx_field_prep*, crx_mixed_prep*): arguments alone, so the answer is the same with and without a device.
+// null_in: an array every call of the entry needs is NULL; null_ilqr: one of the iLQR family's, refused at its place in crx_mixed_prep*'s
+// order.  host_dims: the [n_races][n_cars][2] rows of the host-pointer entry (NULL: none, or on the device where they cannot be read)
+static int check_field_arrays(int n_races, int n_cars, int N_ilqr, bool null_in, bool null_ilqr, arr car_dims, arr obs_s, arr obs_ey, arr lap_off,
+                              arr obs_dims, const double* host_dims) {
+    if (n_cars > 1 && !car_dims != !obs_dims)   // (one car: obs_dims holds nothing, like the other [V] arrays)
+        return fail(CRX_ERR_ARG, "car_dims and obs_dims go together: both or neither (%s is NULL)", car_dims ? "obs_dims" : "car_dims");
+    if (n_races > 0 && (null_in || (n_cars > 1 && any_null(obs_s, obs_ey, lap_off)))) return fail(CRX_ERR_ARG, "NULL array argument");
+    if (n_races > 0 && N_ilqr > 0 && null_ilqr) return fail(CRX_ERR_ARG, "NULL array argument of the iLQR family (N_ilqr=%d)", N_ilqr);
+    for (size_t i = 0; host_dims && i < (size_t)n_races * n_cars; i++)
+        if (!positive(host_dims[2 * i]) || !positive(host_dims[2 * i + 1]))
+            return fail(CRX_ERR_ARG, "car_dims of car %zu of race %zu: length and width must be positive and finite", i % n_cars, i / n_cars);
+    return 0;
+}
+
+// The descriptor and the race count of both field entry families (crx_field_prep*, crx_field_traffic*)
+static int check_field_desc(const crx_field_desc* d, int n_races) {
+    if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
+    return check_field_scalars(d->N, 0, d->n_cars, d->n_seg, d->degree, 0, d->lap_length, d->dt, d->l_sum, d->w_sum, n_races);
+}
+
 static int check_field(crx_field_kparams& fp, const crx_field_desc* d, int n_races, arr track, arr xcurv, arr car_dims, arr pred_s, arr pred_ey,
                        arr obs_s, arr obs_ey, arr lap_off, arr n_obs, arr obs_dims, const double* host_dims = nullptr) {
-    auto positive = [](double v) { return v > 0.0 && isfinite(v); };
     if (int rc = check_field_desc(d, n_races)) return rc;
-    if (d->n_cars > 1 && !car_dims != !obs_dims)   // (one car: obs_dims holds nothing, like the other obs_* arrays)
-        return fail(CRX_ERR_ARG, "car_dims and obs_dims go together: both or neither (%s is NULL)", car_dims ? "obs_dims" : "car_dims");
-    if (n_races > 0 && (any_null(track, xcurv, pred_s, pred_ey, n_obs) || (d->n_cars > 1 && any_null(obs_s, obs_ey, lap_off))))
-        return fail(CRX_ERR_ARG, "NULL array argument");
-    for (size_t i = 0; host_dims && i < (size_t)n_races * d->n_cars; i++)
-        if (!positive(host_dims[2 * i]) || !positive(host_dims[2 * i + 1]))
-            return fail(CRX_ERR_ARG, "car_dims of car %zu of race %zu: length and width must be positive and finite", i % d->n_cars, i / d->n_cars);
+    if (int rc = check_field_arrays(n_races, d->n_cars, 0, any_null(track, xcurv, pred_s, pred_ey, n_obs), false, car_dims, obs_s, obs_ey, lap_off,
+                                    obs_dims, host_dims)) return rc;
     memset(&fp, 0, sizeof(fp));
     fp.d = *d; fp.n_races = n_races;
     return 0;
@@ -1094,8 +1110,8 @@ int crx_field_prep_dev(const crx_field_desc* d, int n_races, const double* track
     if (int rc = check_field(fp, d, n_races, track, xcurv, car_dims, pred_s, pred_ey, obs_s, obs_ey, lap_off, n_obs, obs_dims)) return rc;
     if (int rc = ensure_init()) return rc;
     if (n_races == 0) return CRX_OK;
-    fp.track = track; fp.xcurv = xcurv; fp.car_dims = car_dims; fp.pred_s = pred_s; fp.pred_ey = pred_ey; fp.obs_s = obs_s; fp.obs_ey = obs_ey;
-    fp.lap_off = lap_off; fp.n_obs = n_obs; fp.obs_dims = d->n_cars > 1 ? obs_dims : nullptr; fp.clear = clear;
+    fp.track = track; fp.xcurv = xcurv; fp.car_dims = car_dims; fp.pred_s = pred_s; fp.pred_ey = pred_ey;
+    fp.nlp = {obs_s, obs_ey, lap_off, n_obs, d->n_cars > 1 ? obs_dims : nullptr, clear};
     return launched(crx_launch_field_prep(fp, (hipStream_t)stream), "field prep");
 }
 
@@ -1173,35 +1189,18 @@ void crx_mixed_desc_default(crx_mixed_desc* d, int N, int N_ilqr, int n_cars, in
 
 // The descriptor and the race count of crx_mixed_prep*
 static int check_mixed_desc(const crx_mixed_desc* d, int n_races) {
-    auto positive = [](double v) { return v > 0.0 && isfinite(v); };
     if (!d) return fail(CRX_ERR_ARG, "desc is NULL");
-    if (d->N < 1 || d->N > CRX_MAX_N) return fail(CRX_ERR_ARG, "N=%d outside [1,%d]", d->N, CRX_MAX_N);
-    if (d->N_ilqr < 0 || d->N_ilqr > CRX_ILQR_MAX_N) return fail(CRX_ERR_ARG, "N_ilqr=%d outside [0,%d]", d->N_ilqr, CRX_ILQR_MAX_N);
-    if (d->n_cars < 1 || d->n_cars > CRX_MAX_OBS + 1) return fail(CRX_ERR_ARG, "n_cars=%d outside [1,%d]", d->n_cars, CRX_MAX_OBS + 1);
-    if (d->n_seg < 1 || d->n_seg > CRX_PLANT_MAX_SEG) return fail(CRX_ERR_ARG, "n_seg=%d outside [1,%d]", d->n_seg, CRX_PLANT_MAX_SEG);
-    if (d->degree < 2 || d->degree > 8 || (d->degree & 1)) return fail(CRX_ERR_ARG, "degree must be 2, 4, 6 or 8");
-    if (d->ilqr_obstacles != 0 && d->ilqr_obstacles != 1) return fail(CRX_ERR_ARG, "ilqr_obstacles=%d must be 0 or 1", d->ilqr_obstacles);
-    if (!positive(d->lap_length) || !positive(d->dt) || !positive(d->l_sum) || !positive(d->w_sum))
-        return fail(CRX_ERR_ARG, "lap_length, dt, l_sum and w_sum must be positive and finite");
-    if (n_races < 0) return fail(CRX_ERR_ARG, "n_races < 0");
-    return 0;
+    return check_field_scalars(d->N, d->N_ilqr, d->n_cars, d->n_seg, d->degree, d->ilqr_obstacles, d->lap_length, d->dt, d->l_sum, d->w_sum, n_races);
 }
 
 // Arguments alone, before the library's state is looked at.  host_dims, host_policy: the rows of the host-pointer entry (NULL: on the device)
 static int check_mixed(crx_mixed_kparams& mp, const crx_mixed_desc* d, int n_races, arr track, arr xcurv, arr policy, arr car_dims, arr pred_s,
                        arr pred_ey, arr obs_s, arr obs_ey, arr lap_off, arr n_obs, arr obs_dims, arr m_nlp, arr il_obs_s, arr il_obs_ey,
                        arr il_lap_off, arr il_n_obs, arr m_ilqr, const double* host_dims = nullptr, const int32_t* host_policy = nullptr) {
-    auto positive = [](double v) { return v > 0.0 && isfinite(v); };
     if (int rc = check_mixed_desc(d, n_races)) return rc;
-    if (d->n_cars > 1 && !car_dims != !obs_dims)   // (one car: obs_dims holds nothing, like the other [V] arrays)
-        return fail(CRX_ERR_ARG, "car_dims and obs_dims go together: both or neither (%s is NULL)", car_dims ? "obs_dims" : "car_dims");
-    if (n_races > 0 && (any_null(track, xcurv, policy, pred_s, pred_ey, n_obs, m_nlp) || (d->n_cars > 1 && any_null(obs_s, obs_ey, lap_off))))
-        return fail(CRX_ERR_ARG, "NULL array argument");
-    if (n_races > 0 && d->N_ilqr > 0 && (any_null(il_n_obs, m_ilqr) || (d->n_cars > 1 && any_null(il_obs_s, il_obs_ey, il_lap_off))))
-        return fail(CRX_ERR_ARG, "NULL array argument of the iLQR family (N_ilqr=%d)", d->N_ilqr);
-    for (size_t i = 0; host_dims && i < (size_t)n_races * d->n_cars; i++)
-        if (!positive(host_dims[2 * i]) || !positive(host_dims[2 * i + 1]))
-            return fail(CRX_ERR_ARG, "car_dims of car %zu of race %zu: length and width must be positive and finite", i % d->n_cars, i / d->n_cars);
+    if (int rc = check_field_arrays(n_races, d->n_cars, d->N_ilqr, any_null(track, xcurv, policy, pred_s, pred_ey, n_obs, m_nlp),
+                                    any_null(il_n_obs, m_ilqr) || (d->n_cars > 1 && any_null(il_obs_s, il_obs_ey, il_lap_off)), car_dims, obs_s,
+                                    obs_ey, lap_off, obs_dims, host_dims)) return rc;
     for (size_t i = 0; host_policy && i < (size_t)n_races * d->n_cars; i++)
         if (host_policy[i] < 0 || host_policy[i] >= CRX_POLICY_COUNT)
             return fail(CRX_ERR_ARG, "policy=%d of car %zu of race %zu outside [0,%d]", host_policy[i], i % d->n_cars, i / d->n_cars, CRX_POLICY_COUNT - 1);
@@ -1220,8 +1219,8 @@ int crx_mixed_prep_dev(const crx_mixed_desc* d, int n_races, const double* track
     if (int rc = ensure_init()) return rc;
     if (n_races == 0) return CRX_OK;
     mp.track = track; mp.xcurv = xcurv; mp.policy = policy; mp.car_dims = car_dims; mp.pred_s = pred_s; mp.pred_ey = pred_ey;
-    mp.obs_s = obs_s; mp.obs_ey = obs_ey; mp.lap_off = lap_off; mp.n_obs = n_obs; mp.obs_dims = d->n_cars > 1 ? obs_dims : nullptr; mp.m_nlp = m_nlp;
-    mp.il_obs_s = il_obs_s; mp.il_obs_ey = il_obs_ey; mp.il_lap_off = il_lap_off; mp.il_n_obs = il_n_obs; mp.m_ilqr = m_ilqr; mp.clear = clear;
+    mp.nlp = {obs_s, obs_ey, lap_off, n_obs, d->n_cars > 1 ? obs_dims : nullptr, clear}; mp.m_nlp = m_nlp;
+    mp.il_obs_s = il_obs_s; mp.il_obs_ey = il_obs_ey; mp.il_lap_off = il_lap_off; mp.il_n_obs = il_n_obs; mp.m_ilqr = m_ilqr;
     return launched(crx_launch_mixed_prep(mp, (hipStream_t)stream), "mixed prep");
 }
 

@@ -117,14 +117,20 @@ struct crx_cbfprep_kparams {
     int32_t* n_obs;
 };
 
+// The NLP family's obstacle arrays of the n_races * n_cars egos of a field, in crx_cbf_solve_dev's layout (nlp_ego_pass, crx_prep.hip)
+struct crx_nlp_obs {
+    double *obs_s, *obs_ey, *lap_off;         // [n_races * n_cars][n_cars - 1][N + 1] twice, [..][n_cars - 1]
+    int32_t* n_obs;
+    double *obs_dims, *clear;                 // obs_dims: written iff car_dims; clear: optional
+};
+
 // crx_field_prep_kernel (crx_prep.hip): predictions of every car of every race and the obstacle arrays of the n_races * n_cars NLPs
 struct crx_field_kparams {
     crx_field_desc d;
     int n_races;
     const double *track, *xcurv, *car_dims;   // car_dims: optional [n_races][n_cars][2] (length, width); NULL: d.l_sum, d.w_sum for every pair
-    double *pred_s, *pred_ey, *obs_s, *obs_ey, *lap_off;
-    int32_t* n_obs;
-    double *obs_dims, *clear;                 // obs_dims: written iff car_dims; clear: optional
+    double *pred_s, *pred_ey;
+    crx_nlp_obs nlp;
 };
 
 // crx_field_traffic_kernel (crx_prep.hip): predictions of every car of every race and, per ego, the other cars of its race as the scene's inputs
@@ -144,11 +150,10 @@ struct crx_mixed_kparams {
     const double *track, *xcurv, *car_dims;    // car_dims: optional, as in crx_field_kparams
     const int32_t* policy;                     // [n_races][n_cars] CRX_POLICY_*
     double *pred_s, *pred_ey;                  // [n_races][n_cars][max(N, N_ilqr) + 1]
-    double *obs_s, *obs_ey, *lap_off, *obs_dims;   // the NLP family, [..][n_cars - 1][N + 1] ...; obs_dims: written iff car_dims
-    int32_t *n_obs, *m_nlp;
+    crx_nlp_obs nlp;                           // the NLP family
+    int32_t* m_nlp;
     double *il_obs_s, *il_obs_ey, *il_lap_off; // the iLQR family, [..][n_cars - 1][N_ilqr + 1] ...; touched iff N_ilqr > 0
     int32_t *il_n_obs, *m_ilqr;
-    double* clear;                             // optional
 };
 
 // ---- crx_path.hip: crx_path_kernel, the path QP (crx_path_qp.h) without a mask ----

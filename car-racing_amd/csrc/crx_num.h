@@ -91,11 +91,16 @@ __device__ __forceinline__ double dim_or_default(double v, double dflt) { return
 // ---- Sites that are NOT shared, and why each stays ---------------------------------------------------------------------------------
 // "code changes": as in crx_ipm.h -- same arithmetic, but through a function the kernel's machine code is no longer what it was.
 // Lines as of this header's last edit; the kernel and its comment "crx_num.h" find the site.
-//   strided interp1d        crx_trackprep_kernel (crx_prep.hip:172-187)      the scan over the trajectory's rows (stride 6): code changes through a
+//   strided interp1d        crx_trackprep_kernel (crx_prep.hip:177-189)      the scan over the trajectory's rows (stride 6): code changes through a
 //                                                                            strided interp1d, also with the column offsets as template parameters
-//   zeroed obstacle slots   crx_trackprep_kernel (crx_prep.hip:206-211)      code changes in crx_trackprep_kernel with any shared form, down to the inner
-//                           crx_cbfprep_kernel (crx_prep.hip:244-249)        loop alone; a function with one caller is no sharing, so both copies stay
+//   zeroed obstacle slots   crx_trackprep_kernel (crx_prep.hip:209-214)      code changes in crx_trackprep_kernel with any shared form, down to the inner
+//                           crx_cbfprep_kernel (crx_prep.hip:247-252)        loop alone; a function with one caller is no sharing, so both copies stay.
+//                                                                            (The field family's tail is inside nlp_ego_pass, crx_prep.hip, which its
+//                                                                            two kernels share whole; these two kernels must stay bit for bit)
 //   super-ellipse value     crx_order_key (crx_order.hip:46-48, :62-64)      code changes as a lambda and as a function (the loop over the degree)
+//                           crx_race_stats_kernel (crx_game.hip:289-296)     under `#pragma clang fp contract(off)`, nlp_ego_pass (crx_prep.hip) is
+//                                                                            not: l_e / 2 + l_o / 2 can fuse in one and not in the other, so the
+//                                                                            pair geometry of the field lives in nlp_ego_pass and here, written out
 //   curvature lookup        the plant (crx_plant_step.h: LDS tables), crx_lmpcprep.hip (global table, contraction off): two storage forms; left alone
 
 #endif

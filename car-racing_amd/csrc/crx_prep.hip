@@ -10,12 +10,13 @@
 //   crx_trackprep_kernel   the inputs of control.mpc_multi_agents' NLP from the planner's outputs: per-stage targets, window filter, lap offsets
 //                          and packing of the sorted vehicles' predictions.  control/control.py:373-382, :293-309
 //   crx_cbfprep_kernel     obstacle arrays of control.mpccbf for scripted cars.  control/control.py:500, :519
-//   crx_field_prep_kernel  the same arrays for a field of driven cars: every car of a race predicted by the zero-input roll-out of
-//                          racing/offboard.py:51-94, every car the ego of its own NLP.  control/control.py:499-540 (realtime_flag == True)
-//   crx_field_traffic_kernel  the racing game's traffic arrays for such a field: the same roll-out, then per ego the other cars of its race
-//                          as crx_scene_kernel takes them.  planning/overtake_traj_planner.py:77-85
-//   crx_mixed_prep_kernel  a field whose cars each run their own controller: the same roll-out, crx_field_prep_kernel's arrays for the
-//                          MPC-CBF cars, the iLQR family's for the iLQR cars (control/control.py:99-104), and the masks of both launches
+//   the field family       a field of driven cars, every car of a race predicted by the zero-input roll-out of racing/offboard.py:51-94; the block
+//                          shape, the table load, the ego pass of the NLP family and the block-strided gather stand once, ahead of the three:
+//     crx_field_prep_kernel     every car the ego of its own NLP.  control/control.py:499-540 (realtime_flag == True)
+//     crx_field_traffic_kernel  the racing game's traffic arrays: per ego the other cars of its race as crx_scene_kernel takes them.
+//                               planning/overtake_traj_planner.py:77-85
+//     crx_mixed_prep_kernel     every car under its own controller: the NLP family for the MPC-CBF cars, the iLQR family's arrays for the iLQR
+//                               cars (control/control.py:99-104), and the masks of both launches
 // The comment in front of each kernel has the rest.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -253,176 +254,187 @@ __global__ void __launch_bounds__(256) crx_cbfprep_kernel(const crx_cbfprep_kpar
 }
 
 // ------------------------------------------------------------------------------------------------
-// Obstacle arrays of control.mpccbf for a FIELD: n_races races of C = n_cars driven cars, every car the ego of its own NLP and an
-// obstacle of the C - 1 others (see crx_field_prep_dev in include/crx.h, quirks F1-F7).  One thread per (race, car); a workgroup owns
-// 256 / C WHOLE races, so what a car reads of the others was written inside its own workgroup and one block barrier separates the
-// two phases (the threads past the last whole race of a block, and the races past n_races of the last block, only take the barrier).
-//   phase 1  racing/offboard.py:51-94: N + 1 zero-input Euler steps of the curvilinear state along the track's curvature (the plant's
-//            lookup over LDS tables, crx_plant_step.h), `while s > L: s -= L` after every step (:90-91) as wrap_above -- no loop here
-//            runs on device data.  Trig-bound: 2 (N + 1) sin / cos per car.
-//   phase 2  control/control.py:499-540 with realtime_flag == True: the window test and the lap offset on column 0 of each other car's
-//            prediction, kept cars packed to the front in car order, the rest zero; (l_e / 2 + l_o / 2, w_e / 2 + w_o / 2) per kept
-//            slot (:532-535) when the cars bring their own dimensions; the smallest super-ellipse value against the others at the
-//            CURRENT states (below 1: contact).
-// A car with a non-finite state predicts non-finite rows, passes nobody's window test (every comparison with a NaN is false), keeps
-// nobody itself, and never lowers a `clear`.
+// The FIELD family: crx_field_prep_kernel, crx_field_traffic_kernel, crx_mixed_prep_kernel.  n_races races of C = n_cars driven cars, every
+// car an ego and one of the V = C - 1 others of the egos of its race (see "Field races", "Field games", "Mixed fields" in include/crx.h).
+// What the three share stands here, once.
+//   block shape   one thread per (race, car); a workgroup of 256 threads owns 256 / C WHOLE races, so what a car reads of the others was
+//                 written inside its own workgroup and one block barrier separates the two phases.  The threads past the last whole race of a
+//                 block, and the races past n_races of the last block, are not `live`: they only take the barriers (field_block, below) --
+//                 every thread of a block reaches every __syncthreads(), none returns before the last one.
+//   phase 1       zero_input_rollout (crx_num.h) over the track's segment tables in LDS (load_seg_tables): racing/offboard.py:51-94, N + 1
+//                 zero-input Euler steps of the curvilinear state along the track's curvature, `while s > L: s -= L` after every step (:90-91)
+//                 as wrap_above.  Trig-bound: 2 (N + 1) sin / cos per car.  Every kernel's roll-out columns 0 .. N are the same bits.
+//   phase 2       per ego, the other cars of its race in car order (quirk F5).  nlp_ego_pass: the NLP family's arrays and `clear`;
+//                 block_gather: wide [V][W] rows per ego copied by the whole block.
+// No loop runs on device data: the trip counts come from the descriptor and n_races.
+// A car with a non-finite state predicts non-finite rows, passes nobody's window test (every comparison with a NaN is false), keeps nobody
+// itself, and never lowers a `clear`; where its rows are only copied (block_gather) they arrive as bits.
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) crx_field_prep_kernel(const crx_field_kparams fp) {
-    __shared__ double seg_lo[CRX_PLANT_MAX_SEG], seg_hi[CRX_PLANT_MAX_SEG], seg_cv[CRX_PLANT_MAX_SEG];
-    const crx_field_desc& d = fp.d;
-    for (int i = threadIdx.x; i < d.n_seg; i += blockDim.x) {
-        seg_lo[i] = fp.track[6 * i + 3];
-        seg_hi[i] = fp.track[6 * i + 3] + fp.track[6 * i + 4];
-        seg_cv[i] = fp.track[6 * i + 5];
+// The track's segment tables as the plant keeps them (crx_plant_step.h), into the caller's LDS arrays.  Holds a barrier: every thread calls it.
+__device__ __forceinline__ void load_seg_tables(const double* track, int n_seg, double* seg_lo, double* seg_hi, double* seg_cv) {
+    for (int i = threadIdx.x; i < n_seg; i += blockDim.x) {
+        seg_lo[i] = track[6 * i + 3];
+        seg_hi[i] = track[6 * i + 3] + track[6 * i + 4];
+        seg_cv[i] = track[6 * i + 5];
     }
     __syncthreads();
-    const int C = d.n_cars, V = C - 1, N1 = d.N + 1, per_block = 256 / C;
-    const int rl = threadIdx.x / C, c = threadIdx.x - rl * C, r = blockIdx.x * per_block + rl;
-    const bool live = rl < per_block && r < fp.n_races;
-    const size_t rc = (size_t)r * C + c;   // this thread's car = problem rc of the solver launch (race-major, car-minor)
-    const double L = d.lap_length, dt = d.dt;
-    if (live)   // phase 1, written once: zero_input_rollout (crx_num.h)
-        zero_input_rollout(fp.xcurv + 6 * rc, seg_lo, seg_hi, seg_cv, d.n_seg, L, dt, N1, fp.pred_s + rc * N1, fp.pred_ey + rc * N1);
-    __syncthreads();   // the predictions of this block's races are in memory; workgroup scope is all phase 2 needs
-    if (!live) return;
-    const double* xe = fp.xcurv + 6 * rc;
-    const double s_e = xe[4], ey_e = xe[5], margin = d.safety_time * xe[0];
+}
+
+struct field_block {
+    int n_live, t, c;    // the block's live threads = its cars; this thread, and its car inside its race
+    size_t rc0, rc;      // the block's first car and this thread's: problem / scenario rc of the solver launches (race-major, car-minor)
+    bool live;
+};
+__device__ __forceinline__ field_block field_block_of(int C, int n_races) {
+    const int per_block = 256 / C, r0 = blockIdx.x * per_block;   // r0: first race of this block, < n_races by the grid's size
+    field_block b;
+    b.n_live = min(per_block, n_races - r0) * C;
+    b.t = threadIdx.x; b.c = b.t % C;
+    b.rc0 = (size_t)r0 * C; b.rc = b.rc0 + b.t;
+    b.live = b.t < b.n_live;
+    return b;
+}
+
+// control/control.py:499-540 with realtime_flag == True, for the ego rc = car c of its race: the window test and the lap offset on column 0
+// of each other car's prediction (pred_s, pred_ey: rows of `stride` doubles, the first N1 of them copied), kept cars packed to the front in
+// car order, the rest zero; (l_e / 2 + l_o / 2, w_e / 2 + w_o / 2) per kept slot (:532-535) when the cars bring their own dimensions; the
+// smallest super-ellipse value against the others at the CURRENT states (below 1: contact) into out.clear when it is given.  keep == false:
+// an ego that keeps nobody (its policy is not MPC-CBF, quirk M2); `clear` is computed all the same.
+__device__ __forceinline__ void nlp_ego_pass(const double* xcurv, const double* car_dims, const double* pred_s, const double* pred_ey, int stride,
+                                             double L, double safety_time, double d_l_sum, double d_w_sum, int degree, int N1, int C, int c,
+                                             size_t rc, bool keep, const crx_nlp_obs& out) {
+    const int V = C - 1;
+    const double* xe = xcurv + 6 * rc;
+    const double s_e = xe[4], ey_e = xe[5], margin = safety_time * xe[0];
     double nce;
     const double dist_ego = lap_fold(s_e, L, nce);
     // a car's own (length, width); device-resident dimensions cannot be validated on the host: dim_or_default (crx_num.h)
-    const double l_e = fp.car_dims ? dim_or_default(fp.car_dims[2 * rc], d.l_sum) : 0.0;
-    const double w_e = fp.car_dims ? dim_or_default(fp.car_dims[2 * rc + 1], d.w_sum) : 0.0;
+    const double l_e = car_dims ? dim_or_default(car_dims[2 * rc], d_l_sum) : 0.0;
+    const double w_e = car_dims ? dim_or_default(car_dims[2 * rc + 1], d_w_sum) : 0.0;
     int n = 0;
     double clr = INFINITY;
     for (int o = 0; o < C; o++) {   // car order, skipping the ego (quirk F5)
         if (o == c) continue;
-        const size_t ro = (size_t)r * C + o;
-        double l_sum = d.l_sum, w_sum = d.w_sum;
-        if (fp.car_dims) {
-            l_sum = l_e / 2 + dim_or_default(fp.car_dims[2 * ro], d.l_sum) / 2;
-            w_sum = w_e / 2 + dim_or_default(fp.car_dims[2 * ro + 1], d.w_sum) / 2;
+        const size_t ro = rc - c + o;
+        double l_sum = d_l_sum, w_sum = d_w_sum;
+        if (car_dims) {
+            l_sum = l_e / 2 + dim_or_default(car_dims[2 * ro], d_l_sum) / 2;
+            w_sum = w_e / 2 + dim_or_default(car_dims[2 * ro + 1], d_w_sum) / 2;
         }
-        if (fp.clear) {
-            const double* xo = fp.xcurv + 6 * ro;
+        if (out.clear) {
+            const double* xo = xcurv + 6 * ro;
             double m = fmod(s_e - xo[4] + L / 2, L);   // Python's %: the sign of the divisor
             if (m < 0.0) m += L;
             const double a = (m - L / 2) / l_sum, b = (ey_e - xo[5]) / w_sum;
             double pa = 1.0, pb = 1.0;
-            for (int k = 0; k < d.degree; k++) { pa *= a; pb *= b; }
+            for (int k = 0; k < degree; k++) { pa *= a; pb *= b; }
             const double h = pa + pb;
             clr = h < clr ? h : clr;
         }
-        const double* is = fp.pred_s + ro * N1;
-        const double* ie = fp.pred_ey + ro * N1;
+        const double* is = pred_s + ro * stride;
+        const double* ie = pred_ey + ro * stride;
         double off;
-        if (safety_window(dist_ego, nce, is[0], margin, L, off)) {   // column 0: one estimated step ahead (quirk F2)
-            double* os = fp.obs_s + (rc * V + n) * N1;
-            double* oe = fp.obs_ey + (rc * V + n) * N1;
+        if (keep && safety_window(dist_ego, nce, is[0], margin, L, off)) {   // column 0: one estimated step ahead (quirk F2)
+            double* os = out.obs_s + (rc * V + n) * N1;
+            double* oe = out.obs_ey + (rc * V + n) * N1;
             for (int j = 0; j < N1; j++) { os[j] = is[j]; oe[j] = ie[j]; }
-            fp.lap_off[rc * V + n] = off;
-            if (fp.obs_dims) { fp.obs_dims[(rc * V + n) * 2] = l_sum; fp.obs_dims[(rc * V + n) * 2 + 1] = w_sum; }
+            out.lap_off[rc * V + n] = off;
+            if (out.obs_dims) { out.obs_dims[(rc * V + n) * 2] = l_sum; out.obs_dims[(rc * V + n) * 2 + 1] = w_sum; }
             n++;
         }
     }
     for (int v = n; v < V; v++) {
-        double* os = fp.obs_s + (rc * V + v) * N1;
-        double* oe = fp.obs_ey + (rc * V + v) * N1;
+        double* os = out.obs_s + (rc * V + v) * N1;
+        double* oe = out.obs_ey + (rc * V + v) * N1;
         for (int j = 0; j < N1; j++) { os[j] = 0.0; oe[j] = 0.0; }
-        fp.lap_off[rc * V + v] = 0.0;
-        if (fp.obs_dims) { fp.obs_dims[(rc * V + v) * 2] = 0.0; fp.obs_dims[(rc * V + v) * 2 + 1] = 0.0; }
+        out.lap_off[rc * V + v] = 0.0;
+        if (out.obs_dims) { out.obs_dims[(rc * V + v) * 2] = 0.0; out.obs_dims[(rc * V + v) * 2 + 1] = 0.0; }
     }
-    fp.n_obs[rc] = n;
-    if (fp.clear) fp.clear[rc] = clr;
+    out.n_obs[rc] = n;
+    if (out.clear) out.clear[rc] = clr;
 }
 
-// ------------------------------------------------------------------------------------------------
-// The racing game's traffic arrays for a FIELD (see crx_field_traffic_dev in include/crx.h, quirks F1-F3, F6, G1-G3): what
-// crx_game_traffic_kernel makes of scripted cars, made of the other DRIVEN cars of the race -- the inputs of crx_scene_kernel for the
-// n_races * C scenarios with n_all_max = n_veh_max = V = C - 1.  The block shape is crx_field_prep_kernel's: one thread per (race, car), a
-// workgroup owns 256 / C whole races, the threads past the last whole race and the races past n_races only take the barrier.
-//   phase 1  zero_input_rollout (crx_num.h): pred_s_car, pred_ey_car [R][C][N+1], the bits of crx_field_prep_kernel's pred_s, pred_ey
-//   phase 2  overtake_traj_planner.py:77-85 (the `else` branch: a driven opponent's get_trajectory_nsteps(N + 1)) per ego, the other
-//            cars in car order (F5): slot v of ego c is car o = v + (v >= c).  Pure copies.  The [V][6] and [V][N+1] rows of one ego are
-//            contiguous and consecutive threads are consecutive egos, so what a block writes to each array is ONE contiguous range; its
-//            live threads stride over that range element by element (a wave stores 512 consecutive bytes; its loads are consecutive
-//            inside a row) instead of each walking its own ego's rows at a stride of V (N + 1) doubles.  The trip counts come from the
-//            descriptor and n_races: no loop runs on device data.
-// A car with a non-finite state has non-finite rows and a non-finite veh_xcurv row in the other cars' arrays, as bits; nothing here
-// computes on them.
-// ------------------------------------------------------------------------------------------------
+// NA arrays dst[a] [R C][V][W] filled from rows src[a] [R C][stride]: slot v of ego q of the block holds the first W words of the row of car
+// slot_car(q, v) of q's race.  HOLES: a negative slot_car is an empty slot, which gets zeros; without HOLES every slot is held and the copy is
+// unconditional (the test costs crx_field_traffic_kernel a branch around every load).  The [V][W] rows of one ego are contiguous and
+// consecutive threads are consecutive egos, so what a block writes to each array is ONE contiguous range; its live threads stride over that
+// range element by element (a wave stores 512 consecutive bytes; its loads are consecutive inside a row) instead of each walking its own
+// ego's rows at a stride of V W doubles.  Called by the live threads, after the barrier that publishes the rows.
+template <int NA, bool HOLES, typename SlotCar>
+__device__ __forceinline__ void block_gather(const field_block& b, int C, int W, int stride, const double* const (&src)[NA], double* const (&dst)[NA],
+                                             SlotCar slot_car) {
+    const int row = (C - 1) * W;
+    for (int e = b.t; e < b.n_live * row; e += b.n_live) {
+        const int q = e / row, m = e - q * row, v = m / W, w = m - W * v;
+        const int o = slot_car(q, v);
+        const bool held = !HOLES || o >= 0;
+        const size_t from = (b.rc0 + (q - q % C) + (held ? o : 0)) * stride + w;
+        for (int a = 0; a < NA; a++) dst[a][b.rc0 * row + e] = held ? src[a][from] : 0.0;
+    }
+}
+
+// Obstacle arrays of control.mpccbf for a field (crx_field_prep_dev, quirks F1-F7): the roll-out, then every car the ego of its own NLP.
+__global__ void __launch_bounds__(256) crx_field_prep_kernel(const crx_field_kparams fp) {
+    __shared__ double seg_lo[CRX_PLANT_MAX_SEG], seg_hi[CRX_PLANT_MAX_SEG], seg_cv[CRX_PLANT_MAX_SEG];
+    const crx_field_desc& d = fp.d;
+    load_seg_tables(fp.track, d.n_seg, seg_lo, seg_hi, seg_cv);
+    const int N1 = d.N + 1;
+    const field_block b = field_block_of(d.n_cars, fp.n_races);
+    if (b.live)
+        zero_input_rollout(fp.xcurv + 6 * b.rc, seg_lo, seg_hi, seg_cv, d.n_seg, d.lap_length, d.dt, N1, fp.pred_s + b.rc * N1, fp.pred_ey + b.rc * N1);
+    __syncthreads();   // the predictions of this block's races are in memory; workgroup scope is all phase 2 needs
+    if (!b.live) return;
+    nlp_ego_pass(fp.xcurv, fp.car_dims, fp.pred_s, fp.pred_ey, N1, d.lap_length, d.safety_time, d.l_sum, d.w_sum, d.degree, N1, d.n_cars, b.c, b.rc,
+                 true, fp.nlp);
+}
+
+// The racing game's traffic arrays for a field (crx_field_traffic_dev, quirks F1-F3, F6, G1-G3): what crx_game_traffic_kernel makes of
+// scripted cars, made of the other DRIVEN cars of the race -- the inputs of crx_scene_kernel for the n_races * C scenarios with n_all_max =
+// n_veh_max = V.  Phase 2 is overtake_traj_planner.py:77-85 (the `else` branch: a driven opponent's get_trajectory_nsteps(N + 1)) per ego:
+// slot v of ego c is car o = v + (v >= c).  Pure copies; nothing here computes on a non-finite car's rows.
 __global__ void __launch_bounds__(256) crx_field_traffic_kernel(const crx_field_traffic_kparams tp) {
     __shared__ double seg_lo[CRX_PLANT_MAX_SEG], seg_hi[CRX_PLANT_MAX_SEG], seg_cv[CRX_PLANT_MAX_SEG];
     const crx_field_desc& d = tp.d;
-    for (int i = threadIdx.x; i < d.n_seg; i += blockDim.x) {
-        seg_lo[i] = tp.track[6 * i + 3];
-        seg_hi[i] = tp.track[6 * i + 3] + tp.track[6 * i + 4];
-        seg_cv[i] = tp.track[6 * i + 5];
-    }
-    __syncthreads();
-    const int C = d.n_cars, V = C - 1, N1 = d.N + 1, per_block = 256 / C;
-    const int r0 = blockIdx.x * per_block;                               // first race of this block
-    const int n_live = min(per_block, tp.n_races - r0) * C;              // its live threads = its cars; r0 < n_races by the grid's size
-    const int t = threadIdx.x;
-    const bool live = t < n_live;
-    const size_t rc0 = (size_t)r0 * C, rc = rc0 + t;                     // this thread's car = scenario rc of the scene launch
-    if (live)
-        zero_input_rollout(tp.xcurv + 6 * rc, seg_lo, seg_hi, seg_cv, d.n_seg, d.lap_length, d.dt, N1, tp.pred_s_car + rc * N1, tp.pred_ey_car + rc * N1);
+    load_seg_tables(tp.track, d.n_seg, seg_lo, seg_hi, seg_cv);
+    const int C = d.n_cars, N1 = d.N + 1;
+    const field_block b = field_block_of(C, tp.n_races);
+    if (b.live)
+        zero_input_rollout(tp.xcurv + 6 * b.rc, seg_lo, seg_hi, seg_cv, d.n_seg, d.lap_length, d.dt, N1, tp.pred_s_car + b.rc * N1, tp.pred_ey_car + b.rc * N1);
     __syncthreads();   // the predictions of this block's races are in memory; workgroup scope is all phase 2 needs
-    if (!live) return;
-    tp.n_all[rc] = V;
-    // element e of the block's range of a [R C][V][W] array: ego q = e / (V W) of the block, slot v, word w; its source row is car
-    // o = v + (v >= c) of the ego's race
-    const int row_x = V * 6, row_p = V * N1;
-    for (int e = t; e < n_live * row_x; e += n_live) {
-        const int q = e / row_x, m = e - q * row_x, v = m / 6, w = m - 6 * v;
-        const int c = q % C, o = v + (v >= c ? 1 : 0);
-        tp.veh_xcurv[rc0 * row_x + e] = tp.xcurv[(rc0 + (q - c) + o) * 6 + w];
-    }
-    for (int e = t; e < n_live * row_p; e += n_live) {
-        const int q = e / row_p, m = e - q * row_p, v = m / N1, j = m - N1 * v;
-        const int c = q % C, o = v + (v >= c ? 1 : 0);
-        const size_t src = (rc0 + (q - c) + o) * N1 + j;
-        tp.pred_s[rc0 * row_p + e] = tp.pred_s_car[src];
-        tp.pred_ey[rc0 * row_p + e] = tp.pred_ey_car[src];
-    }
+    if (!b.live) return;
+    tp.n_all[b.rc] = C - 1;
+    const auto others = [C](int q, int v) { return v + (v >= q % C ? 1 : 0); };
+    const double* const x_src[1] = {tp.xcurv};
+    double* const x_dst[1] = {tp.veh_xcurv};
+    block_gather<1, false>(b, C, 6, 6, x_src, x_dst, others);
+    const double* const p_src[2] = {tp.pred_s_car, tp.pred_ey_car};
+    double* const p_dst[2] = {tp.pred_s, tp.pred_ey};
+    block_gather<2, false>(b, C, N1, N1, p_src, p_dst, others);
 }
 
-// ------------------------------------------------------------------------------------------------
-// The solver inputs of a MIXED field (see crx_mixed_prep_dev in include/crx.h, quirks F1-F3, F6, M1, M2): every car of a race under its own
-// policy, so one launch prepares what crx_field_prep_kernel prepares for the MPC-CBF cars, the iLQR family's arrays for the iLQR cars, and the
-// two masks the solver launches run under.  The block shape is the field kernels': one thread per (race, car), a workgroup owns 256 / C whole
-// races, the threads past the last whole race and the races past n_races only take the barriers.
-//   phase 1  zero_input_rollout (crx_num.h), max(N, N_ilqr) + 1 steps: columns 0 .. N are the bits of crx_field_prep_kernel's pred_s, pred_ey.
-//            Before the barrier each ego also decides, from the INPUTS alone (policies, finiteness of the states), which cars its iLQR slots
-//            hold, and leaves that in LDS (il_src: a car index, or -1) -- so the one barrier that publishes the roll-outs publishes the slot
-//            map too.
-//   phase 2  per ego: `clear` and the NLP family as crx_field_prep_kernel writes them (an ego that is not MPCCBF keeps nobody); the iLQR
-//            family's lap offsets and counts; then the wide iLQR rows ([V][N_ilqr + 1] per ego, contiguous over the block's egos) by the
-//            block-strided copy of crx_field_traffic_kernel, each element's source looked up in il_src.
-// The trip counts come from the descriptor and n_races: no loop runs on device data.  Policy codes are compared, never used as an index.
-// ------------------------------------------------------------------------------------------------
+// The solver inputs of a mixed field (crx_mixed_prep_dev, quirks F1-F3, F6, M1, M2): every car of a race under its own policy, so one launch
+// prepares the NLP family for the MPC-CBF cars, the iLQR family's arrays for the iLQR cars (control/control.py:99-104), and the two masks the
+// solver launches run under.
+//   phase 1  the roll-out runs max(N, N_ilqr) + 1 steps.  Before the barrier each ego also decides, from the INPUTS alone (policies,
+//            finiteness of the states), which cars its iLQR slots hold, and leaves that in LDS (il_src: a car index, or -1) -- so the one
+//            barrier that publishes the roll-outs publishes the slot map too.
+//   phase 2  per ego: nlp_ego_pass (an ego that is not MPCCBF keeps nobody); the iLQR family's lap offsets and counts; then the wide iLQR
+//            rows by block_gather, each slot's source looked up in il_src.
+// Policy codes are compared, never used as an index.
 __global__ void __launch_bounds__(256) crx_mixed_prep_kernel(const crx_mixed_kparams mp) {
     __shared__ double seg_lo[CRX_PLANT_MAX_SEG], seg_hi[CRX_PLANT_MAX_SEG], seg_cv[CRX_PLANT_MAX_SEG];
     __shared__ signed char il_src[256 * CRX_MAX_OBS];   // [ego of the block][slot]: the car of the ego's race in that slot, -1: empty
     const crx_mixed_desc& d = mp.d;
-    for (int i = threadIdx.x; i < d.n_seg; i += blockDim.x) {
-        seg_lo[i] = mp.track[6 * i + 3];
-        seg_hi[i] = mp.track[6 * i + 3] + mp.track[6 * i + 4];
-        seg_cv[i] = mp.track[6 * i + 5];
-    }
-    __syncthreads();
-    const int C = d.n_cars, V = C - 1, N1 = d.N + 1, NI1 = d.N_ilqr + 1, NP1 = max(d.N, d.N_ilqr) + 1, per_block = 256 / C;
-    const int r0 = blockIdx.x * per_block;                               // first race of this block
-    const int n_live = min(per_block, mp.n_races - r0) * C;              // its live threads = its cars; r0 < n_races by the grid's size
-    const int t = threadIdx.x;
-    const bool live = t < n_live;
-    const size_t rc0 = (size_t)r0 * C, rc = rc0 + t;                     // this thread's car = problem rc of both solver launches
-    const int c = t % C;
+    load_seg_tables(mp.track, d.n_seg, seg_lo, seg_hi, seg_cv);
+    const int C = d.n_cars, V = C - 1, N1 = d.N + 1, NI1 = d.N_ilqr + 1, NP1 = max(d.N, d.N_ilqr) + 1;
+    const field_block b = field_block_of(C, mp.n_races);
+    const int t = b.t, c = b.c;
+    const size_t rc = b.rc;
     const bool ilqr_on = d.N_ilqr > 0;
     const double L = d.lap_length;
     int pol = CRX_POLICY_NONE;
     bool fin_e = true;
-    if (live) {
+    if (b.live) {
         zero_input_rollout(mp.xcurv + 6 * rc, seg_lo, seg_hi, seg_cv, d.n_seg, L, d.dt, NP1, mp.pred_s + rc * NP1, mp.pred_ey + rc * NP1);
         pol = mp.policy[rc];
         for (int k = 0; k < 6; k++) fin_e = fin_e && isfinite(mp.xcurv[6 * rc + k]);
@@ -440,59 +452,13 @@ __global__ void __launch_bounds__(256) crx_mixed_prep_kernel(const crx_mixed_kpa
         }
     }
     __syncthreads();   // the predictions and the slot maps of this block's races are written; workgroup scope is all phase 2 needs
-    if (!live) return;
-    const double* xe = mp.xcurv + 6 * rc;
-    const double s_e = xe[4], ey_e = xe[5], margin = d.safety_time * xe[0];
-    double nce;
-    const double dist_ego = lap_fold(s_e, L, nce);
+    if (!b.live) return;
     const bool cbf = pol == CRX_POLICY_MPCCBF;
-    // a car's own (length, width): dim_or_default (crx_num.h), as crx_field_prep_kernel takes them
-    const double l_e = mp.car_dims ? dim_or_default(mp.car_dims[2 * rc], d.l_sum) : 0.0;
-    const double w_e = mp.car_dims ? dim_or_default(mp.car_dims[2 * rc + 1], d.w_sum) : 0.0;
-    int n = 0;
-    double clr = INFINITY;
-    for (int o = 0; o < C; o++) {   // car order, skipping the ego (quirk F5)
-        if (o == c) continue;
-        const size_t ro = rc - c + o;
-        double l_sum = d.l_sum, w_sum = d.w_sum;
-        if (mp.car_dims) {
-            l_sum = l_e / 2 + dim_or_default(mp.car_dims[2 * ro], d.l_sum) / 2;
-            w_sum = w_e / 2 + dim_or_default(mp.car_dims[2 * ro + 1], d.w_sum) / 2;
-        }
-        if (mp.clear) {
-            const double* xo = mp.xcurv + 6 * ro;
-            double m = fmod(s_e - xo[4] + L / 2, L);   // Python's %: the sign of the divisor
-            if (m < 0.0) m += L;
-            const double a = (m - L / 2) / l_sum, b = (ey_e - xo[5]) / w_sum;
-            double pa = 1.0, pb = 1.0;
-            for (int k = 0; k < d.degree; k++) { pa *= a; pb *= b; }
-            const double h = pa + pb;
-            clr = h < clr ? h : clr;
-        }
-        const double* is = mp.pred_s + ro * NP1;
-        const double* ie = mp.pred_ey + ro * NP1;
-        double off;
-        if (cbf && safety_window(dist_ego, nce, is[0], margin, L, off)) {   // column 0: one estimated step ahead (quirk F2)
-            double* os = mp.obs_s + (rc * V + n) * N1;
-            double* oe = mp.obs_ey + (rc * V + n) * N1;
-            for (int j = 0; j < N1; j++) { os[j] = is[j]; oe[j] = ie[j]; }
-            mp.lap_off[rc * V + n] = off;
-            if (mp.obs_dims) { mp.obs_dims[(rc * V + n) * 2] = l_sum; mp.obs_dims[(rc * V + n) * 2 + 1] = w_sum; }
-            n++;
-        }
-    }
-    for (int v = n; v < V; v++) {
-        double* os = mp.obs_s + (rc * V + v) * N1;
-        double* oe = mp.obs_ey + (rc * V + v) * N1;
-        for (int j = 0; j < N1; j++) { os[j] = 0.0; oe[j] = 0.0; }
-        mp.lap_off[rc * V + v] = 0.0;
-        if (mp.obs_dims) { mp.obs_dims[(rc * V + v) * 2] = 0.0; mp.obs_dims[(rc * V + v) * 2 + 1] = 0.0; }
-    }
-    mp.n_obs[rc] = n;
+    nlp_ego_pass(mp.xcurv, mp.car_dims, mp.pred_s, mp.pred_ey, NP1, L, d.safety_time, d.l_sum, d.w_sum, d.degree, N1, C, c, rc, cbf, mp.nlp);
     mp.m_nlp[rc] = (pol == CRX_POLICY_MPC_LTI || cbf) ? 1 : 0;
-    if (mp.clear) mp.clear[rc] = clr;
     if (!ilqr_on) return;
     // the iLQR family: lap offsets (quirk I5: the obstacle's cycle from column 0 of its roll-out) and the count, from this ego's slot map
+    const double s_e = mp.xcurv[6 * rc + 4];
     int ni = 0;
     for (int v = 0; v < V; v++) {
         const int o = il_src[t * V + v];
@@ -502,15 +468,9 @@ __global__ void __launch_bounds__(256) crx_mixed_prep_kernel(const crx_mixed_kpa
     }
     mp.il_n_obs[rc] = ni;
     mp.m_ilqr[rc] = pol == CRX_POLICY_ILQR ? 1 : 0;
-    // element e of the block's range of il_obs_s / il_obs_ey [R C][V][N_ilqr + 1]: ego q = e / (V NI1) of the block, slot v, column j
-    const int row_i = V * NI1;
-    for (int e = t; e < n_live * row_i; e += n_live) {
-        const int q = e / row_i, m = e - q * row_i, v = m / NI1, j = m - NI1 * v;
-        const int o = il_src[q * V + v];
-        const size_t src = (rc0 + (q - q % C) + (o >= 0 ? o : 0)) * NP1 + j;
-        mp.il_obs_s[rc0 * row_i + e] = o >= 0 ? mp.pred_s[src] : 0.0;
-        mp.il_obs_ey[rc0 * row_i + e] = o >= 0 ? mp.pred_ey[src] : 0.0;
-    }
+    const double* const i_src[2] = {mp.pred_s, mp.pred_ey};
+    double* const i_dst[2] = {mp.il_obs_s, mp.il_obs_ey};
+    block_gather<2, true>(b, C, NI1, NP1, i_src, i_dst, [&](int q, int v) { return (int)il_src[q * V + v]; });
 }
 
 hipError_t crx_launch_prep(const crx_prep_kparams& pp, hipStream_t st) { return crx_launch_1d(crx_prep_kernel, pp.n_scen, 1, WAVE, st, pp); }

@@ -6,7 +6,9 @@ families (the masked / ordered / dims / wrap / noise variants included) -- a NUL
 the library tests, a negative batch, each NULL array, out-of-range per-element values (host-pointer side) and the empty call.
 One line per call: (return code, crx_last_error()).  Every entry of the table is refused -- or, for the empty call, answered --
 before any launch, so nothing here reaches a kernel; as a second line of defence the _dev calls carry the address of one zeroed
-device block.  Without a GPU the table still runs: the families that look at the device first all answer CRX_ERR_NOT_INIT.
+device block.  Without a GPU the table still runs: the families that look at the device first all answer CRX_ERR_NOT_INIT; the field
+families (crx_field_prep, crx_field_traffic, crx_mixed_prep, crx_mixed_commit_dev) refuse on their arguments alone, with calls that have two
+things wrong at once to pin the order of their checks.
 Part 2, results (GPU only): each of the 12 host-pointer entry points once on a small valid input (the synthetic draws and
 tests/golden/*.npz, as smoke() uses them), every output array dumped; crx_lmpc_prep with a non-zero seed for A, B, C.
 --compare: the two dumps line for line and array for array, bit for bit; exit status 1 on any difference."""
@@ -296,6 +298,58 @@ sc_good = dict(d=abi.scene_desc(N, VA, V, 20.0), n_scen=1, ego_xcurv=z(1, 6), n_
 family(sc_good, [("crx_planner_scene", ["d", "n_scen"] + sc_sig, False), ("crx_planner_scene_dev", ["d", "n_scen"] + sc_sig + ["stream"], True)],
        [("N", 0), ("N", 25), ("n_all_max", 0), ("n_all_max", 65), ("n_veh_max", 0), ("n_veh_max", 7), ("lap_length", 0.0), ("lap_length", float("inf"))],
        sc_sig, batch_key="n_scen", host_cases=[("n_all[0]=-1", setel("n_all", 0, -1)), ("n_all[0]=5", setel("n_all", 0, VA + 1))])
+
+# ---- fields of driven cars: field prep, field traffic, mixed prep (arguments first, the device after), mixed commit ----------------
+RF, CF, NS, NIL = 2, 3, 4, 5
+BF, VF = RF * CF, CF - 1
+fd_fields = [("N", 0), ("N", 25), ("n_cars", 0), ("n_cars", 8), ("n_seg", 0), ("n_seg", 65), ("degree", 0), ("degree", 3), ("degree", 10),
+             ("lap_length", 0.0), ("lap_length", float("inf")), ("dt", 0.0), ("l_sum", 0.0), ("w_sum", float("nan"))]
+fp_arr = ["track", "xcurv", "car_dims", "pred_s", "pred_ey", "obs_s", "obs_ey", "lap_off", "n_obs", "obs_dims"]
+fp_good = dict(d=abi.field_desc(N, CF, NS, 20.0), n_races=RF, track=z(NS, 6), xcurv=z(BF, 6), car_dims=np.ones((RF, CF, 2)), pred_s=z(BF, N + 1),
+               pred_ey=z(BF, N + 1), obs_s=z(BF, VF, N + 1), obs_ey=z(BF, VF, N + 1), lap_off=z(BF, VF), n_obs=z(BF, dtype=I), obs_dims=z(BF, VF, 2),
+               clear=z(BF))
+# (two things wrong at once: the order of the checks decides which message wins)
+dims_cases = [("car_dims, obs_dims NULL", lambda v: v.update(car_dims=None, obs_dims=None)),
+              ("n_cars=1, obs arrays NULL", lambda v: [setf("d", "n_cars", 1)(v), v.update(obs_s=None, obs_ey=None, lap_off=None, obs_dims=None)]),
+              ("n_cars=0, n_races=-1", lambda v: [setf("d", "n_cars", 0)(v), v.update(n_races=-1)]),
+              ("obs_dims NULL, xcurv NULL", lambda v: v.update(obs_dims=None, xcurv=None))]
+host_dims_cases = [("car_dims[0][1]=(0,1)", setel("car_dims", 2, 0.0)), ("car_dims[1][2]=(1,inf)", setel("car_dims", 11, float("inf"))),
+                   ("car_dims[0][0]=(-1,1), pred_s NULL", lambda v: [setel("car_dims", 0, -1.0)(v), v.update(pred_s=None)])]
+family(fp_good, [("crx_field_prep", ["d", "n_races"] + fp_arr + ["clear"], False), ("crx_field_prep_dev", ["d", "n_races"] + fp_arr + ["clear", "stream"], True)],
+       fd_fields, fp_arr, batch_key="n_races", host_cases=dims_cases + host_dims_cases, dev_cases=dims_cases)
+ft_arr = ["track", "xcurv", "pred_s_car", "pred_ey_car", "veh_xcurv", "pred_s", "pred_ey", "n_all"]
+ft_good = dict(d=abi.field_desc(N, CF, NS, 20.0), n_races=RF, track=z(NS, 6), xcurv=z(BF, 6), pred_s_car=z(BF, N + 1), pred_ey_car=z(BF, N + 1),
+               veh_xcurv=z(BF, VF, 6), pred_s=z(BF, VF, N + 1), pred_ey=z(BF, VF, N + 1), n_all=z(BF, dtype=I))
+family(ft_good, [("crx_field_traffic", ["d", "n_races"] + ft_arr, False), ("crx_field_traffic_dev", ["d", "n_races"] + ft_arr + ["stream"], True)],
+       fd_fields, ft_arr, batch_key="n_races",
+       host_cases=[("n_cars=1, per-ego arrays NULL", lambda v: [setf("d", "n_cars", 1)(v), v.update(veh_xcurv=None, pred_s=None, pred_ey=None)])])
+mp_arr = ["track", "xcurv", "policy", "car_dims", "pred_s", "pred_ey", "obs_s", "obs_ey", "lap_off", "n_obs", "obs_dims", "m_nlp", "il_obs_s", "il_obs_ey",
+          "il_lap_off", "il_n_obs", "m_ilqr"]
+mp_good = dict(fp_good, d=abi.mixed_desc(N, NIL, CF, NS, 20.0), policy=z(BF, dtype=I), pred_s=z(BF, N + 1), pred_ey=z(BF, N + 1), m_nlp=z(BF, dtype=I),
+               il_obs_s=z(BF, VF, NIL + 1), il_obs_ey=z(BF, VF, NIL + 1), il_lap_off=z(BF, VF), il_n_obs=z(BF, dtype=I), m_ilqr=z(BF, dtype=I))
+il_null = dict(il_obs_s=None, il_obs_ey=None, il_lap_off=None, il_n_obs=None, m_ilqr=None)
+mixed_cases = dims_cases + [("N_ilqr=0, iLQR arrays NULL", lambda v: [setf("d", "N_ilqr", 0)(v), v.update(il_null)]),
+                            ("N_ilqr=-1, n_cars=0", lambda v: [setf("d", "N_ilqr", -1)(v), setf("d", "n_cars", 0)(v)]),
+                            ("ilqr_obstacles=2, dt=0", lambda v: [setf("d", "ilqr_obstacles", 2)(v), setf("d", "dt", 0.0)(v)]),
+                            ("m_ilqr NULL, m_nlp NULL", lambda v: v.update(m_ilqr=None, m_nlp=None)),
+                            ("n_cars=1, [V] arrays NULL", lambda v: [setf("d", "n_cars", 1)(v), v.update(obs_s=None, obs_ey=None, lap_off=None, obs_dims=None,
+                                                                                                       il_obs_s=None, il_obs_ey=None, il_lap_off=None)])]
+family(mp_good, [("crx_mixed_prep", ["d", "n_races"] + mp_arr + ["clear"], False), ("crx_mixed_prep_dev", ["d", "n_races"] + mp_arr + ["clear", "stream"], True)],
+       fd_fields + [("N_ilqr", -1), ("N_ilqr", 65), ("ilqr_obstacles", -1), ("ilqr_obstacles", 2)], mp_arr, batch_key="n_races",
+       host_cases=mixed_cases + host_dims_cases + [("policy[0]=-1", setel("policy", 0, -1)), ("policy[5]=6", setel("policy", 5, 6)),
+                                                   ("car_dims[0][0]=(0,1), il_n_obs NULL", lambda v: [setel("car_dims", 0, 0.0)(v), v.update(il_n_obs=None)]),
+                                                   ("car_dims[0][0]=(0,1), policy[0]=9", lambda v: [setel("car_dims", 0, 0.0)(v), setel("policy", 0, 9)(v)])],
+       dev_cases=mixed_cases)
+mc_sig = ["batch", "policy", "x", "vt", "eyt", "K", "xt", "U_nlp", "nlp_stride", "nlp_status", "U_ilqr", "ilqr_stride", "ilqr_status", "u", "ctrl_status", "stream"]
+mc_good = dict(batch=BF, policy=z(BF, dtype=I), x=z(BF, 6), vt=z(BF), eyt=z(BF), K=z(BF, 2, 6), xt=z(BF, 6), U_nlp=z(BF, N, 2), nlp_stride=2 * N,
+               nlp_status=z(BF, dtype=I), U_ilqr=z(BF, NIL, 2), ilqr_stride=2 * NIL, ilqr_status=z(BF, dtype=I), u=z(BF, 2), ctrl_status=z(BF, dtype=I))
+for label, mut in ([("good", lambda v: None), ("batch=-1", setv("batch", -1)), ("batch=0", setv("batch", 0)), ("nlp_stride=1", setv("nlp_stride", 1)),
+                    ("ilqr_stride=0", setv("ilqr_stride", 0)), ("batch=-1, eyt NULL", lambda v: v.update(batch=-1, eyt=None)),
+                    ("every family NULL", lambda v: v.update(vt=None, eyt=None, K=None, xt=None, U_nlp=None, nlp_status=None, U_ilqr=None, ilqr_status=None))]
+                   + [("%s NULL" % a, setv(a, None)) for a in mc_sig if isinstance(mc_good.get(a), np.ndarray)]):
+    v = copy_vals(mc_good)
+    mut(v)
+    call("crx_mixed_commit_dev", mc_sig, v, label, True)
 
 os.makedirs(os.path.dirname(OUT), exist_ok=True)
 open(OUT % TAG + ".txt", "w").write("\n".join(lines) + "\n")

@@ -255,15 +255,30 @@ struct Lay {
     static constexpr int T = pv + NX;
     static constexpr int WORK2 = PT_ALIAS ? WORK : T + NX * TS;
     static constexpr int H = H_ALIAS ? dZ : WORK2;           // [NZ][HS]  (over dZ from its start: stage 0 of dZ is written only after the sweep)
-    static constexpr int Kk = H_ALIAS ? WORK2 : H + NZ * HS; // [NMAX][NU][NX]
+    // [r20] The feedback of stage k -- K_k [NU][NX] and kff_k [NU] -- is ONE block of KS = NU (NX + 1) doubles at Kk + k KS, so that every store of the
+    // backward sweep is `lane base + k KS`: an immediate offset in the unrolled sweeps, no pointer that walks the horizon.  Inside the block:
+    //   NX odd  (one or three obstacles; KREC): NU records [K_k[a][0 .. NX) | kff_k[a]] of KR = NX + 1 doubles, kff the view of column NX.  A record is
+    //           an even number of doubles: 16-byte aligned, one contiguous read for a forward stage, and ONE base per lane of the update pass
+    //           (base + a KR + k KS)
+    //   NX even (none, two, six): K_k[a] at a NX, then kff_k[0 .. NU).  Records of NX + 1 doubles would put every other row of K off its 16 bytes, and the
+    //           compiler then reads the rows with ds_read2_b64 where it had ds_read_b128 (measured: planner workloads 3 .. 5 % slower); a lane keeps NU bases
+    // (KA, KFA: the strides of the rows and of kff over the inputs of a stage.)  EVERY lane of the update pass owns a column uj in 0 .. NX (its lane map, or
+    // column 0 where the map gives it nothing) and carries that column's feedback through the same instructions on the same operands as the column's own
+    // lane: all of them store it, to the column's address, lanes of one column the same bits.  So the sweep needs no sink for these stores.  (A sink in
+    // front of Kk, overwritten stage by stage, was the other candidate: in the planner layouts, where P, T and H all live in aliased storage, what precedes
+    // Kk is the tail of hg, which a retry and the second solve of the predictor-corrector iteration read again.)
+    static constexpr int KR = NX + 1, KS = NU * KR;
+    static constexpr bool KREC = KR % 2 == 0;
+    static constexpr int KA = KREC ? KR : NX, KFA = KREC ? KR : 1;
+    static constexpr int Kk = H_ALIAS ? WORK2 : H + NZ * HS; // [NMAX][KS]: K_k[a][j] = Kk[k KS + a KA + j]
     static constexpr int G = SLIM ? Kk : Gpos;
     // slim [r4b]: Sigma = nu / t of the CBF rows, [NMAX][NO], written by assemble_newton and read by the backward sweep's H phase -- behind H
     // in dZ, which is dead from the adjoint to the forward sweep (the full layout has rsig for this; recomputing it per stage and pass
     // was three LDS reads and three VALU instructions per obstacle: 360 of the 12.3 k instructions of a <3,20> iteration)
     static constexpr int sigS = (SLIM && H_ALIAS && NZ * HS + NMAX * NO <= NV) ? dZ + NZ * HS : -1;
-    static_assert(NMAX * NOBS * 4 <= NMAX * NU * NX, "G fits inside Kk");
-    static constexpr int kf = Kk + NMAX * NU * NX;   // [NMAX][NU]
-    static constexpr int Fth = kf + NMAX * NU;
+    static_assert(NMAX * NOBS * 4 <= NMAX * KS, "G fits inside Kk");
+    static constexpr int kf = Kk + (KREC ? NX : NU * NX);   // kff_k[a] = kf[k KS + a KFA]
+    static constexpr int Fth = Kk + NMAX * KS;
     static constexpr int Fph = Fth + MAXF;
     static constexpr int cst = Fph + MAXF;           // 0..5 wq, 6..7 wr, 8.. lap_off (NOBS <= 8), 16.. 1/l_sum per obstacle, 16+NOBS.. 1/w_sum per obstacle
     static constexpr int dmy = cst + 16 + 2 * NOBS;  // sink of the address-predicated stores (lanes without an entry write here)
@@ -292,8 +307,8 @@ struct Lay {
     // behind the layout -- the second wave factorises the reduced Hessian with the NEXT entry of the inertia-correction schedule while the first
     // tries the current one.  In doubles from sm; ctl = {command, dw, convexified, ok} mailbox between the two waves.
     static constexpr int R2 = (int)((BYTES + 15) / 16) * 2;
-    static constexpr int P2 = R2, pv2 = P2 + NX * NX, T2 = pv2 + NX, H2 = (T2 + NX * TS + 1) & ~1, Kk2 = H2 + NZ * HS, kf2 = Kk2 + NMAX * NU * NX,
-                         dZ2 = kf2 + NMAX * NU, ctl = dZ2 + NZ, R2_END = ctl + 4;
+    static constexpr int P2 = R2, pv2 = P2 + NX * NX, T2 = pv2 + NX, H2 = (T2 + NX * TS + 1) & ~1, Kk2 = H2 + NZ * HS, kf2 = Kk2 + (kf - Kk),
+                         dZ2 = Kk2 + NMAX * KS, ctl = dZ2 + NZ, R2_END = ctl + 4;
     static constexpr size_t BYTES_SPEC = (size_t)R2_END * 8;
 };
 
@@ -864,7 +879,7 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
     using L = Lay<NOBS, NMAX>;
     constexpr int NX = L::NX, NU = L::NU, NZ = L::NZ, HS = L::HS;
     constexpr int oP = REG ? L::P2 : L::P, opv = REG ? L::pv2 : L::pv, oT = REG ? L::T2 : L::T, oH = REG ? L::H2 : L::H, oKk = REG ? L::Kk2 : L::Kk,
-                  okf = REG ? L::kf2 : L::kf, odZ = REG ? L::dZ2 : L::dZ;
+                  odZ = REG ? L::dZ2 : L::dZ;
     const int N = c.N, lane = c.lane;
     const long long qs = CLK();
     // [r4] The gradient p of the value function lives in REGISTERS, entry i in lane i: the update phase computes p_new there (its lane
@@ -983,7 +998,7 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
     // update phase: lane map [0, NP) the upper triangle of P_new incl. the gradient column (i <= j <= NX),
     // [NP, NP+NX+1) one feedback column each (<= 64 lanes for NX <= 9: one pass; the six-obstacle instantiation takes two [r4])
     constexpr int NP = NX * (NX + 1) / 2 + NX, UCNT = L::UCNT;
-    int yiA[UCNT], yjA[UCNT], s0A[UCNT], pst1[UCNT], pst2[UCNT], kstr[UCNT], kstep[UCNT], kst[UCNT];
+    int yiA[UCNT], yjA[UCNT], s0A[UCNT], pst1[UCNT], pst2[UCNT], kst[UCNT][L::KREC ? 1 : NU];
     // [r6] 0 / 1 lane masks: t + x on the lanes of a set, t on the others, is fma(mask, x, t) -- one rounding of the same sum (x finite: 0 * x = 0) --
     // instead of two v_cndmask_b32 and an add per use and stage
     bool exSl[UCNT], exEl[UCNT];   // (the lane sets of the two masks below)
@@ -1012,17 +1027,18 @@ __device__ __forceinline__ bool riccati_backward(double* sm, const int* si, cons
         s0A[q] = FULL ? oH + ui * HS + ujj : seli(gcol, oH + ui * HS + ujj, oH + uj * HS + ui);
         pst1[q] = SINK(isP, seli(gcol, opv + ui, oP + ui * NX + uj));
         pst2[q] = SINK(isP, seli(gcol, opv + ui, oP + uj * NX + ui));
-        kstr[q] = seli(isK, seli(gcol, 1, NX), 0); kstep[q] = seli(isK, seli(gcol, NU, NU * NX), 0);
-        kst[q] = SINK(isK, seli(gcol, okf, oKk + uj) + (N - 1) * kstep[q]);
+        // [r20] column uj of the stage's feedback block (uj = NX: kff), the same in every stage: Lay::KS.  No lane is left out
+        if constexpr (L::KREC) {
+            kst[q][0] = oKk + uj;
+        } else {
+#pragma unroll
+            for (int a = 0; a < NU; a++) kst[q][a] = oKk + seli(gcol, (L::kf - L::Kk) + a * L::KFA, uj + a * L::KA);
+        }
+        (void)isK;
         exSl[q] = isP && !gcol && ui == uj && ui == 4; exEl[q] = isP && !gcol && ui == uj && ui == 5;
         mSl[q] = exSl[q] ? 1.0 : 0.0; mEl[q] = exEl[q] ? 1.0 : 0.0;
     }
     if (tsub) tsub[2] += CLK() - qs;   // set-up of the sweep (terminal P, lane maps, stage-invariant operands)
-    int kst0[UCNT];   // (SHARED: kst walks down the horizon with the sweep; every attempt starts from stage N-1 again)
-    if constexpr (SHARED) {
-#pragma unroll
-        for (int q = 0; q < UCNT; q++) kst0[q] = kst[q];
-    }
 attempt: __attribute__((unused));   // (SHARED: a retry of the schedule comes back here, behind the set-up)
 #pragma unroll UNR
     for (int k = N - 1; k >= 0; k--) {
@@ -1224,8 +1240,10 @@ attempt: __attribute__((unused));   // (SHARED: a retry of the schedule comes ba
                     for (int qq = a + 1; qq < NU; qq++) yj[q][a] = fma(-Lf[qq][a], yj[q][qq], yj[q][a]);
                 }
 #pragma unroll
-                for (int a = 0; a < NU; a++) LD(kst[q] + a * kstr[q]) = yj[q][a];
-                kst[q] -= kstep[q];
+                for (int a = 0; a < NU; a++) {
+                    if constexpr (L::KREC) LD(kst[q][0] + a * L::KR + k * L::KS) = yj[q][a];
+                    else LD(kst[q][a] + k * L::KS) = yj[q][a];
+                }
             }
         }
         if (!ok) break;  // uniform: every lane computed the same pivots (the entries just stored are discarded with the sweep)
@@ -1313,10 +1331,6 @@ attempt: __attribute__((unused));   // (SHARED: a retry of the schedule comes ba
                 LD(SINK(isPmt && c8t == 6, oT + g8t * L::TS + NX + 2)) = pn;
                 SYNC();
                 ok = true;
-                // (an opaque copy: the feedback addresses of the twelve unrolled stages -- invariant from attempt to attempt -- are then formed stage by stage
-                // as in the one-attempt form; hoisted in front of the attempts they were 36 registers carried through the whole sweep, 116 B of scratch per lane)
-#pragma unroll
-                for (int q = 0; q < UCNT; q++) { kst[q] = kst0[q]; asm volatile("" : "+v"(kst[q])); }
                 if (tsub) tsub[2] += CLK() - qt;
                 goto attempt;
             }
@@ -1350,14 +1364,14 @@ __device__ __forceinline__ void riccati_backward_vec(double* sm, const Ctx& c) {
         auto stage = [&](int k) {
             const double gn = LD(L::hg + (k >= 1 ? k - 1 : 0) * NZ + la);
             const double rD0 = LD(L::Hd + k * NZ + 0), rD1 = LD(L::Hd + k * NZ + 1), L10 = LD(L::Hd + k * NZ + 2);
-            const double k0 = LD(L::Kk + (k * NU + 0) * NX + lx), k1 = LD(L::Kk + (k * NU + 1) * NX + lx);
+            const double k0 = LD(L::Kk + k * L::KS + lx), k1 = LD(L::Kk + k * L::KS + L::KA + lx);
             double hv = gk;
             hv = stage_dot<L, NX, 0>(p, mcol, hv);
             const double hu0 = lane_f64(hv, NX), hu1 = lane_f64(hv, NX + 1);
             const double y1 = hu1 - L10 * hu0;
             const double z1 = y1 * rD1;
             const double z0 = hu0 * rD0 - L10 * z1;
-            LD(SINK(in && lane < NU, L::kf + k * NU + lane)) = sel(lane == 0, -z0, -z1);
+            LD(SINK(in && lane < NU, L::kf + k * L::KS + (lane < NU ? lane : 0) * L::KFA)) = sel(lane == 0, -z0, -z1);
             p = hv + k0 * hu0 + k1 * hu1;               // lanes < NX: p_k (the other lanes carry numbers nobody reads)
             gk = gn;
             STAGE_FENCE();
@@ -1399,9 +1413,9 @@ __device__ __forceinline__ void riccati_forward(double* sm, const Ctx& c) {
         if (lane < NZ) {
             const bool isx = lane < NX;
             const int ua = isx ? 0 : lane - NX;
-            int cad = isx ? L::M + lane * NZ : L::Kk + ua * NX;            // + k NU NX in the input lanes
-            const int cstep = isx ? 0 : NU * NX;
-            const int kfad = L::kf + ua;                                     // state lanes read kff_k[0] and multiply it with zero
+            int cad = isx ? L::M + lane * NZ : L::Kk + ua * L::KA;         // + k KS in the input lanes
+            const int cstep = isx ? 0 : L::KS;
+            const int kfad = L::kf + ua * L::KFA;                            // state lanes read kff_k[0] and multiply it with zero
             const int sad = L::dZ + lane + (isx ? NZ : 0);                   // state lanes store x_{k+1}, input lanes du_k
             const double one = isx ? 0.0 : 1.0;
             double mu_[NU];
@@ -1418,7 +1432,7 @@ __device__ __forceinline__ void riccati_forward(double* sm, const Ctx& c) {
                 cad += (k + 1 < N) ? cstep : 0;
 #pragma unroll
                 for (int j = 0; j < NX; j++) cnx[j] = LD(cad + j);
-                kfn = LD(kfad + kn * NU);
+                kfn = LD(kfad + kn * L::KS);
                 double acc = fma(kfv, one, 0.0);
                 acc = row_dot<NX, 0>(y, coef, acc);
                 const double du = acc;                                       // lanes NX ..: du_k
@@ -1452,14 +1466,14 @@ __device__ __forceinline__ void riccati_forward(double* sm, const Ctx& c) {
     double zx = LD(L::dZ + (lane < NX ? lane : 0));   // dx_0: zero but for the free sigma_0 (riccati_backward)
     double kr[NX], kfa;
 #pragma unroll
-    for (int j = 0; j < NX; j++) kr[j] = LD(L::Kk + ua * NX + j);
-    kfa = LD(L::kf + ua);
+    for (int j = 0; j < NX; j++) kr[j] = LD(L::Kk + ua * L::KA + j);
+    kfa = LD(L::kf + ua * L::KFA);
     auto stage = [&](int k) {
         double krn[NX], kfn;                           // next stage's feedback row: off the dependent chain
         const int kn = k + 1 < N ? k + 1 : k;
 #pragma unroll
-        for (int j = 0; j < NX; j++) krn[j] = LD(L::Kk + (kn * NU + ua) * NX + j);
-        kfn = LD(L::kf + kn * NU + ua);
+        for (int j = 0; j < NX; j++) krn[j] = LD(L::Kk + kn * L::KS + ua * L::KA + j);
+        kfn = LD(L::kf + kn * L::KS + ua * L::KFA);
         double du = kfa, xn = 0.0;
         // (not through stage_dot: the v_readlane form broadcasts dx once for both products, and the general instantiations' code moves when it does not)
         if constexpr (ROWDPP<L>) {   // broadcast and FMA in one instruction (crx_wave.h row_dot): same terms in the same order
@@ -2503,8 +2517,7 @@ crx_solve_kernel(const crx_solve_params kp) {
                 if (!nvalid) break;                               // the schedule is exhausted (sequential: dw > IPM_DW_MAX)
                 if (!post) { sdw = ndw; cz = ncz; avail = 0; tries = ntries; continue; }
                 if (__builtin_amdgcn_readfirstlane((int)LD(L::ctl + 3)) != 0) {
-                    for (int e = lane; e < N * L::NU * NX; e += WAVE) LD(L::Kk + e) = LD(L::Kk2 + e);
-                    for (int e = lane; e < N * L::NU; e += WAVE) LD(L::kf + e) = LD(L::kf2 + e);
+                    for (int e = lane; e < N * L::KS; e += WAVE) LD(L::Kk + e) = LD(L::Kk2 + e);
                     if (lane < NZ) LD(L::dZ + lane) = LD(L::dZ2 + lane);
                     SYNC();
                     ok = true; used_convex = ncz;

@@ -180,6 +180,23 @@ template <int NOBS, int NMAX> constexpr unsigned LoadsFirst = (NOBS == 1 && NMAX
 template <int NOBS, int NMAX> constexpr bool Obs1Tuned = NOBS == 1 && NMAX == 12 && !CRX_TU_GENERAL;
 template <int NOBS, int NMAX> constexpr bool RetryShared = (CRX_RETRY_SHARED) != 0 && Obs1Tuned<NOBS, NMAX>;
 template <int NOBS, int NMAX> constexpr bool CbfCarry = (CRX_CBF_CARRY) != 0 && Obs1Tuned<NOBS, NMAX> && NMAX * NOBS <= WAVE;
+// [r21] Two more values that the same instantiations formed twice at the same point, from the same operands, with the same roundings (A/B builds:
+// make EXTRA=-DCRX_DIST_CARRY=0 / -DCRX_DNU_CARRY=0 is the parent's code):
+//   CRX_DIST_CARRY    the first_order call that ends the accept step takes the four normalised CBF distances of the lane's row from the accepted
+//                     line-search trial (cbf_dist at Z + al dZ, which is what accept stores in Z: fma(0, dZ, Z) is Z).  Needs CbfCarry's one pass.  The
+//                     stand-alone first_order calls (start, restart, restoration) and eval_rows have no accepted trial and evaluate as before
+//   CRX_DNU_CARRY     the row-step pass stores the multiplier step dnu = -w + Sigma (rp - dt) of every row it forms; the accept pass loads it where
+//                     it loaded rc, rt, rdt, Sigma and w to form the same number again.  It lives in the first rows of Kk, which is dead from the
+//                     end of the forward sweep to the next backward sweep.  (NOT in hg: a jam exit that finds nothing to restore re-runs the
+//                     iteration from its top, and the adjoint sweep of the re-run reads ga = hg as the abandoned iteration left it.)
+#ifndef CRX_DIST_CARRY
+#define CRX_DIST_CARRY 1
+#endif
+#ifndef CRX_DNU_CARRY
+#define CRX_DNU_CARRY 1
+#endif
+template <int NOBS, int NMAX> constexpr bool DistCarry = (CRX_DIST_CARRY) != 0 && CbfCarry<NOBS, NMAX>;
+template <int NOBS, int NMAX> constexpr bool DnuCarry = (CRX_DNU_CARRY) != 0 && Obs1Tuned<NOBS, NMAX>;   // (the rows fit into Kk: static_assert in the kernel)
 // end of a stage of an UNROLLED sweep [r4]: without it the scheduler lifts the loads of all later stages to the top of the sweep and the
 // registers they occupy are paid for in scratch (a wave writes its spills once: 100 B per lane were x8 the algorithmic bytes written of a cfg2 launch)
 #define STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -213,7 +230,7 @@ struct Lay {
     static constexpr int rnu = rt + MR;
     static constexpr int rc = rnu + MR;
     static constexpr int rdt = rc + MR;
-    static constexpr int rtt = rdt + MR;             // trial slack / 1/t (dnu is recomputed at accept: -w + Sigma (rp - dt))
+    static constexpr int rtt = rdt + MR;             // trial slack / 1/t (dnu is recomputed at accept: -w + Sigma (rp - dt); DnuCarry [r21]: parked in Kk)
     // SLIM layout [r3] (the 3-obstacle instantiations: BASELINE configs[3], N = 20): four problems per CU need <= 40 960 B
     // and the full layout is 52 560 B.  Whatever is a pure function of other LDS contents is recomputed where it is used
     // -- Sigma and w from (t, nu, c, mu), the bound of a simple row from its slot, the presence of a simple row from its
@@ -458,6 +475,18 @@ __device__ __forceinline__ double cbf_value(const double* sm, const Ctx& c, int 
     return gn - sk1 - c.om * (gc - sk) - c.alpha * c.cm;
 }
 
+// [r21] cbf_value() that also hands out the four distances it formed (DistCarry: the line-search trial keeps them for first_order)
+template <int NOBS, int NMAX>
+__device__ __forceinline__ double cbf_value_dist(const double* sm, const Ctx& c, int k, int o, double al, double& dsc, double& dec, double& dsn, double& den) {
+    using L = Lay<NOBS, NMAX>;
+    cbf_dist<NOBS, NMAX>(sm, c, k, o, al, dsc, dec, dsn, den);
+    const int q = c.degree;
+    const double gc = ipow_d(dsc, q) + ipow_d(dec, q), gn = ipow_d(dsn, q) + ipow_d(den, q);
+    const double sk = LD(L::Z + k * L::NZ + 6 + o) + al * LD(L::dZ + k * L::NZ + 6 + o);
+    const double sk1 = LD(L::Z + k * L::NZ + L::NX + 2 + o) + al * LD(L::dZ + k * L::NZ + L::NX + 2 + o);
+    return gn - sk1 - c.om * (gc - sk) - c.alpha * c.cm;
+}
+
 // cost at Z + al*dZ (every lane returns the total)
 template <int NOBS, int NMAX>
 __device__ __forceinline__ double cost_value(const double* sm, const Ctx& c, double al) {
@@ -539,10 +568,14 @@ __device__ __forceinline__ void eval_rows(double* sm, const int* si, const Ctx& 
 
 // First-order pieces at the iterate: CBF derivative table G, CBF Jacobians Jc (scaled, stage
 // coordinates) and the Lagrangian gradient ga = grad f - J' nu per stage coordinate.
-template <int NOBS, int NMAX, unsigned LF = 0>
-__device__ __forceinline__ void first_order(double* sm, const int* si, const Ctx& c) {
+// (DC [r21], DistCarry: the caller -- the accept step -- hands in the four distances of this lane's CBF row as the accepted trial formed them, at
+// the point that is now the iterate; one pass, the row of a lane is the same in both places.)
+template <int NOBS, int NMAX, unsigned LF = 0, bool DC = false>
+__device__ __forceinline__ void first_order(double* sm, const int* si, const Ctx& c, double dsc_tr = 0.0, double dec_tr = 0.0, double dsn_tr = 0.0,
+                                            double den_tr = 0.0) {
     using L = Lay<NOBS, NMAX>;
     const int N = c.N;
+    static_assert(!DC || (NOBS > 0 && NMAX * NOBS <= WAVE), "carried distances: one CBF row per lane");
     if (NOBS) {
 #pragma unroll
         for (int q_ = 0; q_ < (NMAX * NOBS + WAVE - 1) / WAVE; q_++) {
@@ -555,7 +588,8 @@ __device__ __forceinline__ void first_order(double* sm, const int* si, const Ctx
             // that 0 * (stale LDS) never becomes NaN in G / J
             const bool here = o < c.nobs;
             double dsc, dec, dsn, den;
-            cbf_dist<NOBS, NMAX>(sm, c, k, o, 0.0, dsc, dec, dsn, den);
+            if constexpr (DC) { dsc = dsc_tr; dec = dec_tr; dsn = dsn_tr; den = den_tr; }
+            else cbf_dist<NOBS, NMAX>(sm, c, k, o, 0.0, dsc, dec, dsn, den);
             const int q = c.degree;
             const double qd = (double)q, qq = (double)(q * (q - 1));
             const double p2sn = ipow_d(dsn, q - 2), p2en = ipow_d(den, q - 2);
@@ -1802,6 +1836,12 @@ crx_solve_kernel(const crx_solve_params kp) {
     // [r9] ... and the two pieces of repeated work they leave out (RetryShared: the one-wave retry loop only; CbfCarry)
     constexpr bool RSH = NFIX != 0 && QPM == 0 && SPEC == 0 && RetryShared<NOBS, NMAX>;
     constexpr bool CBFC = NFIX != 0 && QPM == 0 && CbfCarry<NOBS, NMAX>;
+    // [r21] ... and two more (DistCarry: first_order after accept takes the trial's CBF distances; DnuCarry: accept takes dnu from the row steps, through Kk)
+    // (the one-wave kernels only, like RetryShared: the two-wave kernels stand at 252 / 254 VGPRs; either of the two takes both to 254 .. 256, and with both
+    // the register allocator of this toolchain crashes on <1,12,6,12, SPEC = 1>.  They keep the evaluations -- same bits: tests/test_gpu_obs1_carry_bits.py)
+    constexpr bool DISTC = NFIX != 0 && QPM == 0 && SPEC == 0 && DistCarry<NOBS, NMAX>;
+    constexpr bool DNUC = NFIX != 0 && QPM == 0 && SPEC == 0 && DnuCarry<NOBS, NMAX>;
+    static_assert(!DNUC || (!L::SLIM && L::MR <= NMAX * L::KS && L::G != L::Kk), "dnu of every row inside Kk, and nothing else lives there between the sweeps");
     constexpr int RPASS = (L::MR + WAVE - 1) / WAVE, CPASS = (L::NV + WAVE - 1) / WAVE;
     static_assert(LF == 0 || !L::SLIM, "the loads-first row passes are written for the full layout (row_scale, row_bound, row_sig_w are loads there)");
 #if CRX_STATIC_LDS
@@ -2579,6 +2619,10 @@ crx_solve_kernel(const crx_solve_params kp) {
             // dnu = (mu - t nu - nu dt)/t = mu/t - nu - Sigma dt = -w + Sigma (rp - dt)
             const double dnu = sel(on, -rwj + rsj * (rp - dt), 0.0);
             LD(SINK(store, L::rdt + j)) = dt;
+            // (DNUC: for the accept pass, which formed it again from five loads.  Kk is dead from the forward sweep above to the next backward sweep.
+            // Rows that are off store the zero nobody reads: accept touches the multiplier of a row that is on only.  Storing -dnu, the form the
+            // ratio test below consumes, counted four instructions more: HISTORY.md, round 21)
+            if constexpr (DNUC) LD(SINK(store, L::Kk + j)) = dnu;
             const double dtr = dt * rti;                       // dt / t
             rp_max = fmax(rp_max, sel(cnt, -dtr, 0.0));
             rd_max = fmax(rd_max, sel(cnt && on, -dnu * frcp(nu), 0.0));
@@ -2651,6 +2695,7 @@ crx_solve_kernel(const crx_solve_params kp) {
         // ---- filter line search ----------------------------------------------------------------------
         double al = a_p, fn = f, lt_acc = logsum_t;
         double cbf_tr = 0.0;   // CBFC: this lane's CBF row value of the last trial, unscaled (the accept step's, when the trial is accepted)
+        double dist_tr[4] = {0.0, 0.0, 0.0, 0.0};   // DISTC: ... and the four distances (dsc, dec, dsn, den) that value was formed from, for first_order
         int acc = 0, ftype = 0;
         // switching condition al * (-Dphi)^2.3 > theta^1.1 (only consulted when theta <= theta_min)
         const bool sw_try = (theta <= theta_min) && (Dphi < 0.0);
@@ -2693,7 +2738,9 @@ crx_solve_kernel(const crx_solve_params kp) {
             if (NOBS) {
                 CBF_ROWS(j, k, ob, ev, lane, N) {   // evaluated at Z + al dZ
                     const double sc = cbf_scale<L>(sm, k, ob), t = LD(L::rt + j), dt = LD(L::rdt + j);
-                    const double cv = cbf_value<NOBS, NMAX>(sm, c, k, ob, al);
+                    double cv;
+                    if constexpr (DISTC) cv = cbf_value_dist<NOBS, NMAX>(sm, c, k, ob, al, dist_tr[0], dist_tr[1], dist_tr[2], dist_tr[3]);
+                    else cv = cbf_value<NOBS, NMAX>(sm, c, k, ob, al);
                     if constexpr (CBFC) cbf_tr = cv;
                     row_trial(j, ev, true, sc, sc * cv, t, dt);
                 }
@@ -2765,8 +2812,13 @@ crx_solve_kernel(const crx_solve_params kp) {
         auto row_accept_tail = [&](int j, bool own, bool on, double v, double tn, double rcj, double rtj, double rdj, double rnj, double rsj, double rwj) {
             const bool cnt = own && on;
             const double mut = mu * frcp(tn);
-            const double rp = rcj - rtj;                       // dnu as in the row-step pass (rc, rt, rw, rsig still hold that state)
-            const double dnu = -rwj + rsj * (rp - rdj);
+            double dnu;
+            if constexpr (DNUC) {
+                dnu = rdj;                                     // the row-step pass's own dnu, handed in where the step dt was (ACCEPT_ROW_CARRIED)
+            } else {
+                const double rp = rcj - rtj;                   // dnu as in the row-step pass (rc, rt, rw, rsig still hold that state)
+                dnu = -rwj + rsj * (rp - rdj);
+            }
             double nn = rnj + a_d * dnu;
             nn = ipm_dual_safeguard(nn, mut);
             LD(SINK(cnt, L::rt + j)) = tn;
@@ -2784,16 +2836,41 @@ crx_solve_kernel(const crx_solve_params kp) {
 #define ACCEPT_ROW_STATE(on_, tn, rcj, rtj, rdj, rnj, rsj, rwj) \
         tn = LD(L::rtt + j), rcj = LD(L::rc + j), rtj = LD(L::rt + j), rdj = LD(L::rdt + j), rnj = LD(L::rnu + j); \
         row_sig_w<L>(sm, j, on_, mu, rtj, rnj, L::SLIM ? frcp(rtj) : 0.0, rcj, rsj, rwj)
+        // (DNUC: what is left of the pre-step state -- the trial slack, the multiplier, and dnu as the row steps stored it)
+#define ACCEPT_ROW_CARRIED(tn, dnu, rnj) tn = LD(L::rtt + j), dnu = LD(L::Kk + j), rnj = LD(L::rnu + j)
 #define ACCEPT_Z(pk) LD(L::Z + RIV_IDX(pk))
 #define ACCEPT_RB row_bound<L>(sm, c, j)
 #define ACCEPT_V(pk, z, rb) (RIV_SGN(pk) * (z - rb))
         auto row_accept = [&](int j, bool own, double sc, double v) {   // own: this lane is the one that updates row j
             const bool on = ROW_ON(sc);
+            if constexpr (DNUC) {
+                const double ACCEPT_ROW_CARRIED(tn, dnu, rnj);
+                row_accept_tail(j, own, on, v, tn, 0.0, 0.0, dnu, rnj, 0.0, 0.0);
+            } else {
             double rwj, rsj;
             const double ACCEPT_ROW_STATE(on, tn, rcj, rtj, rdj, rnj, rsj, rwj);
             ROW_LOADS_DONE();
             row_accept_tail(j, own, on, v, tn, rcj, rtj, rdj, rnj, rsj, rwj);
+            }
         };
+        if constexpr ((LF & LF_ROW_ACCEPT) != 0 && DNUC) {   // [r21] the same schedule over the carried operands
+            int pk[RPASS];
+            double sc[RPASS], zv[RPASS], rb[RPASS], tn[RPASS], dnu[RPASS], rnj[RPASS];
+            ROWS(j, jv, lane, m) { (void)jv; pk[q_] = ROW_PK; }
+            __builtin_amdgcn_sched_barrier(0);
+            ROWS(j, jv, lane, m) {
+                (void)jv;
+                sc[q_] = ROW_SC; rb[q_] = ACCEPT_RB;
+                ACCEPT_ROW_CARRIED(tn[q_], dnu[q_], rnj[q_]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int q_ = 0; q_ < RPASS; q_++) zv[q_] = ACCEPT_Z(pk[q_]);
+            LOADS_DONE();
+            ROWS(j, jv, lane, m) {
+                row_accept_tail(j, jv && !ROW_IS_CBF(j, N), ROW_ON(sc[q_]), ACCEPT_V(pk[q_], zv[q_], rb[q_]), tn[q_], 0.0, 0.0, dnu[q_], rnj[q_], 0.0, 0.0);
+            }
+        } else
         if constexpr ((LF & LF_ROW_ACCEPT) != 0) {   // full layout: row_scale, row_bound and row_sig_w are loads
             int pk[RPASS];
             double sc[RPASS], zv[RPASS], rb[RPASS], tn[RPASS], rcj[RPASS], rtj[RPASS], rdj[RPASS], rnj[RPASS], rsj[RPASS], rwj[RPASS];
@@ -2835,7 +2912,8 @@ crx_solve_kernel(const crx_solve_params kp) {
         }
         nus = wave_sum(nus);
         e_p = th;
-        first_order<NOBS, NMAX, LF>(sm, si, c);
+        if constexpr (DISTC) first_order<NOBS, NMAX, LF, true>(sm, si, c, dist_tr[0], dist_tr[1], dist_tr[2], dist_tr[3]);
+        else first_order<NOBS, NMAX, LF>(sm, si, c);
         if (TRACE_ROW(it, lane) && kp.trace_rows > 0)
             kp.trace[(size_t)it * 16 + 8] = (double)(tph[0] + (CLK() - tc8));   // slot 8: KKT rows + accept/first-order
         BREAK_IF_HOPELESS(numax, th)

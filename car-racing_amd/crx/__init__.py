@@ -126,3 +126,8 @@ def mixed_prep(desc, track, xcurv, policy, car_dims=None):
 
 def plant_step(desc, track, xglob, xcurv, u, params=None):
     return binding().plant_step(desc, track, xglob, xcurv, u, params=params)
+
+
+def plant_step_tracks(desc, tracks, track_id, xglob, xcurv, u, params=None):
+    """The plant step with vehicle b on track track_id[b] of a track set (abi.track_set) on host arrays: see abi.Binding.plant_step_tracks."""
+    return binding().plant_step_tracks(desc, tracks, track_id, xglob, xcurv, u, params=params)

@@ -494,6 +494,56 @@ def plant_params(batch, dynamics_params=None):
     return _in(np.array(rows, dtype=np.float64).reshape(batch, CRX_PLANT_NPARAM), _D, (batch, CRX_PLANT_NPARAM))
 
 
+CRX_MAX_TRACKS = 8
+CRX_PLANT_MAX_SEG = 64
+
+
+class TrackSet:
+    """The track set of the plant's `tracks` entries (include/crx.h): tracks [n_tracks, seg_stride, 6] float64 (table t's rows
+    n_seg[t] .. seg_stride - 1 are zero padding, never read), n_seg [n_tracks] int32, lap_length [n_tracks] float64."""
+
+    def __init__(self, tracks, n_seg, lap_length):
+        self.tracks, self.n_seg, self.lap_length = tracks, n_seg, lap_length
+        self.n_tracks, self.seg_stride = int(tracks.shape[0]), int(tracks.shape[1])
+
+    def table(self, t):
+        """Track t's own rows [n_seg[t], 6], without the padding."""
+        return self.tracks[t, :self.n_seg[t]]
+
+
+def track_set(tables, lap_lengths, seg_stride=None):
+    """TrackSet of a list of segment tables [n_seg_t, 6] (ClosedTrack.point_and_tangent) and their lap lengths.  seg_stride: rows per table
+    in the packed array, default the longest table's.  Refuses more than CRX_MAX_TRACKS tracks, a table without rows or with more than
+    seg_stride <= 64 of them, a row that has not 6 columns, and a lap length that is not positive and finite."""
+    tables = list(tables)
+    lap = np.ascontiguousarray(lap_lengths, dtype=np.float64).reshape(-1)
+    if not 1 <= len(tables) <= CRX_MAX_TRACKS:
+        raise ValueError("track_set: %d tracks outside [1, %d]" % (len(tables), CRX_MAX_TRACKS))
+    if lap.shape[0] != len(tables):
+        raise ValueError("track_set: %d lap lengths for %d tracks" % (lap.shape[0], len(tables)))
+    rows = []
+    for t, tab in enumerate(tables):
+        try:
+            a = np.array(tab, dtype=np.float64)
+        except ValueError:
+            raise ValueError("track_set: track %d is ragged, expected rows of 6 columns" % t) from None
+        if a.ndim != 2 or a.shape[1] != 6 or a.shape[0] < 1:
+            raise ValueError("track_set: track %d has shape %s, expected [n_seg >= 1, 6]" % (t, a.shape))
+        rows.append(a)
+    stride = max(a.shape[0] for a in rows) if seg_stride is None else int(seg_stride)
+    if not 1 <= stride <= CRX_PLANT_MAX_SEG:
+        raise ValueError("track_set: seg_stride %d outside [1, %d]" % (stride, CRX_PLANT_MAX_SEG))
+    for t, a in enumerate(rows):
+        if a.shape[0] > stride:
+            raise ValueError("track_set: track %d has %d rows, more than seg_stride %d" % (t, a.shape[0], stride))
+        if not (np.isfinite(lap[t]) and lap[t] > 0.0):
+            raise ValueError("track_set: lap length of track %d must be positive and finite, got %r" % (t, float(lap[t])))
+    tracks = np.zeros((len(rows), stride, 6))
+    for t, a in enumerate(rows):
+        tracks[t, :a.shape[0]] = a
+    return TrackSet(tracks, np.array([a.shape[0] for a in rows], dtype=np.int32), lap)
+
+
 def select_desc(N, n_veh_max, lap_length, veh_length=0.4, veh_width=0.2):
     """overtake_traj_planner.py:209,223,243 literals."""
     return SelectDesc(int(N), int(n_veh_max), veh_length, veh_width, lap_length, 10.0, 100.0, 100.0)
@@ -521,7 +571,8 @@ class Binding:
         self.lib, self.prefix = lib, prefix
         for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve", "ilqr_solve",
                      "ilqr_solve_models", "lqr_design", "sysid_fit", "cbf_solve_models", "planner_solve_models", "planner_plan",
-                     "planner_plan_models", "path_prep", "path_plan", "plant_step_params", "field_prep", "field_traffic", "mixed_prep"):
+                     "planner_plan_models", "path_prep", "path_plan", "plant_step_params", "field_prep", "field_traffic", "mixed_prep",
+                     "plant_step_tracks"):
             if hasattr(lib, prefix + name):
                 getattr(lib, prefix + name).restype = C.c_int
         if hasattr(lib, prefix + "race_stats_dev"):
@@ -848,6 +899,23 @@ class Binding:
                        _p(out["xglob"]), _p(out["xcurv"]))
             return out
         self._call("plant_step", C.byref(desc), C.c_int(Bn), _p(track), _p(xglob), _p(xcurv), _p(u), _p(out["xglob"]),
+                   _p(out["xcurv"]))
+        return out
+
+    def plant_step_tracks(self, desc, tracks, track_id, xglob, xcurv, u, params=None):
+        """crx_plant_step_tracks: the zero-noise step with vehicle b on track track_id[b] of the TrackSet `tracks` (track_set); desc's
+        n_seg and lap_length are not used.  A track_id outside [0, n_tracks) is refused, as a bad params row is."""
+        xglob = np.ascontiguousarray(xglob, dtype=_D)
+        Bn = xglob.shape[0]
+        tab = _in(tracks.tracks, _D, (tracks.n_tracks, tracks.seg_stride, 6))
+        n_seg, lap = _in(tracks.n_seg, _I, (tracks.n_tracks,)), _in(tracks.lap_length, _D, (tracks.n_tracks,))
+        track_id = _in(track_id, _I, (Bn,))
+        xglob, xcurv, u = _in(xglob, _D, (Bn, 6)), _in(xcurv, _D, (Bn, 6)), _in(u, _D, (Bn, 2))
+        if params is not None:
+            params = _in(params, _D, (Bn, CRX_PLANT_NPARAM))
+        out = dict(xglob=np.zeros((Bn, 6)), xcurv=np.zeros((Bn, 6)))
+        self._call("plant_step_tracks", C.byref(desc), C.c_int(Bn), C.c_int(tracks.n_tracks), C.c_int(tracks.seg_stride), _p(tab), _p(n_seg),
+                   _p(lap), _p(track_id), _p(xglob), _p(xcurv), _p(u), None if params is None else _p(params), _p(out["xglob"]),
                    _p(out["xcurv"]))
         return out
 

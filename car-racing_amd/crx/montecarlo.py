@@ -206,7 +206,7 @@ class _Plant:
     process noise, and plant_params: one parameter set per car [B,10], or None.  _advance() is the one place a loop steps its plant.  The contract bench.py times the solver launches by:
     after a step, xc_next is the state that step's solver launch was built for."""
 
-    def _plant_init(self, track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params=None):
+    def _plant_init(self, track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params=None, tracks=None, track_id=None):
         dev = torch.device(device if device is not None else "cuda")
         self.device, self.lap_length, self.timestep = dev, lap_length, timestep
         self.noise = _Noise(noise_seed, dev)
@@ -214,8 +214,24 @@ class _Plant:
         self.xc_next, self.xg_next = torch.empty_like(self.xc), torch.empty_like(self.xg)
         self.batch = self.xc.shape[0]
         self.laps = torch.zeros(self.batch, dtype=torch.int32, device=dev)
-        self.tab = _dev(track_table, dev)
-        self.plant = abi.plant_desc(self.tab.shape[0], lap_length, timestep=timestep)
+        # tracks (abi.track_set) and track_id [B], host array or device tensor: car b on track track_id[b] (crx_plant_step_tracks_dev);
+        # track_table and lap_length are then unused (None), self.lap_length is the per-car tensor lap_length[track_id] and the plant
+        # descriptor carries track 0's row count and lap length only to be a valid one.  None: the one track_table for all cars
+        self.tracks = None
+        if (tracks is None) != (track_id is None):
+            raise ValueError("tracks and track_id go together: a track set and every car's track, or neither")
+        if tracks is not None:
+            if track_table is not None or lap_length is not None:
+                raise ValueError("with tracks= the loop has no track_table / lap_length of its own: pass None for both")
+            self.tracks = torch_api.TrackSetDev(tracks, track_id, dev)
+            if tuple(self.tracks.track_id.shape) != (self.batch,):
+                raise ValueError("track_id: expected shape %s, got %s" % ((self.batch,), tuple(self.tracks.track_id.shape)))
+            self.lap_length = self.tracks.car_lap
+            self.tab = self.tracks.tracks
+            self.plant = abi.plant_desc(int(tracks.n_seg[0]), float(tracks.lap_length[0]), timestep=timestep)
+        else:
+            self.tab = _dev(track_table, dev)
+            self.plant = abi.plant_desc(self.tab.shape[0], lap_length, timestep=timestep)
         # plant_params [B,10] (abi.plant_params, synth.fleet_plant_params), host array or device tensor: every car its own BicycleDynamicsParam
         # set (crx_plant_step_params_dev).  None: the one set of self.plant for all of them
         self.plant_params = None
@@ -232,8 +248,12 @@ class _Plant:
         leaves alone."""
         if noise_z is None:
             noise_z = self.noise.draw(self.batch)
-        torch_api.plant_step_wrap_dev(self.plant, self.tab, self.xg, self.xc, u, u_stride, self.xg_next, self.xc_next, self.laps,
-                                      noise_z=noise_z, params=self.plant_params)
+        if self.tracks is not None:
+            torch_api.plant_step_tracks_wrap_dev(self.plant, self.tracks, self.xg, self.xc, u, u_stride, self.xg_next, self.xc_next, self.laps,
+                                                 noise_z=noise_z, params=self.plant_params)
+        else:
+            torch_api.plant_step_wrap_dev(self.plant, self.tab, self.xg, self.xc, u, u_stride, self.xg_next, self.xc_next, self.laps,
+                                          noise_z=noise_z, params=self.plant_params)
         self.xg, self.xg_next = self.xg_next, self.xg
         self.xc, self.xc_next = self.xc_next, self.xc
 
@@ -245,6 +265,13 @@ class _Plant:
                    track_width=getattr(self, "track_width", None), xt=getattr(self, "xt", None))
         inp.update(more)
         return inp
+
+
+def _one_track_only(loop, tracks, track_id):
+    """The loops whose other launches take ONE track table or ONE lap length (a prep descriptor, a safe set, a scene) refuse a track set."""
+    if tracks is not None or track_id is not None:
+        raise ValueError("%s runs on one track: tracks= / track_id= (one track per car) are taken by PidLaps, LqrLaps and MpccbfRaces only -- "
+                         "its other launches read one track table or one lap length" % loop)
 
 
 def _run_and_log(step, steps, log_every, getters, before=()):
@@ -270,8 +297,9 @@ class MpccbfRaces(_Plant):
     """State of B races on the device; step() advances all of them by one control step."""
 
     def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, car_s0, car_v, car_ey,
-                 vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1, device=None, noise_seed=None, models=None, plant_params=None):
-        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params)
+                 vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1, device=None, noise_seed=None, models=None, plant_params=None, tracks=None,
+                 track_id=None):
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params, tracks, track_id)
         f64 = dict(dtype=torch.float64, device=dev)
         self.s0, self.v, self.ey = (_dev(a, dev) for a in (car_s0, car_v, car_ey))
         Bn, V = self.s0.shape
@@ -295,10 +323,11 @@ class MpccbfRaces(_Plant):
 
     def step(self):
         """One control step of every race, three libcrx launches and nothing else: cbf_prep_dev, cbf_solve_dev,
-        plant_step_wrap_dev (dispatch = "longest_first": one longest_first ahead of the solver launch)."""
+        plant_step_wrap_dev (dispatch = "longest_first": one longest_first ahead of the solver launch).  On a track set: cbf_prep_laps_dev
+        (every race folded by its own lap length), cbf_solve_dev, plant_step_tracks_wrap_dev."""
         N = self.N
-        torch_api.cbf_prep_dev(N, self.lap_length, self.t, self.timestep, self.xc, self.s0, self.v, self.ey,
-                               self.obs_s, self.obs_e, self.lap_off, self.n_obs)
+        prep = torch_api.cbf_prep_dev if self.tracks is None else torch_api.cbf_prep_laps_dev
+        prep(N, self.lap_length, self.t, self.timestep, self.xc, self.s0, self.v, self.ey, self.obs_s, self.obs_e, self.lap_off, self.n_obs)
         torch_api.cbf_solve_dev(self.desc, self.xc, self.xt, self.obs_s, self.obs_e, self.lap_off, self.n_obs, ws=self.ws,
                                 order=_order(self, self.ws.iters), models=self.models)
         self._advance(self.ws.U, 2 * N)   # the plant reads u_0 of every race straight out of the solver's U [B][N][2]
@@ -311,7 +340,8 @@ class MpccbfRaces(_Plant):
     def step_glue(self):
         """The same control step with the prediction / window filter / packing / lap wrap written as element-wise
         torch ops (the first version; kept as an independent restatement for the tests)."""
-        N, L, xc = self.N, self.lap_length, self.xc
+        N, xc = self.N, self.xc
+        L = self.lap_length if self.tracks is None else self.lap_length[:, None]     # a track set: every race's own, [B,1]
         tt = self.t + self.jdt                                                       # [N+1]
         obs_s = self.v[:, :, None] * tt[None, None, :] + self.s0[:, :, None]         # [B,V,N+1]
         obs_e = self.ey[:, :, None] + 0.0 * tt[None, None, :]
@@ -331,21 +361,26 @@ class MpccbfRaces(_Plant):
         torch_api.cbf_solve_dev(self.desc, xc, self.xt, ps.contiguous(), pe.contiguous(), po.contiguous(), n_obs.contiguous(),
                                 ws=self.ws, models=self.models)
         self.u = self.ws.U[:, 0, :].contiguous()
-        self.xg, xc = torch_api.plant_step_dev(self.plant, self.tab, self.xg, xc, self.u, params=self.plant_params)
-        crossed = xc[:, 4] > L
-        xc[:, 4] = torch.where(crossed, xc[:, 4] - L, xc[:, 4])
+        if self.tracks is None:
+            self.xg, xc = torch_api.plant_step_dev(self.plant, self.tab, self.xg, xc, self.u, params=self.plant_params)
+        else:
+            self.xg, xc = torch_api.plant_step_tracks_dev(self.plant, self.tracks, self.xg, xc, self.u, params=self.plant_params)
+        crossed = xc[:, 4] > self.lap_length
+        xc[:, 4] = torch.where(crossed, xc[:, 4] - self.lap_length, xc[:, 4])
         self.laps += crossed.to(torch.int32)
         self.xc = xc
         self.t += self.timestep
 
 
 def mpccbf_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, steps,
-                 vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1, device=None, log_every=1, glue=False, models=None, plant_params=None):
+                 vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1, device=None, log_every=1, glue=False, models=None, plant_params=None,
+                 tracks=None, track_id=None):
     """xcurv0, xglob0 [B,6]; car_s0, car_v, car_ey [B,V] with V <= 3: scripted cars s(t) = v t + s0, ey(t) = ey
     (NoDynamicsModel, utils/base.py:847-890); models = (A [B,6,6], B [B,6,2]): one controller model per race; plant_params [B,10]: one car per race.  Returns host arrays: xcurv [T+1,B,6] (T = steps/log_every), u [T,B,2],
-    status [T,B], laps [B]."""
+    status [T,B], laps [B].  tracks (abi.track_set), track_id [B]: race b on its own track (track_table and lap_length None)."""
     r = MpccbfRaces(track_table, lap_length, track_width, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, vt=vt, eyt=eyt,
-                    N=N, alpha=alpha, timestep=timestep, device=device, models=models, plant_params=plant_params)
+                    N=N, alpha=alpha, timestep=timestep, device=device, models=models, plant_params=plant_params, tracks=tracks,
+                    track_id=track_id)
     logs = _run_and_log(r.step_glue if glue else r.step, steps, log_every,
                         dict(xcurv=lambda: r.xc, u=lambda: r.u, status=lambda: r.ws.status))
     return dict(logs, laps=r.laps.cpu().numpy())
@@ -393,7 +428,8 @@ class FieldRaces(_Field):
     the states at the start of the step (include/crx.h, crx_field_prep_dev, quirks F1-F7).  min_clear [R*C]: see _Field."""
 
     def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, n_cars, vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1,
-                 device=None, noise_seed=None, models=None, plant_params=None, car_dims=None):
+                 device=None, noise_seed=None, models=None, plant_params=None, car_dims=None, tracks=None, track_id=None):
+        _one_track_only("FieldRaces", tracks, track_id)
         dev = self._field_init(track_table, lap_length, track_width, timestep, xcurv0, xglob0, n_cars, vt, eyt, N, car_dims, noise_seed,
                                device, plant_params)
         Bn, R, Cn = self.batch, self.n_races, self.n_cars
@@ -439,7 +475,9 @@ class MixedRaces(_Field):
     and lqr, CRX_SKIPPED for none.  min_clear [R*C] as in FieldRaces."""
 
     def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, policy, vt=0.8, eyt=0.0, N=10, ilqr_N=50, ilqr_max_iter=150,
-                 ilqr_obstacles=0, alpha=0.8, timestep=0.1, device=None, noise_seed=None, models=None, plant_params=None, car_dims=None):
+                 ilqr_obstacles=0, alpha=0.8, timestep=0.1, device=None, noise_seed=None, models=None, plant_params=None, car_dims=None,
+                 tracks=None, track_id=None):
+        _one_track_only("MixedRaces", tracks, track_id)
         pol = abi.policy_codes(policy)
         if pol.ndim != 2 or not 1 <= pol.shape[1] <= abi.CRX_MAX_OBS + 1:
             raise ValueError("policy: [R,C] with 1 .. %d cars per race" % (abi.CRX_MAX_OBS + 1))
@@ -514,7 +552,8 @@ class IlqrRaces(_Plant):
 
     def __init__(self, track_table, lap_length, A, B, xcurv0, xglob0, car_s0, car_v, car_ey, vt=0.8, eyt=0.0, N=50,
                  max_iter=150, timestep=0.1, ego_dims=(0.4, 0.2), car_dims=(0.4, 0.2), device=None, noise_seed=None, models=None,
-                 plant_params=None):
+                 plant_params=None, tracks=None, track_id=None):
+        _one_track_only("IlqrRaces", tracks, track_id)
         dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params)
         f64 = dict(dtype=torch.float64, device=dev)
         self.s0, self.v, self.ey = (_dev(np.asarray(a, dtype=float).reshape(-1, 1), dev) for a in (car_s0, car_v, car_ey))
@@ -584,7 +623,8 @@ class LmpcLaps(_Plant):
     of safe-set storage are full (it then keeps racing on its last two laps)."""
 
     def __init__(self, track_table, lap_length, track_width, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0, lin_points, lin_input,
-                 N=12, timestep=0.1, device=None, noise_seed=None, plant_params=None):
+                 N=12, timestep=0.1, device=None, noise_seed=None, plant_params=None, tracks=None, track_id=None):
+        _one_track_only("LmpcLaps", tracks, track_id)
         dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params)
         f64 = dict(dtype=torch.float64, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
@@ -725,7 +765,8 @@ class GameLaps:
 
     def __init__(self, track_table, lap_length, track_width, A, B, opt_xcurv, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0,
                  lin_points, lin_input, car_s0, car_v, car_ey, N=12, N_plan=10, timestep=0.1, device=None, noise_seed=None, models=None,
-                 planner="traj", alpha=0.98, plant_params=None):
+                 planner="traj", alpha=0.98, plant_params=None, tracks=None, track_id=None):
+        _one_track_only(type(self).__name__, tracks, track_id)
         if planner not in ("traj", "path"):
             raise ValueError("planner must be 'traj' or 'path', got %r" % (planner,))
         self.planner = planner
@@ -928,7 +969,9 @@ class FieldGames(GameLaps):
 
     def __init__(self, track_table, lap_length, track_width, A, B, opt_xcurv, n_cars, ss_xcurv, u_ss, qfun, time_ss, it, xcurv0, xglob0,
                  lin_points, lin_input, step_no=None, n_log=None, log_x=None, log_u=None, u_old=None, u_prev=None, N=12, N_plan=10,
-                 timestep=0.1, device=None, noise_seed=None, models=None, planner="traj", alpha=0.98, plant_params=None):
+                 timestep=0.1, device=None, noise_seed=None, models=None, planner="traj", alpha=0.98, plant_params=None, tracks=None,
+                 track_id=None):
+        _one_track_only("FieldGames", tracks, track_id)
         Cn = int(n_cars)
         if not 1 <= Cn <= abi.CRX_MAX_VEH + 1:
             raise ValueError("1 .. %d cars per race" % (abi.CRX_MAX_VEH + 1))
@@ -1056,8 +1099,8 @@ class PidLaps(_Plant):
     returns the models of B different cars."""
 
     def __init__(self, track_table, lap_length, xcurv0, xglob0, steps, vt=0.5, eyt=0.0, timestep=0.1, noise_z=None,
-                 noise_seed=None, device=None, plant_params=None):
-        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params)
+                 noise_seed=None, device=None, plant_params=None, tracks=None, track_id=None):
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params, tracks, track_id)
         f64 = dict(dtype=torch.float64, device=dev)
         Bn, T = self.batch, int(steps)
         self.steps = T
@@ -1096,10 +1139,11 @@ class PidLaps(_Plant):
 
 
 def pid_laps(track_table, lap_length, xcurv0, xglob0, steps, vt=0.5, eyt=0.0, timestep=0.1, noise_z=None, noise_seed=None,
-             device=None, plant_params=None):
-    """PidLaps run to the end: the logs stay on the device (r.x_log, r.u_log); r.identify(lamb) fits them."""
+             device=None, plant_params=None, tracks=None, track_id=None):
+    """PidLaps run to the end: the logs stay on the device (r.x_log, r.u_log); r.identify(lamb) fits them.  tracks (abi.track_set),
+    track_id [B]: car b on its own track (track_table and lap_length None)."""
     return PidLaps(track_table, lap_length, xcurv0, xglob0, steps, vt=vt, eyt=eyt, timestep=timestep, noise_z=noise_z,
-                   noise_seed=noise_seed, device=device, plant_params=plant_params).run()
+                   noise_seed=noise_seed, device=device, plant_params=plant_params, tracks=tracks, track_id=track_id).run()
 
 
 class SeedLaps(_Plant):
@@ -1123,7 +1167,8 @@ class SeedLaps(_Plant):
     MPC-LTI lap applied an iterate that had not converged, abi.CRX_SEED_LOG_FULL = a lap did not reach the line within n_points - 1 steps."""
 
     def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, vt=0.7, eyt=0.0, N=10, n_points=600, n_laps=4, timestep=0.1,
-                 device=None, noise_seed=None, models=None, plant_params=None):
+                 device=None, noise_seed=None, models=None, plant_params=None, tracks=None, track_id=None):
+        _one_track_only("SeedLaps", tracks, track_id)
         dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params)
         f64 = dict(dtype=torch.float64, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
@@ -1210,8 +1255,9 @@ class LqrLaps(_Plant):
     and drives NaN inputs: `design.status` says which."""
 
     def __init__(self, track_table, lap_length, xcurv0, xglob0, A, B, Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]), R=np.diag([0.1, 0.1]),
-                 vt=0.8, eyt=0.0, max_iter=50, eps=0.01, timestep=0.1, device=None, noise_seed=None, plant_params=None):
-        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params)
+                 vt=0.8, eyt=0.0, max_iter=50, eps=0.01, timestep=0.1, device=None, noise_seed=None, plant_params=None, tracks=None,
+                 track_id=None):
+        dev = self._plant_init(track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params, tracks, track_id)
         f64 = dict(dtype=torch.float64, device=dev)
         Bn = self.batch
         self.A, self.B = _models(A, B, Bn, dev)
@@ -1229,11 +1275,12 @@ class LqrLaps(_Plant):
 
 
 def lqr_laps(track_table, lap_length, xcurv0, xglob0, steps, A, B, Q=np.diag([10.0, 0.0, 0.0, 4.0, 0.0, 40.0]), R=np.diag([0.1, 0.1]),
-             vt=0.8, eyt=0.0, max_iter=50, eps=0.01, timestep=0.1, device=None, noise_seed=None, log_every=1, plant_params=None):
+             vt=0.8, eyt=0.0, max_iter=50, eps=0.01, timestep=0.1, device=None, noise_seed=None, log_every=1, plant_params=None, tracks=None,
+             track_id=None):
     """xcurv0, xglob0 [B,6]; A, B as in LqrLaps; plant_params [B,10]: one car per row.  Returns host arrays: xcurv [T+1,B,6] (T = steps / log_every), u [T,B,2], K [B,2,6],
     design_status [B], design_iters [B], laps [B]."""
     r = LqrLaps(track_table, lap_length, xcurv0, xglob0, A, B, Q=Q, R=R, vt=vt, eyt=eyt, max_iter=max_iter, eps=eps, timestep=timestep,
-                device=device, noise_seed=noise_seed, plant_params=plant_params)
+                device=device, noise_seed=noise_seed, plant_params=plant_params, tracks=tracks, track_id=track_id)
     logs = _run_and_log(r.step, steps, log_every, dict(xcurv=lambda: r.xc, u=lambda: r.u))
     return dict(logs, K=r.K.cpu().numpy(),
                 design_status=r.design.status.cpu().numpy(), design_iters=r.design.iters.cpu().numpy(), laps=r.laps.cpu().numpy())
@@ -1259,6 +1306,8 @@ class RaceStats:
 
     def __init__(self, loop, group=None, n_groups=1, track_width=None, first_sample=0):
         self.loop = loop
+        if getattr(getattr(loop, "lm", loop), "tracks", None) is not None:
+            raise ValueError("RaceStats takes one lap length (crx_stats_desc): a loop on a track set (tracks=, one track per car) has one per car")
         inp = loop.stats_inputs()
         xc = inp["xcurv"]
         Bn, dev = xc.shape[0], xc.device

@@ -241,3 +241,15 @@ def fleet_plant_params(batch, spread, seed):
 
     rng = np.random.Generator(np.random.PCG64(seed))
     return abi.plant_params(batch) * (1.0 + spread * rng.uniform(-1.0, 1.0, (batch, abi.CRX_PLANT_NPARAM)))
+
+
+def fleet_tracks(batch, n_tracks, seed):
+    """Every car's track for the `track_id` argument of the closed loops (crx.montecarlo): [batch] int32 in [0, n_tracks), drawn uniformly,
+    with every track occurring (the first n_tracks draws are replaced by a permutation of the tracks; batch >= n_tracks).  Sort it for a
+    batch in which the cars of a track are neighbours."""
+    if batch < n_tracks:
+        raise ValueError("fleet_tracks: %d cars cannot cover %d tracks" % (batch, n_tracks))
+    rng = np.random.Generator(np.random.PCG64(seed))
+    ids = rng.integers(0, n_tracks, batch).astype(np.int32)
+    ids[rng.permutation(batch)[:n_tracks]] = rng.permutation(n_tracks).astype(np.int32)
+    return ids

@@ -779,6 +779,88 @@ def plant_step_wrap_dev(desc, track, xglob, xcurv, u, u_stride, xglob_next, xcur
           C.c_int(u_stride), _ptr(noise_z), _ptr(xglob_next), _ptr(xcurv_next), _ptr(laps), _stream())
 
 
+class TrackSetDev:
+    """A track set (abi.track_set) on a device, with every car's track: what the plant's `tracks` wrappers take.  track_id [B] int32,
+    host array or tensor.  car_lap [B]: lap_length[track_id], the cars' own lap lengths.  Ids are checked here, once, on the host side of
+    whatever they came from; the kernel gives a car whose id is out of range non-finite states."""
+
+    def __init__(self, tracks, track_id, device):
+        dev = torch.device(device)
+        self.host = tracks
+        self.n_tracks, self.seg_stride = tracks.n_tracks, tracks.seg_stride
+        self.tracks = torch.as_tensor(tracks.tracks, dtype=torch.float64).to(dev).contiguous()
+        self.n_seg = torch.as_tensor(tracks.n_seg, dtype=torch.int32).to(dev).contiguous()
+        self.lap_length = torch.as_tensor(tracks.lap_length, dtype=torch.float64).to(dev).contiguous()
+        tid = track_id if torch.is_tensor(track_id) else torch.as_tensor(track_id)
+        if tid.dim() != 1 or tid.dtype.is_floating_point:
+            raise ValueError("track_id: expected an integer [B] array, got %s %s" % (tid.dtype, tuple(tid.shape)))
+        if tid.numel() and (int(tid.min()) < 0 or int(tid.max()) >= self.n_tracks):
+            raise ValueError("track_id: values outside [0, %d)" % self.n_tracks)
+        self.track_id = tid.to(dtype=torch.int32, device=dev).contiguous()
+        self.car_lap = self.lap_length[self.track_id.long()].contiguous()
+
+
+def _chk_track_set(ts, Bn):
+    _chk(ts.tracks, torch.float64, (ts.n_tracks, ts.seg_stride, 6), "tracks")
+    _chk(ts.n_seg, torch.int32, (ts.n_tracks,), "n_seg")
+    _chk(ts.lap_length, torch.float64, (ts.n_tracks,), "lap_length")
+    _chk(ts.track_id, torch.int32, (Bn,), "track_id")
+    return C.c_int(ts.n_tracks), C.c_int(ts.seg_stride), _ptr(ts.tracks), _ptr(ts.n_seg), _ptr(ts.lap_length), _ptr(ts.track_id)
+
+
+def plant_step_tracks_dev(desc, tracks, xglob, xcurv, u, xglob_next=None, xcurv_next=None, params=None):
+    """crx_plant_step_tracks_plain_dev: plant_step_dev with vehicle b on track tracks.track_id[b] of the TrackSetDev `tracks`; returns
+    (xglob_next, xcurv_next) (allocated unless given)."""
+    Bn = xglob.shape[0]
+    set_args = _chk_track_set(tracks, Bn)
+    _chk(xglob, torch.float64, (Bn, 6), "xglob")
+    _chk(xcurv, torch.float64, (Bn, 6), "xcurv")
+    _chk(u, torch.float64, (Bn, 2), "u")
+    if params is not None:
+        _chk(params, torch.float64, (Bn, 10), "params")
+    xglob_next = xglob_next if xglob_next is not None else torch.empty_like(xglob)
+    xcurv_next = xcurv_next if xcurv_next is not None else torch.empty_like(xcurv)
+    _call("crx_plant_step_tracks_plain_dev", C.byref(desc), C.c_int(Bn), *set_args, _ptr(xglob), _ptr(xcurv), _ptr(u), _ptr(params),
+          _ptr(xglob_next), _ptr(xcurv_next), _stream())
+    return xglob_next, xcurv_next
+
+
+def plant_step_tracks_wrap_dev(desc, tracks, xglob, xcurv, u, u_stride, xglob_next, xcurv_next, laps, noise_z=None, params=None):
+    """crx_plant_step_tracks_dev: plant_step_wrap_dev with vehicle b on track tracks.track_id[b] of the TrackSetDev `tracks`, its lap
+    bookkeeping with that track's lap length.  laps None: no lap counters."""
+    Bn = xglob.shape[0]
+    set_args = _chk_track_set(tracks, Bn)
+    _chk(xglob, torch.float64, (Bn, 6), "xglob")
+    _chk(xcurv, torch.float64, (Bn, 6), "xcurv")
+    _chk(xglob_next, torch.float64, (Bn, 6), "xglob_next")
+    _chk(xcurv_next, torch.float64, (Bn, 6), "xcurv_next")
+    if laps is not None:
+        _chk(laps, torch.int32, (Bn,), "laps")
+    if not u.is_cuda or u.dtype != torch.float64 or not u.is_contiguous() or u.numel() < (Bn - 1) * u_stride + 2:
+        raise ValueError("u: expected a contiguous cuda float64 tensor holding %d inputs at stride %d" % (Bn, u_stride))
+    if noise_z is not None:
+        _chk(noise_z, torch.float64, (Bn, 3), "noise_z")
+    if params is not None:
+        _chk(params, torch.float64, (Bn, 10), "params")
+    _call("crx_plant_step_tracks_dev", C.byref(desc), C.c_int(Bn), *set_args, _ptr(xglob), _ptr(xcurv), _ptr(u), C.c_int(u_stride),
+          _ptr(noise_z), _ptr(params), _ptr(xglob_next), _ptr(xcurv_next), _ptr(laps), _stream())
+
+
+def cbf_prep_laps_dev(N, lap_length, t, dt, xcurv, car_s0, car_v, car_ey, obs_s, obs_ey, lap_off, n_obs, safety_time=2.0):
+    """crx_cbf_prep_laps_dev: cbf_prep_dev with race b folded and offset by lap_length[b] ([B] float64 on the device)."""
+    Bn, V = car_s0.shape
+    _chk(lap_length, torch.float64, (Bn,), "lap_length")
+    _chk(xcurv, torch.float64, (Bn, 6), "xcurv")
+    for name, a in (("car_s0", car_s0), ("car_v", car_v), ("car_ey", car_ey), ("lap_off", lap_off)):
+        _chk(a, torch.float64, (Bn, V), name)
+    _chk(obs_s, torch.float64, (Bn, V, N + 1), "obs_s")
+    _chk(obs_ey, torch.float64, (Bn, V, N + 1), "obs_ey")
+    _chk(n_obs, torch.int32, (Bn,), "n_obs")
+    _call("crx_cbf_prep_laps_dev", C.c_int(N), C.c_int(V), _ptr(lap_length), C.c_double(t), C.c_double(dt),
+          C.c_double(safety_time), C.c_int(Bn), _ptr(xcurv), _ptr(car_s0), _ptr(car_v), _ptr(car_ey), _ptr(obs_s),
+          _ptr(obs_ey), _ptr(lap_off), _ptr(n_obs), _stream())
+
+
 class LmpcPrepWorkspace:
     """Outputs of lmpc_prep_dev = the model and safe-set inputs of lmpc_solve_dev (same layout)."""
 

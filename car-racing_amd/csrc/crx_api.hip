@@ -1034,6 +1034,66 @@ int crx_plant_step_params_plain_dev(const crx_plant_desc* d, int batch, const do
     return plant_launch(d, batch, 0, track, xglob, xcurv, u, 2, nullptr, params, xglob_next, xcurv_next, nullptr, stream);
 }
 
+// ---- one track per car: a track set behind the plant (crx_plant_tracks_kernel), one lap length per race behind the MPC-CBF prep ----
+// host_*: the arrays of the host-pointer entry (NULL: on the device, where they cannot be read)
+static int check_track_set(int batch, int n_tracks, int seg_stride, arr n_seg, arr lap_length, arr track_id, const int32_t* host_n_seg = nullptr,
+                           const double* host_lap = nullptr, const int32_t* host_id = nullptr) {
+    if (n_tracks < 1 || n_tracks > CRX_MAX_TRACKS) return fail(CRX_ERR_ARG, "n_tracks=%d outside [1,%d]", n_tracks, CRX_MAX_TRACKS);
+    if (seg_stride < 1 || seg_stride > CRX_PLANT_MAX_SEG) return fail(CRX_ERR_ARG, "seg_stride=%d outside [1,%d]", seg_stride, CRX_PLANT_MAX_SEG);
+    if (batch > 0 && any_null(n_seg, lap_length, track_id)) return fail(CRX_ERR_ARG, "NULL array argument");
+    for (int t = 0; host_n_seg && t < n_tracks; t++)
+        if (host_n_seg[t] < 1 || host_n_seg[t] > seg_stride) return fail(CRX_ERR_ARG, "n_seg of track %d: %d outside [1,%d]", t, host_n_seg[t], seg_stride);
+    for (int t = 0; host_lap && t < n_tracks; t++)
+        if (!(host_lap[t] > 0.0) || !isfinite(host_lap[t])) return fail(CRX_ERR_ARG, "lap_length of track %d must be positive and finite", t);
+    for (int b = 0; host_id && b < batch; b++)
+        if (host_id[b] < 0 || host_id[b] >= n_tracks) return fail(CRX_ERR_ARG, "track_id of car %d: %d outside [0,%d)", b, host_id[b], n_tracks);
+    return 0;
+}
+
+static int plant_tracks_launch(const crx_plant_desc* d, int batch, int wrap, int n_tracks, int seg_stride, const double* tracks, const int32_t* n_seg,
+                               const double* lap_length, const int32_t* track_id, const double* xglob, const double* xcurv, const double* u,
+                               int u_stride, const double* noise_z, const double* params, double* xglob_next, double* xcurv_next, int32_t* laps,
+                               void* stream) {
+    if (int rc = check_plant(d, batch, u_stride, tracks, xglob, xcurv, u, xglob_next, xcurv_next)) return rc;
+    if (int rc = check_track_set(batch, n_tracks, seg_stride, n_seg, lap_length, track_id)) return rc;
+    if (batch == 0) return CRX_OK;
+    crx_plant_kparams_tracks pk;
+    pk.d = *d; pk.batch = batch; pk.u_stride = u_stride; pk.wrap = wrap; pk.track = tracks; pk.xglob = xglob; pk.xcurv = xcurv; pk.u = u;
+    pk.xglob_next = xglob_next; pk.xcurv_next = xcurv_next; pk.laps = laps; pk.noise_z = noise_z; pk.params = params;
+    pk.n_tracks = n_tracks; pk.seg_stride = seg_stride; pk.n_seg = n_seg; pk.track_id = track_id; pk.lap_length = lap_length;
+    return launched(crx_launch_plant_tracks(pk, (hipStream_t)stream), "plant (track set)");
+}
+
+int crx_plant_step_tracks_dev(const crx_plant_desc* d, int batch, int n_tracks, int seg_stride, const double* tracks, const int32_t* n_seg,
+                              const double* lap_length, const int32_t* track_id, const double* xglob, const double* xcurv, const double* u,
+                              int u_stride, const double* noise_z, const double* params, double* xglob_next, double* xcurv_next,
+                              int32_t* laps, void* stream) {
+    return plant_tracks_launch(d, batch, 1, n_tracks, seg_stride, tracks, n_seg, lap_length, track_id, xglob, xcurv, u, u_stride, noise_z, params,
+                               xglob_next, xcurv_next, laps, stream);
+}
+
+int crx_plant_step_tracks_plain_dev(const crx_plant_desc* d, int batch, int n_tracks, int seg_stride, const double* tracks,
+                                    const int32_t* n_seg, const double* lap_length, const int32_t* track_id, const double* xglob,
+                                    const double* xcurv, const double* u, const double* params, double* xglob_next, double* xcurv_next,
+                                    void* stream) {
+    return plant_tracks_launch(d, batch, 0, n_tracks, seg_stride, tracks, n_seg, lap_length, track_id, xglob, xcurv, u, 2, nullptr, params,
+                               xglob_next, xcurv_next, nullptr, stream);
+}
+
+int crx_cbf_prep_laps_dev(int N, int V, const double* lap_length, double t, double dt, double safety_time, int batch,
+                          const double* xcurv, const double* car_s0, const double* car_v, const double* car_ey,
+                          double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, void* stream) {
+    if (int rc = ensure_init()) return rc;
+    if (N < 1 || N > CRX_MAX_N || V < 1 || V > CRX_MAX_OBS || batch < 0) return fail(CRX_ERR_ARG, "bad cbf prep dimensions");
+    if (batch == 0) return CRX_OK;
+    if (!lap_length || !xcurv || !car_s0 || !car_v || !car_ey || !obs_s || !obs_ey || !lap_off || !n_obs) return fail(CRX_ERR_ARG, "NULL array argument");
+    crx_cbfprep_kparams_laps cp;
+    cp.N = N; cp.V = V; cp.batch = batch; cp.lap_length = 0.0; cp.lap_lengths = lap_length; cp.t = t; cp.dt = dt; cp.safety_time = safety_time;
+    cp.xcurv = xcurv; cp.car_s0 = car_s0; cp.car_v = car_v; cp.car_ey = car_ey;
+    cp.obs_s = obs_s; cp.obs_ey = obs_ey; cp.lap_off = lap_off; cp.n_obs = n_obs;
+    return launched(crx_launch_cbfprep_laps(cp, (hipStream_t)stream), "cbf prep (per-race lap lengths)");
+}
+
 int crx_cbf_prep_dev(int N, int V, double lap_length, double t, double dt, double safety_time, int batch,
                      const double* xcurv, const double* car_s0, const double* car_v, const double* car_ey,
                      double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, void* stream) {
@@ -1288,6 +1348,28 @@ int crx_plant_step_params(const crx_plant_desc* d, int batch, const double* trac
     auto dgn = sg.out(xglob_next, B * 6); auto dcn = sg.out(xcurv_next, B * 6);
     if (int rc = sg.up(g_stream)) return rc;
     if (int rc = crx_plant_step_params_plain_dev(d, batch, sg[dtr], sg[dg], sg[dc], sg[du], sg[dpr], sg[dgn], sg[dcn], g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
+int crx_plant_step_tracks(const crx_plant_desc* d, int batch, int n_tracks, int seg_stride, const double* tracks, const int32_t* n_seg,
+                          const double* lap_length, const int32_t* track_id, const double* xglob, const double* xcurv, const double* u,
+                          const double* params, double* xglob_next, double* xcurv_next) {
+    if (n_tracks >= 1 && n_tracks <= CRX_MAX_TRACKS && !n_seg) return fail(CRX_ERR_ARG, "NULL array argument");   // the set's own arrays are read at any batch
+    if (n_tracks >= 1 && n_tracks <= CRX_MAX_TRACKS && !lap_length) return fail(CRX_ERR_ARG, "NULL array argument");
+    if (int rc = check_track_set(batch, n_tracks, seg_stride, n_seg, lap_length, track_id, n_seg, lap_length, batch > 0 ? track_id : nullptr)) return rc;
+    if (int rc = check_plant(d, batch, 2, tracks, xglob, xcurv, u, xglob_next, xcurv_next, params)) return rc;
+    if (batch == 0) return CRX_OK;
+    const size_t B = (size_t)batch;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    Stage sg;
+    auto dtr = sg.in(tracks, (size_t)n_tracks * seg_stride * 6); auto dns = sg.in(n_seg, (size_t)n_tracks); auto dll = sg.in(lap_length, (size_t)n_tracks);
+    auto dti = sg.in(track_id, B); auto dg = sg.in(xglob, B * 6); auto dc = sg.in(xcurv, B * 6); auto du = sg.in(u, B * 2);
+    auto dpr = params ? sg.in(params, B * CRX_PLANT_NPARAM) : Stage::Ref<double>{};   // unused: sg[dpr] is NULL
+    auto dgn = sg.out(xglob_next, B * 6); auto dcn = sg.out(xcurv_next, B * 6);
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_plant_step_tracks_plain_dev(d, batch, n_tracks, seg_stride, sg[dtr], sg[dns], sg[dll], sg[dti], sg[dg], sg[dc], sg[du], sg[dpr],
+                                                 sg[dgn], sg[dcn], g_stream)) return rc;
     return sg.down(g_stream);
 }
 

@@ -117,6 +117,11 @@ struct crx_cbfprep_kparams {
     int32_t* n_obs;
 };
 
+// crx_cbfprep_laps_kernel.  Derived, so that crx_cbfprep_kparams -- which crx_cbfprep_kernel takes by value -- keeps its size.
+struct crx_cbfprep_kparams_laps : crx_cbfprep_kparams {
+    const double* lap_lengths;   // [batch]: race b's own lap length; lap_length of the base is unused
+};
+
 // The NLP family's obstacle arrays of the n_races * n_cars egos of a field, in crx_cbf_solve_dev's layout (nlp_ego_pass, crx_prep.hip)
 struct crx_nlp_obs {
     double *obs_s, *obs_ey, *lap_off;         // [n_races * n_cars][n_cars - 1][N + 1] twice, [..][n_cars - 1]
@@ -188,7 +193,7 @@ struct crx_pathplan_kparams {
     double* target;
 };
 
-// ---- crx_plant.hip: the two inclusions of crx_plant_step.h ----
+// ---- crx_plant.hip: the four inclusions of crx_plant_step.h ----
 #define CRX_PLANT_MAX_SEG 64   // rows of a track's segment table a kernel keeps in LDS (the plant, crx_field_prep_kernel, crx_field_traffic_kernel)
 struct crx_plant_kparams {
     crx_plant_desc d;
@@ -203,6 +208,14 @@ struct crx_plant_kparams {
 // the code object behind the shared-parameter launches stays what it is.
 struct crx_plant_kparams_cars : crx_plant_kparams {
     const double* params;   // [batch][CRX_PLANT_NPARAM]: m, lf, lr, Iz, Df, Cf, Bf, Dr, Cr, Br of each vehicle; d's ten values are unused
+};
+
+// crx_plant_tracks_kernel / crx_plant_tracks_cars_kernel.  Derived once more, for the same reason.  `track` of the base is the set's
+// tracks [n_tracks][seg_stride][6]; d.n_seg and d.lap_length are unused; params NULL: d's ten values (crx_plant_tracks_kernel).
+struct crx_plant_kparams_tracks : crx_plant_kparams_cars {
+    int n_tracks, seg_stride;          // n_tracks in [1, CRX_MAX_TRACKS], seg_stride in [1, CRX_PLANT_MAX_SEG]
+    const int32_t *n_seg, *track_id;   // [n_tracks], [batch]
+    const double* lap_length;          // [n_tracks]
 };
 
 // ---- crx_lmpcprep.hip ----
@@ -236,12 +249,14 @@ hipError_t crx_launch_prep(const crx_prep_kparams& pp, hipStream_t st);
 hipError_t crx_launch_scene(const crx_scene_kparams& sp, hipStream_t st);
 hipError_t crx_launch_trackprep(const crx_trackprep_kparams& tp, hipStream_t st);
 hipError_t crx_launch_cbfprep(const crx_cbfprep_kparams& cp, hipStream_t st);
+hipError_t crx_launch_cbfprep_laps(const crx_cbfprep_kparams_laps& cp, hipStream_t st);
 hipError_t crx_launch_field_prep(const crx_field_kparams& fp, hipStream_t st);
 hipError_t crx_launch_field_traffic(const crx_field_traffic_kparams& tp, hipStream_t st);
 hipError_t crx_launch_mixed_prep(const crx_mixed_kparams& mp, hipStream_t st);
 // crx_plant.hip
 hipError_t crx_launch_plant(const crx_plant_kparams& pk, hipStream_t st);
 hipError_t crx_launch_plant_cars(const crx_plant_kparams_cars& pk, hipStream_t st);
+hipError_t crx_launch_plant_tracks(const crx_plant_kparams_tracks& pk, hipStream_t st);
 // crx_path.hip
 hipError_t crx_launch_path(const crx_path_kparams& pp, hipStream_t st);
 // crx_pathplan.hip

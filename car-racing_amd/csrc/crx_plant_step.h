@@ -2,21 +2,20 @@
 //   CRX_PLANT_KERNEL, CRX_PLANT_KPARAMS   the kernel's name and its parameter struct (crx_plant_kparams or derived from it)
 //   CRX_PLANT_READ_PARAMS(pk, b)          statements after the bounds check that bring car b's BicycleDynamicsParam values into registers
 //   CRX_PLANT_P(name)                     how the sub-step loop names one of m, lf, lr, Iz, Df, Cf, Bf, Dr, Cr, Br
+//   CRX_PLANT_TABLES(pk)                  the LDS arrays seg_lo, seg_hi, seg_cv, `d`, the block's staging loop and its barrier
+//   CRX_PLANT_READ_TRACK(pk, b)           statements after CRX_PLANT_READ_PARAMS that bring car b's track (rows, first row, lap length) into registers
+//   CRX_PLANT_NSEG, CRX_PLANT_ROW(a, i)   the rows the curvature scan runs over and row i of table a among them
+//   CRX_PLANT_LAP                         the lap length of the two wraps and of the final `s > L` test
 // A text include and not a template over the parameter source (as crx_ilqr.hip's MODELS is): the step inlined into a kernel from a
 // __device__ function compiles crx_plant_kernel to other code than the kernel written out (the block-size read of the table loop and
-// commuted multiplies in the sub-step loop), and the shipped crx_plant_kernel stays what it is, bit for bit.
+// commuted multiplies in the sub-step loop), and the shipped crx_plant_kernel stays what it is, bit for bit: the
+// macros of the one-table kernels expand to the tokens that stood here before there were any.
 __global__ void __launch_bounds__(256) CRX_PLANT_KERNEL(const CRX_PLANT_KPARAMS pk) {
-    __shared__ double seg_lo[CRX_PLANT_MAX_SEG], seg_hi[CRX_PLANT_MAX_SEG], seg_cv[CRX_PLANT_MAX_SEG];
-    const crx_plant_desc& d = pk.d;
-    for (int i = threadIdx.x; i < d.n_seg; i += blockDim.x) {
-        seg_lo[i] = pk.track[6 * i + 3];
-        seg_hi[i] = pk.track[6 * i + 3] + pk.track[6 * i + 4];
-        seg_cv[i] = pk.track[6 * i + 5];
-    }
-    __syncthreads();
+    CRX_PLANT_TABLES(pk)
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= pk.batch) return;
     CRX_PLANT_READ_PARAMS(pk, b)
+    CRX_PLANT_READ_TRACK(pk, b)
     double vx = pk.xcurv[6 * b], vy = pk.xcurv[6 * b + 1], wz = pk.xcurv[6 * b + 2];
     double epsi = pk.xcurv[6 * b + 3], s = pk.xcurv[6 * b + 4], ey = pk.xcurv[6 * b + 5];
     double psi = pk.xglob[6 * b + 3], X = pk.xglob[6 * b + 4], Y = pk.xglob[6 * b + 5];
@@ -25,10 +24,10 @@ __global__ void __launch_bounds__(256) CRX_PLANT_KERNEL(const CRX_PLANT_KPARAMS 
     for (int it = 0; it < d.n_sub; it++) {
         // curvature at s (wrapped into one lap), first segment with lo <= s <= hi
         double sw = s;
-        sw = wrap_below(wrap_above(sw, d.lap_length), d.lap_length);
+        sw = wrap_below(wrap_above(sw, CRX_PLANT_LAP), CRX_PLANT_LAP);
         double curv = 0.0;
-        for (int i = 0; i < d.n_seg; i++)
-            if (sw >= seg_lo[i] && sw <= seg_hi[i]) { curv = seg_cv[i]; break; }
+        for (int i = 0; i < CRX_PLANT_NSEG; i++)
+            if (sw >= CRX_PLANT_ROW(seg_lo, i) && sw <= CRX_PLANT_ROW(seg_hi, i)) { curv = CRX_PLANT_ROW(seg_cv, i); break; }
         // tyre slip angles and lateral forces (the reference uses lf for the rear axle too, :25)
         const double slip_f = delta - atan2(vy + CRX_PLANT_P(lf) * wz, vx);
         const double slip_r = -atan2(vy - CRX_PLANT_P(lf) * wz, vx);
@@ -47,8 +46,8 @@ __global__ void __launch_bounds__(256) CRX_PLANT_KERNEL(const CRX_PLANT_KPARAMS 
         const double vx_n = vx + dt * dvx, vy_n = vy + dt * dvy, wz_n = wz + dt * dwz;
         vx = vx_n; vy = vy_n; wz = wz_n; epsi = epsi_n; s = s_n; ey = ey_n; psi = psi_n; X = X_n; Y = Y_n;
     }
-    if (pk.wrap && s > d.lap_length) {   // ModelBase.update_memory (base.py:795-819)
-        s -= d.lap_length;
+    if (pk.wrap && s > CRX_PLANT_LAP) {   // ModelBase.update_memory (base.py:795-819)
+        s -= CRX_PLANT_LAP;
         if (pk.laps) pk.laps[b] += 1;
     }
     double* g = pk.xglob_next + 6 * (size_t)b;

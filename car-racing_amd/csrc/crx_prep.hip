@@ -219,11 +219,10 @@ __global__ void __launch_bounds__(256) crx_trackprep_kernel(const crx_trackprep_
 // Obstacle arrays of control.mpccbf for scripted cars (see crx_cbf_prep_dev in include/crx.h): one thread
 // per race.  int() of the reference truncates toward zero (control.py:500,519).
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) crx_cbfprep_kernel(const crx_cbfprep_kparams cp) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= cp.batch) return;
+// The race's own text, once: L is the launch's lap length (crx_cbfprep_kernel) or the race's own (crx_cbfprep_laps_kernel).
+__device__ __forceinline__ void cbfprep_race(const crx_cbfprep_kparams& cp, int b, double L) {
     const int N = cp.N, V = cp.V;
-    const double L = cp.lap_length, vx = cp.xcurv[6 * (size_t)b], se = cp.xcurv[6 * (size_t)b + 4];
+    const double vx = cp.xcurv[6 * (size_t)b], se = cp.xcurv[6 * (size_t)b + 4];
     const double margin = cp.safety_time * vx;
     double nce;
     const double dist_ego = lap_fold(se, L, nce);
@@ -251,6 +250,17 @@ __global__ void __launch_bounds__(256) crx_cbfprep_kernel(const crx_cbfprep_kpar
         cp.lap_off[(size_t)b * V + v] = 0.0;
     }
     cp.n_obs[b] = n;
+}
+__global__ void __launch_bounds__(256) crx_cbfprep_kernel(const crx_cbfprep_kparams cp) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= cp.batch) return;
+    cbfprep_race(cp, b, cp.lap_length);
+}
+// crx_cbf_prep_laps_dev: race b folded and offset by lap_lengths[b] (the races of a launch on tracks of their own); cp.lap_length is unused
+__global__ void __launch_bounds__(256) crx_cbfprep_laps_kernel(const crx_cbfprep_kparams_laps cp) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= cp.batch) return;
+    cbfprep_race(cp, b, cp.lap_lengths[b]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -479,6 +489,9 @@ hipError_t crx_launch_trackprep(const crx_trackprep_kparams& tp, hipStream_t st)
     return crx_launch_1d(crx_trackprep_kernel, tp.batch, 256, 256, st, tp);
 }
 hipError_t crx_launch_cbfprep(const crx_cbfprep_kparams& cp, hipStream_t st) { return crx_launch_1d(crx_cbfprep_kernel, cp.batch, 256, 256, st, cp); }
+hipError_t crx_launch_cbfprep_laps(const crx_cbfprep_kparams_laps& cp, hipStream_t st) {
+    return crx_launch_1d(crx_cbfprep_laps_kernel, cp.batch, 256, 256, st, cp);
+}
 // whole races per block: 256 / n_cars of them (n_cars in 1 .. CRX_MAX_OBS + 1, checked by the caller)
 hipError_t crx_launch_field_prep(const crx_field_kparams& fp, hipStream_t st) {
     return crx_launch_1d(crx_field_prep_kernel, fp.n_races, 256 / fp.d.n_cars, 256, st, fp);

@@ -44,7 +44,10 @@
 extern "C" {
 #endif
 
-#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_mixed_desc, crx_mixed_desc_default, crx_mixed_prep, crx_mixed_prep_dev, crx_mixed_commit_dev and
+#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_plant_step_tracks, crx_plant_step_tracks_dev, crx_plant_step_tracks_plain_dev,
+                          crx_cbf_prep_laps_dev and CRX_MAX_TRACKS (one track per vehicle: a track set in the plant, one lap length per race in the
+                          MPC-CBF prep) -- new entry points only.
+                          0.4.0 (additive, same number): crx_mixed_desc, crx_mixed_desc_default, crx_mixed_prep, crx_mixed_prep_dev, crx_mixed_commit_dev and
                           CRX_POLICY_* (mixed fields: every car of a race under its own controller) -- new entry points only.
                           0.4.0 (additive, same number): crx_field_traffic, crx_field_traffic_dev (field games: the racing game's traffic arrays when every car of
                           a race plays it) -- new entry points only.
@@ -689,6 +692,34 @@ int crx_plant_step_params_plain_dev(const crx_plant_desc* d, int batch, const do
                                     double* xcurv_next, void* stream);
 int crx_plant_step_params(const crx_plant_desc* d, int batch, const double* track, const double* xglob, const double* xcurv,
                           const double* u, const double* params, double* xglob_next, double* xcurv_next);
+/*
+ * The same step with every vehicle on a track of its own.  A TRACK SET is four plain arrays:
+ *   tracks [n_tracks][seg_stride][6]   table t holds track t's rows as `track` above; rows n_seg[t] .. seg_stride - 1 are padding, never read
+ *   n_seg [n_tracks] (int32), lap_length [n_tracks]; n_tracks in [1, CRX_MAX_TRACKS], seg_stride in [1, 64]
+ *   track_id [batch] (int32)           vehicle b drives on track track_id[b]: its curvature lookup, and its lap bookkeeping with lap_length[track_id[b]]
+ * d->n_seg and d->lap_length are not used by the step, but the descriptor must still be a valid one (as for `params`, which may be NULL:
+ * the descriptor's ten values).  crx_plant_step_tracks_dev is crx_plant_step_params_dev on a track set (lap bookkeeping, optional noise_z
+ * and laps); crx_plant_step_tracks_plain_dev and the host-pointer crx_plant_step_tracks have no lap bookkeeping and no noise.  The rows of a
+ * launch whose vehicles all name the same track are the bits of the one-table entries on that table.
+ * crx_plant_step_tracks reads its arrays and refuses (CRX_ERR_ARG, the first offender in crx_last_error()) a track_id outside [0, n_tracks),
+ * an n_seg[t] outside [1, seg_stride], a lap length that is not positive and finite, and a bad parameter row.  The `_dev` entries cannot read
+ * device memory: a vehicle with a track_id outside [0, n_tracks) gets non-finite states (its lap counter is left alone) and touches no other
+ * vehicle -- the id never becomes an address; an n_seg[t] is clamped to [0, seg_stride].
+ * The tables are read from LDS per lane: a wavefront whose vehicles sit on different tracks reads different rows in the scan, one whose
+ * vehicles share a track reads one row (a broadcast).  A batch sorted by track makes every wavefront but a few uniform.
+ */
+#define CRX_MAX_TRACKS 8
+int crx_plant_step_tracks_dev(const crx_plant_desc* d, int batch, int n_tracks, int seg_stride, const double* tracks, const int32_t* n_seg,
+                              const double* lap_length, const int32_t* track_id, const double* xglob, const double* xcurv, const double* u,
+                              int u_stride, const double* noise_z, const double* params, double* xglob_next, double* xcurv_next,
+                              int32_t* laps, void* stream);
+int crx_plant_step_tracks_plain_dev(const crx_plant_desc* d, int batch, int n_tracks, int seg_stride, const double* tracks,
+                                    const int32_t* n_seg, const double* lap_length, const int32_t* track_id, const double* xglob,
+                                    const double* xcurv, const double* u, const double* params, double* xglob_next, double* xcurv_next,
+                                    void* stream);
+int crx_plant_step_tracks(const crx_plant_desc* d, int batch, int n_tracks, int seg_stride, const double* tracks, const int32_t* n_seg,
+                          const double* lap_length, const int32_t* track_id, const double* xglob, const double* xcurv, const double* u,
+                          const double* params, double* xglob_next, double* xcurv_next);
 
 /*
  * Overtake PATH planner: one 1-D QP per candidate region
@@ -800,6 +831,10 @@ int crx_path_plan_dev(const crx_pathprep_desc* d, const crx_path_desc* qd, int n
 int crx_cbf_prep_dev(int N, int V, double lap_length, double t, double dt, double safety_time, int batch,
                      const double* xcurv, const double* car_s0, const double* car_v, const double* car_ey,
                      double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, void* stream);
+/* The same with the races of a launch on tracks of their own: race b folded and offset by lap_length[b] ([batch], device). */
+int crx_cbf_prep_laps_dev(int N, int V, const double* lap_length, double t, double dt, double safety_time, int batch,
+                          const double* xcurv, const double* car_s0, const double* car_v, const double* car_ey,
+                          double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, void* stream);
 
 /*
  * Field races: the obstacle arrays of control.mpccbf when EVERY car of a race drives itself.  n_races races of C = n_cars cars

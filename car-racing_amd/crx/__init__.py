@@ -119,6 +119,16 @@ def field_traffic(desc, track, xcurv):
     return binding().field_traffic(desc, track, xcurv)
 
 
+def field_prep_tracks(desc, tracks, race_track, xcurv, car_dims=None):
+    """Field-race prep with race r on track race_track[r] of a track set (abi.track_set) on host arrays: see abi.Binding.field_prep_tracks."""
+    return binding().field_prep_tracks(desc, tracks, race_track, xcurv, car_dims)
+
+
+def mixed_prep_tracks(desc, tracks, race_track, xcurv, policy, car_dims=None):
+    """Mixed-field prep with race r on track race_track[r] of a track set on host arrays: see abi.Binding.mixed_prep_tracks."""
+    return binding().mixed_prep_tracks(desc, tracks, race_track, xcurv, policy, car_dims)
+
+
 def mixed_prep(desc, track, xcurv, policy, car_dims=None):
     """Mixed-field prep (include/crx.h "Mixed fields") on host arrays: see abi.Binding.mixed_prep."""
     return binding().mixed_prep(desc, track, xcurv, policy, car_dims)

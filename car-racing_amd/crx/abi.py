@@ -302,6 +302,7 @@ STATS_ARGTYPES = {
     "stats_desc_default": [_PD, C.c_int, C.c_int, C.c_double, C.c_double],
     "race_stats_reset_dev": [_PD, C.c_int, _PV, _PV, _PV, _PV],
     "race_stats_dev": [_PD, C.c_int, C.c_int, C.c_double] + [_PV] * 12,
+    "race_stats_laps_dev": [_PD, C.c_int, C.c_int, C.c_double] + [_PV] * 13,
     "race_stats_summary_dev": [_PD, C.c_int, _PV, C.c_int, _PV, _PV, _PV, _PV, _PV],
     "race_stats_reset": [_PD, C.c_int, _PV, _PV, _PV],
     "race_stats": [_PD, C.c_int, C.c_int, C.c_double] + [_PV] * 11,
@@ -572,7 +573,7 @@ class Binding:
         for name in ("planner_solve", "cbf_solve", "select", "lmpc_solve", "planner_prep", "plant_step", "path_solve", "ilqr_solve",
                      "ilqr_solve_models", "lqr_design", "sysid_fit", "cbf_solve_models", "planner_solve_models", "planner_plan",
                      "planner_plan_models", "path_prep", "path_plan", "plant_step_params", "field_prep", "field_traffic", "mixed_prep",
-                     "plant_step_tracks"):
+                     "plant_step_tracks", "field_prep_tracks", "mixed_prep_tracks"):
             if hasattr(lib, prefix + name):
                 getattr(lib, prefix + name).restype = C.c_int
         if hasattr(lib, prefix + "race_stats_dev"):
@@ -919,14 +920,30 @@ class Binding:
                    _p(out["xcurv"]))
         return out
 
+    @staticmethod
+    def _race_track_args(tracks, race_track, xcurv, n_cars):
+        """The arguments that stand in place of `track` in the `tracks` entries of the field families: n_tracks, seg_stride, the set's three
+        arrays and race_track (R,), R read off xcurv as the entries' wrappers read it."""
+        R = np.asarray(xcurv).size // (6 * n_cars)
+        return [C.c_int(tracks.n_tracks), C.c_int(tracks.seg_stride), _in(tracks.tracks, _D, (tracks.n_tracks, tracks.seg_stride, 6)),
+                _in(tracks.n_seg, _I, (tracks.n_tracks,)), _in(tracks.lap_length, _D, (tracks.n_tracks,)), _in(race_track, _I, (R,))]
+
     def field_prep(self, desc, track, xcurv, car_dims=None, clear=True):
         """crx_field_prep (include/crx.h F1-F7): the predictions of every car of every race and the obstacle arrays of the R * C NLPs.
         track (n_seg,6); xcurv (R,C,6) or (R*C,6); car_dims (R,C,2) = (length, width) per car, or None.  Returns pred_s, pred_ey
         (R,C,N+1), obs_s, obs_ey (R,C,V,N+1), lap_off (R,C,V), n_obs (R,C) with V = C - 1; obs_dims (R,C,V,2) with car_dims; clear (R,C)
         unless clear is False."""
+        return self._field_prep("field_prep", [_in(track, _D, (desc.n_seg, 6))], desc, xcurv, car_dims, clear)
+
+    def field_prep_tracks(self, desc, tracks, race_track, xcurv, car_dims=None, clear=True):
+        """crx_field_prep_tracks: field_prep with race r on track race_track[r] of the TrackSet `tracks` (track_set); race_track (R,) int32;
+        desc's n_seg and lap_length are not used.  A race_track outside [0, n_tracks) is refused."""
+        return self._field_prep("field_prep_tracks", self._race_track_args(tracks, race_track, xcurv, desc.n_cars), desc, xcurv, car_dims, clear)
+
+    def _field_prep(self, entry, track_args, desc, xcurv, car_dims, clear):
+        """field_prep / field_prep_tracks: track_args, c_ints and arrays, is what the entry takes between n_races and xcurv."""
         N1, Cn = desc.N + 1, desc.n_cars
         V = Cn - 1
-        track = _in(track, _D, (desc.n_seg, 6))
         xcurv = np.ascontiguousarray(xcurv, dtype=_D)
         R = xcurv.size // (6 * Cn)
         xcurv = _in(xcurv.reshape(R, Cn, 6), _D, (R, Cn, 6))
@@ -937,8 +954,8 @@ class Binding:
             out["obs_dims"] = np.zeros((R, Cn, V, 2))
         if clear:
             out["clear"] = np.zeros((R, Cn))
-        self._call("field_prep", C.byref(desc), C.c_int(R), _p(track), _p(xcurv), _p(car_dims) if car_dims is not None else None,
-                   *[_p(out[k]) for k in ("pred_s", "pred_ey", "obs_s", "obs_ey", "lap_off", "n_obs")],
+        self._call(entry, C.byref(desc), C.c_int(R), *[a if isinstance(a, C.c_int) else _p(a) for a in track_args], _p(xcurv),
+                   _p(car_dims) if car_dims is not None else None, *[_p(out[k]) for k in ("pred_s", "pred_ey", "obs_s", "obs_ey", "lap_off", "n_obs")],
                    _p(out["obs_dims"]) if car_dims is not None else None, _p(out["clear"]) if clear else None)
         return out
 
@@ -964,9 +981,18 @@ class Binding:
         track (n_seg,6); xcurv (R,C,6) or (R*C,6); policy (R,C) codes or names; car_dims (R,C,2) or None.  Returns pred_s, pred_ey
         (R,C,NP+1), NP = max(N, N_ilqr); obs_s, obs_ey (R,C,V,N+1), lap_off (R,C,V), n_obs, m_nlp (R,C), obs_dims (R,C,V,2) with car_dims; with
         N_ilqr > 0 il_obs_s, il_obs_ey (R,C,V,N_ilqr+1), il_lap_off (R,C,V), il_n_obs, m_ilqr (R,C); clear (R,C) unless clear is False."""
+        return self._mixed_prep("mixed_prep", [_in(track, _D, (desc.n_seg, 6))], desc, xcurv, policy, car_dims, clear)
+
+    def mixed_prep_tracks(self, desc, tracks, race_track, xcurv, policy, car_dims=None, clear=True):
+        """crx_mixed_prep_tracks: mixed_prep with race r on track race_track[r] of the TrackSet `tracks` (track_set); race_track (R,) int32;
+        desc's n_seg and lap_length are not used.  A race_track outside [0, n_tracks) is refused."""
+        return self._mixed_prep("mixed_prep_tracks", self._race_track_args(tracks, race_track, xcurv, desc.n_cars), desc, xcurv, policy, car_dims,
+                                clear)
+
+    def _mixed_prep(self, entry, track_args, desc, xcurv, policy, car_dims, clear):
+        """mixed_prep / mixed_prep_tracks: track_args as in _field_prep."""
         N1, NI1, Cn = desc.N + 1, desc.N_ilqr + 1, desc.n_cars
         V, NP1 = Cn - 1, max(N1, NI1)
-        track = _in(track, _D, (desc.n_seg, 6))
         xcurv = np.ascontiguousarray(xcurv, dtype=_D)
         R = xcurv.size // (6 * Cn)
         xcurv = _in(xcurv.reshape(R, Cn, 6), _D, (R, Cn, 6))
@@ -982,7 +1008,8 @@ class Binding:
         if clear:
             out["clear"] = np.zeros((R, Cn))
         opt = lambda k: _p(out[k]) if k in out else None   # noqa: E731
-        self._call("mixed_prep", C.byref(desc), C.c_int(R), _p(track), _p(xcurv), _p(policy), _p(car_dims) if car_dims is not None else None,
+        self._call(entry, C.byref(desc), C.c_int(R), *[a if isinstance(a, C.c_int) else _p(a) for a in track_args], _p(xcurv), _p(policy),
+                   _p(car_dims) if car_dims is not None else None,
                    *[opt(k) for k in ("pred_s", "pred_ey", "obs_s", "obs_ey", "lap_off", "n_obs", "obs_dims", "m_nlp", "il_obs_s", "il_obs_ey",
                                       "il_lap_off", "il_n_obs", "m_ilqr", "clear")])
         return out

@@ -206,7 +206,8 @@ class _Plant:
     process noise, and plant_params: one parameter set per car [B,10], or None.  _advance() is the one place a loop steps its plant.  The contract bench.py times the solver launches by:
     after a step, xc_next is the state that step's solver launch was built for."""
 
-    def _plant_init(self, track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params=None, tracks=None, track_id=None):
+    def _plant_init(self, track_table, lap_length, timestep, xcurv0, xglob0, noise_seed, device, plant_params=None, tracks=None, track_id=None,
+                    track_set=None):
         dev = torch.device(device if device is not None else "cuda")
         self.device, self.lap_length, self.timestep = dev, lap_length, timestep
         self.noise = _Noise(noise_seed, dev)
@@ -216,14 +217,17 @@ class _Plant:
         self.laps = torch.zeros(self.batch, dtype=torch.int32, device=dev)
         # tracks (abi.track_set) and track_id [B], host array or device tensor: car b on track track_id[b] (crx_plant_step_tracks_dev);
         # track_table and lap_length are then unused (None), self.lap_length is the per-car tensor lap_length[track_id] and the plant
-        # descriptor carries track 0's row count and lap length only to be a valid one.  None: the one track_table for all cars
+        # descriptor carries track 0's row count and lap length only to be a valid one.  None: the one track_table for all cars.
+        # track_set: the same, already on the device (a field's RaceTrackSetDev: the cars' ids made of the races')
         self.tracks = None
         if (tracks is None) != (track_id is None):
             raise ValueError("tracks and track_id go together: a track set and every car's track, or neither")
+        if track_set is not None:
+            tracks = track_set.host
         if tracks is not None:
             if track_table is not None or lap_length is not None:
                 raise ValueError("with tracks= the loop has no track_table / lap_length of its own: pass None for both")
-            self.tracks = torch_api.TrackSetDev(tracks, track_id, dev)
+            self.tracks = track_set if track_set is not None else torch_api.TrackSetDev(tracks, track_id, dev)
             if tuple(self.tracks.track_id.shape) != (self.batch,):
                 raise ValueError("track_id: expected shape %s, got %s" % ((self.batch,), tuple(self.tracks.track_id.shape)))
             self.lap_length = self.tracks.car_lap
@@ -272,6 +276,15 @@ def _one_track_only(loop, tracks, track_id):
     if tracks is not None or track_id is not None:
         raise ValueError("%s runs on one track: tracks= / track_id= (one track per car) are taken by PidLaps, LqrLaps and MpccbfRaces only -- "
                          "its other launches read one track table or one lap length" % loop)
+
+
+def _race_tracks_only(loop, tracks, track_id, race_track):
+    """FieldRaces and MixedRaces: a field's unit is the race, so a track set comes with race_track= (one id per race); the per-car track_id=
+    stays refused, and so does a set without race_track=."""
+    if track_id is not None:
+        _one_track_only(loop, tracks, track_id)
+    if (tracks is None) != (race_track is None):
+        raise ValueError("%s: tracks= and race_track= go together: a track set (abi.track_set) and every race's track [R], or neither" % loop)
 
 
 def _run_and_log(step, steps, log_every, getters, before=()):
@@ -392,8 +405,12 @@ class _Field(_Plant):
     (below 1: contact); fd: the loop's field or mixed descriptor, for its l_sum, w_sum."""
 
     def _field_init(self, track_table, lap_length, track_width, timestep, xcurv0, xglob0, n_cars, vt, eyt, N, car_dims, noise_seed, device,
-                    plant_params, n_races=None):
-        """n_races: the races the caller's other arguments make (MixedRaces' policy); None: as many as xcurv0 holds.  Returns the device."""
+                    plant_params, n_races=None, tracks=None, race_track=None):
+        """n_races: the races the caller's other arguments make (MixedRaces' policy); None: as many as xcurv0 holds.  tracks (abi.track_set)
+        and race_track [R], integer, host array or tensor: race r on track race_track[r], all its cars on it -- track_table and lap_length are
+        then None, self.tracks is a torch_api.RaceTrackSetDev (the plant steps through its tracks entry with track_id = race_track repeated
+        n_cars times), self.lap_length the cars' own lap lengths [R*C], and _prep_geometry() gives the prep descriptors track 0's row count
+        and lap length only to make them valid ones.  One track_width serves all tracks.  Returns the device."""
         Cn = int(n_cars)
         if not 1 <= Cn <= abi.CRX_MAX_OBS + 1:
             raise ValueError("1 .. %d cars per race" % (abi.CRX_MAX_OBS + 1))
@@ -402,7 +419,12 @@ class _Field(_Plant):
         if x0.shape[0] != R * Cn or g0.shape != x0.shape:
             raise ValueError("xcurv0, xglob0: %d and %d cars" % (x0.shape[0], g0.shape[0])
                              + (" do not make races of %d" % Cn if n_races is None else ", policy has %d x %d" % (R, Cn)))
-        dev = self._plant_init(track_table, lap_length, timestep, x0, g0, noise_seed, device, plant_params)
+        ts = None
+        if tracks is not None:
+            ts = torch_api.RaceTrackSetDev(tracks, race_track, Cn, torch.device(device if device is not None else "cuda"))
+            if tuple(ts.race_track.shape) != (R,):
+                raise ValueError("race_track: expected shape %s, got %s" % ((R,), tuple(ts.race_track.shape)))
+        dev = self._plant_init(track_table, lap_length, timestep, x0, g0, noise_seed, device, plant_params, track_set=ts)
         self.N, self.n_races, self.n_cars, self.track_width = N, R, Cn, track_width
         # vt, eyt: scalars or one value per car [R,C] -- different target speeds are what makes the cars meet
         xt = np.zeros((self.batch, 6))
@@ -413,6 +435,12 @@ class _Field(_Plant):
         self.car_dims = None if car_dims is None else _dev(np.asarray(car_dims, dtype=float).reshape(R, Cn, 2), dev)
         self.min_clear = torch.full((self.batch,), float("inf"), dtype=torch.float64, device=dev)
         return dev
+
+    def _prep_geometry(self):
+        """(n_seg, lap_length) of the loop's prep descriptor: the one track's, or track 0's of a set (unused by the `tracks` entries)."""
+        if self.tracks is not None:
+            return int(self.tracks.host.n_seg[0]), float(self.tracks.host.lap_length[0])
+        return self.tab.shape[0], self.lap_length
 
     def _join_clear(self, clear):
         torch.minimum(self.min_clear, clear, out=self.min_clear)
@@ -428,13 +456,13 @@ class FieldRaces(_Field):
     the states at the start of the step (include/crx.h, crx_field_prep_dev, quirks F1-F7).  min_clear [R*C]: see _Field."""
 
     def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, n_cars, vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1,
-                 device=None, noise_seed=None, models=None, plant_params=None, car_dims=None, tracks=None, track_id=None):
-        _one_track_only("FieldRaces", tracks, track_id)
+                 device=None, noise_seed=None, models=None, plant_params=None, car_dims=None, tracks=None, track_id=None, race_track=None):
+        _race_tracks_only("FieldRaces", tracks, track_id, race_track)
         dev = self._field_init(track_table, lap_length, track_width, timestep, xcurv0, xglob0, n_cars, vt, eyt, N, car_dims, noise_seed,
-                               device, plant_params)
+                               device, plant_params, tracks=tracks, race_track=race_track)
         Bn, R, Cn = self.batch, self.n_races, self.n_cars
         self.desc = abi.cbf_desc(N, Cn - 1, A, B, alpha=alpha, margin=0.2, ey_max=track_width)
-        self.fdesc = self.fd = abi.field_desc(N, Cn, self.tab.shape[0], lap_length, dt=timestep)
+        self.fdesc = self.fd = abi.field_desc(N, Cn, *self._prep_geometry(), dt=timestep)
         self.ws = torch_api.CbfWorkspace(self.desc, Bn, dev)
         # models = (A [R*C,6,6], B [R*C,6,2]): every car's controller on its own model, as in MpccbfRaces
         self.models = None if models is None else torch_api.CbfModels(self.desc, *_models(models[0], models[1], Bn, dev))
@@ -443,9 +471,13 @@ class FieldRaces(_Field):
 
     def step(self):
         """One control step of every car of every race, three libcrx launches: field_prep_dev, cbf_solve_dev, plant_step_wrap_dev
-        (dispatch = "longest_first": one longest_first ahead of the solver launch); then `clear` joins the running minimum."""
+        (dispatch = "longest_first": one longest_first ahead of the solver launch); then `clear` joins the running minimum.  With
+        tracks= / race_track=: field_prep_tracks_dev, cbf_solve_dev, plant_step_tracks_wrap_dev."""
         f = self.fws
-        torch_api.field_prep_dev(self.fdesc, self.tab, self.xc, f, car_dims=self.car_dims)
+        if self.tracks is None:
+            torch_api.field_prep_dev(self.fdesc, self.tab, self.xc, f, car_dims=self.car_dims)
+        else:
+            torch_api.field_prep_tracks_dev(self.fdesc, self.tracks, self.xc, f, car_dims=self.car_dims)
         torch_api.cbf_solve_dev(self.desc, self.xc, self.xt, f.obs_s, f.obs_ey, f.lap_off, f.n_obs, ws=self.ws,
                                 order=_order(self, self.ws.iters), models=self.models, obs_dims=f.obs_dims)
         self._advance(self.ws.U, 2 * self.N)
@@ -454,12 +486,13 @@ class FieldRaces(_Field):
 
 
 def field_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, n_cars, steps, vt=0.8, eyt=0.0, N=10, alpha=0.8, timestep=0.1,
-                device=None, log_every=1, noise_seed=None, models=None, plant_params=None, car_dims=None):
+                device=None, log_every=1, noise_seed=None, models=None, plant_params=None, car_dims=None, tracks=None, race_track=None):
     """xcurv0, xglob0 [R*C,6] or [R,C,6]; vt, eyt scalars or [R,C]; models = (A [R*C,6,6], B [R*C,6,2]); plant_params [R*C,10]; car_dims
     [R,C,2].  Returns host arrays: xcurv [T+1,R*C,6] (T = steps / log_every), u [T,R*C,2], status, iters, n_obs [T,R*C], laps [R*C],
-    min_clear [R*C]."""
+    min_clear [R*C].  tracks (abi.track_set), race_track [R]: race r on its own track (track_table and lap_length None)."""
     r = FieldRaces(track_table, lap_length, track_width, A, B, xcurv0, xglob0, n_cars, vt=vt, eyt=eyt, N=N, alpha=alpha, timestep=timestep,
-                   device=device, noise_seed=noise_seed, models=models, plant_params=plant_params, car_dims=car_dims)
+                   device=device, noise_seed=noise_seed, models=models, plant_params=plant_params, car_dims=car_dims, tracks=tracks,
+                   race_track=race_track)
     logs = _run_and_log(r.step, steps, log_every, dict(xcurv=lambda: r.xc, u=lambda: r.u, status=lambda: r.ws.status,
                                                        iters=lambda: r.ws.iters, n_obs=lambda: r.fws.n_obs))
     return dict(logs, laps=r.laps.cpu().numpy(), min_clear=r.min_clear.cpu().numpy())
@@ -476,20 +509,20 @@ class MixedRaces(_Field):
 
     def __init__(self, track_table, lap_length, track_width, A, B, xcurv0, xglob0, policy, vt=0.8, eyt=0.0, N=10, ilqr_N=50, ilqr_max_iter=150,
                  ilqr_obstacles=0, alpha=0.8, timestep=0.1, device=None, noise_seed=None, models=None, plant_params=None, car_dims=None,
-                 tracks=None, track_id=None):
-        _one_track_only("MixedRaces", tracks, track_id)
+                 tracks=None, track_id=None, race_track=None):
+        _race_tracks_only("MixedRaces", tracks, track_id, race_track)
         pol = abi.policy_codes(policy)
         if pol.ndim != 2 or not 1 <= pol.shape[1] <= abi.CRX_MAX_OBS + 1:
             raise ValueError("policy: [R,C] with 1 .. %d cars per race" % (abi.CRX_MAX_OBS + 1))
         R, Cn = pol.shape
         # xt is the target of the NLP, iLQR and LQR cars, (vt, eyt) the PID cars'
         dev = self._field_init(track_table, lap_length, track_width, timestep, xcurv0, xglob0, Cn, vt, eyt, N, car_dims, noise_seed, device,
-                               plant_params, n_races=R)
+                               plant_params, n_races=R, tracks=tracks, race_track=race_track)
         Bn = self.batch
         has = lambda *codes: bool(np.isin(pol, codes).any())   # noqa: E731
         has_nlp, has_ilqr, has_lqr, has_pid = has(abi.POLICY_MPC_LTI, abi.POLICY_MPCCBF), has(abi.POLICY_ILQR), has(abi.POLICY_LQR), has(abi.POLICY_PID)
         self.policy = _dev(pol.reshape(-1), dev, dtype=torch.int32)
-        self.mdesc = self.fd = abi.mixed_desc(N, ilqr_N if has_ilqr else 0, Cn, self.tab.shape[0], lap_length, ilqr_obstacles=ilqr_obstacles, dt=timestep)
+        self.mdesc = self.fd = abi.mixed_desc(N, ilqr_N if has_ilqr else 0, Cn, *self._prep_geometry(), ilqr_obstacles=ilqr_obstacles, dt=timestep)
         self.vt, self.eyt = (self.xt[:, 0].contiguous(), self.xt[:, 5].contiguous()) if has_pid else (None, None)
         # models = (A [R*C,6,6], B [R*C,6,2]): every car's controller on its own model -- the NLP's, the iLQR's and the LQR design's
         mAB = None if models is None else _models(models[0], models[1], Bn, dev)
@@ -515,9 +548,13 @@ class MixedRaces(_Field):
     def step(self):
         """One control step of every car of every race: mixed_prep_dev, cbf_solve_dev (active = m_nlp), ilqr_solve_dev (active = m_ilqr),
         mixed_commit_dev, plant_step_wrap_dev -- a solver launch whose policy no car has is left out and its family given as None
-        (dispatch = "longest_first": one longest_first ahead of the NLP launch); then `clear` joins the running minimum."""
+        (dispatch = "longest_first": one longest_first ahead of the NLP launch); then `clear` joins the running minimum.  With tracks= /
+        race_track=: mixed_prep_tracks_dev in place of mixed_prep_dev and plant_step_tracks_wrap_dev in place of plant_step_wrap_dev."""
         m = self.mws
-        torch_api.mixed_prep_dev(self.mdesc, self.tab, self.xc, self.policy, m, car_dims=self.car_dims)
+        if self.tracks is None:
+            torch_api.mixed_prep_dev(self.mdesc, self.tab, self.xc, self.policy, m, car_dims=self.car_dims)
+        else:
+            torch_api.mixed_prep_tracks_dev(self.mdesc, self.tracks, self.xc, self.policy, m, car_dims=self.car_dims)
         if self.ws is not None:
             torch_api.cbf_solve_dev(self.desc, self.xc, self.xt, m.obs_s, m.obs_ey, m.lap_off, m.n_obs, ws=self.ws, active=m.m_nlp,
                                     order=_order(self, self.ws.iters, m.m_nlp), models=self.models, obs_dims=m.obs_dims)
@@ -533,13 +570,14 @@ class MixedRaces(_Field):
 
 
 def mixed_races(track_table, lap_length, track_width, A, B, xcurv0, xglob0, policy, steps, vt=0.8, eyt=0.0, N=10, ilqr_N=50, ilqr_max_iter=150,
-                ilqr_obstacles=0, alpha=0.8, timestep=0.1, device=None, log_every=1, noise_seed=None, models=None, plant_params=None, car_dims=None):
+                ilqr_obstacles=0, alpha=0.8, timestep=0.1, device=None, log_every=1, noise_seed=None, models=None, plant_params=None, car_dims=None,
+                tracks=None, race_track=None):
     """policy [R,C] codes or names; xcurv0, xglob0 [R*C,6] or [R,C,6]; vt, eyt scalars or [R,C]; models = (A [R*C,6,6], B [R*C,6,2]);
     plant_params [R*C,10]; car_dims [R,C,2].  Returns host arrays: xcurv [T+1,R*C,6] (T = steps / log_every), u [T,R*C,2], status [T,R*C],
-    laps [R*C], min_clear [R*C]."""
+    laps [R*C], min_clear [R*C].  tracks (abi.track_set), race_track [R]: race r on its own track (track_table and lap_length None)."""
     r = MixedRaces(track_table, lap_length, track_width, A, B, xcurv0, xglob0, policy, vt=vt, eyt=eyt, N=N, ilqr_N=ilqr_N, ilqr_max_iter=ilqr_max_iter,
                    ilqr_obstacles=ilqr_obstacles, alpha=alpha, timestep=timestep, device=device, noise_seed=noise_seed, models=models,
-                   plant_params=plant_params, car_dims=car_dims)
+                   plant_params=plant_params, car_dims=car_dims, tracks=tracks, race_track=race_track)
     logs = _run_and_log(r.step, steps, log_every, dict(xcurv=lambda: r.xc, u=lambda: r.u, status=lambda: r.status))
     return dict(logs, laps=r.laps.cpu().numpy(), min_clear=r.min_clear.cpu().numpy())
 
@@ -1302,12 +1340,19 @@ class RaceStats:
     after the step (or the other cars of the race, same snapshot).  group [B] int32 in [0, n_groups) splits the summary.  All launches
     go to the current stream: construct and step a sub-batch's RaceStats under the stream the sub-batch runs on.  track_width
     overrides the loop's (the loops without a track width -- IlqrRaces, PidLaps, LqrLaps -- never count a car as off track without it).
-    first_sample = 1: for a caller that takes no sample of the initial states, so that the sample after step k is still k + 1."""
+    first_sample = 1: for a caller that takes no sample of the initial states, so that the sample after step k is still k + 1.
+    Track sets: a FieldRaces / MixedRaces built with tracks= / race_track= is sampled through race_stats_laps_dev with the loop's car_lap
+    (every car folded by its own track's lap length).  The per-car loops PidLaps, LqrLaps and MpccbfRaces with tracks= / track_id= are still
+    refused -- crx_race_stats_laps_dev would serve them as well; lifting that is a follow-up."""
 
     def __init__(self, loop, group=None, n_groups=1, track_width=None, first_sample=0):
         self.loop = loop
-        if getattr(getattr(loop, "lm", loop), "tracks", None) is not None:
+        ts = getattr(getattr(loop, "lm", loop), "tracks", None)
+        if ts is not None and getattr(ts, "race_track", None) is None:
             raise ValueError("RaceStats takes one lap length (crx_stats_desc): a loop on a track set (tracks=, one track per car) has one per car")
+        # a field on one track per race (FieldRaces, MixedRaces with race_track=): every sample through race_stats_laps_dev with the cars' own
+        # lap lengths; the descriptor carries track 0's only to be a valid one
+        self.car_lap = None if ts is None else ts.car_lap
         inp = loop.stats_inputs()
         xc = inp["xcurv"]
         Bn, dev = xc.shape[0], xc.device
@@ -1315,7 +1360,8 @@ class RaceStats:
         V = n_cars - 1 if n_cars else (inp["car_s0"].shape[1] if inp.get("car_s0") is not None else 0)
         if track_width is None:
             track_width = inp.get("track_width")
-        self.desc = abi.stats_desc(V, n_cars, inp["lap_length"], float("inf") if track_width is None else track_width,
+        self.desc = abi.stats_desc(V, n_cars, inp["lap_length"] if ts is None else float(ts.host.lap_length[0]),
+                                   float("inf") if track_width is None else track_width,
                                    l_sum=inp.get("l_sum") or 0.4, w_sum=inp.get("w_sum") or 0.2)
         self.ws = torch_api.RaceStatsWorkspace(self.desc, Bn, dev)
         self.group, self.n_groups = None, int(n_groups)
@@ -1325,11 +1371,15 @@ class RaceStats:
         torch_api.race_stats_reset_dev(self.desc, inp["laps"], self.ws)
 
     def update(self):
-        """ONE race_stats_dev on the current stream; the sample index is the number of updates so far."""
+        """ONE race_stats_dev (race_stats_laps_dev for a field on one track per race) on the current stream; the sample index is the
+        number of updates so far."""
         inp = self.loop.stats_inputs()
-        torch_api.race_stats_dev(self.desc, self.n_updates, inp["t"], inp["xcurv"], inp["laps"], self.ws, car_s0=inp.get("car_s0"),
-                                 car_v=inp.get("car_v"), car_ey=inp.get("car_ey"), n_opp=inp.get("n_opp"), car_dims=inp.get("car_dims"),
-                                 xt=inp.get("xt"), flag=inp.get("flag"))
+        kw = dict(car_s0=inp.get("car_s0"), car_v=inp.get("car_v"), car_ey=inp.get("car_ey"), n_opp=inp.get("n_opp"), car_dims=inp.get("car_dims"),
+                  xt=inp.get("xt"), flag=inp.get("flag"))
+        if self.car_lap is None:
+            torch_api.race_stats_dev(self.desc, self.n_updates, inp["t"], inp["xcurv"], inp["laps"], self.ws, **kw)
+        else:
+            torch_api.race_stats_laps_dev(self.desc, self.n_updates, inp["t"], inp["xcurv"], inp["laps"], self.ws, lap_length=self.car_lap, **kw)
         self.n_updates += 1
 
     def step(self):

@@ -553,15 +553,26 @@ def _chk_field_ws(desc, ws, n_pred):
 def field_prep_dev(desc, track, xcurv, ws, car_dims=None):
     """crx_field_prep_dev (include/crx.h F1-F7): xcurv [R*C,6] (race-major, car-minor), track [n_seg,6], car_dims [R,C,2] (length, width
     per car) with a FieldWorkspace(dims=True), None with dims=False.  Writes ws and returns it."""
-    R, Cn = ws.n_races, desc.n_cars
     _chk(track, torch.float64, (desc.n_seg, 6), "track")
+    return _field_prep("crx_field_prep_dev", (_ptr(track),), desc, xcurv, ws, car_dims)
+
+
+def field_prep_tracks_dev(desc, track_set, xcurv, ws, car_dims=None):
+    """crx_field_prep_tracks_dev: field_prep_dev with race r on track track_set.race_track[r] of the RaceTrackSetDev `track_set`; desc's n_seg
+    and lap_length are not used.  Writes ws and returns it."""
+    return _field_prep("crx_field_prep_tracks_dev", _chk_race_track_set(track_set, ws.n_races), desc, xcurv, ws, car_dims)
+
+
+def _field_prep(entry, track_args, desc, xcurv, ws, car_dims):
+    """field_prep_dev / field_prep_tracks_dev: track_args is what the entry takes between n_races and xcurv."""
+    R, Cn = ws.n_races, desc.n_cars
     _chk(xcurv, torch.float64, (R * Cn, 6), "xcurv")
     if (car_dims is None) != (ws.obs_dims is None):
         raise ValueError("car_dims goes with a FieldWorkspace(dims=True), no car_dims with dims=False")
     if car_dims is not None:
         _chk(car_dims, torch.float64, (R, Cn, 2), "car_dims")
     _chk_field_ws(desc, ws, desc.N + 1)
-    _call("crx_field_prep_dev", C.byref(desc), C.c_int(R), _ptr(track), _ptr(xcurv), _ptr(car_dims), _ptr(ws.pred_s), _ptr(ws.pred_ey),
+    _call(entry, C.byref(desc), C.c_int(R), *track_args, _ptr(xcurv), _ptr(car_dims), _ptr(ws.pred_s), _ptr(ws.pred_ey),
           _ptr(ws.obs_s), _ptr(ws.obs_ey), _ptr(ws.lap_off), _ptr(ws.n_obs), _ptr(ws.obs_dims), _ptr(ws.clear), _stream())
     return ws
 
@@ -625,9 +636,20 @@ class MixedWorkspace(FieldWorkspace):
 def mixed_prep_dev(desc, track, xcurv, policy, ws, car_dims=None):
     """crx_mixed_prep_dev (include/crx.h "Mixed fields"): xcurv [R*C,6] (race-major, car-minor), track [n_seg,6], policy int32 [R*C] of
     abi.POLICY_* codes, car_dims [R,C,2] with a MixedWorkspace(dims=True), None with dims=False.  Writes ws and returns it."""
+    _chk(track, torch.float64, (desc.n_seg, 6), "track")
+    return _mixed_prep("crx_mixed_prep_dev", (_ptr(track),), desc, xcurv, policy, ws, car_dims)
+
+
+def mixed_prep_tracks_dev(desc, track_set, xcurv, policy, ws, car_dims=None):
+    """crx_mixed_prep_tracks_dev: mixed_prep_dev with race r on track track_set.race_track[r] of the RaceTrackSetDev `track_set`; desc's
+    n_seg and lap_length are not used.  Writes ws and returns it."""
+    return _mixed_prep("crx_mixed_prep_tracks_dev", _chk_race_track_set(track_set, ws.n_races), desc, xcurv, policy, ws, car_dims)
+
+
+def _mixed_prep(entry, track_args, desc, xcurv, policy, ws, car_dims):
+    """mixed_prep_dev / mixed_prep_tracks_dev: track_args as in _field_prep."""
     R, Cn, NI1 = ws.n_races, desc.n_cars, desc.N_ilqr + 1
     Bn, V = R * Cn, Cn - 1
-    _chk(track, torch.float64, (desc.n_seg, 6), "track")
     _chk(xcurv, torch.float64, (Bn, 6), "xcurv")
     _chk(policy, torch.int32, (Bn,), "policy")
     if (car_dims is None) != (ws.obs_dims is None):
@@ -643,7 +665,7 @@ def mixed_prep_dev(desc, track, xcurv, policy, ws, car_dims=None):
     for name in ("m_nlp", "il_n_obs", "m_ilqr"):
         if getattr(ws, name) is not None:
             _chk(getattr(ws, name), torch.int32, (Bn,), "ws." + name)
-    _call("crx_mixed_prep_dev", C.byref(desc), C.c_int(R), _ptr(track), _ptr(xcurv), _ptr(policy), _ptr(car_dims), _ptr(ws.pred_s), _ptr(ws.pred_ey),
+    _call(entry, C.byref(desc), C.c_int(R), *track_args, _ptr(xcurv), _ptr(policy), _ptr(car_dims), _ptr(ws.pred_s), _ptr(ws.pred_ey),
           _ptr(ws.obs_s), _ptr(ws.obs_ey), _ptr(ws.lap_off), _ptr(ws.n_obs), _ptr(ws.obs_dims), _ptr(ws.m_nlp), _ptr(ws.il_obs_s), _ptr(ws.il_obs_ey),
           _ptr(ws.il_lap_off), _ptr(ws.il_n_obs), _ptr(ws.m_ilqr), _ptr(ws.clear), _stream())
     return ws
@@ -722,6 +744,22 @@ def race_stats_dev(desc, sample, t, xcurv, laps, ws, car_s0=None, car_v=None, ca
     """crx_race_stats_dev (include/crx.h S1-S4): one sample of every car, ONE launch.  xcurv [batch,6], laps [batch] int32; scripted mode
     (desc.n_cars == 0): car_s0, car_v, car_ey [batch, n_opp_max] at the clock t, n_opp [batch] int32 optional; field mode: car_dims
     [batch / n_cars, n_cars, 2] optional; xt [batch,6] and flag [batch] int32 optional.  Updates ws in place and returns it."""
+    return _race_stats("crx_race_stats_dev", (), desc, sample, t, xcurv, laps, ws, car_s0, car_v, car_ey, n_opp, car_dims, xt, flag)
+
+
+def race_stats_laps_dev(desc, sample, t, xcurv, laps, ws, car_s0=None, car_v=None, car_ey=None, n_opp=None, car_dims=None, xt=None, flag=None,
+                        lap_length=None):
+    """crx_race_stats_laps_dev: race_stats_dev with car b folded by lap_length[b] ([batch] float64 on the device; desc.lap_length is not
+    used): the cars of a launch on tracks of their own."""
+    if lap_length is None:
+        raise ValueError("race_stats_laps_dev: lap_length [batch] is required (race_stats_dev takes the descriptor's one lap length)")
+    _chk(lap_length, torch.float64, (ws.batch,), "lap_length")
+    return _race_stats("crx_race_stats_laps_dev", (_ptr(lap_length),), desc, sample, t, xcurv, laps, ws, car_s0, car_v, car_ey, n_opp, car_dims, xt,
+                       flag)
+
+
+def _race_stats(entry, lap_args, desc, sample, t, xcurv, laps, ws, car_s0, car_v, car_ey, n_opp, car_dims, xt, flag):
+    """race_stats_dev / race_stats_laps_dev: lap_args is what the entry takes between t and xcurv."""
     Bn, V = _stats_ws(desc, ws, laps), desc.n_opp_max
     _chk(xcurv, torch.float64, (Bn, 6), "xcurv")
     for name, a in (("car_s0", car_s0), ("car_v", car_v), ("car_ey", car_ey)):
@@ -734,7 +772,7 @@ def race_stats_dev(desc, sample, t, xcurv, laps, ws, car_s0=None, car_v=None, ca
         _chk(car_dims, torch.float64, (Bn // max(desc.n_cars, 1), max(desc.n_cars, 1), 2), "car_dims")
     if xt is not None:
         _chk(xt, torch.float64, (Bn, 6), "xt")
-    _call("crx_race_stats_dev", C.byref(desc), Bn, int(sample), float(t), _ptr(xcurv), _ptr(laps), _ptr(car_s0), _ptr(car_v), _ptr(car_ey),
+    _call(entry, C.byref(desc), Bn, int(sample), float(t), *lap_args, _ptr(xcurv), _ptr(laps), _ptr(car_s0), _ptr(car_v), _ptr(car_ey),
           _ptr(n_opp), _ptr(car_dims), _ptr(xt), _ptr(flag), _ptr(ws.stat_i), _ptr(ws.stat_d), _stream())
     return ws
 
@@ -798,6 +836,31 @@ class TrackSetDev:
             raise ValueError("track_id: values outside [0, %d)" % self.n_tracks)
         self.track_id = tid.to(dtype=torch.int32, device=dev).contiguous()
         self.car_lap = self.lap_length[self.track_id.long()].contiguous()
+
+
+class RaceTrackSetDev(TrackSetDev):
+    """A track set on a device with one track per RACE of n_cars cars, for the field families: race_track [R] int32, host array or tensor.
+    track_id [R * n_cars] = race_track.repeat_interleave(n_cars) is what the plant's `tracks` wrappers take (all cars of a race share its
+    track), car_lap [R * n_cars] the cars' own lap lengths (race_stats_laps_dev).  Ids are checked here, once, on the host side; the kernels
+    give a race whose id is out of range non-finite predictions and no obstacles."""
+
+    def __init__(self, tracks, race_track, n_cars, device):
+        rt = race_track if torch.is_tensor(race_track) else torch.as_tensor(race_track)
+        if rt.dim() != 1 or rt.dtype.is_floating_point or rt.dtype == torch.bool:
+            raise ValueError("race_track: expected an integer [R] array, got %s %s" % (rt.dtype, tuple(rt.shape)))
+        if rt.numel() and (int(rt.min()) < 0 or int(rt.max()) >= tracks.n_tracks):
+            raise ValueError("race_track: values outside [0, %d)" % tracks.n_tracks)
+        rt = rt.to(dtype=torch.int32, device=torch.device(device)).contiguous()
+        super().__init__(tracks, rt.repeat_interleave(int(n_cars)), device)
+        self.race_track, self.n_cars = rt, int(n_cars)
+
+
+def _chk_race_track_set(ts, R):
+    _chk(ts.tracks, torch.float64, (ts.n_tracks, ts.seg_stride, 6), "tracks")
+    _chk(ts.n_seg, torch.int32, (ts.n_tracks,), "n_seg")
+    _chk(ts.lap_length, torch.float64, (ts.n_tracks,), "lap_length")
+    _chk(ts.race_track, torch.int32, (R,), "race_track")
+    return C.c_int(ts.n_tracks), C.c_int(ts.seg_stride), _ptr(ts.tracks), _ptr(ts.n_seg), _ptr(ts.lap_length), _ptr(ts.race_track)
 
 
 def _chk_track_set(ts, Bn):

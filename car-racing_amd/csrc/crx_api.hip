@@ -1036,8 +1036,9 @@ int crx_plant_step_params_plain_dev(const crx_plant_desc* d, int batch, const do
 
 // ---- one track per car: a track set behind the plant (crx_plant_tracks_kernel), one lap length per race behind the MPC-CBF prep ----
 // host_*: the arrays of the host-pointer entry (NULL: on the device, where they cannot be read)
+// `batch` ids, one per car (track_id) or, with per_race, one per race (race_track: the field families)
 static int check_track_set(int batch, int n_tracks, int seg_stride, arr n_seg, arr lap_length, arr track_id, const int32_t* host_n_seg = nullptr,
-                           const double* host_lap = nullptr, const int32_t* host_id = nullptr) {
+                           const double* host_lap = nullptr, const int32_t* host_id = nullptr, bool per_race = false) {
     if (n_tracks < 1 || n_tracks > CRX_MAX_TRACKS) return fail(CRX_ERR_ARG, "n_tracks=%d outside [1,%d]", n_tracks, CRX_MAX_TRACKS);
     if (seg_stride < 1 || seg_stride > CRX_PLANT_MAX_SEG) return fail(CRX_ERR_ARG, "seg_stride=%d outside [1,%d]", seg_stride, CRX_PLANT_MAX_SEG);
     if (batch > 0 && any_null(n_seg, lap_length, track_id)) return fail(CRX_ERR_ARG, "NULL array argument");
@@ -1046,7 +1047,8 @@ static int check_track_set(int batch, int n_tracks, int seg_stride, arr n_seg, a
     for (int t = 0; host_lap && t < n_tracks; t++)
         if (!(host_lap[t] > 0.0) || !isfinite(host_lap[t])) return fail(CRX_ERR_ARG, "lap_length of track %d must be positive and finite", t);
     for (int b = 0; host_id && b < batch; b++)
-        if (host_id[b] < 0 || host_id[b] >= n_tracks) return fail(CRX_ERR_ARG, "track_id of car %d: %d outside [0,%d)", b, host_id[b], n_tracks);
+        if (host_id[b] < 0 || host_id[b] >= n_tracks)
+            return fail(CRX_ERR_ARG, "%s %d: %d outside [0,%d)", per_race ? "race_track of race" : "track_id of car", b, host_id[b], n_tracks);
     return 0;
 }
 
@@ -1198,6 +1200,59 @@ int crx_field_prep(const crx_field_desc* d, int n_races, const double* track, co
     return sg.down(g_stream);
 }
 
+// ---- field races and mixed fields on one track per RACE (crx_field_prep_tracks_kernel, crx_mixed_prep_tracks_kernel, crx_prep.hip) ----------
+// The set's own arrays are read at any race count by the host-pointer entries, as crx_plant_step_tracks reads them
+static int check_race_tracks_host(int n_races, int n_tracks, int seg_stride, const int32_t* n_seg, const double* lap_length, const int32_t* race_track) {
+    if (n_tracks >= 1 && n_tracks <= CRX_MAX_TRACKS && any_null(n_seg, lap_length)) return fail(CRX_ERR_ARG, "NULL array argument");
+    return check_track_set(n_races, n_tracks, seg_stride, n_seg, lap_length, race_track, n_seg, lap_length, n_races > 0 ? race_track : nullptr, true);
+}
+static crx_race_tracks race_tracks_of(int n_tracks, int seg_stride, const int32_t* n_seg, const double* lap_length, const int32_t* race_track) {
+    crx_race_tracks set;
+    set.n_tracks = n_tracks; set.seg_stride = seg_stride; set.n_seg = n_seg; set.race_track = race_track; set.lap_length = lap_length;
+    return set;
+}
+
+int crx_field_prep_tracks_dev(const crx_field_desc* d, int n_races, int n_tracks, int seg_stride, const double* tracks, const int32_t* n_seg,
+                              const double* lap_length, const int32_t* race_track, const double* xcurv, const double* car_dims, double* pred_s,
+                              double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims, double* clear,
+                              void* stream) {
+    crx_field_kparams_tracks fp;
+    if (int rc = check_field(fp, d, n_races, tracks, xcurv, car_dims, pred_s, pred_ey, obs_s, obs_ey, lap_off, n_obs, obs_dims)) return rc;
+    if (int rc = check_track_set(n_races, n_tracks, seg_stride, n_seg, lap_length, race_track)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (n_races == 0) return CRX_OK;
+    fp.track = tracks; fp.xcurv = xcurv; fp.car_dims = car_dims; fp.pred_s = pred_s; fp.pred_ey = pred_ey;
+    fp.nlp = {obs_s, obs_ey, lap_off, n_obs, d->n_cars > 1 ? obs_dims : nullptr, clear};
+    fp.set = race_tracks_of(n_tracks, seg_stride, n_seg, lap_length, race_track);
+    return launched(crx_launch_field_prep_tracks(fp, (hipStream_t)stream), "field prep (track set)");
+}
+
+int crx_field_prep_tracks(const crx_field_desc* d, int n_races, int n_tracks, int seg_stride, const double* tracks, const int32_t* n_seg,
+                          const double* lap_length, const int32_t* race_track, const double* xcurv, const double* car_dims, double* pred_s,
+                          double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims, double* clear) {
+    crx_field_kparams_tracks chk;
+    if (int rc = check_field(chk, d, n_races, tracks, xcurv, car_dims, pred_s, pred_ey, obs_s, obs_ey, lap_off, n_obs, obs_dims, car_dims)) return rc;
+    if (int rc = check_race_tracks_host(n_races, n_tracks, seg_stride, n_seg, lap_length, race_track)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (n_races == 0) return CRX_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    const size_t RC = (size_t)n_races * d->n_cars, V = (size_t)d->n_cars - 1, N1 = (size_t)d->N + 1;
+    Stage sg;
+    auto dtr = sg.in(tracks, (size_t)n_tracks * seg_stride * 6); auto dns = sg.in(n_seg, (size_t)n_tracks); auto dll = sg.in(lap_length, (size_t)n_tracks);
+    auto drt = sg.in(race_track, (size_t)n_races); auto dx = sg.in(xcurv, RC * 6);
+    auto dcd = car_dims ? sg.in(car_dims, RC * 2) : Stage::Ref<double>{};   // unused: sg[dcd] is NULL
+    auto dps = sg.out(pred_s, RC * N1); auto dpe = sg.out(pred_ey, RC * N1);
+    auto dos = sg.out(obs_s, RC * V * N1); auto doe = sg.out(obs_ey, RC * V * N1); auto dlo = sg.out(lap_off, RC * V);
+    auto dno = sg.out(n_obs, RC);
+    auto dod = obs_dims ? sg.out(obs_dims, RC * V * 2) : Stage::Ref<double>{};
+    auto dcl = clear ? sg.out(clear, RC) : Stage::Ref<double>{};
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_field_prep_tracks_dev(d, n_races, n_tracks, seg_stride, sg[dtr], sg[dns], sg[dll], sg[drt], sg[dx], sg[dcd], sg[dps], sg[dpe],
+                                           sg[dos], sg[doe], sg[dlo], sg[dno], sg[dod], sg[dcl], g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
 // ---- field games: the racing game's traffic arrays of a field (crx_field_traffic_kernel, crx_prep.hip) ------------------------------------
 static_assert(CRX_MAX_VEH == CRX_MAX_OBS, "check_field_desc bounds n_cars by CRX_MAX_OBS + 1; the scene takes CRX_MAX_VEH vehicles");
 static int check_field_traffic(crx_field_traffic_kparams& tp, const crx_field_desc* d, int n_races, arr track, arr xcurv, arr pred_s_car,
@@ -1310,6 +1365,58 @@ int crx_mixed_prep(const crx_mixed_desc* d, int n_races, const double* track, co
     if (int rc = sg.up(g_stream)) return rc;
     if (int rc = crx_mixed_prep_dev(d, n_races, sg[dtr], sg[dx], sg[dpo], sg[dcd], sg[dps], sg[dpe], sg[dos], sg[doe], sg[dlo], sg[dno], sg[dod],
                                     sg[dmn], sg[dis], sg[die], sg[dil], sg[din], sg[dmi], sg[dcl], g_stream)) return rc;
+    return sg.down(g_stream);
+}
+
+int crx_mixed_prep_tracks_dev(const crx_mixed_desc* d, int n_races, int n_tracks, int seg_stride, const double* tracks, const int32_t* n_seg,
+                              const double* lap_length, const int32_t* race_track, const double* xcurv, const int32_t* policy,
+                              const double* car_dims, double* pred_s, double* pred_ey, double* obs_s, double* obs_ey, double* lap_off,
+                              int32_t* n_obs, double* obs_dims, int32_t* m_nlp, double* il_obs_s, double* il_obs_ey, double* il_lap_off,
+                              int32_t* il_n_obs, int32_t* m_ilqr, double* clear, void* stream) {
+    crx_mixed_kparams_tracks mp;
+    if (int rc = check_mixed(mp, d, n_races, tracks, xcurv, policy, car_dims, pred_s, pred_ey, obs_s, obs_ey, lap_off, n_obs, obs_dims, m_nlp,
+                             il_obs_s, il_obs_ey, il_lap_off, il_n_obs, m_ilqr)) return rc;
+    if (int rc = check_track_set(n_races, n_tracks, seg_stride, n_seg, lap_length, race_track)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (n_races == 0) return CRX_OK;
+    mp.track = tracks; mp.xcurv = xcurv; mp.policy = policy; mp.car_dims = car_dims; mp.pred_s = pred_s; mp.pred_ey = pred_ey;
+    mp.nlp = {obs_s, obs_ey, lap_off, n_obs, d->n_cars > 1 ? obs_dims : nullptr, clear}; mp.m_nlp = m_nlp;
+    mp.il_obs_s = il_obs_s; mp.il_obs_ey = il_obs_ey; mp.il_lap_off = il_lap_off; mp.il_n_obs = il_n_obs; mp.m_ilqr = m_ilqr;
+    mp.set = race_tracks_of(n_tracks, seg_stride, n_seg, lap_length, race_track);
+    return launched(crx_launch_mixed_prep_tracks(mp, (hipStream_t)stream), "mixed prep (track set)");
+}
+
+int crx_mixed_prep_tracks(const crx_mixed_desc* d, int n_races, int n_tracks, int seg_stride, const double* tracks, const int32_t* n_seg,
+                          const double* lap_length, const int32_t* race_track, const double* xcurv, const int32_t* policy, const double* car_dims,
+                          double* pred_s, double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims,
+                          int32_t* m_nlp, double* il_obs_s, double* il_obs_ey, double* il_lap_off, int32_t* il_n_obs, int32_t* m_ilqr,
+                          double* clear) {
+    crx_mixed_kparams_tracks chk;
+    if (int rc = check_mixed(chk, d, n_races, tracks, xcurv, policy, car_dims, pred_s, pred_ey, obs_s, obs_ey, lap_off, n_obs, obs_dims, m_nlp,
+                             il_obs_s, il_obs_ey, il_lap_off, il_n_obs, m_ilqr, car_dims, n_races > 0 ? policy : nullptr)) return rc;
+    if (int rc = check_race_tracks_host(n_races, n_tracks, seg_stride, n_seg, lap_length, race_track)) return rc;
+    if (int rc = ensure_init()) return rc;
+    if (n_races == 0) return CRX_OK;
+    std::lock_guard<std::mutex> lk(g_mu);
+    HIP_TRY(hipSetDevice(g_device));
+    const size_t RC = (size_t)n_races * d->n_cars, V = (size_t)d->n_cars - 1, N1 = (size_t)d->N + 1, NI1 = (size_t)d->N_ilqr + 1;
+    const size_t NP1 = N1 > NI1 ? N1 : NI1, il = d->N_ilqr > 0 ? 1 : 0;   // il = 0: the iLQR family is not staged (the kernel leaves it alone)
+    Stage sg;
+    auto dtr = sg.in(tracks, (size_t)n_tracks * seg_stride * 6); auto dns = sg.in(n_seg, (size_t)n_tracks); auto dll = sg.in(lap_length, (size_t)n_tracks);
+    auto drt = sg.in(race_track, (size_t)n_races); auto dx = sg.in(xcurv, RC * 6); auto dpo = sg.in(policy, RC);
+    auto dcd = car_dims ? sg.in(car_dims, RC * 2) : Stage::Ref<double>{};   // unused: sg[dcd] is NULL
+    auto dps = sg.out(pred_s, RC * NP1); auto dpe = sg.out(pred_ey, RC * NP1);
+    auto dos = sg.out(obs_s, RC * V * N1); auto doe = sg.out(obs_ey, RC * V * N1); auto dlo = sg.out(lap_off, RC * V);
+    auto dno = sg.out(n_obs, RC); auto dmn = sg.out(m_nlp, RC);
+    auto dod = obs_dims ? sg.out(obs_dims, RC * V * 2) : Stage::Ref<double>{};
+    auto dis = il ? sg.out(il_obs_s, RC * V * NI1) : Stage::Ref<double>{}; auto die = il ? sg.out(il_obs_ey, RC * V * NI1) : Stage::Ref<double>{};
+    auto dil = il ? sg.out(il_lap_off, RC * V) : Stage::Ref<double>{};
+    auto din = il ? sg.out(il_n_obs, RC) : Stage::Ref<int32_t>{}; auto dmi = il ? sg.out(m_ilqr, RC) : Stage::Ref<int32_t>{};
+    auto dcl = clear ? sg.out(clear, RC) : Stage::Ref<double>{};
+    if (int rc = sg.up(g_stream)) return rc;
+    if (int rc = crx_mixed_prep_tracks_dev(d, n_races, n_tracks, seg_stride, sg[dtr], sg[dns], sg[dll], sg[drt], sg[dx], sg[dpo], sg[dcd], sg[dps],
+                                           sg[dpe], sg[dos], sg[doe], sg[dlo], sg[dno], sg[dod], sg[dmn], sg[dis], sg[die], sg[dil], sg[din],
+                                           sg[dmi], sg[dcl], g_stream)) return rc;
     return sg.down(g_stream);
 }
 
@@ -2261,6 +2368,19 @@ int crx_race_stats_dev(const crx_stats_desc* d, int batch, int sample, double t,
     sp.sample = sample; sp.t = t; sp.xcurv = xcurv; sp.laps = laps; sp.car_s0 = car_s0; sp.car_v = car_v; sp.car_ey = car_ey; sp.n_opp = n_opp;
     sp.car_dims = car_dims; sp.xt = xt; sp.flag = flag; sp.stat_i = stat_i; sp.stat_d = stat_d;
     return launched(crx_launch_race_stats(1, sp, (hipStream_t)stream), "race stats");
+}
+
+int crx_race_stats_laps_dev(const crx_stats_desc* d, int batch, int sample, double t, const double* lap_length, const double* xcurv,
+                            const int32_t* laps, const double* car_s0, const double* car_v, const double* car_ey, const int32_t* n_opp,
+                            const double* car_dims, const double* xt, const int32_t* flag, int32_t* stat_i, double* stat_d, void* stream) {
+    crx_stats_kparams_laps sp;
+    if (int rc = check_stats(sp, 1, d, batch, stat_i, stat_d, laps, xcurv, car_s0, car_v, car_ey, n_opp, car_dims)) return rc;
+    if (batch > 0 && !lap_length) return fail(CRX_ERR_ARG, "NULL array argument");
+    if (int rc = ensure_init()) return rc;
+    if (batch == 0) return CRX_OK;
+    sp.sample = sample; sp.t = t; sp.xcurv = xcurv; sp.laps = laps; sp.car_s0 = car_s0; sp.car_v = car_v; sp.car_ey = car_ey; sp.n_opp = n_opp;
+    sp.car_dims = car_dims; sp.xt = xt; sp.flag = flag; sp.stat_i = stat_i; sp.stat_d = stat_d; sp.lap_lengths = lap_length;
+    return launched(crx_launch_race_stats_laps(sp, (hipStream_t)stream), "race stats (per-car lap lengths)");
 }
 
 int crx_race_stats_summary_dev(const crx_stats_desc* d, int batch, const int32_t* group, int n_groups, const int32_t* stat_i,

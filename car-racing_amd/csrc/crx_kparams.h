@@ -161,6 +161,21 @@ struct crx_mixed_kparams {
     int32_t *il_n_obs, *m_ilqr;
 };
 
+// One track per RACE (crx_field_prep_tracks_kernel, crx_mixed_prep_tracks_kernel; crx_prep.hip): the track set of crx_plant_kparams_tracks with the
+// id per race.  `track` of the base is the set's tracks [n_tracks][seg_stride][6]; d.n_seg and d.lap_length of the base are unused.
+struct crx_race_tracks {
+    int n_tracks, seg_stride;            // n_tracks in [1, CRX_MAX_TRACKS], seg_stride in [1, CRX_PLANT_MAX_SEG]
+    const int32_t *n_seg, *race_track;   // [n_tracks], [n_races]
+    const double* lap_length;            // [n_tracks]
+};
+// Derived, so that crx_field_kparams and crx_mixed_kparams -- which the one-track kernels take by value -- keep their size.
+struct crx_field_kparams_tracks : crx_field_kparams {
+    crx_race_tracks set;
+};
+struct crx_mixed_kparams_tracks : crx_mixed_kparams {
+    crx_race_tracks set;
+};
+
 // ---- crx_path.hip: crx_path_kernel, the path QP (crx_path_qp.h) without a mask ----
 struct crx_path_kparams {
     int N, batch;
@@ -253,6 +268,8 @@ hipError_t crx_launch_cbfprep_laps(const crx_cbfprep_kparams_laps& cp, hipStream
 hipError_t crx_launch_field_prep(const crx_field_kparams& fp, hipStream_t st);
 hipError_t crx_launch_field_traffic(const crx_field_traffic_kparams& tp, hipStream_t st);
 hipError_t crx_launch_mixed_prep(const crx_mixed_kparams& mp, hipStream_t st);
+hipError_t crx_launch_field_prep_tracks(const crx_field_kparams_tracks& fp, hipStream_t st);
+hipError_t crx_launch_mixed_prep_tracks(const crx_mixed_kparams_tracks& mp, hipStream_t st);
 // crx_plant.hip
 hipError_t crx_launch_plant(const crx_plant_kparams& pk, hipStream_t st);
 hipError_t crx_launch_plant_cars(const crx_plant_kparams_cars& pk, hipStream_t st);
@@ -342,6 +359,11 @@ struct crx_stats_kparams {
     double* sum_d;                                     //          [n_groups][CRX_STATS_SUM_ND]
 };
 hipError_t crx_launch_race_stats(int which, const crx_stats_kparams& sp, hipStream_t st);   // 0 reset, 1 one sample, 2 summary
+// crx_race_stats_laps_kernel.  Derived, so that crx_stats_kparams -- which the three kernels above take by value -- keeps its size.
+struct crx_stats_kparams_laps : crx_stats_kparams {
+    const double* lap_lengths;                         // [batch]: car b's own lap length; d.lap_length is unused
+};
+hipError_t crx_launch_race_stats_laps(const crx_stats_kparams_laps& sp, hipStream_t st);   // one sample
 // crx_lmpc.hip, crx_lmpcprep.hip
 hipError_t crx_launch_lmpc(const crx_lmpc_kparams& kp, hipStream_t st);
 hipError_t crx_launch_lmpcprep(const crx_lmpcprep_kparams& kp, hipStream_t st);

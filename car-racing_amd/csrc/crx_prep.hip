@@ -17,6 +17,8 @@
 //                               planning/overtake_traj_planner.py:77-85
 //     crx_mixed_prep_kernel     every car under its own controller: the NLP family for the MPC-CBF cars, the iLQR family's arrays for the iLQR
 //                               cars (control/control.py:99-104), and the masks of both launches
+//     crx_field_prep_tracks_kernel, crx_mixed_prep_tracks_kernel   the two with race r on track race_track[r] of a track set; the mixed kernel's
+//                               text is crx_mixed_prep.h, included once per track source
 // The comment in front of each kernel has the rest.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -264,7 +266,7 @@ __global__ void __launch_bounds__(256) crx_cbfprep_laps_kernel(const crx_cbfprep
 }
 
 // ------------------------------------------------------------------------------------------------
-// The FIELD family: crx_field_prep_kernel, crx_field_traffic_kernel, crx_mixed_prep_kernel.  n_races races of C = n_cars driven cars, every
+// The FIELD family: crx_field_prep_kernel, crx_field_traffic_kernel, crx_mixed_prep_kernel (and the two `tracks` kernels).  n_races races of C = n_cars driven cars, every
 // car an ego and one of the V = C - 1 others of the egos of its race (see "Field races", "Field games", "Mixed fields" in include/crx.h).
 // What the three share stands here, once.
 //   block shape   one thread per (race, car); a workgroup of 256 threads owns 256 / C WHOLE races, so what a car reads of the others was
@@ -422,66 +424,107 @@ __global__ void __launch_bounds__(256) crx_field_traffic_kernel(const crx_field_
     block_gather<2, false>(b, C, N1, N1, p_src, p_dst, others);
 }
 
-// The solver inputs of a mixed field (crx_mixed_prep_dev, quirks F1-F3, F6, M1, M2): every car of a race under its own policy, so one launch
-// prepares the NLP family for the MPC-CBF cars, the iLQR family's arrays for the iLQR cars (control/control.py:99-104), and the two masks the
-// solver launches run under.
-//   phase 1  the roll-out runs max(N, N_ilqr) + 1 steps.  Before the barrier each ego also decides, from the INPUTS alone (policies,
-//            finiteness of the states), which cars its iLQR slots hold, and leaves that in LDS (il_src: a car index, or -1) -- so the one
-//            barrier that publishes the roll-outs publishes the slot map too.
-//   phase 2  per ego: nlp_ego_pass (an ego that is not MPCCBF keeps nobody); the iLQR family's lap offsets and counts; then the wide iLQR
-//            rows by block_gather, each slot's source looked up in il_src.
-// Policy codes are compared, never used as an index.
-__global__ void __launch_bounds__(256) crx_mixed_prep_kernel(const crx_mixed_kparams mp) {
-    __shared__ double seg_lo[CRX_PLANT_MAX_SEG], seg_hi[CRX_PLANT_MAX_SEG], seg_cv[CRX_PLANT_MAX_SEG];
-    __shared__ signed char il_src[256 * CRX_MAX_OBS];   // [ego of the block][slot]: the car of the ego's race in that slot, -1: empty
-    const crx_mixed_desc& d = mp.d;
-    load_seg_tables(mp.track, d.n_seg, seg_lo, seg_hi, seg_cv);
-    const int C = d.n_cars, V = C - 1, N1 = d.N + 1, NI1 = d.N_ilqr + 1, NP1 = max(d.N, d.N_ilqr) + 1;
-    const field_block b = field_block_of(C, mp.n_races);
-    const int t = b.t, c = b.c;
-    const size_t rc = b.rc;
-    const bool ilqr_on = d.N_ilqr > 0;
-    const double L = d.lap_length;
-    int pol = CRX_POLICY_NONE;
-    bool fin_e = true;
-    if (b.live) {
-        zero_input_rollout(mp.xcurv + 6 * rc, seg_lo, seg_hi, seg_cv, d.n_seg, L, d.dt, NP1, mp.pred_s + rc * NP1, mp.pred_ey + rc * NP1);
-        pol = mp.policy[rc];
-        for (int k = 0; k < 6; k++) fin_e = fin_e && isfinite(mp.xcurv[6 * rc + k]);
-        if (ilqr_on) {   // the slot map of this ego: the finite other cars in car order (all of them, or the last one alone: quirk I1)
-            const bool il_e = pol == CRX_POLICY_ILQR && fin_e;
-            const int o_last = c == C - 1 ? C - 2 : C - 1;
-            int n = 0;
-            for (int o = 0; o < C; o++) {
-                if (o == c) continue;
-                bool fin_o = true;
-                for (int k = 0; k < 6; k++) fin_o = fin_o && isfinite(mp.xcurv[6 * (rc - c + o) + k]);
-                if (il_e && fin_o && (d.ilqr_obstacles != 0 || o == o_last)) il_src[t * V + n++] = (signed char)o;
-            }
-            for (int v = n; v < V; v++) il_src[t * V + v] = -1;
-        }
-    }
-    __syncthreads();   // the predictions and the slot maps of this block's races are written; workgroup scope is all phase 2 needs
-    if (!b.live) return;
-    const bool cbf = pol == CRX_POLICY_MPCCBF;
-    nlp_ego_pass(mp.xcurv, mp.car_dims, mp.pred_s, mp.pred_ey, NP1, L, d.safety_time, d.l_sum, d.w_sum, d.degree, N1, C, c, rc, cbf, mp.nlp);
-    mp.m_nlp[rc] = (pol == CRX_POLICY_MPC_LTI || cbf) ? 1 : 0;
-    if (!ilqr_on) return;
-    // the iLQR family: lap offsets (quirk I5: the obstacle's cycle from column 0 of its roll-out) and the count, from this ego's slot map
-    const double s_e = mp.xcurv[6 * rc + 4];
-    int ni = 0;
-    for (int v = 0; v < V; v++) {
-        const int o = il_src[t * V + v];
-        double off = 0.0;
-        if (o >= 0) { off = (trunc(s_e / L) - trunc(mp.pred_s[(rc - c + o) * NP1] / L)) * L; ni++; }
-        mp.il_lap_off[rc * V + v] = off;
-    }
-    mp.il_n_obs[rc] = ni;
-    mp.m_ilqr[rc] = pol == CRX_POLICY_ILQR ? 1 : 0;
-    const double* const i_src[2] = {mp.pred_s, mp.pred_ey};
-    double* const i_dst[2] = {mp.il_obs_s, mp.il_obs_ey};
-    block_gather<2, true>(b, C, NI1, NP1, i_src, i_dst, [&](int q, int v) { return (int)il_src[q * V + v]; });
+// ---- one track per RACE (crx_field_prep_tracks_dev, crx_mixed_prep_tracks_dev): a race is on one track and all its cars share it; the races of
+// a launch, and of a block, may be on different tracks.  The block stages all n_tracks * seg_stride rows, padding included, at their own index
+// (load_seg_tables over the whole set: crx_plant_tracks_kernel's staging, 12 KB at most); a lane scans the rows of its race's track and
+// wraps, folds, windows, lap-offsets and `clear`s with that track's lap length.  What lives on the device cannot be validated on the host:
+// race_track[r] is COMPARED before any use and never becomes an address -- a race whose id is outside [0, n_tracks) has no track (ok ==
+// false): every car of it writes NaN prediction rows, keeps nobody (n_obs = 0, zero slots, lap_off = 0), its `clear` is NaN, and it still
+// takes the block's barrier; n_seg[t] is clamped to [0, seg_stride], so the scan stays inside the track's own rows whatever the array holds.
+struct race_track {
+    bool ok;
+    int row0, n_seg;   // the track's first row in the block's tables and its rows
+    double L;
+};
+__device__ __forceinline__ race_track race_track_of(const crx_race_tracks& set, const field_block& b, int C) {
+    race_track k = {false, 0, 0, 1.0};   // (a lap length the folds of a race without a track are harmless with)
+    if (!b.live) return k;
+    const int t = set.race_track[b.rc / C];
+    if (t < 0 || t >= set.n_tracks) return k;
+    k.ok = true;
+    k.row0 = t * set.seg_stride; k.n_seg = min(max(set.n_seg[t], 0), set.seg_stride);
+    k.L = set.lap_length[t];
+    return k;
 }
+__device__ __forceinline__ void nan_rows(int n, double* ps, double* pe) {
+    for (int j = 0; j < n; j++) { ps[j] = NAN; pe[j] = NAN; }
+}
+
+// crx_field_prep_kernel with race r on track race_track[r]: the same two phases, the same pieces.
+__global__ void __launch_bounds__(256) crx_field_prep_tracks_kernel(const crx_field_kparams_tracks fp) {
+    __shared__ double seg_lo[CRX_MAX_TRACKS * CRX_PLANT_MAX_SEG], seg_hi[CRX_MAX_TRACKS * CRX_PLANT_MAX_SEG], seg_cv[CRX_MAX_TRACKS * CRX_PLANT_MAX_SEG];
+    const crx_field_desc& d = fp.d;
+    load_seg_tables(fp.track, fp.set.n_tracks * fp.set.seg_stride, seg_lo, seg_hi, seg_cv);
+    const int N1 = d.N + 1;
+    const field_block b = field_block_of(d.n_cars, fp.n_races);
+    const race_track k = race_track_of(fp.set, b, d.n_cars);
+    if (b.live) {
+        if (!k.ok) nan_rows(N1, fp.pred_s + b.rc * N1, fp.pred_ey + b.rc * N1);
+        else
+            zero_input_rollout(fp.xcurv + 6 * b.rc, seg_lo + k.row0, seg_hi + k.row0, seg_cv + k.row0, k.n_seg, k.L, d.dt, N1, fp.pred_s + b.rc * N1,
+                               fp.pred_ey + b.rc * N1);
+    }
+    __syncthreads();   // the predictions of this block's races are in memory; workgroup scope is all phase 2 needs
+    if (!b.live) return;
+    nlp_ego_pass(fp.xcurv, fp.car_dims, fp.pred_s, fp.pred_ey, N1, k.L, d.safety_time, d.l_sum, d.w_sum, d.degree, N1, d.n_cars, b.c, b.rc, k.ok,
+                 fp.nlp);
+    if (!k.ok && fp.nlp.clear) fp.nlp.clear[b.rc] = NAN;
+}
+
+// crx_mixed_prep_kernel and crx_mixed_prep_tracks_kernel: the kernel's text is crx_mixed_prep.h, included once per track source.
+#define CRX_MIXED_KERNEL crx_mixed_prep_kernel
+#define CRX_MIXED_KPARAMS crx_mixed_kparams
+#define CRX_MIXED_TABLES(mp)                                                                              \
+    __shared__ double seg_lo[CRX_PLANT_MAX_SEG], seg_hi[CRX_PLANT_MAX_SEG], seg_cv[CRX_PLANT_MAX_SEG];    \
+    __shared__ signed char il_src[256 * CRX_MAX_OBS];   /* [ego of the block][slot]: the car of the ego's race in that slot, -1: empty */ \
+    const crx_mixed_desc& d = mp.d;                                                                       \
+    load_seg_tables(mp.track, d.n_seg, seg_lo, seg_hi, seg_cv);
+#define CRX_MIXED_READ_TRACK(mp, b)
+#define CRX_MIXED_LAP d.lap_length
+#define CRX_MIXED_SEG(a) a
+#define CRX_MIXED_NSEG d.n_seg
+#define CRX_MIXED_UNLESS_NO_TRACK(mp, rc, n)
+#define CRX_MIXED_POLICY(mp, rc) mp.policy[rc]
+#define CRX_MIXED_NO_TRACK_CLEAR(mp, rc)
+#include "crx_mixed_prep.h"
+#undef CRX_MIXED_KERNEL
+#undef CRX_MIXED_KPARAMS
+#undef CRX_MIXED_TABLES
+#undef CRX_MIXED_READ_TRACK
+#undef CRX_MIXED_LAP
+#undef CRX_MIXED_SEG
+#undef CRX_MIXED_NSEG
+#undef CRX_MIXED_UNLESS_NO_TRACK
+#undef CRX_MIXED_POLICY
+#undef CRX_MIXED_NO_TRACK_CLEAR
+
+// A race without a track (race_track_of): its egos' policy reads as NONE, so m_nlp = m_ilqr = 0, il_n_obs = 0 and every iLQR slot is a hole --
+// no solver runs for it.
+#define CRX_MIXED_KERNEL crx_mixed_prep_tracks_kernel
+#define CRX_MIXED_KPARAMS crx_mixed_kparams_tracks
+#define CRX_MIXED_TABLES(mp)                                                                                                                      \
+    __shared__ double seg_lo[CRX_MAX_TRACKS * CRX_PLANT_MAX_SEG], seg_hi[CRX_MAX_TRACKS * CRX_PLANT_MAX_SEG], seg_cv[CRX_MAX_TRACKS * CRX_PLANT_MAX_SEG]; \
+    __shared__ signed char il_src[256 * CRX_MAX_OBS];                                                                                             \
+    const crx_mixed_desc& d = mp.d;                                                                                                               \
+    load_seg_tables(mp.track, mp.set.n_tracks * mp.set.seg_stride, seg_lo, seg_hi, seg_cv);
+#define CRX_MIXED_READ_TRACK(mp, b) const race_track k = race_track_of(mp.set, b, C);
+#define CRX_MIXED_LAP k.L
+#define CRX_MIXED_SEG(a) a + k.row0
+#define CRX_MIXED_NSEG k.n_seg
+#define CRX_MIXED_UNLESS_NO_TRACK(mp, rc, n) if (!k.ok) nan_rows(n, mp.pred_s + rc * n, mp.pred_ey + rc * n); else
+#define CRX_MIXED_POLICY(mp, rc) (k.ok ? mp.policy[rc] : CRX_POLICY_NONE)
+#define CRX_MIXED_NO_TRACK_CLEAR(mp, rc) if (!k.ok && mp.nlp.clear) mp.nlp.clear[rc] = NAN;
+#include "crx_mixed_prep.h"
+#undef CRX_MIXED_KERNEL
+#undef CRX_MIXED_KPARAMS
+#undef CRX_MIXED_TABLES
+#undef CRX_MIXED_READ_TRACK
+#undef CRX_MIXED_LAP
+#undef CRX_MIXED_SEG
+#undef CRX_MIXED_NSEG
+#undef CRX_MIXED_UNLESS_NO_TRACK
+#undef CRX_MIXED_POLICY
+#undef CRX_MIXED_NO_TRACK_CLEAR
 
 hipError_t crx_launch_prep(const crx_prep_kparams& pp, hipStream_t st) { return crx_launch_1d(crx_prep_kernel, pp.n_scen, 1, WAVE, st, pp); }
 hipError_t crx_launch_scene(const crx_scene_kparams& sp, hipStream_t st) { return crx_launch_1d(crx_scene_kernel, sp.n_scen, 1, WAVE, st, sp); }
@@ -503,4 +546,11 @@ hipError_t crx_launch_field_traffic(const crx_field_traffic_kparams& tp, hipStre
 // the same shape (n_cars in 1 .. CRX_MAX_OBS + 1, checked by the caller)
 hipError_t crx_launch_mixed_prep(const crx_mixed_kparams& mp, hipStream_t st) {
     return crx_launch_1d(crx_mixed_prep_kernel, mp.n_races, 256 / mp.d.n_cars, 256, st, mp);
+}
+// the same shapes with one track per race (n_tracks, seg_stride inside the LDS tables' bounds, checked by the caller)
+hipError_t crx_launch_field_prep_tracks(const crx_field_kparams_tracks& fp, hipStream_t st) {
+    return crx_launch_1d(crx_field_prep_tracks_kernel, fp.n_races, 256 / fp.d.n_cars, 256, st, fp);
+}
+hipError_t crx_launch_mixed_prep_tracks(const crx_mixed_kparams_tracks& mp, hipStream_t st) {
+    return crx_launch_1d(crx_mixed_prep_tracks_kernel, mp.n_races, 256 / mp.d.n_cars, 256, st, mp);
 }

@@ -44,7 +44,9 @@
 extern "C" {
 #endif
 
-#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_plant_step_tracks, crx_plant_step_tracks_dev, crx_plant_step_tracks_plain_dev,
+#define CRX_VERSION 400 /* 0.4.0 (additive, same number): crx_field_prep_tracks, crx_field_prep_tracks_dev, crx_mixed_prep_tracks, crx_mixed_prep_tracks_dev,
+                          crx_race_stats_laps_dev (field races and mixed fields on one track per race) -- new entry points only.
+                          0.4.0 (additive, same number): crx_plant_step_tracks, crx_plant_step_tracks_dev, crx_plant_step_tracks_plain_dev,
                           crx_cbf_prep_laps_dev and CRX_MAX_TRACKS (one track per vehicle: a track set in the plant, one lap length per race in the
                           MPC-CBF prep) -- new entry points only.
                           0.4.0 (additive, same number): crx_mixed_desc, crx_mixed_desc_default, crx_mixed_prep, crx_mixed_prep_dev, crx_mixed_commit_dev and
@@ -895,6 +897,25 @@ int crx_field_prep(const crx_field_desc* d, int n_races, const double* track, co
 int crx_field_prep_dev(const crx_field_desc* d, int n_races, const double* track, const double* xcurv, const double* car_dims, double* pred_s,
                        double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims, double* clear,
                        void* stream);
+/*
+ * Field races on ONE TRACK PER RACE: a race is on one track and all its cars share it; the races of a launch may be on different tracks.
+ * crx_field_prep_tracks[_dev] is crx_field_prep[_dev] with a track set in place of `track`: tracks, n_seg, lap_length as the plant's
+ * (crx_plant_step_tracks_dev, same limits) and the id PER RACE, race_track [n_races] (int32).  Race r is rolled out over table
+ * race_track[r], and wrapped, folded, windowed, lap-offset and `clear`-ed with lap_length[race_track[r]].  d->n_seg and d->lap_length are
+ * not used, but the descriptor must still be a valid one.  The rows of the races that name track t are the bits of crx_field_prep_dev on
+ * table t over those races, wherever they stand in the launch.  For the plant the cars' ids are race_track[r] repeated n_cars times.
+ * The host-pointer entry reads its arrays and refuses (CRX_ERR_ARG, the first offender in crx_last_error()) a race_track outside
+ * [0, n_tracks), an n_seg[t] outside [1, seg_stride] and a lap length that is not positive and finite.  The `_dev` entry cannot read device
+ * memory: the id is compared, never used as an address -- every car of a race whose id is outside [0, n_tracks) gets NaN prediction rows,
+ * n_obs = 0, zero slots, lap_off = 0 and clear = NaN, and touches no other race; an n_seg[t] is clamped to [0, seg_stride].
+ */
+int crx_field_prep_tracks(const crx_field_desc* d, int n_races, int n_tracks, int seg_stride, const double* tracks, const int32_t* n_seg,
+                          const double* lap_length, const int32_t* race_track, const double* xcurv, const double* car_dims, double* pred_s,
+                          double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims, double* clear);
+int crx_field_prep_tracks_dev(const crx_field_desc* d, int n_races, int n_tracks, int seg_stride, const double* tracks, const int32_t* n_seg,
+                              const double* lap_length, const int32_t* race_track, const double* xcurv, const double* car_dims, double* pred_s,
+                              double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims, double* clear,
+                              void* stream);
 
 /*
  * Field games: the traffic arrays of the racing game (LMPCRacingGame.calc_input: learning MPC, overtake planner + tracking NLP when a car
@@ -993,6 +1014,22 @@ int crx_mixed_prep_dev(const crx_mixed_desc* d, int n_races, const double* track
                        const double* car_dims, double* pred_s, double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs,
                        double* obs_dims, int32_t* m_nlp, double* il_obs_s, double* il_obs_ey, double* il_lap_off, int32_t* il_n_obs,
                        int32_t* m_ilqr, double* clear, void* stream);
+/*
+ * Mixed fields on one track per race: crx_mixed_prep[_dev] with the track set and race_track [n_races] of crx_field_prep_tracks[_dev], same
+ * rules; the iLQR family's il_lap_off (quirk I5) is computed with the race's own lap length too.  A race whose id is outside [0, n_tracks)
+ * (`_dev` entry) gets, besides the rows stated there, m_nlp = m_ilqr = 0, il_n_obs = 0, il_lap_off = 0 and zero iLQR slots: no solver runs
+ * for it.
+ */
+int crx_mixed_prep_tracks(const crx_mixed_desc* d, int n_races, int n_tracks, int seg_stride, const double* tracks, const int32_t* n_seg,
+                          const double* lap_length, const int32_t* race_track, const double* xcurv, const int32_t* policy, const double* car_dims,
+                          double* pred_s, double* pred_ey, double* obs_s, double* obs_ey, double* lap_off, int32_t* n_obs, double* obs_dims,
+                          int32_t* m_nlp, double* il_obs_s, double* il_obs_ey, double* il_lap_off, int32_t* il_n_obs, int32_t* m_ilqr,
+                          double* clear);
+int crx_mixed_prep_tracks_dev(const crx_mixed_desc* d, int n_races, int n_tracks, int seg_stride, const double* tracks, const int32_t* n_seg,
+                              const double* lap_length, const int32_t* race_track, const double* xcurv, const int32_t* policy,
+                              const double* car_dims, double* pred_s, double* pred_ey, double* obs_s, double* obs_ey, double* lap_off,
+                              int32_t* n_obs, double* obs_dims, int32_t* m_nlp, double* il_obs_s, double* il_obs_ey, double* il_lap_off,
+                              int32_t* il_n_obs, int32_t* m_ilqr, double* clear, void* stream);
 /*
  * crx_mixed_commit_dev: after the solver launches, before the plant: u [batch][2] and ctrl_status [batch] from each car's own law, every
  * operation rounded on its own (no fused multiply-add).  x [batch][6] is the state the step starts from.
@@ -1409,6 +1446,12 @@ int crx_race_stats_dev(const crx_stats_desc* d, int batch, int sample, double t,
                        const double* car_s0, const double* car_v, const double* car_ey, const int32_t* n_opp,
                        const double* car_dims, const double* xt, const int32_t* flag, int32_t* stat_i, double* stat_d,
                        void* stream);
+/* crx_race_stats_dev with one lap length per car, lap_length [batch] on the device (the cars of a launch on tracks of their own), field mode
+ * and scripted mode alike; d->lap_length is not used but must be valid.  A car whose lap length is not positive and finite is counted as a
+ * non-finite row.  Reset and summary read no lap length: they serve both. */
+int crx_race_stats_laps_dev(const crx_stats_desc* d, int batch, int sample, double t, const double* lap_length, const double* xcurv,
+                            const int32_t* laps, const double* car_s0, const double* car_v, const double* car_ey, const int32_t* n_opp,
+                            const double* car_dims, const double* xt, const int32_t* flag, int32_t* stat_i, double* stat_d, void* stream);
 int crx_race_stats_summary_dev(const crx_stats_desc* d, int batch, const int32_t* group, int n_groups, const int32_t* stat_i,
                                const double* stat_d, int64_t* sum_i, double* sum_d, void* stream);
 int crx_race_stats_reset(const crx_stats_desc* d, int batch, const int32_t* laps, int32_t* stat_i, double* stat_d);

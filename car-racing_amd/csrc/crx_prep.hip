@@ -62,7 +62,9 @@ __global__ void __launch_bounds__(WAVE) crx_prep_kernel(const crx_prep_kparams p
         pp.bez_ey[o] = e0 * b0 + e12 * b1 + e12 * b2 + e3 * b3;
     }
     // ey bounds (:277-324): both neighbours impose ey >= ey_obs + W + margin inside their s-window (quirk Q2)
-    const double ub = tw - 0.5 * vw, win = pp.veh_length + pp.safety_margin;
+    // The window's ends are formed as the reference forms them, os - length - margin and os + length + margin (:297, :300): with the
+    // two widths summed first, an ego one ulp outside an end is taken for inside (0.5 + 0.15 rounds up; tests/golden/front_edges.npz).
+    const double ub = tw - 0.5 * vw;
     for (int e = lane; e < R * N; e += WAVE) {
         const int r = e / N, k = e - r * N;
         const double s_nom = xw[4] + (k * pp.dt_ref) * xw[0];                                   // :296 (wrapped copy, Q5)
@@ -72,7 +74,7 @@ __global__ void __launch_bounds__(WAVE) crx_prep_kernel(const crx_prep_kparams p
             if (v < 0 || v >= nv) continue;
             double os = pp.obs_s[((size_t)s * V + v) * (N + 1) + k];
             os = wrap_above(os, L);                                                             // :291-292
-            if (s_nom >= os - win && s_nom <= os + win)
+            if (s_nom >= os - pp.veh_length - pp.safety_margin && s_nom <= os + pp.veh_length + pp.safety_margin)
                 lb = fmax(lb, pp.obs_ey[((size_t)s * V + v) * (N + 1) + k] + vw + pp.safety_margin);
         }
         pp.ey_lb[((size_t)s * R + r) * N + k] = lb;

@@ -197,6 +197,19 @@ template <int NOBS, int NMAX> constexpr bool CbfCarry = (CRX_CBF_CARRY) != 0 && 
 #endif
 template <int NOBS, int NMAX> constexpr bool DistCarry = (CRX_DIST_CARRY) != 0 && CbfCarry<NOBS, NMAX>;
 template <int NOBS, int NMAX> constexpr bool DnuCarry = (CRX_DNU_CARRY) != 0 && Obs1Tuned<NOBS, NMAX>;   // (the rows fit into Kk: static_assert in the kernel)
+// [r22] The one-wave kernels of the same reach take the decisions of the LINE SEARCH, which every lane takes alike, as scalar branches (A/B builds:
+// make EXTRA=-DCRX_UNIFORM_CTRL=0 is the parent's code, byte for byte; every other instantiation compiles what it compiled before):
+//   CRX_UNIFORM_CTRL  thn, phin, theta, Dphi and al are wave reductions or formed from them, but they live in VGPRs: to the compiler the backtracking
+//                     loop, `if (okf)`, the switching / Armijo / sufficient-decrease tests and `if (acc) break` are divergent -- EXEC save, branch
+//                     on EXEC = 0 and EXEC restore per region, the loop EXEC-masked.  Each of these conditions goes through wave_uniform
+//                     (crx_wave.h); acc, ftype and the loop are scalar behind them.  A lone wave pays an issue slot for every instruction
+//                     (DESIGN.md 5.1).  No floating-point operation is added, removed or reordered: same bits, tests/test_gpu_uniform_ctrl_bits.py.
+//                     The other uniform decisions of the iteration (barrier update, step-length guards, termination, jam / stall rules, the
+//                     pivot verdicts of the sweep) were tried the same way and grew their phases: HISTORY.md, round 22.
+#ifndef CRX_UNIFORM_CTRL
+#define CRX_UNIFORM_CTRL 1
+#endif
+template <int NOBS, int NMAX> constexpr bool UniformCtrl = (CRX_UNIFORM_CTRL) != 0 && Obs1Tuned<NOBS, NMAX>;
 // end of a stage of an UNROLLED sweep [r4]: without it the scheduler lifts the loads of all later stages to the top of the sweep and the
 // registers they occupy are paid for in scratch (a wave writes its spills once: 100 B per lane were x8 the algorithmic bytes written of a cfg2 launch)
 #define STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -1841,6 +1854,9 @@ crx_solve_kernel(const crx_solve_params kp) {
     // the register allocator of this toolchain crashes on <1,12,6,12, SPEC = 1>.  They keep the evaluations -- same bits: tests/test_gpu_obs1_carry_bits.py)
     constexpr bool DISTC = NFIX != 0 && QPM == 0 && SPEC == 0 && DistCarry<NOBS, NMAX>;
     constexpr bool DNUC = NFIX != 0 && QPM == 0 && SPEC == 0 && DnuCarry<NOBS, NMAX>;
+    // [r22] ... and take the wave-uniform decisions of the interior-point loop as scalar branches (UniformCtrl; the one-wave kernels only, as above)
+    constexpr bool UC = NFIX != 0 && QPM == 0 && SPEC == 0 && UniformCtrl<NOBS, NMAX>;
+#define UNI(b) wave_uniform_if<UC>(b)   /* a decision every lane takes alike, all 64 active: crx_wave.h, contract of wave_uniform */
     static_assert(!DNUC || (!L::SLIM && L::MR <= NMAX * L::KS && L::G != L::Kk), "dnu of every row inside Kk, and nothing else lives there between the sweeps");
     constexpr int RPASS = (L::MR + WAVE - 1) / WAVE, CPASS = (L::NV + WAVE - 1) / WAVE;
     static_assert(LF == 0 || !L::SLIM, "the loads-first row passes are written for the full layout (row_scale, row_bound, row_sig_w are loads there)");
@@ -2698,12 +2714,13 @@ crx_solve_kernel(const crx_solve_params kp) {
         double dist_tr[4] = {0.0, 0.0, 0.0, 0.0};   // DISTC: ... and the four distances (dsc, dec, dsn, den) that value was formed from, for first_order
         int acc = 0, ftype = 0;
         // switching condition al * (-Dphi)^2.3 > theta^1.1 (only consulted when theta <= theta_min)
-        const bool sw_try = (theta <= theta_min) && (Dphi < 0.0);
+        bool sw_try = (theta <= theta_min) && (Dphi < 0.0);
+        if constexpr (UC) sw_try = wave_uniform(sw_try);
         // ... compared in the log2 domain: log2(al) + 2.3 log2(-Dphi) > 1.1 log2(theta), with log2_fast (double exponent +
         // v_log_f32 of the mantissa, ~1e-7 absolute).  Two pow() calls were ~2.6 k cycles of this iteration and kept ~50
         // VGPRs of polynomial constants alive; the test is a heuristic threshold, a tie within 1e-7 may fall either way.
         const double sw_gap = sw_try ? IPM_S_PHI * log2_fast(-Dphi) - IPM_S_THETA * log2_fast(theta) : 0.0;
-        for (int ls = 0; ls < IPM_MAX_BACKTRACK && al >= IPM_ALPHA_MIN; ls++) {   // alpha_min: see crx_ipm.h
+        for (int ls = 0; ls < IPM_MAX_BACKTRACK && UNI(al >= IPM_ALPHA_MIN); ls++) {   // alpha_min: see crx_ipm.h
             fn = f + al * (cost_d + al * cost_qq);   // exact: the cost is quadratic along the step
             double thn = 0.0;
             LogAcc lg;
@@ -2748,19 +2765,24 @@ crx_solve_kernel(const crx_solve_params kp) {
             lt_acc = lg.wave_total_with(thn);                         // thn and the exponent sum share one reduction
             const double phin = fn - mu * lt_acc;
             int okf = (thn <= theta_max) && (phin == phin);
+            if constexpr (UC) okf = wave_uniform(okf != 0);
             {   // filter (nf <= MAXF < WAVE entries: one pass, lanes past nf read entry 0 and are masked)
                 const bool iv = lane < nf;
                 const int i = iv ? lane : 0;
                 const double fth = LD(L::Fth + i), fph = LD(L::Fph + i);
                 if (__any(iv && !(thn < fth || phin < fph))) okf = 0;
             }
-            if (okf) {
-                if (sw_try && log2_fast(al) + sw_gap > 0.0) {
-                    if (phin <= phi0 + IPM_ETA_PHI * al * Dphi + 10.0 * IPM_EPS * fabs(phi0)) { acc = 1; ftype = 1; }   // Armijo: crx_ipm.h, table
-                } else if (ipm_sufficient_decrease(theta, thn, phi0, phin)) {
-                    acc = 1;
-                }
+            // (the acceptance rules, stated once; U: what a condition goes through -- nothing, or wave_uniform [r22])
+#define TRIAL_DECIDE(U) \
+            if (okf) { \
+                if (sw_try && U(log2_fast(al) + sw_gap > 0.0)) { \
+                    if (U(phin <= phi0 + IPM_ETA_PHI * al * Dphi + 10.0 * IPM_EPS * fabs(phi0))) { acc = 1; ftype = 1; }   /* Armijo: crx_ipm.h, table */ \
+                } else if (U(ipm_sufficient_decrease(theta, thn, phi0, phin))) { \
+                    acc = 1; \
+                } \
             }
+#define TRIAL_PLAIN(b) b
+            if constexpr (UC) { TRIAL_DECIDE(wave_uniform) } else { TRIAL_DECIDE(TRIAL_PLAIN) }
             if (acc) break;
             al *= 0.5;
         }

@@ -81,6 +81,25 @@ __device__ __forceinline__ double lane_f64(double v, int l) {
 // that neither the producer of x nor a copy the register allocator may insert can sit closer than that; and acc is an EARLY-CLOBBER operand
 // (+&v): were it given the register of x (same value at entry, as in `acc = row_dot(acc_old, m, acc_old)`), the second term would read through
 // DPP what the first has just written -- the same hazard inside the statement (seen: 87 % of a 4096-problem batch lost).  EXEC covers the lanes read.
+// [r22] A decision that every lane takes alike, handed to the compiler AS uniform.  Wave reductions, broadcast LDS reads and results of readlane live
+// in VGPRs, so to the compiler `if (thn <= theta_max)` is divergent: it saves EXEC, branches on EXEC = 0, restores EXEC at the join and merges what the
+// arms left different with v_cndmask pairs.  Through v_readfirstlane the condition is an SGPR, the branch a scalar one with no EXEC
+// traffic, and a loop on it is a scalar loop.  The value is not changed, only where it lives.  (`ballot(b) != 0` says the same and compiles to fewer
+// instructions -- v_cmp into an SGPR pair, s_cmp_lg_u64 -- but measured a third of the gain on the one kernel that uses this: HISTORY.md, round 22.)
+// CONTRACT of wave_uniform:
+//   (a) every ACTIVE lane passes the same value -- the result is lane FIRST-ACTIVE's, and a lane that disagreed would follow it silently;
+//   (b) all 64 lanes are active at the call: it stands in control flow that is itself uniform, behind the reconvergence point of any lane loop;
+//   (c) never inside an `if (lane == ..)` / `if (lane < ..)` region: there (a) holds trivially and the result is wrong for every lane outside.
+__device__ __forceinline__ bool wave_uniform(bool b) { return __builtin_amdgcn_readfirstlane((int)b) != 0; }
+// the same behind a compile-time switch, for a condition in VALUE context (a loop condition's last operand, an initialiser).  NOT for `if (a && b)`:
+// as an argument the condition is evaluated into one value first, where the plain `if` branches operand by operand, and the instantiations with
+// the switch off then compile to other code than before (seen on the 2- and 3-obstacle kernels) -- state such a decision twice, under `if constexpr`
+template <bool ON>
+__device__ __forceinline__ bool wave_uniform_if(bool b) {
+    if constexpr (ON) return wave_uniform(b);
+    else return b;
+}
+
 #define CRX_DPPT(i) "v_fmac_f64_dpp %0, %1, %" #i " row_newbcast:%"
 #define CRX_DPPE " row_mask:0xf bank_mask:0xf\n\t"
 template <int CNT, int FIRST>

@@ -135,7 +135,9 @@ __device__ __forceinline__ double ipow_d(double a, int p) {
 #define ROWS(j, jv, lane_, m_) _Pragma("unroll") for (int q_ = 0; q_ < (L::MR + WAVE - 1) / WAVE; q_++) \
     if (const bool jv = (lane_) + q_ * WAVE < (m_); true) if (const int j = jv ? (lane_) + q_ * WAVE : 0; true)
 
-#define COORDS(e, ev, lane_, n_) _Pragma("unroll") for (int q_ = 0; q_ < (L::NV + WAVE - 1) / WAVE; q_++) \
+#define COORDS(e, ev, lane_, n_) COORDS_P(e, ev, lane_, n_, (L::NV + WAVE - 1) / WAVE)
+// (P_ passes instead of the layout's: [r24], a caller that knows its horizon at compile time)
+#define COORDS_P(e, ev, lane_, n_, P_) _Pragma("unroll") for (int q_ = 0; q_ < (P_); q_++) \
     if (const bool ev = (lane_) + q_ * WAVE < (n_); true) if (const int e = ev ? (lane_) + q_ * WAVE : 0; true)
 
 #define SINK(cond, off) seli((cond), (off), L::dmy)
@@ -210,6 +212,24 @@ template <int NOBS, int NMAX> constexpr bool DnuCarry = (CRX_DNU_CARRY) != 0 && 
 #define CRX_UNIFORM_CTRL 1
 #endif
 template <int NOBS, int NMAX> constexpr bool UniformCtrl = (CRX_UNIFORM_CTRL) != 0 && Obs1Tuned<NOBS, NMAX>;
+// [r24] The one-wave kernels of DistCarry's reach run the COORDINATE passes of the Newton assembly and of the first_order call that ends the accept
+// step differently, one bit of the switch each (A/B builds: make EXTRA=-DCRX_ASM_CARRY=0 is the parent's code, byte for byte, =1 / =2 one part alone;
+// every other instantiation compiles what it compiled before):
+//   CRX_ASM_CARRY  1  assemble_newton's coordinate pass loads first, like its row pass and first_order's coordinate pass [r8]: the row-of-coordinate
+//                     table entries of every pass, then the loads that need none, then Sigma and w of the bound rows, LOADS_DONE(), then arithmetic
+//                     and stores pass by pass -- same expressions, same store order
+//                  2  both coordinate passes run ceil((NFIX NZ + NX) / 64) = 2 passes over the lanes, not the layout's ceil(NV / 64) = 3.  No lane of
+//                     the third pass owns a coordinate (127 of them at N = 12, 107 at N = 10), but the stores of Hd and of ga are not
+//                     address-predicated, so the compiler kept the whole pass to store entry 0 once more -- from the operands of pass 0 (Hd does not
+//                     read ga, and ga[0] is rebuilt from the same Z and multipliers), so with its bits: 44 + 24 instructions per iteration
+//                     for nothing (profiles/r24_census.txt)
+//                     Same bits: tests/test_gpu_asm_carry_bits.py.  (The name is the round's: what it set out to carry from accept into the assembly,
+//                     and why that stayed out: HISTORY.md, round 24.)
+#ifndef CRX_ASM_CARRY
+#define CRX_ASM_CARRY 3
+#endif
+enum : unsigned { ASMC_LOADS_FIRST = 1, ASMC_PASSES = 2 };
+template <int NOBS, int NMAX> constexpr unsigned AsmCarry = DistCarry<NOBS, NMAX> ? (unsigned)(CRX_ASM_CARRY) : 0u;
 // end of a stage of an UNROLLED sweep [r4]: without it the scheduler lifts the loads of all later stages to the top of the sweep and the
 // registers they occupy are paid for in scratch (a wave writes its spills once: 100 B per lane were x8 the algorithmic bytes written of a cfg2 launch)
 #define STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -583,7 +603,8 @@ __device__ __forceinline__ void eval_rows(double* sm, const int* si, const Ctx& 
 // coordinates) and the Lagrangian gradient ga = grad f - J' nu per stage coordinate.
 // (DC [r21], DistCarry: the caller -- the accept step -- hands in the four distances of this lane's CBF row as the accepted trial formed them, at
 // the point that is now the iterate; one pass, the row of a lane is the same in both places.)
-template <int NOBS, int NMAX, unsigned LF = 0, bool DC = false>
+// (CP [r24], AsmCarry: the loads-first coordinate pass runs CP passes over the lanes -- the caller's horizon needs no more; 0: the layout's count.)
+template <int NOBS, int NMAX, unsigned LF = 0, bool DC = false, int CP = 0>
 __device__ __forceinline__ void first_order(double* sm, const int* si, const Ctx& c, double dsc_tr = 0.0, double dec_tr = 0.0, double dsn_tr = 0.0,
                                             double den_tr = 0.0) {
     using L = Lay<NOBS, NMAX>;
@@ -671,13 +692,13 @@ __device__ __forceinline__ void first_order(double* sm, const int* si, const Ctx
     } while (0)
     if constexpr ((LF & LF_FIRST_ORDER) != 0) {   // [r8] both passes load, then both compute
         static_assert(NOBS > 0, "written for the obstacle instantiations");
-        constexpr int CPASS = (L::NV + WAVE - 1) / WAVE;
+        constexpr int CPASS = CP ? CP : (L::NV + WAVE - 1) / WAVE;
         int rl[CPASS], rh[CPASS];
         double cw[CPASS], xrv[CPASS], ze[CPASS], nl[CPASS], nh[CPASS], nuv[CPASS][NOBS], jv2[CPASS][NOBS];
         // the row-of-coordinate table entries first, the multipliers they point to last: the entries are back by the time the loads between have been issued
-        COORDS(e, ev, c.lane, N * L::NZ + L::NX) { (void)ev; const int k = e / L::NZ, a = e - k * L::NZ; coord_rows<L>(si, c, e, k, a, rl[q_], rh[q_]); }
+        COORDS_P(e, ev, c.lane, N * L::NZ + L::NX, CPASS) { (void)ev; const int k = e / L::NZ, a = e - k * L::NZ; coord_rows<L>(si, c, e, k, a, rl[q_], rh[q_]); }
         __builtin_amdgcn_sched_barrier(0);
-        COORDS(e, ev, c.lane, N * L::NZ + L::NX) {
+        COORDS_P(e, ev, c.lane, N * L::NZ + L::NX, CPASS) {
             (void)ev;
             const int k = e / L::NZ, a = e - k * L::NZ, kk = k < N ? k : N - 1;
             const bool isx = a < 6, isu = a >= L::NX && a < L::NX + 2;
@@ -689,7 +710,7 @@ __device__ __forceinline__ void first_order(double* sm, const int* si, const Ctx
 #pragma unroll
         for (int q_ = 0; q_ < CPASS; q_++) { nl[q_] = FO_NU(rl[q_]); nh[q_] = FO_NU(rh[q_]); }
         LOADS_DONE();
-        COORDS(e, ev, c.lane, N * L::NZ + L::NX) {
+        COORDS_P(e, ev, c.lane, N * L::NZ + L::NX, CPASS) {
             (void)ev;
             FO_GRADIENT(cw[q_], xrv[q_], ze[q_], rl[q_], rh[q_], nl[q_], nh[q_], nuv[q_][ob], jv2[q_][ob], (void)0);
         }
@@ -810,7 +831,8 @@ __device__ __forceinline__ double box_certificate(double* sm, const int* si, con
 //   per coord Hd = cost diag + Sigma of its bound rows + "current" CBF curvature,
 //             hg = ga (reduced form) + J'w
 //   per stage kS,kE = "next" CBF curvature  (- nu d hess g_{k+1}), added to P[4][4], P[5][5]
-template <int NOBS, int NMAX, unsigned LF = 0>
+// (CP, CLF [r24], AsmCarry: the coordinate pass runs CP passes over the lanes -- the caller's horizon needs no more; 0: the layout's count -- and loads first.)
+template <int NOBS, int NMAX, unsigned LF = 0, int CP = 0, bool CLF = false>
 __device__ __forceinline__ void assemble_newton(double* sm, const int* si, const Ctx& c, double mu) {
     using L = Lay<NOBS, NMAX>;
     const int N = c.N;
@@ -846,49 +868,94 @@ __device__ __forceinline__ void assemble_newton(double* sm, const int* si, const
         ASM_ROW(t, nu, ASM_RS, ASM_CJ);
     }
     SYNC();
-    COORDS(e, ev, c.lane, N * L::NZ + L::NX) {   // stage N has states only (127 entries at N=12, 1 obstacle: two passes, not three)
-        const int k = e / L::NZ, a = e - k * L::NZ;
-        const bool isx = a < 6, isu = a >= L::NX && a < L::NX + 2, iss0 = a >= 6 && a < L::NX, iss1 = a >= L::NX + 2;
-        const int o = iss0 ? a - 6 : (iss1 ? a - L::NX - 2 : 0);
-        double g = LD(L::ga + e);
-        const double cw = LD(L::cst + (isx ? a : (isu ? 6 + a - L::NX : 0)));
-        double h = sel(isx || isu, 2.0 * cw, 0.0);
-        // absent obstacle: pin its sigma_0 (state copy at k = 0) and sigma_{k+1} (input copy)
-        h += ((iss0 && k == 0 && o >= c.nobs) || (iss1 && o >= c.nobs)) ? 1.0 : 0.0;
-        int rl, rh;
-        coord_rows<L>(si, c, e, k, a, rl, rh);
-        const int il = rl >= 0 ? rl : 0, ih = rh >= 0 ? rh : 0;
-        double sgl, sgh, wl, wh;
-        if constexpr (L::SLIM) {   // a row found by coord_rows is present
-            sgl = LD(L::rnu + il) * LD(L::rtt + il); wl = LD(L::rdt + il);
-            sgh = LD(L::rnu + ih) * LD(L::rtt + ih); wh = LD(L::rdt + ih);
-        } else {
-            sgl = LD(L::rsig + il); sgh = LD(L::rsig + ih); wl = LD(L::rw + il); wh = LD(L::rw + ih);
-        }
-        h += sel(rl >= 0, sgl, 0.0) + sel(rh >= 0, sgh, 0.0);
-        g += sel(rl >= 0, wl, 0.0) - sel(rh >= 0, wh, 0.0);
-        if (NOBS) {
-            const int kk = k < N ? k : N - 1;
+    // The coordinate pass, stated once: the operands of coordinate e (ASM_*: loads, each on a clamped index; il, ih, kk, j, ob are the names of
+    // ASM_COORD's own text) and the arithmetic with its two stores (ASM_COORD).  ASM_COORD takes the full layout's operands as expressions and reads
+    // each once, where the plain form has always loaded it: the plain form passes the loads themselves (the last arguments: the statements that yield
+    // rl, rh and w of the CBF row), the loads-first form what it loaded before.  The slim layout's operands are recomputed inside, as they always were.
+#define ASM_GA LD(L::ga + e)
+#define ASM_CW LD(L::cst + (isx ? a : (isu ? 6 + a - L::NX : 0)))
+#define ASM_SIG(i) LD(L::rsig + (i))
+#define ASM_W(i) LD(L::rw + (i))
+#define ASM_CSC cbf_scale<L>(sm, kk, ob)
+#define ASM_JCA LD(L::Jc + (kk * L::NO + ob) * L::NZ + a)
+#define ASM_CBF_NU LD(L::rnu + j)
+#define ASM_CBF_G LD(L::G + (kk * L::NO + ob) * 4 + (a == 4 ? 2 : 3))
+#define ASM_COORD(ga_, cw_, rl, rh, sgl_, sgh_, wl_, wh_, csj_, jca_, nuj_, gcur_, ROWS_, RWJ_) do { \
+        const int k = e / L::NZ, a = e - k * L::NZ; \
+        const bool isx = a < 6, isu = a >= L::NX && a < L::NX + 2, iss0 = a >= 6 && a < L::NX, iss1 = a >= L::NX + 2; \
+        const int o = iss0 ? a - 6 : (iss1 ? a - L::NX - 2 : 0); \
+        double g = ga_; \
+        const double cw = cw_; \
+        double h = sel(isx || isu, 2.0 * cw, 0.0); \
+        /* absent obstacle: pin its sigma_0 (state copy at k = 0) and sigma_{k+1} (input copy) */ \
+        h += ((iss0 && k == 0 && o >= c.nobs) || (iss1 && o >= c.nobs)) ? 1.0 : 0.0; \
+        ROWS_; \
+        const int il = rl >= 0 ? rl : 0, ih = rh >= 0 ? rh : 0; \
+        double sgl, sgh, wl, wh; \
+        if constexpr (L::SLIM) {   /* a row found by coord_rows is present */ \
+            sgl = LD(L::rnu + il) * LD(L::rtt + il); wl = LD(L::rdt + il); \
+            sgh = LD(L::rnu + ih) * LD(L::rtt + ih); wh = LD(L::rdt + ih); \
+        } else { \
+            sgl = sgl_; sgh = sgh_; wl = wl_; wh = wh_; \
+        } \
+        h += sel(rl >= 0, sgl, 0.0) + sel(rh >= 0, sgh, 0.0); \
+        g += sel(rl >= 0, wl, 0.0) - sel(rh >= 0, wh, 0.0); \
+        if (NOBS) { \
+            const int kk = k < N ? k : N - 1; \
+            _Pragma("unroll") for (int ob = 0; ob < NOBS; ob++) { \
+                const int j = kk * L::NR + 8 + NOBS + ob; \
+                const double csj = csj_; \
+                const double jca = jca_; \
+                double rsj_, rwj; \
+                if constexpr (L::SLIM) { \
+                    rwj = LD(L::rdt + j); \
+                } else { \
+                    RWJ_; \
+                    (void)rsj_; \
+                } \
+                g += sel(k < N, jca * rwj, 0.0); \
+                const double cur = nuj_ * csj * c.om * gcur_; \
+                h += sel(k < N && (a == 4 || a == 5), cur, 0.0); \
+            } \
+        } \
+        const bool tail = k == N && a >= L::NX; \
+        LD(L::Hd + e) = sel(tail, 0.0, h); \
+        LD(SINK(ev, L::hg + e)) = sel(tail, 0.0, g);   /* in place over ga: read-modify-write */ \
+    } while (0)
+    constexpr int CPASS = CP ? CP : (L::NV + WAVE - 1) / WAVE;
+    if constexpr (CLF) {   // [r24] every pass loads, then every pass computes: the schedule of first_order's coordinate pass [r8]
+        static_assert(NOBS > 0 && !L::SLIM && (LF & LF_ASSEMBLE) != 0, "written for the full layout of the loads-first obstacle instantiations");
+        int rl[CPASS], rh[CPASS];
+        double gav[CPASS], cwv[CPASS], sglv[CPASS], sghv[CPASS], wlv[CPASS], whv[CPASS], csv[CPASS][NOBS], jcv[CPASS][NOBS], rwv[CPASS][NOBS], nuv[CPASS][NOBS], gcv[CPASS][NOBS];
+        // the row-of-coordinate table entries first, Sigma and w of the rows they point to last: the entries are back by the time the loads between have been issued
+        COORDS_P(e, ev, c.lane, N * L::NZ + L::NX, CPASS) { (void)ev; const int k = e / L::NZ, a = e - k * L::NZ; coord_rows<L>(si, c, e, k, a, rl[q_], rh[q_]); }
+        __builtin_amdgcn_sched_barrier(0);
+        COORDS_P(e, ev, c.lane, N * L::NZ + L::NX, CPASS) {
+            (void)ev;
+            const int k = e / L::NZ, a = e - k * L::NZ, kk = k < N ? k : N - 1;
+            const bool isx = a < 6, isu = a >= L::NX && a < L::NX + 2;
+            gav[q_] = ASM_GA; cwv[q_] = ASM_CW;
 #pragma unroll
             for (int ob = 0; ob < NOBS; ob++) {
                 const int j = kk * L::NR + 8 + NOBS + ob;
-                const double csj = cbf_scale<L>(sm, kk, ob);
-                const double jca = LD(L::Jc + (kk * L::NO + ob) * L::NZ + a);
-                double rsj_, rwj;
-                if constexpr (L::SLIM) {
-                    rwj = LD(L::rdt + j);
-                } else {
-                    row_sig_w<L>(sm, j, csj != 0.0, mu, LD(L::rt + j), LD(L::rnu + j), LD(L::rtt + j), LD(L::rc + j), rsj_, rwj);
-                    (void)rsj_;
-                }
-                g += sel(k < N, jca * rwj, 0.0);
-                const double cur = LD(L::rnu + j) * csj * c.om * LD(L::G + (kk * L::NO + ob) * 4 + (a == 4 ? 2 : 3));
-                h += sel(k < N && (a == 4 || a == 5), cur, 0.0);
+                csv[q_][ob] = ASM_CSC; jcv[q_][ob] = ASM_JCA; rwv[q_][ob] = ASM_W(j); nuv[q_][ob] = ASM_CBF_NU; gcv[q_][ob] = ASM_CBF_G;
             }
         }
-        const bool tail = k == N && a >= L::NX;
-        LD(L::Hd + e) = sel(tail, 0.0, h);
-        LD(SINK(ev, L::hg + e)) = sel(tail, 0.0, g);   // in place over ga: read-modify-write
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q_ = 0; q_ < CPASS; q_++) {
+            const int il = rl[q_] >= 0 ? rl[q_] : 0, ih = rh[q_] >= 0 ? rh[q_] : 0;
+            sglv[q_] = ASM_SIG(il); sghv[q_] = ASM_SIG(ih); wlv[q_] = ASM_W(il); whv[q_] = ASM_W(ih);
+        }
+        LOADS_DONE();
+        COORDS_P(e, ev, c.lane, N * L::NZ + L::NX, CPASS) {
+            ASM_COORD(gav[q_], cwv[q_], rl[q_], rh[q_], sglv[q_], sghv[q_], wlv[q_], whv[q_], csv[q_][ob], jcv[q_][ob], nuv[q_][ob], gcv[q_][ob], (void)0, rwj = rwv[q_][ob]);
+        }
+    } else
+    COORDS_P(e, ev, c.lane, N * L::NZ + L::NX, CPASS) {   // stage N has states only (127 entries at N=12, 1 obstacle: two passes own a coordinate; CP = 0 runs the layout's three)
+        int rl, rh;
+        ASM_COORD(ASM_GA, ASM_CW, rl, rh, ASM_SIG(il), ASM_SIG(ih), ASM_W(il), ASM_W(ih), ASM_CSC, ASM_JCA, ASM_CBF_NU, ASM_CBF_G, coord_rows<L>(si, c, e, k, a, rl, rh),
+                  row_sig_w<L>(sm, j, csj != 0.0, mu, LD(L::rt + j), LD(L::rnu + j), LD(L::rtt + j), LD(L::rc + j), rsj_, rwj));
     }
     if (NOBS) {
         const int k = c.lane < N ? c.lane : 0;          // N <= 24 < WAVE: one pass; lanes past N recompute stage 0
@@ -1856,6 +1923,10 @@ crx_solve_kernel(const crx_solve_params kp) {
     constexpr bool DNUC = NFIX != 0 && QPM == 0 && SPEC == 0 && DnuCarry<NOBS, NMAX>;
     // [r22] ... and take the wave-uniform decisions of the interior-point loop as scalar branches (UniformCtrl; the one-wave kernels only, as above)
     constexpr bool UC = NFIX != 0 && QPM == 0 && SPEC == 0 && UniformCtrl<NOBS, NMAX>;
+    // [r24] ... and run the coordinate passes of the assembly and of accept's first_order over the passes their horizon needs, the assembly's loads-first
+    // (AsmCarry; the one-wave kernels only, as above).  ACP: that pass count, 0 where the parent's text stands
+    constexpr unsigned ASMC = (DISTC && (LF & LF_ASSEMBLE) != 0 && (LF & LF_FIRST_ORDER) != 0) ? AsmCarry<NOBS, NMAX> : 0u;
+    constexpr int ACP = (ASMC & ASMC_PASSES) != 0 ? (NFIX * NZ + NX + WAVE - 1) / WAVE : 0;
 #define UNI(b) wave_uniform_if<UC>(b)   /* a decision every lane takes alike, all 64 active: crx_wave.h, contract of wave_uniform */
     static_assert(!DNUC || (!L::SLIM && L::MR <= NMAX * L::KS && L::G != L::Kk), "dnu of every row inside Kk, and nothing else lives there between the sweeps");
     constexpr int RPASS = (L::MR + WAVE - 1) / WAVE, CPASS = (L::NV + WAVE - 1) / WAVE;
@@ -2531,7 +2602,7 @@ crx_solve_kernel(const crx_solve_params kp) {
         const double tau = ipm_tau(mu, o.tau_min);
         // ---- Newton step ---------------------------------------------------------------------------
         long long tc3 = CLK();
-        assemble_newton<NOBS, NMAX, LF>(sm, si, c, mu);
+        assemble_newton<NOBS, NMAX, LF, ACP, (ASMC & ASMC_LOADS_FIRST) != 0>(sm, si, c, mu);
         long long tc4 = CLK();
         // inertia correction: retry the sweep with a growing regularisation dw until every pivot is positive (one call
         // site: the sweep is inlined once)
@@ -2934,7 +3005,7 @@ crx_solve_kernel(const crx_solve_params kp) {
         }
         nus = wave_sum(nus);
         e_p = th;
-        if constexpr (DISTC) first_order<NOBS, NMAX, LF, true>(sm, si, c, dist_tr[0], dist_tr[1], dist_tr[2], dist_tr[3]);
+        if constexpr (DISTC) first_order<NOBS, NMAX, LF, true, ACP>(sm, si, c, dist_tr[0], dist_tr[1], dist_tr[2], dist_tr[3]);
         else first_order<NOBS, NMAX, LF>(sm, si, c);
         if (TRACE_ROW(it, lane) && kp.trace_rows > 0)
             kp.trace[(size_t)it * 16 + 8] = (double)(tph[0] + (CLK() - tc8));   // slot 8: KKT rows + accept/first-order

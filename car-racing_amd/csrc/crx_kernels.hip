@@ -60,7 +60,7 @@
 // CRX_OBS1_WAVES, CRX_GEN_WAVES, CRX_KERNEL_EXTRA_ATTR (section (5)), CRX_NFIX_LIST (section (7)).  Diagnostic builds: CRX_PHASE_CLOCKS.
 // The A/B switches whose verdict is in were folded into the code; HISTORY.md lists them with the record of each verdict.
 #ifndef CRX_TU_GENERAL
-#define CRX_TU_GENERAL 0   /* 1: the general build (crx_kernels_gen.hip, crx_kernels_models_gen.hip): conservative knobs below, no LoadsFirst / CbfCarry forms */
+#define CRX_TU_GENERAL 0   /* 1: the general build (crx_kernels_gen.hip, crx_kernels_models_gen.hip): conservative knobs below, the plain form (Form, below) everywhere */
 #endif
 #ifndef CRX_TU_MODELS
 #define CRX_TU_MODELS 0    /* 1: crx_kernels_models_*.hip -- the CBF NLP and the planner QP with one LTI model per problem */
@@ -154,82 +154,41 @@ __device__ __forceinline__ double ipow_d(double a, int p) {
 #define ROW_IS_CBF(j, n_) (NOBS > 0 && (j) < (n_) * NR && (j) % NR >= 8 + NOBS)
 // nothing moves across: placed after the loads of a phase so that they are issued back to back
 #define LOADS_DONE() __builtin_amdgcn_sched_barrier(0)
-// [r8] Two-pass phases of the tuned one-obstacle instantiations <1,12,6,*> (124 rows, 127 coordinates: two passes over the 64 lanes): left alone,
-// pass 1 loads only after pass 0 has stored -- the SINK-selected store addresses may alias anything -- and the lone wave sits out one more LDS
-// round trip per phase.  A phase whose bit is set here loads the operands of BOTH passes into per-pass locals, LOADS_DONE(), then computes and
-// stores pass by pass.  [r13] Both forms are made of the SAME text: each phase states its operands and its arithmetic with its stores once (macros
-// in front of the `if constexpr ((LF & LF_x) != 0)`; DESIGN.md 5.1 lists them) and the two arms keep only the schedule of the loads -- same bits:
-// tests/test_gpu_obs1_bits.py for the loads-first forms, tests/test_gpu_plain_bits.py for the plain ones.  All six
-// together measured -1 % on the headline at no cost in registers (the peak is the unrolled Riccati sweep; DESIGN.md 5.1, profiles/r08_*);
-// every other instantiation keeps the plain form.
-#ifndef CRX_LOADS_FIRST
-#define CRX_LOADS_FIRST 0x3F   /* A/B builds: make EXTRA=-DCRX_LOADS_FIRST=0 is the plain form everywhere */
-#endif
-enum : unsigned { LF_ROW_STEP = 1, LF_ROW_TRIAL = 2, LF_ROW_ACCEPT = 4, LF_ACCEPT_Z = 8, LF_FIRST_ORDER = 16, LF_ASSEMBLE = 32 };
-template <int NOBS, int NMAX> constexpr unsigned LoadsFirst = (NOBS == 1 && NMAX == 12 && !CRX_TU_GENERAL) ? (unsigned)(CRX_LOADS_FIRST) : 0u;
-// [r9] The same instantiations (the reach of LoadsFirst) stop repeating two pieces of work, each behind a switch of its own (A/B builds: make
-// EXTRA=-DCRX_RETRY_SHARED=0 / -DCRX_CBF_CARRY=0 is the parent's code; every other instantiation compiles what it compiled before):
-//   CRX_RETRY_SHARED  the attempts of the inertia-correction schedule of ONE Newton system share the set-up of riccati_backward (lane maps, the
-//                     stage-invariant model operands, the opaque lane copy): the retry loop runs inside the sweep function, behind its set-up
-//   CRX_CBF_CARRY     the accept step takes the CBF row values from the accepted line-search trial, which evaluated them at the point accept stores
-//                     (NMAX * NOBS <= 64: one pass, the row of a lane is the same in both places)
-#ifndef CRX_RETRY_SHARED
-#define CRX_RETRY_SHARED 1
-#endif
-#ifndef CRX_CBF_CARRY
-#define CRX_CBF_CARRY 1
-#endif
-template <int NOBS, int NMAX> constexpr bool Obs1Tuned = NOBS == 1 && NMAX == 12 && !CRX_TU_GENERAL;
-template <int NOBS, int NMAX> constexpr bool RetryShared = (CRX_RETRY_SHARED) != 0 && Obs1Tuned<NOBS, NMAX>;
-template <int NOBS, int NMAX> constexpr bool CbfCarry = (CRX_CBF_CARRY) != 0 && Obs1Tuned<NOBS, NMAX> && NMAX * NOBS <= WAVE;
-// [r21] Two more values that the same instantiations formed twice at the same point, from the same operands, with the same roundings (A/B builds:
-// make EXTRA=-DCRX_DIST_CARRY=0 / -DCRX_DNU_CARRY=0 is the parent's code):
-//   CRX_DIST_CARRY    the first_order call that ends the accept step takes the four normalised CBF distances of the lane's row from the accepted
-//                     line-search trial (cbf_dist at Z + al dZ, which is what accept stores in Z: fma(0, dZ, Z) is Z).  Needs CbfCarry's one pass.  The
-//                     stand-alone first_order calls (start, restart, restoration) and eval_rows have no accepted trial and evaluate as before
-//   CRX_DNU_CARRY     the row-step pass stores the multiplier step dnu = -w + Sigma (rp - dt) of every row it forms; the accept pass loads it where
-//                     it loaded rc, rt, rdt, Sigma and w to form the same number again.  It lives in the first rows of Kk, which is dead from the
-//                     end of the forward sweep to the next backward sweep.  (NOT in hg: a jam exit that finds nothing to restore re-runs the
-//                     iteration from its top, and the adjoint sweep of the re-run reads ga = hg as the abandoned iteration left it.)
-#ifndef CRX_DIST_CARRY
-#define CRX_DIST_CARRY 1
-#endif
-#ifndef CRX_DNU_CARRY
-#define CRX_DNU_CARRY 1
-#endif
-template <int NOBS, int NMAX> constexpr bool DistCarry = (CRX_DIST_CARRY) != 0 && CbfCarry<NOBS, NMAX>;
-template <int NOBS, int NMAX> constexpr bool DnuCarry = (CRX_DNU_CARRY) != 0 && Obs1Tuned<NOBS, NMAX>;   // (the rows fit into Kk: static_assert in the kernel)
-// [r22] The one-wave kernels of the same reach take the decisions of the LINE SEARCH, which every lane takes alike, as scalar branches (A/B builds:
-// make EXTRA=-DCRX_UNIFORM_CTRL=0 is the parent's code, byte for byte; every other instantiation compiles what it compiled before):
-//   CRX_UNIFORM_CTRL  thn, phin, theta, Dphi and al are wave reductions or formed from them, but they live in VGPRs: to the compiler the backtracking
-//                     loop, `if (okf)`, the switching / Armijo / sufficient-decrease tests and `if (acc) break` are divergent -- EXEC save, branch
-//                     on EXEC = 0 and EXEC restore per region, the loop EXEC-masked.  Each of these conditions goes through wave_uniform
-//                     (crx_wave.h); acc, ftype and the loop are scalar behind them.  A lone wave pays an issue slot for every instruction
-//                     (DESIGN.md 5.1).  No floating-point operation is added, removed or reordered: same bits, tests/test_gpu_uniform_ctrl_bits.py.
-//                     The other uniform decisions of the iteration (barrier update, step-length guards, termination, jam / stall rules, the
-//                     pivot verdicts of the sweep) were tried the same way and grew their phases: HISTORY.md, round 22.
-#ifndef CRX_UNIFORM_CTRL
-#define CRX_UNIFORM_CTRL 1
-#endif
-template <int NOBS, int NMAX> constexpr bool UniformCtrl = (CRX_UNIFORM_CTRL) != 0 && Obs1Tuned<NOBS, NMAX>;
-// [r24] The one-wave kernels of DistCarry's reach run the COORDINATE passes of the Newton assembly and of the first_order call that ends the accept
-// step differently, one bit of the switch each (A/B builds: make EXTRA=-DCRX_ASM_CARRY=0 is the parent's code, byte for byte, =1 / =2 one part alone;
-// every other instantiation compiles what it compiled before):
-//   CRX_ASM_CARRY  1  assemble_newton's coordinate pass loads first, like its row pass and first_order's coordinate pass [r8]: the row-of-coordinate
-//                     table entries of every pass, then the loads that need none, then Sigma and w of the bound rows, LOADS_DONE(), then arithmetic
-//                     and stores pass by pass -- same expressions, same store order
-//                  2  both coordinate passes run ceil((NFIX NZ + NX) / 64) = 2 passes over the lanes, not the layout's ceil(NV / 64) = 3.  No lane of
-//                     the third pass owns a coordinate (127 of them at N = 12, 107 at N = 10), but the stores of Hd and of ga are not
-//                     address-predicated, so the compiler kept the whole pass to store entry 0 once more -- from the operands of pass 0 (Hd does not
-//                     read ga, and ga[0] is rebuilt from the same Z and multipliers), so with its bits: 44 + 24 instructions per iteration
-//                     for nothing (profiles/r24_census.txt)
-//                     Same bits: tests/test_gpu_asm_carry_bits.py.  (The name is the round's: what it set out to carry from accept into the assembly,
-//                     and why that stayed out: HISTORY.md, round 24.)
-#ifndef CRX_ASM_CARRY
-#define CRX_ASM_CARRY 3
-#endif
-enum : unsigned { ASMC_LOADS_FIRST = 1, ASMC_PASSES = 2 };
-template <int NOBS, int NMAX> constexpr unsigned AsmCarry = DistCarry<NOBS, NMAX> ? (unsigned)(CRX_ASM_CARRY) : 0u;
+// The FORMS of the interior-point iteration.  Every instantiation runs the PLAIN form but the tuned one-obstacle ones <1,12,6,*> (124 rows, 127
+// coordinates: two passes over the 64 lanes), which run one of two others -- same bits in all three: tests/test_gpu_plain_bits.py pins the plain
+// form, tests/test_gpu_obs1_*_bits.py, test_gpu_uniform_ctrl_bits.py and test_gpu_asm_carry_bits.py the other two.  Each was an A/B switch of its
+// round; DESIGN.md 5.1 has the measurements, HISTORY.md ("Retired A/B switches": the table, and "Second fold" below it) the verdicts and the last
+// commit that builds the other arms.
+//   loads_first   the two-wave kernels <1,12,6,{12,10}, SPEC = 1>, and part of lone_wave:
+//       * the two-pass phases -- row step, row trial, row accept, the accept of Z, first_order's coordinate pass, assemble_newton's row pass --
+//         load the operands of BOTH passes into per-pass locals, LOADS_DONE(), then compute and store pass by pass.  Left alone, pass 1 loads only
+//         after pass 0 has stored (the SINK-selected store addresses may alias anything): one more LDS round trip per phase.  Both schedules are
+//         made of the SAME text: a phase states its operands and its arithmetic with its stores once (macros in front of the `if constexpr`) and
+//         the arms keep only the schedule of the loads
+//       * the accept step takes the CBF row values from the accepted line-search trial, which evaluated them at the point accept stores
+//         (NMAX * NOBS <= 64: one pass, the row of a lane is the same in both places)
+//   lone_wave     the one-wave kernels <1,12,6,{12,10}>: loads_first, and
+//       * the attempts of the inertia-correction schedule of ONE Newton system share the set-up of riccati_backward (lane maps, the stage-invariant
+//         model operands, the opaque lane copy): the retry loop runs inside the sweep function, behind its set-up (riccati_backward<.., SHARED>:
+//         written for the register-resident (P | p), so only where ROWDPP holds)
+//       * the first_order call that ends the accept step takes the four normalised CBF distances of the lane's row from the accepted trial as well
+//         (cbf_dist at Z + al dZ, which is what accept stores in Z: fma(0, dZ, Z) is Z).  The stand-alone first_order calls (start, restart,
+//         restoration) and eval_rows have no accepted trial: they evaluate, in the plain form
+//       * the row-step pass stores the multiplier step dnu = -w + Sigma (rp - dt) of every row it forms; the accept pass loads it where it loaded
+//         rc, rt, rdt, Sigma and w to form the same number again.  It lives in the first rows of Kk, which is dead from the end of the forward
+//         sweep to the next backward sweep.  (NOT in hg: a jam exit that finds nothing to restore re-runs the iteration from its top, and the
+//         adjoint sweep of the re-run reads ga = hg as the abandoned iteration left it.)
+//       * the decisions of the LINE SEARCH, which every lane takes alike, are scalar branches: thn, phin, theta, Dphi and al are wave reductions or
+//         formed from them, but live in VGPRs -- to the compiler the backtracking loop, `if (okf)`, the switching / Armijo / sufficient-decrease
+//         tests and `if (acc) break` are divergent.  Each condition goes through wave_uniform (crx_wave.h); no floating-point operation is added,
+//         removed or reordered
+//       * assemble_newton's coordinate pass loads first too, and it and the coordinate pass of accept's first_order run the
+//         ceil((NFIX NZ + NX) / 64) = 2 passes that own a coordinate, not the layout's ceil(NV / 64) = 3 (whose third stored entry 0 once more)
+//     (the two-wave kernels stand at 252 / 254 VGPRs: either carry takes them to 254 .. 256, and with both the register allocator of this toolchain
+//     crashes on <1,12,6,12, SPEC = 1>)
+enum class Form { plain, loads_first, lone_wave };
+template <int NOBS, int NMAX, int NFIX, int SPEC, int QPM> constexpr Form SolveForm =
+    !(NOBS == 1 && NMAX == 12 && !CRX_TU_GENERAL && NFIX != 0 && QPM == 0) ? Form::plain : (SPEC == 0 ? Form::lone_wave : Form::loads_first);
 // end of a stage of an UNROLLED sweep [r4]: without it the scheduler lifts the loads of all later stages to the top of the sweep and the
 // registers they occupy are paid for in scratch (a wave writes its spills once: 100 B per lane were x8 the algorithmic bytes written of a cfg2 launch)
 #define STAGE_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -263,7 +222,7 @@ struct Lay {
     static constexpr int rnu = rt + MR;
     static constexpr int rc = rnu + MR;
     static constexpr int rdt = rc + MR;
-    static constexpr int rtt = rdt + MR;             // trial slack / 1/t (dnu is recomputed at accept: -w + Sigma (rp - dt); DnuCarry [r21]: parked in Kk)
+    static constexpr int rtt = rdt + MR;             // trial slack / 1/t (dnu is recomputed at accept: -w + Sigma (rp - dt); lone_wave [r21]: parked in Kk)
     // SLIM layout [r3] (the 3-obstacle instantiations: BASELINE configs[3], N = 20): four problems per CU need <= 40 960 B
     // and the full layout is 52 560 B.  Whatever is a pure function of other LDS contents is recomputed where it is used
     // -- Sigma and w from (t, nu, c, mu), the bound of a simple row from its slot, the presence of a simple row from its
@@ -508,7 +467,7 @@ __device__ __forceinline__ double cbf_value(const double* sm, const Ctx& c, int 
     return gn - sk1 - c.om * (gc - sk) - c.alpha * c.cm;
 }
 
-// [r21] cbf_value() that also hands out the four distances it formed (DistCarry: the line-search trial keeps them for first_order)
+// [r21] cbf_value() that also hands out the four distances it formed (lone_wave: the line-search trial keeps them for first_order)
 template <int NOBS, int NMAX>
 __device__ __forceinline__ double cbf_value_dist(const double* sm, const Ctx& c, int k, int o, double al, double& dsc, double& dec, double& dsn, double& den) {
     using L = Lay<NOBS, NMAX>;
@@ -601,14 +560,16 @@ __device__ __forceinline__ void eval_rows(double* sm, const int* si, const Ctx& 
 
 // First-order pieces at the iterate: CBF derivative table G, CBF Jacobians Jc (scaled, stage
 // coordinates) and the Lagrangian gradient ga = grad f - J' nu per stage coordinate.
-// (DC [r21], DistCarry: the caller -- the accept step -- hands in the four distances of this lane's CBF row as the accepted trial formed them, at
-// the point that is now the iterate; one pass, the row of a lane is the same in both places.)
-// (CP [r24], AsmCarry: the loads-first coordinate pass runs CP passes over the lanes -- the caller's horizon needs no more; 0: the layout's count.)
-template <int NOBS, int NMAX, unsigned LF = 0, bool DC = false, int CP = 0>
+// (F: the form of the caller -- the accept step; the stand-alone calls are plain.  lone_wave [r21, r24]: the caller hands in the four distances of
+// this lane's CBF row as the accepted trial formed them, at the point that is now the iterate -- one pass, the row of a lane is the same in both
+// places -- and the coordinate pass runs CP passes over the lanes: the caller's horizon needs no more.  The other forms run the layout's count.)
+template <int NOBS, int NMAX, Form F = Form::plain, int CP = 0>
 __device__ __forceinline__ void first_order(double* sm, const int* si, const Ctx& c, double dsc_tr = 0.0, double dec_tr = 0.0, double dsn_tr = 0.0,
                                             double den_tr = 0.0) {
     using L = Lay<NOBS, NMAX>;
     const int N = c.N;
+    constexpr bool DC = F == Form::lone_wave;
+    static_assert(DC == (CP != 0), "the lone-wave form, and no other, names its passes");
     static_assert(!DC || (NOBS > 0 && NMAX * NOBS <= WAVE), "carried distances: one CBF row per lane");
     if (NOBS) {
 #pragma unroll
@@ -690,7 +651,7 @@ __device__ __forceinline__ void first_order(double* sm, const int* si, const Ctx
         g = (k == N && a >= L::NX) ? 0.0 : g; \
         LD(L::ga + e) = g; \
     } while (0)
-    if constexpr ((LF & LF_FIRST_ORDER) != 0) {   // [r8] both passes load, then both compute
+    if constexpr (F != Form::plain) {   // [r8] both passes load, then both compute
         static_assert(NOBS > 0, "written for the obstacle instantiations");
         constexpr int CPASS = CP ? CP : (L::NV + WAVE - 1) / WAVE;
         int rl[CPASS], rh[CPASS];
@@ -831,11 +792,13 @@ __device__ __forceinline__ double box_certificate(double* sm, const int* si, con
 //   per coord Hd = cost diag + Sigma of its bound rows + "current" CBF curvature,
 //             hg = ga (reduced form) + J'w
 //   per stage kS,kE = "next" CBF curvature  (- nu d hess g_{k+1}), added to P[4][4], P[5][5]
-// (CP, CLF [r24], AsmCarry: the coordinate pass runs CP passes over the lanes -- the caller's horizon needs no more; 0: the layout's count -- and loads first.)
-template <int NOBS, int NMAX, unsigned LF = 0, int CP = 0, bool CLF = false>
+// (F: the form of the caller.  lone_wave [r24]: the coordinate pass loads first as well and runs CP passes over the lanes -- the caller's horizon needs
+// no more; the other forms run the layout's count.)
+template <int NOBS, int NMAX, Form F = Form::plain, int CP = 0>
 __device__ __forceinline__ void assemble_newton(double* sm, const int* si, const Ctx& c, double mu) {
     using L = Lay<NOBS, NMAX>;
     const int N = c.N;
+    static_assert((F == Form::lone_wave) == (CP != 0), "the lone-wave form, and no other, names its passes");
     // the row pass: operands, then arithmetic and stores.  rtt = 1/t for the row-step pass (rtt is free until the line search); w = the expression
     // of row_sig_w.  slim [r4b]: no Sigma array, and w of the row is parked in rdt for the coordinate pass below (dead from the accept pass until
     // the row steps that follow the forward sweep; the backward sweep's P / T move in only after this function) -- the coordinate pass recomputed it
@@ -855,7 +818,7 @@ __device__ __forceinline__ void assemble_newton(double* sm, const int* si, const
         const double cjv = cj; \
         LD((L::SLIM ? L::rdt : L::rw) + j) = sel(on, nu - mu * rti + sig * (cjv - t), 0.0); \
     } while (0)
-    if constexpr ((LF & LF_ASSEMBLE) != 0) {   // [r8] both passes load, then both compute
+    if constexpr (F != Form::plain) {   // [r8] both passes load, then both compute
         constexpr int RPASS = (L::MR + WAVE - 1) / WAVE;
         double t[RPASS], nu[RPASS], rs[RPASS], cj[RPASS];
         ROWS(j, jv, c.lane, c.m) { (void)jv; ASM_T_NU(t[q_], nu[q_]); rs[q_] = ASM_RS; cj[q_] = ASM_CJ; }
@@ -922,9 +885,9 @@ __device__ __forceinline__ void assemble_newton(double* sm, const int* si, const
         LD(L::Hd + e) = sel(tail, 0.0, h); \
         LD(SINK(ev, L::hg + e)) = sel(tail, 0.0, g);   /* in place over ga: read-modify-write */ \
     } while (0)
-    constexpr int CPASS = CP ? CP : (L::NV + WAVE - 1) / WAVE;
-    if constexpr (CLF) {   // [r24] every pass loads, then every pass computes: the schedule of first_order's coordinate pass [r8]
-        static_assert(NOBS > 0 && !L::SLIM && (LF & LF_ASSEMBLE) != 0, "written for the full layout of the loads-first obstacle instantiations");
+    if constexpr (F == Form::lone_wave) {   // [r24] every pass loads, then every pass computes: the schedule of first_order's coordinate pass [r8]
+        static_assert(NOBS > 0 && !L::SLIM, "written for the full layout of the loads-first obstacle instantiations");
+        constexpr int CPASS = CP;
         int rl[CPASS], rh[CPASS];
         double gav[CPASS], cwv[CPASS], sglv[CPASS], sghv[CPASS], wlv[CPASS], whv[CPASS], csv[CPASS][NOBS], jcv[CPASS][NOBS], rwv[CPASS][NOBS], nuv[CPASS][NOBS], gcv[CPASS][NOBS];
         // the row-of-coordinate table entries first, Sigma and w of the rows they point to last: the entries are back by the time the loads between have been issued
@@ -952,7 +915,7 @@ __device__ __forceinline__ void assemble_newton(double* sm, const int* si, const
             ASM_COORD(gav[q_], cwv[q_], rl[q_], rh[q_], sglv[q_], sghv[q_], wlv[q_], whv[q_], csv[q_][ob], jcv[q_][ob], nuv[q_][ob], gcv[q_][ob], (void)0, rwj = rwv[q_][ob]);
         }
     } else
-    COORDS_P(e, ev, c.lane, N * L::NZ + L::NX, CPASS) {   // stage N has states only (127 entries at N=12, 1 obstacle: two passes own a coordinate; CP = 0 runs the layout's three)
+    COORDS(e, ev, c.lane, N * L::NZ + L::NX) {   // stage N has states only (127 entries at N=12, 1 obstacle: two passes own a coordinate; the layout's count is three)
         int rl, rh;
         ASM_COORD(ASM_GA, ASM_CW, rl, rh, ASM_SIG(il), ASM_SIG(ih), ASM_W(il), ASM_W(ih), ASM_CSC, ASM_JCA, ASM_CBF_NU, ASM_CBF_G, coord_rows<L>(si, c, e, k, a, rl, rh),
                   row_sig_w<L>(sm, j, csj != 0.0, mu, LD(L::rt + j), LD(L::rnu + j), LD(L::rtt + j), LD(L::rc + j), rsj_, rwj));
@@ -1911,26 +1874,18 @@ crx_solve_kernel(const crx_solve_params kp) {
     using L = Lay<NOBS, NMAX>;
     static_assert(!SPEC || (NOBS > 0 && !L::SLIM && CRX_STATIC_LDS), "the speculating wave exists for the obstacle instantiations of the full, static layout");
     constexpr int NX = L::NX, NZ = L::NZ, NR = L::NR;
-    // [r8] the phases of this instantiation that load both passes before they compute (LoadsFirst), and the passes of a row / coordinate phase
-    constexpr unsigned LF = (NFIX != 0 && QPM == 0) ? LoadsFirst<NOBS, NMAX> : 0u;
-    // [r9] ... and the two pieces of repeated work they leave out (RetryShared: the one-wave retry loop only; CbfCarry)
-    constexpr bool RSH = NFIX != 0 && QPM == 0 && SPEC == 0 && RetryShared<NOBS, NMAX>;
-    constexpr bool CBFC = NFIX != 0 && QPM == 0 && CbfCarry<NOBS, NMAX>;
-    // [r21] ... and two more (DistCarry: first_order after accept takes the trial's CBF distances; DnuCarry: accept takes dnu from the row steps, through Kk)
-    // (the one-wave kernels only, like RetryShared: the two-wave kernels stand at 252 / 254 VGPRs; either of the two takes both to 254 .. 256, and with both
-    // the register allocator of this toolchain crashes on <1,12,6,12, SPEC = 1>.  They keep the evaluations -- same bits: tests/test_gpu_obs1_carry_bits.py)
-    constexpr bool DISTC = NFIX != 0 && QPM == 0 && SPEC == 0 && DistCarry<NOBS, NMAX>;
-    constexpr bool DNUC = NFIX != 0 && QPM == 0 && SPEC == 0 && DnuCarry<NOBS, NMAX>;
-    // [r22] ... and take the wave-uniform decisions of the interior-point loop as scalar branches (UniformCtrl; the one-wave kernels only, as above)
-    constexpr bool UC = NFIX != 0 && QPM == 0 && SPEC == 0 && UniformCtrl<NOBS, NMAX>;
-    // [r24] ... and run the coordinate passes of the assembly and of accept's first_order over the passes their horizon needs, the assembly's loads-first
-    // (AsmCarry; the one-wave kernels only, as above).  ACP: that pass count, 0 where the parent's text stands
-    constexpr unsigned ASMC = (DISTC && (LF & LF_ASSEMBLE) != 0 && (LF & LF_FIRST_ORDER) != 0) ? AsmCarry<NOBS, NMAX> : 0u;
-    constexpr int ACP = (ASMC & ASMC_PASSES) != 0 ? (NFIX * NZ + NX + WAVE - 1) / WAVE : 0;
-#define UNI(b) wave_uniform_if<UC>(b)   /* a decision every lane takes alike, all 64 active: crx_wave.h, contract of wave_uniform */
-    static_assert(!DNUC || (!L::SLIM && L::MR <= NMAX * L::KS && L::G != L::Kk), "dnu of every row inside Kk, and nothing else lives there between the sweeps");
+    // the form of this instantiation (Form, at the head of this file): TUNED = loads_first or lone_wave, LONE = lone_wave
+    constexpr Form FORM = SolveForm<NOBS, NMAX, NFIX, SPEC, QPM>;
+    constexpr bool TUNED = FORM != Form::plain, LONE = FORM == Form::lone_wave;
+    // lone_wave: the passes that the coordinate passes of the assembly and of accept's first_order run, 0 where they run the layout's count
+    constexpr int ACP = LONE ? (NFIX * NZ + NX + WAVE - 1) / WAVE : 0;
+    // lone_wave: the retry loop inside the sweep function, where the sweep keeps (P | p) in registers
+    constexpr bool RETRY_SHARED = LONE && ROWDPP<L>;
+#define UNI(b) wave_uniform_if<LONE>(b)   /* a decision every lane takes alike, all 64 active: crx_wave.h, contract of wave_uniform */
+    static_assert(!LONE || (!L::SLIM && L::MR <= NMAX * L::KS && L::G != L::Kk), "dnu of every row inside Kk, and nothing else lives there between the sweeps");
     constexpr int RPASS = (L::MR + WAVE - 1) / WAVE, CPASS = (L::NV + WAVE - 1) / WAVE;
-    static_assert(LF == 0 || !L::SLIM, "the loads-first row passes are written for the full layout (row_scale, row_bound, row_sig_w are loads there)");
+    static_assert(!TUNED || !L::SLIM, "the loads-first row passes are written for the full layout (row_scale, row_bound, row_sig_w are loads there)");
+    static_assert(!TUNED || NMAX * NOBS <= WAVE, "the carried CBF row value: one CBF row per lane");
 #if CRX_STATIC_LDS
     // [r4] The layout is a compile-time constant, so the array is STATIC: the compiler then knows its address (0) and folds it into the
     // offset fields.  As `extern __shared__` the base stays a symbol until emission and every address computed at run time carries an
@@ -2602,7 +2557,7 @@ crx_solve_kernel(const crx_solve_params kp) {
         const double tau = ipm_tau(mu, o.tau_min);
         // ---- Newton step ---------------------------------------------------------------------------
         long long tc3 = CLK();
-        assemble_newton<NOBS, NMAX, LF, ACP, (ASMC & ASMC_LOADS_FIRST) != 0>(sm, si, c, mu);
+        assemble_newton<NOBS, NMAX, FORM, ACP>(sm, si, c, mu);
         long long tc4 = CLK();
         // inertia correction: retry the sweep with a growing regularisation dw until every pivot is positive (one call
         // site: the sweep is inlined once)
@@ -2656,7 +2611,7 @@ crx_solve_kernel(const crx_solve_params kp) {
                 dw = sdw;
                 if (sdw > IPM_DW_MAX) break;
             }
-        } else if constexpr (RSH) {
+        } else if constexpr (RETRY_SHARED) {
             // [r9] the same schedule, run by the sweep function between its attempts (riccati_backward<.., SHARED>): one set-up per Newton system
             // (no state of its own: the convexified retry is still ahead while crash && !used_convex, and the first step of delta_w is the one from 0)
             auto retry = [&](double& dwr) -> bool {
@@ -2706,10 +2661,10 @@ crx_solve_kernel(const crx_solve_params kp) {
             // dnu = (mu - t nu - nu dt)/t = mu/t - nu - Sigma dt = -w + Sigma (rp - dt)
             const double dnu = sel(on, -rwj + rsj * (rp - dt), 0.0);
             LD(SINK(store, L::rdt + j)) = dt;
-            // (DNUC: for the accept pass, which formed it again from five loads.  Kk is dead from the forward sweep above to the next backward sweep.
+            // (lone_wave: for the accept pass, which formed it again from five loads.  Kk is dead from the forward sweep above to the next backward sweep.
             // Rows that are off store the zero nobody reads: accept touches the multiplier of a row that is on only.  Storing -dnu, the form the
             // ratio test below consumes, counted four instructions more: HISTORY.md, round 21)
-            if constexpr (DNUC) LD(SINK(store, L::Kk + j)) = dnu;
+            if constexpr (LONE) LD(SINK(store, L::Kk + j)) = dnu;
             const double dtr = dt * rti;                       // dt / t
             rp_max = fmax(rp_max, sel(cnt, -dtr, 0.0));
             rd_max = fmax(rd_max, sel(cnt && on, -dnu * frcp(nu), 0.0));
@@ -2735,7 +2690,7 @@ crx_solve_kernel(const crx_solve_params kp) {
         };
         // J dz straight from the step (differencing row values would lose eps*|x|, which the
         // multiplier update amplifies by Sigma = nu/t ~ 1e10..1e13)
-        if constexpr ((LF & LF_ROW_STEP) != 0) {   // full layout: row_scale and row_sig_w are loads
+        if constexpr (TUNED) {   // full layout: row_scale and row_sig_w are loads
             int pk[RPASS];
             double sc[RPASS], dz[RPASS], t[RPASS], nu[RPASS], rti[RPASS], rcj[RPASS], rsj[RPASS], rwj[RPASS];
             ROWS(j, jv, lane, m) { (void)jv; pk[q_] = ROW_PK; }
@@ -2781,12 +2736,12 @@ crx_solve_kernel(const crx_solve_params kp) {
         long long tc7 = CLK();
         // ---- filter line search ----------------------------------------------------------------------
         double al = a_p, fn = f, lt_acc = logsum_t;
-        double cbf_tr = 0.0;   // CBFC: this lane's CBF row value of the last trial, unscaled (the accept step's, when the trial is accepted)
-        double dist_tr[4] = {0.0, 0.0, 0.0, 0.0};   // DISTC: ... and the four distances (dsc, dec, dsn, den) that value was formed from, for first_order
+        double cbf_tr = 0.0;   // TUNED: this lane's CBF row value of the last trial, unscaled (the accept step's, when the trial is accepted)
+        double dist_tr[4] = {0.0, 0.0, 0.0, 0.0};   // LONE: ... and the four distances (dsc, dec, dsn, den) that value was formed from, for first_order
         int acc = 0, ftype = 0;
         // switching condition al * (-Dphi)^2.3 > theta^1.1 (only consulted when theta <= theta_min)
         bool sw_try = (theta <= theta_min) && (Dphi < 0.0);
-        if constexpr (UC) sw_try = wave_uniform(sw_try);
+        if constexpr (LONE) sw_try = wave_uniform(sw_try);
         // ... compared in the log2 domain: log2(al) + 2.3 log2(-Dphi) > 1.1 log2(theta), with log2_fast (double exponent +
         // v_log_f32 of the mantissa, ~1e-7 absolute).  Two pow() calls were ~2.6 k cycles of this iteration and kept ~50
         // VGPRs of polynomial constants alive; the test is a heuristic threshold, a tie within 1e-7 may fall either way.
@@ -2808,7 +2763,7 @@ crx_solve_kernel(const crx_solve_params kp) {
             // the simple rows: operands, then arithmetic and stores (linear rows: the trial value is exact)
 #define TRIAL_LOADS(sc, t, dt, cj) sc = row_scale<L>(sm, si, j, N), t = LD(L::rt + j), dt = LD(L::rdt + j), cj = LD(L::rc + j)
 #define TRIAL_SIMPLE(sc, t, dt, cj) row_trial(j, jv && simple, simple, sc, cj + al * (dt - (cj - t)), t, dt)
-            if constexpr ((LF & LF_ROW_TRIAL) != 0) {
+            if constexpr (TUNED) {
                 double sc[RPASS], t[RPASS], dt[RPASS], cj[RPASS];
                 ROWS(j, jv, lane, m) { (void)jv; TRIAL_LOADS(sc[q_], t[q_], dt[q_], cj[q_]); }
                 LOADS_DONE();
@@ -2827,16 +2782,16 @@ crx_solve_kernel(const crx_solve_params kp) {
                 CBF_ROWS(j, k, ob, ev, lane, N) {   // evaluated at Z + al dZ
                     const double sc = cbf_scale<L>(sm, k, ob), t = LD(L::rt + j), dt = LD(L::rdt + j);
                     double cv;
-                    if constexpr (DISTC) cv = cbf_value_dist<NOBS, NMAX>(sm, c, k, ob, al, dist_tr[0], dist_tr[1], dist_tr[2], dist_tr[3]);
+                    if constexpr (LONE) cv = cbf_value_dist<NOBS, NMAX>(sm, c, k, ob, al, dist_tr[0], dist_tr[1], dist_tr[2], dist_tr[3]);
                     else cv = cbf_value<NOBS, NMAX>(sm, c, k, ob, al);
-                    if constexpr (CBFC) cbf_tr = cv;
+                    if constexpr (TUNED) cbf_tr = cv;
                     row_trial(j, ev, true, sc, sc * cv, t, dt);
                 }
             }
             lt_acc = lg.wave_total_with(thn);                         // thn and the exponent sum share one reduction
             const double phin = fn - mu * lt_acc;
             int okf = (thn <= theta_max) && (phin == phin);
-            if constexpr (UC) okf = wave_uniform(okf != 0);
+            if constexpr (LONE) okf = wave_uniform(okf != 0);
             {   // filter (nf <= MAXF < WAVE entries: one pass, lanes past nf read entry 0 and are masked)
                 const bool iv = lane < nf;
                 const int i = iv ? lane : 0;
@@ -2853,7 +2808,7 @@ crx_solve_kernel(const crx_solve_params kp) {
                 } \
             }
 #define TRIAL_PLAIN(b) b
-            if constexpr (UC) { TRIAL_DECIDE(wave_uniform) } else { TRIAL_DECIDE(TRIAL_PLAIN) }
+            if constexpr (LONE) { TRIAL_DECIDE(wave_uniform) } else { TRIAL_DECIDE(TRIAL_PLAIN) }
             if (acc) break;
             al *= 0.5;
         }
@@ -2884,7 +2839,7 @@ crx_solve_kernel(const crx_solve_params kp) {
         SYNC();
 #define Z_LOADS(zo, dz) zo = LD(L::Z + e), dz = LD(L::dZ + e)
 #define Z_STEP(zo, dz) do { const double zn = zo + al * dz; LD(SINK(ev, L::Z + e)) = zn; } while (0)   /* read-modify-write */
-        if constexpr ((LF & LF_ACCEPT_Z) != 0) {
+        if constexpr (TUNED) {
             double zo[CPASS], dz[CPASS];
             COORDS(e, ev, lane, N * NZ + NX) { (void)ev; Z_LOADS(zo[q_], dz[q_]); }
             LOADS_DONE();
@@ -2906,7 +2861,7 @@ crx_solve_kernel(const crx_solve_params kp) {
             const bool cnt = own && on;
             const double mut = mu * frcp(tn);
             double dnu;
-            if constexpr (DNUC) {
+            if constexpr (LONE) {
                 dnu = rdj;                                     // the row-step pass's own dnu, handed in where the step dt was (ACCEPT_ROW_CARRIED)
             } else {
                 const double rp = rcj - rtj;                   // dnu as in the row-step pass (rc, rt, rw, rsig still hold that state)
@@ -2929,14 +2884,14 @@ crx_solve_kernel(const crx_solve_params kp) {
 #define ACCEPT_ROW_STATE(on_, tn, rcj, rtj, rdj, rnj, rsj, rwj) \
         tn = LD(L::rtt + j), rcj = LD(L::rc + j), rtj = LD(L::rt + j), rdj = LD(L::rdt + j), rnj = LD(L::rnu + j); \
         row_sig_w<L>(sm, j, on_, mu, rtj, rnj, L::SLIM ? frcp(rtj) : 0.0, rcj, rsj, rwj)
-        // (DNUC: what is left of the pre-step state -- the trial slack, the multiplier, and dnu as the row steps stored it)
+        // (lone_wave: what is left of the pre-step state -- the trial slack, the multiplier, and dnu as the row steps stored it)
 #define ACCEPT_ROW_CARRIED(tn, dnu, rnj) tn = LD(L::rtt + j), dnu = LD(L::Kk + j), rnj = LD(L::rnu + j)
 #define ACCEPT_Z(pk) LD(L::Z + RIV_IDX(pk))
 #define ACCEPT_RB row_bound<L>(sm, c, j)
 #define ACCEPT_V(pk, z, rb) (RIV_SGN(pk) * (z - rb))
         auto row_accept = [&](int j, bool own, double sc, double v) {   // own: this lane is the one that updates row j
             const bool on = ROW_ON(sc);
-            if constexpr (DNUC) {
+            if constexpr (LONE) {
                 const double ACCEPT_ROW_CARRIED(tn, dnu, rnj);
                 row_accept_tail(j, own, on, v, tn, 0.0, 0.0, dnu, rnj, 0.0, 0.0);
             } else {
@@ -2946,7 +2901,7 @@ crx_solve_kernel(const crx_solve_params kp) {
             row_accept_tail(j, own, on, v, tn, rcj, rtj, rdj, rnj, rsj, rwj);
             }
         };
-        if constexpr ((LF & LF_ROW_ACCEPT) != 0 && DNUC) {   // [r21] the same schedule over the carried operands
+        if constexpr (LONE) {   // [r21] the same schedule over the carried operands
             int pk[RPASS];
             double sc[RPASS], zv[RPASS], rb[RPASS], tn[RPASS], dnu[RPASS], rnj[RPASS];
             ROWS(j, jv, lane, m) { (void)jv; pk[q_] = ROW_PK; }
@@ -2964,7 +2919,7 @@ crx_solve_kernel(const crx_solve_params kp) {
                 row_accept_tail(j, jv && !ROW_IS_CBF(j, N), ROW_ON(sc[q_]), ACCEPT_V(pk[q_], zv[q_], rb[q_]), tn[q_], 0.0, 0.0, dnu[q_], rnj[q_], 0.0, 0.0);
             }
         } else
-        if constexpr ((LF & LF_ROW_ACCEPT) != 0) {   // full layout: row_scale, row_bound and row_sig_w are loads
+        if constexpr (TUNED) {   // full layout: row_scale, row_bound and row_sig_w are loads
             int pk[RPASS];
             double sc[RPASS], zv[RPASS], rb[RPASS], tn[RPASS], rcj[RPASS], rtj[RPASS], rdj[RPASS], rnj[RPASS], rsj[RPASS], rwj[RPASS];
             ROWS(j, jv, lane, m) { (void)jv; pk[q_] = ROW_PK; }
@@ -2990,10 +2945,10 @@ crx_solve_kernel(const crx_solve_params kp) {
         if (NOBS) {
             CBF_ROWS(j, k, ob, ev, lane, N) {
                 const double sc = cbf_scale<L>(sm, k, ob);
-                // (CBFC: Z now holds Z + al dZ of the accepted trial, rounded as the trial rounded it: evaluated here the row would be the trial's, bit for bit.
+                // (TUNED: Z now holds Z + al dZ of the accepted trial, rounded as the trial rounded it: evaluated here the row would be the trial's, bit for bit.
                 // The UNSCALED value is what is carried: the violation |sc v - t| below is formed with one rounding, fma(sc, v, -t), as it always was --
                 // carrying the rounded product sc v changed the last bits of e_p, and with it the reported KKT error: HISTORY.md, round 9)
-                if constexpr (CBFC) row_accept(j, ev, sc, sc * cbf_tr);
+                if constexpr (TUNED) row_accept(j, ev, sc, sc * cbf_tr);
                 else row_accept(j, ev, sc, sc * cbf_value<NOBS, NMAX>(sm, c, k, ob, 0.0));
             }
         }
@@ -3005,8 +2960,7 @@ crx_solve_kernel(const crx_solve_params kp) {
         }
         nus = wave_sum(nus);
         e_p = th;
-        if constexpr (DISTC) first_order<NOBS, NMAX, LF, true, ACP>(sm, si, c, dist_tr[0], dist_tr[1], dist_tr[2], dist_tr[3]);
-        else first_order<NOBS, NMAX, LF>(sm, si, c);
+        first_order<NOBS, NMAX, FORM, ACP>(sm, si, c, dist_tr[0], dist_tr[1], dist_tr[2], dist_tr[3]);   // (the distances: read by the lone-wave form only)
         if (TRACE_ROW(it, lane) && kp.trace_rows > 0)
             kp.trace[(size_t)it * 16 + 8] = (double)(tph[0] + (CLK() - tc8));   // slot 8: KKT rows + accept/first-order
         BREAK_IF_HOPELESS(numax, th)

@@ -11,7 +11,7 @@
 //   * no inline-assembly DPP: the sweeps broadcast with v_readlane, every hazard is the compiler's to see;
 //   * nothing lane-derived is carried across the interior-point loop: the lane index is made opaque once per iteration (half the
 //     register pressure of the hoisted lane maps);
-//   * no LoadsFirst / CbfCarry forms of the tuned one-obstacle instantiations.
+//   * the plain form everywhere: no loads_first / lone_wave forms of the tuned one-obstacle instantiations (Form, crx_kernels.hip).
 // Registers: static LDS, the whole unified register file (AGPR copies where 256 VGPRs do not suffice).  The other choice -- dynamic LDS +
 // a floor of two waves per SIMD = 256 registers and scratch spills, -DCRX_STATIC_LDS=0 -DCRX_GEN_WAVES=2 -- was the shipped one for a few
 // hours of round 5 and is where the spill-placement bug bit (tools/exec_prologue_check.py finds the pattern in the assembly; it is a

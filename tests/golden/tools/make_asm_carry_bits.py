@@ -21,6 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.normpath(os.path.join(HERE, "..", "..", ".."))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "car-racing_amd"), os.path.join(ROOT, "tests"), HERE]
 
+import bit_pins as P   # noqa: E402
 import test_gpu_asm_carry_bits as T   # noqa: E402
 from make_uniform_ctrl_bits import SEEDS, write_npz   # noqa: E402
 
@@ -33,9 +34,9 @@ def choose(orc, AB, N):
     seen = {p: [] for p in T.PATHS}
     draws, d = {}, None
     for seed in SEEDS:
-        p = draws[seed] = T.U.draw(N, seed)
-        d = d or T.U.descriptor(N, AB, p)
-        _, per = T.batch_paths(orc, d, [np.asarray(p[k]) for k in T.INPUTS])
+        p = draws[seed] = P.draw(N, seed)
+        d = d or P.descriptor(N, AB, p)
+        _, per = T.batch_paths(orc, d, [np.asarray(p[k]) for k in P.INPUTS])
         for i, n in enumerate(per):
             for path in T.PATHS:
                 if n[path] and len(seen[path]) < PER_PATH:
@@ -47,15 +48,15 @@ def choose(orc, AB, N):
     assert not missing, (N, "no problem of the scanned draws takes", missing)
     rank = {s: r for r, s in enumerate(SEEDS)}
     chosen = sorted(set(sum(seen.values(), [])), key=lambda si: (rank[si[0]], si[1]))
-    for i in range(T.DRAW):   # the rest of the first draw
-        if len(chosen) >= T.BATCH:
+    for i in range(P.DRAW):   # the rest of the first draw
+        if len(chosen) >= P.BATCH:
             break
         if (SEEDS[0], i) not in chosen:
             chosen.append((SEEDS[0], i))
     chosen.sort(key=lambda si: (rank[si[0]], si[1]))
-    assert len(chosen) <= T.BATCH
+    assert len(chosen) <= P.BATCH
     src = np.array(chosen, dtype=np.int32)
-    args = [np.ascontiguousarray(np.stack([np.asarray(draws[s][k])[i] for s, i in chosen])) for k in T.INPUTS]
+    args = [np.ascontiguousarray(np.stack([np.asarray(draws[s][k])[i] for s, i in chosen])) for k in P.INPUTS]
     return src, args, d
 
 
@@ -79,11 +80,11 @@ def main(argv):
     orc = oracle.load()
     AB = (np.genfromtxt(os.path.join(ROOT, "data/sys/LTI/matrix_A.csv"), delimiter=","), np.genfromtxt(os.path.join(ROOT, "data/sys/LTI/matrix_B.csv"), delimiter=","))
     arrays, todo = {}, []
-    for N in T.HORIZONS:
+    for N in P.HORIZONS:
         src, args, d = choose(orc, AB, N)
         ro = prove(orc, d, N, args)
         arrays["N%d/src" % N] = src
-        for k, a in zip(T.INPUTS, args):
+        for k, a in zip(P.INPUTS, args):
             arrays["N%d/in/%s" % (N, k)] = a
         todo.append((N, d, args, ro))
     if select_only:
@@ -94,17 +95,17 @@ def main(argv):
     print("recording with", crx.LIB_PATH)
     for N, d, args, ro in todo:
         rg = gpu.cbf_solve(d, *args)
-        assert sorted(rg) == sorted(T.OUTPUTS), sorted(rg)
+        assert sorted(rg) == sorted(P.OUTPUTS), sorted(rg)
         again = gpu.cbf_solve(d, *args)
-        for k in T.OUTPUTS:
-            assert np.array_equal(T.U.bits(rg[k]), T.U.bits(again[k])), (N, k, "two launches of the same library disagree")
+        for k in P.OUTPUTS:
+            assert np.array_equal(P.bits(rg[k]), P.bits(again[k])), (N, k, "two launches of the same library disagree")
             arrays["N%d/%s" % (N, k)] = rg[k]
         assert np.array_equal(rg["status"], ro["status"]) and np.array_equal(rg["iters"], ro["iters"]), (N, "the GPU and the oracle took different paths")
         print("N = %d recorded: status counts %s, longest %d" % (N, np.bincount(rg["status"], minlength=6).tolist(), int(rg["iters"].max())))
     write_npz(out, arrays)
     z = np.load(out, allow_pickle=False)
     for k, a in arrays.items():
-        assert z[k].dtype == a.dtype and np.array_equal(T.U.bits(z[k]), T.U.bits(a)), k
+        assert z[k].dtype == a.dtype and np.array_equal(P.bits(z[k]), P.bits(a)), k
     print("wrote", out, os.path.getsize(out), "bytes")
 
 

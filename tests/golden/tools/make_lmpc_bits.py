@@ -4,8 +4,9 @@ Run on an MI355X with the library whose bits are to be pinned -- the commit BEFO
 
     python tests/golden/tools/make_lmpc_bits.py [OUT.npz]        (default: tests/golden/lmpc_bits.npz)
 
-The cases, their inputs and the encoding (byte planes, XOR against fix12) are the test's own: CASES, solve(), SUBSET, planes(), xor_base().  The file is
-read back through the test's recorded_bits() and compared with what was solved before it counts as written.
+The cases, their inputs and the encoding (byte planes, XOR against fix12) are the test's own: CASES, solve(), SUBSET, xor_base(), and
+planes() of tests/bit_pins.py.  The file is read back through the test's recorded_bits() and compared with what was solved before it counts as
+written.
 """
 import os
 import sys
@@ -15,6 +16,7 @@ import numpy as np
 ROOT = os.path.normpath(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", ".."))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "car-racing_amd"), os.path.join(ROOT, "tests")]
 
+import bit_pins as P   # noqa: E402
 import test_gpu_lmpc_bits as T   # noqa: E402
 
 
@@ -22,14 +24,14 @@ def main(out):
     import crx
 
     gpu = crx.init()
-    res = {case: {k: T.bits(np.asarray(v)) for k, v in T.solve(gpu, case).items()} for case in T.CASES}
+    res = {case: {k: P.bits(np.asarray(v)) for k, v in T.solve(gpu, case).items()} for case in T.CASES}
     arrays = {}
     for case, r in res.items():
         assert sorted(r) == list(T.OUTPUTS), sorted(r)
         for k, b in r.items():
             if b.dtype == np.uint64:
                 base = T.xor_base(case, k, lambda c, kk: res[c][kk])
-                b = T.planes(b if base is None else b ^ base)
+                b = P.planes(b if base is None else b ^ base)
             arrays[case + "/" + k] = b
         print(case, "status counts", np.bincount(r["status"], minlength=6).tolist(), "longest", int(r["iters"].max()), "total", int(r["iters"].sum()))
     np.savez_compressed(out, **arrays)

@@ -1,5 +1,6 @@
-"""The tuned one-obstacle NLP kernels with the Newton assembly's schedule changed (round 24, CRX_ASM_CARRY), bit for bit against a recording of the
-PARENT commit's library.
+"""The tuned one-obstacle NLP kernels with the Newton assembly's schedule changed (round 24), bit for bit against a recording of the PARENT commit's
+library.  The round's A/B switch, CRX_ASM_CARRY, is retired: the schedule is part of the lone-wave form of crx_kernels.hip, and this test is the
+standing pin of that code.
 
 crx_solve_kernel<1,12,6,12> and <1,12,6,10> (obstacle unit and per-problem-model unit) rearrange assemble_newton: what the assembly of an
 iteration computes must stay the same expression on the same operands whatever ran in front of it -- an accepted step that kept the barrier
@@ -27,12 +28,11 @@ import os
 import numpy as np
 import pytest
 
+import bit_pins
 import conftest
-import test_gpu_uniform_ctrl_bits as U   # the draw, the descriptor, the oracle's trace and its reader for two_mu / jam_rerun: stated there
+import test_gpu_uniform_ctrl_bits as U   # its reader of the trace for two_mu / jam_rerun
+from bit_pins import AGAIN, BATCH, HORIZONS, INPUTS, IT, STEP, bits, descriptor, draw, recorded_args
 
-HORIZONS = U.HORIZONS
-DRAW, BATCH = U.DRAW, U.BATCH
-INPUTS, OUTPUTS = U.INPUTS, U.OUTPUTS
 # what the oracle's trace (and n_obs) proves of one problem
 PATHS = ("mu_kept",            # an iteration that keeps mu right after an accepted step
          "mu_cut",             # an iteration that cuts mu right after an accepted step
@@ -57,15 +57,15 @@ def paths_of(lines, opts, n_obs):
     n["n_obs_0"] = int(n_obs == 0)
     its = []   # per iteration: [mu found, accepted, RESTART / RESTORE behind it or None]
     for ln in lines:
-        m = U._IT.match(ln)
+        m = IT.match(ln)
         if m:
             its.append([float(m.group(3)), False, None])
             continue
-        m = U._STEP.search(ln)
+        m = STEP.search(ln)
         if m and its:
             its[-1][1] = int(m.group(3)) == 1
             continue
-        m = U._AGAIN.search(ln)
+        m = AGAIN.search(ln)
         if m and its:
             its[-1][2] = m.group(1)
 
@@ -94,14 +94,8 @@ def paths_of(lines, opts, n_obs):
 
 
 def batch_paths(orc, d, args):
-    """-> (oracle outputs per problem, stacked; list of paths_of() per problem): the problems solved ONE AT A TIME, so that a trace is one problem's"""
-    outs, per = [], []
     n_obs = np.asarray(args[INPUTS.index("n_obs")])
-    for b in range(len(args[0])):
-        out, lines = U.oracle_trace(orc, d, [np.ascontiguousarray(a[b:b + 1]) for a in args])
-        outs.append(out)
-        per.append(paths_of(lines, d.opts, int(n_obs[b])))
-    return {k: np.concatenate([o[k] for o in outs]) for k in outs[0]}, per
+    return bit_pins.batch_paths(orc, d, args, lambda lines, b: paths_of(lines, d.opts, int(n_obs[b])))
 
 
 def totals(per):
@@ -117,13 +111,13 @@ def recorded():
 def test_fixture_holds_every_path(N, AB, orc, recorded):
     """No GPU: the recorded inputs are the problems "src" names, and the oracle -- alone -- takes every path of PATHS on them."""
     src = recorded["N%d/src" % N]
-    args = U.recorded_args(recorded, N)
+    args = recorded_args(recorded, N)
     assert 1 <= len(src) <= BATCH and all(len(a) == len(src) for a in args)
-    draws = {int(s): U.draw(N, s) for s in sorted(set(src[:, 0].tolist()))}
+    draws = {int(s): draw(N, s) for s in sorted(set(src[:, 0].tolist()))}
     for k, a in zip(INPUTS, args):
         want = np.stack([np.asarray(draws[int(s)][k])[int(i)] for s, i in src])
-        assert a.dtype == want.dtype and np.array_equal(U.bits(a), U.bits(want)), (N, k, "the recorded inputs are not the draws' problems")
-    d = U.descriptor(N, AB, draws[int(src[0, 0])])
+        assert a.dtype == want.dtype and np.array_equal(bits(a), bits(want)), (N, k, "the recorded inputs are not the draws' problems")
+    d = descriptor(N, AB, draws[int(src[0, 0])])
     ro, per = batch_paths(orc, d, args)
     n = totals(per)
     print("N = %d, %d problems, by the oracle: %s" % (N, len(src), n))
@@ -135,26 +129,13 @@ def test_fixture_holds_every_path(N, AB, orc, recorded):
     assert np.array_equal(recorded["N%d/iters" % N], ro["iters"]), (N, np.nonzero(recorded["N%d/iters" % N] != ro["iters"])[0])
 
 
-def _assert_recorded(N, route, got, recorded):
-    assert sorted(got) == sorted(OUTPUTS)
-    report = []
-    for k in OUTPUTS:
-        want = recorded["N%d/%s" % (N, k)]
-        assert got[k].dtype == want.dtype and got[k].shape == want.shape, (route, k)
-        diff = np.nonzero((U.bits(got[k]) != U.bits(want)).reshape(len(want), -1).any(axis=1))[0]
-        print("N = %d, %s, %s: %d problems differ from the recording%s" % (N, route, k, diff.size, "" if diff.size == 0 else ", first %d" % diff[0]))
-        if diff.size:
-            report.append((k, int(diff.size), int(diff[0])))
-    assert not report, (N, route, report)
-
-
 @pytest.fixture(scope="module", params=HORIZONS)
 def batch(request, AB, recorded):
     import crx
 
     N = request.param
-    args = U.recorded_args(recorded, N)
-    d = U.descriptor(N, AB, U.draw(N, recorded["N%d/src" % N][0, 0]))
+    args = recorded_args(recorded, N)
+    d = descriptor(N, AB, draw(N, recorded["N%d/src" % N][0, 0]))
     return N, crx.init(), d, args
 
 
@@ -164,5 +145,5 @@ def batch(request, AB, recorded):
 def test_bits_are_the_parents(batch, AB, recorded, models, order):
     N, gpu, d, args = batch
     perm = None if order == "index order" else np.random.default_rng(24).permutation(len(args[0]))
-    got = U._solve(gpu, d, args, AB, models, perm)
-    _assert_recorded(N, "%s, %s" % ("per-problem models" if models else "shared model", order), got, recorded)
+    got = bit_pins.solve(gpu, d, args, AB, models, perm)
+    bit_pins.assert_recorded(N, "%s, %s" % ("per-problem models" if models else "shared model", order), got, recorded)

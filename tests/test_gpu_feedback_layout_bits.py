@@ -24,13 +24,13 @@ The fixture holds a float64 output of shape S as its 64-bit patterns cut into by
 format of plain_bits.npz).
 """
 import os
-import re
-import tempfile
 
 import numpy as np
 import pytest
 
+import bit_pins
 import conftest
+from bit_pins import INPUTS, assert_same_bits, bits
 
 pytestmark = pytest.mark.gpu
 
@@ -53,34 +53,13 @@ def solve(binding, AB, case, seed=None):
     N, n_obs, s = CASES[case]
     p = synth.cfg2_mpccbf(BATCH, N=N, seed=s if seed is None else seed, n_obs=n_obs, safe_start=False)
     d = abi.cbf_desc(N, n_obs, A, B, alpha=p["alpha"], margin=p["margin"])
-    return binding.cbf_solve(d, *[p[k] for k in ("x0", "xt", "obs_s", "obs_ey", "lap_off", "n_obs")])
+    return binding.cbf_solve(d, *[p[k] for k in INPUTS])
 
 
 def oracle_nonzero_dw(orc, AB, case, seed=None):
     """(the oracle's outputs for `case`, the number of its iterations with delta_w != 0), the latter from its per-iteration trace (stderr)."""
-    import oracle
-
-    n_threads = oracle.threads()
-    with tempfile.TemporaryFile() as f:
-        keep = os.dup(2)
-        oracle.set_threads(1)   # one writer: whole lines
-        orc.lib.crx_oracle_set_verbose(1)
-        try:
-            os.dup2(f.fileno(), 2)
-            r = solve(orc, AB, case, seed)
-        finally:
-            os.dup2(keep, 2)
-            os.close(keep)
-            orc.lib.crx_oracle_set_verbose(0)
-            oracle.set_threads(n_threads)
-        f.seek(0)
-        text = f.read().decode()
-    return r, sum(1 for m in re.findall(r"curv \S+ dw (\S+)", text) if float(m) != 0.0)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
+    r, text = bit_pins.oracle_stderr(orc, lambda: solve(orc, AB, case, seed))
+    return r, bit_pins.nonzero_dw(text)
 
 
 def planes(a):
@@ -88,14 +67,14 @@ def planes(a):
     a = np.ascontiguousarray(a)
     if a.dtype != np.float64:
         return a
-    return np.ascontiguousarray(np.moveaxis(a.view(np.uint64)[..., None].view(np.uint8), -1, 0))
+    return bit_pins.planes(a.view(np.uint64))
 
 
 def recorded_bits(z, case, k):
     a = z[case + "/" + k]
     if a.dtype != np.uint8:
         return a
-    return np.ascontiguousarray(np.moveaxis(a, 0, -1)).view(np.uint64)[..., 0]
+    return bit_pins.unplanes(a)
 
 
 @pytest.fixture(scope="module")
@@ -119,8 +98,4 @@ def test_outputs_bit_for_bit(orc, AB, recorded, case):
     names = sorted(k[len(case) + 1:] for k in recorded.files if k.startswith(case + "/"))
     assert sorted(rg) == names
     for k in names:
-        want = recorded_bits(recorded, case, k)
-        got = bits(np.asarray(rg[k]))
-        assert got.dtype == want.dtype and got.shape == want.shape, k
-        diff = np.nonzero(got != want)
-        assert diff[0].size == 0, (case, k, "differs from the recording in %d entries, first at problem %d" % (diff[0].size, diff[0][0]))
+        assert_same_bits(case, k, bits(np.asarray(rg[k])), recorded_bits(recorded, case, k))

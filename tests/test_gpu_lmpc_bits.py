@@ -44,8 +44,10 @@ import os
 import numpy as np
 import pytest
 
+import bit_pins
 import conftest
 import helpers
+from bit_pins import assert_same_bits, bits
 
 pytestmark = pytest.mark.gpu
 
@@ -87,16 +89,6 @@ def solve(binding, case):
     return binding.lmpc_solve(d, x, u_old, A[:, idx], B[:, idx], C[:, idx], ss, qf, np.full(n, M0, np.int32))
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
-def planes(b):
-    """uint64 [*S] -> uint8 [8, *S] (byte i of every value together, so that signs and exponents compress)."""
-    return np.ascontiguousarray(np.moveaxis(np.ascontiguousarray(b)[..., None].view(np.uint8), -1, 0))
-
-
 def xor_base(case, k, of):
     """The pattern XORed into the planes of float64 output `k` of `case`: that of XOR_BASE[case] (of(case, k) -> its uint64 pattern), continued with
     zeros along the last axis to this case's width; None for a case that has no base."""
@@ -112,7 +104,7 @@ def recorded_bits(z, case, k):
     a = z[case + "/" + k]
     if a.dtype != np.uint8:
         return a
-    b = np.ascontiguousarray(np.moveaxis(a, 0, -1)).view(np.uint64)[..., 0]
+    b = bit_pins.unplanes(a)
     base = xor_base(case, k, lambda c, kk: b if c == case else recorded_bits(z, c, kk))
     return b if base is None else b ^ base
 
@@ -137,10 +129,6 @@ def test_lmpc_outputs_bit_for_bit(orc, recorded, case):
         assert ro["status"].size == SUBSET.size == 41 and (tuple(counts), longest, total) == TABLE[case][4:]
     assert sorted(rg) == list(OUTPUTS) == sorted(k[len(case) + 1:] for k in recorded.files if k.startswith(case + "/"))
     for k in OUTPUTS:
-        want = recorded_bits(recorded, case, k)
-        got = bits(np.asarray(rg[k]))
-        assert got.dtype == want.dtype and got.shape == want.shape, k
-        diff = np.nonzero(got != want)
-        assert diff[0].size == 0, (case, k, "differs from the recording in %d entries, first at problem %d" % (diff[0].size, diff[0][0]))
+        assert_same_bits(case, k, bits(np.asarray(rg[k])), recorded_bits(recorded, case, k))
     if case in SAME_STATUS_AS_ORACLE:
         assert np.array_equal(rg["status"], ro["status"]), (case, np.nonzero(rg["status"] != ro["status"])[0])

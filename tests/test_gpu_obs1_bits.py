@@ -4,7 +4,8 @@ Work on these kernels that only moves instructions (which pass loads when, what 
 bit of any output.  tests/golden/obs1_bits.npz holds every output of crx_cbf_solve for the batch below (X, U, sigma, cost, status,
 kkt, iters; N = 12 and N = 10), recorded on an MI355X with the library of the commit BEFORE the row passes were reordered (the
 parent of the commit that added this test).  The recording is compared with == on the bit patterns, and status and iteration
-counts are compared with the oracle's, problem by problem, without exceptions.
+counts are compared with the oracle's, problem by problem, without exceptions.  (The A/B switch of that reordering, CRX_LOADS_FIRST, is
+retired: the reordered passes are the loads-first form of crx_kernels.hip, and this test is the standing pin of that code.)
 
 The batch: synth.cfg2_mpccbf(64, N, seed=161, safe_start=False) -- one obstacle, no scenario filter.  Seeds were searched upwards from 0 for a batch in
 which, by the oracle, BOTH horizons hold every path the kernel has beside the healthy iteration: 67 is the first (its longest solve
@@ -26,21 +27,16 @@ import numpy as np
 import pytest
 
 import conftest
+from bit_pins import INPUTS, OUTPUTS, assert_same_bits, bits
 
 pytestmark = pytest.mark.gpu
 
 SEED = 161
-OUTPUTS = ("X", "U", "sigma", "cost", "status", "kkt", "iters")
 
 
 @pytest.fixture(scope="module")
 def recorded():
     return np.load(os.path.join(conftest.GOLDEN, "obs1_bits.npz"), allow_pickle=False)
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
 
 
 @pytest.mark.parametrize("N", [12, 10])
@@ -52,7 +48,7 @@ def test_obs1_outputs_bit_for_bit(orc, AB, recorded, N):
     A, B = AB
     p = synth.cfg2_mpccbf(64, N=N, seed=SEED, safe_start=False)
     d = abi.cbf_desc(N, 1, A, B, alpha=p["alpha"], margin=p["margin"])
-    args = [p[k] for k in ("x0", "xt", "obs_s", "obs_ey", "lap_off", "n_obs")]
+    args = [p[k] for k in INPUTS]
     rg, ro = gpu.cbf_solve(d, *args), orc.cbf_solve(d, *args)
     assert sorted(rg) == sorted(OUTPUTS)
     # the batch is the one the docstring describes: a restored verdict among converged ones
@@ -60,7 +56,6 @@ def test_obs1_outputs_bit_for_bit(orc, AB, recorded, N):
     for k in OUTPUTS:
         want = recorded["N%d/%s" % (N, k)]
         assert rg[k].dtype == want.dtype and rg[k].shape == want.shape, k
-        diff = np.nonzero(_bits(rg[k]) != _bits(want))
-        assert diff[0].size == 0, (N, k, "differs from the recording in %d entries, first at problem %d" % (diff[0].size, diff[0][0]))
+        assert_same_bits(N, k, bits(rg[k]), bits(want))
     assert np.array_equal(rg["status"], ro["status"]), (N, np.nonzero(rg["status"] != ro["status"])[0])
     assert np.array_equal(rg["iters"], ro["iters"]), (N, np.nonzero(rg["iters"] != ro["iters"])[0])

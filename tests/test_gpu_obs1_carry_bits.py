@@ -1,8 +1,9 @@
 """The tuned one-obstacle NLP kernels after the carry-forward of round 21, bit for bit against a recording of the PARENT commit's library.
 
 Round 21 stops crx_solve_kernel<1,12,6,12> and <1,12,6,10> forming two things twice: first_order at the end of the accept step takes the four
-normalised CBF distances of a lane's row from the accepted line-search trial (DistCarry), and the accept pass takes the multiplier step dnu of every
-row from the row-step pass, through the first rows of Kk (DnuCarry).  Both carry a number that the second place formed from the same operands with
+normalised CBF distances of a lane's row from the accepted line-search trial, and the accept pass takes the multiplier step dnu of every row from
+the row-step pass, through the first rows of Kk.  (The round's A/B switches, CRX_DIST_CARRY and CRX_DNU_CARRY, are retired: both carries are part
+of the lone-wave form of crx_kernels.hip, and this test is the standing pin of that code.)  Both carry a number that the second place formed from the same operands with
 the same roundings, so no output bit may move.  This test pins that, on a batch in which the carried values could be the WRONG ones:
 
   * a step accepted after backtracking -- the carried distances must be the last trial's, not the first's;
@@ -27,52 +28,28 @@ The same inputs then go through the per-problem-model unit (which carries, too) 
 the evaluations: its register file has no room for the carried values); both must give the recording's bits.
 """
 import os
-import re
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
+import bit_pins
 import conftest
+from bit_pins import AGAIN, INPUTS, IT, JAM_ALPHA, JAM_COUNT, OUTPUTS, STEP, bits
 
 pytestmark = pytest.mark.gpu
 
 SEED = 67
 BATCH = 64
-INPUTS = ("x0", "xt", "obs_s", "obs_ey", "lap_off", "n_obs")
-OUTPUTS = ("X", "U", "sigma", "cost", "status", "kkt", "iters")
-JAM_COUNT, JAM_ALPHA = 5, 1e-3   # crx_kernels.hip / crx_oracle.c
-
-_IT = re.compile(r"^it +(\d+) f \S+ ed \S+ ep (\S+) ")
-_STEP = re.compile(r"a_p (\S+) a_d \S+ alpha (\S+) acc (\d) ftype \d theta \S+ Dphi \S+ curv \S+ dw (\S+)")
-_AGAIN = re.compile(r"(RESTART|RESTORE).*\(acc (\d) jam (\d+)\)")
 
 
 def _oracle_trace(orc, d, args):
-    """-> (outputs of the oracle, counts over the batch read from its iteration trace).  One thread: the lines of a problem stay together."""
-    import oracle
-
-    threads = oracle.threads()
-    sys.stderr.flush()
-    keep = os.dup(2)
-    with tempfile.TemporaryFile() as tmp:
-        os.dup2(tmp.fileno(), 2)
-        try:
-            oracle.set_threads(1)
-            orc.lib.crx_oracle_set_verbose(1)
-            out = orc.cbf_solve(d, *args)
-        finally:
-            orc.lib.crx_oracle_set_verbose(0)
-            oracle.set_threads(threads)
-            os.dup2(keep, 2)
-            os.close(keep)
-        tmp.seek(0)
-        lines = tmp.read().decode().splitlines()
+    """-> (outputs of the oracle, counts over the batch read from its iteration trace)"""
+    out, text = bit_pins.oracle_stderr(orc, lambda: orc.cbf_solve(d, *args))
+    lines = text.splitlines()
     n = dict(backtracked=0, restart=0, restore=0, jam_exit=0, jam_rerun=0, inertia=0)
     run, ep, pending = 0, 0.0, False
     for ln in lines:
-        m = _IT.match(ln)
+        m = IT.match(ln)
         if m:   # the next iteration begins: a jam that was followed by neither RESTART nor RESTORE had nothing to restore
             n["jam_rerun"] += pending
             pending = False
@@ -80,25 +57,20 @@ def _oracle_trace(orc, d, args):
                 run = 0
             ep = float(m.group(2))
             continue
-        m = _STEP.search(ln)
+        m = STEP.search(ln)
         if m:
-            a_p, al, acc, dw = float(m.group(1)), float(m.group(2)), int(m.group(3)), float(m.group(4))
+            a_p, al, acc, dw = float(m.group(1)), float(m.group(2)), int(m.group(3)), float(m.group(5))
             n["backtracked"] += bool(acc and al < 0.75 * a_p)     # (the trial lengths halve; a_p is printed with four digits)
             n["inertia"] += dw != 0.0
             run = run + 1 if (acc and al < JAM_ALPHA and ep > d.opts.tol) else 0
             pending = bool(acc and run >= JAM_COUNT)
             continue
-        m = _AGAIN.search(ln)
+        m = AGAIN.search(ln)
         if m:
             pending, run = False, 0
             n["restart" if m.group(1) == "RESTART" else "restore"] += 1
             n["jam_exit"] += int(m.group(2)) == 1               # thrown away although the line search had accepted it
     return out, n
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
 
 
 @pytest.fixture(scope="module")
@@ -114,24 +86,16 @@ def batch(request, AB, recorded):
 
     N = request.param
     p = synth.cfg2_mpccbf(BATCH, N=N, seed=SEED, safe_start=False)
-    args = [np.ascontiguousarray(recorded["N%d/in/%s" % (N, k)]) for k in INPUTS]
+    args = bit_pins.recorded_args(recorded, N)
     for k, a in zip(INPUTS, args):
-        assert a.dtype == np.asarray(p[k]).dtype and np.array_equal(_bits(a), _bits(p[k])), (N, k, "the recorded inputs are not the draw of seed %d" % SEED)
+        assert a.dtype == np.asarray(p[k]).dtype and np.array_equal(bits(a), bits(p[k])), (N, k, "the recorded inputs are not the draw of seed %d" % SEED)
     d = abi.cbf_desc(N, 1, AB[0], AB[1], alpha=p["alpha"], margin=p["margin"])
     return N, crx.init(), d, args
 
 
 def _assert_recorded(N, route, got, recorded):
-    assert sorted(got) == sorted(OUTPUTS)
-    report = []
-    for k in OUTPUTS:
-        want = recorded["N%d/%s" % (N, k)]
-        assert got[k].dtype == want.dtype and got[k].shape == want.shape, (route, k)
-        diff = np.nonzero((_bits(got[k]) != _bits(want)).reshape(BATCH, -1).any(axis=1))[0]
-        print("N = %d, %s, %s: %d problems differ from the recording%s" % (N, route, k, diff.size, "" if diff.size == 0 else ", first %d" % diff[0]))
-        if diff.size:
-            report.append((k, int(diff.size), int(diff[0])))
-    assert not report, (N, route, report)
+    assert all(len(recorded["N%d/%s" % (N, k)]) == BATCH for k in OUTPUTS), (N, "the recording is not of %d problems" % BATCH)
+    bit_pins.assert_recorded(N, route, got, recorded)
 
 
 def test_shared_model_route_and_what_the_batch_holds(batch, orc, recorded):
@@ -150,18 +114,9 @@ def test_shared_model_route_and_what_the_batch_holds(batch, orc, recorded):
 
 def test_per_problem_models_route(batch, AB, recorded):
     N, gpu, d, args = batch
-    models = (np.repeat(AB[0][None], BATCH, axis=0), np.repeat(AB[1][None], BATCH, axis=0))
-    _assert_recorded(N, "per-problem models", gpu.cbf_solve(d, *args, models=models), recorded)
+    _assert_recorded(N, "per-problem models", gpu.cbf_solve(d, *args, models=bit_pins.shipped_models(AB, BATCH)), recorded)
 
 
 def test_two_wave_route_second_wave_idle(batch, recorded):
-    import crx
-
     N, gpu, d, args = batch
-    L = crx.lib()
-    try:
-        L.crx_debug_speculation(2)
-        got = gpu.cbf_solve(d, *args)
-    finally:
-        L.crx_debug_speculation(0)
-    _assert_recorded(N, "two-wave unit, second wave idle", got, recorded)
+    _assert_recorded(N, "two-wave unit, second wave idle", bit_pins.solve_two_wave_idle(gpu, d, args), recorded)

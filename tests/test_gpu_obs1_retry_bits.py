@@ -1,8 +1,9 @@
 """The inertia-correction retries and the accept step of crx_solve_kernel<1,12,6,12> and <1,12,6,10>, bit for bit against a recording.
 
-The accept step takes the CBF row values of the accepted line-search trial instead of evaluating them again (crx_kernels.hip: CRX_CBF_CARRY),
-and work on the retry loop of the inertia correction (one set-up of the backward sweep per Newton system: HISTORY.md, round 9) goes through the
-same paths.  Neither may change one bit of any output.  tests/golden/obs1_retry_bits.npz holds every output of crx_cbf_solve for the batch
+The accept step takes the CBF row values of the accepted line-search trial instead of evaluating them again (crx_kernels.hip, the loads-first
+form), and work on the retry loop of the inertia correction (one set-up of the backward sweep per Newton system: HISTORY.md, round 9) goes through
+the same paths.  Neither may change one bit of any output.  (The A/B switches of the two, CRX_CBF_CARRY and CRX_RETRY_SHARED, are retired; this
+test is the standing pin of that code.)  tests/golden/obs1_retry_bits.npz holds every output of crx_cbf_solve for the batch
 below (X, U, sigma, cost, status, kkt, iters; N = 12 and N = 10), recorded on an MI355X with the library of the commit BEFORE the change (the
 parent of the commit that added this test).  The recording is compared with == on the bit patterns, and status and iteration counts are
 compared with the oracle's, problem by problem, without exceptions.
@@ -31,22 +32,17 @@ import numpy as np
 import pytest
 
 import conftest
+from bit_pins import INPUTS, OUTPUTS, assert_same_bits, bits
 
 pytestmark = pytest.mark.gpu
 
 SEED = 127
 BATCH = 32
-OUTPUTS = ("X", "U", "sigma", "cost", "status", "kkt", "iters")
 
 
 @pytest.fixture(scope="module")
 def recorded():
     return np.load(os.path.join(conftest.GOLDEN, "obs1_retry_bits.npz"), allow_pickle=False)
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
 
 
 @pytest.mark.parametrize("N", [12, 10])
@@ -58,7 +54,7 @@ def test_obs1_retry_outputs_bit_for_bit(orc, AB, recorded, N):
     A, B = AB
     p = synth.cfg2_mpccbf(BATCH, N=N, seed=SEED, safe_start=False)
     d = abi.cbf_desc(N, 1, A, B, alpha=p["alpha"], margin=p["margin"])
-    args = [p[k] for k in ("x0", "xt", "obs_s", "obs_ey", "lap_off", "n_obs")]
+    args = [p[k] for k in INPUTS]
     rg, ro = gpu.cbf_solve(d, *args), orc.cbf_solve(d, *args)
     assert sorted(rg) == sorted(OUTPUTS)
     # the batch is the one the docstring describes
@@ -66,7 +62,6 @@ def test_obs1_retry_outputs_bit_for_bit(orc, AB, recorded, N):
     for k in OUTPUTS:
         want = recorded["N%d/%s" % (N, k)]
         assert rg[k].dtype == want.dtype and rg[k].shape == want.shape, k
-        diff = np.nonzero(_bits(rg[k]) != _bits(want))
-        assert diff[0].size == 0, (N, k, "differs from the recording in %d entries, first at problem %d" % (diff[0].size, diff[0][0]))
+        assert_same_bits(N, k, bits(rg[k]), bits(want))
     assert np.array_equal(rg["status"], ro["status"]), (N, np.nonzero(rg["status"] != ro["status"])[0])
     assert np.array_equal(rg["iters"], ro["iters"]), (N, np.nonzero(rg["iters"] != ro["iters"])[0])

@@ -19,16 +19,13 @@ two-wave kernel now hands the compiler an opaque lane index that is known to be 
 import numpy as np
 import pytest
 
+import bit_pins
+from bit_pins import INPUTS, OUTPUTS, bits
+
 pytestmark = pytest.mark.gpu
 
 SEED = 127
 BATCH = 32
-OUTPUTS = ("X", "U", "sigma", "cost", "status", "kkt", "iters")
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
 
 
 @pytest.fixture(scope="module", params=[12, 10])
@@ -42,7 +39,7 @@ def routes(request, AB):
     A, B = AB
     p = synth.cfg2_mpccbf(BATCH, N=N, seed=SEED, safe_start=False)
     d = abi.cbf_desc(N, 1, A, B, alpha=p["alpha"], margin=p["margin"])
-    args = [p[k] for k in ("x0", "xt", "obs_s", "obs_ey", "lap_off", "n_obs")]
+    args = [p[k] for k in INPUTS]
     shared = gpu.cbf_solve(d, *args)
     assert sorted(shared) == sorted(OUTPUTS)
     assert int(shared["iters"].max()) == {12: 51, 10: 37}[N]   # the batch of the recording
@@ -53,7 +50,7 @@ def _assert_same(N, route, got, shared):
     report = []
     for k in OUTPUTS:
         assert got[k].dtype == shared[k].dtype and got[k].shape == shared[k].shape, (route, k)
-        diff = np.nonzero(_bits(got[k]) != _bits(shared[k]))[0]
+        diff = np.nonzero(bits(got[k]) != bits(shared[k]))[0]
         worst = float(np.abs(got[k].astype(np.float64) - shared[k].astype(np.float64)).max()) if diff.size else 0.0
         print("N = %d, %s, %s: %d entries differ%s" % (N, route, k, diff.size, "" if diff.size == 0 else ", first at problem %d, largest |difference| %.3e" % (diff[0], worst)))
         if diff.size:
@@ -63,18 +60,9 @@ def _assert_same(N, route, got, shared):
 
 def test_per_problem_models_route(routes, AB):
     N, gpu, d, args, shared = routes
-    models = (np.repeat(AB[0][None], BATCH, axis=0), np.repeat(AB[1][None], BATCH, axis=0))
-    _assert_same(N, "per-problem models", gpu.cbf_solve(d, *args, models=models), shared)
+    _assert_same(N, "per-problem models", gpu.cbf_solve(d, *args, models=bit_pins.shipped_models(AB, BATCH)), shared)
 
 
 def test_two_wave_route_second_wave_idle(routes):
-    import crx
-
     N, gpu, d, args, shared = routes
-    L = crx.lib()
-    try:
-        L.crx_debug_speculation(2)
-        got = gpu.cbf_solve(d, *args)
-    finally:
-        L.crx_debug_speculation(0)
-    _assert_same(N, "two-wave unit, second wave idle", got, shared)
+    _assert_same(N, "two-wave unit, second wave idle", bit_pins.solve_two_wave_idle(gpu, d, args), shared)

@@ -31,13 +31,13 @@ The planner cases also require the kernel's status to be the oracle's, QP by QP.
 are where kernel and oracle may part by an iteration, and the recording is what pins the kernel there.
 """
 import os
-import re
-import tempfile
 
 import numpy as np
 import pytest
 
+import bit_pins
 import conftest
+from bit_pins import INPUTS, assert_same_bits, bits
 
 pytestmark = pytest.mark.gpu
 
@@ -61,35 +61,13 @@ def solve(binding, AB, case):
     else:
         p = synth.cfg2_mpccbf(32, N=11, seed=47, safe_start=False)
         d = abi.cbf_desc(11, 1, A, B, alpha=p["alpha"], margin=p["margin"])
-    return binding.cbf_solve(d, *[p[k] for k in ("x0", "xt", "obs_s", "obs_ey", "lap_off", "n_obs")])
+    return binding.cbf_solve(d, *[p[k] for k in INPUTS])
 
 
 def oracle_verbose(orc, AB, case):
     """The oracle's outputs for `case` with what its per-iteration trace (stderr) says: (outputs, restarts, iterations with delta_w != 0)."""
-    import oracle
-
-    n_threads = oracle.threads()
-    with tempfile.TemporaryFile() as f:
-        keep = os.dup(2)
-        oracle.set_threads(1)   # one writer: whole lines
-        orc.lib.crx_oracle_set_verbose(1)
-        try:
-            os.dup2(f.fileno(), 2)
-            r = solve(orc, AB, case)
-        finally:
-            os.dup2(keep, 2)
-            os.close(keep)
-            orc.lib.crx_oracle_set_verbose(0)
-            oracle.set_threads(n_threads)
-        f.seek(0)
-        text = f.read().decode()
-    dw = [float(m) for m in re.findall(r"curv \S+ dw (\S+)", text)]
-    return r, text.count("RESTART"), sum(1 for v in dw if v != 0.0)
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
+    r, text = bit_pins.oracle_stderr(orc, lambda: solve(orc, AB, case))
+    return r, text.count("RESTART"), bit_pins.nonzero_dw(text)
 
 
 def recorded_bits(z, case, k):
@@ -97,7 +75,7 @@ def recorded_bits(z, case, k):
     a = z[case + "/" + k]
     if a.dtype != np.uint8:
         return a
-    b = np.ascontiguousarray(np.moveaxis(a, 0, -1)).view(np.uint64)[..., 0]
+    b = bit_pins.unplanes(a)
     return b ^ recorded_bits(z, case.replace("q1", "q0"), k) if case.endswith("q1") else b
 
 
@@ -127,10 +105,6 @@ def test_plain_outputs_bit_for_bit(orc, AB, recorded, case):
     names = sorted(k[len(case) + 1:] for k in recorded.files if k.startswith(case + "/"))
     assert sorted(rg) == names
     for k in names:
-        want = recorded_bits(recorded, case, k)
-        got = bits(np.asarray(rg[k]))
-        assert got.dtype == want.dtype and got.shape == want.shape, k
-        diff = np.nonzero(got != want)
-        assert diff[0].size == 0, (case, k, "differs from the recording in %d entries, first at problem %d" % (diff[0].size, diff[0][0]))
+        assert_same_bits(case, k, bits(np.asarray(rg[k])), recorded_bits(recorded, case, k))
     if case.startswith("plan"):
         assert np.array_equal(rg["status"], ro["status"]), (case, np.nonzero(rg["status"] != ro["status"])[0])

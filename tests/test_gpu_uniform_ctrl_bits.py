@@ -1,5 +1,6 @@
-"""The tuned one-obstacle NLP kernels with their line-search decisions taken as scalar branches (round 22, CRX_UNIFORM_CTRL), bit for bit against
-a recording of the PARENT commit's library.
+"""The tuned one-obstacle NLP kernels with their line-search decisions taken as scalar branches (round 22), bit for bit against a recording of the
+PARENT commit's library.  The round's A/B switch, CRX_UNIFORM_CTRL, is retired: the scalar branches are part of the lone-wave form of
+crx_kernels.hip, and this test is the standing pin of that code.
 
 crx_solve_kernel<1,12,6,12> and <1,12,6,10> pass the conditions of the backtracking loop -- the trial loop's alpha >= alpha_min, theta_max / NaN,
 the filter verdict, the switching condition, Armijo, sufficient decrease -- through wave_uniform (crx_wave.h): where a value lives changes, no
@@ -21,21 +22,14 @@ tests run the recorded inputs through the shared-model and the per-problem-model
 iterations, KKT error and every trajectory array bit for bit.
 """
 import os
-import re
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
+import bit_pins
 import conftest
+from bit_pins import AGAIN, BATCH, HORIZONS, INPUTS, IT, JAM_ALPHA, JAM_COUNT, STEP, bits, descriptor, draw, recorded_args
 
-HORIZONS = (12, 10)
-DRAW = 64    # problems per synth draw
-BATCH = 64   # problems per horizon in the fixture, at most
-INPUTS = ("x0", "xt", "obs_s", "obs_ey", "lap_off", "n_obs")
-OUTPUTS = ("X", "U", "sigma", "cost", "status", "kkt", "iters")
-JAM_COUNT, JAM_ALPHA = 5, 1e-3   # crx_kernels.hip / crx_oracle.c
 # what the oracle's trace proves of one problem
 PATHS = ("backtracked",        # a step accepted behind at least one refused trial (ls >= 1)
          "armijo",             # accepted by the Armijo test under the switching condition (ftype = 1)
@@ -49,44 +43,6 @@ PATHS = ("backtracked",        # a step accepted behind at least one refused tri
 UNVERIFIED = {"filter_reject": "a trial refused by a filter entry (proxy: trials refused while the filter is not empty)",
               "sigma0_pivot": "a sigma_0 pivot that fails behind a clean sweep (proxy: corrected iterations; the oracle factorises densely)"}
 
-_IT = re.compile(r"^it +(\d+) f \S+ ed \S+ ep (\S+) ec \S+ mu (\S+) dw (\S+) nf (\d+)")
-_STEP = re.compile(r"a_p (\S+) a_d \S+ alpha (\S+) acc (\d) ftype (\d) theta \S+ Dphi \S+ curv \S+ dw (\S+)")
-_AGAIN = re.compile(r"(RESTART|RESTORE).*\(acc (\d) jam (\d+)\)")
-
-
-def draw(N, seed):
-    from crx import synth
-
-    return synth.cfg2_mpccbf(DRAW, N=N, seed=int(seed), safe_start=False)
-
-
-def descriptor(N, AB, p):
-    from crx import abi
-
-    return abi.cbf_desc(N, 1, AB[0], AB[1], alpha=p["alpha"], margin=p["margin"])
-
-
-def oracle_trace(orc, d, args):
-    """-> (outputs of the oracle, the lines of its iteration trace).  One thread: the lines of a problem stay together."""
-    import oracle
-
-    threads = oracle.threads()
-    sys.stderr.flush()
-    keep = os.dup(2)
-    with tempfile.TemporaryFile() as tmp:
-        os.dup2(tmp.fileno(), 2)
-        try:
-            oracle.set_threads(1)
-            orc.lib.crx_oracle_set_verbose(1)
-            out = orc.cbf_solve(d, *args)
-        finally:
-            orc.lib.crx_oracle_set_verbose(0)
-            oracle.set_threads(threads)
-            os.dup2(keep, 2)
-            os.close(keep)
-        tmp.seek(0)
-        return out, tmp.read().decode().splitlines()
-
 
 def paths_of(lines, opts):
     """-> {path or proxy: count} of ONE problem's trace.  The `it` line of iteration k prints mu, dw_last and the filter size as the iteration
@@ -98,15 +54,15 @@ def paths_of(lines, opts):
 
     its = []   # per iteration: [ep, mu, dw_last, nf, step or None]
     for ln in lines:
-        m = _IT.match(ln)
+        m = IT.match(ln)
         if m:
             its.append([float(m.group(2)), float(m.group(3)), float(m.group(4)), int(m.group(5)), None, None])
             continue
-        m = _STEP.search(ln)
+        m = STEP.search(ln)
         if m and its:
             its[-1][4] = (float(m.group(1)), float(m.group(2)), int(m.group(3)), int(m.group(4)), float(m.group(5)))
             continue
-        m = _AGAIN.search(ln)
+        m = AGAIN.search(ln)
         if m and its:
             its[-1][5] = (m.group(1), int(m.group(2)))
     run = 0
@@ -140,31 +96,16 @@ def paths_of(lines, opts):
 
 
 def batch_paths(orc, d, args):
-    """-> (oracle outputs per problem, stacked; list of paths_of() per problem): the problems solved ONE AT A TIME, so that a trace is one problem's"""
-    outs, per = [], []
-    for b in range(len(args[0])):
-        out, lines = oracle_trace(orc, d, [np.ascontiguousarray(a[b:b + 1]) for a in args])
-        outs.append(out)
-        per.append(paths_of(lines, d.opts))
-    return {k: np.concatenate([o[k] for o in outs]) for k in outs[0]}, per
+    return bit_pins.batch_paths(orc, d, args, lambda lines, b: paths_of(lines, d.opts))
 
 
 def totals(per):
     return {k: int(sum(p[k] for p in per)) for k in PATHS + tuple(UNVERIFIED)}
 
 
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint64) if a.dtype == np.float64 else a
-
-
 @pytest.fixture(scope="module")
 def recorded():
     return np.load(os.path.join(conftest.GOLDEN, "uniform_ctrl_bits.npz"), allow_pickle=False)
-
-
-def recorded_args(recorded, N):
-    return [np.ascontiguousarray(recorded["N%d/in/%s" % (N, k)]) for k in INPUTS]
 
 
 @pytest.mark.parametrize("N", HORIZONS)
@@ -189,19 +130,6 @@ def test_fixture_holds_every_path(N, AB, orc, recorded):
     assert np.array_equal(recorded["N%d/iters" % N], ro["iters"]), (N, np.nonzero(recorded["N%d/iters" % N] != ro["iters"])[0])
 
 
-def _assert_recorded(N, route, got, recorded):
-    assert sorted(got) == sorted(OUTPUTS)
-    report = []
-    for k in OUTPUTS:
-        want = recorded["N%d/%s" % (N, k)]
-        assert got[k].dtype == want.dtype and got[k].shape == want.shape, (route, k)
-        diff = np.nonzero((bits(got[k]) != bits(want)).reshape(len(want), -1).any(axis=1))[0]
-        print("N = %d, %s, %s: %d problems differ from the recording%s" % (N, route, k, diff.size, "" if diff.size == 0 else ", first %d" % diff[0]))
-        if diff.size:
-            report.append((k, int(diff.size), int(diff[0])))
-    assert not report, (N, route, report)
-
-
 @pytest.fixture(scope="module", params=HORIZONS)
 def batch(request, AB, recorded):
     import crx
@@ -212,23 +140,11 @@ def batch(request, AB, recorded):
     return N, crx.init(), d, args
 
 
-def _solve(gpu, d, args, AB, models, perm):
-    """the batch through one entry; perm: problem i of the launch is problem perm[i] of the batch, the outputs are put back in batch order"""
-    n = len(args[0])
-    a = args if perm is None else [np.ascontiguousarray(x[perm]) for x in args]
-    kw = dict(models=(np.repeat(AB[0][None], n, axis=0), np.repeat(AB[1][None], n, axis=0))) if models else {}
-    got = gpu.cbf_solve(d, *a, **kw)
-    if perm is not None:
-        inv = np.argsort(perm)
-        got = {k: np.ascontiguousarray(v[inv]) for k, v in got.items()}
-    return got
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("order", ["index order", "permuted"])
 @pytest.mark.parametrize("models", [False, True], ids=["shared model", "per-problem models"])
 def test_bits_are_the_parents(batch, AB, recorded, models, order):
     N, gpu, d, args = batch
     perm = None if order == "index order" else np.random.default_rng(22).permutation(len(args[0]))
-    got = _solve(gpu, d, args, AB, models, perm)
-    _assert_recorded(N, "%s, %s" % ("per-problem models" if models else "shared model", order), got, recorded)
+    got = bit_pins.solve(gpu, d, args, AB, models, perm)
+    bit_pins.assert_recorded(N, "%s, %s" % ("per-problem models" if models else "shared model", order), got, recorded)

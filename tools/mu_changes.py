@@ -11,7 +11,7 @@ sys.path[:0] = [ROOT, ROOT + "/car-racing_amd", ROOT + "/tests"]
 import numpy as np
 from crx import abi, synth
 import oracle
-import test_gpu_uniform_ctrl_bits as U
+import bit_pins as U   # the oracle's trace and its line formats
 
 KEYS = ("x0", "xt", "obs_s", "obs_ey", "lap_off", "n_obs")
 A, B = synth.load_AB()
@@ -34,9 +34,9 @@ for b in range(256):
     out, lines = U.oracle_trace(orc, d, [np.ascontiguousarray(p[k][b:b + 1]) for k in KEYS])
     found, again = [], []
     for ln in lines:
-        m = U._IT.match(ln)
+        m = U.IT.match(ln)
         if m: found.append(float(m.group(3))); again.append(False); continue
-        if U._AGAIN.search(ln) and again: again[-1] = True
+        if U.AGAIN.search(ln) and again: again[-1] = True
     # the mu iteration k solved with is the one iteration k + 1 finds (printed with two digits; a cut is a factor of 5 at least above the floor);
     # behind a restart / restoration, and for the last iteration, the trace does not show it: those iterations are left out
     mus = [found[k + 1] for k in range(len(found) - 1) if not again[k]]

@@ -26,9 +26,9 @@ FENCE_UNITS="crx_kernels_plan.hip crx_kernels_obs.hip crx_kernels_spec.hip crx_k
 FENCE_UNITS="$FENCE_UNITS crx_kernels_models_gen.hip crx_lmpc.hip crx_lmpcprep.hip crx_path.hip crx_pathplan.hip crx_ilqr.hip crx_lqr.hip crx_sysid.hip crx_debug_wave.hip"
 bash tools/build_variant.sh fenceonly "-DCRX_SYNC_FENCE_ONLY" $FENCE_UNITS > /dev/null &
 bash tools/build_variant.sh opaqueall "-DCRX_OPAQUE_LANE=2" crx_kernels_obs.hip > /dev/null &
-# (nodpp goes with the shared retry set-up off: riccati_backward<.., SHARED> is written for the register-resident (P | p), which needs the DPP form --
-# since round 12 the variant stopped at that static_assert and left no library)
-bash tools/build_variant.sh nodpp "-DCRX_ROWDPP=0 -DCRX_RETRY_SHARED=0" crx_kernels_plan.hip crx_kernels_obs.hip > /dev/null &
+# (nodpp runs the lone-wave kernels' inertia retries outside the sweep function: riccati_backward<.., SHARED> is written for the register-resident
+# (P | p), which needs the DPP form, and crx_solve_kernel takes it only where ROWDPP holds)
+bash tools/build_variant.sh nodpp "-DCRX_ROWDPP=0" crx_kernels_plan.hip crx_kernels_obs.hip > /dev/null &
 wait
 ls -la tools/ab/*.so
 # every library of the list must be whole: it loads (needs no GPU) -- a variant that lacks a unit of the link line fails here with an undefined symbol
